@@ -16,6 +16,10 @@ N > 1: every rank runs the C3 workload on its own point set (the batch axis is t
 single point set cannot be split without a distributed FFT), no data-path collective, "scaling": "weak"; plus the
 C4 leg sharded for real: `torch_nfft_amd.distributed` over B = 4 N point sets x 64 columns (B = 32 at N = 8, the
 configuration C4 names) with the RCCL all-gather of the per-rank spectra.
+
+`--dump-outputs DIR` writes what the last timed step of the headline handed back to its caller (rank 0's): the adjoint's
+spectrum as DIR/adjoint.npy and the forward's real output as DIR/forward.npy, float32, complex values as (re, im) pairs.
+The inputs come from fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -45,6 +49,8 @@ INTERP_TRAFFIC = {"bytes": int((8.532e5 * 2 + 3.205e5) * 1024),
 TRAFFIC_SOURCE = ("profiles/%s: rocprofv3 --pmc FETCH_SIZE (x2, the gfx950 correction) and WRITE_SIZE passes of this command, "
                   "taken by the builder (scripts/profile_round.sh) and replayed here while the kernel's name, the workload and "
                   "the hash of the kernel's source files still match; null otherwise -- not measured by this run" % TRAFFIC_RECORD)
+DUMP_BYTES = 60_000_000        # payload of --dump-outputs in all (the .npy headers stay well inside 64 MB)
+DUMP_SEED = 20241              # positions of the sampled elements of an output too large to dump whole
 
 
 def parse():
@@ -64,7 +70,51 @@ def parse():
     ap.add_argument("--legs", default="c1,c2,c3clustered,c4share,c5,r1,r2,r3", help="comma-separated legs to run at N=1")
     ap.add_argument("--leg-reps", type=int, default=11, help="individually timed steps per leg (median reported)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed headline step to DIR/<name>.npy (float32, at most %d bytes "
+                         "in all; an output too large for its share is replaced by a fixed, seeded sample of its "
+                         "elements)" % DUMP_BYTES)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+def dump_outputs(dirname, outputs, budget=None):
+    """Write each (name, tensor) of `outputs` as <dirname>/<name>.npy in float32 (float64 stays float64; complex values
+    become a trailing (re, im) axis).  The outputs share `budget` bytes of payload in the order given: an output larger
+    than what is left is replaced by a sample of its elements, flattened, at positions drawn without replacement from a
+    generator with a fixed seed and sorted -- the same positions in every run with the same output shapes."""
+    import numpy as np
+    import torch
+    left = DUMP_BYTES if budget is None else budget
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for name, t in outputs:
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+            per_elem = 2
+        else:
+            per_elem = 1
+        if t.dtype != torch.float64:
+            t = t.float()
+        elem_bytes = per_elem * t.element_size()
+        numel = t.numel() // per_elem
+        if numel * elem_bytes <= left:
+            a = t.cpu().numpy()
+        else:
+            k = left // elem_bytes
+            rng = np.random.default_rng(DUMP_SEED)
+            idx = np.sort(rng.choice(numel, size=k, replace=False))
+            flat = t.reshape(numel, per_elem) if per_elem > 1 else t.reshape(numel)
+            a = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+        left -= a.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = list(a.shape)
+    return written
 
 
 def self_launch(args):
@@ -227,7 +277,7 @@ def main():
         if fresh_plan:
             ops.plan_cache_clear()
         y = tn.nfft_adjoint(x, pos, None, bandwidth=N, cutoff=m)
-        return tn.nfft_forward(y, pos, None, cutoff=m, real_output=True)
+        return y, tn.nfft_forward(y, pos, None, cutoff=m, real_output=True)
 
     for _ in range(args.warmup):
         step()
@@ -238,11 +288,16 @@ def main():
     _lib.profile_enable(True, stages=("spread",))
     _lib.profile_collect()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()  # (kept for --dump-outputs; every earlier step's outputs are dropped as they were)
     barrier()
     elapsed = time.perf_counter() - t0
     spread_live = _lib.profile_collect()["spread"]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, [("forward", last[1]), ("adjoint", last[0])])
+    del last
     _lib.profile_enable(True)
     for _ in range(args.steps):
         step()
@@ -535,6 +590,8 @@ def main():
             "value_with_plan_kept_across_steps": n_gpus * n / (cached_ms * 1e-3) / 1e6,
             "configs": legs,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         if not args.no_cpu_baseline and not distributed:
             out["cpu_baseline"] = cpu_baseline(d, N, args.cpu_seconds)
         json_out.write(json.dumps(out) + "\n")
