@@ -509,13 +509,11 @@ print("RESULT", tuple(y.shape), bool(torch.isfinite(y.abs()).all()))
 
 
 @pytest.mark.parametrize("env_extra", [{"NFFT_HIP_SPREAD": "lds"},
-                                       {"NFFT_HIP_GATHER": "lds", "NFFT_HIP_ROCFFT_ROWS": "1"},
-                                       {"NFFT_HIP_COL_XCD": "0"}])
+                                       {"NFFT_HIP_GATHER": "lds"}])
 def test_fallback_kernels_match_oracle(env_extra):
     """The kernels the defaults replaced stay selectable and correct: NFFT_HIP_SPREAD=lds (f64-LDS-atomic spreading,
-    narrow pencil tiling), NFFT_HIP_GATHER=lds (lane-per-point interpolation on the wide tiling),
-    NFFT_HIP_ROCFFT_ROWS=1 (rocFFT instead of the own row passes) and NFFT_HIP_COL_XCD=0 (column passes in plain
-    workgroup order) on a 128^3 grid: adjoint and forward vs the oracle."""
+    narrow pencil tiling) and NFFT_HIP_GATHER=lds (lane-per-point interpolation on the wide tiling) on a 128^3 grid:
+    adjoint and forward vs the oracle."""
     import subprocess
     import sys
     code = r'''
@@ -544,13 +542,12 @@ print("RESULT", e1, e2)
     assert float(line[1]) < T1 and float(line[2]) < T1
 
 
-@pytest.mark.parametrize("env_extra", [{}, {"NFFT_HIP_SMALL_NARROW": "0"}, {"NFFT_HIP_OWNED_PAIR": "0"}, {"NFFT_HIP_COLFFT_2D": "0"}],
-                         ids=["defaults", "wide-64^3", "unpaired-owned", "rocfft-2d"])
+@pytest.mark.parametrize("env_extra", [{}, {"NFFT_HIP_SMALL_NARROW": "0"}], ids=["defaults", "wide-64^3"])
 def test_round4_selection_switches_match_oracle(env_extra):
-    """What round 4 made the default, and the path each switch brings back, against the oracle: the 64^3 grid (N = 32) with a
+    """What round 4 made the default, and the path its switch brings back, against the oracle: the 64^3 grid (N = 32) with a
     narrow window (narrow tiling by default / NFFT_HIP_SMALL_NARROW=0: the matrix-core kernels on 3 x 2 pencils), a sparse
-    128^3 problem with three columns (paired owner-computes spreading / NFFT_HIP_OWNED_PAIR=0: one sweep per column), a 2-D
-    256^2 grid with two point sets (own row + column passes / NFFT_HIP_COLFFT_2D=0: rocFFT + the roll-off kernel)."""
+    128^3 problem with three columns (paired owner-computes spreading), a 2-D 256^2 grid with two point sets (own row +
+    column passes)."""
     import subprocess
     import sys
     code = r'''
@@ -862,15 +859,16 @@ def test_forward_many_columns_wave_per_column(tn, monkeypatch, C, complex_out, c
     assert rel_l2(y, ref) < 2e-6
 
 
-@pytest.mark.parametrize("env_extra", [{"NFFT_HIP_STREAM_MIN": "1"}, {"NFFT_HIP_STREAM_MIN": "1", "NFFT_HIP_COLGROUPS": "0"},
-                                       {"NFFT_HIP_XGATHER": "1"}],
+@pytest.mark.parametrize("env_extra,columns", [({"NFFT_HIP_STREAM_MIN": "1"}, 2),
+                                               ({"NFFT_HIP_STREAM_MIN": "1", "NFFT_HIP_COLGROUPS": "0"}, 2), ({}, 3)],
                          ids=["stream+groups", "stream-nogroups", "separate-permutation"])
-def test_streamed_gather_and_column_groups_on_small_problems(env_extra):
+def test_streamed_gather_and_column_groups_on_small_problems(env_extra, columns):
     """The streamed gather and the column-group order of the plan are chosen for big work items only; with
     NFFT_HIP_STREAM_MIN=1 they run on problems the oracle can check.  Every cutoff of the wide tiling (chunks of 13 ... 1
     slabs, windows of 4 ... 16 taps), grids whose last pencil is partial, points on pencil and group boundaries, a dense
-    cluster (cut pieces), empty regions, two point sets: adjoint and forward vs the float64 oracle.  The third case
-    runs the coefficient permutation as a pass of its own (the default does it inside the spreading kernel)."""
+    cluster (cut pieces), empty regions, two point sets: adjoint and forward vs the float64 oracle.  The third case has
+    three coefficient columns, which permute the coefficients in a pass of their own (one or two are read inside the
+    spreading kernel)."""
     import subprocess
     import sys
     code = r'''
@@ -898,7 +896,7 @@ for case, (N, m, n, nsets) in enumerate([(32, 1, 3000, 1), (32, 2, 3000, 1), (64
     if nsets == 2:
         batch = (np.arange(n) >= n // 3).astype(np.int64)
         bt = torch.from_numpy(batch).cuda()
-    x = rng.standard_normal((n, 2)).astype(np.float32)
+    x = rng.standard_normal((n, %d)).astype(np.float32)
     xt, pt = torch.from_numpy(x).cuda(), torch.from_numpy(pos).cuda()
     y = tn.nfft_adjoint(xt, pt, bt, bandwidth=N, cutoff=m)
     ref = nfft_ref.nfft_adjoint(x, pos, batch, N=N, m=m)
@@ -909,7 +907,7 @@ for case, (N, m, n, nsets) in enumerate([(32, 1, 3000, 1), (32, 2, 3000, 1), (64
     print("CASE", N, m, n, nsets, e1, e2)
     worst = max(worst, e1, e2)
 print("RESULT", worst)
-''' % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+''' % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), columns)
     env = dict(os.environ, **env_extra)
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:] + out.stdout[-2000:]

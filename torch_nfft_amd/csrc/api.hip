@@ -201,94 +201,70 @@ static int take_pending_fault()
     return 0;
 }
 
-SpreadMode spread_mode()
+// ---- environment switches ------------------------------------------------------------------------------------------
+// Every NFFT_HIP_* variable the library reads (INTEGRATION.md lists them).  All but two are read together, once per
+// process; NFFT_HIP_CHUNK_BYTES and NFFT_HIP_NO_COLFFT are read on every call (tests change them between calls).
+namespace {
+const char *env(const char *name)
 {
-    static const SpreadMode mode = [] {
-        const char *env = std::getenv("NFFT_HIP_SPREAD");
-        if (env && env[0] == 'r') return kSpreadReg;
-        if (env && env[0] == 'l') return kSpreadLds;
-        return kSpreadMfma;
-    }();
-    return mode;
+    const char *v = std::getenv(name);
+    return v ? v : "";
 }
-
-bool column_groups_enabled()
+struct Switches {
+    SpreadMode spread;    // NFFT_HIP_SPREAD=reg|lds: register-tile / LDS-atomic spreading instead of the matrix cores
+    char gather;          // NFFT_HIP_GATHER=lds|mfma: 'l' lane-per-point gather only, 'm' never the wave-per-column or
+                          // streamed kernels; 0 by default
+    int owned;            // NFFT_HIP_OWNED=0|1: never / always the owner-computes plan; -1: by point density
+    bool work_list;       // NFFT_HIP_WORK_LIST=1: every wide plan runs from its work list
+    bool colgroups;       // NFFT_HIP_COLGROUPS=0: plans without the column-group order
+    bool small_grid;      // NFFT_HIP_SMALL_GRID=0: no one-kernel path for small grids
+    bool small_narrow;    // NFFT_HIP_SMALL_NARROW=0: the 64^3 grid keeps the wide tiling
+    int stream_min;       // NFFT_HIP_STREAM_MIN (tuning): smallest streamed work item in points; 3000
+    double items_per_cu;  // NFFT_HIP_ITEMS_PER_CU (tuning): work items per CU of a pencil's slab ranges; 5.4
+};
+const Switches &switches()
 {
-    static const bool on = [] {
-        const char *env = std::getenv("NFFT_HIP_COLGROUPS");
-        return !(env && env[0] == '0');
+    static const Switches s = [] {
+        Switches w;
+        const char *v = env("NFFT_HIP_SPREAD");
+        w.spread = v[0] == 'r' ? kSpreadReg : v[0] == 'l' ? kSpreadLds : kSpreadMfma;
+        v = env("NFFT_HIP_GATHER");
+        w.gather = (v[0] == 'l' || v[0] == 'm') ? v[0] : 0;
+        v = env("NFFT_HIP_OWNED");
+        w.owned = v[0] == '0' ? 0 : v[0] == '1' ? 1 : -1;
+        w.work_list = env("NFFT_HIP_WORK_LIST")[0] == '1';
+        w.colgroups = env("NFFT_HIP_COLGROUPS")[0] != '0';
+        w.small_grid = env("NFFT_HIP_SMALL_GRID")[0] != '0';
+        w.small_narrow = env("NFFT_HIP_SMALL_NARROW")[0] != '0';
+        const int sm = std::atoi(env("NFFT_HIP_STREAM_MIN"));
+        w.stream_min = sm > 0 ? sm : 3000;
+        const double ipc = std::atof(env("NFFT_HIP_ITEMS_PER_CU"));
+        w.items_per_cu = ipc >= 1.0 && ipc <= 64.0 ? ipc : 5.4;
+        return w;
     }();
-    return on;
+    return s;
 }
-
-// NFFT_HIP_WORK_LIST=1: every wide plan is run from its work list (the persistent launch), balanced or not -- for tests
-// and for timing the two forms of the matrix-core kernels against each other
-bool work_list_forced()
+// upper bound for (real grid + half spectrum) of one chunk of planes; the rest of the 288 GB stays free for the caller
+int64_t chunk_budget_bytes()
 {
-    static const bool on = [] {
-        const char *env = std::getenv("NFFT_HIP_WORK_LIST");
-        return env && env[0] == '1';
-    }();
-    return on;
+    const long long v = std::atoll(env("NFFT_HIP_CHUNK_BYTES"));
+    return v > 0 ? (int64_t)v : int64_t(16) << 30;
 }
+bool colfft_enabled() { return env("NFFT_HIP_NO_COLFFT")[0] != '1'; }
+} // namespace
 
-double items_per_cu()
-{
-    static const double v = [] {
-        const char *env = std::getenv("NFFT_HIP_ITEMS_PER_CU");
-        const double t = env ? std::atof(env) : 0.0;
-        return t >= 1.0 && t <= 64.0 ? t : 5.4;
-    }();
-    return v;
-}
+SpreadMode spread_mode() { return switches().spread; }
+bool column_groups_enabled() { return switches().colgroups; }
+bool work_list_forced() { return switches().work_list; }
+double items_per_cu() { return switches().items_per_cu; }
+int stream_min_item_points() { return switches().stream_min; }
+int owned_override() { return switches().owned; }
 
-int stream_min_item_points()
-{
-    static const int v = [] {
-        const char *env = std::getenv("NFFT_HIP_STREAM_MIN");
-        const int t = env ? std::atoi(env) : 0;
-        return t > 0 ? t : 3000;
-    }();
-    return v;
-}
-
-// NFFT_HIP_OWNED_PAIR=0: owned plans keep the 32 x 64 tiles and the one-column sweeps for every column count
-bool owned_pair_enabled()
-{
-    static const bool on = [] {
-        const char *env = std::getenv("NFFT_HIP_OWNED_PAIR");
-        return !(env && env[0] == '0');
-    }();
-    return on;
-}
-
-int owned_override()
-{
-    static const int v = [] {
-        const char *env = std::getenv("NFFT_HIP_OWNED");
-        if (env && env[0] == '0') return 0;
-        if (env && env[0] == '1') return 1;
-        return -1;
-    }();
-    return v;
-}
-
+// ---- the route of a call -------------------------------------------------------------------------------------------
+// Which kernels a call runs is decided here and nowhere else: the kernel files' *_supported functions only say whether
+// a kernel can run a geometry.  Every entry point builds a Route and reads nothing else.
 namespace {
 
-// The point plan of a problem: the tile-sorted points (pencils with halo: what the interpolation kernels and the
-// scatter spreading kernels walk) and, for sparse 3-D problems, a second sort by owned 32 x 64 tiles with an entry
-// per touched tile for the owner-computes spreading kernel (common.h choose_owned), stored behind the first.
-struct PlanSet {
-    Geom g;
-    PlanLayout L;
-    bool owned;
-    Geom go;
-    PlanLayout Lo;
-    int64_t off_own, total;
-    const Geom &spread_geom() const { return owned ? go : g; }
-    const PlanLayout &spread_layout() const { return owned ? Lo : L; }
-    const void *spread_plan(const void *plan) const { return owned ? (const char *)plan + off_own : (const char *)plan; }
-};
 // Geometry of a problem's (halo-tiling) plan.  The column-group order of the plan (common.h Geom::CG) pays where the
 // streamed gather runs, i.e. for big work items; below that it only costs sorting time (+0.03 ms at 10^6 points).
 // The 64^3 grid (N = 32, the reference's default bandwidth: torch_nfft/nfft.py:150-156) is 3 x 2 pencils of the wide tiling,
@@ -296,14 +272,9 @@ struct PlanSet {
 // per range) cannot spread a dense point set over 256 CUs -- 10^6 points, m = 3: 1.46 ms per adjoint + forward against 0.51
 // with the narrow tiling, whose LDS kernels share a (pencil, segment) among up to 32 workgroups.  What the narrow path pays is
 // one LDS atomic per window tap: it wins for the narrow windows and for few points (sweep: profiles/r04_experiments.md).
-// NFFT_HIP_SMALL_NARROW=0 keeps the wide tiling.
 bool prefer_narrow(const nfft_hip_problem *p)
 {
-    static const bool off = [] {
-        const char *env = std::getenv("NFFT_HIP_SMALL_NARROW");
-        return env && env[0] == '0';
-    }();
-    if (off || p->dim != 3) return false;
+    if (!switches().small_narrow || p->dim != 3) return false;
     // 128^3 grid, narrow window, many point sets: every (set, pencil) is a chain of nearly empty K-blocks (2e4 points per set:
     // 9 per pencil and slab), and from eight sets up there are more chains than CUs -- 16 sets x 2e4 points, m = 2: 1.17 ms
     // against 0.90 on the narrow tiling; with four sets the matrix-core path is still ahead (0.42 against 0.45)
@@ -319,50 +290,270 @@ Geom problem_geom(const nfft_hip_problem *p)
     if (g.CG > 1 && !stream_items(p->num_points, p->batch_size, device_cu_count(), g.M)) g.CG = 1;
     return g;
 }
-PlanSet plan_set(const nfft_hip_problem *p)
+
+// Grids of at most 4096 cells run as one kernel per direction when no plan is supplied (smallgrid.hip).  Average window
+// taps per point set: a set is ONE workgroup's loop, ~0.35 ns per tap and direction (LDS atomics of a single CU) on top of
+// ~25 us per adjoint + forward pair, against 80-145 us for the general path on these sizes -- measured break-even ~10^5
+// taps (profiles/r03_experiments.md).  8e4 since round 4: the reference's own test shape (test/test_adjoint.py: 2-D N = 16,
+// m = 3, 1 000 points per set = 64 000 taps) sat just above the first limit of 6e4 and took the general path (0.122 ms
+// against 0.07 here, profiles/r04_experiments.md)
+bool small_grid_route(const nfft_hip_problem *p)
 {
-    PlanSet ps;
-    ps.g = problem_geom(p);
-    ps.L = plan_layout(ps.g, p->num_points, p->batch_size);
-    ps.owned = choose_owned(p->dim, p->N, p->m, p->num_points, p->batch_size,
-                            (p->flags & NFFT_HIP_POINTS_IN_QUARTER_BALL) ? 0.125 : 1.0);
+    if (!switches().small_grid || !small_grid_supported(p)) return false;
+    int64_t taps = 1;
+    for (int k = 0; k < p->dim; ++k) taps *= 2 * p->m + 2;
+    const int64_t sets = p->batch_size < 1 ? 1 : (p->batch_size > 8 ? 8 : p->batch_size);
+    return p->num_points * taps <= int64_t(80000) * sets;
+}
+
+enum GatherKernel { kGatherCols, kGatherStream, kGatherRing, kGatherLanes };
+// FFT stage of a chunk: full rocFFT + the roll-off kernel; rocFFT rows + the pruned column passes; own rows + the planar
+// column passes (column_layout transposes for C > 1); own rows + the column-innermost passes (C > 1, >= 32 planes)
+enum FftRoute { kFftFull, kFftRocRows, kFftOwnPlanar, kFftOwnCi };
+
+struct Route {
+    // The point plan: the tile-sorted points (pencils with halo: what the interpolation kernels and the scatter spreading
+    // kernels walk) and, for sparse 3-D problems, a second sort by owned tiles with an entry per touched tile for the
+    // owner-computes spreading kernel (common.h choose_owned), stored behind the first.
+    Geom g;
+    PlanLayout L;
+    bool owned;
+    Geom go;
+    PlanLayout Lo;
+    int64_t off_own, plan_bytes;
+    int64_t n, B, Cr;       // points, point sets, real planes per point set
+    SpreadMode spread;      // spreading kernel: matrix cores, register tiles or LDS atomics
+    bool x_through_plan;    // the spreading kernel reads x through the plan (no gather_rows pass)
+    GatherKernel gather;
+    // FFT stage (make_route only)
+    FftRoute fft;           // kFftFull, kFftRocRows or kFftOwnPlanar; chunk_fft() says when a chunk goes column-innermost
+    bool ci;                // several columns on a grid the column-innermost passes take
+    int64_t C, ppc, total_planes, chunk_planes, half_cells;
+    int64_t off_plan, off_xs, off_xmax, off_grid, off_spec, off_col, off_work, work_bytes, total;
+
+    const Geom &spread_geom() const { return owned ? go : g; }
+    const PlanLayout &spread_layout() const { return owned ? Lo : L; }
+    const void *spread_plan(const void *plan) const { return owned ? (const char *)plan + off_own : (const char *)plan; }
+    // the column-innermost passes need at least two groups of 16 planes
+    FftRoute chunk_fft(int64_t np) const { return fft == kFftOwnPlanar && ci && np >= 32 ? kFftOwnCi : fft; }
+};
+
+// Plans and point-side kernels of a problem whose calls have Cr real planes per point set.
+Route plan_route(const nfft_hip_problem *p, int64_t Cr)
+{
+    Route r{};
+    r.g = problem_geom(p);
+    r.L = plan_layout(r.g, p->num_points, p->batch_size);
+    r.owned = choose_owned(p->dim, p->N, p->m, p->num_points, p->batch_size,
+                           (p->flags & NFFT_HIP_POINTS_IN_QUARTER_BALL) ? 0.125 : 1.0);
     // (a single column on a 128^3 grid: what the owner-computes kernel saves -- 10 us of zero-fill, the atomics of a few
     // thousand K-blocks -- is less than its second sort costs: plan 0.074 against 0.038 ms at 2e4 points, round 4)
-    if (p->N < 128 && p->num_columns < 2 && owned_override() < 0) ps.owned = false;
-    if (!ps.g.wide) ps.owned = false;  // (the narrow tiling was preferred: no matrix-core spreading, no owned plan)
-    ps.go = ps.g;
-    ps.Lo = ps.L;
-    ps.off_own = 0;
-    ps.total = ps.L.total;
-    if (ps.owned) {
+    if (p->N < 128 && p->num_columns < 2 && owned_override() < 0) r.owned = false;
+    if (!r.g.wide) r.owned = false;  // (the narrow tiling was preferred: no matrix-core spreading, no owned plan)
+    r.go = r.g;
+    r.Lo = r.L;
+    r.plan_bytes = r.L.total;
+    if (r.owned) {
         // two or more coefficient columns: 32 x 32 tiles, one sweep of the points per PAIR of columns (spread_mfma.hip)
-        ps.go = make_geom(p->dim, p->N, p->m, true, p->num_columns >= 2 && owned_pair_enabled());
-        ps.Lo = plan_layout(ps.go, p->num_points, p->batch_size);
-        ps.off_own = align_up(ps.L.total, 256);
-        ps.total = ps.off_own + ps.Lo.total;
+        r.go = make_geom(p->dim, p->N, p->m, true, p->num_columns >= 2);
+        r.Lo = plan_layout(r.go, p->num_points, p->batch_size);
+        r.off_own = align_up(r.L.total, 256);
+        r.plan_bytes = r.off_own + r.Lo.total;
     }
-    return ps;
+    r.n = p->num_points;
+    r.B = p->batch_size;
+    r.Cr = Cr;
+    const Geom &gs = r.spread_geom();
+    r.spread = spread_mfma_supported(gs) ? kSpreadMfma
+             : spread_reg_supported(gs) && spread_mode() == kSpreadReg ? kSpreadReg : kSpreadLds;
+    // The matrix-core spreading kernel reads one or two real coefficient columns in place: every plan record carries the
+    // index of its point in the caller's arrays and the staging pipeline fetches x[index] two steps ahead of its use -- no
+    // permutation pass (0.18 ms at C3 as a kernel of its own, a 23 us latency-bound prologue per work item inside the
+    // spreading kernel).  With more columns one pass (gather_rows) reads every row once for all of them.  (The LDS-tile
+    // kernel of the narrow tilings reads x through the plan's permutation as well; the register-tile kernel does not.)
+    r.x_through_plan = Cr <= 2 && r.spread != kSpreadReg;
+    // interpolation on the wide 3-D tiling: the wave-per-column kernel from 4 real columns up (half its waves busy), the
+    // streamed one for big work items, else the plane-ring kernel
+    const char gsw = switches().gather;
+    if (!gsw && interp_cols_supported(r.g) && Cr >= 4) r.gather = kGatherCols;
+    else if (!gsw && interp_stream_supported(r.g) && interp_stream_pays(r.g, r.L, r.n)) r.gather = kGatherStream;
+    else if (gsw != 'l' && interp_mfma_supported(r.g)) r.gather = kGatherRing;
+    else r.gather = kGatherLanes;
+    return r;
 }
-int build_plans(const PlanSet &ps, const float *pos, const int64_t *batch, int64_t n, int64_t B, void *plan, hipStream_t s)
+
+// The whole route of an adjoint (x: ppc real planes per column) or forward transform (y: ppc real planes per column),
+// the chunk size and the workspace carve included.
+int make_route(const nfft_hip_problem *p, int ppc, bool adjoint, Route &r)
 {
-    if (int rc = launch_plan_points(ps.g, ps.L, pos, batch, n, B, plan, s)) return rc;
-    if (ps.owned) return launch_plan_points(ps.go, ps.Lo, pos, batch, n, B, (char *)plan + ps.off_own, s);
+    r = plan_route(p, p->num_columns * ppc);
+    r.C = p->num_columns;
+    r.ppc = ppc;
+    r.total_planes = r.B * r.Cr;
+    r.half_cells = (int64_t)(r.g.M / 2 + 1);
+    for (int a = 0; a < 2; ++a) r.half_cells *= r.g.Ma[a];
+    const bool colfft = colfft_supported(r.g) && colfft_enabled();
+    r.fft = !colfft ? kFftFull : rowfft_supported(r.g) ? kFftOwnPlanar : kFftRocRows;
+    r.ci = r.C > 1 && colfft_ci_supported(r.g);
+    // (the work area is sized for the rocFFT row transforms wherever the column passes run)
+    const FftKind fkind = colfft ? (adjoint ? kR2CRows : kC2RRows) : (adjoint ? kR2C : kC2R);
+    const int64_t plane_bytes = r.g.cells * 4 + r.half_cells * 8 + (colfft ? colfft_scratch_bytes(r.g, 1) : 0);
+    // (the budget is a soft one: the group padding of the column-innermost passes, <= 15 planes of scratch, comes on top)
+    int64_t chunk = chunk_budget_bytes() / plane_bytes;
+    chunk -= chunk % ppc;
+    if (chunk < ppc) chunk = ppc;
+    if (chunk > r.total_planes) chunk = r.total_planes;
+    if (chunk > 32768) chunk = 32768 - 32768 % ppc;  // blockIdx.y limit
+    r.chunk_planes = chunk;
+    r.work_bytes = 0;
+    if (r.total_planes > 0) {
+        // plans for the full chunk and for the remainder chunk
+        int64_t w = fft_work_bytes(fkind, r.g.dim, r.g.M, chunk);
+        if (w < 0) return NFFT_HIP_EFFT;
+        r.work_bytes = w;
+        const int64_t rem = r.total_planes % chunk;
+        if (rem) {
+            w = fft_work_bytes(fkind, r.g.dim, r.g.M, rem);
+            if (w < 0) return NFFT_HIP_EFFT;
+            if (w > r.work_bytes) r.work_bytes = w;
+        }
+    }
+    const bool need_xs = adjoint;
+    int64_t o = 0;
+    r.off_plan = o; o = align_up(o + r.plan_bytes, 256);
+    r.off_xs = o;   o = align_up(o + (need_xs ? (align_up(r.spread_layout().cap * r.Cr, 64) + 64) * 4 : 0), 256);
+    r.off_xmax = o; o = align_up(o + (need_xs ? r.total_planes * 4 : 0), 256);
+    r.off_grid = o; o = align_up(o + chunk * r.g.cells * 4, 256);
+    r.off_spec = o; o = align_up(o + chunk * r.half_cells * 8, 256);
+    // (several columns: the column-innermost passes work on whole groups of 16 planes)
+    r.off_col = o;  o = align_up(o + (colfft ? colfft_scratch_bytes(r.g, r.C > 1 ? colfft_ci_planes(chunk) : chunk) : 0), 256);
+    r.off_work = o; o = align_up(o + r.work_bytes, 256);
+    r.total = o + 256;
     return 0;
 }
 
-// interpolation: matrix-core kernels for the wide 3-D tiling (the wave-per-column one from 4 real columns up) unless
-// NFFT_HIP_GATHER=lds (lane-per-point kernel) or =mfma (always the plane-ring kernel)
-int gather_any(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-               int64_t plane0, int64_t nplanes, float *yr, hipStream_t s)
+int build_plans(const Route &r, const float *pos, const int64_t *batch, void *plan, hipStream_t s)
 {
-    static const bool lds_only = [] {
-        const char *env = std::getenv("NFFT_HIP_GATHER");
-        return env && env[0] == 'l';
-    }();
-    if (!lds_only && interp_cols_supported(g, Cr)) return launch_interp_cols(g, L, plan, grid, n, Cr, plane0, nplanes, yr, s);
-    if (!lds_only && interp_stream_supported(g) && interp_stream_pays(g, L, n)) return launch_interp_stream(g, L, plan, grid, n, Cr, plane0, nplanes, yr, s);
-    if (!lds_only && interp_mfma_supported(g)) return launch_interp_mfma(g, L, plan, grid, n, Cr, plane0, nplanes, yr, s);
-    return launch_interp(g, L, plan, grid, n, Cr, plane0, nplanes, yr, s);
+    if (int rc = launch_plan_points(r.g, r.L, pos, batch, r.n, r.B, plan, s)) return rc;
+    if (r.owned) return launch_plan_points(r.go, r.Lo, pos, batch, r.n, r.B, (char *)plan + r.off_own, s);
+    return 0;
+}
+
+// planes [p0, p0 + np) of the grid; xs: the planar copy in plan order; xr: nullptr when gather_rows has filled xs, else x
+// (x_through_plan); xmax: per-plane largest |x| (matrix-core kernel only: launch_plane_absmax)
+int spread_chunk(const Route &r, const void *plan, const float *xr, float *xs, const unsigned *xmax, int64_t p0, int64_t np,
+                 float *grid, hipStream_t s)
+{
+    const Geom &g = r.spread_geom();
+    const PlanLayout &L = r.spread_layout();
+    plan = r.spread_plan(plan);
+    switch (r.spread) {
+    case kSpreadMfma: {
+        // (the owner-computes variant writes every cell itself)
+        if (!g.owned) { StageTimer t(kStageZero, s); NFFT_HIP_CHECK(hipMemsetAsync(grid, 0, (size_t)(np * g.cells * 4), s)); }
+        StageTimer t(kStageSpread, s);
+        return launch_spread_mfma(g, L, plan, xr, xs, xmax, r.n, r.Cr, p0, np, grid, s);
+    }
+    case kSpreadReg: {
+        StageTimer t(kStageSpread, s);
+        return launch_spread_reg(g, L, plan, xs, r.n, r.Cr, p0, np, grid, s);
+    }
+    case kSpreadLds: break;
+    }
+    { StageTimer t(kStageZero, s); NFFT_HIP_CHECK(hipMemsetAsync(grid, 0, (size_t)(np * g.cells * 4), s)); }
+    StageTimer t(kStageSpread, s);
+    return launch_spread(g, L, plan, xr, xs, r.n, r.Cr, p0, np, grid, s);
+}
+
+int gather_chunk(const Route &r, const void *plan, const float *grid, int64_t p0, int64_t np, float *yr, hipStream_t s)
+{
+    switch (r.gather) {
+    case kGatherCols: return launch_interp_cols(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, yr, s);
+    case kGatherStream: return launch_interp_stream(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, yr, s);
+    case kGatherRing: return launch_interp_mfma(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, yr, s);
+    case kGatherLanes: break;
+    }
+    return launch_interp(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, yr, s);
+}
+
+// FFT stage of the planes [p0, p0 + np) of an adjoint: grid -> spec -> y
+int fft_adjoint_chunk(const Route &r, char *ws, float *grid, float2 *spec, int x_is_complex, int real_output, int64_t p0,
+                      int64_t np, void *y, const void *mult, int mult_kind, hipStream_t s)
+{
+    const Geom &g = r.g;
+    void *col = ws + r.off_col;
+    const FftRoute route = r.chunk_fft(np);
+    switch (route) {
+    case kFftFull: {
+        { StageTimer t(kStageFft, s); if (int rc = fft_execute(kR2C, g.dim, g.M, np, grid, spec, ws + r.off_work, r.work_bytes, s)) return rc; }
+        StageTimer t(kStageDeconv, s);
+        return launch_deconv_adjoint(g, spec, r.C, x_is_complex, real_output, p0, np, y, mult, mult_kind, s);
+    }
+    case kFftOwnCi: {
+        // several columns: the planes travel in groups of 16, plane index innermost, and the last pass writes the
+        // reference's [B, N^3, C] layout directly
+        { StageTimer t(kStageFft, s); if (int rc = launch_row_r2c_ci(g, grid, np, spec, s)) return rc; }
+        StageTimer t(kStageDeconv, s);
+        return launch_colfft_adjoint_ci(g, spec, col, r.C, x_is_complex, real_output, p0, np, y, mult, mult_kind, s);
+    }
+    case kFftRocRows: {
+        StageTimer t(kStageFft, s);
+        if (int rc = fft_execute(kR2CRows, g.dim, g.M, np, grid, spec, ws + r.off_work, r.work_bytes, s)) return rc;
+        break;
+    }
+    case kFftOwnPlanar: {
+        StageTimer t(kStageFft, s);
+        if (int rc = launch_row_r2c(g, grid, col, r.chunk_planes, np, spec, s)) return rc;
+        break;
+    }
+    }
+    const bool own_rows = route == kFftOwnPlanar;
+    StageTimer t(kStageDeconv, s);
+    if (r.C < 2)
+        return launch_colfft_adjoint(g, spec, own_rows, col, r.chunk_planes, r.C, x_is_complex, real_output, p0, np, y, mult, mult_kind, s);
+    // several columns: the passes write a planar copy (into the grid buffer, free by now), one tiled transpose brings it
+    // into the reference's column-interleaved layout
+    const int64_t K = g.dim == 2 ? g.N * (int64_t)g.N : g.N * (int64_t)g.N * g.N;
+    if (int rc = launch_colfft_adjoint(g, spec, own_rows, col, r.chunk_planes, 1, x_is_complex, real_output, 0, np, grid, mult, mult_kind, s)) return rc;
+    return launch_column_layout(true, grid, y, K, r.C, p0 / r.ppc, np / r.ppc, real_output ? 4 : 8, s);
+}
+
+// FFT stage of the planes [p0, p0 + np) of a forward transform: xhat -> spec -> grid
+int fft_forward_chunk(const Route &r, char *ws, const void *xhat, int x_is_complex, int real_output, int64_t p0, int64_t np,
+                      float *grid, float2 *spec, hipStream_t s)
+{
+    const Geom &g = r.g;
+    void *col = ws + r.off_col;
+    const FftRoute route = r.chunk_fft(np);
+    switch (route) {
+    case kFftFull: {
+        { StageTimer t(kStageDeconv, s); if (int rc = launch_deconv_forward(g, xhat, r.C, x_is_complex, real_output, p0, np, spec, s)) return rc; }
+        StageTimer t(kStageFft, s);
+        return fft_execute(kC2R, g.dim, g.M, np, spec, grid, ws + r.off_work, r.work_bytes, s);
+    }
+    case kFftOwnCi: {
+        { StageTimer t(kStageDeconv, s); if (int rc = launch_colfft_forward_ci(g, xhat, spec, col, r.C, x_is_complex, real_output, p0, np, s)) return rc; }
+        StageTimer t(kStageFft, s);
+        return launch_row_c2r_ci(g, spec, np, grid, s);
+    }
+    case kFftRocRows:
+    case kFftOwnPlanar: break;
+    }
+    const bool own_rows = route == kFftOwnPlanar;
+    {
+        StageTimer t(kStageDeconv, s);
+        if (r.C < 2) {
+            if (int rc = launch_colfft_forward(g, xhat, col, r.chunk_planes, r.C, x_is_complex, real_output, p0, np, spec, own_rows, s)) return rc;
+        } else {
+            // several columns: planar copy of this chunk's columns first (the grid buffer is free until the row pass)
+            const int64_t K = g.dim == 2 ? g.N * (int64_t)g.N : g.N * (int64_t)g.N * g.N;
+            if (int rc = launch_column_layout(false, xhat, grid, K, r.C, p0 / r.ppc, np / r.ppc, x_is_complex ? 8 : 4, s)) return rc;
+            if (int rc = launch_colfft_forward(g, grid, col, r.chunk_planes, 1, x_is_complex, real_output, 0, np, spec, own_rows, s)) return rc;
+        }
+    }
+    StageTimer t(kStageFft, s);
+    if (own_rows) return launch_row_c2r(g, spec, col, r.chunk_planes, np, grid, s);
+    return fft_execute(kC2RRows, g.dim, g.M, np, spec, grid, ws + r.off_work, r.work_bytes, s);
 }
 
 int validate(const nfft_hip_problem *p)
@@ -386,143 +577,6 @@ int validate(const nfft_hip_problem *p)
             return NFFT_HIP_EINVAL;
         }
     }
-    return 0;
-}
-
-int64_t grid_budget_bytes()
-{
-    // upper bound for (real grid + half spectrum) of one chunk of planes; the rest of the 288 GB stays free
-    // for the caller.  Overridable for tests of the chunked path.
-    const char *env = std::getenv("NFFT_HIP_CHUNK_BYTES");
-    if (env) {
-        const long long v = std::atoll(env);
-        if (v > 0) return (int64_t)v;
-    }
-    return int64_t(16) << 30;
-}
-
-struct Carve {
-    PlanSet ps;
-    Geom g;        // = ps.g
-    PlanLayout L;  // = ps.L
-    int64_t n, B, C, Cr, total_planes, chunk_planes;
-    int64_t half_cells;
-    bool colfft;  // pruned column passes (colfft.hip) instead of the full dim-dimensional rocFFT transform
-    int64_t off_plan, off_xs, off_xmax, off_grid, off_spec, off_col, off_work, work_bytes, total;
-};
-
-bool spread_reg_enabled() { return subblock_plan_enabled(); }
-
-// The matrix-core spreading kernel reads one or two real coefficient columns in place: every plan record carries the
-// index of its point in the caller's arrays and the staging pipeline fetches x[index] two steps ahead of its use -- no
-// permutation pass (0.18 ms at C3 as a kernel of its own, a 23 us latency-bound prologue per work item inside the
-// spreading kernel).  With more columns one pass (gather_rows) reads every row once for all of them.
-// NFFT_HIP_XGATHER=1 always runs the separate pass.
-bool spread_permutes(const Geom &g, int64_t Cr)
-{
-    static const bool off = [] {
-        const char *env = std::getenv("NFFT_HIP_XGATHER");
-        return env && env[0] == '1';
-    }();
-    if (off || Cr > 2) return false;
-    // (the LDS-tile kernel of the narrow tilings reads x through the plan's permutation as well; the opt-in register-tile
-    // kernel does not)
-    return spread_mfma_supported(g) || !(spread_reg_supported(g) && spread_reg_enabled());
-}
-
-// xs: the planar copy in plan order; xr: nullptr when the caller has filled xs, else what spread_permutes() reads;
-// xmax: per-plane largest |x| (matrix-core kernel only: launch_plane_absmax)
-int spread_any(const Geom &g, const PlanLayout &L, const void *plan, const float *xr, float *xs, const unsigned *xmax,
-               int64_t n, int64_t Cr, int64_t p0, int64_t np, float *grid, hipStream_t s)
-{
-    if (spread_mfma_supported(g)) {
-        // (the owner-computes variant writes every cell itself)
-        if (!g.owned) { StageTimer t(kStageZero, s); NFFT_HIP_CHECK(hipMemsetAsync(grid, 0, (size_t)(np * g.cells * 4), s)); }
-        StageTimer t(kStageSpread, s);
-        return launch_spread_mfma(g, L, plan, xr, xs, xmax, n, Cr, p0, np, grid, s);
-    }
-    if (spread_reg_supported(g) && spread_reg_enabled()) {
-        StageTimer t(kStageSpread, s);
-        return launch_spread_reg(g, L, plan, xs, n, Cr, p0, np, grid, s);
-    }
-    { StageTimer t(kStageZero, s); NFFT_HIP_CHECK(hipMemsetAsync(grid, 0, (size_t)(np * g.cells * 4), s)); }
-    StageTimer t(kStageSpread, s);
-    return launch_spread(g, L, plan, xr, xs, n, Cr, p0, np, grid, s);
-}
-
-// own pruned row passes instead of rocFFT's for the contiguous axis (NFFT_HIP_ROCFFT_ROWS=1 keeps rocFFT)
-bool own_row_passes(const Geom &g)
-{
-    static const bool off = [] {
-        const char *env = std::getenv("NFFT_HIP_ROCFFT_ROWS");
-        return env && env[0] == '1';
-    }();
-    return !off && rowfft_supported(g);
-}
-
-// Several coefficient columns: column-innermost passes (no planar copy, no layout transposes) for chunks of at least two
-// groups of planes; NFFT_HIP_COL_PLANAR=1 keeps the planar passes + transposes of rounds 1-2.
-bool column_innermost(const Geom &g, int64_t C, int64_t nplanes)
-{
-    static const bool off = [] {
-        const char *env = std::getenv("NFFT_HIP_COL_PLANAR");
-        return env && env[0] == '1';
-    }();
-    return !off && C > 1 && nplanes >= 32 && colfft_ci_supported(g);
-}
-
-bool colfft_enabled()
-{
-    const char *env = std::getenv("NFFT_HIP_NO_COLFFT");
-    return !(env && env[0] == '1');
-}
-
-// planes_per_col: 2 when a column owns a (re, im) pair of real planes, else 1
-int make_carve(const nfft_hip_problem *p, int planes_per_col, bool need_xs, FftKind kind, Carve &c)
-{
-    c.ps = plan_set(p);
-    c.g = c.ps.g;
-    c.L = c.ps.L;
-    c.n = p->num_points;
-    c.B = p->batch_size;
-    c.C = p->num_columns;
-    c.Cr = c.C * planes_per_col;
-    c.total_planes = c.B * c.Cr;
-    c.half_cells = (int64_t)(c.g.M / 2 + 1);
-    for (int a = 0; a < 2; ++a) c.half_cells *= c.g.Ma[a];
-    c.colfft = colfft_supported(c.g) && colfft_enabled();
-    const FftKind fkind = c.colfft ? (kind == kR2C ? kR2CRows : kC2RRows) : kind;
-    const int64_t plane_bytes = c.g.cells * 4 + c.half_cells * 8 + (c.colfft ? colfft_scratch_bytes(c.g, 1) : 0);
-    // (the budget is a soft one: the group padding of the column-innermost passes, <= 15 planes of scratch, comes on top)
-    int64_t chunk = grid_budget_bytes() / plane_bytes;
-    chunk -= chunk % planes_per_col;
-    if (chunk < planes_per_col) chunk = planes_per_col;
-    if (chunk > c.total_planes) chunk = c.total_planes;
-    if (chunk > 32768) chunk = 32768 - 32768 % planes_per_col;  // blockIdx.y limit
-    c.chunk_planes = chunk;
-    c.work_bytes = 0;
-    if (c.total_planes > 0) {
-        // plans for the full chunk and for the remainder chunk
-        int64_t w = fft_work_bytes(fkind, c.g.dim, c.g.M, chunk);
-        if (w < 0) return NFFT_HIP_EFFT;
-        c.work_bytes = w;
-        const int64_t rem = c.total_planes % chunk;
-        if (rem) {
-            w = fft_work_bytes(fkind, c.g.dim, c.g.M, rem);
-            if (w < 0) return NFFT_HIP_EFFT;
-            if (w > c.work_bytes) c.work_bytes = w;
-        }
-    }
-    int64_t o = 0;
-    c.off_plan = o; o = align_up(o + c.ps.total, 256);
-    c.off_xs = o;   o = align_up(o + (need_xs ? (align_up(c.ps.spread_layout().cap * c.Cr, 64) + 64) * 4 : 0), 256);
-    c.off_xmax = o; o = align_up(o + (need_xs ? c.total_planes * 4 : 0), 256);
-    c.off_grid = o; o = align_up(o + chunk * c.g.cells * 4, 256);
-    c.off_spec = o; o = align_up(o + chunk * c.half_cells * 8, 256);
-    // (several columns: the column-innermost passes work on whole groups of 16 planes)
-    c.off_col = o;  o = align_up(o + (c.colfft ? colfft_scratch_bytes(c.g, c.C > 1 ? colfft_ci_planes(chunk) : chunk) : 0), 256);
-    c.off_work = o; o = align_up(o + c.work_bytes, 256);
-    c.total = o + 256;
     return 0;
 }
 
@@ -572,24 +626,24 @@ int64_t nfft_hip_adjoint_workspace_bytes(const nfft_hip_problem *p, int x_is_com
 {
     (void)real_output;
     if (validate(p)) return -1;
-    Carve c;
-    if (make_carve(p, x_is_complex ? 2 : 1, true, kR2C, c)) return -1;
-    return c.total;
+    Route r;
+    if (make_route(p, x_is_complex ? 2 : 1, true, r)) return -1;
+    return r.total;
 }
 
 int64_t nfft_hip_forward_workspace_bytes(const nfft_hip_problem *p, int x_is_complex, int real_output)
 {
     (void)x_is_complex;
     if (validate(p)) return -1;
-    Carve c;
-    if (make_carve(p, real_output ? 1 : 2, false, kC2R, c)) return -1;
-    return c.total;
+    Route r;
+    if (make_route(p, real_output ? 1 : 2, false, r)) return -1;
+    return r.total;
 }
 
 int64_t nfft_hip_plan_bytes(const nfft_hip_problem *p)
 {
     if (validate(p)) return -1;
-    return plan_set(p).total;
+    return plan_route(p, 0).plan_bytes;
 }
 
 int nfft_hip_plan_points(const nfft_hip_problem *p, const float *pos, const int64_t *batch, void *plan,
@@ -597,11 +651,11 @@ int nfft_hip_plan_points(const nfft_hip_problem *p, const float *pos, const int6
 {
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate(p)) return rc;
-    const PlanSet ps = plan_set(p);
-    if (!plan || plan_bytes < ps.total) { set_error("plan buffer too small"); return NFFT_HIP_EWORKSPACE; }
+    const Route r = plan_route(p, 0);
+    if (!plan || plan_bytes < r.plan_bytes) { set_error("plan buffer too small"); return NFFT_HIP_EWORKSPACE; }
     if (p->num_points > 0 && !pos) { set_error("Input mismatch: pos is null"); return NFFT_HIP_EINVAL; }
     StageTimer t(kStagePlan, (hipStream_t)stream);
-    return build_plans(ps, pos, batch, p->num_points, p->batch_size, plan, (hipStream_t)stream);
+    return build_plans(r, pos, batch, plan, (hipStream_t)stream);
 }
 
 int nfft_hip_plan_verify(const nfft_hip_problem *p, const float *pos, const int64_t *batch, void *plan, void *stream)
@@ -609,15 +663,16 @@ int nfft_hip_plan_verify(const nfft_hip_problem *p, const float *pos, const int6
     if (int rc = validate(p)) return rc;
     if (!plan || (p->num_points > 0 && !pos)) { set_error("Input mismatch: null plan or pos"); return NFFT_HIP_EINVAL; }
     static std::atomic<unsigned> slot{0};  // eight verifications of one plan may be in flight (on different streams)
-    return launch_points_verify(pos, batch, p->num_points, p->dim, (char *)plan + plan_set(p).L.off_seal, (int)(slot++ & 7u),
-                                (hipStream_t)stream);
+    return launch_points_verify(pos, batch, p->num_points, p->dim, (char *)plan + plan_route(p, 0).L.off_seal,
+                                (int)(slot++ & 7u), (hipStream_t)stream);
 }
 
 int64_t nfft_hip_spread_scratch_bytes(const nfft_hip_problem *p, int64_t real_columns)
 {
     if (validate(p) || real_columns < 0) return -1;
     // plan-ordered copy of the coefficients + one word per plane (its largest |x|)
-    return (align_up(plan_set(p).spread_layout().cap * real_columns, 64) + 64 + align_up(p->batch_size * real_columns, 64)) * 4;
+    return (align_up(plan_route(p, real_columns).spread_layout().cap * real_columns, 64) + 64 +
+            align_up(p->batch_size * real_columns, 64)) * 4;
 }
 
 int nfft_hip_spread(const nfft_hip_problem *p, const void *plan, const float *xr, int64_t real_columns, float *grid,
@@ -625,20 +680,17 @@ int nfft_hip_spread(const nfft_hip_problem *p, const void *plan, const float *xr
 {
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate(p)) return rc;
-    const PlanSet ps = plan_set(p);
-    const Geom &g = ps.spread_geom();
-    const PlanLayout &L = ps.spread_layout();
-    const void *const halo_plan = plan;
-    plan = ps.spread_plan(plan);
+    const Route r = plan_route(p, real_columns);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t planes = p->batch_size * real_columns;
+    const int64_t planes = r.B * real_columns;
     if (planes > 32768) { set_error("Input mismatch: too many planes for one spread call"); return NFFT_HIP_EINVAL; }
-    unsigned *xmax = (unsigned *)(scratch + align_up(L.cap * real_columns, 64) + 64);
-    if (spread_mfma_supported(g))
-        if (int rc = launch_plane_absmax(ps.g, ps.L, halo_plan, xr, p->num_points, p->batch_size, real_columns, xmax, s)) return rc;
-    if (spread_permutes(g, real_columns)) return spread_any(g, L, plan, xr, scratch, xmax, p->num_points, real_columns, 0, planes, grid, s);
-    if (int rc = launch_gather_rows(g, L, plan, p->num_points, xr, real_columns, scratch, s)) return rc;
-    return spread_any(g, L, plan, nullptr, scratch, xmax, p->num_points, real_columns, 0, planes, grid, s);
+    unsigned *xmax = (unsigned *)(scratch + align_up(r.spread_layout().cap * real_columns, 64) + 64);
+    if (r.spread == kSpreadMfma)
+        if (int rc = launch_plane_absmax(r.g, r.L, plan, xr, r.n, r.B, real_columns, xmax, s)) return rc;
+    if (r.x_through_plan) return spread_chunk(r, plan, xr, scratch, xmax, 0, planes, grid, s);
+    if (int rc = launch_gather_rows(r.spread_geom(), r.spread_layout(), r.spread_plan(plan), r.n, xr, real_columns, scratch, s))
+        return rc;
+    return spread_chunk(r, plan, nullptr, scratch, xmax, 0, planes, grid, s);
 }
 
 int nfft_hip_interpolate(const nfft_hip_problem *p, const void *plan, const float *grid, int64_t real_columns,
@@ -646,11 +698,10 @@ int nfft_hip_interpolate(const nfft_hip_problem *p, const void *plan, const floa
 {
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate(p)) return rc;
-    const Geom g = problem_geom(p);
-    const PlanLayout L = plan_layout(g, p->num_points, p->batch_size);
-    const int64_t planes = p->batch_size * real_columns;
+    const Route r = plan_route(p, real_columns);
+    const int64_t planes = r.B * real_columns;
     if (planes > 32768) { set_error("Input mismatch: too many planes for one interpolate call"); return NFFT_HIP_EINVAL; }
-    return gather_any(g, L, plan, grid, p->num_points, real_columns, 0, planes, yr, (hipStream_t)stream);
+    return gather_chunk(r, plan, grid, 0, planes, yr, (hipStream_t)stream);
 }
 
 static int adjoint_impl(const nfft_hip_problem *p, const float *pos, const int64_t *batch, const void *ext_plan,
@@ -660,7 +711,7 @@ static int adjoint_impl(const nfft_hip_problem *p, const float *pos, const int64
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate(p)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (!ext_plan && small_grid_supported(p)) {
+    if (!ext_plan && small_grid_route(p)) {
         // grid in one workgroup's LDS: one kernel, no plan, no workspace (smallgrid.hip)
         if (p->batch_size * p->num_columns == 0) return 0;
         if (!y) { set_error("Input mismatch: y is null"); return NFFT_HIP_EINVAL; }
@@ -668,67 +719,38 @@ static int adjoint_impl(const nfft_hip_problem *p, const float *pos, const int64
         StageTimer t(kStageSpread, s);
         return launch_small_grid_adjoint(p, pos, batch, x, x_is_complex, real_output, y, mult, mult_kind, s);
     }
-    const int ppc = x_is_complex ? 2 : 1;
-    Carve c;
-    if (int rc = make_carve(p, ppc, true, kR2C, c)) return rc;
-    if (c.total_planes == 0) return 0;
+    Route r;
+    if (int rc = make_route(p, x_is_complex ? 2 : 1, true, r)) return rc;
+    if (r.total_planes == 0) return 0;
     if (!y) { set_error("Input mismatch: y is null"); return NFFT_HIP_EINVAL; }
-    if (c.n > 0 && ((!pos && !ext_plan) || !x)) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    if (!workspace || workspace_bytes < c.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    if (r.n > 0 && ((!pos && !ext_plan) || !x)) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    if (!workspace || workspace_bytes < r.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
     char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
     const void *plan = ext_plan;
-    float *xs = (float *)(ws + c.off_xs);
-    float *grid = (float *)(ws + c.off_grid);
-    float2 *spec = (float2 *)(ws + c.off_spec);
-    void *work = ws + c.off_work;
+    float *xs = (float *)(ws + r.off_xs);
+    unsigned *xmax = (unsigned *)(ws + r.off_xmax);
+    float *grid = (float *)(ws + r.off_grid);
+    float2 *spec = (float2 *)(ws + r.off_spec);
 
     if (!ext_plan) {
         StageTimer t(kStagePlan, s);
-        if (int rc = build_plans(c.ps, pos, batch, c.n, c.B, ws + c.off_plan, s)) return rc;
-        plan = ws + c.off_plan;
+        if (int rc = build_plans(r, pos, batch, ws + r.off_plan, s)) return rc;
+        plan = ws + r.off_plan;
     }
-    const Geom &gs = c.ps.spread_geom();
-    const PlanLayout &Ls = c.ps.spread_layout();
-    const void *plan_s = c.ps.spread_plan(plan);
-    const bool fused = spread_permutes(gs, c.Cr);
-    unsigned *xmax = (unsigned *)(ws + c.off_xmax);
-    if (spread_mfma_supported(gs)) {
+    if (r.spread == kSpreadMfma) {
         // operand scales of the matrix-core kernel: one streaming pass over x for all planes of the call
         StageTimer t(kStageGather, s);
-        if (int rc = launch_plane_absmax(c.g, c.L, plan, (const float *)x, c.n, c.B, c.Cr, xmax, s)) return rc;
+        if (int rc = launch_plane_absmax(r.g, r.L, plan, (const float *)x, r.n, r.B, r.Cr, xmax, s)) return rc;
     }
-    if (!fused) { StageTimer t(kStageGather, s); if (int rc = launch_gather_rows(gs, Ls, plan_s, c.n, (const float *)x, c.Cr, xs, s)) return rc; }
-    for (int64_t p0 = 0; p0 < c.total_planes; p0 += c.chunk_planes) {
-        const int64_t np = std::min(c.chunk_planes, c.total_planes - p0);
-        if (int rc = spread_any(gs, Ls, plan_s, fused ? (const float *)x : nullptr, xs, xmax, c.n, c.Cr, p0, np, grid, s)) return rc;
-        if (c.colfft) {
-            const bool own_rows = own_row_passes(c.g);
-            if (own_rows && column_innermost(c.g, c.C, np)) {
-                // several columns: the planes travel in groups of 16, plane index innermost, and the last pass writes the
-                // reference's [B, N^3, C] layout directly
-                { StageTimer t(kStageFft, s); if (int rc = launch_row_r2c_ci(c.g, grid, np, spec, s)) return rc; }
-                StageTimer t(kStageDeconv, s);
-                if (int rc = launch_colfft_adjoint_ci(c.g, spec, ws + c.off_col, c.C, x_is_complex, real_output, p0, np, y, mult, mult_kind, s)) return rc;
-                continue;
-            }
-            if (own_rows) { StageTimer t(kStageFft, s); if (int rc = launch_row_r2c(c.g, grid, ws + c.off_col, c.chunk_planes, np, spec, s)) return rc; }
-            else { StageTimer t(kStageFft, s); if (int rc = fft_execute(kR2CRows, c.g.dim, c.g.M, np, grid, spec, work, c.work_bytes, s)) return rc; }
-            if (c.C > 1) {
-                // several columns: the passes write a planar copy (into the grid buffer, free by now), one tiled
-                // transpose brings it into the reference's column-interleaved layout
-                StageTimer t(kStageDeconv, s);
-                const int ppc_a = x_is_complex ? 2 : 1;
-                const int64_t K = c.g.dim == 2 ? c.g.N * (int64_t)c.g.N : c.g.N * (int64_t)c.g.N * c.g.N;
-                if (int rc = launch_colfft_adjoint(c.g, spec, own_rows, ws + c.off_col, c.chunk_planes, 1, x_is_complex, real_output, 0, np, grid, mult, mult_kind, s)) return rc;
-                if (int rc = launch_column_layout(true, grid, y, K, c.C, p0 / ppc_a, np / ppc_a, real_output ? 4 : 8, s)) return rc;
-            } else {
-                StageTimer t(kStageDeconv, s);
-                if (int rc = launch_colfft_adjoint(c.g, spec, own_rows, ws + c.off_col, c.chunk_planes, c.C, x_is_complex, real_output, p0, np, y, mult, mult_kind, s)) return rc;
-            }
-        } else {
-            { StageTimer t(kStageFft, s); if (int rc = fft_execute(kR2C, c.g.dim, c.g.M, np, grid, spec, work, c.work_bytes, s)) return rc; }
-            { StageTimer t(kStageDeconv, s); if (int rc = launch_deconv_adjoint(c.g, spec, c.C, x_is_complex, real_output, p0, np, y, mult, mult_kind, s)) return rc; }
-        }
+    if (!r.x_through_plan) {
+        StageTimer t(kStageGather, s);
+        if (int rc = launch_gather_rows(r.spread_geom(), r.spread_layout(), r.spread_plan(plan), r.n, (const float *)x, r.Cr, xs, s))
+            return rc;
+    }
+    for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes) {
+        const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
+        if (int rc = spread_chunk(r, plan, r.x_through_plan ? (const float *)x : nullptr, xs, xmax, p0, np, grid, s)) return rc;
+        if (int rc = fft_adjoint_chunk(r, ws, grid, spec, x_is_complex, real_output, p0, np, y, mult, mult_kind, s)) return rc;
     }
     return 0;
 }
@@ -740,56 +762,33 @@ static int forward_impl(const nfft_hip_problem *p, const float *pos, const int64
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate(p)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (!ext_plan && small_grid_supported(p)) {
+    if (!ext_plan && small_grid_route(p)) {
         if (p->batch_size * p->num_columns == 0 || p->num_points == 0) return 0;
         if (!y || !pos || !xhat) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
         StageTimer t(kStageInterp, s);
         return launch_small_grid_forward(p, pos, batch, xhat, x_is_complex, real_output, y, s);
     }
-    const int ppc = real_output ? 1 : 2;
-    Carve c;
-    if (int rc = make_carve(p, ppc, false, kC2R, c)) return rc;
-    if (c.total_planes == 0 || c.n == 0) return 0;
+    Route r;
+    if (int rc = make_route(p, real_output ? 1 : 2, false, r)) return rc;
+    if (r.total_planes == 0 || r.n == 0) return 0;
     if (!y || (!pos && !ext_plan) || !xhat) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    if (!workspace || workspace_bytes < c.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    if (!workspace || workspace_bytes < r.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
     char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
     const void *plan = ext_plan;
-    float *grid = (float *)(ws + c.off_grid);
-    float2 *spec = (float2 *)(ws + c.off_spec);
-    void *work = ws + c.off_work;
+    float *grid = (float *)(ws + r.off_grid);
+    float2 *spec = (float2 *)(ws + r.off_spec);
 
     if (!ext_plan) {
         // (only the first sort: the forward transform never spreads)
         StageTimer t(kStagePlan, s);
-        if (int rc = launch_plan_points(c.g, c.L, pos, batch, c.n, c.B, ws + c.off_plan, s)) return rc;
-        plan = ws + c.off_plan;
+        if (int rc = launch_plan_points(r.g, r.L, pos, batch, r.n, r.B, ws + r.off_plan, s)) return rc;
+        plan = ws + r.off_plan;
     }
-    for (int64_t p0 = 0; p0 < c.total_planes; p0 += c.chunk_planes) {
-        const int64_t np = std::min(c.chunk_planes, c.total_planes - p0);
-        if (c.colfft) {
-            const bool own_rows = own_row_passes(c.g);
-            if (own_rows && column_innermost(c.g, c.C, np)) {
-                { StageTimer t(kStageDeconv, s); if (int rc = launch_colfft_forward_ci(c.g, xhat, spec, ws + c.off_col, c.C, x_is_complex, real_output, p0, np, s)) return rc; }
-                { StageTimer t(kStageFft, s); if (int rc = launch_row_c2r_ci(c.g, spec, np, grid, s)) return rc; }
-            } else {
-                if (c.C > 1) {
-                    // several columns: planar copy of this chunk's columns first (the grid buffer is free until the row pass)
-                    StageTimer t(kStageDeconv, s);
-                    const int64_t K = c.g.dim == 2 ? c.g.N * (int64_t)c.g.N : c.g.N * (int64_t)c.g.N * c.g.N;
-                    if (int rc = launch_column_layout(false, xhat, grid, K, c.C, p0 / ppc, np / ppc, x_is_complex ? 8 : 4, s)) return rc;
-                    if (int rc = launch_colfft_forward(c.g, grid, ws + c.off_col, c.chunk_planes, 1, x_is_complex, real_output, 0, np, spec, own_rows, s)) return rc;
-                } else {
-                    StageTimer t(kStageDeconv, s);
-                    if (int rc = launch_colfft_forward(c.g, xhat, ws + c.off_col, c.chunk_planes, c.C, x_is_complex, real_output, p0, np, spec, own_rows, s)) return rc;
-                }
-                if (own_rows) { StageTimer t(kStageFft, s); if (int rc = launch_row_c2r(c.g, spec, ws + c.off_col, c.chunk_planes, np, grid, s)) return rc; }
-                else { StageTimer t(kStageFft, s); if (int rc = fft_execute(kC2RRows, c.g.dim, c.g.M, np, spec, grid, work, c.work_bytes, s)) return rc; }
-            }
-        } else {
-            { StageTimer t(kStageDeconv, s); if (int rc = launch_deconv_forward(c.g, xhat, c.C, x_is_complex, real_output, p0, np, spec, s)) return rc; }
-            { StageTimer t(kStageFft, s); if (int rc = fft_execute(kC2R, c.g.dim, c.g.M, np, spec, grid, work, c.work_bytes, s)) return rc; }
-        }
-        { StageTimer t(kStageInterp, s); if (int rc = gather_any(c.g, c.L, plan, grid, c.n, c.Cr, p0, np, (float *)y, s)) return rc; }
+    for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes) {
+        const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
+        if (int rc = fft_forward_chunk(r, ws, xhat, x_is_complex, real_output, p0, np, grid, spec, s)) return rc;
+        StageTimer t(kStageInterp, s);
+        if (int rc = gather_chunk(r, plan, grid, p0, np, (float *)y, s)) return rc;
     }
     return 0;
 }
@@ -811,7 +810,7 @@ int nfft_hip_forward(const nfft_hip_problem *p, const float *pos, const void *xh
 int nfft_hip_plan_needed(const nfft_hip_problem *p)
 {
     if (validate(p)) return 1;
-    return small_grid_supported(p) ? 0 : 1;
+    return small_grid_route(p) ? 0 : 1;
 }
 
 int nfft_hip_adjoint_planned(const nfft_hip_problem *p, const void *plan, const void *x, int x_is_complex,
@@ -831,6 +830,7 @@ int nfft_hip_forward_planned(const nfft_hip_problem *p, const void *plan, const 
 // ---- fast summation -------------------------------------------------------------------------
 namespace {
 struct FastsumCarve {
+    Route src, tgt;  // adjoint at the sources, forward transform at the targets
     int64_t band_bytes, plan_s, plan_t, inner, off_band, off_plan_s, off_plan_t, off_inner, total;
 };
 int fastsum_check(const nfft_hip_problem *src, const nfft_hip_problem *tgt)
@@ -847,15 +847,14 @@ int fastsum_check(const nfft_hip_problem *src, const nfft_hip_problem *tgt)
 int fastsum_carve(const nfft_hip_problem *src, const nfft_hip_problem *tgt, int x_is_complex, bool own_plans,
                   bool shared_points, FastsumCarve &f)
 {
-    Carve a, b;
-    if (int rc = make_carve(src, x_is_complex ? 2 : 1, true, kR2C, a)) return rc;
-    if (int rc = make_carve(tgt, x_is_complex ? 2 : 1, false, kC2R, b)) return rc;
+    if (int rc = make_route(src, x_is_complex ? 2 : 1, true, f.src)) return rc;
+    if (int rc = make_route(tgt, x_is_complex ? 2 : 1, false, f.tgt)) return rc;
     int64_t band = src->batch_size * src->num_columns * 8;
     for (int d = 0; d < src->dim; ++d) band *= src->N;
     f.band_bytes = align_up(band, 256);
-    f.plan_s = own_plans ? align_up(a.ps.total, 256) : 0;
-    f.plan_t = own_plans && !shared_points ? align_up(b.ps.total, 256) : 0;
-    f.inner = std::max(a.total, b.total);
+    f.plan_s = own_plans ? align_up(f.src.plan_bytes, 256) : 0;
+    f.plan_t = own_plans && !shared_points ? align_up(f.tgt.plan_bytes, 256) : 0;
+    f.inner = std::max(f.src.total, f.tgt.total);
     int64_t o = 0;
     f.off_band = o;   o += f.band_bytes;
     f.off_plan_s = o; o += f.plan_s;
@@ -889,7 +888,7 @@ int fastsum_impl(const nfft_hip_problem *src_in, const float *sources, const int
     hipStream_t s = (hipStream_t)stream;
     // problems whose grid fits one workgroup's LDS: adjoint (with the kernel's coefficients folded into its roll-off)
     // and forward transform are one fused kernel each on the caller's points -- no plans (smallgrid.hip)
-    const bool fused1d = own_plans && small_grid_supported(src) && small_grid_supported(tgt);
+    const bool fused1d = own_plans && small_grid_route(src) && small_grid_route(tgt);
     if (fused1d) {
         if (src->num_points > 0 && !sources) { set_error("Input mismatch: sources is null"); return NFFT_HIP_EINVAL; }
         if (!targets) { set_error("Input mismatch: targets is null"); return NFFT_HIP_EINVAL; }
@@ -907,15 +906,13 @@ int fastsum_impl(const nfft_hip_problem *src_in, const float *sources, const int
         if (!targets) { set_error("Input mismatch: targets is null"); return NFFT_HIP_EINVAL; }
         {
             StageTimer t(kStagePlan, s);
-            if (int rc = build_plans(plan_set(src), sources, source_batch, src->num_points, src->batch_size,
-                                     ws + f.off_plan_s, s)) return rc;
+            if (int rc = build_plans(f.src, sources, source_batch, ws + f.off_plan_s, s)) return rc;
         }
         source_plan = ws + f.off_plan_s;
         target_plan = source_plan;
         if (!shared) {
             StageTimer t(kStagePlan, s);
-            if (int rc = build_plans(plan_set(tgt), targets, target_batch, tgt->num_points, tgt->batch_size,
-                                     ws + f.off_plan_t, s)) return rc;
+            if (int rc = build_plans(f.tgt, targets, target_batch, ws + f.off_plan_t, s)) return rc;
             target_plan = ws + f.off_plan_t;
         }
     }

@@ -15,7 +15,6 @@
 //
 // "band+" is k in [-N/2, N/2]: the extra +N/2 row feeds the Hermitian mirror g_hat[-k] = conj(g_hat[k])
 // that reconstructs the k2 < 0 half of the spectrum from the stored k2 >= 0 half.
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -1152,14 +1151,9 @@ column_layout_kernel(const T *__restrict__ src, T *__restrict__ dst, int64_t K /
 // runs of a tile start on 32- / 64-byte boundaries
 int compact_stride(const Geom &g)
 {
-    static const int forced = [] {
-        const char *env = std::getenv("NFFT_HIP_KS_ALIGN");
-        const int v = env ? std::atoi(env) : 0;
-        return (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) ? v : 0;
-    }();
     // measured (profiles/r02_experiments.md): 8 at M = 512 (129 -> 136 columns), 4 at M = 256 (65 -> 68: padding to
     // whole 16-column tiles, 80, costs more bytes than the alignment wins)
-    const int a = forced ? forced : (g.M >= 512 ? 8 : 4);
+    const int a = g.M >= 512 ? 8 : 4;
     return (g.N / 2 + 1 + a - 1) / a * a;
 }
 
@@ -1180,7 +1174,7 @@ ColGeom make_col_geom(const Geom &g, bool two_buffers, bool compact, int64_t pla
     cg.NBm = cg.two_d ? 1 : cg.NB;
     // tile of NC columns: M * NC * 8 bytes per buffer.  32 KB tiles (NC = 8 at M = 512) let four workgroups share a
     // CU and overlap their load / transform / store phases: 6 % faster than 64 KB tiles, 16 KB tiles (64-byte row
-    // segments) lose 30 %; NFFT_HIP_COL_NC overrides.
+    // segments) lose 30 %.
     int nc = 16;
     const int64_t cap = g.M >= 1024 ? 65536 : 32768;
     while (nc > 1 && (int64_t)g.M * nc * 8 * (two_buffers ? 2 : 1) > cap) nc >>= 1;
@@ -1189,19 +1183,11 @@ ColGeom make_col_geom(const Geom &g, bool two_buffers, bool compact, int64_t pla
     // until the launch has ~64 workgroups
     if (g.dim == 2 && planes > 0)
         while (nc > 4 && ((g.N / 2 + 1 + nc - 1) / nc) * planes < 64) nc >>= 1;
-    if (const char *env = std::getenv("NFFT_HIP_COL_NC")) {
-        const int v = std::atoi(env);
-        if ((v == 4 || v == 8 || v == 16) && (int64_t)g.M * v * 8 * (two_buffers ? 2 : 1) <= 131072) nc = v;
-    }
     cg.NC = nc;
     cg.logNC = 0;
     while ((1 << cg.logNC) < nc) ++cg.logNC;
     cg.param = 1.047197551196597746f * (float)g.m / ((float)g.N * (float)g.N);
-    static const bool pairs_off = [] {
-        const char *env = std::getenv("NFFT_HIP_COL_XCD");
-        return env && env[0] == '0';
-    }();
-    cg.TG = pairs_off || nc >= 16 ? 1 : 16 / nc;
+    cg.TG = nc >= 16 ? 1 : 16 / nc;
     return cg;
 }
 
@@ -1229,12 +1215,8 @@ void allow_lds(K kernel, size_t bytes)
 bool colfft_supported(const Geom &g)
 {
     // 3-D, and (round 4) 2-D grids the own row passes take: row pass + ONE column pass with the roll-off instead of rocFFT's
-    // two kernels + the roll-off kernel (three launches per direction -> two; NFFT_HIP_COLFFT_2D=0: rocFFT as before)
-    static const bool no2d = [] {
-        const char *env = std::getenv("NFFT_HIP_COLFFT_2D");
-        return env && env[0] == '0';
-    }();
-    if (g.dim == 2) return !no2d && g.M >= 128 && g.M <= 1024 && (g.M & (g.M - 1)) == 0;
+    // two kernels + the roll-off kernel (three launches per direction -> two)
+    if (g.dim == 2) return g.M >= 128 && g.M <= 1024 && (g.M & (g.M - 1)) == 0;
     return g.dim == 3 && g.M >= 16 && g.M <= 1024 && (g.M & (g.M - 1)) == 0;
 }
 
@@ -1246,20 +1228,15 @@ int64_t colfft_scratch_bytes(const Geom &g, int64_t nplanes)
 }
 
 // Calls f(log2 M, log2 NC) as integral constants for the sizes the column kernels are specialised for -- 512^3 grids
-// with their default tile widths (one and two tile buffers) -- and f(0, 0), the run-time version, otherwise
-// (NFFT_HIP_COL_GENERIC=1: always).  Compile-time sizes take 6-14 % off a pass at M = 512 (C3: 110 / 90 / 110 / 120 ->
-// 103 / 84 / 98 / 103 us); the same specialisation for 256^3 grids measured 6 % SLOWER (C4-share column passes 16.55 ->
-// 17.5 ms) and is not instantiated.
+// with their default tile widths (one and two tile buffers) -- and f(0, 0), the run-time version, otherwise.
+// Compile-time sizes take 6-14 % off a pass at M = 512 (C3: 110 / 90 / 110 / 120 -> 103 / 84 / 98 / 103 us); the same
+// specialisation for 256^3 grids measured 6 % SLOWER (C4-share column passes 16.55 -> 17.5 ms) and is not instantiated.
 template <typename F>
 static void col_dispatch(const ColGeom &cg, F &&f)
 {
-    static const bool generic = [] {
-        const char *env = std::getenv("NFFT_HIP_COL_GENERIC");
-        return env && env[0] == '1';
-    }();
     using std::integral_constant;
-    if (!generic && cg.logM == 9 && cg.logNC == 3) return f(integral_constant<int, 9>{}, integral_constant<int, 3>{});
-    if (!generic && cg.logM == 9 && cg.logNC == 2) return f(integral_constant<int, 9>{}, integral_constant<int, 2>{});
+    if (cg.logM == 9 && cg.logNC == 3) return f(integral_constant<int, 9>{}, integral_constant<int, 3>{});
+    if (cg.logM == 9 && cg.logNC == 2) return f(integral_constant<int, 9>{}, integral_constant<int, 2>{});
     return f(integral_constant<int, 0>{}, integral_constant<int, 0>{});
 }
 

@@ -18,10 +18,9 @@
 // Blocks are handled in groups of kIcBlocks (what fits the LDS); a group's plane sweep runs from the first
 // point's window to the last one's, so a sparse item (config C4: 6.5 points per slab and pencil) sweeps its
 // planes ~1.2 times, a dense one more often -- the kernel is chosen for multi-column problems, where the column
-// sharing pays for that (api.hip gather_any).
+// sharing pays for that (api.hip plan_route).
 // The results leave through LDS: 8 columns of a point are 32 contiguous bytes of y.
 #include <algorithm>
-#include <cstdlib>
 
 #include "common.h"
 #include "kernels.h"
@@ -314,15 +313,7 @@ interp_cols_kernel(const Geom g, const int *__restrict__ tile_offsets,
 
 } // namespace
 
-// Worth it from 4 real columns up (half the waves busy); 3-D wide tiling only.
-bool interp_cols_supported(const Geom &g, int64_t Cr)
-{
-    static const bool off = [] {
-        const char *env = std::getenv("NFFT_HIP_GATHER");
-        return env && (env[0] == 'l' || env[0] == 'm');  // lds: lane-per-point kernel, mfma: plane-ring kernel
-    }();
-    return !off && g.dim == 3 && g.wide && !g.owned && Cr >= 4;
-}
+bool interp_cols_supported(const Geom &g) { return g.dim == 3 && g.wide && !g.owned; }
 
 template <int W>
 static int launch_ic_t(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,

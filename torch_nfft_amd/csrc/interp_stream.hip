@@ -26,7 +26,6 @@
 // returns NFFT_HIP_EKERNEL instead of handing out the unfinished rows as a result.
 #include <algorithm>
 #include <climits>
-#include <cstdlib>
 
 #include "common.h"
 #include "kernels.h"
@@ -516,14 +515,7 @@ bool interp_stream_pays(const Geom &g, const PlanLayout &L, int64_t n)
     return stream_items(n, nsets, device_cu_count(), g.M);
 }
 
-bool interp_stream_supported(const Geom &g)
-{
-    static const bool off = [] {
-        const char *env = std::getenv("NFFT_HIP_GATHER");
-        return env && (env[0] == 'l' || env[0] == 'm');  // lds: lane-per-point kernel, mfma: plane-ring kernel in lock step
-    }();
-    return !off && g.dim == 3 && g.wide && !g.owned && g.W <= 16;
-}
+bool interp_stream_supported(const Geom &g) { return g.dim == 3 && g.wide && !g.owned && g.W <= 16; }
 
 template <int W, int NG>
 static int launch_is_t(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,

@@ -42,7 +42,7 @@ int launch_spread_mfma(const Geom &g, const PlanLayout &L, const void *plan, con
 // interp.hip: yr[perm[slot] * Cr + cr] = sum over taps of grid[p, ...]
 int launch_interp(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                   int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream);
-// matrix-core gather for the wide 3-D tiling (interp_mfma.hip); NFFT_HIP_GATHER=lds keeps launch_interp
+// matrix-core gather for the wide 3-D tiling (interp_mfma.hip)
 bool interp_mfma_supported(const Geom &g);
 int launch_interp_mfma(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                        int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream);
@@ -54,7 +54,7 @@ int launch_interp_stream(const Geom &g, const PlanLayout &L, const void *plan, c
                          int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream);
 // several coefficient columns per workgroup, one wave per column (interp_cols.hip): the point-side operands are built
 // once for 8 columns, each wave streams its own column's planes from global memory
-bool interp_cols_supported(const Geom &g, int64_t Cr);
+bool interp_cols_supported(const Geom &g);
 int launch_interp_cols(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                        int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream);
 

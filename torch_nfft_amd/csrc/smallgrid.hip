@@ -20,29 +20,18 @@ namespace nfft {
 
 constexpr int kSgThreads = 1024;          // (16 waves: the LDS atomics and reads of the tap loops are latency-bound with fewer)
 constexpr int kSgMaxCells = 4096;         // grid cells: 16 B of fp64 sums + 8 B of FFT buffer per cell (+ twiddles)
-// average window taps per point set: a set is ONE workgroup's loop, ~0.35 ns per tap and direction (LDS atomics of a single
-// CU) on top of ~25 us per adjoint + forward pair, against 80-145 us for the general path on these sizes -- measured
-// break-even ~10^5 taps (profiles/r03_experiments.md).  8e4 since round 4: the reference's own test shape (test/test_adjoint.py:
-// 2-D N = 16, m = 3, 1 000 points per set = 64 000 taps) sat just above the first limit of 6e4 and took the general path
-// (0.122 ms against 0.07 here, profiles/r04_experiments.md)
-constexpr int64_t kSgMaxSetTaps = 80000;
 
+// (whether the path pays -- window taps per point set -- is decided with the route: api.hip small_grid_route)
 bool small_grid_supported(const nfft_hip_problem *p)
 {
-    static const bool off = [] {
-        const char *env = std::getenv("NFFT_HIP_SMALL_GRID");
-        return env && env[0] == '0';
-    }();
-    if (off || !p || p->dim < 1 || p->dim > 3) return false;
+    if (!p || p->dim < 1 || p->dim > 3) return false;
     const int64_t M = 2 * p->N;
     if (M < 4 || (M & (M - 1)) != 0) return false;
-    int64_t cells = 1, taps = 1;
-    for (int k = 0; k < p->dim; ++k) { cells *= M; taps *= 2 * p->m + 2; }
+    int64_t cells = 1;
+    for (int k = 0; k < p->dim; ++k) cells *= M;
     if (cells > kSgMaxCells) return false;
     if (p->m < 1 || p->m > 8 || 2 * p->m + 2 > M) return false;
-    if (p->batch_size > 65535) return false;  // (point sets are the y dimension of the launch)
-    const int64_t sets = p->batch_size < 1 ? 1 : (p->batch_size > 8 ? 8 : p->batch_size);
-    return p->num_points * taps <= kSgMaxSetTaps * sets;
+    return p->batch_size <= 65535;  // (point sets are the y dimension of the launch)
 }
 
 namespace {
