@@ -116,6 +116,22 @@ int nfft_hip_adjoint_planned(const nfft_hip_problem *p, const void *plan, const 
 int nfft_hip_forward_planned(const nfft_hip_problem *p, const void *plan, const void *xhat, int x_is_complex,
                              int real_output, void *y, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Gradient of a forward transform with respect to the points (no counterpart: the reference has no gradient w.r.t. pos).
+ * With Fr[i, cr] the real columns of y = nfft_hip_forward(xhat) at the points (Cr = C with real_output, else 2C:
+ * re, im interleaved),
+ *     dpos[i, a] = sum_cr w[i, cr] * d Fr[i, cr] / d pos[i, a],
+ * evaluated the way the transform itself is: the same deconvolved, FFT'd grid, gathered with the derivative of the
+ * window.  Autograd uses it for both transforms: for y = forward(xhat, pos), xhat and w = the real view of dy; for
+ * y = adjoint(x, pos), xhat = dy with real_output = !x_is_complex and w = the real view of x.
+ *   w     float32 [n, Cr] in caller order;  dpos  float32 [n, dim], every element is written
+ * Always runs on a point plan (nfft_hip_plan_points, same problem), also for problems whose transforms need none
+ * (nfft_hip_plan_needed == 0).  Deterministic: no atomics, the same inputs give bitwise the same dpos.
+ * Workspace: the forward transform's plus, when Cr > 1, Cr * n * dim floats of per-plane partial gradients. */
+int64_t nfft_hip_forward_grad_workspace_bytes(const nfft_hip_problem *p, int x_is_complex, int real_output);
+int nfft_hip_forward_grad_points_planned(const nfft_hip_problem *p, const void *plan, const void *xhat,
+                                         int x_is_complex, int real_output, const float *w, float *dpos,
+                                         void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- stage-level entry points (used by the parity tests and by bench.py to time
  * the spreading kernel on its own; the two calls above are built from them) ---- */
 

@@ -26,6 +26,8 @@ SYMBOLS = (
     "nfft_hip_forward",
     "nfft_hip_adjoint_planned",
     "nfft_hip_forward_planned",
+    "nfft_hip_forward_grad_workspace_bytes",
+    "nfft_hip_forward_grad_points_planned",
     "nfft_hip_plan_bytes",
     "nfft_hip_plan_points",
     "nfft_hip_plan_verify",
@@ -102,6 +104,10 @@ def load():
     for f in (lib.nfft_hip_adjoint_planned, lib.nfft_hip_forward_planned):
         f.argtypes = [P, vp, vp, ci, ci, vp, vp, i64, vp]
         f.restype = ci
+    lib.nfft_hip_forward_grad_workspace_bytes.argtypes = [P, ci, ci]
+    lib.nfft_hip_forward_grad_workspace_bytes.restype = i64
+    lib.nfft_hip_forward_grad_points_planned.argtypes = [P, vp, vp, ci, ci, vp, vp, vp, i64, vp]
+    lib.nfft_hip_forward_grad_points_planned.restype = ci
     lib.nfft_hip_plan_needed.argtypes = [P]
     lib.nfft_hip_plan_needed.restype = ci
     lib.nfft_hip_plan_bytes.argtypes = [P]

@@ -827,6 +827,69 @@ int nfft_hip_forward_planned(const nfft_hip_problem *p, const void *plan, const 
     return forward_impl(p, nullptr, nullptr, plan, xhat, x_is_complex, real_output, y, workspace, workspace_bytes, stream);
 }
 
+// ---- gradient with respect to the points ---------------------------------------------------------
+namespace {
+// Workspace of nfft_hip_forward_grad_points: the forward transform's (its route, unchanged) and, with two or more real
+// planes per point set, the per-plane partial gradients [Cr, n, dim] that grad_reduce sums in plane order.
+int forward_grad_route(const nfft_hip_problem *p, int real_output, Route &r, int64_t &off_part, int64_t &total)
+{
+    if (int rc = make_route(p, real_output ? 1 : 2, false, r)) return rc;
+    off_part = r.total - 256;  // (make_route's total is its aligned end + 256 bytes of slack for the base alignment)
+    const int64_t part = r.Cr > 1 ? align_up(r.Cr * r.n * p->dim * 4, 256) : 0;
+    total = off_part + part + 256;
+    return 0;
+}
+} // namespace
+
+int64_t nfft_hip_forward_grad_workspace_bytes(const nfft_hip_problem *p, int x_is_complex, int real_output)
+{
+    (void)x_is_complex;
+    if (validate(p)) return -1;
+    Route r;
+    int64_t off_part = 0, total = 0;
+    if (forward_grad_route(p, real_output, r, off_part, total)) return -1;
+    return total;
+}
+
+int nfft_hip_forward_grad_points_planned(const nfft_hip_problem *p, const void *plan, const void *xhat, int x_is_complex,
+                                         int real_output, const float *w, float *dpos, void *workspace,
+                                         int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate(p)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (p->num_points > 0 && p->num_columns > 0) {
+        // a missing workspace, or one below the partial gradients plus one chunk of grid planes, is refused before the
+        // route makes its rocFFT plans
+        const int64_t Cr = p->num_columns * (real_output ? 1 : 2);
+        const int64_t least = (Cr > 1 ? Cr * p->num_points * p->dim * 4 : 0) + problem_geom(p).cells * 4 * (real_output ? 1 : 2);
+        if (!workspace || workspace_bytes < least) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    }
+    Route r;
+    int64_t off_part = 0, total = 0;
+    if (int rc = forward_grad_route(p, real_output, r, off_part, total)) return rc;
+    if (r.n == 0) return 0;
+    if (!dpos) { set_error("Input mismatch: dpos is null"); return NFFT_HIP_EINVAL; }
+    if (r.total_planes == 0) {  // no columns: the transform is empty and so is its gradient
+        NFFT_HIP_CHECK(hipMemsetAsync(dpos, 0, (size_t)(r.n * p->dim * 4), s));
+        return 0;
+    }
+    if (!plan || !xhat || !w) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    if (!workspace || workspace_bytes < total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    float *grid = (float *)(ws + r.off_grid);
+    float2 *spec = (float2 *)(ws + r.off_spec);
+    float *part = r.Cr > 1 ? (float *)(ws + off_part) : dpos;  // one plane per set: the kernel writes dpos itself
+    for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes) {
+        const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
+        if (int rc = fft_forward_chunk(r, ws, xhat, x_is_complex, real_output, p0, np, grid, spec, s)) return rc;
+        StageTimer t(kStageInterp, s);
+        if (int rc = launch_interp_grad(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, w, part, s)) return rc;
+    }
+    if (r.Cr > 1) return launch_grad_reduce(part, r.n * p->dim, r.Cr, dpos, s);
+    return 0;
+}
+
 // ---- fast summation -------------------------------------------------------------------------
 namespace {
 struct FastsumCarve {

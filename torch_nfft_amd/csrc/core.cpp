@@ -413,6 +413,44 @@ at::Tensor nfft_forward(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> 
     return y;
 }
 
+// not in the reference: the gradient of nfft_forward(pos, x, batch, m, real_output) with respect to pos, weighted by w
+// [n, Cr] (the real view of the upstream gradient, or of the adjoint's input: include/nfft_hip.h
+// nfft_hip_forward_grad_points_planned).  Same checks and the same problem as the transform, so the plan the forward
+// pass cached is reused; always planned.  Returns dpos [n, dim] float32.
+at::Tensor nfft_forward_grad_points(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch, int64_t m,
+                                    int64_t real_output, at::Tensor w)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_forward_grad_points is only implemented for GPU tensors");
+    const Points p = check_points(pos, opt_batch, "(*out_batch)");
+    const bool real_input = real_dtype(x);
+    CHECK_INPUT(x.dim() >= p.dim + 1);
+    CHECK_INPUT(x.size(0) == p.B);
+    CHECK_INPUT(x.device() == pos.device());
+    const int64_t N = x.size(1);
+    CHECK_INPUT(N >= 2);
+    for (int d = 2; d <= p.dim; ++d) CHECK_INPUT(x.size(d) == N);
+    int64_t C = 1;
+    for (int64_t d = p.dim + 1; d < x.dim(); ++d) C *= x.size(d);
+    const int64_t Cr = real_output ? C : 2 * C;
+    CHECK_INPUT(w.is_cuda() && w.device() == pos.device());
+    CHECK_INPUT(w.scalar_type() == at::kFloat);
+    CHECK_INPUT(w.numel() == p.n * Cr);
+    at::Tensor dpos = at::empty({p.n, (int64_t)p.dim}, pos.options());
+    if (p.n == 0) return dpos;
+    if (C == 0) return dpos.zero_();
+    const at::Tensor xc = x.contiguous(), wc = w.contiguous();
+    const nfft_hip_problem q = problem(p, C, N, m);
+    c10::DeviceGuard guard(x.device());
+    const int64_t ws_bytes = nfft_hip_forward_grad_workspace_bytes(&q, real_input ? 0 : 1, real_output ? 1 : 0);
+    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
+    at::Tensor ws = byte_buffer(ws_bytes, x);
+    const at::Tensor plan = get_plan(p, q);
+    check_rc(nfft_hip_forward_grad_points_planned(&q, plan.data_ptr(), xc.data_ptr(), real_input ? 0 : 1,
+                                                  real_output ? 1 : 0, wc.data_ptr<float>(), dpos.data_ptr<float>(),
+                                                  ws.data_ptr(), ws_bytes, stream_of(x)));
+    return dpos;
+}
+
 // torch_nfft::nfft_fastsum (csrc/core.cpp:108-121; driver core_cuda.cu:535-852)
 at::Tensor nfft_fastsum(at::Tensor sources, at::Tensor targets, at::Tensor x, at::Tensor coeffs,
                         c10::optional<at::Tensor> opt_source_batch, c10::optional<at::Tensor> opt_target_batch, int64_t m)
@@ -563,4 +601,7 @@ TORCH_LIBRARY(torch_nfft, m)
     m.def("_plan_cache(int action) -> int", &plan_cache_control);
     // not in the reference: device-side fault reports (torch_nfft_amd.ops.check_status)
     m.def("_check_status(int synchronize) -> int", &check_status);
+    // not in the reference: gradient of nfft_forward with respect to the points (autograd of both transforms)
+    m.def("_nfft_forward_grad_points(Tensor pos, Tensor x, Tensor? batch, int m, int real_output, Tensor w) -> Tensor",
+          &nfft_forward_grad_points);
 }

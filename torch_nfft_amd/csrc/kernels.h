@@ -42,6 +42,13 @@ int launch_spread_mfma(const Geom &g, const PlanLayout &L, const void *plan, con
 // interp.hip: yr[perm[slot] * Cr + cr] = sum over taps of grid[p, ...]
 int launch_interp(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                   int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream);
+// interp_grad.hip: gradient gather of the forward transform with respect to the points, on the halo plan of any tiling.
+// part[(cr * n + i) * dim + u] = w[i * Cr + cr] * d/dpos[i, u] (interpolation of plane b * Cr + cr at point i); every
+// (cr, i) of the planes [plane0, plane0 + nplanes) is written once.  grad_reduce: dpos[e] = sum_cr part[cr * len + e] in
+// plane order (len = n * dim).
+int launch_interp_grad(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
+                       int64_t plane0, int64_t nplanes, const float *w, float *part, hipStream_t stream);
+int launch_grad_reduce(const float *part, int64_t len, int64_t Cr, float *dpos, hipStream_t stream);
 // matrix-core gather for the wide 3-D tiling (interp_mfma.hip)
 bool interp_mfma_supported(const Geom &g);
 int launch_interp_mfma(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,

@@ -1,28 +1,48 @@
 """Public API: ``nfft_adjoint`` / ``nfft_forward`` / ``nfft_fastsum`` with the reference's signatures and
 autograd behaviour (reference: ``torch_nfft/nfft.py:11-179``).
 
-Adjoint and forward are each other's transposes, so each one's backward is the other
-(``nfft.py:22-28, 48-54``); there is no gradient w.r.t. the points.
+Adjoint and forward are each other's transposes, so each one's backward w.r.t. the coefficients is the other
+(``nfft.py:22-28, 48-54``).  Not in the reference: both transforms are also differentiable w.r.t. the points ``pos``.
+Both gradients come from one native gather of the window's derivative (``ops.nfft_forward_grad_points``):
+``y = nfft_forward(x, pos)`` weights the derivative of its own output by ``dy``; ``y = nfft_adjoint(x, pos)`` gives
+``dpos_i = Re(x_i conj(grad F(pos_i)))`` with ``F = nfft_forward(dy)``.  ``batch`` gets no gradient, and double backward
+(``create_graph=True``) is not supported.
 """
 import torch
 
 from . import ops
 
 
+def _real_columns(t, n):
+    """[n, Cr] float32 view of a coefficient array: the real columns, or re / im interleaved for complex data."""
+    t = t.contiguous()
+    return (torch.view_as_real(t) if t.is_complex() else t).reshape(n, -1)
+
+
 class NfftAdjointFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, pos, batch, bandwidth, cutoff, real_output):
         y = ops.nfft_adjoint(pos, x, batch, bandwidth, cutoff, 1 if real_output else 0)
-        ctx.save_for_backward(pos, batch)
+        ctx.pos_grad = ctx.needs_input_grad[1]
+        if ctx.pos_grad:  # (x only for the gradient w.r.t. the points)
+            ctx.save_for_backward(pos, batch, x)
+        else:
+            ctx.save_for_backward(pos, batch)
         ctx.cutoff = cutoff
         ctx.real_input = not x.is_complex()
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        pos, batch = ctx.saved_tensors
-        dx = ops.nfft_forward(pos, dy, batch, ctx.cutoff, 1 if ctx.real_input else 0)
-        return dx, None, None, None, None, None
+        pos, batch = ctx.saved_tensors[:2]
+        dx = dpos = None
+        if ctx.needs_input_grad[0] or not ctx.pos_grad:
+            dx = ops.nfft_forward(pos, dy, batch, ctx.cutoff, 1 if ctx.real_input else 0)
+        if ctx.pos_grad:
+            x = ctx.saved_tensors[2]
+            w = _real_columns(x, pos.size(0))
+            dpos = ops.nfft_forward_grad_points(pos, dy, batch, ctx.cutoff, 1 if ctx.real_input else 0, w)
+        return dx, dpos, None, None, None, None
 
 
 def nfft_adjoint(x, pos, batch=None, bandwidth=16, cutoff=3, real_output=False):
@@ -34,17 +54,28 @@ class NfftForwardFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, pos, batch, cutoff, real_output):
         y = ops.nfft_forward(pos, x, batch, cutoff, 1 if real_output else 0)
-        ctx.save_for_backward(pos, batch)
+        ctx.pos_grad = ctx.needs_input_grad[1]
+        if ctx.pos_grad:  # (x only for the gradient w.r.t. the points)
+            ctx.save_for_backward(pos, batch, x)
+        else:
+            ctx.save_for_backward(pos, batch)
         ctx.cutoff = cutoff
         ctx.bandwidth = x.size(1)
         ctx.real_input = not x.is_complex()
+        ctx.real_output = bool(real_output)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        pos, batch = ctx.saved_tensors
-        dx = ops.nfft_adjoint(pos, dy, batch, ctx.bandwidth, ctx.cutoff, 1 if ctx.real_input else 0)
-        return dx, None, None, None, None
+        pos, batch = ctx.saved_tensors[:2]
+        dx = dpos = None
+        if ctx.needs_input_grad[0] or not ctx.pos_grad:
+            dx = ops.nfft_adjoint(pos, dy, batch, ctx.bandwidth, ctx.cutoff, 1 if ctx.real_input else 0)
+        if ctx.pos_grad:
+            x = ctx.saved_tensors[2]
+            w = _real_columns(dy, pos.size(0))
+            dpos = ops.nfft_forward_grad_points(pos, x, batch, ctx.cutoff, 1 if ctx.real_output else 0, w)
+        return dx, dpos, None, None, None
 
 
 def nfft_forward(x, pos, batch=None, cutoff=3, real_output=False):

@@ -62,6 +62,15 @@ def nfft_forward(pos, x, batch, m, real_output):
     return _ops.nfft_forward(pos, x, batch, int(m), 1 if real_output else 0)
 
 
+def nfft_forward_grad_points(pos, x, batch, m, real_output, w):
+    """torch_nfft::_nfft_forward_grad_points(Tensor pos, Tensor x, Tensor? batch, int m, int real_output, Tensor w)
+    -> Tensor [n, dim] (not in the reference): ``dpos[i, a] = sum_cr w[i, cr] d Fr[i, cr] / d pos[i, a]``, where ``Fr``
+    are the real columns of ``nfft_forward(pos, x, batch, m, real_output)`` (``2 C`` interleaved re / im without
+    ``real_output``) and ``w`` is ``[n, Cr]`` float32.  One native call (``nfft_hip_forward_grad_points_planned``) on the
+    cached point plan."""
+    return _ops._nfft_forward_grad_points(pos, x, batch, int(m), 1 if real_output else 0, w)
+
+
 def nfft_fastsum(sources, targets, x, coeffs, source_batch, target_batch, m):
     """torch_nfft::nfft_fastsum(Tensor sources, Tensor targets, Tensor x, Tensor coeffs, Tensor? source_batch,
     Tensor? target_batch, int m) -> Tensor   (csrc/core.cpp:108-121; driver core_cuda.cu:535-852).
