@@ -131,6 +131,14 @@ int64_t nfft_hip_forward_grad_workspace_bytes(const nfft_hip_problem *p, int x_i
 int nfft_hip_forward_grad_points_planned(const nfft_hip_problem *p, const void *plan, const void *xhat,
                                          int x_is_complex, int real_output, const float *w, float *dpos,
                                          void *workspace, int64_t workspace_bytes, void *stream);
+/* The forward transform and its weighted point gradient in one pass: y as nfft_hip_forward_planned writes it (same layout,
+ * same normalisation; [n, C] float32 with real_output, else complex64) and dpos as nfft_hip_forward_grad_points_planned,
+ * from one gather that stores the value it has in registers anyway.  Same workspace
+ * (nfft_hip_forward_grad_workspace_bytes).  y agrees with the forward transform's to rounding, not bit for bit: the
+ * transform may gather with another kernel. */
+int nfft_hip_forward_value_grad_points_planned(const nfft_hip_problem *p, const void *plan, const void *xhat,
+                                               int x_is_complex, int real_output, const float *w, void *y, float *dpos,
+                                               void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---- stage-level entry points (used by the parity tests and by bench.py to time
  * the spreading kernel on its own; the two calls above are built from them) ---- */
@@ -203,6 +211,38 @@ int nfft_hip_fastsum(const nfft_hip_problem *src, const float *sources, const in
 int nfft_hip_fastsum_planned(const nfft_hip_problem *src, const void *source_plan, const nfft_hip_problem *tgt,
                              const void *target_plan, const void *x, int x_is_complex, const void *coeffs,
                              int coeffs_are_complex, void *y, void *workspace, int64_t workspace_bytes, void *stream);
+/* The same fast summation that also returns its band spectrum band = coeffs * A_s(x), [B, N^dim, C] complex64 with the
+ * coefficients multiplied in (y = forward_t(band)): what the gradient with respect to the targets needs.  Same workspace
+ * (nfft_hip_fastsum_workspace_bytes), same route and the same computation of y as nfft_hip_fastsum[_planned] (equal up to
+ * the order of the spreading atomics, which varies from call to call on most routes); band is written whenever y is (no
+ * targets or no columns: neither is). */
+int nfft_hip_fastsum_band(const nfft_hip_problem *src, const float *sources, const int64_t *source_batch,
+                          const nfft_hip_problem *tgt, const float *targets, const int64_t *target_batch, const void *x,
+                          int x_is_complex, const void *coeffs, int coeffs_are_complex, void *y, void *band,
+                          void *workspace, int64_t workspace_bytes, void *stream);
+int nfft_hip_fastsum_band_planned(const nfft_hip_problem *src, const void *source_plan, const nfft_hip_problem *tgt,
+                                  const void *target_plan, const void *x, int x_is_complex, const void *coeffs,
+                                  int coeffs_are_complex, void *y, void *band, void *workspace, int64_t workspace_bytes,
+                                  void *stream);
+
+/* Backward of the fast summation y = fastsum(x, c, sources, targets) (no reference counterpart), with dy the upstream
+ * gradient in y's layout and torch's convention, and the real views of DESIGN.md section 7a:
+ *   dtargets[i] = sum_cr dy[i, cr] d Fr[i, cr] / d t_i,  F = forward_t(band)            (band: nfft_hip_fastsum_band's)
+ *   dsources[j] = Re(conj(x_j) grad H(s_j)),             H = forward_s(coeffs * A_t(dy))
+ *   dx          = H(s_j) (its real part when x is real)
+ * `coeffs` is the array of the sources' grid: conj(c) for the gradient of the forward pass with coefficients c (c itself
+ * when c is real; then dx is the forward pass's x gradient, the swapped fastsum, to rounding).  One adjoint at the targets
+ * (the coefficients folded into its roll-off), one forward FFT stage at the sources and one gather -- the value-writing one
+ * when dx is wanted too; one forward FFT stage at the targets and one gradient gather.  Each of dx, dsources, dtargets may
+ * be NULL.  dsources [n_s, dim], dtargets [n_t, dim] float32.  Both problems are treated as NFFT_HIP_POINTS_IN_QUARTER_BALL
+ * and take the forward pass's plans.  No columns or an empty side: zero gradients.  Deterministic (no atomics after the
+ * adjoint's spreading).  Workspace: nfft_hip_fastsum_grad_workspace_bytes. */
+int64_t nfft_hip_fastsum_grad_workspace_bytes(const nfft_hip_problem *src, const nfft_hip_problem *tgt, int x_is_complex);
+int nfft_hip_fastsum_backward_planned(const nfft_hip_problem *src, const void *source_plan, const nfft_hip_problem *tgt,
+                                      const void *target_plan, const void *x, int x_is_complex, const void *dy,
+                                      const void *coeffs, int coeffs_are_complex, const void *band, void *dx,
+                                      float *dsources, float *dtargets, void *workspace, int64_t workspace_bytes,
+                                      void *stream);
 
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.

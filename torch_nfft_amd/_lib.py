@@ -28,6 +28,7 @@ SYMBOLS = (
     "nfft_hip_forward_planned",
     "nfft_hip_forward_grad_workspace_bytes",
     "nfft_hip_forward_grad_points_planned",
+    "nfft_hip_forward_value_grad_points_planned",
     "nfft_hip_plan_bytes",
     "nfft_hip_plan_points",
     "nfft_hip_plan_verify",
@@ -38,6 +39,10 @@ SYMBOLS = (
     "nfft_hip_fastsum_workspace_bytes",
     "nfft_hip_fastsum",
     "nfft_hip_fastsum_planned",
+    "nfft_hip_fastsum_band",
+    "nfft_hip_fastsum_band_planned",
+    "nfft_hip_fastsum_grad_workspace_bytes",
+    "nfft_hip_fastsum_backward_planned",
     "nfft_hip_gaussian_analytic_coeffs",
     "nfft_hip_interpolation_grid",
     "nfft_hip_coeffs_workspace_bytes",
@@ -108,6 +113,8 @@ def load():
     lib.nfft_hip_forward_grad_workspace_bytes.restype = i64
     lib.nfft_hip_forward_grad_points_planned.argtypes = [P, vp, vp, ci, ci, vp, vp, vp, i64, vp]
     lib.nfft_hip_forward_grad_points_planned.restype = ci
+    lib.nfft_hip_forward_value_grad_points_planned.argtypes = [P, vp, vp, ci, ci, vp, vp, vp, vp, i64, vp]
+    lib.nfft_hip_forward_value_grad_points_planned.restype = ci
     lib.nfft_hip_plan_needed.argtypes = [P]
     lib.nfft_hip_plan_needed.restype = ci
     lib.nfft_hip_plan_bytes.argtypes = [P]
@@ -130,6 +137,14 @@ def load():
     lib.nfft_hip_fastsum.restype = ci
     lib.nfft_hip_fastsum_planned.argtypes = [P, vp, P, vp, vp, ci, vp, ci, vp, vp, i64, vp]
     lib.nfft_hip_fastsum_planned.restype = ci
+    lib.nfft_hip_fastsum_band.argtypes = [P, vp, vp, P, vp, vp, vp, ci, vp, ci, vp, vp, vp, i64, vp]
+    lib.nfft_hip_fastsum_band.restype = ci
+    lib.nfft_hip_fastsum_band_planned.argtypes = [P, vp, P, vp, vp, ci, vp, ci, vp, vp, vp, i64, vp]
+    lib.nfft_hip_fastsum_band_planned.restype = ci
+    lib.nfft_hip_fastsum_grad_workspace_bytes.argtypes = [P, P, ci]
+    lib.nfft_hip_fastsum_grad_workspace_bytes.restype = i64
+    lib.nfft_hip_fastsum_backward_planned.argtypes = [P, vp, P, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, i64, vp]
+    lib.nfft_hip_fastsum_backward_planned.restype = ci
     lib.nfft_hip_gaussian_analytic_coeffs.argtypes = [ctypes.c_double, i64, ctypes.c_int32, vp, vp]
     lib.nfft_hip_gaussian_analytic_coeffs.restype = ci
     lib.nfft_hip_interpolation_grid.argtypes = [i64, ctypes.c_int32, ci, vp, vp]

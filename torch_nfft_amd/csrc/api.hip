@@ -851,13 +851,14 @@ int64_t nfft_hip_forward_grad_workspace_bytes(const nfft_hip_problem *p, int x_i
     return total;
 }
 
-int nfft_hip_forward_grad_points_planned(const nfft_hip_problem *p, const void *plan, const void *xhat, int x_is_complex,
-                                         int real_output, const float *w, float *dpos, void *workspace,
-                                         int64_t workspace_bytes, void *stream)
+namespace {
+// The weighted gradient gather of a forward transform on its point plan; y non-null: the value-writing gather, which also
+// stores the transform itself (nfft_hip_forward's layout).
+int forward_grad_impl(const nfft_hip_problem *p, const void *plan, const void *xhat, int x_is_complex, int real_output,
+                      const float *w, float *y, float *dpos, void *workspace, int64_t workspace_bytes, hipStream_t s)
 {
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate(p)) return rc;
-    hipStream_t s = (hipStream_t)stream;
     if (p->num_points > 0 && p->num_columns > 0) {
         // a missing workspace, or one below the partial gradients plus one chunk of grid planes, is refused before the
         // route makes its rocFFT plans
@@ -884,18 +885,47 @@ int nfft_hip_forward_grad_points_planned(const nfft_hip_problem *p, const void *
         const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
         if (int rc = fft_forward_chunk(r, ws, xhat, x_is_complex, real_output, p0, np, grid, spec, s)) return rc;
         StageTimer t(kStageInterp, s);
-        if (int rc = launch_interp_grad(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, w, part, s)) return rc;
+        if (y) {
+            if (int rc = launch_interp_value_grad(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, w, part, y, s)) return rc;
+        } else {
+            if (int rc = launch_interp_grad(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, w, part, s)) return rc;
+        }
     }
     if (r.Cr > 1) return launch_grad_reduce(part, r.n * p->dim, r.Cr, dpos, s);
     return 0;
+}
+} // namespace
+
+int nfft_hip_forward_grad_points_planned(const nfft_hip_problem *p, const void *plan, const void *xhat, int x_is_complex,
+                                         int real_output, const float *w, float *dpos, void *workspace,
+                                         int64_t workspace_bytes, void *stream)
+{
+    return forward_grad_impl(p, plan, xhat, x_is_complex, real_output, w, nullptr, dpos, workspace, workspace_bytes,
+                             (hipStream_t)stream);
+}
+
+int nfft_hip_forward_value_grad_points_planned(const nfft_hip_problem *p, const void *plan, const void *xhat,
+                                               int x_is_complex, int real_output, const float *w, void *y, float *dpos,
+                                               void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!y && p && p->num_points > 0 && p->num_columns > 0) { set_error("Input mismatch: y is null"); return NFFT_HIP_EINVAL; }
+    return forward_grad_impl(p, plan, xhat, x_is_complex, real_output, w, (float *)y, dpos, workspace, workspace_bytes,
+                             (hipStream_t)stream);
 }
 
 // ---- fast summation -------------------------------------------------------------------------
 namespace {
 struct FastsumCarve {
     Route src, tgt;  // adjoint at the sources, forward transform at the targets
-    int64_t band_bytes, plan_s, plan_t, inner, off_band, off_plan_s, off_plan_t, off_inner, total;
+    int64_t band_size, band_bytes, plan_s, plan_t, inner, off_band, off_plan_s, off_plan_t, off_inner, total;
 };
+// bytes of a band spectrum [B, N^dim, C] complex64
+int64_t band_size_of(const nfft_hip_problem *p)
+{
+    int64_t band = p->batch_size * p->num_columns * 8;
+    for (int d = 0; d < p->dim; ++d) band *= p->N;
+    return band;
+}
 int fastsum_check(const nfft_hip_problem *src, const nfft_hip_problem *tgt)
 {
     if (int rc = validate(src)) return rc;
@@ -912,9 +942,8 @@ int fastsum_carve(const nfft_hip_problem *src, const nfft_hip_problem *tgt, int 
 {
     if (int rc = make_route(src, x_is_complex ? 2 : 1, true, f.src)) return rc;
     if (int rc = make_route(tgt, x_is_complex ? 2 : 1, false, f.tgt)) return rc;
-    int64_t band = src->batch_size * src->num_columns * 8;
-    for (int d = 0; d < src->dim; ++d) band *= src->N;
-    f.band_bytes = align_up(band, 256);
+    f.band_size = band_size_of(src);
+    f.band_bytes = align_up(f.band_size, 256);
     f.plan_s = own_plans ? align_up(f.src.plan_bytes, 256) : 0;
     f.plan_t = own_plans && !shared_points ? align_up(f.tgt.plan_bytes, 256) : 0;
     f.inner = std::max(f.src.total, f.tgt.total);
@@ -930,7 +959,7 @@ int fastsum_impl(const nfft_hip_problem *src_in, const float *sources, const int
                  const void *source_plan, const nfft_hip_problem *tgt_in, const float *targets,
                  const int64_t *target_batch, const void *target_plan, const void *x, int x_is_complex,
                  const void *coeffs, int coeffs_are_complex, void *y, void *workspace, int64_t workspace_bytes,
-                 void *stream)
+                 void *stream, void *band_out = nullptr)
 {
     if (!src_in || !tgt_in) { set_error("Input mismatch: null problem"); return NFFT_HIP_EINVAL; }
     // fastsum geometry: every point within radius 1/4 (the kernel is only defined there)
@@ -955,9 +984,10 @@ int fastsum_impl(const nfft_hip_problem *src_in, const float *sources, const int
     if (fused1d) {
         if (src->num_points > 0 && !sources) { set_error("Input mismatch: sources is null"); return NFFT_HIP_EINVAL; }
         if (!targets) { set_error("Input mismatch: targets is null"); return NFFT_HIP_EINVAL; }
-        void *band1 = ws + f.off_band;
+        // (band_out: the caller keeps the band spectrum, the carve's band is not used)
+        void *band1 = band_out ? band_out : ws + f.off_band;
         if (src->num_points == 0) {
-            NFFT_HIP_CHECK(hipMemsetAsync(band1, 0, (size_t)f.band_bytes, s));
+            NFFT_HIP_CHECK(hipMemsetAsync(band1, 0, (size_t)f.band_size, s));
         } else {
             if (int rc = adjoint_impl(src, sources, source_batch, nullptr, x, x_is_complex, 0, band1, nullptr, 0, stream,
                                       coeffs, coeffs_are_complex ? 2 : 1)) return rc;
@@ -979,9 +1009,9 @@ int fastsum_impl(const nfft_hip_problem *src_in, const float *sources, const int
             target_plan = ws + f.off_plan_t;
         }
     }
-    void *band = ws + f.off_band;
+    void *band = band_out ? band_out : ws + f.off_band;
     if (src->num_points == 0) {
-        NFFT_HIP_CHECK(hipMemsetAsync(band, 0, (size_t)f.band_bytes, s));
+        NFFT_HIP_CHECK(hipMemsetAsync(band, 0, (size_t)f.band_size, s));
     } else {
         // adjoint of the sources; the kernel's Fourier coefficients are multiplied in by the last spectral pass
         if (int rc = adjoint_impl(src, nullptr, nullptr, source_plan, x, x_is_complex, 0, band, ws + f.off_inner, f.inner,
@@ -1022,6 +1052,139 @@ int nfft_hip_fastsum_planned(const nfft_hip_problem *src, const void *source_pla
     if (!source_plan || !target_plan) { set_error("Input mismatch: plan is null"); return NFFT_HIP_EINVAL; }
     return fastsum_impl(src, nullptr, nullptr, source_plan, tgt, nullptr, nullptr, target_plan, x, x_is_complex, coeffs,
                         coeffs_are_complex, y, workspace, workspace_bytes, stream);
+}
+
+int nfft_hip_fastsum_band(const nfft_hip_problem *src, const float *sources, const int64_t *source_batch,
+                          const nfft_hip_problem *tgt, const float *targets, const int64_t *target_batch, const void *x,
+                          int x_is_complex, const void *coeffs, int coeffs_are_complex, void *y, void *band,
+                          void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!band) { set_error("Input mismatch: band is null"); return NFFT_HIP_EINVAL; }
+    return fastsum_impl(src, sources, source_batch, nullptr, tgt, targets, target_batch, nullptr, x, x_is_complex, coeffs,
+                        coeffs_are_complex, y, workspace, workspace_bytes, stream, band);
+}
+
+int nfft_hip_fastsum_band_planned(const nfft_hip_problem *src, const void *source_plan, const nfft_hip_problem *tgt,
+                                  const void *target_plan, const void *x, int x_is_complex, const void *coeffs,
+                                  int coeffs_are_complex, void *y, void *band, void *workspace, int64_t workspace_bytes,
+                                  void *stream)
+{
+    if (!source_plan || !target_plan) { set_error("Input mismatch: plan is null"); return NFFT_HIP_EINVAL; }
+    if (!band) { set_error("Input mismatch: band is null"); return NFFT_HIP_EINVAL; }
+    return fastsum_impl(src, nullptr, nullptr, source_plan, tgt, nullptr, nullptr, target_plan, x, x_is_complex, coeffs,
+                        coeffs_are_complex, y, workspace, workspace_bytes, stream, band);
+}
+
+} // extern "C"
+
+// ---- gradient of the fast summation with respect to its points ---------------------------------
+namespace {
+// Workspace of the fastsum backward: the grid H of the sources' gather (a band spectrum) and one area that the adjoint at
+// the targets and the two gradient gathers use in turn.
+struct FastsumGradCarve {
+    int64_t band_size, off_h, off_inner, inner, total;
+};
+int fastsum_grad_carve(const nfft_hip_problem *src, const nfft_hip_problem *tgt, int x_is_complex, FastsumGradCarve &f)
+{
+    Route adj;
+    if (int rc = make_route(tgt, x_is_complex ? 2 : 1, true, adj)) return rc;
+    f.inner = adj.total;
+    for (const nfft_hip_problem *p : {src, tgt}) {
+        Route r;
+        int64_t off_part = 0, total = 0;
+        if (int rc = forward_grad_route(p, x_is_complex ? 0 : 1, r, off_part, total)) return rc;
+        f.inner = std::max(f.inner, total);
+    }
+    f.band_size = band_size_of(src);
+    f.off_h = 0;
+    f.off_inner = align_up(f.band_size, 256);
+    f.total = f.off_inner + f.inner + 256;
+    return 0;
+}
+void quarter_ball(const nfft_hip_problem *in, nfft_hip_problem &out)
+{
+    out = *in;
+    out.flags |= NFFT_HIP_POINTS_IN_QUARTER_BALL;
+}
+} // namespace
+
+extern "C" {
+
+int64_t nfft_hip_fastsum_grad_workspace_bytes(const nfft_hip_problem *src, const nfft_hip_problem *tgt, int x_is_complex)
+{
+    if (!src || !tgt) return -1;
+    nfft_hip_problem s, t;
+    quarter_ball(src, s);
+    quarter_ball(tgt, t);
+    if (fastsum_check(&s, &t)) return -1;
+    FastsumGradCarve f;
+    if (fastsum_grad_carve(&s, &t, x_is_complex, f)) return -1;
+    return f.total;
+}
+
+int nfft_hip_fastsum_backward_planned(const nfft_hip_problem *src_in, const void *source_plan,
+                                      const nfft_hip_problem *tgt_in, const void *target_plan, const void *x,
+                                      int x_is_complex, const void *dy, const void *coeffs, int coeffs_are_complex,
+                                      const void *band, void *dx, float *dsources, float *dtargets, void *workspace,
+                                      int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (!src_in || !tgt_in) { set_error("Input mismatch: null problem"); return NFFT_HIP_EINVAL; }
+    // the problems of the forward pass (fastsum_impl), so that its cached plans are the ones used
+    nfft_hip_problem src_q, tgt_q;
+    quarter_ball(src_in, src_q);
+    quarter_ball(tgt_in, tgt_q);
+    const nfft_hip_problem *src = &src_q, *tgt = &tgt_q;
+    if (int rc = fastsum_check(src, tgt)) return rc;
+    if (!source_plan || !target_plan) { set_error("Input mismatch: plan is null"); return NFFT_HIP_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t ns = src->num_points, nt = tgt->num_points, C = src->num_columns;
+    const int real_output = x_is_complex ? 0 : 1;  // as the forward pass: a real x gives a real y
+    const bool sources_side = (dsources || dx) && ns > 0;
+    const bool targets_side = dtargets && nt > 0;
+    const bool work = C > 0 && ns > 0 && nt > 0 && (sources_side || targets_side);
+    if (work) {
+        // refused before any route makes its rocFFT plans: the grid H plus one grid plane per real plane of a column
+        const int64_t least = align_up(band_size_of(src), 256) + problem_geom(src).cells * 4 * (x_is_complex ? 2 : 1);
+        if (!workspace || workspace_bytes < least) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    }
+    // nothing to gather (no columns, or one side empty: the sum and every gradient of it are zero)
+    if (!work) {
+        if (dsources && ns > 0) NFFT_HIP_CHECK(hipMemsetAsync(dsources, 0, (size_t)(ns * src->dim * 4), s));
+        if (dx && ns > 0 && C > 0) NFFT_HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)(ns * C * (x_is_complex ? 8 : 4)), s));
+        if (dtargets && nt > 0) NFFT_HIP_CHECK(hipMemsetAsync(dtargets, 0, (size_t)(nt * tgt->dim * 4), s));
+        return 0;
+    }
+    if (!dy || (sources_side && !coeffs) || (dsources && !x) || (targets_side && !band)) {
+        set_error("Input mismatch: null input");
+        return NFFT_HIP_EINVAL;
+    }
+    FastsumGradCarve f;
+    if (int rc = fastsum_grad_carve(src, tgt, x_is_complex, f)) return rc;
+    if (!workspace || workspace_bytes < f.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    void *inner = ws + f.off_inner;
+    if (sources_side) {
+        // H = coeffs * A_t(dy): the adjoint at the targets with the coefficients folded into its roll-off, as fastsum_impl
+        // does at the sources; then ONE forward FFT stage at the sources and one gather: dsources weighted by x, and with
+        // dx its value -- the swapped fastsum when coeffs is the forward's (real) array
+        void *h = ws + f.off_h;
+        if (int rc = adjoint_impl(tgt, nullptr, nullptr, target_plan, dy, x_is_complex, 0, h, inner, f.inner, stream,
+                                  coeffs, coeffs_are_complex ? 2 : 1)) return rc;
+        if (dsources) {
+            if (int rc = forward_grad_impl(src, source_plan, h, 1, real_output, (const float *)x, (float *)dx, dsources,
+                                           inner, f.inner, s)) return rc;
+        } else {
+            if (int rc = forward_impl(src, nullptr, nullptr, source_plan, h, 1, real_output, dx, inner, f.inner, stream))
+                return rc;
+        }
+    }
+    if (targets_side) {
+        // y = forward_t(band): the gradient gather of the saved band at the targets, weighted by dy
+        if (int rc = forward_grad_impl(tgt, target_plan, band, 1, real_output, (const float *)dy, nullptr, dtargets, inner,
+                                       f.inner, s)) return rc;
+    }
+    return 0;
 }
 
 } // extern "C"

@@ -13,6 +13,7 @@
 #include <torch/library.h>
 
 #include <mutex>
+#include <tuple>
 #include <vector>
 
 #include "../../include/nfft_hip.h"
@@ -451,59 +452,166 @@ at::Tensor nfft_forward_grad_points(at::Tensor pos, at::Tensor x, c10::optional<
     return dpos;
 }
 
-// torch_nfft::nfft_fastsum (csrc/core.cpp:108-121; driver core_cuda.cu:535-852)
-at::Tensor nfft_fastsum(at::Tensor sources, at::Tensor targets, at::Tensor x, at::Tensor coeffs,
-                        c10::optional<at::Tensor> opt_source_batch, c10::optional<at::Tensor> opt_target_batch, int64_t m)
+// Inputs of a fast summation, checked as the reference does (core_cuda.cu:535-590), and its two problems.
+struct Fastsum {
+    Points ps, pt;
+    bool shared, real_coeffs, real_input;
+    int64_t N, C;
+    std::vector<int64_t> out_shape;  // [n_t, *x.shape[1:]]
+    nfft_hip_problem qs, qt;
+};
+
+Fastsum check_fastsum(const at::Tensor &sources, const at::Tensor &targets, const at::Tensor &x, const at::Tensor &coeffs,
+                      const c10::optional<at::Tensor> &opt_source_batch, const c10::optional<at::Tensor> &opt_target_batch,
+                      int64_t m)
 {
     TORCH_CHECK(x.is_cuda(), "torch_nfft.nfft_fastsum is currently only implemented for GPU tensors");
     TORCH_CHECK(coeffs.is_cuda(), "coeffs must be CUDA tensor");
-    const Points ps = check_points(sources, opt_source_batch, "(*out_batch)");
+    Fastsum f;
+    f.ps = check_points(sources, opt_source_batch, "(*out_batch)");
     const bool same_tensor = sources.is_same(targets);
     const bool same_batch = (!opt_source_batch.has_value() && !opt_target_batch.has_value()) ||
                             (opt_source_batch.has_value() && opt_target_batch.has_value() &&
                              opt_source_batch->is_same(*opt_target_batch));
-    const bool shared = same_tensor && same_batch;  // core_cuda.cu:552-564
-    const Points pt = shared ? ps : check_points(targets, opt_target_batch, "(*out_batch)");
-    CHECK_INPUT(pt.dim == ps.dim);
-    CHECK_INPUT(pt.B == ps.B);  // core_cuda.cu:566-568
-    CHECK_INPUT(coeffs.dim() == ps.dim);  // core_cuda.cu:585-590
-    const int64_t N = coeffs.size(0);
-    for (int d = 1; d < ps.dim; ++d) CHECK_INPUT(coeffs.size(d) == N);
-    const bool real_coeffs = real_dtype(coeffs);
-    const bool real_input = real_dtype(x);
+    f.shared = same_tensor && same_batch;  // core_cuda.cu:552-564
+    f.pt = f.shared ? f.ps : check_points(targets, opt_target_batch, "(*out_batch)");
+    CHECK_INPUT(f.pt.dim == f.ps.dim);
+    CHECK_INPUT(f.pt.B == f.ps.B);  // core_cuda.cu:566-568
+    CHECK_INPUT(coeffs.dim() == f.ps.dim);  // core_cuda.cu:585-590
+    f.N = coeffs.size(0);
+    for (int d = 1; d < f.ps.dim; ++d) CHECK_INPUT(coeffs.size(d) == f.N);
+    f.real_coeffs = real_dtype(coeffs);
+    f.real_input = real_dtype(x);
     CHECK_INPUT(x.dim() >= 1);
-    CHECK_INPUT(x.size(0) == ps.n);
+    CHECK_INPUT(x.size(0) == f.ps.n);
     CHECK_INPUT(x.device() == sources.device() && targets.device() == sources.device() &&
                 coeffs.device() == sources.device());
-    int64_t C = 1;
-    std::vector<int64_t> shape{pt.n};
+    f.C = 1;
+    f.out_shape = {f.pt.n};
     for (int64_t d = 1; d < x.dim(); ++d) {
-        C *= x.size(d);
-        shape.push_back(x.size(d));
+        f.C *= x.size(d);
+        f.out_shape.push_back(x.size(d));
     }
-    at::Tensor y = at::empty(shape, x.options());  // same dtype as x (core_cuda.cu:817-821)
+    f.qs = problem(f.ps, f.C, f.N, m, NFFT_HIP_POINTS_IN_QUARTER_BALL);
+    f.qt = problem(f.pt, f.C, f.N, m, NFFT_HIP_POINTS_IN_QUARTER_BALL);
+    return f;
+}
+
+// y = K x, and with `band` the band spectrum coeffs * A_s(x) [B, N^dim, *cols] complex64 (nfft_hip_fastsum_band)
+at::Tensor fastsum_run(const at::Tensor &x, const at::Tensor &coeffs, const Fastsum &f, at::Tensor *band)
+{
+    at::Tensor y = at::empty(f.out_shape, x.options());  // same dtype as x (core_cuda.cu:817-821)
+    if (band) {
+        std::vector<int64_t> shape{f.ps.B};
+        for (int d = 0; d < f.ps.dim; ++d) shape.push_back(f.N);
+        for (size_t d = 1; d < f.out_shape.size(); ++d) shape.push_back(f.out_shape[d]);
+        *band = y.numel() == 0 ? at::zeros(shape, x.options().dtype(at::kComplexFloat))
+                               : at::empty(shape, x.options().dtype(at::kComplexFloat));
+    }
     if (y.numel() == 0) return y;
     const at::Tensor xc = x.contiguous(), cc = coeffs.contiguous();
-    const nfft_hip_problem qs = problem(ps, C, N, m, NFFT_HIP_POINTS_IN_QUARTER_BALL),
-                           qt = problem(pt, C, N, m, NFFT_HIP_POINTS_IN_QUARTER_BALL);
+    void *bp = band ? band->data_ptr() : nullptr;
     c10::DeviceGuard guard(x.device());
-    const bool planned = nfft_hip_plan_needed(&qs) != 0 || nfft_hip_plan_needed(&qt) != 0;
-    const int64_t ws_bytes = nfft_hip_fastsum_workspace_bytes(&qs, &qt, real_input ? 0 : 1, shared ? 1 : 0, planned ? 1 : 0);
+    const bool planned = nfft_hip_plan_needed(&f.qs) != 0 || nfft_hip_plan_needed(&f.qt) != 0;
+    const int64_t ws_bytes = nfft_hip_fastsum_workspace_bytes(&f.qs, &f.qt, f.real_input ? 0 : 1, f.shared ? 1 : 0, planned ? 1 : 0);
     if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
     at::Tensor ws = byte_buffer(ws_bytes, x);
+    const Points &ps = f.ps, &pt = f.pt;
     if (!planned) {  // two fused kernels on the caller's points (1-D, grid in LDS): no plans
-        check_rc(nfft_hip_fastsum(&qs, ps.pos.data_ptr<float>(), ps.batch.defined() ? ps.batch.data_ptr<int64_t>() : nullptr,
-                                  &qt, pt.pos.data_ptr<float>(), pt.batch.defined() ? pt.batch.data_ptr<int64_t>() : nullptr,
-                                  xc.data_ptr(), real_input ? 0 : 1, cc.data_ptr(), real_coeffs ? 0 : 1, y.data_ptr(),
-                                  ws.data_ptr(), ws_bytes, stream_of(x)));
+        const float *spos = ps.pos.data_ptr<float>(), *tpos = pt.pos.data_ptr<float>();
+        const int64_t *sb = ps.batch.defined() ? ps.batch.data_ptr<int64_t>() : nullptr;
+        const int64_t *tb = pt.batch.defined() ? pt.batch.data_ptr<int64_t>() : nullptr;
+        if (band)
+            check_rc(nfft_hip_fastsum_band(&f.qs, spos, sb, &f.qt, tpos, tb, xc.data_ptr(), f.real_input ? 0 : 1,
+                                           cc.data_ptr(), f.real_coeffs ? 0 : 1, y.data_ptr(), bp, ws.data_ptr(), ws_bytes,
+                                           stream_of(x)));
+        else
+            check_rc(nfft_hip_fastsum(&f.qs, spos, sb, &f.qt, tpos, tb, xc.data_ptr(), f.real_input ? 0 : 1, cc.data_ptr(),
+                                      f.real_coeffs ? 0 : 1, y.data_ptr(), ws.data_ptr(), ws_bytes, stream_of(x)));
         return y;
     }
-    const at::Tensor plan_s = get_plan(ps, qs);
-    const at::Tensor plan_t = shared ? plan_s : get_plan(pt, qt);
-    check_rc(nfft_hip_fastsum_planned(&qs, plan_s.data_ptr(), &qt, plan_t.data_ptr(), xc.data_ptr(), real_input ? 0 : 1,
-                                      cc.data_ptr(), real_coeffs ? 0 : 1, y.data_ptr(), ws.data_ptr(), ws_bytes,
-                                      stream_of(x)));
+    const at::Tensor plan_s = get_plan(ps, f.qs);
+    const at::Tensor plan_t = f.shared ? plan_s : get_plan(pt, f.qt);
+    if (band)
+        check_rc(nfft_hip_fastsum_band_planned(&f.qs, plan_s.data_ptr(), &f.qt, plan_t.data_ptr(), xc.data_ptr(),
+                                               f.real_input ? 0 : 1, cc.data_ptr(), f.real_coeffs ? 0 : 1, y.data_ptr(), bp,
+                                               ws.data_ptr(), ws_bytes, stream_of(x)));
+    else
+        check_rc(nfft_hip_fastsum_planned(&f.qs, plan_s.data_ptr(), &f.qt, plan_t.data_ptr(), xc.data_ptr(),
+                                          f.real_input ? 0 : 1, cc.data_ptr(), f.real_coeffs ? 0 : 1, y.data_ptr(),
+                                          ws.data_ptr(), ws_bytes, stream_of(x)));
     return y;
+}
+
+// torch_nfft::nfft_fastsum (csrc/core.cpp:108-121; driver core_cuda.cu:535-852)
+at::Tensor nfft_fastsum(at::Tensor sources, at::Tensor targets, at::Tensor x, at::Tensor coeffs,
+                        c10::optional<at::Tensor> opt_source_batch, c10::optional<at::Tensor> opt_target_batch, int64_t m)
+{
+    const Fastsum f = check_fastsum(sources, targets, x, coeffs, opt_source_batch, opt_target_batch, m);
+    return fastsum_run(x, coeffs, f, nullptr);
+}
+
+// not in the reference: nfft_fastsum that also returns its band spectrum coeffs * A_s(x) [B, N^dim, *x.shape[1:]]
+// complex64, which the gradient with respect to the targets gathers from.  Same checks, route and y as nfft_fastsum.
+std::tuple<at::Tensor, at::Tensor> nfft_fastsum_band(at::Tensor sources, at::Tensor targets, at::Tensor x, at::Tensor coeffs,
+                                                     c10::optional<at::Tensor> opt_source_batch,
+                                                     c10::optional<at::Tensor> opt_target_batch, int64_t m)
+{
+    const Fastsum f = check_fastsum(sources, targets, x, coeffs, opt_source_batch, opt_target_batch, m);
+    at::Tensor band;
+    at::Tensor y = fastsum_run(x, coeffs, f, &band);
+    return {y, band};
+}
+
+// not in the reference: the backward of nfft_fastsum with respect to x (real coeffs only), the sources and the targets
+// (include/nfft_hip.h nfft_hip_fastsum_backward_planned).  dy: the gradient of y; band: nfft_fastsum_band's, needed for the
+// targets.  The native call gets conj(coeffs), the array of the sources' grid.  Same problems as nfft_fastsum, so the
+// plans its forward pass cached are reused.  Returns (dx, dsources, dtargets); what was not asked for is an empty tensor.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> nfft_fastsum_backward(
+    at::Tensor sources, at::Tensor targets, at::Tensor x, at::Tensor dy, at::Tensor coeffs, c10::optional<at::Tensor> band,
+    c10::optional<at::Tensor> opt_source_batch, c10::optional<at::Tensor> opt_target_batch, int64_t m, int64_t need_x,
+    int64_t need_sources, int64_t need_targets)
+{
+    const Fastsum f = check_fastsum(sources, targets, x, coeffs, opt_source_batch, opt_target_batch, m);
+    TORCH_CHECK(!need_x || f.real_coeffs, "_nfft_fastsum_backward: dx needs real coeffs (complex ones: the swapped fastsum)");
+    CHECK_INPUT(dy.is_cuda() && dy.device() == x.device() && dy.scalar_type() == x.scalar_type());
+    CHECK_INPUT(dy.sizes().vec() == f.out_shape);
+    const bool want_band = need_targets && band.has_value() && band->defined();
+    TORCH_CHECK(!need_targets || want_band, "_nfft_fastsum_backward: the targets' gradient needs the band");
+    if (want_band) {
+        CHECK_INPUT(band->is_cuda() && band->device() == x.device() && band->scalar_type() == at::kComplexFloat);
+        int64_t size = f.ps.B * f.C;
+        for (int d = 0; d < f.ps.dim; ++d) size *= f.N;
+        CHECK_INPUT(band->numel() == size);
+    }
+    const at::TensorOptions fo = sources.options().dtype(at::kFloat);
+    at::Tensor dx = need_x ? at::empty_like(x, at::MemoryFormat::Contiguous) : at::empty({0}, x.options());
+    at::Tensor ds = need_sources ? at::empty({f.ps.n, (int64_t)f.ps.dim}, fo) : at::empty({0}, fo);
+    at::Tensor dt = need_targets ? at::empty({f.pt.n, (int64_t)f.pt.dim}, fo) : at::empty({0}, fo);
+    if (!need_x && !need_sources && !need_targets) return {dx, ds, dt};
+    if (f.ps.n == 0 || f.pt.n == 0 || f.C == 0) {  // an empty sum: zero gradients, no native call
+        if (need_x) dx.zero_();
+        if (need_sources) ds.zero_();
+        if (need_targets) dt.zero_();
+        return {dx, ds, dt};
+    }
+    const at::Tensor xc = x.contiguous(), dyc = dy.contiguous();
+    const at::Tensor cc = f.real_coeffs ? coeffs.contiguous() : coeffs.conj_physical().contiguous();
+    const at::Tensor bc = want_band ? band->contiguous() : at::Tensor();
+    c10::DeviceGuard guard(x.device());
+    const int64_t ws_bytes = nfft_hip_fastsum_grad_workspace_bytes(&f.qs, &f.qt, f.real_input ? 0 : 1);
+    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
+    at::Tensor ws = byte_buffer(ws_bytes, x);
+    // (gradient gathers always run on plans: on the small-grid routes the forward pass made none and they are built here)
+    const at::Tensor plan_s = get_plan(f.ps, f.qs);
+    const at::Tensor plan_t = f.shared ? plan_s : get_plan(f.pt, f.qt);
+    check_rc(nfft_hip_fastsum_backward_planned(&f.qs, plan_s.data_ptr(), &f.qt, plan_t.data_ptr(), xc.data_ptr(),
+                                               f.real_input ? 0 : 1, dyc.data_ptr(), cc.data_ptr(), f.real_coeffs ? 0 : 1,
+                                               want_band ? bc.data_ptr() : nullptr, need_x ? dx.data_ptr() : nullptr,
+                                               need_sources ? ds.data_ptr<float>() : nullptr,
+                                               need_targets ? dt.data_ptr<float>() : nullptr, ws.data_ptr(), ws_bytes,
+                                               stream_of(x)));
+    return {dx, ds, dt};
 }
 
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
@@ -604,4 +712,10 @@ TORCH_LIBRARY(torch_nfft, m)
     // not in the reference: gradient of nfft_forward with respect to the points (autograd of both transforms)
     m.def("_nfft_forward_grad_points(Tensor pos, Tensor x, Tensor? batch, int m, int real_output, Tensor w) -> Tensor",
           &nfft_forward_grad_points);
+    // not in the reference: gradient of nfft_fastsum with respect to the points (autograd of nfft_fastsum)
+    m.def("_nfft_fastsum_band(Tensor sources, Tensor targets, Tensor x, Tensor coeffs, Tensor? source_batch, "
+          "Tensor? target_batch, int m) -> (Tensor, Tensor)", &nfft_fastsum_band);
+    m.def("_nfft_fastsum_backward(Tensor sources, Tensor targets, Tensor x, Tensor dy, Tensor coeffs, Tensor? band, "
+          "Tensor? source_batch, Tensor? target_batch, int m, int need_x, int need_sources, int need_targets) "
+          "-> (Tensor, Tensor, Tensor)", &nfft_fastsum_backward);
 }

@@ -11,7 +11,8 @@
 // ds_read_b128 rows and packed FMAs, same point splits) with two dot products per row instead of one -- the row with the
 // axis-2 window and with its derivative -- and d partial sums carried through the plane and slab loops.  Every G value is
 // written by exactly one lane and the sum over the planes runs in a fixed order (grad_reduce_kernel): no atomics, the
-// result is bitwise reproducible.
+// result is bitwise reproducible.  A second kernel writes the interpolated value alongside (the fused gather of the fastsum
+// backward: DESIGN.md section 7a).
 #include "common.h"
 #include "kernels.h"
 #include "window.h"
@@ -43,16 +44,25 @@ struct GradCfg {
     // waves per SIMD the register allocation must allow: at least what interp_kernel reaches for the same geometry
     // (without the floor the compiler gives the 1-D / 2-D kernels and the narrow 3-D one of m <= 2 up to 16 more VGPRs)
     static constexpr int WPE = DIM == 1 ? 8 : DIM == 2 ? (W <= 6 ? 8 : W == 10 || W == 18 ? 6 : 7) : (!WIDE && W <= 6) ? 6 : 1;
+    // the value-writing kernel: the occupancy the gradient-only kernel reaches.  2-D m = 4: 7 (the floor of 6 would let the
+    // allocator take the VGPRs the value needs from it); 2-D m = 1: 7, where the floor of 8 caps the SGPRs below what the
+    // y pointer needs -- its 62 VGPRs still give 8 waves.  (2-D m = 2 keeps 8: at 7 it takes 65 VGPRs and loses a wave, at
+    // 8 six SGPRs live in VGPR lanes -- v_writelane / v_readlane, no scratch.)
+    static constexpr int WPE_VALUE = DIM == 2 && (W == 10 || W == 4) ? 7 : WPE;
     static_assert(CELLS * 4 <= 160 * 1024, "LDS budget");
 };
 
 // part[(cr * n + i) * DIM + u]: the gradient of point i (caller order, user axis u) from real plane cr of its set, already
 // multiplied by w[i, cr].  With one real plane per set part is dpos itself.
-template <int DIM, int W, bool WIDE>
-__global__ void __launch_bounds__((GradCfg<DIM, W, WIDE>::NT)) __attribute__((amdgpu_waves_per_eu(GradCfg<DIM, W, WIDE>::WPE)))
+// VALUE: also y[i * Cr + cr], the plain interpolated value -- what interp_kernel writes for the same grid (same
+// normalisation, same layout).  Every row sum V the gradient needs is the value's row sum as well, so the value costs one
+// FMA per axis-0 plane and one store.  With VALUE = false, y is unused and the code is the gradient-only kernel's.
+template <int DIM, int W, bool WIDE, bool VALUE>
+__global__ void __launch_bounds__((GradCfg<DIM, W, WIDE>::NT))
+__attribute__((amdgpu_waves_per_eu(VALUE ? GradCfg<DIM, W, WIDE>::WPE_VALUE : GradCfg<DIM, W, WIDE>::WPE)))
 interp_grad_kernel(const Geom g, const int *__restrict__ tile_offsets, const int *__restrict__ perm,
                    const float *__restrict__ spos, const float *__restrict__ grid, const int Cr, const int plane0,
-                   const float *__restrict__ w, const int64_t n, float *__restrict__ part)
+                   const float *__restrict__ w, const int64_t n, float *__restrict__ part, float *__restrict__ y)
 {
     using C = GradCfg<DIM, W, WIDE>;
     constexpr int NT = C::NT;
@@ -150,7 +160,10 @@ interp_grad_kernel(const Geom g, const int *__restrict__ tile_offsets, const int
                 split_cell(spos[j], g.M, c2, f2);
                 idx = perm[j];
             }
-            const float wi = w[(int64_t)idx * Cr + cr];
+            // (the value-writing 2-D kernels from m = 4 on read w[i, cr] after the window loops, where its register is free)
+            constexpr bool LATE_W = VALUE && DIM == 2 && W >= 10;
+            float wi = 0.0f;
+            if (!LATE_W) wi = w[(int64_t)idx * Cr + cr];
             const int col = c2 - tb2;
             const int sh = col & 3;
             // axis-2 window on the aligned positions k = l2 + sh (zero outside the window), as in interp.hip.  Its derivative
@@ -179,6 +192,7 @@ interp_grad_kernel(const Geom g, const int *__restrict__ tile_offsets, const int
                 w1[l1] = DIM >= 2 ? __builtin_amdgcn_exp2f(sc * t1 * t1) : 1.0f;
             }
             float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f;  // d/d internal axis 0, 1, 2 (without dk, norm, w)
+            float accv = 0.0f;                            // VALUE: the interpolated value (without norm)
             for (int l0 = 0; l0 < C::W0; ++l0) {
                 const f32x4 *rowp = row0 + l0 * (C::S0 / 4);
                 // rows from the last down, the same suffix-sum device along axis 1: pv = sum_{l1' >= l1} w1 S, and
@@ -216,10 +230,12 @@ interp_grad_kernel(const Geom g, const int *__restrict__ tile_offsets, const int
                     p0 = __builtin_amdgcn_exp2f(sc * t0 * t0);
                     acc0 = fmaf(t0 * p0, V, acc0);
                 }
+                if (VALUE) accv = fmaf(p0, V, accv);
                 // sum l1 w1 S = pu - pv
                 if (DIM >= 2) acc1 = fmaf(p0, fmaf(tau1, V, V - (pu.x + pu.y)), acc1);
                 acc2 = fmaf(p0, fmaf(tau2, V, -K), acc2);
             }
+            if (LATE_W) wi = w[(int64_t)idx * Cr + cr];
             const float f = dk * wi * norm;
             float *const o = out + (int64_t)idx * DIM;
             if (DIM == 3) {
@@ -232,6 +248,7 @@ interp_grad_kernel(const Geom g, const int *__restrict__ tile_offsets, const int
             } else {
                 o[0] = acc2 * f;
             }
+            if (VALUE) y[(int64_t)idx * Cr + cr] = accv * norm;
         }
     }
 }
@@ -247,47 +264,57 @@ grad_reduce_kernel(const float *__restrict__ part, const int64_t len, const int 
     }
 }
 
+template <int DIM, int W, bool WIDE>
+void launch_w(const dim3 &blocks, const Geom &g, const int *to, const int *perm, const float *spos, const float *grid,
+              int64_t Cr, int64_t plane0, const float *w, int64_t n, float *part, float *y, hipStream_t stream)
+{
+    if (y)
+        hipLaunchKernelGGL((interp_grad_kernel<DIM, W, WIDE, true>), blocks, dim3(GradCfg<DIM, W, WIDE>::NT), 0, stream, g,
+                           to, perm, spos, grid, (int)Cr, (int)plane0, w, n, part, y);
+    else
+        hipLaunchKernelGGL((interp_grad_kernel<DIM, W, WIDE, false>), blocks, dim3(GradCfg<DIM, W, WIDE>::NT), 0, stream, g, to,
+                           perm, spos, grid, (int)Cr, (int)plane0, w, n, part, nullptr);
+}
+
 template <int DIM, int W>
 int launch_t(const Geom &g, const int *to, const int *perm, const float *spos, const float *grid, int64_t Cr,
-             int64_t plane0, int64_t nplanes, int splits, const float *w, int64_t n, float *part, hipStream_t stream)
+             int64_t plane0, int64_t nplanes, int splits, const float *w, int64_t n, float *part, float *y,
+             hipStream_t stream)
 {
     const dim3 blocks((unsigned)(g.nta[1] * g.nta[2] * g.nseg), (unsigned)nplanes, (unsigned)splits);
     if constexpr (DIM == 3) {
         if (g.wide) {
-            hipLaunchKernelGGL((interp_grad_kernel<DIM, W, true>), blocks, dim3(GradCfg<DIM, W, true>::NT), 0, stream, g,
-                               to, perm, spos, grid, (int)Cr, (int)plane0, w, n, part);
+            launch_w<DIM, W, true>(blocks, g, to, perm, spos, grid, Cr, plane0, w, n, part, y, stream);
             NFFT_HIP_CHECK(hipGetLastError());
             return 0;
         }
     }
-    hipLaunchKernelGGL((interp_grad_kernel<DIM, W, false>), blocks, dim3(GradCfg<DIM, W, false>::NT), 0, stream, g, to,
-                       perm, spos, grid, (int)Cr, (int)plane0, w, n, part);
+    launch_w<DIM, W, false>(blocks, g, to, perm, spos, grid, Cr, plane0, w, n, part, y, stream);
     NFFT_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 template <int DIM>
 int launch_d(const Geom &g, const int *to, const int *perm, const float *spos, const float *grid, int64_t Cr,
-             int64_t plane0, int64_t nplanes, int splits, const float *w, int64_t n, float *part, hipStream_t stream)
+             int64_t plane0, int64_t nplanes, int splits, const float *w, int64_t n, float *part, float *y,
+             hipStream_t stream)
 {
     switch (g.m) {
-    case 1: return launch_t<DIM, 4>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, stream);
-    case 2: return launch_t<DIM, 6>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, stream);
-    case 3: return launch_t<DIM, 8>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, stream);
-    case 4: return launch_t<DIM, 10>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, stream);
-    case 5: return launch_t<DIM, 12>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, stream);
-    case 6: return launch_t<DIM, 14>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, stream);
-    case 7: return launch_t<DIM, 16>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, stream);
-    case 8: return launch_t<DIM, 18>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, stream);
+    case 1: return launch_t<DIM, 4>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
+    case 2: return launch_t<DIM, 6>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
+    case 3: return launch_t<DIM, 8>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
+    case 4: return launch_t<DIM, 10>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
+    case 5: return launch_t<DIM, 12>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
+    case 6: return launch_t<DIM, 14>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
+    case 7: return launch_t<DIM, 16>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
+    case 8: return launch_t<DIM, 18>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
     }
     set_error("cutoff m must be in 1..8");
     return 1;
 }
 
-} // namespace
-
-int launch_interp_grad(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                       int64_t plane0, int64_t nplanes, const float *w, float *part, hipStream_t stream)
+int launch_grad(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
+                int64_t plane0, int64_t nplanes, const float *w, float *part, float *y, hipStream_t stream)
 {
     const char *base = (const char *)plan;
     const int *to = (const int *)(base + L.off_offsets);
@@ -296,12 +323,27 @@ int launch_interp_grad(const Geom &g, const PlanLayout &L, const void *plan, con
     if (nplanes <= 0 || n <= 0) return 0;
     const int splits = point_splits(g, L, n, nplanes);
     switch (g.dim) {
-    case 1: return launch_d<1>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, stream);
-    case 2: return launch_d<2>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, stream);
-    case 3: return launch_d<3>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, stream);
+    case 1: return launch_d<1>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
+    case 2: return launch_d<2>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
+    case 3: return launch_d<3>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
     }
     set_error("dim must be 1, 2 or 3");
     return 1;
+}
+
+} // namespace
+
+int launch_interp_grad(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
+                       int64_t plane0, int64_t nplanes, const float *w, float *part, hipStream_t stream)
+{
+    return launch_grad(g, L, plan, grid, n, Cr, plane0, nplanes, w, part, nullptr, stream);
+}
+
+int launch_interp_value_grad(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
+                             int64_t plane0, int64_t nplanes, const float *w, float *part, float *yr, hipStream_t stream)
+{
+    if (!yr) { set_error("Input mismatch: y is null"); return 1; }
+    return launch_grad(g, L, plan, grid, n, Cr, plane0, nplanes, w, part, yr, stream);
 }
 
 int launch_grad_reduce(const float *part, int64_t len, int64_t Cr, float *dpos, hipStream_t stream)

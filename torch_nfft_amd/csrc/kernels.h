@@ -48,6 +48,9 @@ int launch_interp(const Geom &g, const PlanLayout &L, const void *plan, const fl
 // plane order (len = n * dim).
 int launch_interp_grad(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                        int64_t plane0, int64_t nplanes, const float *w, float *part, hipStream_t stream);
+// The same gather that also writes the interpolated value yr[i * Cr + cr] of every (plane, point), as launch_interp does.
+int launch_interp_value_grad(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
+                             int64_t plane0, int64_t nplanes, const float *w, float *part, float *yr, hipStream_t stream);
 int launch_grad_reduce(const float *part, int64_t len, int64_t Cr, float *dpos, hipStream_t stream);
 // matrix-core gather for the wide 3-D tiling (interp_mfma.hip)
 bool interp_mfma_supported(const Geom &g);

@@ -7,6 +7,12 @@ Both gradients come from one native gather of the window's derivative (``ops.nff
 ``y = nfft_forward(x, pos)`` weights the derivative of its own output by ``dy``; ``y = nfft_adjoint(x, pos)`` gives
 ``dpos_i = Re(x_i conj(grad F(pos_i)))`` with ``F = nfft_forward(dy)``.  ``batch`` gets no gradient, and double backward
 (``create_graph=True``) is not supported.
+
+``nfft_fastsum`` is differentiable w.r.t. ``x``, ``sources`` and ``targets`` (not ``coeffs`` or the batch vectors).  With
+``band = c * A_s(x)`` its forward pass's band spectrum (saved only when ``targets`` needs a gradient: ``B C N^d`` complex
+values), ``dtargets`` is the gather of ``forward_t(band)`` weighted by ``dy`` and ``dsources_j = Re(conj(x_j) grad H(s_j))``
+with ``H = forward_s(conj(c) * A_t(dy))``; one native backward call (``ops.nfft_fastsum_backward``).  For real ``c``,
+``H`` is also ``dx`` and one gather returns both; for complex ``c``, ``dx`` stays the swapped fastsum.
 """
 import torch
 
@@ -85,25 +91,44 @@ def nfft_forward(x, pos, batch=None, cutoff=3, real_output=False):
 
 class NfftFastsumFunction(torch.autograd.Function):
     """y = K x with the trigonometric kernel matrix K_ij = sum_l coeffs[l] exp(2 pi i l.(source_j - target_i)).
-    Linear in x; its transpose swaps sources and targets (reference: nfft.py:62-88)."""
+    Linear in x; its transpose swaps sources and targets (reference: nfft.py:62-88).  Not in the reference: gradients
+    w.r.t. sources and targets."""
 
     @staticmethod
     def forward(ctx, x, coeffs, sources, targets, source_batch, target_batch, cutoff):
-        # the operator is linear in x only: nothing else may ask for a gradient (reference: nfft.py:67-74)
-        for name, t in (("coeffs", coeffs), ("sources", sources), ("targets", targets),
-                        ("source_batch", source_batch), ("target_batch", target_batch)):
+        # (reference: nfft.py:67-74 refuses everything but x)
+        for name, t in (("coeffs", coeffs), ("source_batch", source_batch), ("target_batch", target_batch)):
             if t is not None and t.requires_grad:
-                raise AssertionError("nfft_fastsum is differentiable w.r.t. x only, but %s requires grad" % name)
-        y = ops.nfft_fastsum(sources, targets, x, coeffs, source_batch, target_batch, cutoff)
-        ctx.save_for_backward(sources, targets, coeffs, source_batch, target_batch)
+                raise AssertionError("nfft_fastsum is differentiable w.r.t. x, sources and targets only, but %s requires "
+                                     "grad" % name)
+        ctx.points_grad = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        band = None
+        if ctx.needs_input_grad[3]:  # (the band spectrum only for the gradient w.r.t. the targets)
+            y, band = ops.nfft_fastsum_band(sources, targets, x, coeffs, source_batch, target_batch, cutoff)
+        else:
+            y = ops.nfft_fastsum(sources, targets, x, coeffs, source_batch, target_batch, cutoff)
+        if ctx.points_grad:
+            ctx.save_for_backward(sources, targets, coeffs, source_batch, target_batch, x, band)
+        else:
+            ctx.save_for_backward(sources, targets, coeffs, source_batch, target_batch)
         ctx.cutoff = cutoff
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        sources, targets, coeffs, source_batch, target_batch = ctx.saved_tensors
-        dx = ops.nfft_fastsum(targets, sources, dy, coeffs, target_batch, source_batch, ctx.cutoff)
-        return dx, None, None, None, None, None, None
+        sources, targets, coeffs, source_batch, target_batch = ctx.saved_tensors[:5]
+        if not ctx.points_grad:
+            dx = ops.nfft_fastsum(targets, sources, dy, coeffs, target_batch, source_batch, ctx.cutoff)
+            return dx, None, None, None, None, None, None
+        x, band = ctx.saved_tensors[5:]
+        need_x, need_s, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        fused_x = need_x and not coeffs.is_complex()  # real coefficients: dx and dsources share one gather
+        dx, ds, dt = ops.nfft_fastsum_backward(sources, targets, x, dy.contiguous(), coeffs, band, source_batch,
+                                               target_batch, ctx.cutoff, fused_x, need_s, need_t)
+        if need_x and not fused_x:
+            dx = ops.nfft_fastsum(targets, sources, dy, coeffs, target_batch, source_batch, ctx.cutoff)
+        # (targets is sources: both gradients go to the one tensor, and autograd sums them)
+        return dx if need_x else None, None, ds if need_s else None, dt if need_t else None, None, None, None
 
 
 def nfft_fastsum(x, coeffs, sources, targets=None, source_batch=None, target_batch=None, /, batch=None, cutoff=3):

@@ -18,6 +18,10 @@ re-checks it (one streaming pass, ~25 us for 10^7 points): a stale plan raises "
 callers who never write that way).  The same switches govern the remembered ENDS of the batch vector
 (``B = batch[-1] + 1`` otherwise costs a blocking read-back of ~35 us in every operator call, as in the reference's
 ``check_point_input``, core_cuda.cu:60): same key (identity + version counter), same limitation.
+
+Not in the reference, for gradients with respect to the points: ``nfft_forward_grad_points`` (both transforms),
+``nfft_fastsum_band`` and ``nfft_fastsum_backward`` (the fast summation).  They take their plans
+from the same cache with the same problems, so a backward pass right after its forward pass plans nothing.
 """
 import torch
 
@@ -77,6 +81,26 @@ def nfft_fastsum(sources, targets, x, coeffs, source_batch, target_batch, m):
     One native call (``nfft_hip_fastsum_planned``): adjoint at the sources with the kernel coefficients folded
     into its last spectral pass, forward at the targets; shared points share one plan (core_cuda.cu:552-564)."""
     return _ops.nfft_fastsum(sources, targets, x, coeffs, source_batch, target_batch, int(m))
+
+
+def nfft_fastsum_band(sources, targets, x, coeffs, source_batch, target_batch, m):
+    """torch_nfft::_nfft_fastsum_band(...same arguments as nfft_fastsum...) -> (Tensor y, Tensor band) (not in the
+    reference): ``nfft_fastsum`` (same route, bitwise the same ``y``) that also returns its band spectrum
+    ``coeffs * A_s(x)``, ``[B] + [N]*d + x.shape[1:]`` complex64 -- what ``nfft_fastsum_backward`` needs for the targets'
+    gradient.  One native call (``nfft_hip_fastsum_band[_planned]``)."""
+    return _ops._nfft_fastsum_band(sources, targets, x, coeffs, source_batch, target_batch, int(m))
+
+
+def nfft_fastsum_backward(sources, targets, x, dy, coeffs, band, source_batch, target_batch, m, need_x, need_sources,
+                          need_targets):
+    """torch_nfft::_nfft_fastsum_backward(Tensor sources, Tensor targets, Tensor x, Tensor dy, Tensor coeffs,
+    Tensor? band, Tensor? source_batch, Tensor? target_batch, int m, int need_x, int need_sources, int need_targets)
+    -> (Tensor dx, Tensor dsources, Tensor dtargets) (not in the reference): the gradients of ``nfft_fastsum`` for the
+    upstream gradient ``dy``; what was not asked for comes back empty.  ``dx`` only for real ``coeffs`` (it comes from the
+    same gather as ``dsources``); ``band`` from ``nfft_fastsum_band`` when ``need_targets``.  One native call
+    (``nfft_hip_fastsum_backward_planned``) on the point plans the forward pass cached."""
+    return _ops._nfft_fastsum_backward(sources, targets, x, dy, coeffs, band, source_batch, target_batch, int(m),
+                                       1 if need_x else 0, 1 if need_sources else 0, 1 if need_targets else 0)
 
 
 class _on_device:
