@@ -169,14 +169,16 @@ int nfft_hip_plan_verify(const nfft_hip_problem *p, const float *pos, const int6
  *   grid  float32 [B*Cr, (2N)^dim] real planes; every cell is written by this call.
  *   scratch  nfft_hip_spread_scratch_bytes(p, Cr) bytes: the tile-ordered copy of xr (n * Cr floats, or one per plan
  *            entry when the problem is sparse enough for the owner-computes kernel, whose plan enters a point into
- *            every tile its window touches) and one word per plane (its largest |x|, the operand scale of the
- *            matrix-core kernel). */
+ *            every tile its window touches), one word per plane (its largest |x|, the operand scale of the
+ *            matrix-core kernel) and the ticket counters of the kernel's persistent launch. */
 int64_t nfft_hip_spread_scratch_bytes(const nfft_hip_problem *p, int64_t real_columns);
 int nfft_hip_spread(const nfft_hip_problem *p, const void *plan, const float *xr, int64_t real_columns,
                     float *grid, float *scratch, void *stream);
 
 /* Interpolation (forward gather):  yr[i, cr] = sum_u grid[(b*Cr + cr), u] * prod_k psi_k(i, u_k).
- * Replaces complex_/real_forward_window_convolution_kernel (spatial_window_operations.cu:214-332). */
+ * Replaces complex_/real_forward_window_convolution_kernel (spatial_window_operations.cu:214-332).
+ * There is no workspace for ticket counters here: on an unbalanced (clustered) plan the persistent launch deals its
+ * work list round robin, where nfft_hip_forward hands it out dynamically. */
 int nfft_hip_interpolate(const nfft_hip_problem *p, const void *plan, const float *grid,
                          int64_t real_columns, float *yr, void *stream);
 

@@ -24,7 +24,7 @@ plan = torch.empty(lib.nfft_hip_plan_bytes(ctypes.byref(prob)), dtype=torch.uint
 s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 _lib.check(lib.nfft_hip_plan_points(ctypes.byref(prob), p(pos), None, p(plan), plan.numel(), s))
 grid = torch.empty((2 * N,) * 3, device="cuda")
-scratch = torch.empty(n + 256, device="cuda")
+scratch = torch.empty(lib.nfft_hip_spread_scratch_bytes(ctypes.byref(prob), 1) // 4, device="cuda")
 nwg = 1 << 16
 trace = torch.zeros((nwg, 8), dtype=torch.int64, device="cuda")
 assert lib.nfft_dbg_set_spread_trace(p(trace)) == 0

@@ -7,6 +7,8 @@ the exact NDFT of config C3 is 1.7e14 point-frequency pairs):
   * linearity in x;
   * fastsum (config C5): a subset of targets against the exact Gaussian kernel sums.
 """
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -384,10 +386,10 @@ def test_grid_2d_16384_squared(tn):
 
 
 def test_work_list_tickets_on_concurrent_streams(tn):
-    """Two streams run the persistent (work-list) kernels at the same time on the SAME cached plan: the ticket words that
-    hand out the list live in a ring owned by the library, one set per launch -- the plan itself is read-only -- so the
-    launches must not disturb each other.  4e6 clustered points (most work items are cut pieces), three rounds, results
-    compared with the same transforms run one after the other."""
+    """Two streams run the persistent (work-list) kernels at the same time on the SAME cached plan: the ticket counters
+    that hand out the list live in the workspace of each call -- the plan itself is read-only -- so the launches must not
+    disturb each other.  4e6 clustered points (most work items are cut pieces), three rounds, results compared with the
+    same transforms run one after the other."""
     N, m, n = 128, 4, 4_000_000
     gen = torch.Generator(device="cuda").manual_seed(77)
     centres = torch.rand((4, 3), generator=gen, device="cuda") - 0.5
@@ -413,6 +415,70 @@ def test_work_list_tickets_on_concurrent_streams(tn):
         assert torch.equal(fa2, fa)  # the gather has no atomics
     from torch_nfft_amd import ops
     ops.check_status()
+
+
+@pytest.mark.parametrize("cols,real_output,env_extra,kernels", [
+    (1, 1, {}, "spread_mfma_kernel, interp_stream_kernel"),  # (one real plane: items big enough for the streamed gather)
+    (2, 0, {}, "spread_mfma_kernel, interp_cols_kernel"),  # (complex forward output: four real planes, one wave each)
+    (1, 1, {"NFFT_HIP_GATHER": "mfma"}, "spread_mfma_kernel, interp_mfma_kernel"),
+], ids=["stream", "cols", "ring"])
+def test_work_list_tickets_in_graph_replays(cols, real_output, env_extra, kernels):
+    """The persistent (work-list) launches captured into a HIP graph and replayed: their ticket counters are zeroed by the
+    launch enqueued just before them, so every replay hands the list out afresh.  The input of
+    test_work_list_tickets_on_concurrent_streams with 1 or 2 columns, through the C ABI (plan built before the capture;
+    adjoint + forward captured), replayed three times: the forward equal bit for bit to the eager run (the gathers have no
+    atomics), the adjoint within 2e-6.  NFFT_HIP_OWNED=0 keeps the scatter form of the spreading kernel; the cases reach
+    the persistent form of the kernels named in `kernels` (api.hip: plan_route)."""
+    import subprocess
+    import sys
+    code = r'''
+import ctypes, sys, torch
+sys.path.insert(0, %r)
+from torch_nfft_amd import _lib, ops
+lib = _lib.load()
+C, real_output, N, m, n = %d, %d, 128, 4, 4_000_000
+gen = torch.Generator(device="cuda").manual_seed(77)
+centres = torch.rand((4, 3), generator=gen, device="cuda") - 0.5
+pos = centres[torch.randint(0, 4, (n,), generator=gen, device="cuda")] + 0.03 * torch.randn((n, 3), generator=gen, device="cuda")
+pos = (pos - torch.floor(pos + 0.5)).contiguous()
+x = torch.randn((n, C), generator=gen, device="cuda")
+xhat = torch.randn((1, N, N, N, C), dtype=torch.complex64, generator=gen, device="cuda")
+prob = _lib.Problem(3, n, C, 1, N, m)
+P = ctypes.byref(prob)
+ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+stream = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+plan = torch.empty(lib.nfft_hip_plan_bytes(P), dtype=torch.uint8, device="cuda")
+_lib.check(lib.nfft_hip_plan_points(P, ptr(pos), None, ptr(plan), plan.numel(), stream()))
+nws = max(lib.nfft_hip_adjoint_workspace_bytes(P, 0, 0), lib.nfft_hip_forward_workspace_bytes(P, 1, real_output))
+ws = torch.empty(nws, dtype=torch.uint8, device="cuda")
+y = torch.empty((1, N, N, N, C), dtype=torch.complex64, device="cuda")
+f = torch.empty((n, C), dtype=torch.float32 if real_output else torch.complex64, device="cuda")
+
+def calls():
+    _lib.check(lib.nfft_hip_adjoint_planned(P, ptr(plan), ptr(x), 0, 0, ptr(y), ptr(ws), nws, stream()))
+    _lib.check(lib.nfft_hip_forward_planned(P, ptr(plan), ptr(xhat), 1, real_output, ptr(f), ptr(ws), nws, stream()))
+
+calls()
+torch.cuda.synchronize()
+y_eager, f_eager = y.clone(), f.clone()
+graph = torch.cuda.CUDAGraph()
+with torch.cuda.graph(graph):
+    calls()
+for r in range(3):
+    y.fill_(float("nan"))
+    f.fill_(float("nan"))
+    graph.replay()
+    torch.cuda.synchronize()
+    err = float(torch.linalg.vector_norm(y - y_eager) / torch.linalg.vector_norm(y_eager))
+    print("REPLAY", r, "forward equal", torch.equal(f, f_eager), "adjoint rel L2 %%.3g" %% err)
+    assert torch.equal(f, f_eager), r
+    assert err < 2e-6, (r, err)
+ops.check_status()
+print("RESULT ok")
+''' % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), cols, real_output)
+    env = dict(os.environ, NFFT_HIP_OWNED="0", **env_extra)
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "RESULT ok" in out.stdout, (kernels, out.stdout[-2000:], out.stderr[-2000:])
 
 
 # ----------------------------------------------------------------------------- stage level at full C3 size

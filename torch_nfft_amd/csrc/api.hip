@@ -136,53 +136,6 @@ int *device_status_block()
     return (int *)d;
 }
 
-// Ticket counters of the persistent launches over a plan's work list (common.h: WorkTickets): a ring of 64-bit words
-// {launch number, tickets taken} per device, zeroed once.  A launch owns the 256 words of its number modulo 4096 -- one per
-// plane -- and claims a word by overwriting whatever an earlier launch (4096 launches ago: long finished) left there, so
-// nothing is reset between launches and the plan itself stays read-only (it may be in use on several streams).
-unsigned long long *device_ticket_ring()
-{
-    static std::mutex mutex;
-    static unsigned long long *ring[kMaxDevices] = {};
-    const int dev = current_device();
-    if (dev >= kMaxDevices) return nullptr;
-    std::lock_guard<std::mutex> lock(mutex);
-    if (!ring[dev]) {
-        void *p = nullptr;
-        if (hipMalloc(&p, (size_t)kTicketSlots * 8) != hipSuccess || hipMemset(p, 0, (size_t)kTicketSlots * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        ring[dev] = (unsigned long long *)p;
-    }
-    return ring[dev];
-}
-
-unsigned next_launch_number()
-{
-    static std::atomic<unsigned> counter{0};
-    unsigned v = ++counter;
-    if (v == 0) v = ++counter;  // (0 is what the zeroed ring holds)
-    // A launch takes over the ring row that the launch kTicketLaunches numbers earlier used, and must not do so while that
-    // one is still running (two launches claiming one word from each other would hand work-list entries out twice).
-    // Numbers come in epochs of half a ring; a device that sees a new epoch first waits for everything it has in flight:
-    // whatever ran in the epoch before the previous one -- the only launches that can own this epoch's rows -- is then
-    // finished.  One hipDeviceSynchronize per kTicketLaunches / 2 persistent launches and device (the reference
-    // synchronises the device six times per call, cuda_utils.cu:16).
-    static std::mutex mutex;
-    static unsigned last_epoch[kMaxDevices] = {};
-    const int dev = current_device();
-    if (dev >= 0 && dev < kMaxDevices) {
-        const unsigned epoch = v / (kTicketLaunches / 2) + 1;
-        std::lock_guard<std::mutex> lock(mutex);
-        if (last_epoch[dev] != epoch) {
-            if (last_epoch[dev] != 0) (void)hipDeviceSynchronize();
-            last_epoch[dev] = epoch;
-        }
-    }
-    return v;
-}
-
 // Faults the kernels of the current device have reported since the last look: sets the error text, clears the flags and
 // returns NFFT_HIP_EKERNEL (NFFT_HIP_EINVAL for a bad batch vector); 0 when there is none.
 static int take_pending_fault()
@@ -329,7 +282,7 @@ struct Route {
     FftRoute fft;           // kFftFull, kFftRocRows or kFftOwnPlanar; chunk_fft() says when a chunk goes column-innermost
     bool ci;                // several columns on a grid the column-innermost passes take
     int64_t C, ppc, total_planes, chunk_planes, half_cells;
-    int64_t off_plan, off_xs, off_xmax, off_grid, off_spec, off_col, off_work, work_bytes, total;
+    int64_t off_plan, off_xs, off_xmax, off_grid, off_spec, off_col, off_work, off_tickets, work_bytes, total;
 
     const Geom &spread_geom() const { return owned ? go : g; }
     const PlanLayout &spread_layout() const { return owned ? Lo : L; }
@@ -428,6 +381,8 @@ int make_route(const nfft_hip_problem *p, int ppc, bool adjoint, Route &r)
     // (several columns: the column-innermost passes work on whole groups of 16 planes)
     r.off_col = o;  o = align_up(o + (colfft ? colfft_scratch_bytes(r.g, r.C > 1 ? colfft_ci_planes(chunk) : chunk) : 0), 256);
     r.off_work = o; o = align_up(o + r.work_bytes, 256);
+    // (the counters of the persistent work-list launches: every launch of the call in turn, on its stream)
+    r.off_tickets = o; o = align_up(o + kTicketPlanes * 4, 256);
     r.total = o + 256;
     return 0;
 }
@@ -440,9 +395,10 @@ int build_plans(const Route &r, const float *pos, const int64_t *batch, void *pl
 }
 
 // planes [p0, p0 + np) of the grid; xs: the planar copy in plan order; xr: nullptr when gather_rows has filled xs, else x
-// (x_through_plan); xmax: per-plane largest |x| (matrix-core kernel only: launch_plane_absmax)
+// (x_through_plan); xmax: per-plane largest |x| (matrix-core kernel only: launch_plane_absmax); tickets: the work-list
+// counters (kernels.h: launch_spread_mfma)
 int spread_chunk(const Route &r, const void *plan, const float *xr, float *xs, const unsigned *xmax, int64_t p0, int64_t np,
-                 float *grid, hipStream_t s)
+                 float *grid, int *tickets, hipStream_t s)
 {
     const Geom &g = r.spread_geom();
     const PlanLayout &L = r.spread_layout();
@@ -452,7 +408,7 @@ int spread_chunk(const Route &r, const void *plan, const float *xr, float *xs, c
         // (the owner-computes variant writes every cell itself)
         if (!g.owned) { StageTimer t(kStageZero, s); NFFT_HIP_CHECK(hipMemsetAsync(grid, 0, (size_t)(np * g.cells * 4), s)); }
         StageTimer t(kStageSpread, s);
-        return launch_spread_mfma(g, L, plan, xr, xs, xmax, r.n, r.Cr, p0, np, grid, s);
+        return launch_spread_mfma(g, L, plan, xr, xs, xmax, r.n, r.Cr, p0, np, grid, tickets, s);
     }
     case kSpreadReg: {
         StageTimer t(kStageSpread, s);
@@ -465,12 +421,13 @@ int spread_chunk(const Route &r, const void *plan, const float *xr, float *xs, c
     return launch_spread(g, L, plan, xr, xs, r.n, r.Cr, p0, np, grid, s);
 }
 
-int gather_chunk(const Route &r, const void *plan, const float *grid, int64_t p0, int64_t np, float *yr, hipStream_t s)
+int gather_chunk(const Route &r, const void *plan, const float *grid, int64_t p0, int64_t np, float *yr, int *tickets,
+                 hipStream_t s)
 {
     switch (r.gather) {
-    case kGatherCols: return launch_interp_cols(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, yr, s);
-    case kGatherStream: return launch_interp_stream(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, yr, s);
-    case kGatherRing: return launch_interp_mfma(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, yr, s);
+    case kGatherCols: return launch_interp_cols(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, yr, tickets, s);
+    case kGatherStream: return launch_interp_stream(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, yr, tickets, s);
+    case kGatherRing: return launch_interp_mfma(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, yr, tickets, s);
     case kGatherLanes: break;
     }
     return launch_interp(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, yr, s);
@@ -670,9 +627,9 @@ int nfft_hip_plan_verify(const nfft_hip_problem *p, const float *pos, const int6
 int64_t nfft_hip_spread_scratch_bytes(const nfft_hip_problem *p, int64_t real_columns)
 {
     if (validate(p) || real_columns < 0) return -1;
-    // plan-ordered copy of the coefficients + one word per plane (its largest |x|)
+    // plan-ordered copy of the coefficients + one word per plane (its largest |x|) + the work-list counters
     return (align_up(plan_route(p, real_columns).spread_layout().cap * real_columns, 64) + 64 +
-            align_up(p->batch_size * real_columns, 64)) * 4;
+            align_up(p->batch_size * real_columns, 64) + kTicketPlanes) * 4;
 }
 
 int nfft_hip_spread(const nfft_hip_problem *p, const void *plan, const float *xr, int64_t real_columns, float *grid,
@@ -685,12 +642,13 @@ int nfft_hip_spread(const nfft_hip_problem *p, const void *plan, const float *xr
     const int64_t planes = r.B * real_columns;
     if (planes > 32768) { set_error("Input mismatch: too many planes for one spread call"); return NFFT_HIP_EINVAL; }
     unsigned *xmax = (unsigned *)(scratch + align_up(r.spread_layout().cap * real_columns, 64) + 64);
+    int *tickets = (int *)(xmax + align_up(r.B * real_columns, 64));
     if (r.spread == kSpreadMfma)
         if (int rc = launch_plane_absmax(r.g, r.L, plan, xr, r.n, r.B, real_columns, xmax, s)) return rc;
-    if (r.x_through_plan) return spread_chunk(r, plan, xr, scratch, xmax, 0, planes, grid, s);
+    if (r.x_through_plan) return spread_chunk(r, plan, xr, scratch, xmax, 0, planes, grid, tickets, s);
     if (int rc = launch_gather_rows(r.spread_geom(), r.spread_layout(), r.spread_plan(plan), r.n, xr, real_columns, scratch, s))
         return rc;
-    return spread_chunk(r, plan, nullptr, scratch, xmax, 0, planes, grid, s);
+    return spread_chunk(r, plan, nullptr, scratch, xmax, 0, planes, grid, tickets, s);
 }
 
 int nfft_hip_interpolate(const nfft_hip_problem *p, const void *plan, const float *grid, int64_t real_columns,
@@ -701,7 +659,8 @@ int nfft_hip_interpolate(const nfft_hip_problem *p, const void *plan, const floa
     const Route r = plan_route(p, real_columns);
     const int64_t planes = r.B * real_columns;
     if (planes > 32768) { set_error("Input mismatch: too many planes for one interpolate call"); return NFFT_HIP_EINVAL; }
-    return gather_chunk(r, plan, grid, 0, planes, yr, (hipStream_t)stream);
+    // (no workspace here: the persistent launches of unbalanced plans deal their work lists round robin)
+    return gather_chunk(r, plan, grid, 0, planes, yr, nullptr, (hipStream_t)stream);
 }
 
 static int adjoint_impl(const nfft_hip_problem *p, const float *pos, const int64_t *batch, const void *ext_plan,
@@ -731,6 +690,7 @@ static int adjoint_impl(const nfft_hip_problem *p, const float *pos, const int64
     unsigned *xmax = (unsigned *)(ws + r.off_xmax);
     float *grid = (float *)(ws + r.off_grid);
     float2 *spec = (float2 *)(ws + r.off_spec);
+    int *tickets = (int *)(ws + r.off_tickets);
 
     if (!ext_plan) {
         StageTimer t(kStagePlan, s);
@@ -749,7 +709,8 @@ static int adjoint_impl(const nfft_hip_problem *p, const float *pos, const int64
     }
     for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes) {
         const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
-        if (int rc = spread_chunk(r, plan, r.x_through_plan ? (const float *)x : nullptr, xs, xmax, p0, np, grid, s)) return rc;
+        if (int rc = spread_chunk(r, plan, r.x_through_plan ? (const float *)x : nullptr, xs, xmax, p0, np, grid, tickets, s))
+            return rc;
         if (int rc = fft_adjoint_chunk(r, ws, grid, spec, x_is_complex, real_output, p0, np, y, mult, mult_kind, s)) return rc;
     }
     return 0;
@@ -777,6 +738,7 @@ static int forward_impl(const nfft_hip_problem *p, const float *pos, const int64
     const void *plan = ext_plan;
     float *grid = (float *)(ws + r.off_grid);
     float2 *spec = (float2 *)(ws + r.off_spec);
+    int *tickets = (int *)(ws + r.off_tickets);
 
     if (!ext_plan) {
         // (only the first sort: the forward transform never spreads)
@@ -788,7 +750,7 @@ static int forward_impl(const nfft_hip_problem *p, const float *pos, const int64
         const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
         if (int rc = fft_forward_chunk(r, ws, xhat, x_is_complex, real_output, p0, np, grid, spec, s)) return rc;
         StageTimer t(kStageInterp, s);
-        if (int rc = gather_chunk(r, plan, grid, p0, np, (float *)y, s)) return rc;
+        if (int rc = gather_chunk(r, plan, grid, p0, np, (float *)y, tickets, s)) return rc;
     }
     return 0;
 }

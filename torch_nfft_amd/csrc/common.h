@@ -115,11 +115,9 @@ struct Geom {
 };
 
 inline bool owned_supported(int dim, int64_t N, int64_t m);
-// (4096 launch numbers before a row of the ring is used again: a launch would have to outlive 4096 later ones -- on other
-// streams -- for two to meet in a row; 8 MB per device)
-constexpr int kTicketPlanes = 256, kTicketLaunches = 4096, kTicketSlots = kTicketPlanes * kTicketLaunches;
-unsigned long long *device_ticket_ring();  // api.hip: per-device ring of ticket words (WorkTickets below); nullptr on failure
-unsigned next_launch_number();             // api.hip: process-wide, never 0
+// Ticket counters of a persistent launch (next_work_item below): one int per blockIdx.y, in the caller's workspace.  A launch
+// with more planes (pair slots, column groups) than this deals its work list round robin.
+constexpr int kTicketPlanes = 256;
 bool work_list_forced();       // api.hip: NFFT_HIP_WORK_LIST=1 runs every wide plan from its work list
 bool column_groups_enabled();  // api.hip: NFFT_HIP_COLGROUPS=0 turns the column-group order of the plan off
 
@@ -332,42 +330,26 @@ __device__ __forceinline__ int sub_of_cells(const Geom &g, const int cell[3])
 
 // Dynamic hand-out of the sorted work list to the workgroups of a persistent launch: a workgroup starts with entry
 // blockIdx.x and then takes the next free entry whenever it is done (the list is sorted biggest first: longest-processing-
-// time-first scheduling).  One 64-bit word {launch number, entries handed out} per plane of the launch in the library's
-// ring (api.hip: device_ticket_ring).  A ticket is ONE atomic add; only the first arrivals of a launch, which find an
-// older launch's number in the word, claim it with a compare-and-swap (a CAS per ticket was quadratic under the
-// stampede of a launch's first round: +2.3 ms at C3-clustered).
-struct WorkTickets {
-    unsigned long long *ring;  // nullptr: static round robin (more planes than a launch's share of the ring)
-    unsigned launch;
-};
-__device__ __forceinline__ int take_ticket(const WorkTickets &t, const int plane_local)
+// time-first scheduling).  A ticket is one atomic add on the counter of the workgroup's plane, tickets[blockIdx.y]: the
+// launch's kTicketPlanes ints in the workspace of the call, so the plan stays read-only (it may be in use on several
+// streams).  nullptr: the static round robin of listed_item.  The one-workgroup-per-range launch, always enqueued just
+// before the persistent one on the same stream with the same gridDim.y, zeroes the counters as its first statement
+// (before any early return).  The zero is an atomic exchange: every access to a counter is a device-scope atomic,
+// performed where the adds are, and none depends on the end-of-kernel write-back of one XCD's L2.
+__device__ __forceinline__ void reset_tickets(int *tickets)
 {
-    unsigned long long *slot = t.ring + (((t.launch & (kTicketLaunches - 1)) * kTicketPlanes) + plane_local);
-    const unsigned long long mine = (unsigned long long)t.launch << 32;
-    while (true) {
-        const unsigned long long old = atomicAdd(slot, 1ull);
-        if ((old >> 32) == t.launch) return (int)(unsigned)old;
-        // an older launch's word (plus the increment just made): install {launch, 1} and take ticket 0 -- unless another
-        // workgroup of this launch gets there first
-        unsigned long long cur = old + 1ull;
-        while ((cur >> 32) != t.launch) {
-            const unsigned long long seen = atomicCAS(slot, cur, mine | 1ull);
-            if (seen == cur) return 0;
-            cur = seen;
-        }
-    }
+    if (tickets && blockIdx.x == 0 && threadIdx.x == 0) (void)atomicExch(&tickets[blockIdx.y], 0);
 }
 
 // Next entry of the work list for this workgroup of a persistent launch (n_items or more: none left): its own index
 // first, then tickets -- or the static round robin.  Called by all threads of the workgroup together; `word` is an LDS
 // int of the workgroup.
-__device__ __forceinline__ int next_work_item(const WorkTickets &t, int *word, const int prev /* < 0: first call */,
-                                              const int plane_local)
+__device__ __forceinline__ int next_work_item(int *tickets, int *word, const int prev /* < 0: first call */)
 {
     if (prev < 0) return (int)blockIdx.x;
-    if (!t.ring) return prev + (int)gridDim.x;
+    if (!tickets) return prev + (int)gridDim.x;
     __syncthreads();  // every wave is done with the previous item (and has read the previous ticket)
-    if (threadIdx.x == 0) *word = (int)gridDim.x + take_ticket(t, plane_local);
+    if (threadIdx.x == 0) *word = (int)gridDim.x + atomicAdd(&tickets[blockIdx.y], 1);
     __syncthreads();
     return *word;
 }
@@ -393,7 +375,7 @@ __device__ __forceinline__ int4 listed_item(const int4 *__restrict__ sorted, con
 //   [0] = {entries, any range cut, 1 = walk the list, 0};  then one int2 {entries, first entry} per point set;
 //   then the entries {point set * pencils + pencil, first slab, end slab, points} as they were produced;
 //   then the same entries grouped by point set, every set's biggest first.
-// ONE persistent launch walks a set's part of the sorted list instead (entries handed out by tickets, below).  Both
+// ONE persistent launch walks a set's part of the sorted list instead (entries handed out by tickets: next_work_item).  Both
 // launches are always enqueued; the one that is not the plan's returns at once.
 constexpr int kSegMax = 32;      // most ranges per pencil
 constexpr int kSegPieces = 16;   // most pieces a range is cut into

@@ -58,9 +58,10 @@ __global__ void __launch_bounds__(kIcThreads) __attribute__((amdgpu_waves_per_eu
 interp_cols_kernel(const Geom g, const int *__restrict__ tile_offsets,
                    const float *__restrict__ spos, const float *__restrict__ grid, const int Cr, const int64_t plane0,
                    const int64_t nplanes, const int64_t group0, float *__restrict__ yr, const int seg_slabs,
-                   const int nsegm, const int4 *__restrict__ work, const int4 *__restrict__ sorted, const WorkTickets tickets)
+                   const int nsegm, const int4 *__restrict__ work, const int4 *__restrict__ sorted, int *tickets)
 {
     constexpr int m = W / 2 - 1;
+    if constexpr (!OVERFLOW) reset_tickets(tickets);
     extern __shared__ __align__(16) unsigned char smem_raw[];
     IcLds &L = *reinterpret_cast<IcLds *>(smem_raw);
     float *const ystage = reinterpret_cast<float *>(&L.blk[0]);
@@ -89,11 +90,11 @@ interp_cols_kernel(const Geom g, const int *__restrict__ tile_offsets,
     const int2 set_hdr = OVERFLOW ? ((const int2 *)(work + 1))[b] : make_int2(1, 0);
     const int n_items = set_hdr.x;
     const int4 *const entries = sorted + set_hdr.y;
-    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1, (int)blockIdx.y) : 0; item < n_items;
-         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item, (int)blockIdx.y) : 1) {
+    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : 0; item < n_items;
+         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : 1) {
     int pencil, sb, se;
     if constexpr (OVERFLOW) {
-        const int4 it = tickets.ring ? entries[item] : listed_item(entries, item, n_items);
+        const int4 it = tickets ? entries[item] : listed_item(entries, item, n_items);
         pencil = it.x - b * pencils;
         sb = it.y;
         se = it.z;
@@ -317,7 +318,7 @@ bool interp_cols_supported(const Geom &g) { return g.dim == 3 && g.wide && !g.ow
 
 template <int W>
 static int launch_ic_t(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                       int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream)
+                       int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
 {
     const char *base = (const char *)plan;
     const int *to = (const int *)(base + L.off_offsets);
@@ -342,11 +343,11 @@ static int launch_ic_t(const Geom &g, const PlanLayout &L, const void *plan, con
         attr_done.mark();
     }
     const dim3 blocks((unsigned)(pencils * nsegm), (unsigned)ngroups);
+    // The persistent launch over the work list (unbalanced plans; its workgroups leave at once otherwise) hands its entries
+    // out by tickets when its planes fit the call's counters, else round robin; the launch before it zeroes the counters.
+    if (ngroups > kTicketPlanes) tickets = nullptr;
     hipLaunchKernelGGL((interp_cols_kernel<W, false>), blocks, dim3(kIcThreads), sizeof(IcLds), stream, g, to, spos,
-                       grid, (int)Cr, plane0, nplanes, group0, yr, seg_slabs, nsegm, work, sorted, WorkTickets{nullptr, 0u});
-    // the persistent launch over the work list (unbalanced plans; its workgroups leave at once otherwise); entries are
-    // handed out by tickets when the launch's planes fit its share of the ticket ring, else round robin
-    const WorkTickets tickets{ngroups <= kTicketPlanes ? device_ticket_ring() : nullptr, next_launch_number()};
+                       grid, (int)Cr, plane0, nplanes, group0, yr, seg_slabs, nsegm, work, sorted, tickets);
     const dim3 oblocks(work_list_workgroups(n, nsets, pencils, nsegm, device_cu_count()), (unsigned)ngroups);
     hipLaunchKernelGGL((interp_cols_kernel<W, true>), oblocks, dim3(kIcThreads), sizeof(IcLds), stream, g, to,
                        spos, grid, (int)Cr, plane0, nplanes, group0, yr, seg_slabs, nsegm, work, sorted, tickets);
@@ -355,17 +356,17 @@ static int launch_ic_t(const Geom &g, const PlanLayout &L, const void *plan, con
 }
 
 int launch_interp_cols(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                       int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream)
+                       int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
 {
     if (nplanes <= 0 || n <= 0) return 0;
     switch (g.m) {
-    case 1: return launch_ic_t<4>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 2: return launch_ic_t<6>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 3: return launch_ic_t<8>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 4: return launch_ic_t<10>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 5: return launch_ic_t<12>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 6: return launch_ic_t<14>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 7: return launch_ic_t<16>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
+    case 1: return launch_ic_t<4>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 2: return launch_ic_t<6>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 3: return launch_ic_t<8>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 4: return launch_ic_t<10>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 5: return launch_ic_t<12>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 6: return launch_ic_t<14>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 7: return launch_ic_t<16>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
     }
     set_error("matrix-core interpolation supports cutoff 1..7");
     return 1;

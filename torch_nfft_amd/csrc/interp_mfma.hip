@@ -40,11 +40,12 @@ template <int W, bool OVERFLOW>
 __global__ void __launch_bounds__(kGmThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
 interp_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets,
                    const float *__restrict__ spos, const float *__restrict__ grid, const int Cr, const int plane0,
-                   float *__restrict__ yr, const int seg_slabs, const int nsegm, const int4 *__restrict__ work, const int4 *__restrict__ sorted, const WorkTickets tickets)
+                   float *__restrict__ yr, const int seg_slabs, const int nsegm, const int4 *__restrict__ work, const int4 *__restrict__ sorted, int *tickets)
 {
     constexpr int m = W / 2 - 1;
     constexpr int TC = 17 - W;
     static_assert(TC >= 1 && TC + W - 1 == kRing, "ring holds exactly one chunk's planes");
+    if constexpr (!OVERFLOW) reset_tickets(tickets);
     extern __shared__ __align__(16) unsigned char smem_raw[];
     GatherMfmaLds &L = *reinterpret_cast<GatherMfmaLds *>(smem_raw);
 
@@ -68,12 +69,12 @@ interp_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets,
     const int2 set_hdr = OVERFLOW ? ((const int2 *)(work + 1))[b] : make_int2(1, 0);
     const int n_items = set_hdr.x;
     const int4 *const entries = sorted + set_hdr.y;
-    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1, plane_local) : 0; item < n_items;
-         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item, plane_local) : 1) {
+    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : 0; item < n_items;
+         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : 1) {
     if (OVERFLOW && item != (int)blockIdx.x) __syncthreads();  // the previous item is done with the LDS
     int pencil, sb, se;
     if constexpr (OVERFLOW) {
-        const int4 it = tickets.ring ? entries[item] : listed_item(entries, item, n_items);
+        const int4 it = tickets ? entries[item] : listed_item(entries, item, n_items);
         pencil = it.x - b * pencils;
         sb = it.y;
         se = it.z;
@@ -269,7 +270,7 @@ bool interp_mfma_supported(const Geom &g) { return g.dim == 3 && g.wide; }
 template <int W>
 static int launch_gm_t(const Geom &g, const PlanLayout &L, const void *plan, const int *to,
                        const float *spos, const float *grid, int64_t n, int64_t Cr, int64_t plane0, int64_t nplanes,
-                       float *yr, hipStream_t stream)
+                       float *yr, int *tickets, hipStream_t stream)
 {
     // the work decomposition of the spreading kernel (ranges of M / runs slabs per pencil + the plan's work list
     // for dense ranges); every item starts by staging all 16 planes of its first chunk
@@ -289,11 +290,11 @@ static int launch_gm_t(const Geom &g, const PlanLayout &L, const void *plan, con
     }
     const char *base = (const char *)plan;
     const int4 *work = (const int4 *)(base + L.off_work), *sorted = work + L.work_head + L.work_cap;
+    // The persistent launch over the work list (unbalanced plans; its workgroups leave at once otherwise) hands its entries
+    // out by tickets when its planes fit the call's counters, else round robin; the launch before it zeroes the counters.
+    if (nplanes > kTicketPlanes) tickets = nullptr;
     hipLaunchKernelGGL((interp_mfma_kernel<W, false>), blocks, dim3(kGmThreads), sizeof(GatherMfmaLds), stream, g, to,
-                       spos, grid, (int)Cr, (int)plane0, yr, seg_slabs, nsegm, work, sorted, WorkTickets{nullptr, 0u});
-    // the persistent launch over the work list (unbalanced plans; its workgroups leave at once otherwise); entries are
-    // handed out by tickets when the launch's planes fit its share of the ticket ring, else round robin
-    const WorkTickets tickets{nplanes <= kTicketPlanes ? device_ticket_ring() : nullptr, next_launch_number()};
+                       spos, grid, (int)Cr, (int)plane0, yr, seg_slabs, nsegm, work, sorted, tickets);
     const dim3 oblocks(work_list_workgroups(n, nsets, pencils, nsegm, device_cu_count()), (unsigned)nplanes);
     hipLaunchKernelGGL((interp_mfma_kernel<W, true>), oblocks, dim3(kGmThreads), sizeof(GatherMfmaLds), stream, g,
                        to, spos, grid, (int)Cr, (int)plane0, yr, seg_slabs, nsegm, work, sorted, tickets);
@@ -302,20 +303,20 @@ static int launch_gm_t(const Geom &g, const PlanLayout &L, const void *plan, con
 }
 
 int launch_interp_mfma(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                       int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream)
+                       int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
 {
     const char *base = (const char *)plan;
     const int *to = (const int *)(base + L.off_offsets);
     const float *spos = (const float *)(base + L.off_spos);
     if (nplanes <= 0 || n <= 0) return 0;
     switch (g.m) {
-    case 1: return launch_gm_t<4>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 2: return launch_gm_t<6>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 3: return launch_gm_t<8>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 4: return launch_gm_t<10>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 5: return launch_gm_t<12>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 6: return launch_gm_t<14>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 7: return launch_gm_t<16>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, stream);
+    case 1: return launch_gm_t<4>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 2: return launch_gm_t<6>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 3: return launch_gm_t<8>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 4: return launch_gm_t<10>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 5: return launch_gm_t<12>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 6: return launch_gm_t<14>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 7: return launch_gm_t<16>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
     }
     set_error("matrix-core interpolation supports cutoff 1..7");
     return 1;

@@ -96,9 +96,10 @@ __global__ void __launch_bounds__(kIsThreads) __attribute__((amdgpu_waves_per_eu
 interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const int *__restrict__ group_starts,
                      const float *__restrict__ spos, const float *__restrict__ grid,
                      const int Cr, const int plane0, float *__restrict__ yr, const int seg_slabs, const int nsegm,
-                     const int4 *__restrict__ work, const int4 *__restrict__ sorted, const WorkTickets tickets, int *__restrict__ status)
+                     const int4 *__restrict__ work, const int4 *__restrict__ sorted, int *tickets, int *__restrict__ status)
 {
     constexpr int m = W / 2 - 1;
+    if constexpr (!OVERFLOW) reset_tickets(tickets);
     constexpr int TC = 17 - W;                                   // slabs per chunk
     constexpr int SPAN = TC + W - 1;                             // planes a chunk's blocks may touch
     constexpr int NKS = NG == 3 ? 2 : 4;  // k-steps of a block
@@ -126,11 +127,11 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
     const int2 set_hdr = OVERFLOW ? ((const int2 *)(work + 1))[b] : make_int2(1, 0);
     const int n_items = set_hdr.x;
     const int4 *const entries = sorted + set_hdr.y;
-    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1, plane_local) : 0; item < n_items;
-         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item, plane_local) : 1) {
+    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : 0; item < n_items;
+         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : 1) {
     int pencil, sb, se;
     if constexpr (OVERFLOW) {
-        const int4 it = tickets.ring ? entries[item] : listed_item(entries, item, n_items);
+        const int4 it = tickets ? entries[item] : listed_item(entries, item, n_items);
         pencil = it.x - b * pencils;
         sb = it.y;
         se = it.z;
@@ -519,7 +520,7 @@ bool interp_stream_supported(const Geom &g) { return g.dim == 3 && g.wide && !g.
 
 template <int W, int NG>
 static int launch_is_t(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                       int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream)
+                       int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
 {
     const char *base = (const char *)plan;
     const int *to = (const int *)(base + L.off_offsets);
@@ -541,11 +542,11 @@ static int launch_is_t(const Geom &g, const PlanLayout &L, const void *plan, con
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(StreamLds)));
         attr_done.mark();
     }
+    // The persistent launch over the work list (unbalanced plans; its workgroups leave at once otherwise) hands its entries
+    // out by tickets when its planes fit the call's counters, else round robin; the launch before it zeroes the counters.
+    if (nplanes > kTicketPlanes) tickets = nullptr;
     hipLaunchKernelGGL((interp_stream_kernel<W, false, NG>), blocks, dim3(kIsThreads), sizeof(StreamLds), stream, g, to, gs,
-                       spos, grid, (int)Cr, (int)plane0, yr, seg_slabs, nsegm, work, sorted, WorkTickets{nullptr, 0u}, status);
-    // the persistent launch over the work list (unbalanced plans; its workgroups leave at once otherwise); entries are
-    // handed out by tickets when the launch's planes fit its share of the ticket ring, else round robin
-    const WorkTickets tickets{nplanes <= kTicketPlanes ? device_ticket_ring() : nullptr, next_launch_number()};
+                       spos, grid, (int)Cr, (int)plane0, yr, seg_slabs, nsegm, work, sorted, tickets, status);
     const dim3 oblocks(work_list_workgroups(n, nsets, pencils, nsegm, device_cu_count()), (unsigned)nplanes);
     hipLaunchKernelGGL((interp_stream_kernel<W, true, NG>), oblocks, dim3(kIsThreads), sizeof(StreamLds), stream, g, to,
                        gs, spos, grid, (int)Cr, (int)plane0, yr, seg_slabs, nsegm, work, sorted, tickets, status);
@@ -555,24 +556,24 @@ static int launch_is_t(const Geom &g, const PlanLayout &L, const void *plan, con
 
 template <int W>
 static int launch_is_w(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                       int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream)
+                       int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
 {
-    return L.grouped ? launch_is_t<W, 3>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream)
-                     : launch_is_t<W, 1>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
+    return L.grouped ? launch_is_t<W, 3>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream)
+                     : launch_is_t<W, 1>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
 }
 
 int launch_interp_stream(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                         int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream)
+                         int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
 {
     if (nplanes <= 0 || n <= 0) return 0;
     switch (g.m) {
-    case 1: return launch_is_w<4>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 2: return launch_is_w<6>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 3: return launch_is_w<8>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 4: return launch_is_w<10>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 5: return launch_is_w<12>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 6: return launch_is_w<14>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
-    case 7: return launch_is_w<16>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, stream);
+    case 1: return launch_is_w<4>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 2: return launch_is_w<6>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 3: return launch_is_w<8>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 4: return launch_is_w<10>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 5: return launch_is_w<12>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 6: return launch_is_w<14>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    case 7: return launch_is_w<16>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
     }
     set_error("matrix-core interpolation supports cutoff 1..7");
     return 1;

@@ -34,10 +34,12 @@ bool spread_mfma_supported(const Geom &g);
 int launch_plane_absmax(const Geom &g_halo, const PlanLayout &L_halo, const void *plan_halo, const float *xr, int64_t n,
                         int64_t B, int64_t Cr, unsigned *xmax, hipStream_t stream);
 // coefficients: xr (row-major [point][Cr], read through the index in the plan records) or, when xr == nullptr, xs (copy in
-// plan order, planar, stride L.cap: gather_rows)
+// plan order, planar, stride L.cap: gather_rows).  tickets: kTicketPlanes ints of the caller's workspace, the counters of
+// the persistent launch over the plan's work list (common.h: next_work_item); nullptr: round robin.  The same for the
+// matrix-core gathers below.
 int launch_spread_mfma(const Geom &g, const PlanLayout &L, const void *plan, const float *xr, const float *xs,
                        const unsigned *xmax, int64_t n, int64_t Cr, int64_t plane0, int64_t nplanes, float *grid,
-                       hipStream_t stream);
+                       int *tickets, hipStream_t stream);
 
 // interp.hip: yr[perm[slot] * Cr + cr] = sum over taps of grid[p, ...]
 int launch_interp(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
@@ -55,18 +57,18 @@ int launch_grad_reduce(const float *part, int64_t len, int64_t Cr, float *dpos, 
 // matrix-core gather for the wide 3-D tiling (interp_mfma.hip)
 bool interp_mfma_supported(const Geom &g);
 int launch_interp_mfma(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                       int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream);
+                       int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream);
 
 // streamed variant (interp_stream.hip): producer waves feed the plane ring, consumer waves pull blocks from a queue
 bool interp_stream_supported(const Geom &g);
 bool interp_stream_pays(const Geom &g, const PlanLayout &L, int64_t n);  // big work items only
 int launch_interp_stream(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                         int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream);
+                         int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream);
 // several coefficient columns per workgroup, one wave per column (interp_cols.hip): the point-side operands are built
 // once for 8 columns, each wave streams its own column's planes from global memory
 bool interp_cols_supported(const Geom &g);
 int launch_interp_cols(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                       int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream);
+                       int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream);
 
 // spectral.hip
 // adjoint roll-off: spec = R2C(grid) per real plane [nplanes, M^(d-1) * (M/2+1)] complex -> y [B, N^d, C]

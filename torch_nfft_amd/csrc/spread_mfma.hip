@@ -144,9 +144,10 @@ spread_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets, const flo
                    const float *__restrict__ xr, const float *__restrict__ xs, const int64_t xs_stride,
                    const unsigned *__restrict__ xmax, const int Cr,
                    const int plane0, const int nplanes, float *__restrict__ grid, const int seg_slabs, const int nsegm,
-                   const int4 *__restrict__ work, const int4 *__restrict__ sorted, const WorkTickets tickets, int *__restrict__ status)
+                   const int4 *__restrict__ work, const int4 *__restrict__ sorted, int *tickets, int *__restrict__ status)
 {
     static_assert(!PAIR || OWNED, "the paired variant is an owner-computes kernel");
+    if constexpr (!OVERFLOW) reset_tickets(tickets);
     constexpr int m = W / 2 - 1;
     constexpr int TW = PAIR ? 32 : 64;  // columns of the accumulator tile
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -188,12 +189,12 @@ spread_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets, const flo
     const int2 set_hdr = OVERFLOW ? ((const int2 *)(work + 1))[b] : make_int2(1, 0);
     const int n_items = set_hdr.x;
     const int4 *const entries = sorted + set_hdr.y;
-    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1, (int)blockIdx.y) : 0; item < n_items;
-         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item, (int)blockIdx.y) : 1) {
+    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : 0; item < n_items;
+         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : 1) {
     if (OVERFLOW && item != (int)blockIdx.x) __syncthreads();  // the previous item is done with the LDS
     int pencil, sb, se;
     if constexpr (OVERFLOW) {
-        const int4 it = tickets.ring ? entries[item] : listed_item(entries, item, n_items);
+        const int4 it = tickets ? entries[item] : listed_item(entries, item, n_items);
         pencil = it.x - b * pencils;
         sb = it.y;
         se = it.z;
@@ -847,7 +848,7 @@ int launch_plane_absmax(const Geom &g_halo, const PlanLayout &L_halo, const void
 template <int W, bool OWNED, bool PAIR>
 static int launch_mfma_t(const Geom &g, const PlanLayout &L, const void *plan, const int *to, const float *spos,
                          const float *xr, const float *xs, const unsigned *xmax, int64_t n, int64_t Cr, int64_t plane0,
-                         int64_t nplanes, float *grid, hipStream_t stream)
+                         int64_t nplanes, float *grid, int *tickets, hipStream_t stream)
 {
     // Ranges per pencil: about 5-6 workgroups per CU balance the tail of the launch against the 2m+1 halo planes
     // every range flushes on top of its own (measured at C3: 6 ranges 7 % faster than 4, 12 in between).  The count
@@ -876,12 +877,12 @@ static int launch_mfma_t(const Geom &g, const PlanLayout &L, const void *plan, c
     const char *base = (const char *)plan;
     const int4 *work = (const int4 *)(base + L.off_work), *sorted = work + L.work_head + L.work_cap;
     int *const status = device_status_block();
+    // The persistent launch over the work list (unbalanced plans; its workgroups leave at once otherwise) hands its entries
+    // out by tickets when its planes fit the call's counters, else round robin; the launch before it zeroes the counters.
+    if (ny > kTicketPlanes) tickets = nullptr;
     hipLaunchKernelGGL((spread_mfma_kernel<W, false, OWNED, PAIR>), blocks, dim3(kMfmaThreads), sizeof(MfmaLds<W>), stream, g, to,
                        spos, xr, xs, L.cap, xmax, (int)Cr, (int)plane0, (int)nplanes, grid, seg_slabs, nsegm, work, sorted,
-                       WorkTickets{nullptr, 0u}, status);
-    // the persistent launch over the work list (unbalanced plans; its workgroups leave at once otherwise); entries are
-    // handed out by tickets when the launch's planes fit its share of the ticket ring, else round robin
-    const WorkTickets tickets{ny <= kTicketPlanes ? device_ticket_ring() : nullptr, next_launch_number()};
+                       tickets, status);
     const dim3 oblocks(work_list_workgroups(n, nsets, pencils, nsegm, device_cu_count()), (unsigned)ny);
     hipLaunchKernelGGL((spread_mfma_kernel<W, true, OWNED, PAIR>), oblocks, dim3(kMfmaThreads), sizeof(MfmaLds<W>), stream, g, to,
                        spos, xr, xs, L.cap, xmax, (int)Cr, (int)plane0, (int)nplanes, grid, seg_slabs, nsegm, work, sorted, tickets,
@@ -893,19 +894,19 @@ static int launch_mfma_t(const Geom &g, const PlanLayout &L, const void *plan, c
 template <bool OWNED, bool PAIR>
 static int launch_mfma_w(const Geom &g, const PlanLayout &L, const void *plan, const float *xr, const float *xs,
                          const unsigned *xmax, int64_t n, int64_t Cr, int64_t plane0, int64_t nplanes, float *grid,
-                         hipStream_t stream)
+                         int *tickets, hipStream_t stream)
 {
     const char *base = (const char *)plan;
     const int *to = (const int *)(base + L.off_offsets);
     const float *spos = (const float *)(base + L.off_spos);
     switch (g.m) {
-    case 1: return launch_mfma_t<4, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, stream);
-    case 2: return launch_mfma_t<6, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, stream);
-    case 3: return launch_mfma_t<8, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, stream);
-    case 4: return launch_mfma_t<10, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, stream);
-    case 5: return launch_mfma_t<12, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, stream);
-    case 6: return launch_mfma_t<14, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, stream);
-    case 7: return launch_mfma_t<16, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, stream);
+    case 1: return launch_mfma_t<4, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
+    case 2: return launch_mfma_t<6, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
+    case 3: return launch_mfma_t<8, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
+    case 4: return launch_mfma_t<10, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
+    case 5: return launch_mfma_t<12, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
+    case 6: return launch_mfma_t<14, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
+    case 7: return launch_mfma_t<16, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
     }
     set_error("matrix-core spreading supports cutoff 1..7");
     return 1;
@@ -918,7 +919,7 @@ static int launch_mfma_w(const Geom &g, const PlanLayout &L, const void *plan, c
 // xmax: largest |x| of every plane [B * Cr] (launch_plane_absmax), indexed by the global plane number plane0 + p.
 int launch_spread_mfma(const Geom &g, const PlanLayout &L, const void *plan, const float *xr, const float *xs,
                        const unsigned *xmax, int64_t n, int64_t Cr, int64_t plane0, int64_t nplanes, float *grid,
-                       hipStream_t stream)
+                       int *tickets, hipStream_t stream)
 {
     if (nplanes <= 0) return 0;
     if (n <= 0) {
@@ -929,9 +930,9 @@ int launch_spread_mfma(const Geom &g, const PlanLayout &L, const void *plan, con
         set_error("Input mismatch: a plan of the paired owned tiling (num_columns >= 2) used with one real column");
         return 1;
     }
-    return g.pair    ? launch_mfma_w<true, true>(g, L, plan, xr, xs, xmax, n, Cr, plane0, nplanes, grid, stream)
-           : g.owned ? launch_mfma_w<true, false>(g, L, plan, xr, xs, xmax, n, Cr, plane0, nplanes, grid, stream)
-                     : launch_mfma_w<false, false>(g, L, plan, xr, xs, xmax, n, Cr, plane0, nplanes, grid, stream);
+    return g.pair    ? launch_mfma_w<true, true>(g, L, plan, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream)
+           : g.owned ? launch_mfma_w<true, false>(g, L, plan, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream)
+                     : launch_mfma_w<false, false>(g, L, plan, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
 }
 
 } // namespace nfft
