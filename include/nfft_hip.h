@@ -139,6 +139,22 @@ int nfft_hip_forward_grad_points_planned(const nfft_hip_problem *p, const void *
 int nfft_hip_forward_value_grad_points_planned(const nfft_hip_problem *p, const void *plan, const void *xhat,
                                                int x_is_complex, int real_output, const float *w, void *y, float *dpos,
                                                void *workspace, int64_t workspace_bytes, void *stream);
+/* The backward of that gradient, for second derivatives (double backward of both transforms).  With
+ * G[i, a] = sum_cr w[i, cr] d Fr[i, cr] / d pos[i, a] as nfft_hip_forward_grad_points_planned computes it and an upstream
+ * v float32 [n, dim] (caller order), any subset of
+ *     dxhat  d<v, G>/d xhat = sum_a 2 pi i k_a adjoint(pos, omega v_a),  omega = w_re + i w_im (w with real_output);
+ *            xhat's layout and type (the real part for real xhat)
+ *     dw     float32 [n, Cr]:  dw[i, cr] = sum_a v[i, a] d Fr[i, cr] / d pos[i, a]
+ *     dpos   float32 [n, dim]: dpos[i, b] = sum_cr w[i, cr] sum_a v[i, a] d^2 Fr[i, cr] / d pos[i, a] d pos[i, b]
+ * NULL outputs are skipped.  dw and dpos come from one gather of the window's first and second derivatives on the forward
+ * transform's grid, deterministic like the first-order gather; dxhat from the derivative spreading of w and the
+ * adjoint's FFT stage on 1-D, 2-D and narrow 3-D tilings, else from dim adjoints of omega v_a on the same plan.
+ * No points or no columns: zeros.  w may be NULL when only dw is asked for.  Workspace: the query below. */
+int64_t nfft_hip_forward_grad_points_backward_workspace_bytes(const nfft_hip_problem *p, int x_is_complex, int real_output);
+int nfft_hip_forward_grad_points_backward_planned(const nfft_hip_problem *p, const void *plan, const void *xhat,
+                                                  int x_is_complex, int real_output, const float *w, const float *v,
+                                                  void *dxhat, float *dw, float *dpos, void *workspace,
+                                                  int64_t workspace_bytes, void *stream);
 
 /* ---- stage-level entry points (used by the parity tests and by bench.py to time
  * the spreading kernel on its own; the two calls above are built from them) ---- */

@@ -29,6 +29,8 @@ SYMBOLS = (
     "nfft_hip_forward_grad_workspace_bytes",
     "nfft_hip_forward_grad_points_planned",
     "nfft_hip_forward_value_grad_points_planned",
+    "nfft_hip_forward_grad_points_backward_workspace_bytes",
+    "nfft_hip_forward_grad_points_backward_planned",
     "nfft_hip_plan_bytes",
     "nfft_hip_plan_points",
     "nfft_hip_plan_verify",
@@ -115,6 +117,10 @@ def load():
     lib.nfft_hip_forward_grad_points_planned.restype = ci
     lib.nfft_hip_forward_value_grad_points_planned.argtypes = [P, vp, vp, ci, ci, vp, vp, vp, vp, i64, vp]
     lib.nfft_hip_forward_value_grad_points_planned.restype = ci
+    lib.nfft_hip_forward_grad_points_backward_workspace_bytes.argtypes = [P, ci, ci]
+    lib.nfft_hip_forward_grad_points_backward_workspace_bytes.restype = i64
+    lib.nfft_hip_forward_grad_points_backward_planned.argtypes = [P, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.nfft_hip_forward_grad_points_backward_planned.restype = ci
     lib.nfft_hip_plan_needed.argtypes = [P]
     lib.nfft_hip_plan_needed.restype = ci
     lib.nfft_hip_plan_bytes.argtypes = [P]

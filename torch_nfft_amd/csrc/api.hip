@@ -335,6 +335,16 @@ Route plan_route(const nfft_hip_problem *p, int64_t Cr)
     return r;
 }
 
+// dxhat of the second-order backward of the point gradient, given the adjoint route of its problem:
+// the derivative spreading + the adjoint's FFT stage where the LDS spreading kernel takes the plan's tiling (1-D, 2-D and
+// the narrow 3-D tiling), else dim adjoints of omega v_a with the spectral multipliers 2 pi i k_a.  (The wide tiling's
+// spreading runs on matrix cores, whose tap weights are a product of per-axis windows: the derivative's sum over the axes
+// is not.)  NFFT_HIP_DXHAT=compose takes the composition everywhere (scripts/bench_pos_hvp.py compares the two).
+bool hvp_fused_dxhat(const Route &ra)
+{
+    return spread_deriv_supported(ra.g) && env("NFFT_HIP_DXHAT")[0] != 'c';
+}
+
 // The whole route of an adjoint (x: ppc real planes per column) or forward transform (y: ppc real planes per column),
 // the chunk size and the workspace carve included.
 int make_route(const nfft_hip_problem *p, int ppc, bool adjoint, Route &r)
@@ -873,6 +883,117 @@ int nfft_hip_forward_value_grad_points_planned(const nfft_hip_problem *p, const 
     if (!y && p && p->num_points > 0 && p->num_columns > 0) { set_error("Input mismatch: y is null"); return NFFT_HIP_EINVAL; }
     return forward_grad_impl(p, plan, xhat, x_is_complex, real_output, w, (float *)y, dpos, workspace, workspace_bytes,
                              (hipStream_t)stream);
+}
+
+// ---- backward of the point gradient: second derivatives -------------------------------------
+namespace {
+// Workspace: the gradient gather's (forward route + partial sums) for dw / dpos, then, reusing the same bytes, for dxhat
+// an adjoint of the same problem (u = omega v_a as its input: complex unless real_output) + u [n, Cr] + its output
+// [B, N^dim, C] complex.
+struct HvpCarve {
+    int64_t grad_total, adj_total, off_u, off_y, total;
+};
+int hvp_carve(const nfft_hip_problem *p, int real_output, HvpCarve &h)
+{
+    Route r;
+    int64_t off_part = 0;
+    if (int rc = forward_grad_route(p, real_output, r, off_part, h.grad_total)) return rc;
+    Route ra;
+    if (int rc = make_route(p, real_output ? 1 : 2, true, ra)) return rc;
+    h.adj_total = ra.total;
+    int64_t spec = p->batch_size * p->num_columns;
+    for (int a = 0; a < p->dim; ++a) spec *= p->N;
+    h.off_u = align_up(h.adj_total, 256);
+    h.off_y = align_up(h.off_u + p->num_points * r.Cr * 4, 256);
+    h.total = std::max(h.grad_total, h.off_y + spec * 8 + 256);
+    return 0;
+}
+} // namespace
+
+int64_t nfft_hip_forward_grad_points_backward_workspace_bytes(const nfft_hip_problem *p, int x_is_complex, int real_output)
+{
+    (void)x_is_complex;
+    if (validate(p)) return -1;
+    HvpCarve h;
+    if (hvp_carve(p, real_output, h)) return -1;
+    return h.total;
+}
+
+int nfft_hip_forward_grad_points_backward_planned(const nfft_hip_problem *p, const void *plan, const void *xhat,
+                                                  int x_is_complex, int real_output, const float *w, const float *v,
+                                                  void *dxhat, float *dw, float *dpos, void *workspace,
+                                                  int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate(p)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (!dxhat && !dw && !dpos) return 0;
+    const int64_t n = p->num_points, C = p->num_columns, Cr = C * (real_output ? 1 : 2);
+    int64_t spec = p->batch_size * C;
+    for (int a = 0; a < p->dim; ++a) spec *= p->N;
+    if (n == 0 || C == 0) {  // no points or no columns: G is empty or identically zero, and so is every derivative of it
+        if (dxhat) NFFT_HIP_CHECK(hipMemsetAsync(dxhat, 0, (size_t)(spec * (x_is_complex ? 8 : 4)), s));
+        if (dpos) NFFT_HIP_CHECK(hipMemsetAsync(dpos, 0, (size_t)(n * p->dim * 4), s));
+        return 0;  // (dw has n * Cr = 0 elements)
+    }
+    if (!plan || !xhat || !v || ((dpos || dxhat) && !w)) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    {
+        // a missing workspace, or one below the partial gradients plus one chunk of grid planes, is refused before the
+        // routes make their rocFFT plans (as in forward_grad_impl)
+        const int64_t least = (Cr > 1 ? Cr * n * p->dim * 4 : 0) + problem_geom(p).cells * 4 * (real_output ? 1 : 2);
+        if (!workspace || workspace_bytes < least) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    }
+    HvpCarve h;
+    if (int rc = hvp_carve(p, real_output, h)) return rc;
+    if (workspace_bytes < h.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    if (dw || dpos) {
+        // the moment gather on the forward transform's grid, chunk by chunk as the gradient gather runs
+        Route r;
+        int64_t off_part = 0, total = 0;
+        if (int rc = forward_grad_route(p, real_output, r, off_part, total)) return rc;
+        float *grid = (float *)(ws + r.off_grid);
+        float2 *spec_buf = (float2 *)(ws + r.off_spec);
+        float *part = !dpos ? nullptr : r.Cr > 1 ? (float *)(ws + off_part) : dpos;
+        for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes) {
+            const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
+            if (int rc = fft_forward_chunk(r, ws, xhat, x_is_complex, real_output, p0, np, grid, spec_buf, s)) return rc;
+            StageTimer t(kStageInterp, s);
+            if (int rc = launch_interp_hvp(r.g, r.L, plan, grid, n, r.Cr, p0, np, w, v, dw, part, s)) return rc;
+        }
+        if (dpos && r.Cr > 1)
+            if (int rc = launch_grad_reduce(part, n * p->dim, r.Cr, dpos, s)) return rc;
+    }
+    if (dxhat) {
+        Route ra;
+        if (int rc = make_route(p, real_output ? 1 : 2, true, ra)) return rc;
+        if (hvp_fused_dxhat(ra)) {
+            // the derivative spreading of w, then the adjoint's own FFT stage and roll-off, chunk by chunk
+            float *grid = (float *)(ws + ra.off_grid);
+            float2 *spec_buf = (float2 *)(ws + ra.off_spec);
+            for (int64_t p0 = 0; p0 < ra.total_planes; p0 += ra.chunk_planes) {
+                const int64_t np = std::min(ra.chunk_planes, ra.total_planes - p0);
+                { StageTimer t(kStageZero, s); NFFT_HIP_CHECK(hipMemsetAsync(grid, 0, (size_t)(np * ra.g.cells * 4), s)); }
+                {
+                    StageTimer t(kStageSpread, s);
+                    if (int rc = launch_spread_deriv(ra.g, ra.L, plan, w, v, n, ra.Cr, p0, np, grid, s)) return rc;
+                }
+                if (int rc = fft_adjoint_chunk(ra, ws, grid, spec_buf, real_output ? 0 : 1, x_is_complex ? 0 : 1, p0, np, dxhat,
+                                               nullptr, 0, s))
+                    return rc;
+            }
+            return 0;
+        }
+        // sum_a 2 pi i k_a adjoint(omega v_a), axes in order (hvp_spectral.hip)
+        float *u = (float *)(ws + h.off_u);
+        void *y = ws + h.off_y;
+        for (int a = 0; a < p->dim; ++a) {
+            if (int rc = launch_hvp_stage(w, v, n, Cr, p->dim, a, u, s)) return rc;
+            if (int rc = adjoint_impl(p, nullptr, nullptr, plan, u, real_output ? 0 : 1, 0, y, ws, h.adj_total, stream)) return rc;
+            if (int rc = launch_hvp_combine(y, p->batch_size, p->N, p->dim, C, a, a > 0, x_is_complex, dxhat, s)) return rc;
+        }
+    }
+    return 0;
 }
 
 // ---- fast summation -------------------------------------------------------------------------

@@ -452,6 +452,56 @@ at::Tensor nfft_forward_grad_points(at::Tensor pos, at::Tensor x, c10::optional<
     return dpos;
 }
 
+// not in the reference: the backward of _nfft_forward_grad_points for an upstream v [n, dim] (second derivatives of both
+// transforms; include/nfft_hip.h nfft_hip_forward_grad_points_backward_planned).  Returns (dxhat, dw, dpos) -- xhat's shape
+// and type, [n, Cr] and [n, dim] float32; what was not asked for is an empty tensor.  Same checks and problem as
+// _nfft_forward_grad_points, so the plan its forward pass cached is reused.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> nfft_forward_grad_points_backward(
+    at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch, int64_t m, int64_t real_output, at::Tensor w,
+    at::Tensor v, int64_t need_xhat, int64_t need_w, int64_t need_pos)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_forward_grad_points_backward is only implemented for GPU tensors");
+    const Points p = check_points(pos, opt_batch, "(*out_batch)");
+    const bool real_input = real_dtype(x);
+    CHECK_INPUT(x.dim() >= p.dim + 1);
+    CHECK_INPUT(x.size(0) == p.B);
+    CHECK_INPUT(x.device() == pos.device());
+    const int64_t N = x.size(1);
+    CHECK_INPUT(N >= 2);
+    for (int d = 2; d <= p.dim; ++d) CHECK_INPUT(x.size(d) == N);
+    int64_t C = 1;
+    for (int64_t d = p.dim + 1; d < x.dim(); ++d) C *= x.size(d);
+    const int64_t Cr = real_output ? C : 2 * C;
+    CHECK_INPUT(w.is_cuda() && w.device() == pos.device());
+    CHECK_INPUT(w.scalar_type() == at::kFloat);
+    CHECK_INPUT(w.numel() == p.n * Cr);
+    CHECK_INPUT(v.is_cuda() && v.device() == pos.device());
+    CHECK_INPUT(v.scalar_type() == at::kFloat);
+    CHECK_INPUT(v.numel() == p.n * p.dim);
+    const at::TensorOptions fo = pos.options();
+    at::Tensor dx = need_xhat ? at::empty_like(x, at::MemoryFormat::Contiguous) : at::empty({0}, x.options());
+    at::Tensor dw = need_w ? at::empty({p.n, Cr}, fo) : at::empty({0}, fo);
+    at::Tensor dp = need_pos ? at::empty({p.n, (int64_t)p.dim}, fo) : at::empty({0}, fo);
+    if (!need_xhat && !need_w && !need_pos) return {dx, dw, dp};
+    if (p.n == 0 || C == 0) {  // G is empty or zero: so is every derivative of it, no native call
+        if (need_xhat) dx.zero_();
+        if (need_pos) dp.zero_();
+        return {dx, dw, dp};
+    }
+    const at::Tensor xc = x.contiguous(), wc = w.contiguous(), vc = v.contiguous();
+    const nfft_hip_problem q = problem(p, C, N, m);
+    c10::DeviceGuard guard(x.device());
+    const int64_t ws_bytes = nfft_hip_forward_grad_points_backward_workspace_bytes(&q, real_input ? 0 : 1, real_output ? 1 : 0);
+    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
+    at::Tensor ws = byte_buffer(ws_bytes, x);
+    const at::Tensor plan = get_plan(p, q);
+    check_rc(nfft_hip_forward_grad_points_backward_planned(
+        &q, plan.data_ptr(), xc.data_ptr(), real_input ? 0 : 1, real_output ? 1 : 0, wc.data_ptr<float>(),
+        vc.data_ptr<float>(), need_xhat ? dx.data_ptr() : nullptr, need_w ? dw.data_ptr<float>() : nullptr,
+        need_pos ? dp.data_ptr<float>() : nullptr, ws.data_ptr(), ws_bytes, stream_of(x)));
+    return {dx, dw, dp};
+}
+
 // Inputs of a fast summation, checked as the reference does (core_cuda.cu:535-590), and its two problems.
 struct Fastsum {
     Points ps, pt;
@@ -712,6 +762,10 @@ TORCH_LIBRARY(torch_nfft, m)
     // not in the reference: gradient of nfft_forward with respect to the points (autograd of both transforms)
     m.def("_nfft_forward_grad_points(Tensor pos, Tensor x, Tensor? batch, int m, int real_output, Tensor w) -> Tensor",
           &nfft_forward_grad_points);
+    // not in the reference: its backward, for second derivatives of both transforms
+    m.def("_nfft_forward_grad_points_backward(Tensor pos, Tensor xhat, Tensor? batch, int m, int real_output, Tensor w, "
+          "Tensor v, int need_xhat, int need_w, int need_pos) -> (Tensor, Tensor, Tensor)",
+          &nfft_forward_grad_points_backward);
     // not in the reference: gradient of nfft_fastsum with respect to the points (autograd of nfft_fastsum)
     m.def("_nfft_fastsum_band(Tensor sources, Tensor targets, Tensor x, Tensor coeffs, Tensor? source_batch, "
           "Tensor? target_batch, int m) -> (Tensor, Tensor)", &nfft_fastsum_band);

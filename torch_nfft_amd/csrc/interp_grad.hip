@@ -49,6 +49,9 @@ struct GradCfg {
     // y pointer needs -- its 62 VGPRs still give 8 waves.  (2-D m = 2 keeps 8: at 7 it takes 65 VGPRs and loses a wave, at
     // 8 six SGPRs live in VGPR lanes -- v_writelane / v_readlane, no scratch.)
     static constexpr int WPE_VALUE = DIM == 2 && (W == 10 || W == 4) ? 7 : WPE;
+    // the second-order gather (interp_hvp_kernel): the gradient kernel's occupancy, except three kernels one wave lower,
+    // where its two more moments would otherwise spill VGPRs to scratch (1-D and 2-D m = 8, narrow 3-D m = 2)
+    static constexpr int WPE_HVP = DIM == 2 && W == 10 ? 7 : (DIM <= 2 && W == 18) || (DIM == 3 && !WIDE && W == 6) ? WPE - 1 : WPE;
     static_assert(CELLS * 4 <= 160 * 1024, "LDS budget");
 };
 
@@ -264,6 +267,218 @@ grad_reduce_kernel(const float *__restrict__ part, const int64_t len, const int 
     }
 }
 
+// Second-order gather (the backward of the weighted gradient gather G above).  For an upstream v
+// [n, dim] (user axes), with q = sum_a v[i, a] t_a and the same deconvolved, FFT'd grid:
+//     dw[i, cr]               = norm dk sum_l g psi q                                   (sum_a v_a d Fr / d pos_a)
+//     part[(cr * n + i) * DIM + b] = w[i, cr] norm (dk^2 T_b + dk M v_b S0)               (the Hessian-vector gather)
+// where S0 = sum_l g psi, T_b = sum_l g psi t_b q and psi is the product window: d + 2 accumulators with v folded in.
+// Same plan, plane loading and lane-per-point walk as interp_grad_kernel.  Along axis 2 a row gives A = sum psi2 g,
+// B = sum psi2 t2 g and C2 = sum psi2 t2^2 g = tau2 B - sum k psi2 t2 g, whose k-weighted sum is the running suffix sum
+// of interp_grad_kernel.  dw is written once per (plane, point); the partial
+// gradients are summed over the planes by grad_reduce_kernel in a fixed order: bitwise reproducible.  dw or part may be null.
+template <int DIM, int W, bool WIDE>
+__global__ void __launch_bounds__((GradCfg<DIM, W, WIDE>::NT))
+__attribute__((amdgpu_waves_per_eu(GradCfg<DIM, W, WIDE>::WPE_HVP)))
+interp_hvp_kernel(const Geom g, const int *__restrict__ tile_offsets, const int *__restrict__ perm,
+                  const float *__restrict__ spos, const float *__restrict__ grid, const int Cr, const int plane0,
+                  const float *__restrict__ w, const float *__restrict__ v, const int64_t n, float *__restrict__ dw,
+                  float *__restrict__ part)
+{
+    using C = GradCfg<DIM, W, WIDE>;
+    constexpr int NT = C::NT;
+    constexpr int NWAVES = C::NWAVES;
+    __shared__ float4 planes4[C::CELLS / 4];
+    float *const planes = (float *)planes4;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+
+    const int seg = blockIdx.x % g.nseg;
+    const int pencil = blockIdx.x / g.nseg;
+    const int j2 = pencil % g.nta[2];
+    const int j1 = pencil / g.nta[2];
+    const int plane_local = blockIdx.y;
+    const int plane = plane0 + plane_local;
+    const int b = plane / Cr;
+    const int cr = plane - b * Cr;
+
+    const int k_begin = seg * kSegChunks;
+    const int k_end = min(g.nta[0], k_begin + kSegChunks);
+    const int bin0 = b * g.tiles_per_batch + pencil * g.np0;
+    {
+        int s0, e0, s1, e1;
+        chunk_range(g, tile_offsets, bin0, k_begin, s0, e0);
+        chunk_range(g, tile_offsets, bin0, k_end - 1, s1, e1);
+        if (s0 == e1) return;
+    }
+
+    const int m = g.m;
+    const int tb1 = j1 * g.Ta[1], tb2 = j2 * g.Ta[2];
+    const float sc = win_exp_scale(m);
+    const float dk = -(4.71238898038469f / (float)m) * (float)g.M;  // -2 (3 pi / 4) / m * M
+    const float Mf = (float)g.M;
+    float norm = win_norm(m);
+    norm = DIM == 3 ? norm * norm * norm : (DIM == 2 ? norm * norm : norm);
+    const float *const gplane = grid + (int64_t)plane_local * g.cells;
+    float *const out = part ? part + (int64_t)cr * n * DIM : nullptr;
+
+    int base_z = 0, have = 0;
+    const int nsplit = gridDim.z, split = blockIdx.z;
+    for (int k = k_begin; k < k_end; ++k) {
+        int s, e;
+        chunk_range(g, tile_offsets, bin0, k, s, e);
+        if (nsplit > 1) {
+            const int span = (e - s + nsplit - 1) / nsplit;
+            s = min(e, s + split * span);
+            e = min(e, s + span);
+        }
+        if (e == s) continue;
+        const int want_z = k * C::TC - C::M0OFF;
+        // resident planes: slide the ones still needed down, fetch the rest (interp.hip)
+        const int shift = have > 0 ? min(want_z - base_z, have) : 0;
+        const int kept = have - shift;
+        __syncthreads();
+        if (kept > 0) {
+            for (int lo = 0; lo < kept * C::S0; lo += shift * C::S0) {
+                const int hi = min(lo + shift * C::S0, kept * C::S0);
+                for (int idx = lo + tid; idx < hi; idx += NT) planes[idx] = planes[idx + shift * C::S0];
+                __syncthreads();
+            }
+        }
+        for (int row = kept * C::P1 + wave; row < C::NP * C::P1; row += NWAVES) {
+            const int p = row / C::P1;
+            const int r = row - p * C::P1;
+            const int64_t gz = DIM == 3 ? wrap(want_z + p, g.Ma[0]) : 0;
+            const int64_t g1 = DIM >= 2 ? wrap(tb1 - m + r, g.Ma[1]) : 0;
+            const float *const grow = gplane + (gz * g.Ma[1] + g1) * g.Ma[2];
+            for (int c = lane; c < C::S2; c += 64)
+                planes[row * C::S2 + c] = c < C::P2 ? grow[wrap_near(tb2 - m + c, g.Ma[2])] : 0.0f;
+        }
+        base_z = want_z;
+        have = C::NP;
+        __syncthreads();
+        const int tb0 = k * C::TC;
+
+        for (int j0 = s + wave * 64; j0 < e; j0 += NWAVES * 64) {
+            const int j = j0 + lane;
+            if (j >= e) continue;
+            int c0 = 0, c1 = 0, c2 = 0;
+            float f0 = 0.f, f1 = 0.f, f2 = 0.f;
+            int idx;
+            if (DIM == 3) {
+                const f32x4 rec = *(const f32x4 *)(spos + (int64_t)j * 4);  // {p0, p1, p2, index}
+                split_cell(rec.x, g.M, c0, f0);
+                split_cell(rec.y, g.M, c1, f1);
+                split_cell(rec.z, g.M, c2, f2);
+                idx = __float_as_int(rec.w);
+            } else if (DIM == 2) {
+                split_cell(spos[(int64_t)j * 2 + 0], g.M, c1, f1);
+                split_cell(spos[(int64_t)j * 2 + 1], g.M, c2, f2);
+                idx = perm[j];
+            } else {
+                split_cell(spos[j], g.M, c2, f2);
+                idx = perm[j];
+            }
+            // v on the internal axes (axis 2 is the last user axis)
+            float v0 = 0.0f, v1 = 0.0f, v2;
+            const float *const vi = v + (int64_t)idx * DIM;
+            if (DIM == 3) { v0 = vi[0]; v1 = vi[1]; v2 = vi[2]; }
+            else if (DIM == 2) { v1 = vi[0]; v2 = vi[1]; }
+            else v2 = vi[0];
+            const int col = c2 - tb2;
+            const int sh = col & 3;
+            const float tau2 = f2 + (float)(m + sh);  // t of aligned position k: tau2 - k
+            const float tau1 = f1 + (float)m;         // t of row l1: tau1 - l1
+            // axis-2 window on the aligned positions k = l2 + sh (zero outside the window), as in interp_grad_kernel
+            f32x2 w2[2 * C::NR];
+#pragma unroll
+            for (int q = 0; q < 2 * C::NR; ++q) {
+                float pair[2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int l2 = 2 * q + h - sh;
+                    const float t = f2 + (float)(m - l2);
+                    const float wv = __builtin_amdgcn_exp2f(sc * t * t);
+                    pair[h] = (l2 >= 0 && l2 < W) ? wv : 0.0f;
+                }
+                w2[q] = f32x2{pair[0], pair[1]};
+            }
+            const f32x4 *row0 = (const f32x4 *)(planes + (c0 - tb0) * C::S0 + (c1 - tb1) * C::S2 + (col - sh));
+            float S0 = 0.0f, Q = 0.0f, T0 = 0.0f, T1 = 0.0f, T2 = 0.0f;  // (without norm, dk)
+            for (int l0 = 0; l0 < C::W0; ++l0) {
+                const f32x4 *rowp = row0 + l0 * (C::S0 / 4);
+                float t0 = 0.0f, p0 = 1.0f;
+                if (DIM == 3) {
+                    t0 = f0 + (float)(m - l0);
+                    p0 = __builtin_amdgcn_exp2f(sc * t0 * t0);
+                }
+                const float a0 = v0 * t0;
+                float sA = 0.0f, sE = 0.0f, sE1 = 0.0f, sT2 = 0.0f;
+#pragma unroll 1
+                for (int l1 = 0; l1 < C::W1; ++l1) {
+                    f32x4 vv[C::NR];
+#pragma unroll
+                    for (int q = 0; q < C::NR; ++q) vv[q] = rowp[l1 * (C::S2 / 4) + q];
+                    // pairs from the last down, X = w2 v: SA = sum X, SB = sum t X, TB = sum_P (P + 1) t X.  The t of
+                    // the pairs is recomputed per row: a second weight set held across the rows would spill
+                    float tau = tau2;
+                    asm volatile("" : "+v"(tau));
+                    f32x2 tv = f32x2{tau, tau} - f32x2{(float)(4 * C::NR - 2), (float)(4 * C::NR - 1)};
+                    f32x2 X = w2[2 * C::NR - 1] * vv[C::NR - 1].zw;
+                    f32x2 SA = X;
+                    f32x2 SB = X * tv;
+                    f32x2 TB = SB;
+#pragma unroll
+                    for (int P = 2 * C::NR - 2; P >= 0; --P) {
+                        tv += f32x2{2.0f, 2.0f};  // (exact: small integers apart)
+                        X = w2[P] * ((P & 1) ? vv[P >> 1].zw : vv[P >> 1].xy);
+                        SA += X;
+                        SB = __builtin_elementwise_fma(X, tv, SB);
+                        TB += SB;
+                    }
+                    const float A = SA.x + SA.y;
+                    const float Bm = SB.x + SB.y;
+                    const float KB = 2.0f * (TB.x + TB.y) - 2.0f * SB.x - SB.y;  // sum k t X
+                    const float C2 = fmaf(tau2, Bm, -KB);                        // sum t2^2 psi2 v
+                    float t1 = 0.0f, p1 = 1.0f;
+                    if (DIM >= 2) {
+                        t1 = tau1 - (float)l1;
+                        p1 = __builtin_amdgcn_exp2f(sc * t1 * t1);
+                    }
+                    const float alpha = fmaf(v1, t1, a0);   // v0 t0 + v1 t1
+                    const float E = fmaf(alpha, A, v2 * Bm); // sum psi2 q v
+                    sA = fmaf(p1, A, sA);
+                    sE = fmaf(p1, E, sE);
+                    if (DIM >= 2) sE1 = fmaf(p1 * t1, E, sE1);
+                    sT2 = fmaf(p1, fmaf(alpha, Bm, v2 * C2), sT2);
+                }
+                S0 = fmaf(p0, sA, S0);
+                Q = fmaf(p0, sE, Q);
+                if (DIM == 3) T0 = fmaf(p0 * t0, sE, T0);
+                T1 = fmaf(p0, sE1, T1);
+                T2 = fmaf(p0, sT2, T2);
+            }
+            if (dw) dw[(int64_t)idx * Cr + cr] = Q * (dk * norm);
+            if (out) {
+                const float wi = w[(int64_t)idx * Cr + cr] * norm;
+                const float dd = dk * dk, dm = dk * Mf;
+                float *const o = out + (int64_t)idx * DIM;
+                if (DIM == 3) {
+                    o[0] = wi * fmaf(dd, T0, dm * v0 * S0);
+                    o[1] = wi * fmaf(dd, T1, dm * v1 * S0);
+                    o[2] = wi * fmaf(dd, T2, dm * v2 * S0);
+                } else if (DIM == 2) {
+                    o[0] = wi * fmaf(dd, T1, dm * v1 * S0);
+                    o[1] = wi * fmaf(dd, T2, dm * v2 * S0);
+                } else {
+                    o[0] = wi * fmaf(dd, T2, dm * v2 * S0);
+                }
+            }
+        }
+    }
+}
+
 template <int DIM, int W, bool WIDE>
 void launch_w(const dim3 &blocks, const Geom &g, const int *to, const int *perm, const float *spos, const float *grid,
               int64_t Cr, int64_t plane0, const float *w, int64_t n, float *part, float *y, hipStream_t stream)
@@ -313,6 +528,42 @@ int launch_d(const Geom &g, const int *to, const int *perm, const float *spos, c
     return 1;
 }
 
+template <int DIM, int W>
+void launch_hvp_t(const dim3 &blocks, const Geom &g, const int *to, const int *perm, const float *spos, const float *grid,
+                  int64_t Cr, int64_t plane0, const float *w, const float *v, int64_t n, float *dw, float *part,
+                  hipStream_t stream)
+{
+    if constexpr (DIM == 3) {
+        if (g.wide) {
+            hipLaunchKernelGGL((interp_hvp_kernel<DIM, W, true>), blocks, dim3(GradCfg<DIM, W, true>::NT), 0, stream, g, to,
+                               perm, spos, grid, (int)Cr, (int)plane0, w, v, n, dw, part);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((interp_hvp_kernel<DIM, W, false>), blocks, dim3(GradCfg<DIM, W, false>::NT), 0, stream, g, to, perm,
+                       spos, grid, (int)Cr, (int)plane0, w, v, n, dw, part);
+}
+
+template <int DIM>
+int launch_hvp_d(const dim3 &blocks, const Geom &g, const int *to, const int *perm, const float *spos, const float *grid,
+                 int64_t Cr, int64_t plane0, const float *w, const float *v, int64_t n, float *dw, float *part,
+                 hipStream_t stream)
+{
+    switch (g.m) {
+    case 1: launch_hvp_t<DIM, 4>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
+    case 2: launch_hvp_t<DIM, 6>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
+    case 3: launch_hvp_t<DIM, 8>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
+    case 4: launch_hvp_t<DIM, 10>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
+    case 5: launch_hvp_t<DIM, 12>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
+    case 6: launch_hvp_t<DIM, 14>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
+    case 7: launch_hvp_t<DIM, 16>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
+    case 8: launch_hvp_t<DIM, 18>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
+    default: set_error("cutoff m must be in 1..8"); return 1;
+    }
+    NFFT_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 int launch_grad(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                 int64_t plane0, int64_t nplanes, const float *w, float *part, float *y, hipStream_t stream)
 {
@@ -344,6 +595,26 @@ int launch_interp_value_grad(const Geom &g, const PlanLayout &L, const void *pla
 {
     if (!yr) { set_error("Input mismatch: y is null"); return 1; }
     return launch_grad(g, L, plan, grid, n, Cr, plane0, nplanes, w, part, yr, stream);
+}
+
+int launch_interp_hvp(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
+                      int64_t plane0, int64_t nplanes, const float *w, const float *v, float *dw, float *part,
+                      hipStream_t stream)
+{
+    const char *base = (const char *)plan;
+    const int *to = (const int *)(base + L.off_offsets);
+    const int *perm = (const int *)(base + L.off_perm);
+    const float *spos = (const float *)(base + L.off_spos);
+    if (nplanes <= 0 || n <= 0 || (!dw && !part)) return 0;
+    const int splits = point_splits(g, L, n, nplanes);
+    const dim3 blocks((unsigned)(g.nta[1] * g.nta[2] * g.nseg), (unsigned)nplanes, (unsigned)splits);
+    switch (g.dim) {
+    case 1: return launch_hvp_d<1>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream);
+    case 2: return launch_hvp_d<2>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream);
+    case 3: return launch_hvp_d<3>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream);
+    }
+    set_error("dim must be 1, 2 or 3");
+    return 1;
 }
 
 int launch_grad_reduce(const float *part, int64_t len, int64_t Cr, float *dpos, hipStream_t stream)

@@ -54,6 +54,22 @@ int launch_interp_grad(const Geom &g, const PlanLayout &L, const void *plan, con
 int launch_interp_value_grad(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                              int64_t plane0, int64_t nplanes, const float *w, float *part, float *yr, hipStream_t stream);
 int launch_grad_reduce(const float *part, int64_t len, int64_t Cr, float *dpos, hipStream_t stream);
+// The backward of that gather for an upstream v [n, dim]: dw[i * Cr + cr] = sum_u v[i, u] d Fr / d pos[i, u]
+// and part[(cr * n + i) * dim + b] = w[i * Cr + cr] sum_u v[i, u] d^2 Fr / d pos[i, u] d pos[i, b] (grad_reduce sums it);
+// either output may be null (w is read only for part).
+int launch_interp_hvp(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
+                      int64_t plane0, int64_t nplanes, const float *w, const float *v, float *dw, float *part,
+                      hipStream_t stream);
+// spread.hip, the derivative spreading (the transpose of launch_interp_hvp's dw): grid planes
+// [plane0, plane0 + nplanes) += xr[i * Cr + cr] prod psi (-2 c M) sum_u v[i, u] t_u; the halo plan of a narrow tiling only
+bool spread_deriv_supported(const Geom &g);
+int launch_spread_deriv(const Geom &g, const PlanLayout &L, const void *plan, const float *xr, const float *v, int64_t n,
+                        int64_t Cr, int64_t plane0, int64_t nplanes, float *grid, hipStream_t stream);
+// hvp_spectral.hip: u[i * Cr + j] = w[i * Cr + j] v[i * dim + a] (the adjoint's input of axis a), and
+// dxhat (+)= 2 pi i k_a y (y: that adjoint's complex [B, N^dim, C]; the real part when dxhat is real)
+int launch_hvp_stage(const float *w, const float *v, int64_t n, int64_t Cr, int dim, int a, float *u, hipStream_t stream);
+int launch_hvp_combine(const void *y, int64_t B, int64_t N, int dim, int64_t C, int a, int accumulate, int out_complex,
+                       void *dxhat, hipStream_t stream);
 // matrix-core gather for the wide 3-D tiling (interp_mfma.hip)
 bool interp_mfma_supported(const Geom &g);
 int launch_interp_mfma(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,

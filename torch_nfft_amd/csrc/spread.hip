@@ -18,6 +18,11 @@
 //     float LDS atomic is unusable, the 64-bit one is native.  Side effect: tile sums are exact to fp64;
 //   * finished planes leave LDS as contiguous row segments of global_atomic_add_f32 (one padded row =
 //     one <=256-byte run of a wave instruction), so HBM sees line-sized updates, never scattered dwords.
+//
+// DERIV: the derivative spreading of the second-order backward.  The tap weight is
+// x[i, c] * prod_k psi_k * (-2 c M) sum_a v[i, a] t_a with t_a = pos_a M - shift_a - l_a, the transpose of
+// interp_hvp_kernel's dw gather; the FFT stage of the adjoint then turns the grid into dxhat.  Same tiles, passes and
+// ds_add_f64 accumulation; v is read through the plan's index like x (xr only).
 
 #include "common.h"
 #include "kernels.h"
@@ -28,11 +33,11 @@ namespace nfft {
 template <int DIM>
 constexpr int spread_threads() { return DIM == 3 ? 1024 : 256; }
 
-template <int DIM, int W>
+template <int DIM, int W, bool DERIV>
 __global__ void __launch_bounds__((spread_threads<DIM>()))
 spread_kernel(const Geom g, const int *__restrict__ tile_offsets, const int *__restrict__ perm,
               const float *__restrict__ spos, const float *__restrict__ xr, const float *__restrict__ xs, const int64_t n,
-              const int Cr, const int plane0, float *__restrict__ grid)
+              const int Cr, const int plane0, float *__restrict__ grid, const float *__restrict__ v)
 {
     using C = TapCfg<DIM, W>;
     constexpr int NT = spread_threads<DIM>();
@@ -70,6 +75,7 @@ spread_kernel(const Geom g, const int *__restrict__ tile_offsets, const int *__r
     const float sc = win_exp_scale(m);
     float norm = win_norm(m);
     norm = DIM == 3 ? norm * norm * norm : (DIM == 2 ? norm * norm : norm);
+    if (DERIV) norm *= -(4.71238898038469f / (float)m) * (float)g.M;  // d psi / d pos = -2 (3 pi / 4) / m * M * t * psi
 
     LaneTaps<DIM, W> taps;
     taps.init(lane, m);
@@ -145,11 +151,18 @@ spread_kernel(const Geom g, const int *__restrict__ tile_offsets, const int *__r
             const int cnt = min(64, bnd - j0);
             PointPrep<DIM, W> pp;
             float xv = 0.0f;
+            float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;  // DERIV: v on the internal axes
             if (lane < cnt) {
                 pp.load(g, spos, (int64_t)j0 + lane, tb0, tb1, tb2);
                 if (xr) {
                     const int64_t src = DIM == 3 ? __float_as_int(spos[((int64_t)j0 + lane) * 4 + 3]) : perm[(int64_t)j0 + lane];
                     xv = xr[src * Cr + cr] * norm;
+                    if (DERIV) {
+                        const float *const vi = v + src * DIM;
+                        if (DIM == 3) { v0 = vi[0]; v1 = vi[1]; v2 = vi[2]; }
+                        else if (DIM == 2) { v1 = vi[0]; v2 = vi[1]; }
+                        else v2 = vi[0];
+                    }
                 } else {
                     xv = xcol[(int64_t)j0 + lane] * norm;
                 }
@@ -161,13 +174,24 @@ spread_kernel(const Geom g, const int *__restrict__ tile_offsets, const int *__r
                 const float xq = readlane_f(xv, q);
                 double *const origin = acc + readlane_i(pp.base, q);
                 float ps0[C::W0];
+                float vt0[C::W0];  // DERIV: v0 t0 of the axis-0 taps
+                float q1 = 0.0f, q2 = 0.0f;
+                if (DERIV) {
+                    q1 = readlane_f(v1, q);
+                    q2 = readlane_f(v2, q);
+                }
                 if (DIM == 3) {
                     const float d0 = readlane_f(pp.f0, q) + c0;
                     const float psi0 = __builtin_amdgcn_exp2f(sc * d0 * d0);
+                    const float vd0 = DERIV ? readlane_f(v0, q) * d0 : 0.0f;
 #pragma unroll
-                    for (int l0 = 0; l0 < C::W0; ++l0) ps0[l0] = readlane_f(psi0, l0);
+                    for (int l0 = 0; l0 < C::W0; ++l0) {
+                        ps0[l0] = readlane_f(psi0, l0);
+                        if (DERIV) vt0[l0] = readlane_f(vd0, l0);
+                    }
                 } else {
                     ps0[0] = 1.0f;
+                    vt0[0] = 0.0f;
                 }
 #pragma unroll
                 for (int p = 0; p < C::PASSES; ++p) {
@@ -176,8 +200,16 @@ spread_kernel(const Geom g, const int *__restrict__ tile_offsets, const int *__r
                         const float r2 = DIM >= 2 ? fmaf(d1, d1, d2 * d2) : d2 * d2;
                         const float w12 = __builtin_amdgcn_exp2f(sc * r2) * xq;
                         double *dst = origin + taps.off[p];
+                        if (DERIV) {
+                            // t . v = v0 t0 + (v1 t1 + v2 t2), the in-plane part once per pass
+                            const float vt12 = DIM >= 2 ? fmaf(q1, d1, q2 * d2) : q2 * d2;
 #pragma unroll
-                        for (int l0 = 0; l0 < C::W0; ++l0) atomicAdd(dst + l0 * C::S0, (double)(w12 * ps0[l0]));
+                            for (int l0 = 0; l0 < C::W0; ++l0)
+                                atomicAdd(dst + l0 * C::S0, (double)(w12 * ps0[l0] * (vt12 + vt0[l0])));
+                        } else {
+#pragma unroll
+                            for (int l0 = 0; l0 < C::W0; ++l0) atomicAdd(dst + l0 * C::S0, (double)(w12 * ps0[l0]));
+                        }
                     }
                 }
             }
@@ -189,37 +221,41 @@ spread_kernel(const Geom g, const int *__restrict__ tile_offsets, const int *__r
 template <int DIM, int W>
 static int launch_spread_t(const Geom &g, const int *tile_offsets, const int *perm, const float *spos, const float *xr,
                            const float *xs, int64_t n, int64_t Cr, int64_t plane0, int64_t nplanes, int splits, float *grid,
-                           hipStream_t stream)
+                           const float *v, hipStream_t stream)
 {
     const dim3 blocks((unsigned)(g.nta[1] * g.nta[2] * g.nseg), (unsigned)nplanes, (unsigned)splits);
-    hipLaunchKernelGGL((spread_kernel<DIM, W>), blocks, dim3(spread_threads<DIM>()), 0, stream, g, tile_offsets, perm, spos,
-                       xr, xs, n, (int)Cr, (int)plane0, grid);
+    if (v)
+        hipLaunchKernelGGL((spread_kernel<DIM, W, true>), blocks, dim3(spread_threads<DIM>()), 0, stream, g, tile_offsets,
+                           perm, spos, xr, xs, n, (int)Cr, (int)plane0, grid, v);
+    else
+        hipLaunchKernelGGL((spread_kernel<DIM, W, false>), blocks, dim3(spread_threads<DIM>()), 0, stream, g, tile_offsets,
+                           perm, spos, xr, xs, n, (int)Cr, (int)plane0, grid, nullptr);
     NFFT_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 template <int DIM>
 static int launch_spread_d(const Geom &g, const int *to, const int *perm, const float *spos, const float *xr, const float *xs,
-                           int64_t n, int64_t Cr, int64_t plane0, int64_t nplanes, int splits, float *grid, hipStream_t stream)
+                           int64_t n, int64_t Cr, int64_t plane0, int64_t nplanes, int splits, float *grid, const float *v,
+                           hipStream_t stream)
 {
     switch (g.m) {
-    case 1: return launch_spread_t<DIM, 4>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, stream);
-    case 2: return launch_spread_t<DIM, 6>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, stream);
-    case 3: return launch_spread_t<DIM, 8>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, stream);
-    case 4: return launch_spread_t<DIM, 10>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, stream);
-    case 5: return launch_spread_t<DIM, 12>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, stream);
-    case 6: return launch_spread_t<DIM, 14>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, stream);
-    case 7: return launch_spread_t<DIM, 16>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, stream);
-    case 8: return launch_spread_t<DIM, 18>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, stream);
+    case 1: return launch_spread_t<DIM, 4>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
+    case 2: return launch_spread_t<DIM, 6>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
+    case 3: return launch_spread_t<DIM, 8>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
+    case 4: return launch_spread_t<DIM, 10>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
+    case 5: return launch_spread_t<DIM, 12>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
+    case 6: return launch_spread_t<DIM, 14>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
+    case 7: return launch_spread_t<DIM, 16>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
+    case 8: return launch_spread_t<DIM, 18>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
     }
     set_error("cutoff m must be in 1..8");
     return 1;
 }
 
-// xr != nullptr: the caller's row-major [point][Cr] coefficients (read through the plan's permutation); else xs, the
-// planar copy in plan order (gather_rows)
-int launch_spread(const Geom &g, const PlanLayout &L, const void *plan, const float *xr, const float *xs, int64_t n,
-                  int64_t Cr, int64_t plane0, int64_t nplanes, float *grid, hipStream_t stream)
+namespace {
+int launch_spread_any(const Geom &g, const PlanLayout &L, const void *plan, const float *xr, const float *xs, int64_t n,
+                      int64_t Cr, int64_t plane0, int64_t nplanes, float *grid, const float *v, hipStream_t stream)
 {
     const char *base = (const char *)plan;
     const int *to = (const int *)(base + L.off_offsets);
@@ -228,12 +264,30 @@ int launch_spread(const Geom &g, const PlanLayout &L, const void *plan, const fl
     if (nplanes <= 0 || n <= 0) return 0;
     const int splits = point_splits(g, L, n, nplanes);
     switch (g.dim) {
-    case 1: return launch_spread_d<1>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, stream);
-    case 2: return launch_spread_d<2>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, stream);
-    case 3: return launch_spread_d<3>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, stream);
+    case 1: return launch_spread_d<1>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
+    case 2: return launch_spread_d<2>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
+    case 3: return launch_spread_d<3>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
     }
     set_error("dim must be 1, 2 or 3");
     return 1;
+}
+} // namespace
+
+// xr != nullptr: the caller's row-major [point][Cr] coefficients (read through the plan's permutation); else xs, the
+// planar copy in plan order (gather_rows)
+int launch_spread(const Geom &g, const PlanLayout &L, const void *plan, const float *xr, const float *xs, int64_t n,
+                  int64_t Cr, int64_t plane0, int64_t nplanes, float *grid, hipStream_t stream)
+{
+    return launch_spread_any(g, L, plan, xr, xs, n, Cr, plane0, nplanes, grid, nullptr, stream);
+}
+
+bool spread_deriv_supported(const Geom &g) { return !g.wide && !g.owned; }
+
+int launch_spread_deriv(const Geom &g, const PlanLayout &L, const void *plan, const float *xr, const float *v, int64_t n,
+                        int64_t Cr, int64_t plane0, int64_t nplanes, float *grid, hipStream_t stream)
+{
+    if (!xr || !v) { set_error("Input mismatch: null input"); return 1; }
+    return launch_spread_any(g, L, plan, xr, nullptr, n, Cr, plane0, nplanes, grid, v, stream);
 }
 
 } // namespace nfft

@@ -5,8 +5,10 @@ Adjoint and forward are each other's transposes, so each one's backward w.r.t. t
 (``nfft.py:22-28, 48-54``).  Not in the reference: both transforms are also differentiable w.r.t. the points ``pos``.
 Both gradients come from one native gather of the window's derivative (``ops.nfft_forward_grad_points``):
 ``y = nfft_forward(x, pos)`` weights the derivative of its own output by ``dy``; ``y = nfft_adjoint(x, pos)`` gives
-``dpos_i = Re(x_i conj(grad F(pos_i)))`` with ``F = nfft_forward(dy)``.  ``batch`` gets no gradient, and double backward
-(``create_graph=True``) is not supported.
+``dpos_i = Re(x_i conj(grad F(pos_i)))`` with ``F = nfft_forward(dy)``.  ``batch`` gets no gradient.  Under
+``create_graph=True`` the backward passes are built from differentiable pieces -- the other transform and the gather
+``_PointGradFunction`` -- so both transforms can be differentiated twice in ``x`` and ``pos``; the gather's own backward is
+one native call (``ops.nfft_forward_grad_points_backward``), and a third derivative raises.
 
 ``nfft_fastsum`` is differentiable w.r.t. ``x``, ``sources`` and ``targets`` (not ``coeffs`` or the batch vectors).  With
 ``band = c * A_s(x)`` its forward pass's band spectrum (saved only when ``targets`` needs a gradient: ``B C N^d`` complex
@@ -14,7 +16,10 @@ values), ``dtargets`` is the gather of ``forward_t(band)`` weighted by ``dy`` an
 with ``H = forward_s(conj(c) * A_t(dy))``; one native backward call (``ops.nfft_fastsum_backward``).  For real ``c``,
 ``H`` is also ``dx`` and one gather returns both; for complex ``c``, ``dx`` stays the swapped fastsum.
 """
+import math
+
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import ops
 
@@ -22,7 +27,29 @@ from . import ops
 def _real_columns(t, n):
     """[n, Cr] float32 view of a coefficient array: the real columns, or re / im interleaved for complex data."""
     t = t.contiguous()
-    return (torch.view_as_real(t) if t.is_complex() else t).reshape(n, -1)
+    r = torch.view_as_real(t) if t.is_complex() else t
+    return r.reshape(n, math.prod(r.shape[1:]))  # (explicit column count: also for n = 0)
+
+
+class _PointGradFunction(torch.autograd.Function):
+    """G(pos, xhat, w)[i, a] = sum_cr w[i, cr] d Fr[i, cr] / d pos[i, a], Fr the real columns of nfft_forward(xhat, pos):
+    the first-order point gradient of both transforms as a differentiable function of pos, xhat and w."""
+
+    @staticmethod
+    def forward(ctx, pos, xhat, batch, cutoff, real_output, w):
+        ctx.save_for_backward(pos, xhat, batch, w)
+        ctx.cutoff = cutoff
+        ctx.real_output = real_output
+        return ops.nfft_forward_grad_points(pos, xhat, batch, cutoff, real_output, w)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v):
+        pos, xhat, batch, w = ctx.saved_tensors
+        need_p, need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[5]
+        dx, dw, dp = ops.nfft_forward_grad_points_backward(pos, xhat, batch, ctx.cutoff, ctx.real_output, w,
+                                                           v.contiguous(), need_x, need_w, need_p)
+        return dp if need_p else None, dx if need_x else None, None, None, None, dw if need_w else None
 
 
 class NfftAdjointFunction(torch.autograd.Function):
@@ -42,6 +69,13 @@ class NfftAdjointFunction(torch.autograd.Function):
     def backward(ctx, dy):
         pos, batch = ctx.saved_tensors[:2]
         dx = dpos = None
+        if torch.is_grad_enabled():  # create_graph: differentiable pieces
+            if ctx.needs_input_grad[0] or not ctx.pos_grad:
+                dx = NfftForwardFunction.apply(dy, pos, batch, ctx.cutoff, ctx.real_input)
+            if ctx.pos_grad:
+                x = ctx.saved_tensors[2]
+                dpos = _PointGradFunction.apply(pos, dy, batch, ctx.cutoff, ctx.real_input, _real_columns(x, pos.size(0)))
+            return dx, dpos, None, None, None, None
         if ctx.needs_input_grad[0] or not ctx.pos_grad:
             dx = ops.nfft_forward(pos, dy, batch, ctx.cutoff, 1 if ctx.real_input else 0)
         if ctx.pos_grad:
@@ -75,6 +109,13 @@ class NfftForwardFunction(torch.autograd.Function):
     def backward(ctx, dy):
         pos, batch = ctx.saved_tensors[:2]
         dx = dpos = None
+        if torch.is_grad_enabled():  # create_graph: differentiable pieces
+            if ctx.needs_input_grad[0] or not ctx.pos_grad:
+                dx = NfftAdjointFunction.apply(dy, pos, batch, ctx.bandwidth, ctx.cutoff, ctx.real_input)
+            if ctx.pos_grad:
+                x = ctx.saved_tensors[2]
+                dpos = _PointGradFunction.apply(pos, x, batch, ctx.cutoff, ctx.real_output, _real_columns(dy, pos.size(0)))
+            return dx, dpos, None, None, None
         if ctx.needs_input_grad[0] or not ctx.pos_grad:
             dx = ops.nfft_adjoint(pos, dy, batch, ctx.bandwidth, ctx.cutoff, 1 if ctx.real_input else 0)
         if ctx.pos_grad:

@@ -19,8 +19,9 @@ callers who never write that way).  The same switches govern the remembered ENDS
 (``B = batch[-1] + 1`` otherwise costs a blocking read-back of ~35 us in every operator call, as in the reference's
 ``check_point_input``, core_cuda.cu:60): same key (identity + version counter), same limitation.
 
-Not in the reference, for gradients with respect to the points: ``nfft_forward_grad_points`` (both transforms),
-``nfft_fastsum_band`` and ``nfft_fastsum_backward`` (the fast summation).  They take their plans
+Not in the reference, for gradients with respect to the points: ``nfft_forward_grad_points`` (both transforms) and its
+backward ``nfft_forward_grad_points_backward`` (their second derivatives), ``nfft_fastsum_band``
+and ``nfft_fastsum_backward`` (the fast summation).  They take their plans
 from the same cache with the same problems, so a backward pass right after its forward pass plans nothing.
 """
 import torch
@@ -73,6 +74,16 @@ def nfft_forward_grad_points(pos, x, batch, m, real_output, w):
     ``real_output``) and ``w`` is ``[n, Cr]`` float32.  One native call (``nfft_hip_forward_grad_points_planned``) on the
     cached point plan."""
     return _ops._nfft_forward_grad_points(pos, x, batch, int(m), 1 if real_output else 0, w)
+
+
+def nfft_forward_grad_points_backward(pos, x, batch, m, real_output, w, v, need_xhat, need_w, need_pos):
+    """torch_nfft::_nfft_forward_grad_points_backward(Tensor pos, Tensor xhat, Tensor? batch, int m, int real_output,
+    Tensor w, Tensor v, int need_xhat, int need_w, int need_pos) -> (Tensor dxhat, Tensor dw, Tensor dpos) (not in the
+    reference): the gradients of ``<v, nfft_forward_grad_points(pos, x, batch, m, real_output, w)>`` for ``v`` [n, dim]
+    float32 -- ``dxhat`` like ``x``, ``dw`` [n, Cr], ``dpos`` [n, dim]; what was not asked for comes back empty.  One native
+    call (``nfft_hip_forward_grad_points_backward_planned``) on the cached point plan."""
+    return _ops._nfft_forward_grad_points_backward(pos, x, batch, int(m), 1 if real_output else 0, w, v,
+                                                   1 if need_xhat else 0, 1 if need_w else 0, 1 if need_pos else 0)
 
 
 def nfft_fastsum(sources, targets, x, coeffs, source_batch, target_batch, m):
