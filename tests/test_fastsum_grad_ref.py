@@ -137,7 +137,7 @@ def _resource_usage(src):
 def test_value_gather_resource_usage():
     """Every instantiation of the value-writing gather: no scratch, no VGPR spills, and at least the occupancy of the
     gradient-only kernel with the same <DIM, W, WIDE>.  SGPR spills (into VGPR lanes, no memory) only where the occupancy
-    would drop without them: the 2-D m = 2 kernel (interp_grad.hip GradCfg::WPE_VALUE)."""
+    would drop without them: the 2-D m = 2 kernel (lane_gather.h GatherCfg::WPE_VALUE)."""
     usage = _resource_usage(os.path.join(ROOT, "torch_nfft_amd", "csrc", "interp_grad.hip"))
     # mangled: ...interp_grad_kernelILi<DIM>ELi<W>ELb<WIDE>ELb<VALUE>EE...
     pat = re.compile(r"interp_grad_kernelILi(\d)ELi(\d+)ELb([01])ELb([01])EE")

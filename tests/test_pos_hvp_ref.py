@@ -196,7 +196,7 @@ def test_operator_schema_and_cpu_rejection():
 
 def test_hvp_gather_resource_usage():
     """Every instantiation of interp_hvp_kernel: no scratch, no VGPR spills, and the occupancy of interp_grad_kernel with
-    the same <DIM, W, WIDE> except one wave less for the three kernels GradCfg::WPE_HVP names.  SGPR spills (into VGPR
+    the same <DIM, W, WIDE> except one wave less for the three kernels GatherCfg::WPE_HVP names.  SGPR spills (into VGPR
     lanes, no memory) only for 2-D m = 1, 2."""
     from test_fastsum_grad_ref import _resource_usage
     usage = _resource_usage(os.path.join(ROOT, "torch_nfft_amd", "csrc", "interp_grad.hip"))

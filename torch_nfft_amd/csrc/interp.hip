@@ -14,36 +14,11 @@
 //     cross-lane reduction, no per-point scalar broadcasts: ~40 wave instructions per point instead of ~120
 //     for the tap-per-lane layout this kernel started with.
 // g is held as real planes (re and im of a complex grid are separate planes = separate real columns).
-#include "common.h"
+// Tile geometry (GatherCfg) and host launch (launch_lane_gather): lane_gather.h, shared with interp_grad.hip.
 #include "kernels.h"
-#include "window.h"
+#include "lane_gather.h"
 
 namespace nfft {
-
-// Geometry of the gather kernel.  It shares the point plan (pencils, chunks of TC planes) with the spreading
-// kernel but keeps 4-byte cells and rows padded to a multiple of 4 floats so that a lane can fetch its
-// 2m+2 taps of a row with aligned ds_read_b128.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <int DIM, int W, bool WIDE>
-struct GatherCfg {
-    static constexpr TileCfg tc = tile_cfg(DIM, W, WIDE);
-    static constexpr int T1 = tc.T1, T2 = tc.T2, TC = tc.TC;
-    static constexpr int W0 = DIM == 3 ? W : 1;
-    static constexpr int W1 = DIM >= 2 ? W : 1;
-    static constexpr int M0OFF = DIM == 3 ? (W / 2 - 1) : 0;
-    static constexpr int NP = TC + W0 - 1;
-    static constexpr int P1 = T1 + W1 - 1;
-    static constexpr int P2 = T2 + W - 1;
-    static constexpr int NR = (W + 3 + 3) / 4;            // aligned 16-byte reads covering any 2m+2 window
-    static constexpr int S2 = (P2 + 3 + 3) / 4 * 4;       // row stride (floats): room for the aligned over-read
-    static constexpr int S0 = P1 * S2;
-    static constexpr int CELLS = NP * S0;
-    static constexpr int NT = DIM == 3 ? (WIDE ? 1024 : 512) : 256;  // the wide tiling fills the LDS with one workgroup
-    static constexpr int NWAVES = NT / 64;
-    static_assert(CELLS * 4 <= 160 * 1024, "LDS budget");
-};
 
 template <int DIM, int W, bool WIDE>
 __global__ void __launch_bounds__((GatherCfg<DIM, W, WIDE>::NT))
@@ -212,59 +187,14 @@ interp_kernel(const Geom g, const int *__restrict__ tile_offsets, const int *__r
     }
 }
 
-template <int DIM, int W>
-static int launch_interp_t(const Geom &g, const int *to, const int *perm, const float *spos, const float *grid,
-                           int64_t Cr, int64_t plane0, int64_t nplanes, int splits, float *yr, hipStream_t stream)
-{
-    const dim3 blocks((unsigned)(g.nta[1] * g.nta[2] * g.nseg), (unsigned)nplanes, (unsigned)splits);
-    if constexpr (DIM == 3) {
-        if (g.wide) {
-            hipLaunchKernelGGL((interp_kernel<DIM, W, true>), blocks, dim3(GatherCfg<DIM, W, true>::NT), 0, stream, g, to,
-                               perm, spos, grid, (int)Cr, (int)plane0, yr);
-            NFFT_HIP_CHECK(hipGetLastError());
-            return 0;
-        }
-    }
-    hipLaunchKernelGGL((interp_kernel<DIM, W, false>), blocks, dim3(GatherCfg<DIM, W, false>::NT), 0, stream, g, to, perm,
-                       spos, grid, (int)Cr, (int)plane0, yr);
-    NFFT_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-template <int DIM>
-static int launch_interp_d(const Geom &g, const int *to, const int *perm, const float *spos, const float *grid,
-                           int64_t Cr, int64_t plane0, int64_t nplanes, int splits, float *yr, hipStream_t stream)
-{
-    switch (g.m) {
-    case 1: return launch_interp_t<DIM, 4>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, yr, stream);
-    case 2: return launch_interp_t<DIM, 6>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, yr, stream);
-    case 3: return launch_interp_t<DIM, 8>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, yr, stream);
-    case 4: return launch_interp_t<DIM, 10>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, yr, stream);
-    case 5: return launch_interp_t<DIM, 12>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, yr, stream);
-    case 6: return launch_interp_t<DIM, 14>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, yr, stream);
-    case 7: return launch_interp_t<DIM, 16>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, yr, stream);
-    case 8: return launch_interp_t<DIM, 18>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, yr, stream);
-    }
-    set_error("cutoff m must be in 1..8");
-    return 1;
-}
-
 int launch_interp(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                   int64_t plane0, int64_t nplanes, float *yr, hipStream_t stream)
 {
-    const char *base = (const char *)plan;
-    const int *to = (const int *)(base + L.off_offsets);
-    const int *perm = (const int *)(base + L.off_perm);
-    const float *spos = (const float *)(base + L.off_spos);
-    if (nplanes <= 0 || n <= 0) return 0;
-    const int splits = point_splits(g, L, n, nplanes);
-    switch (g.dim) {
-    case 1: return launch_interp_d<1>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, yr, stream);
-    case 2: return launch_interp_d<2>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, yr, stream);
-    case 3: return launch_interp_d<3>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, yr, stream);
-    }
-    set_error("dim must be 1, 2 or 3");
-    return 1;
+    return launch_lane_gather(g, L, plan, n, nplanes, [&](auto cfg, const dim3 &blocks, const LanePlan &p) {
+        using C = decltype(cfg);
+        hipLaunchKernelGGL((interp_kernel<C::DIM, C::W, C::WIDE>), blocks, dim3(C::NT), 0, stream, g, p.tile_offsets,
+                           p.perm, p.spos, grid, (int)Cr, (int)plane0, yr);
+    });
 }
 
 } // namespace nfft

@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lane_gather.h"
 #include "mfma_split.h"
 
 namespace nfft {
@@ -359,17 +360,9 @@ int launch_interp_cols(const Geom &g, const PlanLayout &L, const void *plan, con
                        int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
 {
     if (nplanes <= 0 || n <= 0) return 0;
-    switch (g.m) {
-    case 1: return launch_ic_t<4>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 2: return launch_ic_t<6>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 3: return launch_ic_t<8>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 4: return launch_ic_t<10>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 5: return launch_ic_t<12>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 6: return launch_ic_t<14>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 7: return launch_ic_t<16>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    }
-    set_error("matrix-core interpolation supports cutoff 1..7");
-    return 1;
+    return with_window<7>(g.m, "matrix-core interpolation supports cutoff 1..7", [&](auto w) {
+        return launch_ic_t<decltype(w)::value>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    });
 }
 
 } // namespace nfft

@@ -8,52 +8,17 @@
 // dpos[i, a] = sum_cr G[cr, i, a] (nfft_hip_forward_grad_points: DESIGN.md section "Gradient with respect to the points").
 //
 // The kernel is interp.hip's one-lane-per-point gather (same plan, same resident-plane sliding window, same aligned
-// ds_read_b128 rows and packed FMAs, same point splits) with two dot products per row instead of one -- the row with the
-// axis-2 window and with its derivative -- and d partial sums carried through the plane and slab loops.  Every G value is
-// written by exactly one lane and the sum over the planes runs in a fixed order (grad_reduce_kernel): no atomics, the
-// result is bitwise reproducible.  A second kernel writes the interpolated value alongside (the fused gather of the fastsum
-// backward: DESIGN.md section 7a).
-#include "common.h"
+// ds_read_b128 rows and packed FMAs, same point splits; geometry and launch from lane_gather.h) with two dot products per
+// row instead of one -- the row with the axis-2 window and with its derivative -- and d partial sums carried through the
+// plane and slab loops.  Every G value is written by exactly one lane and the sum over the planes runs in a fixed order
+// (grad_reduce_kernel): no atomics, the result is bitwise reproducible.  A second kernel writes the interpolated value
+// alongside (the fused gather of the fastsum backward: DESIGN.md section 7a).
 #include "kernels.h"
-#include "window.h"
+#include "lane_gather.h"
 
 namespace nfft {
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// Same geometry as interp.hip's GatherCfg (tiling, padded rows, LDS footprint, workgroup size).
-template <int DIM, int W, bool WIDE>
-struct GradCfg {
-    static constexpr TileCfg tc = tile_cfg(DIM, W, WIDE);
-    static constexpr int T1 = tc.T1, T2 = tc.T2, TC = tc.TC;
-    static constexpr int W0 = DIM == 3 ? W : 1;
-    static constexpr int W1 = DIM >= 2 ? W : 1;
-    static constexpr int M0OFF = DIM == 3 ? (W / 2 - 1) : 0;
-    static constexpr int NP = TC + W0 - 1;
-    static constexpr int P1 = T1 + W1 - 1;
-    static constexpr int P2 = T2 + W - 1;
-    static constexpr int NR = (W + 3 + 3) / 4;
-    static constexpr int S2 = (P2 + 3 + 3) / 4 * 4;
-    static constexpr int S0 = P1 * S2;
-    static constexpr int CELLS = NP * S0;
-    static constexpr int NT = DIM == 3 ? (WIDE ? 1024 : 512) : 256;
-    static constexpr int NWAVES = NT / 64;
-    // waves per SIMD the register allocation must allow: at least what interp_kernel reaches for the same geometry
-    // (without the floor the compiler gives the 1-D / 2-D kernels and the narrow 3-D one of m <= 2 up to 16 more VGPRs)
-    static constexpr int WPE = DIM == 1 ? 8 : DIM == 2 ? (W <= 6 ? 8 : W == 10 || W == 18 ? 6 : 7) : (!WIDE && W <= 6) ? 6 : 1;
-    // the value-writing kernel: the occupancy the gradient-only kernel reaches.  2-D m = 4: 7 (the floor of 6 would let the
-    // allocator take the VGPRs the value needs from it); 2-D m = 1: 7, where the floor of 8 caps the SGPRs below what the
-    // y pointer needs -- its 62 VGPRs still give 8 waves.  (2-D m = 2 keeps 8: at 7 it takes 65 VGPRs and loses a wave, at
-    // 8 six SGPRs live in VGPR lanes -- v_writelane / v_readlane, no scratch.)
-    static constexpr int WPE_VALUE = DIM == 2 && (W == 10 || W == 4) ? 7 : WPE;
-    // the second-order gather (interp_hvp_kernel): the gradient kernel's occupancy, except three kernels one wave lower,
-    // where its two more moments would otherwise spill VGPRs to scratch (1-D and 2-D m = 8, narrow 3-D m = 2)
-    static constexpr int WPE_HVP = DIM == 2 && W == 10 ? 7 : (DIM <= 2 && W == 18) || (DIM == 3 && !WIDE && W == 6) ? WPE - 1 : WPE;
-    static_assert(CELLS * 4 <= 160 * 1024, "LDS budget");
-};
 
 // part[(cr * n + i) * DIM + u]: the gradient of point i (caller order, user axis u) from real plane cr of its set, already
 // multiplied by w[i, cr].  With one real plane per set part is dpos itself.
@@ -61,13 +26,13 @@ struct GradCfg {
 // normalisation, same layout).  Every row sum V the gradient needs is the value's row sum as well, so the value costs one
 // FMA per axis-0 plane and one store.  With VALUE = false, y is unused and the code is the gradient-only kernel's.
 template <int DIM, int W, bool WIDE, bool VALUE>
-__global__ void __launch_bounds__((GradCfg<DIM, W, WIDE>::NT))
-__attribute__((amdgpu_waves_per_eu(VALUE ? GradCfg<DIM, W, WIDE>::WPE_VALUE : GradCfg<DIM, W, WIDE>::WPE)))
+__global__ void __launch_bounds__((GatherCfg<DIM, W, WIDE>::NT))
+__attribute__((amdgpu_waves_per_eu(VALUE ? GatherCfg<DIM, W, WIDE>::WPE_VALUE : GatherCfg<DIM, W, WIDE>::WPE)))
 interp_grad_kernel(const Geom g, const int *__restrict__ tile_offsets, const int *__restrict__ perm,
                    const float *__restrict__ spos, const float *__restrict__ grid, const int Cr, const int plane0,
                    const float *__restrict__ w, const int64_t n, float *__restrict__ part, float *__restrict__ y)
 {
-    using C = GradCfg<DIM, W, WIDE>;
+    using C = GatherCfg<DIM, W, WIDE>;
     constexpr int NT = C::NT;
     constexpr int NWAVES = C::NWAVES;
     __shared__ float4 planes4[C::CELLS / 4];
@@ -277,14 +242,14 @@ grad_reduce_kernel(const float *__restrict__ part, const int64_t len, const int 
 // of interp_grad_kernel.  dw is written once per (plane, point); the partial
 // gradients are summed over the planes by grad_reduce_kernel in a fixed order: bitwise reproducible.  dw or part may be null.
 template <int DIM, int W, bool WIDE>
-__global__ void __launch_bounds__((GradCfg<DIM, W, WIDE>::NT))
-__attribute__((amdgpu_waves_per_eu(GradCfg<DIM, W, WIDE>::WPE_HVP)))
+__global__ void __launch_bounds__((GatherCfg<DIM, W, WIDE>::NT))
+__attribute__((amdgpu_waves_per_eu(GatherCfg<DIM, W, WIDE>::WPE_HVP)))
 interp_hvp_kernel(const Geom g, const int *__restrict__ tile_offsets, const int *__restrict__ perm,
                   const float *__restrict__ spos, const float *__restrict__ grid, const int Cr, const int plane0,
                   const float *__restrict__ w, const float *__restrict__ v, const int64_t n, float *__restrict__ dw,
                   float *__restrict__ part)
 {
-    using C = GradCfg<DIM, W, WIDE>;
+    using C = GatherCfg<DIM, W, WIDE>;
     constexpr int NT = C::NT;
     constexpr int NWAVES = C::NWAVES;
     __shared__ float4 planes4[C::CELLS / 4];
@@ -479,142 +444,39 @@ interp_hvp_kernel(const Geom g, const int *__restrict__ tile_offsets, const int 
     }
 }
 
-template <int DIM, int W, bool WIDE>
-void launch_w(const dim3 &blocks, const Geom &g, const int *to, const int *perm, const float *spos, const float *grid,
-              int64_t Cr, int64_t plane0, const float *w, int64_t n, float *part, float *y, hipStream_t stream)
-{
-    if (y)
-        hipLaunchKernelGGL((interp_grad_kernel<DIM, W, WIDE, true>), blocks, dim3(GradCfg<DIM, W, WIDE>::NT), 0, stream, g,
-                           to, perm, spos, grid, (int)Cr, (int)plane0, w, n, part, y);
-    else
-        hipLaunchKernelGGL((interp_grad_kernel<DIM, W, WIDE, false>), blocks, dim3(GradCfg<DIM, W, WIDE>::NT), 0, stream, g, to,
-                           perm, spos, grid, (int)Cr, (int)plane0, w, n, part, nullptr);
-}
-
-template <int DIM, int W>
-int launch_t(const Geom &g, const int *to, const int *perm, const float *spos, const float *grid, int64_t Cr,
-             int64_t plane0, int64_t nplanes, int splits, const float *w, int64_t n, float *part, float *y,
-             hipStream_t stream)
-{
-    const dim3 blocks((unsigned)(g.nta[1] * g.nta[2] * g.nseg), (unsigned)nplanes, (unsigned)splits);
-    if constexpr (DIM == 3) {
-        if (g.wide) {
-            launch_w<DIM, W, true>(blocks, g, to, perm, spos, grid, Cr, plane0, w, n, part, y, stream);
-            NFFT_HIP_CHECK(hipGetLastError());
-            return 0;
-        }
-    }
-    launch_w<DIM, W, false>(blocks, g, to, perm, spos, grid, Cr, plane0, w, n, part, y, stream);
-    NFFT_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-template <int DIM>
-int launch_d(const Geom &g, const int *to, const int *perm, const float *spos, const float *grid, int64_t Cr,
-             int64_t plane0, int64_t nplanes, int splits, const float *w, int64_t n, float *part, float *y,
-             hipStream_t stream)
-{
-    switch (g.m) {
-    case 1: return launch_t<DIM, 4>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
-    case 2: return launch_t<DIM, 6>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
-    case 3: return launch_t<DIM, 8>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
-    case 4: return launch_t<DIM, 10>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
-    case 5: return launch_t<DIM, 12>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
-    case 6: return launch_t<DIM, 14>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
-    case 7: return launch_t<DIM, 16>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
-    case 8: return launch_t<DIM, 18>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
-    }
-    set_error("cutoff m must be in 1..8");
-    return 1;
-}
-
-template <int DIM, int W>
-void launch_hvp_t(const dim3 &blocks, const Geom &g, const int *to, const int *perm, const float *spos, const float *grid,
-                  int64_t Cr, int64_t plane0, const float *w, const float *v, int64_t n, float *dw, float *part,
-                  hipStream_t stream)
-{
-    if constexpr (DIM == 3) {
-        if (g.wide) {
-            hipLaunchKernelGGL((interp_hvp_kernel<DIM, W, true>), blocks, dim3(GradCfg<DIM, W, true>::NT), 0, stream, g, to,
-                               perm, spos, grid, (int)Cr, (int)plane0, w, v, n, dw, part);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((interp_hvp_kernel<DIM, W, false>), blocks, dim3(GradCfg<DIM, W, false>::NT), 0, stream, g, to, perm,
-                       spos, grid, (int)Cr, (int)plane0, w, v, n, dw, part);
-}
-
-template <int DIM>
-int launch_hvp_d(const dim3 &blocks, const Geom &g, const int *to, const int *perm, const float *spos, const float *grid,
-                 int64_t Cr, int64_t plane0, const float *w, const float *v, int64_t n, float *dw, float *part,
-                 hipStream_t stream)
-{
-    switch (g.m) {
-    case 1: launch_hvp_t<DIM, 4>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
-    case 2: launch_hvp_t<DIM, 6>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
-    case 3: launch_hvp_t<DIM, 8>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
-    case 4: launch_hvp_t<DIM, 10>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
-    case 5: launch_hvp_t<DIM, 12>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
-    case 6: launch_hvp_t<DIM, 14>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
-    case 7: launch_hvp_t<DIM, 16>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
-    case 8: launch_hvp_t<DIM, 18>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream); break;
-    default: set_error("cutoff m must be in 1..8"); return 1;
-    }
-    NFFT_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-int launch_grad(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                int64_t plane0, int64_t nplanes, const float *w, float *part, float *y, hipStream_t stream)
-{
-    const char *base = (const char *)plan;
-    const int *to = (const int *)(base + L.off_offsets);
-    const int *perm = (const int *)(base + L.off_perm);
-    const float *spos = (const float *)(base + L.off_spos);
-    if (nplanes <= 0 || n <= 0) return 0;
-    const int splits = point_splits(g, L, n, nplanes);
-    switch (g.dim) {
-    case 1: return launch_d<1>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
-    case 2: return launch_d<2>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
-    case 3: return launch_d<3>(g, to, perm, spos, grid, Cr, plane0, nplanes, splits, w, n, part, y, stream);
-    }
-    set_error("dim must be 1, 2 or 3");
-    return 1;
-}
-
 } // namespace
 
 int launch_interp_grad(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                        int64_t plane0, int64_t nplanes, const float *w, float *part, hipStream_t stream)
 {
-    return launch_grad(g, L, plan, grid, n, Cr, plane0, nplanes, w, part, nullptr, stream);
+    return launch_lane_gather(g, L, plan, n, nplanes, [&](auto cfg, const dim3 &blocks, const LanePlan &p) {
+        using C = decltype(cfg);
+        hipLaunchKernelGGL((interp_grad_kernel<C::DIM, C::W, C::WIDE, false>), blocks, dim3(C::NT), 0, stream, g,
+                           p.tile_offsets, p.perm, p.spos, grid, (int)Cr, (int)plane0, w, n, part, nullptr);
+    });
 }
 
 int launch_interp_value_grad(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                              int64_t plane0, int64_t nplanes, const float *w, float *part, float *yr, hipStream_t stream)
 {
     if (!yr) { set_error("Input mismatch: y is null"); return 1; }
-    return launch_grad(g, L, plan, grid, n, Cr, plane0, nplanes, w, part, yr, stream);
+    return launch_lane_gather(g, L, plan, n, nplanes, [&](auto cfg, const dim3 &blocks, const LanePlan &p) {
+        using C = decltype(cfg);
+        hipLaunchKernelGGL((interp_grad_kernel<C::DIM, C::W, C::WIDE, true>), blocks, dim3(C::NT), 0, stream, g,
+                           p.tile_offsets, p.perm, p.spos, grid, (int)Cr, (int)plane0, w, n, part, yr);
+    });
 }
 
 int launch_interp_hvp(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                       int64_t plane0, int64_t nplanes, const float *w, const float *v, float *dw, float *part,
                       hipStream_t stream)
 {
-    const char *base = (const char *)plan;
-    const int *to = (const int *)(base + L.off_offsets);
-    const int *perm = (const int *)(base + L.off_perm);
-    const float *spos = (const float *)(base + L.off_spos);
-    if (nplanes <= 0 || n <= 0 || (!dw && !part)) return 0;
-    const int splits = point_splits(g, L, n, nplanes);
-    const dim3 blocks((unsigned)(g.nta[1] * g.nta[2] * g.nseg), (unsigned)nplanes, (unsigned)splits);
-    switch (g.dim) {
-    case 1: return launch_hvp_d<1>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream);
-    case 2: return launch_hvp_d<2>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream);
-    case 3: return launch_hvp_d<3>(blocks, g, to, perm, spos, grid, Cr, plane0, w, v, n, dw, part, stream);
-    }
-    set_error("dim must be 1, 2 or 3");
-    return 1;
+    if (!dw && !part) return 0;
+    return launch_lane_gather(g, L, plan, n, nplanes, [&](auto cfg, const dim3 &blocks, const LanePlan &p) {
+        using C = decltype(cfg);
+        hipLaunchKernelGGL((interp_hvp_kernel<C::DIM, C::W, C::WIDE>), blocks, dim3(C::NT), 0, stream, g, p.tile_offsets,
+                           p.perm, p.spos, grid, (int)Cr, (int)plane0, w, v, n, dw, part);
+    });
 }
 
 int launch_grad_reduce(const float *part, int64_t len, int64_t Cr, float *dpos, hipStream_t stream)

@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lane_gather.h"
 #include "mfma_split.h"
 
 namespace nfft {
@@ -309,17 +310,9 @@ int launch_interp_mfma(const Geom &g, const PlanLayout &L, const void *plan, con
     const int *to = (const int *)(base + L.off_offsets);
     const float *spos = (const float *)(base + L.off_spos);
     if (nplanes <= 0 || n <= 0) return 0;
-    switch (g.m) {
-    case 1: return launch_gm_t<4>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 2: return launch_gm_t<6>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 3: return launch_gm_t<8>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 4: return launch_gm_t<10>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 5: return launch_gm_t<12>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 6: return launch_gm_t<14>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 7: return launch_gm_t<16>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    }
-    set_error("matrix-core interpolation supports cutoff 1..7");
-    return 1;
+    return with_window<7>(g.m, "matrix-core interpolation supports cutoff 1..7", [&](auto w) {
+        return launch_gm_t<decltype(w)::value>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    });
 }
 
 } // namespace nfft

@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lane_gather.h"
 #include "mfma_split.h"
 
 namespace nfft {
@@ -566,17 +567,9 @@ int launch_interp_stream(const Geom &g, const PlanLayout &L, const void *plan, c
                          int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
 {
     if (nplanes <= 0 || n <= 0) return 0;
-    switch (g.m) {
-    case 1: return launch_is_w<4>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 2: return launch_is_w<6>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 3: return launch_is_w<8>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 4: return launch_is_w<10>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 5: return launch_is_w<12>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 6: return launch_is_w<14>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    case 7: return launch_is_w<16>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-    }
-    set_error("matrix-core interpolation supports cutoff 1..7");
-    return 1;
+    return with_window<7>(g.m, "matrix-core interpolation supports cutoff 1..7", [&](auto w) {
+        return launch_is_w<decltype(w)::value>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+    });
 }
 
 } // namespace nfft

@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lane_gather.h"
 #include "window.h"
 
 namespace nfft {
@@ -239,18 +240,10 @@ static int launch_spread_d(const Geom &g, const int *to, const int *perm, const 
                            int64_t n, int64_t Cr, int64_t plane0, int64_t nplanes, int splits, float *grid, const float *v,
                            hipStream_t stream)
 {
-    switch (g.m) {
-    case 1: return launch_spread_t<DIM, 4>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
-    case 2: return launch_spread_t<DIM, 6>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
-    case 3: return launch_spread_t<DIM, 8>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
-    case 4: return launch_spread_t<DIM, 10>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
-    case 5: return launch_spread_t<DIM, 12>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
-    case 6: return launch_spread_t<DIM, 14>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
-    case 7: return launch_spread_t<DIM, 16>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
-    case 8: return launch_spread_t<DIM, 18>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v, stream);
-    }
-    set_error("cutoff m must be in 1..8");
-    return 1;
+    return with_window<8>(g.m, "cutoff m must be in 1..8", [&](auto w) {
+        return launch_spread_t<DIM, decltype(w)::value>(g, to, perm, spos, xr, xs, n, Cr, plane0, nplanes, splits, grid, v,
+                                                        stream);
+    });
 }
 
 namespace {

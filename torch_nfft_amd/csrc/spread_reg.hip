@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lane_gather.h"
 #include "window.h"
 
 namespace nfft {
@@ -196,17 +197,9 @@ int launch_spread_reg(const Geom &g, const PlanLayout &L, const void *plan, cons
     const int *to = (const int *)(base + L.off_offsets);
     const float *spos = (const float *)(base + L.off_spos);
     if (nplanes <= 0) return 0;
-    switch (g.m) {
-    case 1: return launch_reg_t<4>(g, to, spos, xs, n, Cr, plane0, nplanes, grid, stream);
-    case 2: return launch_reg_t<6>(g, to, spos, xs, n, Cr, plane0, nplanes, grid, stream);
-    case 3: return launch_reg_t<8>(g, to, spos, xs, n, Cr, plane0, nplanes, grid, stream);
-    case 4: return launch_reg_t<10>(g, to, spos, xs, n, Cr, plane0, nplanes, grid, stream);
-    case 5: return launch_reg_t<12>(g, to, spos, xs, n, Cr, plane0, nplanes, grid, stream);
-    case 6: return launch_reg_t<14>(g, to, spos, xs, n, Cr, plane0, nplanes, grid, stream);
-    case 7: return launch_reg_t<16>(g, to, spos, xs, n, Cr, plane0, nplanes, grid, stream);
-    }
-    set_error("register-tile spreading supports cutoff 1..7");
-    return 1;
+    return with_window<7>(g.m, "register-tile spreading supports cutoff 1..7", [&](auto w) {
+        return launch_reg_t<decltype(w)::value>(g, to, spos, xs, n, Cr, plane0, nplanes, grid, stream);
+    });
 }
 
 } // namespace nfft
