@@ -10,6 +10,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "range_items.h"
 
 namespace nfft {
 
@@ -550,8 +551,9 @@ sort2_scatter_kernel(Geom g, int npencils, int nblocks, const int *__restrict__ 
     }
 }
 
-// Work list of the wide tiling (common.h): every range of slabs of every (point set, pencil), dense ranges cut
-// into pieces of about `target` points.  One wave per (point set, pencil), lane r = range r of the pencil.
+// Work list of the wide tiling (common.h): every range of slabs (range_items.h range_split) of every (point set,
+// pencil), dense ranges cut into pieces of about `target` points.  One wave per (point set, pencil), lane r = range r
+// of the pencil.
 // work[0] = {entries, 1 if any range was cut, 0, 0}; entries {point set * pencils + pencil, first slab, end slab, points}.
 __global__ void __launch_bounds__(64)
 segment_split_kernel(Geom g, int npl /* point sets x pencils */, int pencils, int runs, int target,
@@ -748,17 +750,16 @@ static inline int grid_for(int64_t work, int block)
 static int launch_segment_split(const Geom &g, const PlanLayout &L, int64_t n, int64_t B, const int *offsets, int4 *work,
                                  hipStream_t stream)
 {
-    const int64_t pencils = (int64_t)g.nta[1] * g.nta[2], npl = pencils * B;
-    const int ncu = device_cu_count();
-    const int runs = seg_base_runs(n, B, pencils, g.M, ncu);
-    const int target = (int)std::min<int64_t>(seg_target_points(n, B, ncu), int64_t(1) << 30);
+    const RangeSplit s = range_split(g, n, B);
+    const int64_t npl = s.pencils * B;
+    const int target = (int)std::min<int64_t>(seg_target_points(n, B, device_cu_count()), int64_t(1) << 30);
     NFFT_HIP_CHECK(hipMemsetAsync(work, 0, (size_t)L.work_head * 16, stream));
     if (npl <= 0) return 0;
     int4 *const list = work + L.work_head;
-    hipLaunchKernelGGL(segment_split_kernel, dim3((unsigned)npl), dim3(64), 0, stream, g, (int)npl, (int)pencils, runs, target,
-                       offsets, work, list, (int)L.work_cap);
+    hipLaunchKernelGGL(segment_split_kernel, dim3((unsigned)npl), dim3(64), 0, stream, g, (int)npl, (int)s.pencils, s.nsegm,
+                       target, offsets, work, list, (int)L.work_cap);
     hipLaunchKernelGGL(work_order_kernel, dim3((unsigned)B), dim3(1024), 0, stream, work, list, list + L.work_cap,
-                       (int)L.work_cap, (int)pencils, work_list_forced() ? 1 : 0);
+                       (int)L.work_cap, (int)s.pencils, work_list_forced() ? 1 : 0);
     return 0;
 }
 

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <atomic>
 #include <string>
+#include <type_traits>
 
 namespace nfft {
 
@@ -115,8 +116,8 @@ struct Geom {
 };
 
 inline bool owned_supported(int dim, int64_t N, int64_t m);
-// Ticket counters of a persistent launch (next_work_item below): one int per blockIdx.y, in the caller's workspace.  A launch
-// with more planes (pair slots, column groups) than this deals its work list round robin.
+// Ticket counters of a persistent launch (range_items.h next_work_item): one int per blockIdx.y, in the caller's
+// workspace.  A launch with more planes (pair slots, column groups) than this deals its work list round robin.
 constexpr int kTicketPlanes = 256;
 bool work_list_forced();       // api.hip: NFFT_HIP_WORK_LIST=1 runs every wide plan from its work list
 bool column_groups_enabled();  // api.hip: NFFT_HIP_COLGROUPS=0 turns the column-group order of the plan off
@@ -184,6 +185,28 @@ inline bool choose_owned(int dim, int64_t N, int64_t m, int64_t n, int64_t B, do
     if (ov >= 0) return ov != 0;
     const double cells = 8.0 * (double)N * (double)N * (double)N * (double)(B > 0 ? B : 1) * occupied;
     return n > 0 && (double)n < 0.026 * cells;
+}
+
+// Cutoff dispatch of every kernel file's host side: f(std::integral_constant<int, W>{}) for the window width W = 2m + 2
+// of the cutoff m in 1..MMAX (the cutoffs the calling kernel file instantiates); any other m: set_error(err) and 1.
+template <int MMAX, class F>
+int with_window(int m, const char *err, F &&f)
+{
+    static_assert(MMAX == 7 || MMAX == 8, "kernels exist for cutoffs 1..7 or 1..8");
+    switch (m) {
+    case 1: return f(std::integral_constant<int, 4>{});
+    case 2: return f(std::integral_constant<int, 6>{});
+    case 3: return f(std::integral_constant<int, 8>{});
+    case 4: return f(std::integral_constant<int, 10>{});
+    case 5: return f(std::integral_constant<int, 12>{});
+    case 6: return f(std::integral_constant<int, 14>{});
+    case 7: return f(std::integral_constant<int, 16>{});
+    case 8:
+        if constexpr (MMAX == 8) return f(std::integral_constant<int, 18>{});
+        break;
+    }
+    set_error(err);
+    return 1;
 }
 
 // ---- device helpers --------------------------------------------------------
@@ -328,42 +351,6 @@ __device__ __forceinline__ int sub_of_cells(const Geom &g, const int cell[3])
     return s1 * g.sb2 + s2;
 }
 
-// Dynamic hand-out of the sorted work list to the workgroups of a persistent launch: a workgroup starts with entry
-// blockIdx.x and then takes the next free entry whenever it is done (the list is sorted biggest first: longest-processing-
-// time-first scheduling).  A ticket is one atomic add on the counter of the workgroup's plane, tickets[blockIdx.y]: the
-// launch's kTicketPlanes ints in the workspace of the call, so the plan stays read-only (it may be in use on several
-// streams).  nullptr: the static round robin of listed_item.  The one-workgroup-per-range launch, always enqueued just
-// before the persistent one on the same stream with the same gridDim.y, zeroes the counters as its first statement
-// (before any early return).  The zero is an atomic exchange: every access to a counter is a device-scope atomic,
-// performed where the adds are, and none depends on the end-of-kernel write-back of one XCD's L2.
-__device__ __forceinline__ void reset_tickets(int *tickets)
-{
-    if (tickets && blockIdx.x == 0 && threadIdx.x == 0) (void)atomicExch(&tickets[blockIdx.y], 0);
-}
-
-// Next entry of the work list for this workgroup of a persistent launch (n_items or more: none left): its own index
-// first, then tickets -- or the static round robin.  Called by all threads of the workgroup together; `word` is an LDS
-// int of the workgroup.
-__device__ __forceinline__ int next_work_item(int *tickets, int *word, const int prev /* < 0: first call */)
-{
-    if (prev < 0) return (int)blockIdx.x;
-    if (!tickets) return prev + (int)gridDim.x;
-    __syncthreads();  // every wave is done with the previous item (and has read the previous ticket)
-    if (threadIdx.x == 0) *word = (int)gridDim.x + atomicAdd(&tickets[blockIdx.y], 1);
-    __syncthreads();
-    return *word;
-}
-
-// Entry `item` (= round * gridDim.x + blockIdx.x) of a persistent launch over the plan's sorted work list: a static
-// round robin, every other round in reverse -- the workgroup that took the biggest item of one round takes the
-// smallest of the next.  (A partial last round stays in order.)
-__device__ __forceinline__ int4 listed_item(const int4 *__restrict__ sorted, const int item, const int n_items)
-{
-    const int G = (int)gridDim.x, round = item / G;
-    const bool reverse = (round & 1) && (round + 1) * G <= n_items;
-    return sorted[reverse ? (round + 1) * G - 1 - (int)blockIdx.x : item];
-}
-
 #endif // __HIPCC__
 
 // ---- plan layout -----------------------------------------------------------
@@ -375,8 +362,7 @@ __device__ __forceinline__ int4 listed_item(const int4 *__restrict__ sorted, con
 //   [0] = {entries, any range cut, 1 = walk the list, 0};  then one int2 {entries, first entry} per point set;
 //   then the entries {point set * pencils + pencil, first slab, end slab, points} as they were produced;
 //   then the same entries grouped by point set, every set's biggest first.
-// ONE persistent launch walks a set's part of the sorted list instead (entries handed out by tickets: next_work_item).  Both
-// launches are always enqueued; the one that is not the plan's returns at once.
+// The matrix-core kernels run a balanced plan one workgroup per range and any other from its list (range_items.h).
 constexpr int kSegMax = 32;      // most ranges per pencil
 constexpr int kSegPieces = 16;   // most pieces a range is cut into
 double items_per_cu();  // api.hip: work items per CU the ranges of a pencil are sized for (5.4; NFFT_HIP_ITEMS_PER_CU: tuning)

@@ -3,8 +3,8 @@
 // Same result as interp_mfma.hip / the reference's forward_window_convolution kernels
 // (csrc/cuda/spatial_window_operations.cu:214-332); the reference loops over the trailing columns inside its
 // kernel (":281-330") re-using shift and psi of a point for every column.  Here the sharing is:
-//   * a workgroup of 8 waves takes one work item of the wide tiling (point set, pencil, range of slabs) for 8
-//     consecutive grid planes of that point set -- 8 real coefficient columns; wave w owns column w;
+//   * a workgroup of 8 waves takes one work item of the wide tiling (range_items.h: point set, pencil, range of
+//     slabs) for 8 consecutive grid planes of that point set -- 8 real coefficient columns; wave w owns column w;
 //   * what depends only on the POINTS is built once per block of 32 points and shared through LDS by all 8
 //     columns: the B fragments (psi2 on the 64 padded columns, f16-split, in MFMA register order), the 16 psi1
 //     weights per lane, the cell / fraction along axis 0 -- in interp_mfma.hip every (set, column) plane has its
@@ -24,8 +24,8 @@
 
 #include "common.h"
 #include "kernels.h"
-#include "lane_gather.h"
 #include "mfma_split.h"
+#include "range_items.h"
 
 namespace nfft {
 
@@ -84,10 +84,8 @@ interp_cols_kernel(const Geom g, const int *__restrict__ tile_offsets,
     const int pencils = g.nta[1] * g.nta[2];
     const int M = g.M;
 
-    // (work items as in spread_mfma.hip: one workgroup per range, or a persistent grid over the plan's work list)
-    const int listed = work[0].z;
-    if (OVERFLOW ? !listed : listed) return;
-    // (a plane walks its own point set's part of the sorted list: set_hdr[b] = {entries, first entry})
+    // work items (range_items.h; work_items written out: as a call it changed the persistent form's code)
+    if (!plan_launch<OVERFLOW>(work)) return;
     const int2 set_hdr = OVERFLOW ? ((const int2 *)(work + 1))[b] : make_int2(1, 0);
     const int n_items = set_hdr.x;
     const int4 *const entries = sorted + set_hdr.y;
@@ -100,10 +98,7 @@ interp_cols_kernel(const Geom g, const int *__restrict__ tile_offsets,
         sb = it.y;
         se = it.z;
     } else {
-        pencil = (int)blockIdx.x / nsegm;
-        const int seg = (int)blockIdx.x - pencil * nsegm;
-        sb = min(seg * seg_slabs, M);
-        se = min(sb + seg_slabs, M);
+        range_of_block(nsegm, seg_slabs, M, pencil, sb, se);
     }
     if (se <= sb) continue;
     const int bin0 = b * g.tiles_per_batch + pencil * g.np0;  // one plan bin per slab
@@ -317,51 +312,22 @@ interp_cols_kernel(const Geom g, const int *__restrict__ tile_offsets,
 
 bool interp_cols_supported(const Geom &g) { return g.dim == 3 && g.wide && !g.owned; }
 
-template <int W>
-static int launch_ic_t(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                       int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
-{
-    const char *base = (const char *)plan;
-    const int *to = (const int *)(base + L.off_offsets);
-    const float *spos = (const float *)(base + L.off_spos);
-    const int4 *work = (const int4 *)(base + L.off_work), *sorted = work + L.work_head + L.work_cap;
-    const int64_t pencils = (int64_t)g.nta[1] * g.nta[2];
-    int64_t nsets = g.tiles_per_batch > 0 ? L.ntiles / g.tiles_per_batch : 1;
-    if (nsets < 1) nsets = 1;
-    const int nsegm = seg_base_runs(n, nsets, pencils, g.M, device_cu_count());
-    const int seg_slabs = (g.M + nsegm - 1) / nsegm;
-    // column groups that intersect the planes [plane0, plane0 + nplanes)
-    const int64_t G = (Cr + kIcWaves - 1) / kIcWaves;
-    auto group_of = [&](int64_t pl) { return (pl / Cr) * G + (pl % Cr) / kIcWaves; };
-    const int64_t group0 = group_of(plane0), ngroups = group_of(plane0 + nplanes - 1) - group0 + 1;
-    if (ngroups > 65535) { set_error("Input mismatch: too many planes for one interpolate call"); return 1; }
-    static DeviceOnce attr_done;
-    if (attr_done.first_use()) {
-        NFFT_HIP_CHECK(hipFuncSetAttribute((const void *)interp_cols_kernel<W, false>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(IcLds)));
-        NFFT_HIP_CHECK(hipFuncSetAttribute((const void *)interp_cols_kernel<W, true>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(IcLds)));
-        attr_done.mark();
-    }
-    const dim3 blocks((unsigned)(pencils * nsegm), (unsigned)ngroups);
-    // The persistent launch over the work list (unbalanced plans; its workgroups leave at once otherwise) hands its entries
-    // out by tickets when its planes fit the call's counters, else round robin; the launch before it zeroes the counters.
-    if (ngroups > kTicketPlanes) tickets = nullptr;
-    hipLaunchKernelGGL((interp_cols_kernel<W, false>), blocks, dim3(kIcThreads), sizeof(IcLds), stream, g, to, spos,
-                       grid, (int)Cr, plane0, nplanes, group0, yr, seg_slabs, nsegm, work, sorted, tickets);
-    const dim3 oblocks(work_list_workgroups(n, nsets, pencils, nsegm, device_cu_count()), (unsigned)ngroups);
-    hipLaunchKernelGGL((interp_cols_kernel<W, true>), oblocks, dim3(kIcThreads), sizeof(IcLds), stream, g, to,
-                       spos, grid, (int)Cr, plane0, nplanes, group0, yr, seg_slabs, nsegm, work, sorted, tickets);
-    NFFT_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
 int launch_interp_cols(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                        int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
 {
     if (nplanes <= 0 || n <= 0) return 0;
     return with_window<7>(g.m, "matrix-core interpolation supports cutoff 1..7", [&](auto w) {
-        return launch_ic_t<decltype(w)::value>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+        constexpr int W = decltype(w)::value;
+        // column groups that intersect the planes [plane0, plane0 + nplanes)
+        const int64_t G = (Cr + kIcWaves - 1) / kIcWaves;
+        auto group_of = [&](int64_t pl) { return (pl / Cr) * G + (pl % Cr) / kIcWaves; };
+        const int64_t group0 = group_of(plane0), ngroups = group_of(plane0 + nplanes - 1) - group0 + 1;
+        if (ngroups > 65535) { set_error("Input mismatch: too many planes for one interpolate call"); return 1; }
+        return launch_range_kernels<interp_cols_kernel<W, false>, interp_cols_kernel<W, true>>(
+            g, L, plan, n, ngroups, sizeof(IcLds), tickets, [&](auto kernel, dim3 blocks, const RangeArgs &a) {
+                hipLaunchKernelGGL(kernel, blocks, dim3(kIcThreads), sizeof(IcLds), stream, g, a.tile_offsets, a.spos, grid,
+                                   (int)Cr, plane0, nplanes, group0, yr, a.seg_slabs, a.nsegm, a.work, a.sorted, a.tickets);
+            });
     });
 }
 

@@ -19,8 +19,8 @@
 
 #include "common.h"
 #include "kernels.h"
-#include "lane_gather.h"
 #include "mfma_split.h"
+#include "range_items.h"
 
 namespace nfft {
 
@@ -61,15 +61,12 @@ interp_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets,
     const int cr = plane - b * Cr;
     const int pencils = g.nta[1] * g.nta[2];
 
-    // ---- work items: the same ranges of slabs (or, for unbalanced plans, the entries of the plan's work list) as the
-    // spreading kernel (spread_mfma.hip); an item owns the chunks whose first slab lies in its range.
-    // (work items as in spread_mfma.hip: one workgroup per range, or a persistent grid over the plan's work list)
-    const int listed = work[0].z;
-    if (OVERFLOW ? !listed : listed) return;
-    // (a plane walks its own point set's part of the sorted list: set_hdr[b] = {entries, first entry})
-    const int2 set_hdr = OVERFLOW ? ((const int2 *)(work + 1))[b] : make_int2(1, 0);
-    const int n_items = set_hdr.x;
-    const int4 *const entries = sorted + set_hdr.y;
+    // ---- work items (range_items.h): the ranges of slabs of the spreading kernel, or the entries of the plan's work
+    // list; an item owns the chunks whose first slab lies in its range.
+    if (!plan_launch<OVERFLOW>(work)) return;
+    const WorkItems items = work_items<OVERFLOW>(work, sorted, b);
+    const int n_items = items.n;
+    const int4 *const entries = items.entries;
     for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : 0; item < n_items;
          item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : 1) {
     if (OVERFLOW && item != (int)blockIdx.x) __syncthreads();  // the previous item is done with the LDS
@@ -80,10 +77,7 @@ interp_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets,
         sb = it.y;
         se = it.z;
     } else {
-        pencil = (int)blockIdx.x / nsegm;
-        const int seg = (int)blockIdx.x - pencil * nsegm;
-        sb = min(seg * seg_slabs, g.M);
-        se = min(sb + seg_slabs, g.M);
+        range_of_block(nsegm, seg_slabs, g.M, pencil, sb, se);
     }
     const int j2 = pencil % g.nta[2];
     const int j1 = pencil / g.nta[2];
@@ -268,50 +262,17 @@ interp_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets,
 
 bool interp_mfma_supported(const Geom &g) { return g.dim == 3 && g.wide; }
 
-template <int W>
-static int launch_gm_t(const Geom &g, const PlanLayout &L, const void *plan, const int *to,
-                       const float *spos, const float *grid, int64_t n, int64_t Cr, int64_t plane0, int64_t nplanes,
-                       float *yr, int *tickets, hipStream_t stream)
-{
-    // the work decomposition of the spreading kernel (ranges of M / runs slabs per pencil + the plan's work list
-    // for dense ranges); every item starts by staging all 16 planes of its first chunk
-    const int64_t pencils = (int64_t)g.nta[1] * g.nta[2];
-    int64_t nsets = g.tiles_per_batch > 0 ? L.ntiles / g.tiles_per_batch : 1;
-    if (nsets < 1) nsets = 1;
-    const int nsegm = seg_base_runs(n, nsets, pencils, g.M, device_cu_count());
-    const int seg_slabs = (g.M + nsegm - 1) / nsegm;
-    const dim3 blocks((unsigned)(pencils * nsegm), (unsigned)nplanes);
-    static DeviceOnce attr_done;
-    if (attr_done.first_use()) {
-        NFFT_HIP_CHECK(hipFuncSetAttribute((const void *)interp_mfma_kernel<W, false>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(GatherMfmaLds)));
-        NFFT_HIP_CHECK(hipFuncSetAttribute((const void *)interp_mfma_kernel<W, true>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(GatherMfmaLds)));
-        attr_done.mark();
-    }
-    const char *base = (const char *)plan;
-    const int4 *work = (const int4 *)(base + L.off_work), *sorted = work + L.work_head + L.work_cap;
-    // The persistent launch over the work list (unbalanced plans; its workgroups leave at once otherwise) hands its entries
-    // out by tickets when its planes fit the call's counters, else round robin; the launch before it zeroes the counters.
-    if (nplanes > kTicketPlanes) tickets = nullptr;
-    hipLaunchKernelGGL((interp_mfma_kernel<W, false>), blocks, dim3(kGmThreads), sizeof(GatherMfmaLds), stream, g, to,
-                       spos, grid, (int)Cr, (int)plane0, yr, seg_slabs, nsegm, work, sorted, tickets);
-    const dim3 oblocks(work_list_workgroups(n, nsets, pencils, nsegm, device_cu_count()), (unsigned)nplanes);
-    hipLaunchKernelGGL((interp_mfma_kernel<W, true>), oblocks, dim3(kGmThreads), sizeof(GatherMfmaLds), stream, g,
-                       to, spos, grid, (int)Cr, (int)plane0, yr, seg_slabs, nsegm, work, sorted, tickets);
-    NFFT_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
 int launch_interp_mfma(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                        int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
 {
-    const char *base = (const char *)plan;
-    const int *to = (const int *)(base + L.off_offsets);
-    const float *spos = (const float *)(base + L.off_spos);
     if (nplanes <= 0 || n <= 0) return 0;
     return with_window<7>(g.m, "matrix-core interpolation supports cutoff 1..7", [&](auto w) {
-        return launch_gm_t<decltype(w)::value>(g, L, plan, to, spos, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+        constexpr int W = decltype(w)::value;
+        return launch_range_kernels<interp_mfma_kernel<W, false>, interp_mfma_kernel<W, true>>(
+            g, L, plan, n, nplanes, sizeof(GatherMfmaLds), tickets, [&](auto kernel, dim3 blocks, const RangeArgs &a) {
+                hipLaunchKernelGGL(kernel, blocks, dim3(kGmThreads), sizeof(GatherMfmaLds), stream, g, a.tile_offsets, a.spos,
+                                   grid, (int)Cr, (int)plane0, yr, a.seg_slabs, a.nsegm, a.work, a.sorted, a.tickets);
+            });
     });
 }
 

@@ -29,8 +29,8 @@
 
 #include "common.h"
 #include "kernels.h"
-#include "lane_gather.h"
 #include "mfma_split.h"
+#include "range_items.h"
 
 namespace nfft {
 
@@ -121,13 +121,11 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
     const int pencils = g.nta[1] * g.nta[2];
     const int M = g.M;
 
-    // (work items as in spread_mfma.hip: one workgroup per range, or a persistent grid over the plan's work list)
-    const int listed = work[0].z;
-    if (OVERFLOW ? !listed : listed) return;
-    // (a plane walks its own point set's part of the sorted list: set_hdr[b] = {entries, first entry})
-    const int2 set_hdr = OVERFLOW ? ((const int2 *)(work + 1))[b] : make_int2(1, 0);
-    const int n_items = set_hdr.x;
-    const int4 *const entries = sorted + set_hdr.y;
+    // work items (range_items.h)
+    if (!plan_launch<OVERFLOW>(work)) return;
+    const WorkItems items = work_items<OVERFLOW>(work, sorted, b);
+    const int n_items = items.n;
+    const int4 *const entries = items.entries;
     for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : 0; item < n_items;
          item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : 1) {
     int pencil, sb, se;
@@ -137,10 +135,7 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
         sb = it.y;
         se = it.z;
     } else {
-        pencil = (int)blockIdx.x / nsegm;
-        const int seg = (int)blockIdx.x - pencil * nsegm;
-        sb = min(seg * seg_slabs, M);
-        se = min(sb + seg_slabs, M);
+        range_of_block(nsegm, seg_slabs, M, pencil, sb, se);
     }
     // an item owns the chunks whose first slab lies in its range (as in interp_mfma.hip)
     const int k_begin = (sb + TC - 1) / TC;
@@ -512,63 +507,27 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
 
 bool interp_stream_pays(const Geom &g, const PlanLayout &L, int64_t n)
 {
-    int64_t nsets = g.tiles_per_batch > 0 ? L.ntiles / g.tiles_per_batch : 1;
-    if (nsets < 1) nsets = 1;
-    return stream_items(n, nsets, device_cu_count(), g.M);
+    return stream_items(n, range_split(g, L, n).nsets, device_cu_count(), g.M);
 }
 
 bool interp_stream_supported(const Geom &g) { return g.dim == 3 && g.wide && !g.owned && g.W <= 16; }
-
-template <int W, int NG>
-static int launch_is_t(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                       int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
-{
-    const char *base = (const char *)plan;
-    const int *to = (const int *)(base + L.off_offsets);
-    const int *gs = (const int *)(base + L.off_groups);
-    const float *spos = (const float *)(base + L.off_spos);
-    const int4 *work = (const int4 *)(base + L.off_work), *sorted = work + L.work_head + L.work_cap;
-    const int64_t pencils = (int64_t)g.nta[1] * g.nta[2];
-    int64_t nsets = g.tiles_per_batch > 0 ? L.ntiles / g.tiles_per_batch : 1;
-    if (nsets < 1) nsets = 1;
-    const int nsegm = seg_base_runs(n, nsets, pencils, g.M, device_cu_count());
-    const int seg_slabs = (g.M + nsegm - 1) / nsegm;
-    const dim3 blocks((unsigned)(pencils * nsegm), (unsigned)nplanes);
-    int *const status = device_status_block();
-    static DeviceOnce attr_done;
-    if (attr_done.first_use()) {
-        NFFT_HIP_CHECK(hipFuncSetAttribute((const void *)interp_stream_kernel<W, false, NG>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(StreamLds)));
-        NFFT_HIP_CHECK(hipFuncSetAttribute((const void *)interp_stream_kernel<W, true, NG>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(StreamLds)));
-        attr_done.mark();
-    }
-    // The persistent launch over the work list (unbalanced plans; its workgroups leave at once otherwise) hands its entries
-    // out by tickets when its planes fit the call's counters, else round robin; the launch before it zeroes the counters.
-    if (nplanes > kTicketPlanes) tickets = nullptr;
-    hipLaunchKernelGGL((interp_stream_kernel<W, false, NG>), blocks, dim3(kIsThreads), sizeof(StreamLds), stream, g, to, gs,
-                       spos, grid, (int)Cr, (int)plane0, yr, seg_slabs, nsegm, work, sorted, tickets, status);
-    const dim3 oblocks(work_list_workgroups(n, nsets, pencils, nsegm, device_cu_count()), (unsigned)nplanes);
-    hipLaunchKernelGGL((interp_stream_kernel<W, true, NG>), oblocks, dim3(kIsThreads), sizeof(StreamLds), stream, g, to,
-                       gs, spos, grid, (int)Cr, (int)plane0, yr, seg_slabs, nsegm, work, sorted, tickets, status);
-    NFFT_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-template <int W>
-static int launch_is_w(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
-                       int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
-{
-    return L.grouped ? launch_is_t<W, 3>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream)
-                     : launch_is_t<W, 1>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
-}
 
 int launch_interp_stream(const Geom &g, const PlanLayout &L, const void *plan, const float *grid, int64_t n, int64_t Cr,
                          int64_t plane0, int64_t nplanes, float *yr, int *tickets, hipStream_t stream)
 {
     if (nplanes <= 0 || n <= 0) return 0;
+    const int *gs = (const int *)((const char *)plan + L.off_groups);
     return with_window<7>(g.m, "matrix-core interpolation supports cutoff 1..7", [&](auto w) {
-        return launch_is_w<decltype(w)::value>(g, L, plan, grid, n, Cr, plane0, nplanes, yr, tickets, stream);
+        constexpr int W = decltype(w)::value;
+        int *const status = device_status_block();
+        const auto launch = [&](auto kernel, dim3 blocks, const RangeArgs &a) {
+            hipLaunchKernelGGL(kernel, blocks, dim3(kIsThreads), sizeof(StreamLds), stream, g, a.tile_offsets, gs, a.spos, grid,
+                               (int)Cr, (int)plane0, yr, a.seg_slabs, a.nsegm, a.work, a.sorted, a.tickets, status);
+        };
+        return L.grouped ? launch_range_kernels<interp_stream_kernel<W, false, 3>, interp_stream_kernel<W, true, 3>>(
+                               g, L, plan, n, nplanes, sizeof(StreamLds), tickets, launch)
+                         : launch_range_kernels<interp_stream_kernel<W, false, 1>, interp_stream_kernel<W, true, 1>>(
+                               g, L, plan, n, nplanes, sizeof(StreamLds), tickets, launch);
     });
 }
 

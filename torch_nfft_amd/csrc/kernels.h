@@ -35,7 +35,7 @@ int launch_plane_absmax(const Geom &g_halo, const PlanLayout &L_halo, const void
                         int64_t B, int64_t Cr, unsigned *xmax, hipStream_t stream);
 // coefficients: xr (row-major [point][Cr], read through the index in the plan records) or, when xr == nullptr, xs (copy in
 // plan order, planar, stride L.cap: gather_rows).  tickets: kTicketPlanes ints of the caller's workspace, the counters of
-// the persistent launch over the plan's work list (common.h: next_work_item); nullptr: round robin.  The same for the
+// the persistent launch over the plan's work list (range_items.h: next_work_item); nullptr: round robin.  The same for the
 // matrix-core gathers below.
 int launch_spread_mfma(const Geom &g, const PlanLayout &L, const void *plan, const float *xr, const float *xs,
                        const unsigned *xmax, int64_t n, int64_t Cr, int64_t plane0, int64_t nplanes, float *grid,

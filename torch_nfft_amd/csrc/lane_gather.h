@@ -1,6 +1,5 @@
 // What the one-lane-per-point gathers share: interp_kernel (interp.hip), interp_grad_kernel and interp_hvp_kernel
-// (interp_grad.hip) run on one tile geometry (GatherCfg) and one launch shape (launch_lane_gather); with_window is the
-// cutoff dispatch of every kernel file's host side.
+// (interp_grad.hip) run on one tile geometry (GatherCfg) and one launch shape (launch_lane_gather).
 #pragma once
 #include <type_traits>
 
@@ -45,28 +44,6 @@ struct GatherCfg {
     static constexpr int WPE_HVP = DIM == 2 && W == 10 ? 7 : (DIM <= 2 && W == 18) || (DIM == 3 && !WIDE && W == 6) ? WPE - 1 : WPE;
     static_assert(CELLS * 4 <= 160 * 1024, "LDS budget");
 };
-
-// f(std::integral_constant<int, W>{}) for the window width W = 2m + 2 of the cutoff m in 1..MMAX (the cutoffs the
-// calling kernel file instantiates); any other m: set_error(err) and 1.
-template <int MMAX, class F>
-int with_window(int m, const char *err, F &&f)
-{
-    static_assert(MMAX == 7 || MMAX == 8, "kernels exist for cutoffs 1..7 or 1..8");
-    switch (m) {
-    case 1: return f(std::integral_constant<int, 4>{});
-    case 2: return f(std::integral_constant<int, 6>{});
-    case 3: return f(std::integral_constant<int, 8>{});
-    case 4: return f(std::integral_constant<int, 10>{});
-    case 5: return f(std::integral_constant<int, 12>{});
-    case 6: return f(std::integral_constant<int, 14>{});
-    case 7: return f(std::integral_constant<int, 16>{});
-    case 8:
-        if constexpr (MMAX == 8) return f(std::integral_constant<int, 18>{});
-        break;
-    }
-    set_error(err);
-    return 1;
-}
 
 // The plan arrays a lane gather reads
 struct LanePlan {

@@ -15,11 +15,11 @@
 //     arrays, the staging pipeline fetches x[index] by LDS-DMA two steps after the record (one or two real columns; more
 //     columns come from the plan-ordered copy of gather_rows).  The f16 operand scale is the plane's largest |x|, taken
 //     by plane_absmax_kernel in a pass of its own (no per-item prologue);
-//   * one workgroup (16 waves) sweeps a segment of a pencil.  Plane-owner wave w holds the plane z = w (mod NOWN) of
-//     the sliding window in its accumulators: no LDS accumulator, no barrier to accumulate; it flushes its 32 x 64
-//     tile with global atomics (each instruction = two 128-byte row segments) as soon as the sweep has passed it
-//     and moves on to plane z + NOWN.  NOWN = 12 for 2m+2 <= 12 -- the other four waves, one per SIMD, only stage
-//     points and build operands -- and 16 for wider windows;
+//   * one workgroup (16 waves) sweeps a work item, a range of slabs of a pencil (range_items.h).  Plane-owner wave w
+//     holds the plane z = w (mod NOWN) of the sliding window in its accumulators: no LDS accumulator, no barrier to
+//     accumulate; it flushes its 32 x 64 tile with global atomics (each instruction = two 128-byte row segments) as
+//     soon as the sweep has passed it and moves on to plane z + NOWN.  NOWN = 12 for 2m+2 <= 12 -- the other four
+//     waves, one per SIMD, only stage points and build operands -- and 16 for wider windows;
 //   * per batch of 8 K-blocks the operands are built once in LDS, one batch ahead of the MFMAs, in wave-sized tasks (one
 //     per K-block) handed out through an LDS counter: f16-split B fragments in MFMA register order, and the f16 splits of
 //     the psi1 table [row][point] and of the axis-0 table [tap][point] (x' psi0).  Every owner whose plane lies in a
@@ -45,6 +45,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "mfma_split.h"
+#include "range_items.h"
 
 namespace nfft {
 
@@ -180,15 +181,12 @@ spread_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets, const flo
     const int cr = plane - b * Cr;
     const int pencils = g.nta[1] * g.nta[2];
 
-    // ---- work items (common.h).  Balanced plan: workgroup (pencil, range) sweeps its range of seg_slabs slabs,
-    // straight-line code.  Otherwise a persistent grid walks the plan's work list, biggest items first.  Both launches
-    // are enqueued; the one that is not the plan's leaves here.  (two instantiations: the item loop costs registers)
-    const int listed = work[0].z;
-    if (OVERFLOW ? !listed : listed) return;
-    // (a plane walks its own point set's part of the sorted list: set_hdr[b] = {entries, first entry})
-    const int2 set_hdr = OVERFLOW ? ((const int2 *)(work + 1))[b] : make_int2(1, 0);
-    const int n_items = set_hdr.x;
-    const int4 *const entries = sorted + set_hdr.y;
+    // ---- work items (range_items.h): straight-line code for the range of a balanced plan's workgroup, else a walk of
+    // the plan's work list, biggest items first
+    if (!plan_launch<OVERFLOW>(work)) return;
+    const WorkItems items = work_items<OVERFLOW>(work, sorted, b);
+    const int n_items = items.n;
+    const int4 *const entries = items.entries;
     for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : 0; item < n_items;
          item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : 1) {
     if (OVERFLOW && item != (int)blockIdx.x) __syncthreads();  // the previous item is done with the LDS
@@ -199,10 +197,7 @@ spread_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets, const flo
         sb = it.y;
         se = it.z;
     } else {
-        pencil = (int)blockIdx.x / nsegm;
-        const int seg = (int)blockIdx.x - pencil * nsegm;
-        sb = min(seg * seg_slabs, g.M);
-        se = min(sb + seg_slabs, g.M);
+        range_of_block(nsegm, seg_slabs, g.M, pencil, sb, se);
     }
     const int j2 = pencil % g.nta[2];
     const int j1 = pencil / g.nta[2];
@@ -846,18 +841,12 @@ int launch_plane_absmax(const Geom &g_halo, const PlanLayout &L_halo, const void
 }
 
 template <int W, bool OWNED, bool PAIR>
-static int launch_mfma_t(const Geom &g, const PlanLayout &L, const void *plan, const int *to, const float *spos,
-                         const float *xr, const float *xs, const unsigned *xmax, int64_t n, int64_t Cr, int64_t plane0,
-                         int64_t nplanes, float *grid, int *tickets, hipStream_t stream)
+static int launch_mfma_t(const Geom &g, const PlanLayout &L, const void *plan, const float *xr, const float *xs,
+                         const unsigned *xmax, int64_t n, int64_t Cr, int64_t plane0, int64_t nplanes, float *grid,
+                         int *tickets, hipStream_t stream)
 {
-    // Ranges per pencil: about 5-6 workgroups per CU balance the tail of the launch against the 2m+1 halo planes
-    // every range flushes on top of its own (measured at C3: 6 ranges 7 % faster than 4, 12 in between).  The count
-    // is a function of the plan's sizes only, because the plan's load-balance tables are built for it (common.h).
-    const int64_t pencils = (int64_t)g.nta[1] * g.nta[2];
-    int64_t nsets = g.tiles_per_batch > 0 ? L.ntiles / g.tiles_per_batch : 1;
-    if (nsets < 1) nsets = 1;
-    const int nsegm = seg_base_runs(n, nsets, pencils, g.M, device_cu_count());
-    const int seg_slabs = (g.M + nsegm - 1) / nsegm;
+    // Ranges per pencil (range_split): about 5-6 workgroups per CU balance the tail of the launch against the 2m+1 halo
+    // planes every range flushes on top of its own (measured at C3: 6 ranges 7 % faster than 4, 12 in between).
     // y grid: planes, or the pair slots the chunk of planes touches (paired variant)
     int64_t ny = nplanes;
     if (PAIR) {
@@ -865,51 +854,14 @@ static int launch_mfma_t(const Geom &g, const PlanLayout &L, const void *plan, c
         const int64_t s0 = (plane0 / Cr) * P + (plane0 % Cr) / 2, s1 = (last / Cr) * P + (last % Cr) / 2;
         ny = s1 - s0 + 1;
     }
-    const dim3 blocks((unsigned)(pencils * nsegm), (unsigned)ny);
-    static DeviceOnce attr_done;  // one workgroup per CU: the double-buffered operands take most of the 160 KB LDS
-    if (attr_done.first_use()) {
-        NFFT_HIP_CHECK(hipFuncSetAttribute((const void *)spread_mfma_kernel<W, false, OWNED, PAIR>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MfmaLds<W>)));
-        NFFT_HIP_CHECK(hipFuncSetAttribute((const void *)spread_mfma_kernel<W, true, OWNED, PAIR>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MfmaLds<W>)));
-        attr_done.mark();
-    }
-    const char *base = (const char *)plan;
-    const int4 *work = (const int4 *)(base + L.off_work), *sorted = work + L.work_head + L.work_cap;
     int *const status = device_status_block();
-    // The persistent launch over the work list (unbalanced plans; its workgroups leave at once otherwise) hands its entries
-    // out by tickets when its planes fit the call's counters, else round robin; the launch before it zeroes the counters.
-    if (ny > kTicketPlanes) tickets = nullptr;
-    hipLaunchKernelGGL((spread_mfma_kernel<W, false, OWNED, PAIR>), blocks, dim3(kMfmaThreads), sizeof(MfmaLds<W>), stream, g, to,
-                       spos, xr, xs, L.cap, xmax, (int)Cr, (int)plane0, (int)nplanes, grid, seg_slabs, nsegm, work, sorted,
-                       tickets, status);
-    const dim3 oblocks(work_list_workgroups(n, nsets, pencils, nsegm, device_cu_count()), (unsigned)ny);
-    hipLaunchKernelGGL((spread_mfma_kernel<W, true, OWNED, PAIR>), oblocks, dim3(kMfmaThreads), sizeof(MfmaLds<W>), stream, g, to,
-                       spos, xr, xs, L.cap, xmax, (int)Cr, (int)plane0, (int)nplanes, grid, seg_slabs, nsegm, work, sorted, tickets,
-                       status);
-    NFFT_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-template <bool OWNED, bool PAIR>
-static int launch_mfma_w(const Geom &g, const PlanLayout &L, const void *plan, const float *xr, const float *xs,
-                         const unsigned *xmax, int64_t n, int64_t Cr, int64_t plane0, int64_t nplanes, float *grid,
-                         int *tickets, hipStream_t stream)
-{
-    const char *base = (const char *)plan;
-    const int *to = (const int *)(base + L.off_offsets);
-    const float *spos = (const float *)(base + L.off_spos);
-    switch (g.m) {
-    case 1: return launch_mfma_t<4, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
-    case 2: return launch_mfma_t<6, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
-    case 3: return launch_mfma_t<8, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
-    case 4: return launch_mfma_t<10, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
-    case 5: return launch_mfma_t<12, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
-    case 6: return launch_mfma_t<14, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
-    case 7: return launch_mfma_t<16, OWNED, PAIR>(g, L, plan, to, spos, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
-    }
-    set_error("matrix-core spreading supports cutoff 1..7");
-    return 1;
+    // one workgroup per CU: the double-buffered operands take most of the 160 KB LDS
+    constexpr size_t lds = sizeof(MfmaLds<W>);
+    return launch_range_kernels<spread_mfma_kernel<W, false, OWNED, PAIR>, spread_mfma_kernel<W, true, OWNED, PAIR>>(
+        g, L, plan, n, ny, lds, tickets, [&](auto kernel, dim3 blocks, const RangeArgs &a) {
+            hipLaunchKernelGGL(kernel, blocks, dim3(kMfmaThreads), lds, stream, g, a.tile_offsets, a.spos, xr, xs, L.cap, xmax,
+                               (int)Cr, (int)plane0, (int)nplanes, grid, a.seg_slabs, a.nsegm, a.work, a.sorted, a.tickets, status);
+        });
 }
 
 // `n` is the problem's point count (it fixes the work decomposition the plan was built for); the plan may hold more
@@ -930,9 +882,12 @@ int launch_spread_mfma(const Geom &g, const PlanLayout &L, const void *plan, con
         set_error("Input mismatch: a plan of the paired owned tiling (num_columns >= 2) used with one real column");
         return 1;
     }
-    return g.pair    ? launch_mfma_w<true, true>(g, L, plan, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream)
-           : g.owned ? launch_mfma_w<true, false>(g, L, plan, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream)
-                     : launch_mfma_w<false, false>(g, L, plan, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
+    return with_window<7>(g.m, "matrix-core spreading supports cutoff 1..7", [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        return g.pair    ? launch_mfma_t<W, true, true>(g, L, plan, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream)
+               : g.owned ? launch_mfma_t<W, true, false>(g, L, plan, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream)
+                         : launch_mfma_t<W, false, false>(g, L, plan, xr, xs, xmax, n, Cr, plane0, nplanes, grid, tickets, stream);
+    });
 }
 
 } // namespace nfft
