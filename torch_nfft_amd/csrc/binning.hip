@@ -21,13 +21,33 @@ constexpr int kSortThreads = 512;
 constexpr int kMaxPencilsLds = 8192;    // first-level bins that fit an LDS histogram
 constexpr int kSort2Parts = 8;          // workgroups that share one first-level bin in the second level (a dense bin of a
                                         // clustered input is otherwise one workgroup's serial loop: 1.4 ms at C3-clustered)
+// Second level in one pass (sort2_lds_kernel): a first-level bin of up to kFuseCap records is sorted by ONE workgroup that
+// holds kFuseRecs records per thread in registers and writes the bin's range through LDS in rounds of kFuseChunk records.
+constexpr int kFuseThreads = 1024;
+constexpr int kFuseRecs = 16;
+constexpr int kFuseCap = kFuseThreads * kFuseRecs;  // 16 384 records (256 KB) per bin
+constexpr int kFuseChunk = 8192;                    // records per LDS round (128 KB)
+constexpr int kFuseMaxKeys = 4096;                  // fine keys per bin that fit next to them (16 KB)
+constexpr int kFuseLds = kFuseChunk * 16 + kFuseMaxKeys * 4;
 
 PlanLayout plan_layout(const Geom &g, int64_t n, int64_t B)
 {
     PlanLayout L;
     L.cap = g.owned ? 4 * n : n;
     L.ntiles = (int64_t)g.tiles_per_batch * B * g.SB;  // (tile, sub-block) bins
-    L.npencils = (int64_t)g.nta[1] * g.nta[2] * B * g.l1seg;  // first-level bins: (batch, pencil, segment)
+    // first-level segments of the wide tiling: g.l1bins slabs (128), halved while the expected entries of a segment exceed
+    // 3/4 of what the one-pass second level holds (kFuseCap), so that the bins of a uniform input take that pass (10^7 points
+    // at N = 256: 10.9k per segment of 128 slabs; 10^6 at N = 64: 6.9k per segment of 16), as long as the first level
+    // keeps its LDS histogram
+    L.l1bins = g.l1bins;
+    if (g.wide) {
+        const double per_slab = (double)n * (g.owned ? 2.0 : 1.0) / ((double)B * g.nta[1] * g.nta[2] * g.np0);
+        while (L.l1bins > 16 && per_slab * L.l1bins > 0.75 * kFuseCap &&
+               (int64_t)g.nta[1] * g.nta[2] * B * ((g.np0 + L.l1bins / 2 - 1) / (L.l1bins / 2)) <= kMaxPencilsLds)
+            L.l1bins /= 2;
+    }
+    L.l1seg = (g.np0 + L.l1bins - 1) / L.l1bins;
+    L.npencils = (int64_t)g.nta[1] * g.nta[2] * B * L.l1seg;  // first-level bins: (batch, pencil, segment)
     // first-level slices: 16 384 points for big inputs, smaller ones (>= 1 024) as long as that gives fewer than ~512
     // workgroups -- at n = 10^5 seven workgroups of 16 384 took 22 + 14 us for the two passes
     L.block_points = 1024;
@@ -51,7 +71,7 @@ PlanLayout plan_layout(const Geom &g, int64_t n, int64_t B)
     L.off_hscan = o;   o = align_up(o + (L.two_level ? scan_items * 4 : 0), 256);
     L.off_tmp = o;     o = align_up(o + (L.two_level ? L.cap * 16 : 0), 256);
     // second level: per (first-level bin, part) counts of the fine keys
-    L.off_hist2 = o;   o = align_up(o + (L.two_level ? L.npencils * kSort2Parts * (int64_t)g.l1bins * g.SB * g.CG * 4 : 0), 256);
+    L.off_hist2 = o;   o = align_up(o + (L.two_level ? L.npencils * kSort2Parts * (int64_t)L.l1bins * g.SB * g.CG * 4 : 0), 256);
     L.grouped = L.two_level && g.CG == 3;
     L.off_groups = o;  o = align_up(o + (L.grouped ? L.ntiles * 2 * 4 : 0), 256);
     // work list of the matrix-core kernels (wide tiling; segment_split_kernel / work_order_kernel below): a header,
@@ -417,8 +437,25 @@ __device__ __forceinline__ int fine_key(const Geom &g, const float4 rec, const i
 // Second level: the records of first-level bin l1 are counting-sorted by fine key (slab, sub-block) by kSort2Parts
 // workgroups, each taking an equal share of the bin's records: a count pass (per-part histograms to HBM) and a
 // scatter pass whose prologue turns the bin's small table of counts into this part's cursors.
-__device__ __forceinline__ void sort2_range(const int *__restrict__ hscan, int l1, int nblocks, int part, int &p0,
-                                            int &r0, int &r1)
+// Which second level runs is decided on the device, for the whole plan: the one-pass kernel when EVERY first-level bin
+// fits it (a uniform input), else the eight parts for every bin.  Taking the one-pass kernel only for the bins of a
+// clustered input that fit it cost C3-clustered 0.01-0.07 ms of plan and 0.06-0.17 ms of gather (why is open: both paths
+// order a plan bin by LDS atomics; profiles/r05_plan_ab.txt).  *route = 1: one pass, and then every bin fits it.
+__global__ void __launch_bounds__(1024) sort2_route_kernel(int npencils, int nblocks, const int *__restrict__ hscan,
+                                                           int *__restrict__ route)
+{
+    __shared__ int big;
+    if (threadIdx.x == 0) big = 0;
+    __syncthreads();
+    for (int l1 = threadIdx.x; l1 < npencils; l1 += 1024)
+        if (hscan[(int64_t)(l1 + 1) * nblocks] - hscan[(int64_t)l1 * nblocks] > kFuseCap) big = 1;
+    __syncthreads();
+    if (threadIdx.x == 0) *route = big ? 0 : 1;
+}
+
+// (sort2_count / sort2_scatter return at once when the one-pass kernel has the plan: `route` != null and *route = 1)
+__device__ __forceinline__ bool sort2_range(const int *__restrict__ hscan, int l1, int nblocks, int part,
+                                            const int *__restrict__ route, int &p0, int &r0, int &r1)
 {
     // (the scan has one item more than there are (bin, block) counts: its last entry is the number of plan entries,
     // n for ordinary plans, larger for the owned tiling)
@@ -427,11 +464,12 @@ __device__ __forceinline__ void sort2_range(const int *__restrict__ hscan, int l
     const int64_t len = p1 - p0;
     r0 = p0 + (int)(len * part / kSort2Parts);
     r1 = p0 + (int)(len * (part + 1) / kSort2Parts);
+    return !(route && *route);
 }
 
 template <bool COMMON>
 __global__ void __launch_bounds__(kSortThreads)
-sort2_count_kernel(Geom g_in, int nblocks, const int *__restrict__ hscan, const float4 *__restrict__ tmp,
+sort2_count_kernel(Geom g_in, int nblocks, const int *__restrict__ route, const int *__restrict__ hscan, const float4 *__restrict__ tmp,
                    int *__restrict__ hist2 /* [l1][part][key] */, unsigned short *__restrict__ key2 /* fine key of every record */)
 {
     // COMMON: a 3-D problem on the scatter tiling (every benchmark configuration): with the two flags constant the
@@ -446,7 +484,7 @@ sort2_count_kernel(Geom g_in, int nblocks, const int *__restrict__ hscan, const 
     const int col0 = (pencil % g.nta[2]) * g.Ta[2];
     const int nt0 = (min(g.np0, bin_lo + g.l1bins) - bin_lo) * g.SB * g.CG;  // fine keys of this first-level bin
     int p0, r0, r1;
-    sort2_range(hscan, l1, nblocks, part, p0, r0, r1);
+    if (!sort2_range(hscan, l1, nblocks, part, route, p0, r0, r1)) return;
     for (int i = threadIdx.x; i < nt0; i += kSortThreads) lds2[i] = 0;
     __syncthreads();
     for (int j0 = r0 + threadIdx.x; j0 < r1; j0 += kSortThreads * 8) {
@@ -470,7 +508,7 @@ sort2_count_kernel(Geom g_in, int nblocks, const int *__restrict__ hscan, const 
 }
 
 __global__ void __launch_bounds__(kSortThreads)
-sort2_scatter_kernel(Geom g, int npencils, int nblocks, const int *__restrict__ hscan, const float4 *__restrict__ tmp,
+sort2_scatter_kernel(Geom g, int npencils, int nblocks, const int *__restrict__ route, const int *__restrict__ hscan, const float4 *__restrict__ tmp,
                      const int *__restrict__ hist2, const unsigned short *__restrict__ key2, int *__restrict__ offsets,
                      int *__restrict__ groups, int *__restrict__ perm, float *__restrict__ spos)
 {
@@ -482,7 +520,7 @@ sort2_scatter_kernel(Geom g, int npencils, int nblocks, const int *__restrict__ 
     const int64_t obase = ((int64_t)pencil * g.np0 + bin_lo) * g.SB;   // first entry of these keys in the offsets table
                                                                         // (one entry per CG ordering keys)
     int p0, r0, r1;
-    sort2_range(hscan, l1, nblocks, part, p0, r0, r1);
+    if (!sort2_range(hscan, l1, nblocks, part, route, p0, r0, r1)) return;
     const int *table = hist2 + (int64_t)l1 * kSort2Parts * g.l1bins * g.SB * g.CG;
     const int kstride = g.l1bins * g.SB * g.CG;
     // cursor of a key = p0 + keys before (totals over the parts) + the same key in the parts before this one.
@@ -548,6 +586,87 @@ sort2_scatter_kernel(Geom g, int npencils, int nblocks, const int *__restrict__ 
                 if (g.dim > 1) spos[(int64_t)slot * g.dim + 1] = rec.y;
             }
         }
+    }
+}
+
+// Second level in one pass for plans whose first-level bins all hold at most kFuseCap records (uniform inputs; plan_layout
+// sizes the segments for it): one workgroup per bin loads the records with coalesced 16-byte loads into registers, ranks
+// them by fine key with LDS atomics, scans the keys (offsets / groups of the bin's plan bins), and writes the bin's range
+// in rounds of kFuseChunk records through LDS -- consecutive lanes store consecutive records.  Against the two passes of
+// eight parts: no count pass, no key2, one read of the records instead of two, coalesced stores instead of one scattered
+// 16-byte store per record.  (The order inside a plan bin is that of the LDS atomics, as in the eight-part path.)
+template <bool COMMON>
+__global__ void __launch_bounds__(kFuseThreads)
+sort2_lds_kernel(Geom g_in, int npencils, int nblocks, const int *__restrict__ route, const int *__restrict__ hscan,
+                 const float4 *__restrict__ tmp, int *__restrict__ offsets, int *__restrict__ groups, float4 *__restrict__ spos)
+{
+    if (!*route) return;  // (sort2_count / sort2_scatter)
+    Geom g = g_in;
+    if constexpr (COMMON) { g.dim = 3; g.owned = 0; }
+    extern __shared__ float4 lds_rec[];  // [kFuseChunk] records of the current round, then [fine keys] cursors
+    int *const cur = (int *)(lds_rec + kFuseChunk);
+    const int l1 = blockIdx.x;
+    const int p0 = hscan[(int64_t)l1 * nblocks];
+    const int len = hscan[(int64_t)(l1 + 1) * nblocks] - p0;
+    const int pencil = l1 / g.l1seg, sg = l1 - pencil * g.l1seg;
+    const int bin_lo = sg * g.l1bins;
+    const int col0 = (pencil % g.nta[2]) * g.Ta[2];
+    const int nt0 = (min(g.np0, bin_lo + g.l1bins) - bin_lo) * g.SB * g.CG;  // fine keys of this bin (<= kFuseMaxKeys)
+    const int64_t obase = ((int64_t)pencil * g.np0 + bin_lo) * g.SB;
+    for (int i = threadIdx.x; i < nt0; i += kFuseThreads) cur[i] = 0;
+    __syncthreads();
+    float4 rec[kFuseRecs];
+    int dst[kFuseRecs];  // (key << 14 | rank inside the key), then the record's slot in the bin; -1: no record
+#pragma unroll
+    for (int q = 0; q < kFuseRecs; ++q) {
+        const int j = q * kFuseThreads + (int)threadIdx.x;
+        rec[q] = j < len ? tmp[p0 + j] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int q = 0; q < kFuseRecs; ++q) {
+        const int j = q * kFuseThreads + (int)threadIdx.x;
+        dst[q] = -1;
+        if (j < len) {
+            const int key = fine_key(g, rec[q], bin_lo, col0);
+            dst[q] = key << 14 | atomicAdd(&cur[key], 1);  // (rank < kFuseCap <= 2^14)
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {  // exclusive scan of the key counts, one wave: cursors, and the plan's offsets / groups
+        int carry = 0;
+        for (int base = 0; base < nt0; base += 64) {
+            const int idx = base + threadIdx.x;
+            const int tot = idx < nt0 ? cur[idx] : 0;
+            int incl = tot;
+            for (int off = 1; off < 64; off <<= 1) {
+                const int t = __shfl_up(incl, off);
+                if ((int)threadIdx.x >= off) incl += t;
+            }
+            if (idx < nt0) {
+                const int excl = carry + incl - tot;
+                cur[idx] = excl;
+                const int bin = idx / g.CG, grp = idx - bin * g.CG;
+                if (grp == 0) offsets[obase + bin] = p0 + excl;
+                else groups[(obase + bin) * 2 + grp - 1] = p0 + excl;
+            }
+            carry += __shfl(incl, 63);
+        }
+        if (l1 == npencils - 1 && threadIdx.x == 0) offsets[obase + nt0 / g.CG] = p0 + carry;  // = entries
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kFuseRecs; ++q)
+        if (dst[q] >= 0) dst[q] = cur[dst[q] >> 14] + (dst[q] & ((1 << 14) - 1));
+    for (int c0 = 0; c0 < len; c0 += kFuseChunk) {
+#pragma unroll
+        for (int q = 0; q < kFuseRecs; ++q) {
+            const unsigned s = (unsigned)(dst[q] - c0);  // (no record: dst = -1, a huge s)
+            if (s < (unsigned)kFuseChunk) lds_rec[s] = rec[q];
+        }
+        __syncthreads();
+        const int cn = min(kFuseChunk, len - c0);
+        for (int s = threadIdx.x; s < cn; s += kFuseThreads) spos[p0 + c0 + s] = lds_rec[s];
+        __syncthreads();
     }
 }
 
@@ -842,9 +961,12 @@ static int exclusive_scan(const int *in, int *out, int64_t items, void *scratch,
     return 0;
 }
 
-int launch_plan_points(const Geom &g, const PlanLayout &L, const float *pos, const int64_t *batch, int64_t n, int64_t B,
+int launch_plan_points(const Geom &g_in, const PlanLayout &L, const float *pos, const int64_t *batch, int64_t n, int64_t B,
                        void *plan, hipStream_t stream)
 {
+    Geom g = g_in;  // (with the plan's first-level segments)
+    g.l1bins = L.l1bins;
+    g.l1seg = L.l1seg;
     char *base = (char *)plan;
     int *offsets = (int *)(base + L.off_offsets);
     int *cursor = (int *)(base + L.off_cursor);
@@ -866,7 +988,9 @@ int launch_plan_points(const Geom &g, const PlanLayout &L, const float *pos, con
                            device_status_block());
         // (1-D / 2-D: the first level is the whole sort; a small table of counts is scanned inside the scatter pass)
         const bool one_level = g.dim < 3 && g.l1seg == 1 && (int64_t)g.l1bins * g.SB * g.CG == 1 && L.ntiles == L.npencils;
-        const bool local_scan = one_level && items <= 16384;
+        // (local_scan: two LDS ints per bin + the static 128 bytes of the seal sum must stay within the 64 KB a launch gets
+        // without raising the kernel's limit -- not so for 8 177 .. 8 192 bins)
+        const bool local_scan = one_level && items <= 16384 && 2 * lds1 + 16 * 8 <= 65536;
         if (!local_scan)
             if (int rc = exclusive_scan(hist, hscan, items, base + L.off_scan, L.scan_bytes, stream)) return rc;
         hipLaunchKernelGGL(common ? sort1_scatter_kernel<true> : sort1_scatter_kernel<false>, dim3(nblocks), dim3(kSortThreads),
@@ -879,10 +1003,26 @@ int launch_plan_points(const Geom &g, const PlanLayout &L, const float *pos, con
         }
         int *hist2 = (int *)(base + L.off_hist2);
         const size_t lds2 = (size_t)g.l1bins * g.SB * g.CG * 4;
+        // second level: in one pass when every bin fits it (3-D: 16-byte records), else by eight parts per bin; the route
+        // is taken on the device (sort2_route_kernel), and the launches that do not have it return at once
+        const bool fuse = g.dim == 3 && (int64_t)g.l1bins * g.SB * g.CG <= kFuseMaxKeys;
+        int *const route = fuse ? cursor : nullptr;  // (the cursors serve the single-level sort only)
+        if (fuse) {
+            hipLaunchKernelGGL(sort2_route_kernel, dim3(1), dim3(1024), 0, stream, npencils, nblocks, hscan, route);
+            static DeviceOnce attr_done;
+            if (attr_done.first_use()) {
+                NFFT_HIP_CHECK(hipFuncSetAttribute((const void *)sort2_lds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kFuseLds));
+                NFFT_HIP_CHECK(hipFuncSetAttribute((const void *)sort2_lds_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kFuseLds));
+                attr_done.mark();
+            }
+            hipLaunchKernelGGL(common ? sort2_lds_kernel<true> : sort2_lds_kernel<false>, dim3(npencils), dim3(kFuseThreads),
+                               (size_t)kFuseChunk * 16 + lds2, stream, g, npencils, nblocks, route, hscan, tmp, offsets,
+                               (int *)(base + L.off_groups), (float4 *)spos);
+        }
         hipLaunchKernelGGL(common ? sort2_count_kernel<true> : sort2_count_kernel<false>, dim3(npencils, kSort2Parts), dim3(kSortThreads), lds2, stream, g, nblocks,
-                           hscan, tmp, hist2, key2);
+                           route, hscan, tmp, hist2, key2);
         hipLaunchKernelGGL(sort2_scatter_kernel, dim3(npencils, kSort2Parts), dim3(kSortThreads), 2 * lds2, stream, g,
-                           npencils, nblocks, hscan, tmp, hist2, key2, offsets, (int *)(base + L.off_groups), perm, spos);
+                           npencils, nblocks, route, hscan, tmp, hist2, key2, offsets, (int *)(base + L.off_groups), perm, spos);
         if (g.wide && launch_segment_split(g, L, n, B, offsets, (int4 *)(base + L.off_work), stream)) return 2;
         NFFT_HIP_CHECK(hipGetLastError());
         return 0;

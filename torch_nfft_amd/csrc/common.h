@@ -155,7 +155,8 @@ inline Geom make_geom(int dim, int64_t N, int64_t m, bool owned = false, bool pa
     g.bin0 = g.wide ? 1 : g.Ta[0];
     g.np0 = g.wide ? g.Ma[0] : g.nta[0];
     g.tiles_per_batch = g.np0 * g.nta[1] * g.nta[2];
-    // the wide tiling has few, long pencils: its second-level sort works on segments of 128 slabs
+    // the wide tiling has few, long pencils: its second-level sort works on segments of (at most) 128 slabs -- a plan picks
+    // shorter ones for dense inputs (plan_layout: PlanLayout::l1bins)
     g.l1bins = g.wide ? 128 : g.np0;
     g.l1seg = (g.np0 + g.l1bins - 1) / g.l1bins;
     // only the opt-in register-tile spreading kernel needs the sub-block order (it costs ~0.25 ms of sorting at C3)
@@ -424,6 +425,7 @@ struct PlanLayout {
     int64_t cap;  // entries the plan can hold: n, or 4 n for the owned tiling (an entry per touched tile)
     int64_t ntiles;
     int64_t npencils, nblocks, block_points;  // two-level sort geometry
+    int l1bins, l1seg;   // first-level segments of this plan (Geom::l1bins is the longest; plan_layout picks by points per bin)
     bool two_level;
     int64_t off_offsets, off_cursor, off_perm, off_spos, off_scan, scan_bytes;
     int64_t off_seal, off_sealpart;  // the plan's seal (checksum of pos / batch: kernels.h) and the count pass's partial sums
