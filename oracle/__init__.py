@@ -14,6 +14,11 @@ Contents
                  roll-off) -- restates ``csrc/cuda/spatial_window_operations.cu``,
                  ``csrc/cuda/spectral_window_operations.cu`` and the drivers in
                  ``csrc/cuda/core_cuda.cu:144-531``.
+``nfft_ref_torch.py``  the same restatement in torch, device-agnostic and memory-aware (one plane at a time, the
+                 band cut out / padded axis by axis): on the GPU it serves as the dense float64 oracle of the
+                 full-size tests (``tests/test_gpu_dense_oracle.py``); its float32 mode is the yardstick for what
+                 single precision costs on a problem.  Pinned against ``nfft_ref.py`` at 1e-12
+                 (``tests/test_ref_torch.py``).
 ``coeffs_ref.py`` float64 restatement of the kernel-coefficient recipes (csrc/cuda/kernel_coeffs.cu).
 ``ndft_c.c``     plain-C (OpenMP) exact NDFT used for the CPU baseline timing;
                  built into ``oracle/_build/libndft_oracle.so`` by ``oracle/Makefile``.
