@@ -35,7 +35,7 @@ extern "C" {
 #define NFFT_HIP_EHIP 4       /* HIP runtime error (reference aborts the process, cuda_utils.cu:7-14; we report) */
 #define NFFT_HIP_EKERNEL 5    /* a kernel of an earlier call on this device reported a fault (nfft_hip_check_status) */
 
-#define NFFT_HIP_ABI_VERSION 4
+#define NFFT_HIP_ABI_VERSION 5
 
 int nfft_hip_abi_version(void);
 const char *nfft_hip_last_error(void);
@@ -262,6 +262,30 @@ int nfft_hip_fastsum_backward_planned(const nfft_hip_problem *src, const void *s
                                       float *dsources, float *dtargets, void *workspace, int64_t workspace_bytes,
                                       void *stream);
 
+/* ---- Toeplitz normal operator A^H W A (no reference counterpart) ----
+ * With A = nfft_hip_forward on a fixed point set and W = diag(w) real weights,
+ *     (A^H W A)[k, k'] = sum_i w_i e^{2 pi i (k - k').pos_i} = t[k - k']
+ * is a dim-level Toeplitz matrix.  It embeds in a circulant of size M = 2N per axis, so one application is the forward
+ * FFT stage (band -> grid M^dim, no roll-off), a pointwise product with a real grid K and the adjoint FFT stage (grid ->
+ * band, no roll-off): no points, no plan, no spreading and no gather, at a cost independent of the number of points.
+ *
+ * Set-up, once per (points, weights):  t = nfft_hip_adjoint of the weights at bandwidth 2N (real x = w, one column),
+ * [B, (2N)^dim] complex64 with lag n at index n + N;  nfft_hip_toeplitz_kernel turns it into
+ *     K[b, j] = M^-dim sum_n t[b, n] e^{-2 pi i n.j / M},   j in [0, M)^dim,   float32 [B, M^dim]
+ * (lags with a component -N never occur in k - k' and are dropped; the Hermitian part of t is taken, so K is real).
+ * p is the bandwidth-N problem: dim, N and batch_size are read, m must be valid, num_points / num_columns are ignored. */
+int64_t nfft_hip_toeplitz_kernel_workspace_bytes(const nfft_hip_problem *p);
+int nfft_hip_toeplitz_kernel(const nfft_hip_problem *p, const void *t, float *K, void *workspace, int64_t workspace_bytes,
+                             void *stream);
+/* Application:  y = A^H W A xhat  for xhat [B, N^dim, C] float32 (x_is_complex = 0) or complex64;  y [B, N^dim, C] is
+ * always complex64, every element is written.  K must be 16-byte aligned.  p->num_points is ignored (0 is valid),
+ * p->num_columns = C; p->m is not used beyond validation.  The planes of the grid (two per column: re, im) run through
+ * the FFT stages of the transforms in chunks (NFFT_HIP_CHUNK_BYTES); chunked and unchunked results are bitwise equal,
+ * and so are repeated calls (no atomics anywhere). */
+int64_t nfft_hip_toeplitz_workspace_bytes(const nfft_hip_problem *p);
+int nfft_hip_toeplitz_apply(const nfft_hip_problem *p, const float *K, const void *xhat, int x_is_complex, void *y,
+                            void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.
  *   gaussian_analytic_coeffs      float32:  prod_d sqrt(pi) sigma exp(-sigma^2 pi^2 l_d^2)      (kernel_coeffs.cu:6-30)
@@ -281,12 +305,13 @@ int nfft_hip_interpolated_kernel_coeffs(const void *grid_values, int values_are_
  * When enabled, nfft_hip_adjoint / nfft_hip_forward bracket each stage with HIP events recorded on the
  * caller's stream.  nfft_hip_profile_collect waits for the recorded events and returns, per stage, the
  * summed GPU time in milliseconds and the number of launches since the last collect.  Stage order:
- * 0 point plan (binning), 1 coefficient gather, 2 grid zero-fill, 3 spreading, 4 FFT, 5 roll-off, 6 interpolation.
+ * 0 point plan (binning), 1 coefficient gather, 2 grid zero-fill, 3 spreading, 4 FFT, 5 roll-off, 6 interpolation,
+ * 7 product with the kernel grid (nfft_hip_toeplitz_apply only).
  * The reference has no counterpart (it has no timers at all).
  * Two event records per stage cost 3-6 us of stream time each: ~70 us per adjoint + forward pair, which is 1-2 % of a
  * 10^7-point step but more than half of a 10^3-point one.  nfft_hip_profile_stages restricts the timers to the stages
  * whose bit is set (bit s = stage s; default: all), e.g. 1u << 3 times the spreading kernel alone. */
-#define NFFT_HIP_NUM_STAGES 7
+#define NFFT_HIP_NUM_STAGES 8
 void nfft_hip_profile_enable(int enable);
 void nfft_hip_profile_stages(unsigned stage_mask);
 int nfft_hip_profile_collect(double *ms_per_stage, int64_t *launches_per_stage, int num_stages);

@@ -12,6 +12,7 @@ _lib.load_core()
 from . import ops  # noqa: E402
 from .nfft import (nfft_adjoint, nfft_forward, nfft_fastsum, NfftAdjointFunction, NfftForwardFunction,  # noqa: E402
                    NfftFastsumFunction)
+from .toeplitz import nfft_toeplitz_kernel, nfft_normal, nfft_inverse, NfftNormalFunction  # noqa: E402
 from .ndft import ndft_forward, ndft_adjoint, ndft_fastsum, exact_trigonometric_matrix, exact_gaussian_matrix  # noqa: E402
 from .coeffs import (gaussian_analytic_coeffs, gaussian_interpolated_coeffs, interpolation_grid,  # noqa: E402
                      radial_interpolation_grid, interpolated_kernel_coeffs)
@@ -20,7 +21,8 @@ from .kernel import GaussianKernel  # noqa: E402
 from . import utils  # noqa: E402
 
 
-__all__ = ["nfft_adjoint", "nfft_forward", "nfft_fastsum", "ndft_forward", "ndft_adjoint", "ndft_fastsum",
+__all__ = ["nfft_adjoint", "nfft_forward", "nfft_fastsum", "nfft_toeplitz_kernel", "nfft_normal", "nfft_inverse",
+           "NfftNormalFunction", "ndft_forward", "ndft_adjoint", "ndft_fastsum",
            "exact_trigonometric_matrix", "exact_gaussian_matrix", "NfftAdjointFunction", "NfftForwardFunction",
            "NfftFastsumFunction", "gaussian_analytic_coeffs", "gaussian_interpolated_coeffs", "interpolation_grid",
            "radial_interpolation_grid", "interpolated_kernel_coeffs", "GramMatrix", "AdjacencyMatrix",

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NFFT_HIP_LIB") or os.path.join(_HERE, "libnfft_hip.so")
 CORE_PATH = os.path.join(_HERE, "core.so")
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 POINTS_IN_QUARTER_BALL = 1
 
 # every symbol include/nfft_hip.h declares
@@ -45,6 +45,10 @@ SYMBOLS = (
     "nfft_hip_fastsum_band_planned",
     "nfft_hip_fastsum_grad_workspace_bytes",
     "nfft_hip_fastsum_backward_planned",
+    "nfft_hip_toeplitz_kernel_workspace_bytes",
+    "nfft_hip_toeplitz_kernel",
+    "nfft_hip_toeplitz_workspace_bytes",
+    "nfft_hip_toeplitz_apply",
     "nfft_hip_gaussian_analytic_coeffs",
     "nfft_hip_interpolation_grid",
     "nfft_hip_coeffs_workspace_bytes",
@@ -55,7 +59,7 @@ SYMBOLS = (
     "nfft_hip_profile_stages",
     "nfft_hip_profile_collect",
 )
-STAGES = ("plan", "gather", "zero", "spread", "fft", "rolloff", "interp")
+STAGES = ("plan", "gather", "zero", "spread", "fft", "rolloff", "interp", "multiply")
 
 OK, EINVAL, EWORKSPACE, EFFT, EHIP, EKERNEL = 0, 1, 2, 3, 4, 5
 
@@ -151,6 +155,13 @@ def load():
     lib.nfft_hip_fastsum_grad_workspace_bytes.restype = i64
     lib.nfft_hip_fastsum_backward_planned.argtypes = [P, vp, P, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, i64, vp]
     lib.nfft_hip_fastsum_backward_planned.restype = ci
+    for f in (lib.nfft_hip_toeplitz_kernel_workspace_bytes, lib.nfft_hip_toeplitz_workspace_bytes):
+        f.argtypes = [P]
+        f.restype = i64
+    lib.nfft_hip_toeplitz_kernel.argtypes = [P, vp, vp, vp, i64, vp]
+    lib.nfft_hip_toeplitz_kernel.restype = ci
+    lib.nfft_hip_toeplitz_apply.argtypes = [P, vp, vp, ci, vp, vp, i64, vp]
+    lib.nfft_hip_toeplitz_apply.restype = ci
     lib.nfft_hip_gaussian_analytic_coeffs.argtypes = [ctypes.c_double, i64, ctypes.c_int32, vp, vp]
     lib.nfft_hip_gaussian_analytic_coeffs.restype = ci
     lib.nfft_hip_interpolation_grid.argtypes = [i64, ctypes.c_int32, ci, vp, vp]

@@ -156,7 +156,8 @@ static int take_pending_fault()
 
 // ---- environment switches ------------------------------------------------------------------------------------------
 // Every NFFT_HIP_* variable the library reads (INTEGRATION.md lists them).  All but two are read together, once per
-// process; NFFT_HIP_CHUNK_BYTES and NFFT_HIP_NO_COLFFT are read on every call (tests change them between calls).
+// process; NFFT_HIP_CHUNK_BYTES, NFFT_HIP_NO_COLFFT and NFFT_HIP_TOEPLITZ_FUSED are read on every call (tests change
+// them between calls).
 namespace {
 const char *env(const char *name)
 {
@@ -204,6 +205,7 @@ int64_t chunk_budget_bytes()
     return v > 0 ? (int64_t)v : int64_t(16) << 30;
 }
 bool colfft_enabled() { return env("NFFT_HIP_NO_COLFFT")[0] != '1'; }
+bool toeplitz_fused_enabled() { return env("NFFT_HIP_TOEPLITZ_FUSED")[0] != '0'; }
 } // namespace
 
 SpreadMode spread_mode() { return switches().spread; }
@@ -281,6 +283,7 @@ struct Route {
     // FFT stage (make_route only)
     FftRoute fft;           // kFftFull, kFftRocRows or kFftOwnPlanar; chunk_fft() says when a chunk goes column-innermost
     bool ci;                // several columns on a grid the column-innermost passes take
+    bool toeplitz_fused;    // normal operator: both row passes and the product with K in one kernel (toeplitz_fused_chunk)
     int64_t C, ppc, total_planes, chunk_planes, half_cells;
     int64_t off_plan, off_xs, off_xmax, off_grid, off_spec, off_col, off_work, off_tickets, work_bytes, total;
 
@@ -345,11 +348,24 @@ bool hvp_fused_dxhat(const Route &ra)
     return spread_deriv_supported(ra.g) && env("NFFT_HIP_DXHAT")[0] != 'c';
 }
 
-// The whole route of an adjoint (x: ppc real planes per column) or forward transform (y: ppc real planes per column),
-// the chunk size and the workspace carve included.
-int make_route(const nfft_hip_problem *p, int ppc, bool adjoint, Route &r)
+// The whole route of an adjoint (x: ppc real planes per column), a forward transform (y: ppc real planes per column) or
+// an application of the Toeplitz normal operator (the forward FFT stage, the product with the
+// kernel grid and the adjoint FFT stage on the same chunk of planes -- no points, no plan, and no roll-off in either
+// stage), the chunk size and the workspace carve included.
+enum RouteKind { kRouteForward, kRouteAdjoint, kRouteToeplitz };
+int make_route(const nfft_hip_problem *p, int ppc, RouteKind kind, Route &r)
 {
-    r = plan_route(p, p->num_columns * ppc);
+    const bool adjoint = kind == kRouteAdjoint, toeplitz = kind == kRouteToeplitz;
+    if (toeplitz) {
+        // FFT stages only: the grid of the problem, whatever tiling its points would get
+        r = Route{};
+        r.g = make_geom(p->dim, p->N, p->m);
+        r.g.rolloff = 0;
+        r.B = p->batch_size;
+        r.Cr = p->num_columns * ppc;
+    } else {
+        r = plan_route(p, p->num_columns * ppc);
+    }
     r.C = p->num_columns;
     r.ppc = ppc;
     r.total_planes = r.B * r.Cr;
@@ -358,6 +374,9 @@ int make_route(const nfft_hip_problem *p, int ppc, bool adjoint, Route &r)
     const bool colfft = colfft_supported(r.g) && colfft_enabled();
     r.fft = !colfft ? kFftFull : rowfft_supported(r.g) ? kFftOwnPlanar : kFftRocRows;
     r.ci = r.C > 1 && colfft_ci_supported(r.g);
+    // the normal operator on the planar route with its own row passes: the rows stay in LDS between the two transforms
+    // (NFFT_HIP_TOEPLITZ_FUSED=0: the three kernels of the general route, which every other FFT route takes)
+    r.toeplitz_fused = toeplitz && r.fft == kFftOwnPlanar && r.C < 2 && toeplitz_fused_enabled();
     // (the work area is sized for the rocFFT row transforms wherever the column passes run)
     const FftKind fkind = colfft ? (adjoint ? kR2CRows : kC2RRows) : (adjoint ? kR2C : kC2R);
     const int64_t plane_bytes = r.g.cells * 4 + r.half_cells * 8 + (colfft ? colfft_scratch_bytes(r.g, 1) : 0);
@@ -370,15 +389,17 @@ int make_route(const nfft_hip_problem *p, int ppc, bool adjoint, Route &r)
     r.chunk_planes = chunk;
     r.work_bytes = 0;
     if (r.total_planes > 0) {
-        // plans for the full chunk and for the remainder chunk
-        int64_t w = fft_work_bytes(fkind, r.g.dim, r.g.M, chunk);
-        if (w < 0) return NFFT_HIP_EFFT;
-        r.work_bytes = w;
+        // plans for the full chunk and for the remainder chunk (the normal operator runs both directions)
+        const FftKind kinds[2] = {fkind, colfft ? kR2CRows : kR2C};
         const int64_t rem = r.total_planes % chunk;
-        if (rem) {
-            w = fft_work_bytes(fkind, r.g.dim, r.g.M, rem);
-            if (w < 0) return NFFT_HIP_EFFT;
-            if (w > r.work_bytes) r.work_bytes = w;
+        for (int i = 0; i < (toeplitz ? 2 : 1); ++i) {
+            const FftKind k = kinds[i];
+            for (const int64_t planes : {chunk, rem}) {
+                if (!planes) continue;
+                const int64_t w = fft_work_bytes(k, r.g.dim, r.g.M, planes);
+                if (w < 0) return NFFT_HIP_EFFT;
+                if (w > r.work_bytes) r.work_bytes = w;
+            }
         }
     }
     const bool need_xs = adjoint;
@@ -386,7 +407,8 @@ int make_route(const nfft_hip_problem *p, int ppc, bool adjoint, Route &r)
     r.off_plan = o; o = align_up(o + r.plan_bytes, 256);
     r.off_xs = o;   o = align_up(o + (need_xs ? (align_up(r.spread_layout().cap * r.Cr, 64) + 64) * 4 : 0), 256);
     r.off_xmax = o; o = align_up(o + (need_xs ? r.total_planes * 4 : 0), 256);
-    r.off_grid = o; o = align_up(o + chunk * r.g.cells * 4, 256);
+    // (the fused normal operator keeps its grid rows in LDS)
+    r.off_grid = o; o = align_up(o + (r.toeplitz_fused ? 0 : chunk * r.g.cells * 4), 256);
     r.off_spec = o; o = align_up(o + chunk * r.half_cells * 8, 256);
     // (several columns: the column-innermost passes work on whole groups of 16 planes)
     r.off_col = o;  o = align_up(o + (colfft ? colfft_scratch_bytes(r.g, r.C > 1 ? colfft_ci_planes(chunk) : chunk) : 0), 256);
@@ -523,6 +545,24 @@ int fft_forward_chunk(const Route &r, char *ws, const void *xhat, int x_is_compl
     return fft_execute(kC2RRows, g.dim, g.M, np, spec, grid, ws + r.off_work, r.work_bytes, s);
 }
 
+// The normal operator's planes [p0, p0 + np) on the fused route (Route::toeplitz_fused; one column: np is even):
+// xhat -> column passes -> spec -> row passes around the product with K, in place -> column passes -> y
+int toeplitz_fused_chunk(const Route &r, char *ws, const void *xhat, int x_is_complex, const float *K, int64_t p0, int64_t np,
+                         float2 *spec, void *y, hipStream_t s)
+{
+    void *col = ws + r.off_col;
+    {
+        StageTimer t(kStageDeconv, s);
+        if (int rc = launch_colfft_forward(r.g, xhat, col, r.chunk_planes, r.C, x_is_complex, 0, p0, np, spec, true, s)) return rc;
+    }
+    {
+        StageTimer t(kStageFft, s);
+        if (int rc = launch_row_toeplitz(r.g, spec, K, r.Cr / 2, p0 / 2, np / 2, s)) return rc;
+    }
+    StageTimer t(kStageDeconv, s);
+    return launch_colfft_adjoint(r.g, spec, true, col, r.chunk_planes, r.C, 1, 0, p0, np, y, nullptr, 0, s);
+}
+
 int validate(const nfft_hip_problem *p)
 {
     if (!p) { set_error("Input mismatch: null problem"); return NFFT_HIP_EINVAL; }
@@ -594,7 +634,7 @@ int64_t nfft_hip_adjoint_workspace_bytes(const nfft_hip_problem *p, int x_is_com
     (void)real_output;
     if (validate(p)) return -1;
     Route r;
-    if (make_route(p, x_is_complex ? 2 : 1, true, r)) return -1;
+    if (make_route(p, x_is_complex ? 2 : 1, kRouteAdjoint, r)) return -1;
     return r.total;
 }
 
@@ -603,7 +643,7 @@ int64_t nfft_hip_forward_workspace_bytes(const nfft_hip_problem *p, int x_is_com
     (void)x_is_complex;
     if (validate(p)) return -1;
     Route r;
-    if (make_route(p, real_output ? 1 : 2, false, r)) return -1;
+    if (make_route(p, real_output ? 1 : 2, kRouteForward, r)) return -1;
     return r.total;
 }
 
@@ -689,7 +729,7 @@ static int adjoint_impl(const nfft_hip_problem *p, const float *pos, const int64
         return launch_small_grid_adjoint(p, pos, batch, x, x_is_complex, real_output, y, mult, mult_kind, s);
     }
     Route r;
-    if (int rc = make_route(p, x_is_complex ? 2 : 1, true, r)) return rc;
+    if (int rc = make_route(p, x_is_complex ? 2 : 1, kRouteAdjoint, r)) return rc;
     if (r.total_planes == 0) return 0;
     if (!y) { set_error("Input mismatch: y is null"); return NFFT_HIP_EINVAL; }
     if (r.n > 0 && ((!pos && !ext_plan) || !x)) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
@@ -740,7 +780,7 @@ static int forward_impl(const nfft_hip_problem *p, const float *pos, const int64
         return launch_small_grid_forward(p, pos, batch, xhat, x_is_complex, real_output, y, s);
     }
     Route r;
-    if (int rc = make_route(p, real_output ? 1 : 2, false, r)) return rc;
+    if (int rc = make_route(p, real_output ? 1 : 2, kRouteForward, r)) return rc;
     if (r.total_planes == 0 || r.n == 0) return 0;
     if (!y || (!pos && !ext_plan) || !xhat) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
     if (!workspace || workspace_bytes < r.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
@@ -805,7 +845,7 @@ namespace {
 // planes per point set, the per-plane partial gradients [Cr, n, dim] that grad_reduce sums in plane order.
 int forward_grad_route(const nfft_hip_problem *p, int real_output, Route &r, int64_t &off_part, int64_t &total)
 {
-    if (int rc = make_route(p, real_output ? 1 : 2, false, r)) return rc;
+    if (int rc = make_route(p, real_output ? 1 : 2, kRouteForward, r)) return rc;
     off_part = r.total - 256;  // (make_route's total is its aligned end + 256 bytes of slack for the base alignment)
     const int64_t part = r.Cr > 1 ? align_up(r.Cr * r.n * p->dim * 4, 256) : 0;
     total = off_part + part + 256;
@@ -899,7 +939,7 @@ int hvp_carve(const nfft_hip_problem *p, int real_output, HvpCarve &h)
     int64_t off_part = 0;
     if (int rc = forward_grad_route(p, real_output, r, off_part, h.grad_total)) return rc;
     Route ra;
-    if (int rc = make_route(p, real_output ? 1 : 2, true, ra)) return rc;
+    if (int rc = make_route(p, real_output ? 1 : 2, kRouteAdjoint, ra)) return rc;
     h.adj_total = ra.total;
     int64_t spec = p->batch_size * p->num_columns;
     for (int a = 0; a < p->dim; ++a) spec *= p->N;
@@ -966,7 +1006,7 @@ int nfft_hip_forward_grad_points_backward_planned(const nfft_hip_problem *p, con
     }
     if (dxhat) {
         Route ra;
-        if (int rc = make_route(p, real_output ? 1 : 2, true, ra)) return rc;
+        if (int rc = make_route(p, real_output ? 1 : 2, kRouteAdjoint, ra)) return rc;
         if (hvp_fused_dxhat(ra)) {
             // the derivative spreading of w, then the adjoint's own FFT stage and roll-off, chunk by chunk
             float *grid = (float *)(ws + ra.off_grid);
@@ -1023,8 +1063,8 @@ int fastsum_check(const nfft_hip_problem *src, const nfft_hip_problem *tgt)
 int fastsum_carve(const nfft_hip_problem *src, const nfft_hip_problem *tgt, int x_is_complex, bool own_plans,
                   bool shared_points, FastsumCarve &f)
 {
-    if (int rc = make_route(src, x_is_complex ? 2 : 1, true, f.src)) return rc;
-    if (int rc = make_route(tgt, x_is_complex ? 2 : 1, false, f.tgt)) return rc;
+    if (int rc = make_route(src, x_is_complex ? 2 : 1, kRouteAdjoint, f.src)) return rc;
+    if (int rc = make_route(tgt, x_is_complex ? 2 : 1, kRouteForward, f.tgt)) return rc;
     f.band_size = band_size_of(src);
     f.band_bytes = align_up(f.band_size, 256);
     f.plan_s = own_plans ? align_up(f.src.plan_bytes, 256) : 0;
@@ -1170,7 +1210,7 @@ struct FastsumGradCarve {
 int fastsum_grad_carve(const nfft_hip_problem *src, const nfft_hip_problem *tgt, int x_is_complex, FastsumGradCarve &f)
 {
     Route adj;
-    if (int rc = make_route(tgt, x_is_complex ? 2 : 1, true, adj)) return rc;
+    if (int rc = make_route(tgt, x_is_complex ? 2 : 1, kRouteAdjoint, adj)) return rc;
     f.inner = adj.total;
     for (const nfft_hip_problem *p : {src, tgt}) {
         Route r;
@@ -1266,6 +1306,97 @@ int nfft_hip_fastsum_backward_planned(const nfft_hip_problem *src_in, const void
         // y = forward_t(band): the gradient gather of the saved band at the targets, weighted by dy
         if (int rc = forward_grad_impl(tgt, target_plan, band, 1, real_output, (const float *)dy, nullptr, dtargets, inner,
                                        f.inner, s)) return rc;
+    }
+    return 0;
+}
+
+} // extern "C"
+
+// ---- Toeplitz normal operator A^H W A ------------------------------------------------------------
+namespace {
+// Workspace of the kernel-grid set-up: the half spectrum of K for all point sets + rocFFT's work area.
+struct ToeplitzKernelCarve {
+    Geom g;
+    int64_t half_cells, off_spec, off_work, work_bytes, total;
+};
+int toeplitz_kernel_carve(const nfft_hip_problem *p, ToeplitzKernelCarve &c)
+{
+    c.g = make_geom(p->dim, p->N, p->m);
+    c.half_cells = c.g.M / 2 + 1;
+    for (int a = 0; a < 2; ++a) c.half_cells *= c.g.Ma[a];
+    c.work_bytes = fft_work_bytes(kC2R, c.g.dim, c.g.M, p->batch_size);
+    if (c.work_bytes < 0) return NFFT_HIP_EFFT;
+    c.off_spec = 0;
+    c.off_work = align_up(p->batch_size * c.half_cells * 8, 256);
+    c.total = c.off_work + align_up(c.work_bytes, 256) + 256;
+    return 0;
+}
+bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; }
+} // namespace
+
+extern "C" {
+
+int64_t nfft_hip_toeplitz_kernel_workspace_bytes(const nfft_hip_problem *p)
+{
+    if (validate(p)) return -1;
+    ToeplitzKernelCarve c;
+    if (toeplitz_kernel_carve(p, c)) return -1;
+    return c.total;
+}
+
+int nfft_hip_toeplitz_kernel(const nfft_hip_problem *p, const void *t, float *K, void *workspace, int64_t workspace_bytes,
+                             void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate(p)) return rc;
+    if (!t || !K) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    ToeplitzKernelCarve c;
+    if (int rc = toeplitz_kernel_carve(p, c)) return rc;
+    if (!workspace || workspace_bytes < c.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    hipStream_t s = (hipStream_t)stream;
+    float2 *spec = (float2 *)(ws + c.off_spec);
+    if (int rc = launch_toeplitz_spectrum(c.g, (const float2 *)t, p->batch_size, spec, s)) return rc;
+    StageTimer tm(kStageFft, s);
+    return fft_execute(kC2R, c.g.dim, c.g.M, p->batch_size, spec, K, ws + c.off_work, c.work_bytes, s);
+}
+
+int64_t nfft_hip_toeplitz_workspace_bytes(const nfft_hip_problem *p)
+{
+    if (validate(p)) return -1;
+    Route r;
+    if (make_route(p, 2, kRouteToeplitz, r)) return -1;
+    return r.total;
+}
+
+int nfft_hip_toeplitz_apply(const nfft_hip_problem *p, const float *K, const void *xhat, int x_is_complex, void *y,
+                            void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate(p)) return rc;
+    if (p->num_columns == 0) return 0;
+    if (!K || !xhat || !y) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    if (!aligned16(K)) { set_error("Input mismatch: the kernel grid must be 16-byte aligned"); return NFFT_HIP_EINVAL; }
+    // the grid of x is complex whether x is or not: two real planes per column through both FFT stages
+    Route r;
+    if (int rc = make_route(p, 2, kRouteToeplitz, r)) return rc;
+    if (!workspace || workspace_bytes < r.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    hipStream_t s = (hipStream_t)stream;
+    float *grid = (float *)(ws + r.off_grid);
+    float2 *spec = (float2 *)(ws + r.off_spec);
+    for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes) {
+        const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
+        if (r.toeplitz_fused) {
+            if (int rc = toeplitz_fused_chunk(r, ws, xhat, x_is_complex, K, p0, np, spec, y, s)) return rc;
+            continue;
+        }
+        if (int rc = fft_forward_chunk(r, ws, xhat, x_is_complex, 0, p0, np, grid, spec, s)) return rc;
+        {
+            StageTimer t(kStageMultiply, s);
+            if (int rc = launch_toeplitz_multiply(r.g, grid, K, r.Cr, p0, np, s)) return rc;
+        }
+        if (int rc = fft_adjoint_chunk(r, ws, grid, spec, 1, 0, p0, np, y, nullptr, 0, s)) return rc;
     }
     return 0;
 }

@@ -782,6 +782,99 @@ row_c2r_kernel(int KC, int KS, int64_t nrows, const float2 *__restrict__ tw, con
     }
 }
 
+// The two row passes of the Toeplitz normal operator around its product with the kernel grid, in one
+// kernel: half-spectrum rows -> C2R in LDS -> times the rows of K -> R2C in LDS -> half-spectrum rows, in place.  The grid
+// itself never reaches HBM: per row 2 * 8 (N/2 + 1) bytes of spectrum and the row of K instead of the C2R pass's write,
+// the multiply's read and write and the R2C pass's read.  A wave takes the same RP consecutive rows of the TWO planes
+// (re, im) of a column, so the rows of K are loaded once for both and stay in registers.  spec: planes 2 pair, 2 pair + 1
+// of the chunk for pair < npairs; K row block of global pair pair0 + pair: point set (pair0 + pair) / pairs_per_set.
+template <int LOGL>
+__global__ void __launch_bounds__(kRowWaves * 64)
+row_toeplitz_kernel(int KC, int KS, int64_t rows_per_plane, int64_t npairs, int64_t pair0, int64_t pairs_per_set,
+                    const float2 *__restrict__ tw, const float *__restrict__ K, float2 *spec)
+{
+    constexpr int L = 1 << LOGL, M = 2 * L, RP = kWaveCplx / L, NIT = kWaveCplx / 64, NQ = kWaveCplx / 128;
+    __shared__ RowLds<LOGL> S;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float2 *z = S.z[wave];
+    row_tables<LOGL>(S, tw, tid);
+    // (no workgroup barrier below this point: a wave without work may leave)
+    const int64_t units_per_pair = rows_per_plane / RP;  // (M >= 128 rows per plane, RP <= 8)
+    const int64_t unit = (int64_t)blockIdx.x * kRowWaves + wave;
+    if (unit >= npairs * units_per_pair) return;
+    const int64_t pair = unit / units_per_pair, rb = unit - pair * units_per_pair;
+    const int64_t row_re = 2 * pair * rows_per_plane + rb * RP;
+    const int64_t set = (pair0 + pair) / pairs_per_set;
+    // everything the wave reads is requested before the first transform: RP rows of K, RP half rows of either plane
+    const float4 *k4 = (const float4 *)(K + (set * rows_per_plane + rb * RP) * M);
+    float4 kv[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) kv[q] = k4[q * 64 + lane];
+    float2 va[2][NIT];
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) {
+        const float2 *src = spec + (row_re + pl * rows_per_plane) * KS;
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int n = it * 64 + lane;
+            const int rr = n >> LOGL, k = n & (L - 1);
+            const int kk = k <= L / 2 ? k : L - k;  // (one load per element, as in row_c2r_kernel)
+            va[pl][it] = src[rr * KS + kk];
+        }
+    }
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) {
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            // Z[k] = (X[k] + conj X[L-k]) + i conj(W_M^k) (X[k] - conj X[L-k]),  X = 0 beyond the band
+            const int n = it * 64 + lane;
+            const int k = n & (L - 1);
+            const float2 v = va[pl][it], zero = make_float2(0.f, 0.f);
+            const float2 a = k <= L / 2 ? v : zero;
+            float2 b = k >= L / 2 ? v : zero;
+            b.y = -b.y;
+            const float2 sum = make_float2(a.x + b.x, a.y + b.y), dif = make_float2(a.x - b.x, a.y - b.y);
+            float2 w = S.tw[k];
+            w.y = -w.y;
+            const float2 wd = cmul(w, dif);
+            z[zsw(n)] = make_float2(sum.x - wd.y, sum.y + wd.x);  // sum + i w dif
+        }
+        wave_fft<true, LOGL>(z, S.tw, lane);
+        // the real rows (x[2n] = Re z[n], x[2n+1] = Im z[n], at their digit-reversed places) times K, back in natural order
+        float4 v4[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int n2 = q * 64 + lane;
+            const int na = 2 * n2, nb = 2 * n2 + 1;
+            const int rr = na >> LOGL;
+            const float2 a = z[zsw(rr * L + S.rev[na & (L - 1)])], b = z[zsw(rr * L + S.rev[nb & (L - 1)])];
+            v4[q] = make_float4(a.x * kv[q].x, a.y * kv[q].y, b.x * kv[q].z, b.y * kv[q].w);
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int n2 = q * 64 + lane;
+            z[zsw(2 * n2)] = make_float2(v4[q].x, v4[q].y);
+            z[zsw(2 * n2 + 1)] = make_float2(v4[q].z, v4[q].w);
+        }
+        wave_fft<false, LOGL>(z, S.tw, lane);
+        for (int rr = 0; rr < RP; ++rr) {
+            float2 *dst = spec + (row_re + pl * rows_per_plane + rr) * KS;
+            for (int k = lane; k < KC; k += 64) {
+                const float2 a = z[zsw(rr * L + S.rev[k])];
+                float2 b = z[zsw(rr * L + S.rev[(L - k) & (L - 1)])];
+                b.y = -b.y;  // conj Z[L - k]
+                const float2 e = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y + b.y));
+                const float2 o = make_float2(0.5f * (a.x - b.x), 0.5f * (a.y - b.y));
+                const float2 wo = cmul(S.tw[k], o);
+                dst[k] = make_float2(e.x + wo.y, e.y - wo.x);  // e - i w o
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // =====================================================================================================================
 // Column-innermost pipeline for several coefficient columns (C > 1).
 //
@@ -1186,7 +1279,8 @@ ColGeom make_col_geom(const Geom &g, bool two_buffers, bool compact, int64_t pla
     cg.NC = nc;
     cg.logNC = 0;
     while ((1 << cg.logNC) < nc) ++cg.logNC;
-    cg.param = 1.047197551196597746f * (float)g.m / ((float)g.N * (float)g.N);
+    // (no roll-off: exponent scale 0, and expf(0) is exactly 1)
+    cg.param = g.rolloff ? 1.047197551196597746f * (float)g.m / ((float)g.N * (float)g.N) : 0.0f;
     cg.TG = nc >= 16 ? 1 : 16 / nc;
     return cg;
 }
@@ -1495,6 +1589,34 @@ int launch_row_c2r(const Geom &g, const float2 *spec, void *scratch, int64_t scr
     const float2 *tw = twiddle_table(g.M);
     if (!tw) { set_error("no twiddle table for this grid size"); return 4; }
     return launch_rows(true, g, nplanes, tw, spec, grid, stream);
+}
+
+template <int LOGL>
+static void launch_row_toeplitz_t(const Geom &g, const float2 *tw, float2 *spec, const float *K, int64_t pairs_per_set,
+                                  int64_t pair0, int64_t npairs, hipStream_t stream)
+{
+    const int64_t rows_per_plane = (int64_t)g.Ma[0] * g.Ma[1];
+    const int64_t units = npairs * (rows_per_plane / (kWaveCplx >> LOGL));
+    const dim3 blocks((unsigned)((units + kRowWaves - 1) / kRowWaves));
+    hipLaunchKernelGGL((row_toeplitz_kernel<LOGL>), blocks, dim3(kRowWaves * 64), 0, stream, g.N / 2 + 1, compact_stride(g),
+                       rows_per_plane, npairs, pair0, pairs_per_set, tw, K, spec);
+}
+
+int launch_row_toeplitz(const Geom &g, float2 *spec, const float *K, int64_t pairs_per_set, int64_t pair0, int64_t npairs,
+                        hipStream_t stream)
+{
+    if (npairs <= 0) return 0;
+    const float2 *tw = twiddle_table(g.M);
+    if (!tw) { set_error("no twiddle table for this grid size"); return 4; }
+    switch (g.M) {
+    case 128: launch_row_toeplitz_t<6>(g, tw, spec, K, pairs_per_set, pair0, npairs, stream); break;
+    case 256: launch_row_toeplitz_t<7>(g, tw, spec, K, pairs_per_set, pair0, npairs, stream); break;
+    case 512: launch_row_toeplitz_t<8>(g, tw, spec, K, pairs_per_set, pair0, npairs, stream); break;
+    case 1024: launch_row_toeplitz_t<9>(g, tw, spec, K, pairs_per_set, pair0, npairs, stream); break;
+    default: set_error("row passes support M = 128 .. 1024"); return 1;
+    }
+    NFFT_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 // planar [ncols][N^d] <-> interleaved [B, N^d, C] for the columns col0 .. col0 + ncols (global column = b * C + c)

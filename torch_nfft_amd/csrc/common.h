@@ -112,6 +112,9 @@ struct Geom {
     // in the caller's arrays (int bits)} -- one aligned 16-byte access per point for every consumer, one scattered store
     // per point for the sort, no separate permutation array; 1-D / 2-D keep dim floats + the permutation array
     int pstride;
+    // 0: the FFT stages leave the roll-off out (every factor phi_hat_inv is 1) -- the Toeplitz normal operator, whose
+    // window error lives in its kernel grid (api.hip make_route); 1 for every transform
+    int rolloff;
     int64_t cells; // M^dim
 };
 
@@ -130,6 +133,7 @@ inline Geom make_geom(int dim, int64_t N, int64_t m, bool owned = false, bool pa
     g.M = (int)(2 * N);
     g.m = (int)m;
     g.W = (int)(2 * m + 2);
+    g.rolloff = 1;
     g.cells = 1;
     for (int a = 0; a < 3; ++a) {
         const bool live = a >= 3 - dim;

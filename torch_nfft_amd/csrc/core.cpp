@@ -664,6 +664,75 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> nfft_fastsum_backward(
     return {dx, ds, dt};
 }
 
+// ---- Toeplitz normal operator A^H W A (not in the reference; include/nfft_hip.h) ---------------
+// The bandwidth-N problem of a kernel grid [B, M, ..., M] (M = 2N); the cutoff only has to be valid.
+nfft_hip_problem toeplitz_problem(int64_t dim, int64_t B, int64_t N, int64_t C)
+{
+    nfft_hip_problem q;
+    q.dim = (int32_t)dim;
+    q.flags = 0;
+    q.num_points = 0;
+    q.num_columns = C;
+    q.batch_size = B;
+    q.N = N;
+    q.m = 1;
+    return q;
+}
+
+// t = nfft_adjoint(weights, pos, batch, bandwidth 2N) [B, 2N, ..., 2N] complex64 -> the real kernel grid K [B, M, ..., M]
+at::Tensor nfft_toeplitz_kernel(at::Tensor t)
+{
+    TORCH_CHECK(t.is_cuda(), "torch_nfft._nfft_toeplitz_kernel is currently only implemented for GPU tensors");
+    CHECK_INPUT(t.scalar_type() == at::kComplexFloat);
+    const int64_t dim = t.dim() - 1;
+    CHECK_INPUT(dim >= 1 && dim <= 3);
+    const int64_t B = t.size(0), M = t.size(1);
+    CHECK_INPUT(B >= 1 && M >= 4 && M % 4 == 0);  // M = 2N, N even
+    for (int64_t d = 2; d <= dim; ++d) CHECK_INPUT(t.size(d) == M);
+    const at::Tensor tc = t.contiguous();
+    at::Tensor K = at::empty(t.sizes(), t.options().dtype(at::kFloat));
+    const nfft_hip_problem q = toeplitz_problem(dim, B, M / 2, 1);
+    c10::DeviceGuard guard(t.device());
+    const int64_t ws_bytes = nfft_hip_toeplitz_kernel_workspace_bytes(&q);
+    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
+    at::Tensor ws = byte_buffer(ws_bytes, t);
+    check_rc(nfft_hip_toeplitz_kernel(&q, tc.data_ptr(), K.data_ptr<float>(), ws.data_ptr(), ws_bytes, stream_of(t)));
+    return K;
+}
+
+// y = A^H W A x for x [B, N, ..., N, *cols] float32 or complex64 and the kernel grid of the same points; complex64
+at::Tensor nfft_normal(at::Tensor kernel, at::Tensor x)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_normal is currently only implemented for GPU tensors");
+    TORCH_CHECK(kernel.is_cuda(), "kernel must be CUDA tensor");
+    CHECK_INPUT(kernel.scalar_type() == at::kFloat);
+    const bool real_input = real_dtype(x);
+    const int64_t dim = kernel.dim() - 1;
+    CHECK_INPUT(dim >= 1 && dim <= 3);
+    CHECK_INPUT(x.dim() >= dim + 1);
+    CHECK_INPUT(x.device() == kernel.device());
+    const int64_t B = kernel.size(0), M = kernel.size(1);
+    CHECK_INPUT(x.size(0) == B);
+    const int64_t N = x.size(1);
+    CHECK_INPUT(N >= 2 && M == 2 * N);
+    for (int64_t d = 2; d <= dim; ++d) CHECK_INPUT(x.size(d) == N && kernel.size(d) == M);
+    int64_t C = 1;
+    for (int64_t d = dim + 1; d < x.dim(); ++d) C *= x.size(d);
+    at::Tensor y = at::empty(x.sizes(), x.options().dtype(at::kComplexFloat));
+    if (y.numel() == 0) return y;
+    const at::Tensor xc = x.contiguous();
+    at::Tensor kc = kernel.contiguous();
+    if ((uintptr_t)kc.data_ptr() & 15u) kc = kc.clone();  // (a view at an odd offset: the multiply loads 16 bytes)
+    const nfft_hip_problem q = toeplitz_problem(dim, B, N, C);
+    c10::DeviceGuard guard(x.device());
+    const int64_t ws_bytes = nfft_hip_toeplitz_workspace_bytes(&q);
+    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
+    at::Tensor ws = byte_buffer(ws_bytes, x);
+    check_rc(nfft_hip_toeplitz_apply(&q, kc.data_ptr<float>(), xc.data_ptr(), real_input ? 0 : 1, y.data_ptr(),
+                                     ws.data_ptr(), ws_bytes, stream_of(x)));
+    return y;
+}
+
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
 at::TensorOptions current_device_options(at::ScalarType dtype)
 {
@@ -772,4 +841,7 @@ TORCH_LIBRARY(torch_nfft, m)
     m.def("_nfft_fastsum_backward(Tensor sources, Tensor targets, Tensor x, Tensor dy, Tensor coeffs, Tensor? band, "
           "Tensor? source_batch, Tensor? target_batch, int m, int need_x, int need_sources, int need_targets) "
           "-> (Tensor, Tensor, Tensor)", &nfft_fastsum_backward);
+    // not in the reference: the Toeplitz normal operator A^H W A (nfft_toeplitz_kernel / nfft_normal / nfft_inverse)
+    m.def("_nfft_toeplitz_kernel(Tensor t) -> Tensor", &nfft_toeplitz_kernel);
+    m.def("_nfft_normal(Tensor kernel, Tensor x) -> Tensor", &nfft_normal);
 }

@@ -138,6 +138,22 @@ int launch_row_r2c(const Geom &g, const float *grid, void *scratch, int64_t scra
 int launch_row_c2r(const Geom &g, const float2 *spec, void *scratch, int64_t scratch_planes, int64_t nplanes,
                    float *grid, hipStream_t stream);
 
+// toeplitz.hip (the normal operator A^H W A)
+// set-up: t [B, M^dim] complex, lag n at index n + N (the bandwidth-2N adjoint of the weights) -> the Hermitian half
+// spectrum [B, M^(dim-1) * (M/2+1)] whose kC2R transform is the real kernel grid K; lags with a component -N zeroed,
+// M^-dim folded in.  g: the geometry of the bandwidth-N problem (g.M = 2N)
+int launch_toeplitz_spectrum(const Geom &g, const float2 *t, int64_t B, float2 *spec, hipStream_t stream);
+// grid planes [plane0, plane0 + nplanes) of a chunk (local index 0 .. nplanes) *= K[plane / Cr]; K [B, M^dim] float32,
+// 16-byte aligned.  One load of K per point set and cell for all of the set's planes in the chunk; no atomics.
+int launch_toeplitz_multiply(const Geom &g, float *grid, const float *K, int64_t Cr, int64_t plane0, int64_t nplanes,
+                             hipStream_t stream);
+
+// colfft.hip: the row passes of both FFT stages fused with that product (rowfft_supported grids, planar route): the compact
+// half spectrum of the planes 2 * pair, 2 * pair + 1 (pair < npairs) of a chunk is transformed to real rows in LDS,
+// multiplied by K[(pair0 + pair) / pairs_per_set] and transformed back, in place -- the grid never reaches memory
+int launch_row_toeplitz(const Geom &g, float2 *spec, const float *K, int64_t pairs_per_set, int64_t pair0, int64_t npairs,
+                        hipStream_t stream);
+
 // smallgrid.hip: transforms whose oversampled grid (<= 4096 cells) fits one workgroup's LDS -- one kernel per direction,
 // no point plan
 bool small_grid_supported(const nfft_hip_problem *p);
@@ -147,7 +163,7 @@ int launch_small_grid_forward(const nfft_hip_problem *p, const float *pos, const
                            int real_output, void *y, hipStream_t stream);
 
 // api.hip: optional per-stage GPU timing with HIP events on the caller's stream (nfft_hip_profile_*)
-enum Stage { kStagePlan = 0, kStageGather, kStageZero, kStageSpread, kStageFft, kStageDeconv, kStageInterp, kNumStages };
+enum Stage { kStagePlan = 0, kStageGather, kStageZero, kStageSpread, kStageFft, kStageDeconv, kStageInterp, kStageMultiply, kNumStages };
 struct StageTimer {
     StageTimer(Stage stage, hipStream_t stream);
     ~StageTimer();

@@ -39,7 +39,8 @@ static SpecGeom make_spec_geom(const Geom &g)
         s.band *= s.Na[a];
         if (a < 2) s.half_cells *= g.Ma[a];
     }
-    s.param = 1.047197551196597746f * (float)g.m / ((float)g.N * (float)g.N);
+    // (no roll-off: exponent scale 0, and expf(0) is exactly 1)
+    s.param = g.rolloff ? 1.047197551196597746f * (float)g.m / ((float)g.N * (float)g.N) : 0.0f;
     return s;
 }
 

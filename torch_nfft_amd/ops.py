@@ -23,6 +23,8 @@ Not in the reference, for gradients with respect to the points: ``nfft_forward_g
 backward ``nfft_forward_grad_points_backward`` (their second derivatives), ``nfft_fastsum_band``
 and ``nfft_fastsum_backward`` (the fast summation).  They take their plans
 from the same cache with the same problems, so a backward pass right after its forward pass plans nothing.
+``nfft_toeplitz_kernel`` and ``nfft_normal`` (the normal operator ``A^H W A`` as a Toeplitz product)
+use no plan at all.
 """
 import torch
 
@@ -112,6 +114,21 @@ def nfft_fastsum_backward(sources, targets, x, dy, coeffs, band, source_batch, t
     (``nfft_hip_fastsum_backward_planned``) on the point plans the forward pass cached."""
     return _ops._nfft_fastsum_backward(sources, targets, x, dy, coeffs, band, source_batch, target_batch, int(m),
                                        1 if need_x else 0, 1 if need_sources else 0, 1 if need_targets else 0)
+
+
+def nfft_toeplitz_kernel(t):
+    """torch_nfft::_nfft_toeplitz_kernel(Tensor t) -> Tensor (not in the reference): the real kernel grid ``K``
+    ``[B, 2N, ..., 2N]`` float32 of the normal operator ``A^H W A`` from ``t = nfft_adjoint(weights, bandwidth 2N)``
+    ``[B, 2N, ..., 2N]`` complex64 (lag ``n`` at index ``n + N``).  One native call (``nfft_hip_toeplitz_kernel``;
+    DESIGN.md section 7c)."""
+    return _ops._nfft_toeplitz_kernel(t)
+
+
+def nfft_normal(kernel, x):
+    """torch_nfft::_nfft_normal(Tensor kernel, Tensor x) -> Tensor (not in the reference): ``A^H W A x`` for ``x``
+    ``[B] + [N]*d + cols`` float32 or complex64 and the kernel grid of the same points; complex64.  One native call
+    (``nfft_hip_toeplitz_apply``): forward FFT stage, product with ``kernel``, adjoint FFT stage -- no point plan."""
+    return _ops._nfft_normal(kernel, x)
 
 
 class _on_device:
