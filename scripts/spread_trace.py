@@ -1,7 +1,9 @@
-"""Developer tool: per-workgroup timeline of spread_mfma_kernel at the C3 size from a trace build
-(scripts/exp_build.sh spread_mfma.hip trace:torch_nfft_amd/csrc/spread_mfma.hip:"-DNFFT_HIP_TRACE";
-NFFT_HIP_LIB=scripts/ubench/libnfft_trace.so).  Prints how busy the CUs are over the launch, the share of the
-per-item prologue and the tail, and saves the raw stamps under gpurun_out/."""
+"""Developer tool: per-workgroup timeline of spread_mfma_kernel -- or, with KERNEL=interp, of interp_stream_kernel -- at
+the C3 size from a trace build
+(scripts/exp_build.sh spread_mfma.hip trace:torch_nfft_amd/csrc/spread_mfma.hip:"-DNFFT_HIP_TRACE", or the same with
+interp_stream.hip; NFFT_HIP_LIB=scripts/ubench/libnfft_trace.so).  Prints how busy the CUs are over the launch, the
+workgroups resident over time, the share of the per-item prologue and the tail, and saves the raw stamps as .npy.
+(The gather's stamps: entry, end of the item's set-up, end of its last wave; [5] = blocks of 32 points and points.)"""
 import ctypes, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -27,22 +29,30 @@ grid = torch.empty((2 * N,) * 3, device="cuda")
 scratch = torch.empty(lib.nfft_hip_spread_scratch_bytes(ctypes.byref(prob), 1) // 4, device="cuda")
 nwg = 1 << 16
 trace = torch.zeros((nwg, 8), dtype=torch.int64, device="cuda")
-assert lib.nfft_dbg_set_spread_trace(p(trace)) == 0
-for it in range(3):
+gather = os.environ.get("KERNEL", "spread") == "interp"
+if gather:
+    y = torch.empty(n, device="cuda")
+    assert lib.nfft_dbg_set_stream_trace(p(trace)) == 0
     _lib.check(lib.nfft_hip_spread(ctypes.byref(prob), p(plan), p(x), 1, p(grid), p(scratch), s))
+    call = lambda: _lib.check(lib.nfft_hip_interpolate(ctypes.byref(prob), p(plan), p(grid), 1, p(y), s))
+else:
+    assert lib.nfft_dbg_set_spread_trace(p(trace)) == 0
+    call = lambda: _lib.check(lib.nfft_hip_spread(ctypes.byref(prob), p(plan), p(x), 1, p(grid), p(scratch), s))
+for it in range(3):
+    call()
 torch.cuda.synchronize()
 trace.zero_()
 torch.cuda.synchronize()
 t0 = time.perf_counter()
-_lib.check(lib.nfft_hip_spread(ctypes.byref(prob), p(plan), p(x), 1, p(grid), p(scratch), s))
+call()
 torch.cuda.synchronize()
-print("call: %.3f ms (zero-fill + spreading + overflow launch)" % ((time.perf_counter() - t0) * 1e3))
+print("call: %.3f ms (%s + overflow launch)" % ((time.perf_counter() - t0) * 1e3, "gather" if gather else "zero-fill + spreading"))
 t = trace.cpu().numpy().astype(np.int64)
 ran = t[:, 0] != 0
 t = t[ran]
 out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
 os.makedirs(out, exist_ok=True)
-np.save(os.path.join(out, "spread_trace_%s.npy" % os.environ.get("TRACE_TAG", "c3")), t)
+np.save(os.path.join(out, "%s_trace_%s.npy" % ("interp" if gather else "spread", os.environ.get("TRACE_TAG", "c3"))), t)
 tick = 10.0  # ns per stamp (100 MHz)
 start, xmax, loop, end, hw, cnt, preflush = (t[:, k] for k in (0, 1, 2, 3, 4, 5, 6))
 worked = end != 0
@@ -75,8 +85,13 @@ print("items: duration us mean %.1f (min %.1f max %.1f); max-|x| + permutation p
       % (dur.mean(), dur.min(), dur.max(), pro1.mean(), pro2.mean(), main.mean(), tail.mean()))
 print("shares of the summed item time: prologue %.1f %%, main loop %.1f %%, final flush %.1f %%"
       % (100 * (pro1 + pro2).sum() / dur.sum(), 100 * main.sum() / dur.sum(), 100 * tail.sum() / dur.sum()))
-print("K-blocks per item mean %.0f, points per item mean %.0f, fill %.3f; main-loop ns per K-block %.1f (over items with >= 100 K-blocks)"
-      % (kb.mean(), pts.mean(), pts.sum() / (16 * kb.sum()), (main[kb >= 100] * 1e3 / kb[kb >= 100]).mean()))
+print("%s per item mean %.0f, points per item mean %.0f, fill %.3f; main-loop ns per %s %.1f (over items with >= 100)"
+      % ("blocks" if gather else "K-blocks", kb.mean(), pts.mean(), pts.sum() / ((32 if gather else 16) * kb.sum()),
+         "block" if gather else "K-block", (main[kb >= 100] * 1e3 / kb[kb >= 100]).mean()))
+# cost model of scripts/item_schedule_sim.py: item time = a * K-blocks (blocks) + b, least squares over the items
+A = np.stack([kb, np.ones_like(kb)], axis=1)
+coef = np.linalg.lstsq(A, dur, rcond=None)[0]
+print("fit: item us = %.4f x %s + %.1f" % (coef[0], "blocks" if gather else "K-blocks", coef[1]))
 # how many CUs are busy over time (20 bins)
 edges = np.linspace(T0, T1, 21)
 occ = []

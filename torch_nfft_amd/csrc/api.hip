@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "range_items.h"
 
 namespace nfft {
 
@@ -174,7 +175,10 @@ struct Switches {
     bool small_grid;      // NFFT_HIP_SMALL_GRID=0: no one-kernel path for small grids
     bool small_narrow;    // NFFT_HIP_SMALL_NARROW=0: the 64^3 grid keeps the wide tiling
     int stream_min;       // NFFT_HIP_STREAM_MIN (tuning): smallest streamed work item in points; 3000
-    double items_per_cu;  // NFFT_HIP_ITEMS_PER_CU (tuning): work items per CU of a pencil's slab ranges; 5.4
+    double items_per_cu;  // NFFT_HIP_ITEMS_PER_CU (tuning): work items per CU the items of a pencil are sized for; 5.4
+    bool fine_tail;       // NFFT_HIP_FINE_TAIL=0 (tuning): no finer ranges for the last pencils of a launch of several rounds
+    int grade;            // NFFT_HIP_GRADE=1|2 (tuning): work items cut per pencil by point count with a graded tail, for launches
+                          // of more than one round of workgroups / always; 0 (default): equal ranges of slabs
 };
 const Switches &switches()
 {
@@ -194,6 +198,9 @@ const Switches &switches()
         w.stream_min = sm > 0 ? sm : 3000;
         const double ipc = std::atof(env("NFFT_HIP_ITEMS_PER_CU"));
         w.items_per_cu = ipc >= 1.0 && ipc <= 64.0 ? ipc : 5.4;
+        w.fine_tail = env("NFFT_HIP_FINE_TAIL")[0] != '0';
+        v = env("NFFT_HIP_GRADE");
+        w.grade = v[0] == '1' ? 1 : v[0] == '2' ? 2 : 0;
         return w;
     }();
     return s;
@@ -212,6 +219,8 @@ SpreadMode spread_mode() { return switches().spread; }
 bool column_groups_enabled() { return switches().colgroups; }
 bool work_list_forced() { return switches().work_list; }
 double items_per_cu() { return switches().items_per_cu; }
+int grading_mode() { return switches().grade; }
+bool fine_tail_enabled() { return switches().fine_tail; }
 int stream_min_item_points() { return switches().stream_min; }
 int owned_override() { return switches().owned; }
 
@@ -672,6 +681,41 @@ int nfft_hip_plan_verify(const nfft_hip_problem *p, const float *pos, const int6
     static std::atomic<unsigned> slot{0};  // eight verifications of one plan may be in flight (on different streams)
     return launch_points_verify(pos, batch, p->num_points, p->dim, (char *)plan + plan_route(p, 0).L.off_seal,
                                 (int)(slot++ & 7u), (hipStream_t)stream);
+}
+
+// Test entry (tests/test_gpu_graded_items.py; not part of the C ABI of include/nfft_hip.h, like nfft_dbg_eft): copies the
+// work list of a plan of the wide tiling to the host.  which = 0: the plan of the gather (and of scatter spreading), 1: the
+// plan the spreading kernel uses (the owned one if the problem has one).  info[8] = {entries written by the plan, 1 if the
+// plan runs from the persistent launch, capacity of the list (work_cap), workgroups of the per-entry launch, pencils per
+// point set, point sets, slabs per pencil, items of an average pencil}; set_hdr[2 * sets] = {entries, first entry} of every
+// point set; entries[4 * min(capacity, max_entries)] = the list in launch order, rows {point set * pencils + pencil, first
+// slab, end slab, points}.  All three are host buffers; the call waits for the stream.
+int nfft_dbg_work_list(const nfft_hip_problem *p, const void *plan, int which, int64_t *info, int32_t *set_hdr, int32_t *entries,
+                       int64_t max_entries, void *stream)
+{
+    if (int rc = validate(p)) return rc;
+    const Route r = plan_route(p, 0);
+    const Geom &g = which ? r.spread_geom() : r.g;
+    const PlanLayout &L = which ? r.spread_layout() : r.L;
+    if (!g.wide || !plan || !info || !set_hdr || !entries) { set_error("Input mismatch: no work list"); return NFFT_HIP_EINVAL; }
+    const char *base = (const char *)(which ? r.spread_plan(plan) : plan) + L.off_work;
+    hipStream_t s = (hipStream_t)stream;
+    int32_t hdr[4];
+    NFFT_HIP_CHECK(hipMemcpyAsync(hdr, base, 16, hipMemcpyDeviceToHost, s));
+    NFFT_HIP_CHECK(hipMemcpyAsync(set_hdr, base + 16, (size_t)r.B * 8, hipMemcpyDeviceToHost, s));
+    const int64_t rows = std::min<int64_t>(L.work_cap, max_entries);
+    NFFT_HIP_CHECK(hipMemcpyAsync(entries, base + (L.work_head + L.work_cap) * 16, (size_t)rows * 16, hipMemcpyDeviceToHost, s));
+    NFFT_HIP_CHECK(hipStreamSynchronize(s));
+    const RangeSplit rs = range_split(g, L, r.n);
+    info[0] = hdr[0];
+    info[1] = hdr[2];
+    info[2] = L.work_cap;
+    info[3] = std::min<int64_t>(per_entry_workgroups(r.n, rs.nsets, rs.pencils, rs.runs, g.M, device_cu_count()), L.work_cap);
+    info[4] = rs.pencils;
+    info[5] = rs.nsets;
+    info[6] = g.M;
+    info[7] = rs.runs;
+    return 0;
 }
 
 int64_t nfft_hip_spread_scratch_bytes(const nfft_hip_problem *p, int64_t real_columns)

@@ -75,8 +75,9 @@ PlanLayout plan_layout(const Geom &g, int64_t n, int64_t B)
     L.grouped = L.two_level && g.CG == 3;
     L.off_groups = o;  o = align_up(o + (L.grouped ? L.ntiles * 2 * 4 : 0), 256);
     // work list of the matrix-core kernels (wide tiling; segment_split_kernel / work_order_kernel below): a header,
-    // the list and its copy in launch order.  ranges + entries / 2048 bounds the list (pieces hold >= 2048 points)
-    L.work_cap = g.wide ? (int64_t)g.nta[1] * g.nta[2] * B * kSegMax + L.cap / 2048 + 16 : 0;
+    // the list and its copy in launch order.  A pencil of P points has at most max(kSegMax, P / 2048 + 1) items by point count
+    // (seg_target_points >= 2048) and ceil(M / kItemMaxSlabs) more where such items are cut at kItemMaxSlabs slabs
+    L.work_cap = g.wide ? (int64_t)g.nta[1] * g.nta[2] * B * (kSegMax + 1 + (g.M + kItemMaxSlabs - 1) / kItemMaxSlabs) + L.cap / 2048 + 16 : 0;
     L.work_head = 1 + (B * 8 + 15) / 16;
     L.off_work = o;    o = align_up(o + (g.wide ? (L.work_head + 2 * L.work_cap) * 16 : 0), 256);
     // the count passes leave the keys they computed for the scatter passes (two bytes per point / record instead of
@@ -670,82 +671,151 @@ sort2_lds_kernel(Geom g_in, int npencils, int nblocks, const int *__restrict__ r
     }
 }
 
-// Work list of the wide tiling (common.h): every range of slabs (range_items.h range_split) of every (point set,
-// pencil), dense ranges cut into pieces of about `target` points.  One wave per (point set, pencil), lane r = range r
-// of the pencil.
-// work[0] = {entries, 1 if any range was cut, 0, 0}; entries {point set * pencils + pencil, first slab, end slab, points}.
+// Work list of the wide tiling (common.h): the items of every (point set, pencil), cut from the pencil's own slab
+// offsets by the equal or the graded cut.  One wave per (point set, pencil) holds the offsets in LDS; lane i cuts and lists
+// range i (equal cut) or finds the i-th cut by point count with a binary search of its own and lists item i (graded cut).
+// work[0] = {entries, 0, 1 if the plan runs from the persistent launch, 0}; entries {point set * pencils + pencil, first
+// slab, end slab, points}.  `ordered`: the list in launch order, which a balanced plan of the equal cut gets here.
 __global__ void __launch_bounds__(64)
-segment_split_kernel(Geom g, int npl /* point sets x pencils */, int pencils, int runs, int target,
-                     const int *__restrict__ offsets, int4 *__restrict__ work, int4 *__restrict__ list, int capacity)
+segment_split_kernel(Geom g, int npl /* point sets x pencils */, int pencils, int runs, int target, int grade,
+                     int tailp /* equal cut: the last `tailp` pencils of a set get 2 x runs ranges (common.h tail_pencils) */,
+                     const int *__restrict__ offsets, int4 *__restrict__ work, int4 *__restrict__ list, int4 *__restrict__ ordered,
+                     int capacity)
 {
+    extern __shared__ int off_lds[];  // [M + 1] slab offsets of the pencil
     const int pl = blockIdx.x;
     if (pl >= npl) return;
-    const int r = threadIdx.x;
-    if (r >= runs) return;
+    const int lane = threadIdx.x, M = g.M;
     const int *off = offsets + (int64_t)pl * g.np0;  // np0 == M bins per pencil, SB == 1
-    const int seg_slabs = (g.M + runs - 1) / runs;
-    const int sb = min(r * seg_slabs, g.M), se = min(sb + seg_slabs, g.M);
-    const int o_sb = off[sb], pts = off[se] - o_sb;
-    if (se <= sb) return;
-    int pieces = (int)(((int64_t)pts + target / 2) / target);
-    pieces = pieces < 1 ? 1 : (pieces > kSegPieces ? kSegPieces : pieces);
-    // (pieces <= 1 + pts / target with target >= 2048: the list's capacity, ranges + entries / 2048, always suffices)
-    // the plan runs from its list (work[0].z) when a range is cut or holds >= 1.5 x the mean over ALL ranges of its point
-    // set, empty ones included (work_order_kernel)
-    {
-        const int64_t first = (int64_t)(pl / pencils) * pencils * g.np0;
-        const int64_t set_pts = offsets[first + (int64_t)pencils * g.np0] - offsets[first];
-        if (pieces > 1 || (pts > 0 && (double)pts * (double)(pencils * runs) >= 1.5 * (double)set_pts))
+    for (int i = lane; i <= M; i += 64) off_lds[i] = off[i];
+    __syncthreads();
+    const int o0 = off_lds[0], P = off_lds[M] - o0;
+    const int64_t first = (int64_t)(pl / pencils) * pencils * g.np0;
+    const int64_t set_pts = offsets[first + (int64_t)pencils * g.np0] - offsets[first];
+    // The plan runs from the persistent launch (work[0].z) when one of the pencil's `runs` equal ranges of slabs holds
+    // >= 1.5 x `target` points or >= 1.5 x the mean over ALL such ranges of its point set, empty ones included: a clustered
+    // input, whose dense pencils are many small items (the persistent form has no turn-around between them)
+    if (lane < runs) {
+        const int seg_slabs = (M + runs - 1) / runs;
+        const int sb = min(lane * seg_slabs, M), se = min(sb + seg_slabs, M);
+        const int pts = off_lds[se] - off_lds[sb];
+        if (2 * (int64_t)pts >= 3 * (int64_t)target || (pts > 0 && (double)pts * (double)(pencils * runs) >= 1.5 * (double)set_pts))
             atomicOr(&((int *)work)[2], 1);
     }
-    int prev = sb;  // end of the previous piece
-    for (int p = 1; p <= pieces; ++p) {
-        int end = se;
-        if (p < pieces) {
-            const int t = o_sb + (int)((int64_t)pts * p / pieces);
-            int lo = prev, hi = se;  // smallest slab in [prev, se] whose offset is >= t
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (off[mid] >= t) hi = mid; else lo = mid + 1;
-            }
-            end = lo;
+    if (!grade) {
+        // Equal cut (the default): `runs` equal ranges of slabs, a range of >= 1.5 x `target` points cut on by point count.
+        // A plan whose ranges are all whole is balanced, and its launch order is the grid order: range r of pencil p is entry
+        // p * runs + r of its set's part of the ordered list (work_order_kernel leaves it alone); the pencils of the launch's
+        // tail hold twice as many, half as long
+        const int set = pl / pencils, pin = pl - set * pencils;
+        const int fine = pin >= pencils - tailp ? pin - (pencils - tailp) : -1;  // >= 0: a pencil of the launch's tail
+        const int k = fine >= 0 ? 2 * runs : runs;
+        if (lane >= k) return;
+        const int seg_slabs = (M + k - 1) / k;
+        const int sb = min(lane * seg_slabs, M), se = min(sb + seg_slabs, M);
+        const int64_t set_entries = (int64_t)(pencils + tailp) * runs;
+        const int64_t slot_ordered = set * set_entries + (int64_t)(pin + (fine > 0 ? fine : 0)) * runs + lane;
+        const bool fits = (int64_t)(npl / pencils) * set_entries <= capacity;
+        if (se <= sb) {  // (no slabs left for this range: an empty entry keeps the grid order whole)
+            if (fits) ordered[slot_ordered] = make_int4(pl, sb, sb, 0);
+            return;
         }
-        const int piece_pts = off[end] - off[prev];
-        // (pieces without points are listed too: the owned tiling writes every plane, and the gather kernels give an
+        const int o_sb = off_lds[sb], pts = off_lds[se] - o_sb;
+        int pieces = (int)(((int64_t)pts + target / 2) / target);
+        pieces = pieces < 1 ? 1 : (pieces > kSegPieces ? kSegPieces : pieces);
+        if (pieces == 1 && fits) ordered[slot_ordered] = make_int4(pl, sb, se, pts);
+        int prev = sb;
+        for (int p = 1; p <= pieces; ++p) {
+            int end = se;
+            if (p < pieces) {
+                const int t = o_sb + (int)((int64_t)pts * p / pieces);
+                int lo_ = prev, hi_ = se;  // smallest slab in [prev, se] whose offset is >= t
+                while (lo_ < hi_) {
+                    const int mid = (lo_ + hi_) >> 1;
+                    if (off_lds[mid] >= t) hi_ = mid; else lo_ = mid + 1;
+                }
+                end = lo_;
+            }
+            if (end > prev) {
+                const int slot = atomicAdd(&((int *)work)[0], 1);
+                if (slot < capacity) {
+                    list[slot] = make_int4(pl, prev, end, off_lds[end] - off_lds[prev]);
+                    atomicAdd(&((int2 *)(work + 1))[pl / pencils].x, 1);
+                }
+            }
+            prev = end;
+        }
+        return;
+    }
+    // Graded cut (NFFT_HIP_GRADE): the pencil's points at the rate that gives the set's average pencil `runs` items -- a
+    // light pencil gets FEWER items, not smaller ones -- at most M / 32 of them (a floor of 32 slabs: every item pays a
+    // set-up and 2m+1 halo planes), or one per `target` points if that is more (a dense pencil), and never fewer than the
+    // slab limit asks for
+    const int lo = (M + kItemMaxSlabs - 1) / kItemMaxSlabs, hi = M / 32 > lo ? M / 32 : lo;
+    const double at_rate = fmin((double)runs * (double)pencils / (double)(set_pts > 0 ? set_pts : 1) * (double)P + 0.5, (double)hi);
+    const double dense = (double)P / (double)target + 0.5;
+    int k = (int)fmin(fmax(at_rate, dense), (double)kItemMaxCount);
+    k = k < lo ? lo : k;
+    // (k <= 1 + P / target with target >= 2048, or <= kSegMax at the average rate, or lo: the list's capacity always suffices)
+    const bool by_slabs = k == lo;  // a light pencil: equal ranges of slabs (by point count one of them might exceed the limit)
+    const bool graded = k >= lo + 2 && k > kGradeTail;  // (k = lo + 1 graded: the big items would exceed the limit)
+    auto cut = [&](const int i) {
+        if (i <= 0) return 0;
+        if (i >= k) return M;
+        if (by_slabs) return min(M, i * ((M + k - 1) / k));
+        const int t = o0 + (int)((double)P * grade_fraction(i, k, graded));
+        int lo_ = 0, hi_ = M;  // smallest slab whose offset is >= t
+        while (lo_ < hi_) {
+            const int mid = (lo_ + hi_) >> 1;
+            if (off_lds[mid] >= t) hi_ = mid; else lo_ = mid + 1;
+        }
+        return lo_;
+    };
+    for (int i = lane; i < k; i += 64) {
+        const int b0 = cut(i), b1 = cut(i + 1);
+        if (b1 <= b0) continue;
+        // (items without points are listed too: the owned tiling writes every plane, and the gather kernels give an
         // item the chunks of slabs that START in it -- such a chunk may reach into the next item's slabs)
-        if (end > prev) {
+        const int parts = (b1 - b0 + kItemMaxSlabs - 1) / kItemMaxSlabs;
+        for (int p = 0; p < parts; ++p) {
+            const int sb = b0 + (int)((int64_t)(b1 - b0) * p / parts), se = b0 + (int)((int64_t)(b1 - b0) * (p + 1) / parts);
             const int slot = atomicAdd(&((int *)work)[0], 1);
             if (slot < capacity) {
-                list[slot] = make_int4(pl, prev, end, piece_pts);
+                list[slot] = make_int4(pl, sb, se, off_lds[se] - off_lds[sb]);
                 atomicAdd(&((int2 *)(work + 1))[pl / pencils].x, 1);
             }
         }
-        prev = end;
     }
 }
 
-// Puts the work list of an unbalanced plan in launch order (a balanced one -- segment_split_kernel saw no range that was
-// cut or holds >= 1.5 x its set's mean: every uniform input -- returns at once: its kernels run one workgroup per range in
-// grid order, straight-line code, neighbouring ranges side by side; measured 1 % faster at config C3 than any sorted
-// order).  One workgroup per point set b: its entries are copied to sorted[start_b ...), biggest first (a counting sort
-// into 16 size classes, sixteenths of the set's largest entry), and set_hdr[b] = {entries, start_b}.  ONE persistent
-// launch per plane then walks the set's part of `sorted`, so that the tail of the launch is made of small items:
-// clustered inputs leave most CUs idle behind their few heavy ranges in grid order (43 % CU utilisation at C3-clustered),
-// and a separate launch for the cut-off pieces (rounds 2-3) started only when the last first piece was done.
+// Puts the work list in launch order.  One workgroup per point set b: its entries are copied to sorted[start_b ...),
+// biggest first (a counting sort into 16 size classes, sixteenths of the set's largest entry), and set_hdr[b] = {entries,
+// start_b}.  Every launch takes its items from there: the tail of the launch is then made of small items.  In grid
+// order clustered inputs leave most CUs idle behind their few heavy ranges (43 % CU utilisation at C3-clustered).  A
+// balanced plan of the equal cut keeps the grid order that segment_split_kernel wrote: with equal items sorting buys
+// nothing (measured 1 % slower than grid order at config C3 in round 3).  A set with more entries than the
+// one-workgroup-per-entry launch has workgroups (per_entry_cap: common.h per_entry_workgroups) sends the plan to the
+// persistent launch.
 constexpr int kOrderClasses = 16;
 __global__ void __launch_bounds__(1024)
 work_order_kernel(int4 *__restrict__ work, const int4 *__restrict__ list, int4 *__restrict__ sorted, int capacity,
-                  int pencils, int forced)
+                  int pencils, int forced, int per_entry_cap, int grid_runs /* > 0: the equal cut, `grid_runs` ranges per pencil */,
+                  int tailp /* ... and twice as many for the last `tailp` pencils */)
 {
     __shared__ int cnt[kOrderClasses][1024];  // [class][thread]: entries of the class in the thread's chunk -> their first slot
     __shared__ int total[kOrderClasses];
     __shared__ int maxpts, start;
     const int b = blockIdx.x;
     const int4 hdr = work[0];
-    if (!hdr.z && !forced) return;  // balanced: nobody reads the list
-    if (forced && b == 0 && threadIdx.x == 0) ((int *)work)[2] = 1;
     const int nitems = min(hdr.x, capacity);
     int2 *const set_hdr = (int2 *)(work + 1);
+    if (grid_runs > 0 && !hdr.z && !forced) {
+        // balanced plan of the equal cut: segment_split_kernel wrote the ordered list itself, in grid order (neighbouring
+        // ranges run side by side: measured 1 % faster at config C3 than any sorted order of equal items)
+        if (threadIdx.x == 0) set_hdr[b] = make_int2((pencils + tailp) * grid_runs, b * (pencils + tailp) * grid_runs);
+        return;
+    }
+    if (threadIdx.x == 0 && (forced || set_hdr[b].x > per_entry_cap)) atomicOr(&((int *)work)[2], 1);
     if (threadIdx.x == 0) { maxpts = 1; start = 0; }
     __syncthreads();
     {   // entries of the sets in front of this one
@@ -875,10 +945,17 @@ static int launch_segment_split(const Geom &g, const PlanLayout &L, int64_t n, i
     NFFT_HIP_CHECK(hipMemsetAsync(work, 0, (size_t)L.work_head * 16, stream));
     if (npl <= 0) return 0;
     int4 *const list = work + L.work_head;
-    hipLaunchKernelGGL(segment_split_kernel, dim3((unsigned)npl), dim3(64), 0, stream, g, (int)npl, (int)s.pencils, s.nsegm,
-                       target, offsets, work, list, (int)L.work_cap);
+    const bool grade = grade_items(B, s.pencils, s.runs, device_cu_count());
+    const int tailp = grade ? 0 : tail_pencils(B, s.pencils, s.runs, g.M, device_cu_count());
+    // the equal cut writes a balanced plan's ordered list itself, (pencils + tailp) * runs entries per set: they must fit
+    // (plan_layout: kSegMax + 1 + M / 128 entries per pencil, and tailp <= pencils / 2 pencils of 2 * runs <= M / 32)
+    if (!grade && (s.pencils + tailp) * s.runs * B > L.work_cap) { set_error("work list too small for the equal cut"); return 2; }
+    hipLaunchKernelGGL(segment_split_kernel, dim3((unsigned)npl), dim3(64), (size_t)(g.M + 1) * 4, stream, g, (int)npl,
+                       (int)s.pencils, s.runs, target, grade ? 1 : 0, tailp, offsets, work, list, list + L.work_cap, (int)L.work_cap);
     hipLaunchKernelGGL(work_order_kernel, dim3((unsigned)B), dim3(1024), 0, stream, work, list, list + L.work_cap,
-                       (int)L.work_cap, (int)s.pencils, work_list_forced() ? 1 : 0);
+                       (int)L.work_cap, (int)s.pencils, work_list_forced() ? 1 : 0,
+                       (int)std::min<int64_t>(per_entry_workgroups(n, B, s.pencils, s.runs, g.M, device_cu_count()), INT32_MAX),
+                       grade ? 0 : s.runs, tailp);
     return 0;
 }
 

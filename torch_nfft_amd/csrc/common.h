@@ -360,39 +360,102 @@ __device__ __forceinline__ int sub_of_cells(const Geom &g, const int cell[3])
 
 // ---- plan layout -----------------------------------------------------------
 // [ tile_offset int32[ntiles*SB+1] | cursor int32[ntiles] | perm int32[n] | spos float[n*pstride] | scan temp | sort scratch ]
-// Wide tiling, load balance of the matrix-core kernels: a pencil is swept in `runs` equal ranges of slabs (as many as
-// give ~5.4 workgroups per CU for an average pencil).  Balanced inputs (every uniform one) run one workgroup per range.
-// Ranges that hold far more points than average (clustered inputs) are cut further by point count at plan time, and all
-// pieces go to a work list in the plan:
-//   [0] = {entries, any range cut, 1 = walk the list, 0};  then one int2 {entries, first entry} per point set;
+// Wide tiling, load balance of the matrix-core kernels: a pencil is swept in work items, ranges of slabs.  The plan cuts
+// every (point set, pencil) from that pencil's own slab offsets (binning.hip segment_split_kernel), in one of two ways:
+//   * the equal cut (default): `runs` equal ranges of slabs per pencil (seg_base_runs: as many as give ~5.4 workgroups per
+//     CU for an average pencil); a range that holds >= 1.5 x seg_target_points points (clustered inputs) is cut on by point
+//     count.  A plan whose ranges are all whole is balanced, and its launch order is the grid order.  In a launch of
+//     several rounds of workgroups the last pencils of the grid order get twice as many ranges, half as long (tail_pencils);
+//   * the graded cut (NFFT_HIP_GRADE; grade_items): a pencil gets as many items as its points are worth at the rate that
+//     gives an average pencil `runs` of them -- a light pencil FEWER items, not smaller ones -- or one per
+//     seg_target_points points where that is more, cut by point count; the last three hold 3/4, 1/2 and 1/4 of the
+//     others (grade_fraction), so that a launch that takes its items biggest first ends on small ones; no item exceeds
+//     kItemMaxSlabs slabs.  By the list-scheduling model of scripts/item_schedule_sim.py the equal cut leaves a launch of
+//     5.4 rounds at 92 % and this one at 99 % CU utilisation at config C3; measured, it LOSES there (spreading + 2 %, gather
+//     + 8 %, profiles/r08_graded_items.md): the gather's item time follows an item's slabs, not its points (it stages every
+//     plane of its range), so the long items of light pencils end its launch, more items cost the spreading kernel as much
+//     as its tail gains, and neighbouring ranges no longer run side by side.  Kept as a switch for other shapes.
+// All items go to the work list in the plan:
+//   [0] = {entries, 0, 1 = persistent launch, 0};  then one int2 {entries, first entry} per point set;
 //   then the entries {point set * pencils + pencil, first slab, end slab, points} as they were produced;
-//   then the same entries grouped by point set, every set's biggest first.
-// The matrix-core kernels run a balanced plan one workgroup per range and any other from its list (range_items.h).
-constexpr int kSegMax = 32;      // most ranges per pencil
-constexpr int kSegPieces = 16;   // most pieces a range is cut into
-double items_per_cu();  // api.hip: work items per CU the ranges of a pencil are sized for (5.4; NFFT_HIP_ITEMS_PER_CU: tuning)
+//   then the same entries in launch order, grouped by point set: a balanced plan of the equal cut in grid order, every
+//   other plan biggest first.
+// Every launch of a matrix-core kernel reads its items from the ordered list, and nothing else says what the ranges are
+// (range_items.h): a balanced plan one workgroup per entry -- the hardware dispatcher starts them in list order -- and
+// any other plan (a range far above its set's mean) one persistent workgroup per CU.
+constexpr int kSegMax = 32;        // most items of a pencil at the average rate
+constexpr int kSegPieces = 16;     // equal cut: most pieces a range is cut into
+constexpr int kItemMaxSlabs = 128; // slabs of one work item (spread_mfma.hip kMaxSegSlabs, interp_stream.hip kIsMaxSlabs)
+constexpr int kItemMaxCount = 256; // most items of one pencil by point count
+constexpr int kGradeTail = 3;      // graded items at the end of a pencil's list
+double items_per_cu();  // api.hip: work items per CU the items of a pencil are sized for (5.4; NFFT_HIP_ITEMS_PER_CU: tuning)
+int grading_mode();     // api.hip: NFFT_HIP_GRADE: 0 (default) the equal cut; 1: the graded cut for launches of several rounds of
+                        // workgroups, 2: for every launch
+// Share of a pencil's points in front of item i of k (0 <= i <= k).  Graded (k >= kGradeTail + 1): the first k - 3 items are
+// equal, the last three hold 3/4, 1/2 and 1/4 of one of them.
+__host__ __device__ inline double grade_fraction(int i, int k, bool graded)
+{
+    if (i <= 0) return 0.0;
+    if (i >= k) return 1.0;
+    if (!graded) return (double)i / (double)k;
+    const int big = k - kGradeTail;
+    const double sum = (double)big + 1.5;
+    if (i <= big) return (double)i / sum;
+    return ((double)big + (i - big == 1 ? 0.75 : 1.25)) / sum;
+}
 inline int64_t seg_target_points(int64_t n, int64_t nsets, int ncu)
 {
     const double per_set = (double)n / (double)(nsets > 0 ? nsets : 1);
     const int64_t t = (int64_t)(per_set / (items_per_cu() * (ncu > 0 ? ncu : 256)) + 0.5);
     return t < 2048 ? 2048 : t;
 }
+// Items of an average pencil
 inline int seg_base_runs(int64_t n, int64_t nsets, int64_t pencils, int M, int ncu)
 {
     const double avg = (double)n / (double)((nsets > 0 ? nsets : 1) * (pencils > 0 ? pencils : 1));
     int64_t r = (int64_t)(avg / (double)seg_target_points(n, nsets, ncu) + 0.5);
-    const int64_t lo = (M + 127) / 128, hi = M / 32 > lo ? M / 32 : lo;  // a range holds 32 .. 128 slabs
+    const int64_t lo = (M + kItemMaxSlabs - 1) / kItemMaxSlabs, hi = M / 32 > lo ? M / 32 : lo;  // an item holds 32 .. 128 slabs
     r = r < lo ? lo : (r > hi ? hi : r);
-    // Small problems: a range is ONE workgroup's serial chain of chunks, so few long ranges leave most CUs idle behind a long
+    // Small problems: an item is ONE workgroup's serial chain of chunks, so few long items leave most CUs idle behind a long
     // chain (N = 64, 2e4 points: 18 workgroups of 128 slabs took 0.26 ms in the gather, 72 of 32 slabs 0.08):
-    // as many ranges as the CUs take in ONE round (a count chosen by a cost model, rounds x (slabs + halo), also cut the ranges
+    // as many items as the CUs take in ONE round (a count chosen by a cost model, rounds x (slabs + halo), also cut the items
     // of problems that fill the CUs more than once: measured slower, N = 64, four sets of 10^5 points 0.484 -> 0.532 ms)
     const int64_t groups = (nsets > 0 ? nsets : 1) * (pencils > 0 ? pencils : 1);
     while (r < hi && groups * (r + 1) <= (ncu > 0 ? ncu : 256)) ++r;
     return (int)(r > kSegMax ? kSegMax : r);
 }
+// Whether the plan takes the graded cut (NFFT_HIP_GRADE=1: only a launch of more than one round of workgroups has a tail
+// to fill; one round takes as long as its longest item)
+inline bool grade_items(int64_t nsets, int64_t pencils, int runs, int ncu)
+{
+    return grading_mode() == 2 || (grading_mode() == 1 && (nsets > 0 ? nsets : 1) * pencils * runs > (ncu > 0 ? ncu : 256));
+}
+// Equal cut, the tail of a launch of several rounds of workgroups: the LAST pencils of the grid order -- as many as give
+// one round of half-size items, ncu / (2 runs) -- are cut into 2 x runs ranges, so that the launch ends on items of half the
+// length in BOTH kernels (the gather's item time follows an item's slabs, the spreading kernel's its points), in grid order,
+// without a sort.  At config C3 (5.39 equal items per CU, the last round 39 % full): 22 of 230 pencils, 1 512 items.
+// (The streamed gather is still chosen from the average item, stream_items: its half-length tail items were measured at C3 only.)
+bool fine_tail_enabled();  // api.hip: NFFT_HIP_FINE_TAIL=0 keeps every pencil at `runs` ranges (tuning)
+inline int tail_pencils(int64_t nsets, int64_t pencils, int runs, int M, int ncu)
+{
+    const int cus = ncu > 0 ? ncu : 256;
+    // (one round of workgroups, counted as seg_base_runs and grade_items count it: nothing to fill)
+    if (!fine_tail_enabled() || runs < 1 || (nsets > 0 ? nsets : 1) * pencils * runs <= cus || 2 * runs > M / 32 || 2 * runs > 64) return 0;
+    const int64_t t = (cus + 2 * runs - 1) / (2 * runs);
+    return (int)(t < pencils / 2 ? t : pencils / 2);
+}
+// Workgroups (gridDim.x) of the one-workgroup-per-entry launch: 5/4 of the entries a point set has when its points are
+// spread evenly, or all in dense pencils, plus one per pencil -- a bound the host knows without reading the plan.  A
+// plan with a set of more entries runs from the persistent launch (work_order_kernel).  Workgroups past a set's last
+// entry return at once.
+inline int64_t per_entry_workgroups(int64_t n, int64_t nsets, int64_t pencils, int runs, int M, int ncu)
+{
+    const int64_t even = (pencils + tail_pencils(nsets, pencils, runs, M, ncu)) * runs, dense = n / seg_target_points(n, nsets, ncu);
+    if (!grade_items(nsets, pencils, runs, ncu)) return even;  // the equal cut: a balanced plan has exactly these
+    return (even > dense ? even : dense) * 5 / 4 + pencils + 16;
+}
 // Workgroups of the persistent launch over a plan's work list: one per CU, but no more than a point set can have entries
-// (its ranges plus one cut per `target` points) -- a batch of many small point sets launches a few per plane, not 256.
+// (its pencils' items plus one cut per `target` points) -- a batch of many small point sets launches a few per plane, not 256.
 inline unsigned work_list_workgroups(int64_t n, int64_t nsets, int64_t pencils, int runs, int ncu)
 {
     const int64_t most = pencils * runs + n / seg_target_points(n, nsets, ncu) + 1;

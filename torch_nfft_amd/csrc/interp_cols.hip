@@ -58,8 +58,8 @@ template <int W, bool OVERFLOW>
 __global__ void __launch_bounds__(kIcThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
 interp_cols_kernel(const Geom g, const int *__restrict__ tile_offsets,
                    const float *__restrict__ spos, const float *__restrict__ grid, const int Cr, const int64_t plane0,
-                   const int64_t nplanes, const int64_t group0, float *__restrict__ yr, const int seg_slabs,
-                   const int nsegm, const int4 *__restrict__ work, const int4 *__restrict__ sorted, int *tickets)
+                   const int64_t nplanes, const int64_t group0, float *__restrict__ yr,
+                   const int4 *__restrict__ work, const int4 *__restrict__ sorted, int *tickets)
 {
     constexpr int m = W / 2 - 1;
     if constexpr (!OVERFLOW) reset_tickets(tickets);
@@ -86,20 +86,15 @@ interp_cols_kernel(const Geom g, const int *__restrict__ tile_offsets,
 
     // work items (range_items.h; work_items written out: as a call it changed the persistent form's code)
     if (!plan_launch<OVERFLOW>(work)) return;
-    const int2 set_hdr = OVERFLOW ? ((const int2 *)(work + 1))[b] : make_int2(1, 0);
-    const int n_items = set_hdr.x;
-    const int4 *const entries = sorted + set_hdr.y;
-    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : 0; item < n_items;
-         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : 1) {
-    int pencil, sb, se;
-    if constexpr (OVERFLOW) {
-        const int4 it = tickets ? entries[item] : listed_item(entries, item, n_items);
-        pencil = it.x - b * pencils;
-        sb = it.y;
-        se = it.z;
-    } else {
-        range_of_block(nsegm, seg_slabs, M, pencil, sb, se);
-    }
+    const int2 set_hdr = ((const int2 *)(work + 1))[b];
+    const int n_items = __builtin_amdgcn_readfirstlane(set_hdr.x);
+    const int4 *const entries = sorted + __builtin_amdgcn_readfirstlane(set_hdr.y);
+    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : (int)blockIdx.x; item < n_items;
+         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : n_items) {
+    const int4 it = OVERFLOW && !tickets ? listed_item(entries, item, n_items) : entries[item];
+    // (the entry is the same for every lane: say so -- a load the compiler cannot prove unclobbered lands in vector registers)
+    const int pencil = __builtin_amdgcn_readfirstlane(it.x) - b * pencils, sb = __builtin_amdgcn_readfirstlane(it.y),
+              se = __builtin_amdgcn_readfirstlane(it.z);
     if (se <= sb) continue;
     const int bin0 = b * g.tiles_per_batch + pencil * g.np0;  // one plan bin per slab
     const int p_begin = tile_offsets[bin0 + sb], p_end = tile_offsets[bin0 + se];
@@ -326,7 +321,7 @@ int launch_interp_cols(const Geom &g, const PlanLayout &L, const void *plan, con
         return launch_range_kernels<interp_cols_kernel<W, false>, interp_cols_kernel<W, true>>(
             g, L, plan, n, ngroups, sizeof(IcLds), tickets, [&](auto kernel, dim3 blocks, const RangeArgs &a) {
                 hipLaunchKernelGGL(kernel, blocks, dim3(kIcThreads), sizeof(IcLds), stream, g, a.tile_offsets, a.spos, grid,
-                                   (int)Cr, plane0, nplanes, group0, yr, a.seg_slabs, a.nsegm, a.work, a.sorted, a.tickets);
+                                   (int)Cr, plane0, nplanes, group0, yr, a.work, a.sorted, a.tickets);
             });
     });
 }

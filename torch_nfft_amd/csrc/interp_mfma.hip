@@ -41,7 +41,7 @@ template <int W, bool OVERFLOW>
 __global__ void __launch_bounds__(kGmThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
 interp_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets,
                    const float *__restrict__ spos, const float *__restrict__ grid, const int Cr, const int plane0,
-                   float *__restrict__ yr, const int seg_slabs, const int nsegm, const int4 *__restrict__ work, const int4 *__restrict__ sorted, int *tickets)
+                   float *__restrict__ yr, const int4 *__restrict__ work, const int4 *__restrict__ sorted, int *tickets)
 {
     constexpr int m = W / 2 - 1;
     constexpr int TC = 17 - W;
@@ -61,24 +61,19 @@ interp_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets,
     const int cr = plane - b * Cr;
     const int pencils = g.nta[1] * g.nta[2];
 
-    // ---- work items (range_items.h): the ranges of slabs of the spreading kernel, or the entries of the plan's work
-    // list; an item owns the chunks whose first slab lies in its range.
+    // ---- work items (range_items.h): the entries of the plan's work list, the ranges of slabs of the spreading kernel;
+    // an item owns the chunks whose first slab lies in its range.
     if (!plan_launch<OVERFLOW>(work)) return;
-    const WorkItems items = work_items<OVERFLOW>(work, sorted, b);
+    const WorkItems items = work_items(work, sorted, b);
     const int n_items = items.n;
     const int4 *const entries = items.entries;
-    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : 0; item < n_items;
-         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : 1) {
+    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : (int)blockIdx.x; item < n_items;
+         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : n_items) {
     if (OVERFLOW && item != (int)blockIdx.x) __syncthreads();  // the previous item is done with the LDS
-    int pencil, sb, se;
-    if constexpr (OVERFLOW) {
-        const int4 it = tickets ? entries[item] : listed_item(entries, item, n_items);
-        pencil = it.x - b * pencils;
-        sb = it.y;
-        se = it.z;
-    } else {
-        range_of_block(nsegm, seg_slabs, g.M, pencil, sb, se);
-    }
+    const int4 it = OVERFLOW && !tickets ? listed_item(entries, item, n_items) : entries[item];
+    // (the entry is the same for every lane: say so -- a load the compiler cannot prove unclobbered lands in vector registers)
+    const int pencil = __builtin_amdgcn_readfirstlane(it.x) - b * pencils, sb = __builtin_amdgcn_readfirstlane(it.y),
+              se = __builtin_amdgcn_readfirstlane(it.z);
     const int j2 = pencil % g.nta[2];
     const int j1 = pencil / g.nta[2];
     const int k_begin = (sb + TC - 1) / TC;
@@ -271,7 +266,7 @@ int launch_interp_mfma(const Geom &g, const PlanLayout &L, const void *plan, con
         return launch_range_kernels<interp_mfma_kernel<W, false>, interp_mfma_kernel<W, true>>(
             g, L, plan, n, nplanes, sizeof(GatherMfmaLds), tickets, [&](auto kernel, dim3 blocks, const RangeArgs &a) {
                 hipLaunchKernelGGL(kernel, blocks, dim3(kGmThreads), sizeof(GatherMfmaLds), stream, g, a.tile_offsets, a.spos,
-                                   grid, (int)Cr, (int)plane0, yr, a.seg_slabs, a.nsegm, a.work, a.sorted, a.tickets);
+                                   grid, (int)Cr, (int)plane0, yr, a.work, a.sorted, a.tickets);
             });
     });
 }

@@ -34,6 +34,30 @@
 
 namespace nfft {
 
+#ifdef NFFT_HIP_TRACE
+// Developer instrumentation (variant builds only, scripts/exp_build.sh -DNFFT_HIP_TRACE), in the layout of the spreading
+// kernel's (spread_mfma.hip, scripts/spread_trace.py): eight 64-bit words per workgroup of the per-entry launch -- 100 MHz
+// real-time stamps at entry [0, 1], after the item's set-up [2], when the last wave is done [3, 6], the hardware id of the
+// CU [4], the item's block and point counts [5].
+__device__ unsigned long long *g_stream_trace = nullptr;
+#define NFFT_GTRACE_AT(slot) (&g_stream_trace[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (slot)])
+#define NFFT_GTRACE(slot, value)                                                                                  \
+    do {                                                                                                          \
+        if (!OVERFLOW && threadIdx.x == 0 && g_stream_trace) *NFFT_GTRACE_AT(slot) = (value);                     \
+    } while (0)
+#define NFFT_GTRACE_END()                                                                                         \
+    do {                                                                                                          \
+        if (!OVERFLOW && lane == 0 && g_stream_trace) {                                                           \
+            const unsigned long long now_ = __builtin_amdgcn_s_memrealtime();                                     \
+            atomicMax(NFFT_GTRACE_AT(3), now_);                                                                   \
+            atomicMax(NFFT_GTRACE_AT(6), now_);                                                                   \
+        }                                                                                                         \
+    } while (0)
+#else
+#define NFFT_GTRACE(slot, value) do { } while (0)
+#define NFFT_GTRACE_END() do { } while (0)
+#endif
+
 namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -43,7 +67,7 @@ constexpr int kIsWaves = kIsThreads / 64;
 constexpr int kIsProducers = 4;      // measured at C3: 3 producers 1.50 ms, 4: 1.41, 5: 1.50 (each owns 16 / 4 ring slots)
 constexpr int kIsConsumers = kIsWaves - kIsProducers;
 constexpr int kIsRing = 16;          // resident planes: TC + 2m+1 = 16 for every cutoff of the wide tiling
-constexpr int kIsMaxSlabs = 160;     // slabs the chunks of one work item cover (<= 128 + 2 TC)
+constexpr int kIsMaxSlabs = 160;     // slabs the chunks of one work item cover (<= kItemMaxSlabs + 2 TC)
 constexpr int kIsMaxRuns = 3 * kIsMaxSlabs;
 #ifndef NFFT_HIP_SPIN_LIMIT
 #define NFFT_HIP_SPIN_LIMIT (1 << 22)
@@ -96,7 +120,7 @@ template <int W, bool OVERFLOW, int NG>
 __global__ void __launch_bounds__(kIsThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
 interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const int *__restrict__ group_starts,
                      const float *__restrict__ spos, const float *__restrict__ grid,
-                     const int Cr, const int plane0, float *__restrict__ yr, const int seg_slabs, const int nsegm,
+                     const int Cr, const int plane0, float *__restrict__ yr,
                      const int4 *__restrict__ work, const int4 *__restrict__ sorted, int *tickets, int *__restrict__ status)
 {
     constexpr int m = W / 2 - 1;
@@ -105,7 +129,7 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
     constexpr int SPAN = TC + W - 1;                             // planes a chunk's blocks may touch
     constexpr int NKS = NG == 3 ? 2 : 4;  // k-steps of a block
     static_assert(TC >= 1 && SPAN <= kIsRing, "the ring holds a chunk's planes");
-    static_assert(128 + 2 * TC <= kIsMaxSlabs, "run tables");
+    static_assert(kItemMaxSlabs + 2 * TC <= kIsMaxSlabs, "run tables");
     extern __shared__ __align__(16) unsigned char smem_raw[];
     StreamLds &L = *reinterpret_cast<StreamLds *>(smem_raw);
 
@@ -113,6 +137,9 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r32 = lane & 31, h = lane >> 5;
+    NFFT_GTRACE(0, __builtin_amdgcn_s_memrealtime());
+    NFFT_GTRACE(1, __builtin_amdgcn_s_memrealtime());
+    NFFT_GTRACE(4, (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32));
 
     const int plane_local = blockIdx.y;
     const int plane = plane0 + plane_local;
@@ -123,20 +150,15 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
 
     // work items (range_items.h)
     if (!plan_launch<OVERFLOW>(work)) return;
-    const WorkItems items = work_items<OVERFLOW>(work, sorted, b);
+    const WorkItems items = work_items(work, sorted, b);
     const int n_items = items.n;
     const int4 *const entries = items.entries;
-    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : 0; item < n_items;
-         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : 1) {
-    int pencil, sb, se;
-    if constexpr (OVERFLOW) {
-        const int4 it = tickets ? entries[item] : listed_item(entries, item, n_items);
-        pencil = it.x - b * pencils;
-        sb = it.y;
-        se = it.z;
-    } else {
-        range_of_block(nsegm, seg_slabs, M, pencil, sb, se);
-    }
+    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : (int)blockIdx.x; item < n_items;
+         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : n_items) {
+    const int4 it = OVERFLOW && !tickets ? listed_item(entries, item, n_items) : entries[item];
+    // (the entry is the same for every lane: say so -- a load the compiler cannot prove unclobbered lands in vector registers)
+    const int pencil = __builtin_amdgcn_readfirstlane(it.x) - b * pencils, sb = __builtin_amdgcn_readfirstlane(it.y),
+              se = __builtin_amdgcn_readfirstlane(it.z);
     // an item owns the chunks whose first slab lies in its range (as in interp_mfma.hip)
     const int k_begin = (sb + TC - 1) / TC;
     const int k_end = min((M + TC - 1) / TC, (se + TC - 1) / TC);
@@ -193,6 +215,8 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
     }
     __syncthreads();
     const int total_blocks = L.run_blk[nruns];
+    NFFT_GTRACE(2, __builtin_amdgcn_s_memrealtime());
+    NFFT_GTRACE(5, (unsigned long long)(unsigned)total_blocks | ((unsigned long long)(unsigned)(L.run_start[nruns] - L.run_start[0]) << 32));
 
     if (wave >= kIsConsumers) {
         // ================================ producer: planes z = z_begin + p, + 4, ... ================================
@@ -500,10 +524,18 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
         lds_release();
         if (lane == 0) lds_store(&L.progress[wave], INT_MAX);
     }
+    NFFT_GTRACE_END();
     }  // work items
 }
 
 } // namespace
+
+#ifdef NFFT_HIP_TRACE
+extern "C" int nfft_dbg_set_stream_trace(void *device_buffer)
+{
+    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stream_trace), &device_buffer, sizeof(device_buffer));
+}
+#endif
 
 bool interp_stream_pays(const Geom &g, const PlanLayout &L, int64_t n)
 {
@@ -522,7 +554,7 @@ int launch_interp_stream(const Geom &g, const PlanLayout &L, const void *plan, c
         int *const status = device_status_block();
         const auto launch = [&](auto kernel, dim3 blocks, const RangeArgs &a) {
             hipLaunchKernelGGL(kernel, blocks, dim3(kIsThreads), sizeof(StreamLds), stream, g, a.tile_offsets, gs, a.spos, grid,
-                               (int)Cr, (int)plane0, yr, a.seg_slabs, a.nsegm, a.work, a.sorted, a.tickets, status);
+                               (int)Cr, (int)plane0, yr, a.work, a.sorted, a.tickets, status);
         };
         return L.grouped ? launch_range_kernels<interp_stream_kernel<W, false, 3>, interp_stream_kernel<W, true, 3>>(
                                g, L, plan, n, nplanes, sizeof(StreamLds), tickets, launch)

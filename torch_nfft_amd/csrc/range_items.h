@@ -1,14 +1,16 @@
 // What the matrix-core kernels of the wide tiling share: spread_mfma_kernel (spread_mfma.hip), interp_mfma_kernel
 // (interp_mfma.hip), interp_cols_kernel (interp_cols.hip) and interp_stream_kernel (interp_stream.hip) sweep work items
-// -- ranges of slabs of a pencil -- in one split of the work (range_split), from one pair of launches
-// (launch_range_kernels), through one work-item frame on the device (plan_launch, work_items, range_of_block).
+// -- ranges of slabs of a pencil -- that they all take from ONE place, the plan's work list in launch order (common.h,
+// plan layout; binning.hip segment_split_kernel / work_order_kernel), from one pair of launches (launch_range_kernels),
+// through one work-item frame on the device (plan_launch, work_items).
 //
-// The two launches.  A plan of the wide tiling is either balanced (common.h, plan layout): one workgroup per range, in
-// grid order, decodes its range from blockIdx.x -- or it walks its work list: ONE persistent launch per plane takes the
-// entries of its point set's part of the sorted list, biggest first.  Both launches are always enqueued, the per-range
-// one first, on the same stream with the same gridDim.y; the one that is not the plan's returns at once (work[0].z
-// says which).  Each kernel is instantiated for both (template flag OVERFLOW: the persistent form), because the item
-// loop costs registers.
+// The two launches.  A balanced plan runs one workgroup per list entry: workgroup blockIdx.x takes entry blockIdx.x of
+// its point set's part of the list, straight-line code without an item loop.  The dispatcher starts workgroups in grid
+// order as CUs fall free, so the list's order is the launch order: the grid order of the equal cut, or biggest first
+// (longest-first scheduling for free).  Any other plan walks the same list with ONE persistent launch per plane.  Both
+// launches are always enqueued, the per-entry one first, on the same stream with the same gridDim.y; the one that is
+// not the plan's returns at once (work[0].z says which).  Each kernel is instantiated for both (template flag OVERFLOW:
+// the persistent form), because the item loop costs registers.
 #pragma once
 #include <cassert>
 
@@ -16,20 +18,18 @@
 
 namespace nfft {
 
-// How a call's pencils are cut into ranges of slabs: seg_base_runs ranges of seg_slabs slabs per pencil (the last one
-// may be shorter).  Computed here only: the plan's work list (binning.hip launch_segment_split) is built for it, and
-// every launch over that plan must find the same ranges.
+// What the host knows of a call's work items without reading the plan: the items of an average pencil (seg_base_runs),
+// from which the plan's list is cut (binning.hip launch_segment_split) and the launches are sized.  The ranges
+// themselves exist in the plan's list only.
 struct RangeSplit {
     int64_t pencils;  // pencils per point set
     int64_t nsets;    // point sets (>= 1)
-    int nsegm;        // ranges per pencil
-    int seg_slabs;    // slabs per range
+    int runs;         // items of an average pencil
 };
 inline RangeSplit range_split(const Geom &g, int64_t n, int64_t B)
 {
     const int64_t pencils = (int64_t)g.nta[1] * g.nta[2], nsets = B > 0 ? B : 1;
-    const int runs = seg_base_runs(n, nsets, pencils, g.M, device_cu_count());
-    return RangeSplit{pencils, nsets, runs, (g.M + runs - 1) / runs};
+    return RangeSplit{pencils, nsets, seg_base_runs(n, nsets, pencils, g.M, device_cu_count())};
 }
 // ... at launch time, for the plan L of n points: its point-set count is ntiles / tiles_per_batch, because a plan of the
 // wide tiling has no sub-blocks (common.h make_geom: they exist for the register-tile spreading mode only, the wide
@@ -40,16 +40,15 @@ inline RangeSplit range_split(const Geom &g, const PlanLayout &L, int64_t n)
     return range_split(g, n, g.tiles_per_batch > 0 ? L.ntiles / g.tiles_per_batch : 1);
 }
 
-// What the launcher hands to a range kernel's launch: the plan arrays and the work decomposition
+// What the launcher hands to a range kernel's launch: the plan arrays and the work list
 struct RangeArgs {
     const int *tile_offsets;
     const float *spos;
-    int seg_slabs, nsegm;
-    const int4 *work, *sorted;  // the plan's work list and its copy in launch order
+    const int4 *work, *sorted;  // the plan's work list (header) and its entries in launch order
     int *tickets;               // counters of the persistent launch (next_work_item), or nullptr: round robin
 };
 
-// Host side of the range kernels: launch(kernel, blocks, args) enqueues `kernel` (BALANCED: one workgroup per range;
+// Host side of the range kernels: launch(kernel, blocks, args) enqueues `kernel` (BALANCED: one workgroup per list entry;
 // LISTED: the persistent form) with the grid `blocks`.  ny = gridDim.y: planes, pair slots or column groups.  The
 // kernels take up to `lds` bytes of dynamic LDS (one workgroup per CU: raised once per device).  `tickets`: kTicketPlanes
 // ints of the caller's workspace; the persistent launch hands its entries out by tickets when its planes fit them, else
@@ -67,10 +66,11 @@ int launch_range_kernels(const Geom &g, const PlanLayout &L, const void *plan, i
     }
     const char *base = (const char *)plan;
     const int4 *work = (const int4 *)(base + L.off_work);
-    const RangeArgs a{(const int *)(base + L.off_offsets), (const float *)(base + L.off_spos), s.seg_slabs, s.nsegm, work,
+    const RangeArgs a{(const int *)(base + L.off_offsets), (const float *)(base + L.off_spos), work,
                       work + L.work_head + L.work_cap, ny > kTicketPlanes ? nullptr : tickets};
-    launch(BALANCED, dim3((unsigned)(s.pencils * s.nsegm), (unsigned)ny), a);
-    launch(LISTED, dim3(work_list_workgroups(n, s.nsets, s.pencils, s.nsegm, device_cu_count()), (unsigned)ny), a);
+    const int64_t per_entry = std::min<int64_t>(per_entry_workgroups(n, s.nsets, s.pencils, s.runs, g.M, device_cu_count()), L.work_cap);
+    launch(BALANCED, dim3((unsigned)per_entry, (unsigned)ny), a);
+    launch(LISTED, dim3(work_list_workgroups(n, s.nsets, s.pencils, s.runs, device_cu_count()), (unsigned)ny), a);
     NFFT_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -121,29 +121,19 @@ __device__ __forceinline__ bool plan_launch(const int4 *work)
     return OVERFLOW ? listed : !listed;
 }
 
-// The items of the launch for point set b: the persistent form walks the set's part of the sorted list, n entries from
-// `entries` (set header b = {entries, first entry}); the per-range form has one item, its range.
+// The items of the launch for point set b: its part of the sorted list, n entries from `entries` (set header b =
+// {entries, first entry}).  The persistent form walks them (next_work_item); workgroup blockIdx.x of the per-entry form
+// has one, entry blockIdx.x, and none if the set has fewer entries (it returns before it touches its LDS).  (The decode of
+// an entry {point set * pencils + pencil, sb, se, points} is written out in the kernels: as a helper it changed their code.)
 struct WorkItems {
     int n;
     const int4 *entries;
 };
-template <bool OVERFLOW>
 __device__ __forceinline__ WorkItems work_items(const int4 *work, const int4 *sorted, const int b)
 {
-    const int2 set_hdr = OVERFLOW ? ((const int2 *)(work + 1))[b] : make_int2(1, 0);
-    return WorkItems{set_hdr.x, sorted + set_hdr.y};
-}
-
-// The range of a workgroup of the per-range form: blockIdx.x -> pencil and its slabs [sb, se) (nsegm ranges of
-// seg_slabs slabs per pencil, M slabs).  (The persistent form takes them from its list entry {point set * pencils +
-// pencil, sb, se, points}; that decode is written out in the kernels: as a helper it changed their code.)
-__device__ __forceinline__ void range_of_block(const int nsegm, const int seg_slabs, const int M, int &pencil, int &sb,
-                                               int &se)
-{
-    pencil = (int)blockIdx.x / nsegm;
-    const int seg = (int)blockIdx.x - pencil * nsegm;
-    sb = min(seg * seg_slabs, M);
-    se = min(sb + seg_slabs, M);
+    // (the same for every lane: say so -- a load the compiler cannot prove unclobbered lands in vector registers)
+    const int2 set_hdr = ((const int2 *)(work + 1))[b];
+    return WorkItems{__builtin_amdgcn_readfirstlane(set_hdr.x), sorted + __builtin_amdgcn_readfirstlane(set_hdr.y)};
 }
 
 #endif // __HIPCC__

@@ -83,7 +83,7 @@ constexpr int kKB = 16;        // points per K-block (the MFMA K dimension; the 
 constexpr int kNKB = 8;        // K-blocks per batch
 constexpr int kSlots = kKB * kNKB;
 constexpr int kMfmaThreads = 1024;
-constexpr int kMaxSegSlabs = 128;   // planes of one work item (a range of M / runs slabs or a piece of it)
+constexpr int kMaxSegSlabs = kItemMaxSlabs;  // planes of one work item (common.h: the plan cuts no longer one)
 constexpr int kMaxSweep = kMaxSegSlabs + 2 * kMaxCutoff;  // slabs it sweeps: the owned variant adds 2m+1 halo slabs
 constexpr float kPsiScale = 16.0f;  // psi1 <= 1 enters its f16 split times 16: psi1 * (x' psi0 * 2^11) <= 2^15 fits f16, and the
                                     // lo parts of the three central taps on either side are normal f16 numbers
@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_
 spread_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets, const float *__restrict__ spos,
                    const float *__restrict__ xr, const float *__restrict__ xs, const int64_t xs_stride,
                    const unsigned *__restrict__ xmax, const int Cr,
-                   const int plane0, const int nplanes, float *__restrict__ grid, const int seg_slabs, const int nsegm,
+                   const int plane0, const int nplanes, float *__restrict__ grid,
                    const int4 *__restrict__ work, const int4 *__restrict__ sorted, int *tickets, int *__restrict__ status)
 {
     static_assert(!PAIR || OWNED, "the paired variant is an owner-computes kernel");
@@ -181,24 +181,19 @@ spread_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets, const flo
     const int cr = plane - b * Cr;
     const int pencils = g.nta[1] * g.nta[2];
 
-    // ---- work items (range_items.h): straight-line code for the range of a balanced plan's workgroup, else a walk of
-    // the plan's work list, biggest items first
+    // ---- work items (range_items.h): straight-line code for the list entry of a balanced plan's workgroup, else a walk
+    // of the plan's work list, biggest items first
     if (!plan_launch<OVERFLOW>(work)) return;
-    const WorkItems items = work_items<OVERFLOW>(work, sorted, b);
+    const WorkItems items = work_items(work, sorted, b);
     const int n_items = items.n;
     const int4 *const entries = items.entries;
-    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : 0; item < n_items;
-         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : 1) {
+    for (int item = OVERFLOW ? next_work_item(tickets, &L.ticket, -1) : (int)blockIdx.x; item < n_items;
+         item = OVERFLOW ? next_work_item(tickets, &L.ticket, item) : n_items) {
     if (OVERFLOW && item != (int)blockIdx.x) __syncthreads();  // the previous item is done with the LDS
-    int pencil, sb, se;
-    if constexpr (OVERFLOW) {
-        const int4 it = tickets ? entries[item] : listed_item(entries, item, n_items);
-        pencil = it.x - b * pencils;
-        sb = it.y;
-        se = it.z;
-    } else {
-        range_of_block(nsegm, seg_slabs, g.M, pencil, sb, se);
-    }
+    const int4 it = OVERFLOW && !tickets ? listed_item(entries, item, n_items) : entries[item];
+    // (the entry is the same for every lane: say so -- a load the compiler cannot prove unclobbered lands in vector registers)
+    const int pencil = __builtin_amdgcn_readfirstlane(it.x) - b * pencils, sb = __builtin_amdgcn_readfirstlane(it.y),
+              se = __builtin_amdgcn_readfirstlane(it.z);
     const int j2 = pencil % g.nta[2];
     const int j1 = pencil / g.nta[2];
     const int nplane = se - sb;  // planes (scatter variant: slabs) of this item
@@ -322,7 +317,8 @@ spread_mfma_kernel(const Geom g, const int *__restrict__ tile_offsets, const flo
             // wrapped row offsets of the boundary pencils above all -- is then computed HERE, once per flush, instead of being
             // hoisted out of the K-block loop into ~35 registers the kernel does not have: it sat at the 128-VGPR limit with
             // 15 VGPRs and 62 SGPRs spilled to scratch until round 4)
-            int o1 = tb1 - m, o2 = tb2 - m, M = g.M, hh = h, rr = r32;
+            // (the tile origin comes out of an integer division, i.e. of vector instructions: name it uniform for the "s" operands)
+            int o1 = __builtin_amdgcn_readfirstlane(tb1 - m), o2 = __builtin_amdgcn_readfirstlane(tb2 - m), M = g.M, hh = h, rr = r32;
             asm volatile("" : "+s"(o1), "+s"(o2), "+s"(M), "+v"(hh), "+v"(rr));
             const int gz = wrap(myz, M);
             const float zscale = ((myz + m) & 1) ? -unscale : unscale;  // plane s - m + l0: parity of s + l0 + m
@@ -845,8 +841,8 @@ static int launch_mfma_t(const Geom &g, const PlanLayout &L, const void *plan, c
                          const unsigned *xmax, int64_t n, int64_t Cr, int64_t plane0, int64_t nplanes, float *grid,
                          int *tickets, hipStream_t stream)
 {
-    // Ranges per pencil (range_split): about 5-6 workgroups per CU balance the tail of the launch against the 2m+1 halo
-    // planes every range flushes on top of its own (measured at C3: 6 ranges 7 % faster than 4, 12 in between).
+    // Items per pencil (common.h): about 5-6 workgroups per CU balance the tail of the launch against the 2m+1 halo
+    // planes every item flushes on top of its own (measured at C3: 6 equal ranges 7 % faster than 4, 12 in between).
     // y grid: planes, or the pair slots the chunk of planes touches (paired variant)
     int64_t ny = nplanes;
     if (PAIR) {
@@ -860,7 +856,7 @@ static int launch_mfma_t(const Geom &g, const PlanLayout &L, const void *plan, c
     return launch_range_kernels<spread_mfma_kernel<W, false, OWNED, PAIR>, spread_mfma_kernel<W, true, OWNED, PAIR>>(
         g, L, plan, n, ny, lds, tickets, [&](auto kernel, dim3 blocks, const RangeArgs &a) {
             hipLaunchKernelGGL(kernel, blocks, dim3(kMfmaThreads), lds, stream, g, a.tile_offsets, a.spos, xr, xs, L.cap, xmax,
-                               (int)Cr, (int)plane0, (int)nplanes, grid, a.seg_slabs, a.nsegm, a.work, a.sorted, a.tickets, status);
+                               (int)Cr, (int)plane0, (int)nplanes, grid, a.work, a.sorted, a.tickets, status);
         });
 }
 
