@@ -35,7 +35,7 @@ extern "C" {
 #define NFFT_HIP_EHIP 4       /* HIP runtime error (reference aborts the process, cuda_utils.cu:7-14; we report) */
 #define NFFT_HIP_EKERNEL 5    /* a kernel of an earlier call on this device reported a fault (nfft_hip_check_status) */
 
-#define NFFT_HIP_ABI_VERSION 5
+#define NFFT_HIP_ABI_VERSION 6
 
 int nfft_hip_abi_version(void);
 const char *nfft_hip_last_error(void);
@@ -285,6 +285,51 @@ int nfft_hip_toeplitz_kernel(const nfft_hip_problem *p, const void *t, float *K,
 int64_t nfft_hip_toeplitz_workspace_bytes(const nfft_hip_problem *p);
 int nfft_hip_toeplitz_apply(const nfft_hip_problem *p, const float *K, const void *xhat, int x_is_complex, void *y,
                             void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- near field of the fast summation for singular kernels (no reference counterpart) ----
+ * The fast summation is exact only for kernels that are smooth on the torus.  For K(r) = 1/r, log r, ... the host side
+ * sums a regularised kernel K_R with nfft_hip_fastsum -- K replaced inside the radius eps_I by the even polynomial
+ * T_I(r) = sum_{k < poly_terms} poly[k] (r / eps_I)^(2k) that matches its derivatives at eps_I -- and this entry point adds
+ *     z[i, c] = sum_{j in the point set of i, |t_i - s_j| < eps_I} (K(r_ij) - T_I(r_ij)) xr[j, c],   r_ij = |t_i - s_j|
+ * (Euclidean, not periodic: the points lie in the quarter ball).  A pair with r = 0 contributes K(0) - poly[0] for the
+ * kernels that are finite at 0 and -poly[0] for 1/r, 1/r^2 and log r: the singular self term is left out of the sum.
+ *
+ * Both point sets come ORDERED BY CELL: cells_per_axis^dim cubes of edge 1 / (2 cells_per_axis) >= eps_I over
+ * [-1/4, 1/4]^dim, cell index c_0 + G c_1 + G^2 c_2 with c_a = clamp(floor((pos_a + 1/4) 2 G), 0, G - 1), key =
+ * point set * G^dim + cell; the caller sorts by key (stably) and passes
+ *   sources [n_s, dim] float32, xr [n_s, Cr] float32 (real columns; re, im interleaved for complex data) in that order
+ *   source_start / target_start  int32 [batch_size * G^dim + 1]: index of the first point with key >= entry
+ *   targets [n_t, dim] float32 in that order, target_index int64 [n_t]: the row of z that sorted target i writes
+ *   z [n_t, Cr] float32: row target_index[i] is written for every target whose key lies in the table
+ * nfft_hip_nearfield_cells proposes cells_per_axis: the most cells with edge >= eps_I, at most 2^20 in all point sets.
+ * No atomics: a target's pairs are added in the order of the sorted sources, two calls give the same bits.  No targets or
+ * no columns: nothing is done; no sources: z is zeroed.  Workspace: the work items (blocks of targets of one cell). */
+#define NFFT_HIP_KERNEL_ONE_OVER_MODULUS 0     /* 1 / r */
+#define NFFT_HIP_KERNEL_ONE_OVER_SQUARE 1      /* 1 / r^2 */
+#define NFFT_HIP_KERNEL_LOGARITHM 2            /* log r */
+#define NFFT_HIP_KERNEL_THINPLATE_SPLINE 3     /* r^2 log r */
+#define NFFT_HIP_KERNEL_MULTIQUADRIC 4         /* sqrt(r^2 + c^2) */
+#define NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC 5 /* 1 / sqrt(r^2 + c^2) */
+#define NFFT_HIP_KERNEL_GAUSSIAN 6             /* exp(-r^2 / c^2) */
+#define NFFT_HIP_KERNEL_LAPLACIAN_RBF 7        /* exp(-r / c) */
+typedef struct nfft_hip_nearfield_problem {
+    int32_t dim;            /* 1..3 */
+    int32_t kernel;         /* NFFT_HIP_KERNEL_* */
+    int32_t poly_terms;     /* p, 1..8 */
+    int32_t cells_per_axis; /* G >= 1 with 1 / (2 G) >= eps_I */
+    int64_t num_sources;
+    int64_t num_targets;
+    int64_t num_columns;    /* real columns Cr */
+    int64_t batch_size;
+    double c;               /* shape parameter (> 0 for the last three kernels, >= 0 for the multiquadric) */
+    double eps_I;
+    double poly[8];         /* a_0 .. a_{p-1} */
+} nfft_hip_nearfield_problem;
+int64_t nfft_hip_nearfield_cells(int32_t dim, double eps_I, int64_t batch_size);
+int64_t nfft_hip_nearfield_workspace_bytes(const nfft_hip_nearfield_problem *p);
+int nfft_hip_nearfield(const nfft_hip_nearfield_problem *p, const float *sources, const float *xr,
+                       const int32_t *source_start, const float *targets, const int64_t *target_index,
+                       const int32_t *target_start, float *z, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.

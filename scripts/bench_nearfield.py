@@ -1,0 +1,113 @@
+"""Times nfft_fastsum_nearfield's two halves (profiles/r09_nearfield.md):
+
+    python scripts/bench_nearfield.py [--points 100000] [--reps 10]
+
+3-D one_over_modulus, N = 64, p = 4 (eps_I = eps_B = 1/16), cutoff m = 4, shared points uniform in the ball of radius
+kern.max_radius, C = 1 and C = 4 real columns.  Device-event medians of `reps` calls after two warm-up calls:
+  far field     nfft_fastsum with kern.coeffs
+  near field    ops.nfft_nearfield as a whole, and its two parts on their own -- the plumbing (cell keys, one stable
+                sort, the start table, the gathers of the points and of x: the torch calls core.so makes, restated here)
+                and the pair loop (nfft_hip_nearfield through the C ABI on the arrays the plumbing made)
+  pairs         distance tests per call = sum over targets of the sources in the 3^3 cells around it, and per second of
+                the pair loop; `in range` counts those with r < eps_I
+One JSON line per column count.
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch_nfft_amd as tn  # noqa: E402
+from torch_nfft_amd import _lib  # noqa: E402
+
+
+def median_ms(fn, reps):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return float(np.median(times))
+
+
+def cell_order(pos, G):
+    """what core.so's cell_order does for one point set without a batch vector"""
+    cell = ((pos + 0.25) * float(2 * G)).floor().clamp(0, G - 1).to(torch.int64)
+    key = cell[:, 0] + cell[:, 1] * G + cell[:, 2] * (G * G)
+    skey, order = torch.sort(key, stable=True)
+    start = torch.searchsorted(skey, torch.arange(G ** 3 + 1, device=pos.device), out_int32=True)
+    return pos.index_select(0, order), order, start
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=int, default=100000)
+    ap.add_argument("--reps", type=int, default=10)
+    args = ap.parse_args()
+    torch.cuda.set_device(0)
+    lib = _lib.load()
+    N, p, m, n = 64, 4, 4, args.points
+    kern = tn.RegularizedKernel("one_over_modulus", dim=3, bandwidth=N, p=p)
+    rng = np.random.default_rng(0)
+    v = rng.standard_normal((n, 3))
+    v *= (kern.max_radius * rng.random((n, 1)) ** (1.0 / 3.0)) / np.linalg.norm(v, axis=1, keepdims=True)
+    pos = torch.from_numpy(v.astype(np.float32)).cuda()
+    G = int(lib.nfft_hip_nearfield_cells(3, kern.eps_I, 1))
+    # pairs tested: targets of a cell x sources of the 27 cells around it
+    cells = np.clip(np.floor((v.astype(np.float32) + 0.25) * (2 * G)), 0, G - 1).astype(np.int64)
+    count = np.zeros((G + 2,) * 3, dtype=np.int64)
+    np.add.at(count, (cells[:, 0] + 1, cells[:, 1] + 1, cells[:, 2] + 1), 1)
+    box = sum(count[1 + a:G + 1 + a, 1 + b:G + 1 + b, 1 + c:G + 1 + c] for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1))
+    pairs = int((count[1:-1, 1:-1, 1:-1] * box).sum())
+    sub = rng.choice(n, 2000, replace=False)
+    hits = sum(int((np.linalg.norm(v[sub[i:i + 100]][:, None, :] - v[None, :, :], axis=-1) < kern.eps_I).sum())
+               for i in range(0, 2000, 100))
+    in_range = int(hits * (n / 2000.0))
+    for C in (1, 4):
+        x = torch.from_numpy(rng.standard_normal((n, C)).astype(np.float32)).cuda()
+        poly = kern.near_poly.tolist()
+        far = median_ms(lambda: tn.nfft_fastsum(x, kern.coeffs, pos, cutoff=m), args.reps)
+        near = median_ms(lambda: tn.ops.nfft_nearfield(pos, pos, x, None, None, kern.kernel_id, kern.c, kern.eps_I, poly), args.reps)
+
+        def plumbing():
+            spos, order, start = cell_order(pos, G)
+            return spos, order, start, x.index_select(0, order), torch.zeros(n, C, device="cuda")
+
+        plumb = median_ms(plumbing, args.reps)
+        spos, order, start, xs, z = plumbing()
+        q = _lib.NearfieldProblem(dim=3, kernel=kern.kernel_id, poly_terms=p, cells_per_axis=G, num_sources=n, num_targets=n,
+                                  num_columns=C, batch_size=1, c=kern.c, eps_I=kern.eps_I)
+        for e, a in enumerate(poly):
+            q.poly[e] = a
+        nbytes = lib.nfft_hip_nearfield_workspace_bytes(ctypes.byref(q))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+        def loop():
+            _lib.check(lib.nfft_hip_nearfield(ctypes.byref(q), spos.data_ptr(), xs.data_ptr(), start.data_ptr(), spos.data_ptr(),
+                                              order.data_ptr(), start.data_ptr(), z.data_ptr(), ws.data_ptr(), nbytes, stream))
+
+        pair_loop = median_ms(loop, args.reps)
+        full = tn.ops.nfft_nearfield(pos, pos, x, None, None, kern.kernel_id, kern.c, kern.eps_I, poly)
+        assert torch.equal(full, z), "the restated plumbing must give the operator's bits"
+        tn.ops.check_status()
+        print(json.dumps({"bench": "nearfield", "kernel": kern.name, "N": N, "p": p, "m": m, "points": n, "columns": C,
+                          "cells_per_axis": G, "far_ms": round(far, 4), "near_ms": round(near, 4),
+                          "near_plumbing_ms": round(plumb, 4), "near_pair_loop_ms": round(pair_loop, 4),
+                          "pairs_tested": pairs, "pairs_in_range_estimate": in_range,
+                          "pairs_per_second": round(pairs / (pair_loop * 1e-3), 1)}))
+
+
+if __name__ == "__main__":
+    main()

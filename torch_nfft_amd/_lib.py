@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NFFT_HIP_LIB") or os.path.join(_HERE, "libnfft_hip.so")
 CORE_PATH = os.path.join(_HERE, "core.so")
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 POINTS_IN_QUARTER_BALL = 1
 
 # every symbol include/nfft_hip.h declares
@@ -49,6 +49,9 @@ SYMBOLS = (
     "nfft_hip_toeplitz_kernel",
     "nfft_hip_toeplitz_workspace_bytes",
     "nfft_hip_toeplitz_apply",
+    "nfft_hip_nearfield_cells",
+    "nfft_hip_nearfield_workspace_bytes",
+    "nfft_hip_nearfield",
     "nfft_hip_gaussian_analytic_coeffs",
     "nfft_hip_interpolation_grid",
     "nfft_hip_coeffs_workspace_bytes",
@@ -79,6 +82,23 @@ class Problem(ctypes.Structure):
 
     def __init__(self, dim=0, num_points=0, num_columns=0, batch_size=1, N=0, m=0, flags=0):
         super().__init__(dim, flags, num_points, num_columns, batch_size, N, m)
+
+
+class NearfieldProblem(ctypes.Structure):
+    """``nfft_hip_nearfield_problem`` of include/nfft_hip.h."""
+    _fields_ = [
+        ("dim", ctypes.c_int32),
+        ("kernel", ctypes.c_int32),
+        ("poly_terms", ctypes.c_int32),
+        ("cells_per_axis", ctypes.c_int32),
+        ("num_sources", ctypes.c_int64),
+        ("num_targets", ctypes.c_int64),
+        ("num_columns", ctypes.c_int64),
+        ("batch_size", ctypes.c_int64),
+        ("c", ctypes.c_double),
+        ("eps_I", ctypes.c_double),
+        ("poly", ctypes.c_double * 8),
+    ]
 
 
 _lib = None
@@ -162,6 +182,12 @@ def load():
     lib.nfft_hip_toeplitz_kernel.restype = ci
     lib.nfft_hip_toeplitz_apply.argtypes = [P, vp, vp, ci, vp, vp, i64, vp]
     lib.nfft_hip_toeplitz_apply.restype = ci
+    lib.nfft_hip_nearfield_cells.argtypes = [ctypes.c_int32, ctypes.c_double, i64]
+    lib.nfft_hip_nearfield_cells.restype = i64
+    lib.nfft_hip_nearfield_workspace_bytes.argtypes = [ctypes.POINTER(NearfieldProblem)]
+    lib.nfft_hip_nearfield_workspace_bytes.restype = i64
+    lib.nfft_hip_nearfield.argtypes = [ctypes.POINTER(NearfieldProblem), vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.nfft_hip_nearfield.restype = ci
     lib.nfft_hip_gaussian_analytic_coeffs.argtypes = [ctypes.c_double, i64, ctypes.c_int32, vp, vp]
     lib.nfft_hip_gaussian_analytic_coeffs.restype = ci
     lib.nfft_hip_interpolation_grid.argtypes = [i64, ctypes.c_int32, ci, vp, vp]

@@ -1446,3 +1446,88 @@ int nfft_hip_toeplitz_apply(const nfft_hip_problem *p, const float *K, const voi
 }
 
 } // extern "C"
+
+// ---- near field of the fast summation for singular kernels ------------------------------------
+namespace {
+constexpr int64_t kNearMaxCells = int64_t(1) << 20;
+
+int validate_nearfield(const nfft_hip_nearfield_problem *p)
+{
+    if (!p) { set_error("Input mismatch: null problem"); return NFFT_HIP_EINVAL; }
+    if (p->dim < 1 || p->dim > 3) { set_error("Input mismatch: dim must be 1, 2 or 3"); return NFFT_HIP_EINVAL; }
+    if (p->kernel < 0 || p->kernel > NFFT_HIP_KERNEL_LAPLACIAN_RBF) { set_error("Input mismatch: unknown kernel"); return NFFT_HIP_EINVAL; }
+    if (p->poly_terms < 1 || p->poly_terms > 8) { set_error("Input mismatch: poly_terms must be in 1..8"); return NFFT_HIP_EINVAL; }
+    if (p->num_sources < 0 || p->num_targets < 0 || p->num_columns < 0 || p->batch_size < 1) {
+        set_error("Input mismatch: negative size");
+        return NFFT_HIP_EINVAL;
+    }
+    if (p->num_sources >= (int64_t(1) << 31) || p->num_targets >= (int64_t(1) << 31)) {
+        set_error("Input mismatch: too many points");
+        return NFFT_HIP_EINVAL;
+    }
+    if (!(p->eps_I > 0.0) || !(p->eps_I < 0.5)) { set_error("Input mismatch: eps_I must lie in (0, 1/2)"); return NFFT_HIP_EINVAL; }
+    if (p->cells_per_axis < 1 || 0.5 / p->cells_per_axis < p->eps_I * (1.0 - 1e-12)) {
+        set_error("Input mismatch: cells must have an edge 1 / (2 cells_per_axis) >= eps_I");
+        return NFFT_HIP_EINVAL;
+    }
+    int64_t cells = p->batch_size;
+    for (int a = 0; a < p->dim && cells <= kNearMaxCells; ++a) cells *= p->cells_per_axis;
+    if (cells > kNearMaxCells && p->cells_per_axis > 1) { set_error("Input mismatch: too many cells"); return NFFT_HIP_EINVAL; }
+    if (cells >= (int64_t(1) << 30)) { set_error("Input mismatch: too many point sets"); return NFFT_HIP_EINVAL; }
+    const bool needs_c = p->kernel >= NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC;
+    if (!(p->c >= 0.0) || (needs_c && !(p->c > 0.0))) { set_error("Input mismatch: the shape parameter c must be positive"); return NFFT_HIP_EINVAL; }
+    for (int e = 0; e < p->poly_terms; ++e)
+        if (!(p->poly[e] == p->poly[e]) || p->poly[e] > 3e38 || p->poly[e] < -3e38) {
+            set_error("Input mismatch: poly is not finite");
+            return NFFT_HIP_EINVAL;
+        }
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int64_t nfft_hip_nearfield_cells(int32_t dim, double eps_I, int64_t batch_size)
+{
+    if (dim < 1 || dim > 3 || !(eps_I > 0.0) || !(eps_I < 0.5) || batch_size < 1) {
+        set_error("Input mismatch: nearfield cells need dim in 1..3, eps_I in (0, 1/2) and batch_size >= 1");
+        return -1;
+    }
+    int64_t G = (int64_t)std::min(0.5 / eps_I, 1048576.0);
+    while (G > 1 && 0.5 / (double)G < eps_I) --G;  // (the quotient may have been rounded up)
+    auto cells = [&](int64_t g) { int64_t c = batch_size; for (int a = 0; a < dim; ++a) c *= g; return c; };
+    while (G > 1 && cells(G) > kNearMaxCells) G = G > 64 ? G / 2 : G - 1;
+    return G < 1 ? 1 : G;
+}
+
+int64_t nfft_hip_nearfield_workspace_bytes(const nfft_hip_nearfield_problem *p)
+{
+    if (validate_nearfield(p)) return -1;
+    return nearfield_item_slots(p) * (int64_t)sizeof(int2) + 256;
+}
+
+int nfft_hip_nearfield(const nfft_hip_nearfield_problem *p, const float *sources, const float *xr,
+                       const int32_t *source_start, const float *targets, const int64_t *target_index,
+                       const int32_t *target_start, float *z, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_nearfield(p)) return rc;
+    if (p->num_targets == 0 || p->num_columns == 0) return 0;
+    if (!z) { set_error("Input mismatch: z is null"); return NFFT_HIP_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    if (p->num_sources == 0) {
+        NFFT_HIP_CHECK(hipMemsetAsync(z, 0, (size_t)(p->num_targets * p->num_columns) * sizeof(float), s));
+        return 0;
+    }
+    if (!sources || !xr || !source_start || !targets || !target_index || !target_start) {
+        set_error("Input mismatch: null input");
+        return NFFT_HIP_EINVAL;
+    }
+    const int64_t need = nearfield_item_slots(p) * (int64_t)sizeof(int2) + 256;
+    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    return launch_nearfield(p, sources, xr, source_start, targets, target_index, target_start, z, ws, s);
+}
+
+}  // extern "C"

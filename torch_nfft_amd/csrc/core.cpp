@@ -733,6 +733,87 @@ at::Tensor nfft_normal(at::Tensor kernel, at::Tensor x)
     return y;
 }
 
+// ---- near field of the fast summation for singular kernels (not in the reference) --------------
+// A point set ordered by (point set, cell) for nfft_hip_nearfield: the key of include/nfft_hip.h, one stable sort and the
+// first point of every cell by a sorted search.  Device work on the current stream only: no read-back.
+struct CellOrder {
+    at::Tensor pos, order, start;  // [n, dim] float32 in cell order; [n] int64: the caller's row; [B G^dim + 1] int32
+};
+
+CellOrder cell_order(const Points &p, int64_t G, int64_t cells_per_set)
+{
+    const at::Tensor cell = ((p.pos + 0.25) * (double)(2 * G)).floor().clamp(0, G - 1).to(at::kLong);
+    at::Tensor key = cell.select(1, 0);
+    int64_t stride = G;
+    for (int a = 1; a < p.dim; ++a, stride *= G) key = key + cell.select(1, a) * stride;
+    if (p.batch.defined()) key = key + p.batch * cells_per_set;
+    const auto sorted = at::sort(key, /*stable=*/true, /*dim=*/0, /*descending=*/false);
+    CellOrder o;
+    o.order = std::get<1>(sorted);
+    o.start = at::searchsorted(std::get<0>(sorted), at::arange(p.B * cells_per_set + 1, key.options()), /*out_int32=*/true);
+    o.pos = p.pos.index_select(0, o.order);
+    return o;
+}
+
+// z[i] = sum_{j: same point set, |t_i - s_j| < eps_I} (K(r_ij) - T_I(r_ij)) x[j]; x's type and trailing shape
+at::Tensor nfft_nearfield(at::Tensor sources, at::Tensor targets, at::Tensor x, c10::optional<at::Tensor> opt_source_batch,
+                          c10::optional<at::Tensor> opt_target_batch, int64_t kernel, double c, double eps_I,
+                          at::ArrayRef<double> poly)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_nearfield is currently only implemented for GPU tensors");
+    const Points ps = check_points(sources, opt_source_batch, "(*out_batch)");
+    const bool same_batch = (!opt_source_batch.has_value() && !opt_target_batch.has_value()) ||
+                            (opt_source_batch.has_value() && opt_target_batch.has_value() &&
+                             opt_source_batch->is_same(*opt_target_batch));
+    const bool shared = sources.is_same(targets) && same_batch;
+    const Points pt = shared ? ps : check_points(targets, opt_target_batch, "(*out_batch)");
+    CHECK_INPUT(pt.dim == ps.dim);
+    CHECK_INPUT(pt.B == ps.B);
+    const bool real_input = real_dtype(x);
+    CHECK_INPUT(x.dim() >= 1);
+    CHECK_INPUT(x.size(0) == ps.n);
+    CHECK_INPUT(x.device() == sources.device() && targets.device() == sources.device());
+    CHECK_INPUT(poly.size() >= 1 && poly.size() <= 8);
+    int64_t C = 1;
+    std::vector<int64_t> out_shape{pt.n};
+    for (int64_t d = 1; d < x.dim(); ++d) {
+        C *= x.size(d);
+        out_shape.push_back(x.size(d));
+    }
+    nfft_hip_nearfield_problem q;
+    q.dim = ps.dim;
+    q.kernel = (int32_t)kernel;
+    q.poly_terms = (int32_t)poly.size();
+    q.num_sources = ps.n;
+    q.num_targets = pt.n;
+    q.num_columns = real_input ? C : 2 * C;
+    q.batch_size = ps.B;
+    q.c = c;
+    q.eps_I = eps_I;
+    for (size_t e = 0; e < 8; ++e) q.poly[e] = e < poly.size() ? poly[e] : 0.0;
+    const int64_t G = nfft_hip_nearfield_cells(q.dim, eps_I, q.batch_size);
+    if (G < 0) check_rc(NFFT_HIP_EINVAL);
+    q.cells_per_axis = (int32_t)G;
+    const int64_t ws_bytes = nfft_hip_nearfield_workspace_bytes(&q);
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    if (ps.n == 0 || pt.n == 0 || C == 0) return at::zeros(out_shape, x.options());  // an empty sum: no launch
+    c10::DeviceGuard guard(x.device());
+    int64_t cells_per_set = 1;
+    for (int a = 0; a < q.dim; ++a) cells_per_set *= G;
+    const CellOrder os = cell_order(ps, G, cells_per_set);
+    const CellOrder ot = shared ? os : cell_order(pt, G, cells_per_set);
+    const at::Tensor xc = x.contiguous();
+    const at::Tensor xr = (real_input ? xc : at::view_as_real(xc)).reshape({ps.n, q.num_columns}).index_select(0, os.order);
+    // (zeros: a target whose coordinates are not numbers has no cell and is not written)
+    at::Tensor z = at::zeros({pt.n, q.num_columns}, x.options().dtype(at::kFloat));
+    at::Tensor ws = byte_buffer(ws_bytes, x);
+    check_rc(nfft_hip_nearfield(&q, os.pos.data_ptr<float>(), xr.data_ptr<float>(), os.start.data_ptr<int32_t>(),
+                                ot.pos.data_ptr<float>(), ot.order.data_ptr<int64_t>(), ot.start.data_ptr<int32_t>(),
+                                z.data_ptr<float>(), ws.data_ptr(), ws_bytes, stream_of(x)));
+    if (!real_input) z = at::view_as_complex(z.reshape({pt.n, C, 2}));
+    return z.reshape(out_shape);
+}
+
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
 at::TensorOptions current_device_options(at::ScalarType dtype)
 {
@@ -844,4 +925,7 @@ TORCH_LIBRARY(torch_nfft, m)
     // not in the reference: the Toeplitz normal operator A^H W A (nfft_toeplitz_kernel / nfft_normal / nfft_inverse)
     m.def("_nfft_toeplitz_kernel(Tensor t) -> Tensor", &nfft_toeplitz_kernel);
     m.def("_nfft_normal(Tensor kernel, Tensor x) -> Tensor", &nfft_normal);
+    // not in the reference: the near-field pair sum of the fast summation for singular kernels (nfft_fastsum_nearfield)
+    m.def("_nfft_nearfield(Tensor sources, Tensor targets, Tensor x, Tensor? source_batch, Tensor? target_batch, "
+          "int kernel, float c, float eps_I, float[] poly) -> Tensor", &nfft_nearfield);
 }

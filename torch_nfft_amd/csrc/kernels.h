@@ -154,6 +154,12 @@ int launch_toeplitz_multiply(const Geom &g, float *grid, const float *K, int64_t
 int launch_row_toeplitz(const Geom &g, float2 *spec, const float *K, int64_t pairs_per_set, int64_t pair0, int64_t npairs,
                         hipStream_t stream);
 
+// nearfield.hip (the near-field pair sum of the fast summation for singular kernels): arguments as
+// nfft_hip_nearfield; `items`: nearfield_item_slots(p) int2 of workspace for the work items
+int64_t nearfield_item_slots(const nfft_hip_nearfield_problem *p);
+int launch_nearfield(const nfft_hip_nearfield_problem *p, const float *src, const float *xr, const int *sstart,
+                     const float *tgt, const int64_t *tindex, const int *tstart, float *z, void *items, hipStream_t stream);
+
 // smallgrid.hip: transforms whose oversampled grid (<= 4096 cells) fits one workgroup's LDS -- one kernel per direction,
 // no point plan
 bool small_grid_supported(const nfft_hip_problem *p);

@@ -1,0 +1,213 @@
+// Near field of the fast summation for singular kernels: the pair sum
+//
+//     z_i = sum_{j in the point set of i, |t_i - s_j| < eps_I} (K(r_ij) - T_I(r_ij)) x_j,      r_ij = |t_i - s_j|,
+//
+// that turns the NFFT sum of the regularised kernel K_R (T_I inside eps_I) back into the sum of K itself (Potts, Steidl,
+// Nieslony 2004).  No reference counterpart: the reference sums smooth kernels only.
+//
+// The caller hands in both point sets ordered by (point set, cell) of a grid of G^dim cubes of edge 1/(2G) >= eps_I over
+// [-1/4, 1/4]^dim, cell index c_0 + G c_1 + G^2 c_2, with the first point of every cell (start tables).  A target meets
+// sources of its own and the 3^dim - 1 neighbouring cells only; along axis 0 the three neighbours are consecutive cells, so
+// the walk is over 3^(dim-1) contiguous source ranges ("rows").
+//
+// nearfield_items_kernel   one thread per cell: cuts the cell's targets into work items of kNearBlock
+// nearfield_kernel         the tiled N-body loop.  A workgroup owns one item, a lane one target; the sources of a row
+//                          stream through LDS in tiles of kNearTile (position as one float4, CC columns of x); every lane
+//                          reads the same source (an LDS broadcast) and keeps its CC sums in registers.  The loop is bound by
+//                          the VALU: about 20 instructions and one transcendental per pair against one or two 16-byte LDS
+//                          broadcasts.  No atomics: a target's pairs are added in the order of the sorted sources.
+#include "common.h"
+#include "kernels.h"
+
+namespace nfft {
+
+namespace {
+
+constexpr int kNearBlock = 128;  // targets of a work item = lanes of its workgroup (two waves)
+constexpr int kNearTile = 256;   // sources per LDS tile: 4 KiB of positions + 4 CC bytes each
+
+struct NearParams {
+    int dim, G, terms;
+    int64_t Cr;
+    float c2, inv_c, inv_c2;  // shape parameter: c^2, 1/c, 1/c^2
+    float eps2, inv_eps2;     // eps_I^2 and its inverse
+    float poly[8];            // a_0 .. a_{terms-1}
+};
+
+// K(r) from r^2.  The kernels that are singular at 0 return 0 there: the self term is left out of the sum.
+template <int KERNEL>
+__device__ __forceinline__ float kernel_value(float r2, const NearParams &q)
+{
+    if (KERNEL == NFFT_HIP_KERNEL_ONE_OVER_MODULUS) return r2 > 0.f ? rsqrtf(r2) : 0.f;
+    if (KERNEL == NFFT_HIP_KERNEL_ONE_OVER_SQUARE) return r2 > 0.f ? 1.0f / r2 : 0.f;
+    if (KERNEL == NFFT_HIP_KERNEL_LOGARITHM) return r2 > 0.f ? 0.5f * logf(r2) : 0.f;
+    if (KERNEL == NFFT_HIP_KERNEL_THINPLATE_SPLINE) return r2 > 0.f ? 0.5f * r2 * logf(r2) : 0.f;
+    if (KERNEL == NFFT_HIP_KERNEL_MULTIQUADRIC) return sqrtf(r2 + q.c2);
+    if (KERNEL == NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC) return rsqrtf(r2 + q.c2);
+    if (KERNEL == NFFT_HIP_KERNEL_GAUSSIAN) return expf(-r2 * q.inv_c2);
+    return expf(-sqrtf(r2) * q.inv_c);  // NFFT_HIP_KERNEL_LAPLACIAN_RBF
+}
+
+// items[slot] = (cell, first target) for slot = first / kNearBlock + cell + piece: distinct for all pieces of all cells
+// (the pieces of a cell end at or before slot (end of the cell) / kNearBlock + cell, the next cell starts one later).
+// The slots nobody writes keep the -1 they were filled with.
+__global__ void __launch_bounds__(256) nearfield_items_kernel(const int *__restrict__ tstart, int ncells, int2 *__restrict__ items)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= ncells) return;
+    const int ts = tstart[k], te = tstart[k + 1];
+    int64_t slot = (int64_t)(ts / kNearBlock) + k;
+    for (int t = ts; t < te; t += kNearBlock, ++slot) items[slot] = make_int2(k, t);
+}
+
+// PT: Horner terms, 4 or 8; the coefficients past `terms` are zero, which leaves the sum of the others bit for bit
+template <int KERNEL, int CC, int PT>
+__global__ void __launch_bounds__(kNearBlock) nearfield_kernel(NearParams q, const int2 *__restrict__ items,
+                                                               const float *__restrict__ src, const float *__restrict__ xr,
+                                                               const int *__restrict__ sstart, const float *__restrict__ tgt,
+                                                               const int64_t *__restrict__ tindex,
+                                                               const int *__restrict__ tstart, float *__restrict__ z)
+{
+    __shared__ float4 s_pos[kNearTile];
+    __shared__ __attribute__((aligned(16))) float s_x[kNearTile * CC];
+    const int2 item = items[blockIdx.x];
+    if (item.x < 0) return;  // (uniform: an empty slot)
+    const int tid = threadIdx.x;
+    const int k = item.x;
+    const int tend = min(item.y + kNearBlock, tstart[k + 1]);
+    const int ti = item.y + tid;
+    const bool active = ti < tend;
+    const bool wave_active = item.y + (tid & ~63) < tend;
+    const int G = q.G;
+    const int c0 = k % G;
+    const int c1 = q.dim >= 2 ? (k / G) % G : 0;
+    const int c2 = q.dim >= 3 ? (k / (G * G)) % G : 0;
+    // a lane without a target sits far away: every pair fails the distance test
+    float tx = 1e9f, ty = 0.f, tz = 0.f;
+    if (active) {
+        const float *tp = tgt + (int64_t)ti * q.dim;
+        tx = tp[0];
+        if (q.dim >= 2) ty = tp[1];
+        if (q.dim >= 3) tz = tp[2];
+    }
+    const int r1 = q.dim >= 2 ? 1 : 0, r2 = q.dim >= 3 ? 1 : 0;
+    float a[PT];
+#pragma unroll
+    for (int e = 0; e < PT; ++e) a[e] = q.poly[e];
+    for (int64_t col0 = 0; col0 < q.Cr; col0 += CC) {
+        float acc[CC];
+#pragma unroll
+        for (int c = 0; c < CC; ++c) acc[c] = 0.f;
+        for (int d2 = -r2; d2 <= r2; ++d2) {
+            if (c2 + d2 < 0 || c2 + d2 >= G) continue;
+            for (int d1 = -r1; d1 <= r1; ++d1) {
+                if (c1 + d1 < 0 || c1 + d1 >= G) continue;
+                const int row = k + (d2 * G + d1) * G;
+                const int first = sstart[row - (c0 > 0 ? 1 : 0)];
+                const int last = sstart[row + (c0 < G - 1 ? 1 : 0) + 1];
+                for (int t0 = first; t0 < last; t0 += kNearTile) {
+                    const int cnt = min(kNearTile, last - t0);
+                    __syncthreads();
+                    for (int j = tid; j < cnt; j += kNearBlock) {
+                        const float *sp = src + (int64_t)(t0 + j) * q.dim;
+                        float4 v = make_float4(sp[0], 0.f, 0.f, 0.f);
+                        if (q.dim >= 2) v.y = sp[1];
+                        if (q.dim >= 3) v.z = sp[2];
+                        s_pos[j] = v;
+                        const float *xp = xr + (int64_t)(t0 + j) * q.Cr + col0;
+#pragma unroll
+                        for (int c = 0; c < CC; ++c) s_x[j * CC + c] = col0 + c < q.Cr ? xp[c] : 0.f;
+                    }
+                    __syncthreads();
+                    if (!wave_active) continue;
+#pragma unroll 4
+                    for (int j = 0; j < cnt; ++j) {
+                        const float4 s = s_pos[j];
+                        const float dx = tx - s.x, dy = ty - s.y, dz = tz - s.z;
+                        const float rr = dx * dx + dy * dy + dz * dz;
+                        const float u = rr * q.inv_eps2;
+                        float t = a[PT - 1];
+#pragma unroll
+                        for (int e = PT - 2; e >= 0; --e) t = t * u + a[e];
+                        const float w = rr < q.eps2 ? kernel_value<KERNEL>(rr, q) - t : 0.f;
+#pragma unroll
+                        for (int c = 0; c < CC; ++c) acc[c] += w * s_x[j * CC + c];
+                    }
+                }
+            }
+        }
+        if (active) {
+            float *zp = z + tindex[ti] * q.Cr + col0;
+#pragma unroll
+            for (int c = 0; c < CC; ++c)
+                if (col0 + c < q.Cr) zp[c] = acc[c];
+        }
+    }
+}
+
+template <int KERNEL>
+void launch_pairs(const NearParams &q, int64_t slots, const int2 *items, const float *src, const float *xr, const int *sstart,
+                  const float *tgt, const int64_t *tindex, const int *tstart, float *z, hipStream_t stream)
+{
+    const dim3 grid((unsigned)slots), block(kNearBlock);
+#define NEAR_LAUNCH(CC, PT)                                                                                             \
+    hipLaunchKernelGGL((nearfield_kernel<KERNEL, CC, PT>), grid, block, 0, stream, q, items, src, xr, sstart, tgt, tindex, \
+                       tstart, z)
+    if (q.terms <= 4) {
+        if (q.Cr == 1) NEAR_LAUNCH(1, 4);
+        else if (q.Cr == 2) NEAR_LAUNCH(2, 4);
+        else NEAR_LAUNCH(4, 4);
+    } else {
+        if (q.Cr == 1) NEAR_LAUNCH(1, 8);
+        else if (q.Cr == 2) NEAR_LAUNCH(2, 8);
+        else NEAR_LAUNCH(4, 8);
+    }
+#undef NEAR_LAUNCH
+}
+
+}  // namespace
+
+int64_t nearfield_item_slots(const nfft_hip_nearfield_problem *p)
+{
+    int64_t cells = p->batch_size;
+    for (int a = 0; a < p->dim; ++a) cells *= p->cells_per_axis;
+    return p->num_targets / kNearBlock + cells + 1;
+}
+
+int launch_nearfield(const nfft_hip_nearfield_problem *p, const float *src, const float *xr, const int *sstart,
+                     const float *tgt, const int64_t *tindex, const int *tstart, float *z, void *items, hipStream_t stream)
+{
+    NearParams q;
+    q.dim = p->dim;
+    q.G = p->cells_per_axis;
+    q.terms = p->poly_terms;
+    q.Cr = p->num_columns;
+    q.c2 = (float)(p->c * p->c);
+    q.inv_c = p->c > 0.0 ? (float)(1.0 / p->c) : 0.f;
+    q.inv_c2 = p->c > 0.0 ? (float)(1.0 / (p->c * p->c)) : 0.f;
+    q.eps2 = (float)(p->eps_I * p->eps_I);
+    q.inv_eps2 = (float)(1.0 / (p->eps_I * p->eps_I));
+    for (int e = 0; e < 8; ++e) q.poly[e] = e < p->poly_terms ? (float)p->poly[e] : 0.f;
+    int64_t cells = p->batch_size;
+    for (int a = 0; a < p->dim; ++a) cells *= p->cells_per_axis;
+    const int64_t slots = nearfield_item_slots(p);
+    NFFT_HIP_CHECK(hipMemsetAsync(items, 0xFF, (size_t)slots * sizeof(int2), stream));
+    hipLaunchKernelGGL(nearfield_items_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, tstart, (int)cells,
+                       (int2 *)items);
+    NFFT_HIP_CHECK(hipGetLastError());
+    const int2 *it = (const int2 *)items;
+    switch (p->kernel) {
+    case NFFT_HIP_KERNEL_ONE_OVER_MODULUS: launch_pairs<NFFT_HIP_KERNEL_ONE_OVER_MODULUS>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
+    case NFFT_HIP_KERNEL_ONE_OVER_SQUARE: launch_pairs<NFFT_HIP_KERNEL_ONE_OVER_SQUARE>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
+    case NFFT_HIP_KERNEL_LOGARITHM: launch_pairs<NFFT_HIP_KERNEL_LOGARITHM>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
+    case NFFT_HIP_KERNEL_THINPLATE_SPLINE: launch_pairs<NFFT_HIP_KERNEL_THINPLATE_SPLINE>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
+    case NFFT_HIP_KERNEL_MULTIQUADRIC: launch_pairs<NFFT_HIP_KERNEL_MULTIQUADRIC>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
+    case NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC: launch_pairs<NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
+    case NFFT_HIP_KERNEL_GAUSSIAN: launch_pairs<NFFT_HIP_KERNEL_GAUSSIAN>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
+    default: launch_pairs<NFFT_HIP_KERNEL_LAPLACIAN_RBF>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
+    }
+    NFFT_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace nfft

@@ -24,7 +24,8 @@ backward ``nfft_forward_grad_points_backward`` (their second derivatives; DESIGN
 and ``nfft_fastsum_backward`` (the fast summation).  They take their plans
 from the same cache with the same problems, so a backward pass right after its forward pass plans nothing.
 ``nfft_toeplitz_kernel`` and ``nfft_normal`` (the normal operator ``A^H W A`` as a Toeplitz product)
-use no plan at all.
+use no plan at all.  ``nfft_nearfield`` (the near-field pair sum of the fast summation for singular kernels; DESIGN.md
+section 7d) orders the points by cells of its own and uses no plan either.
 """
 import torch
 
@@ -129,6 +130,18 @@ def nfft_normal(kernel, x):
     ``[B] + [N]*d + cols`` float32 or complex64 and the kernel grid of the same points; complex64.  One native call
     (``nfft_hip_toeplitz_apply``): forward FFT stage, product with ``kernel``, adjoint FFT stage -- no point plan."""
     return _ops._nfft_normal(kernel, x)
+
+
+def nfft_nearfield(sources, targets, x, source_batch, target_batch, kernel, c, eps_I, poly):
+    """torch_nfft::_nfft_nearfield(Tensor sources, Tensor targets, Tensor x, Tensor? source_batch, Tensor? target_batch,
+    int kernel, float c, float eps_I, float[] poly) -> Tensor (not in the reference): the near field of the fast summation
+    for singular kernels, ``z_i = sum_{j: |t_i - s_j| < eps_I} (K(r_ij) - T_I(r_ij)) x_j`` over the sources of target i's
+    point set, with ``K`` the kernel number ``kernel`` of include/nfft_hip.h (shape parameter ``c``) and
+    ``T_I(r) = sum_k poly[k] (r / eps_I)^(2k)``.  ``z`` has ``x``'s type and trailing shape.  Both point sets are ordered
+    by cell with torch on the device (one stable sort each, one for shared points; no read-back), the pair sum is one
+    native call (``nfft_hip_nearfield``)."""
+    return _ops._nfft_nearfield(sources, targets, x, source_batch, target_batch, int(kernel), float(c), float(eps_I),
+                                [float(a) for a in poly])
 
 
 class _on_device:
