@@ -35,7 +35,7 @@ extern "C" {
 #define NFFT_HIP_EHIP 4       /* HIP runtime error (reference aborts the process, cuda_utils.cu:7-14; we report) */
 #define NFFT_HIP_EKERNEL 5    /* a kernel of an earlier call on this device reported a fault (nfft_hip_check_status) */
 
-#define NFFT_HIP_ABI_VERSION 6
+#define NFFT_HIP_ABI_VERSION 7
 
 int nfft_hip_abi_version(void);
 const char *nfft_hip_last_error(void);
@@ -330,6 +330,27 @@ int64_t nfft_hip_nearfield_workspace_bytes(const nfft_hip_nearfield_problem *p);
 int nfft_hip_nearfield(const nfft_hip_nearfield_problem *p, const float *sources, const float *xr,
                        const int32_t *source_start, const float *targets, const int64_t *target_index,
                        const int32_t *target_start, float *z, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- gradient of that near field at the targets, and its transpose ----
+ * With g(r^2) = (K'(r) - T_I'(r)) / r and the pairs of nfft_hip_nearfield without those at r = 0 (they weigh exactly zero),
+ *   transpose = 0:  out[i, a, c] = sum_j g(r_ij^2) (t_i - s_j)[a] xr[j, c]        out [n_t, dim, Cr], xr [n_s, Cr]
+ *   transpose = 1:  out[j, c]    = sum_i g(r_ij^2) sum_a (t_i - s_j)[a] xr[i, a, c]   out [n_s, Cr], xr [n_t, dim, Cr]
+ * K'(r) / r is evaluated in closed form from r^2 for the kernel p->kernel;  T_I'(r) / r = sum_{k < poly_terms - 1}
+ * gradient_poly[k] (r / eps_I)^(2k) with gradient_poly[k] = (2 / eps_I^2) (k + 1) a_{k+1}: poly_terms - 1 DOUBLES that the
+ * host derives from the a_k of T_I.  p->poly_terms counts the terms of T_I and must be >= 2 (with one term K_R is only
+ * continuous and g does not vanish at eps_I); p->poly is validated as for nfft_hip_nearfield and not read.
+ *
+ * The arguments keep the roles they have in nfft_hip_nearfield, named by what the kernel does with them: `sources`, `xr`,
+ * `source_start` and p->num_sources are the STREAMED side, `targets`, `target_index`, `target_start` and p->num_targets the
+ * OUTPUT side (row target_index[i] of `out` is written for the sorted output point i).  For transpose = 1 the caller
+ * therefore passes the sum's targets (with their values, rows in cell order) as the streamed side and the sum's sources
+ * as the output side; the library takes the difference vector with the sign above in both modes.  Ordering by cell,
+ * start tables, determinism, empty sides and the workspace are those of nfft_hip_nearfield. */
+int64_t nfft_hip_nearfield_gradient_workspace_bytes(const nfft_hip_nearfield_problem *p);
+int nfft_hip_nearfield_gradient(const nfft_hip_nearfield_problem *p, int32_t transpose, const double *gradient_poly,
+                                const float *sources, const float *xr, const int32_t *source_start, const float *targets,
+                                const int64_t *target_index, const int32_t *target_start, float *out, void *workspace,
+                                int64_t workspace_bytes, void *stream);
 
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.

@@ -1,6 +1,6 @@
 """Times nfft_fastsum_nearfield's two halves (profiles/r09_nearfield.md):
 
-    python scripts/bench_nearfield.py [--points 100000] [--reps 10]
+    python scripts/bench_nearfield.py [--points 100000] [--reps 10] [--gradient]
 
 3-D one_over_modulus, N = 64, p = 4 (eps_I = eps_B = 1/16), cutoff m = 4, shared points uniform in the ball of radius
 kern.max_radius, C = 1 and C = 4 real columns.  Device-event medians of `reps` calls after two warm-up calls:
@@ -11,6 +11,12 @@ kern.max_radius, C = 1 and C = 4 real columns.  Device-event medians of `reps` c
   pairs         distance tests per call = sum over targets of the sources in the 3^3 cells around it, and per second of
                 the pair loop; `in range` counts those with r < eps_I
 One JSON line per column count.
+
+--gradient times nfft_fastsum_nearfield_gradient on the same problem instead (DESIGN.md section 7e,
+profiles/r10_nearfield_gradient.md): the far gradient (one adjoint, the product with the dim coefficient arrays, one forward
+with dim C columns), the near gradient and its transpose as operators, their plumbing, and the three pair loops through
+the C ABI on the same sorted arrays -- gradient, transpose and, next to them, the value loop (nfft_hip_nearfield, the
+kernel of section 7d unchanged) -- with the ratios gradient / value and transpose / value.
 """
 import argparse
 import ctypes
@@ -50,10 +56,66 @@ def cell_order(pos, G):
     return pos.index_select(0, order), order, start
 
 
+def gradient_mode(args, lib, kern, pos, x, G, m, pairs, in_range):
+    from torch_nfft_amd.nearfield import _far_gradient
+    n, C = x.shape
+    gpoly = kern.near_gradient_poly.tolist()
+    v = torch.randn(n, 3, C, device="cuda")
+    grad_op = lambda t, transpose: tn.ops.nfft_nearfield_gradient(pos, pos, t, None, None, kern.kernel_id, kern.c, kern.eps_I,  # noqa: E731
+                                                                  gpoly, transpose)
+    far = median_ms(lambda: _far_gradient(x, kern, pos, pos, None, None, m), args.reps)
+    near = median_ms(lambda: grad_op(x, False), args.reps)
+    near_t = median_ms(lambda: grad_op(v, True), args.reps)
+
+    def plumbing(t, out_row):
+        spos, order, start = cell_order(pos, G)
+        return spos, order, start, t.reshape(n, -1).index_select(0, order), torch.zeros(n, out_row, device="cuda")
+
+    plumb = median_ms(lambda: plumbing(x, 3 * C), args.reps)
+    plumb_t = median_ms(lambda: plumbing(v, C), args.reps)
+    spos, order, start, xs, z = plumbing(x, 3 * C)
+    _, _, _, vs, zt = plumbing(v, C)
+    zv = torch.zeros(n, C, device="cuda")
+    q = _lib.NearfieldProblem(dim=3, kernel=kern.kernel_id, poly_terms=kern.p, cells_per_axis=G, num_sources=n, num_targets=n,
+                              num_columns=C, batch_size=1, c=kern.c, eps_I=kern.eps_I)
+    for e, a in enumerate(kern.near_poly.tolist()):
+        q.poly[e] = a
+    gp = (ctypes.c_double * 8)(*gpoly)
+    nbytes = lib.nfft_hip_nearfield_gradient_workspace_bytes(ctypes.byref(q))
+    assert nbytes == lib.nfft_hip_nearfield_workspace_bytes(ctypes.byref(q))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def loop(transpose, src, out):
+        _lib.check(lib.nfft_hip_nearfield_gradient(ctypes.byref(q), transpose, ctypes.cast(gp, ctypes.c_void_p), spos.data_ptr(),
+                                                   src.data_ptr(), start.data_ptr(), spos.data_ptr(), order.data_ptr(),
+                                                   start.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, stream))
+
+    def value_loop():
+        _lib.check(lib.nfft_hip_nearfield(ctypes.byref(q), spos.data_ptr(), xs.data_ptr(), start.data_ptr(), spos.data_ptr(),
+                                          order.data_ptr(), start.data_ptr(), zv.data_ptr(), ws.data_ptr(), nbytes, stream))
+
+    value = median_ms(value_loop, args.reps)
+    pair = median_ms(lambda: loop(0, xs, z), args.reps)
+    pair_t = median_ms(lambda: loop(1, vs, zt), args.reps)
+    assert torch.equal(grad_op(x, False), z.reshape(n, 3, C)), "the restated plumbing must give the operator's bits"
+    assert torch.equal(grad_op(v, True), zt), "the restated plumbing must give the operator's bits"
+    tn.ops.check_status()
+    print(json.dumps({"bench": "nearfield_gradient", "kernel": kern.name, "N": kern.bandwidth, "p": kern.p, "m": m, "points": n,
+                      "columns": C, "cells_per_axis": G, "far_gradient_ms": round(far, 4), "near_gradient_ms": round(near, 4),
+                      "near_transpose_ms": round(near_t, 4), "gradient_plumbing_ms": round(plumb, 4),
+                      "transpose_plumbing_ms": round(plumb_t, 4), "gradient_pair_loop_ms": round(pair, 4),
+                      "transpose_pair_loop_ms": round(pair_t, 4), "value_pair_loop_ms": round(value, 4),
+                      "gradient_over_value": round(pair / value, 3), "transpose_over_value": round(pair_t / value, 3),
+                      "pairs_tested": pairs, "pairs_in_range_estimate": in_range,
+                      "gradient_pairs_per_second": round(pairs / (pair * 1e-3), 1)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=100000)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--gradient", action="store_true")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     lib = _lib.load()
@@ -77,6 +139,9 @@ def main():
     for C in (1, 4):
         x = torch.from_numpy(rng.standard_normal((n, C)).astype(np.float32)).cuda()
         poly = kern.near_poly.tolist()
+        if args.gradient:
+            gradient_mode(args, lib, kern, pos, x, G, m, pairs, in_range)
+            continue
         far = median_ms(lambda: tn.nfft_fastsum(x, kern.coeffs, pos, cutoff=m), args.reps)
         near = median_ms(lambda: tn.ops.nfft_nearfield(pos, pos, x, None, None, kern.kernel_id, kern.c, kern.eps_I, poly), args.reps)
 

@@ -16,7 +16,8 @@ from .toeplitz import nfft_toeplitz_kernel, nfft_normal, nfft_inverse, NfftNorma
 from .ndft import ndft_forward, ndft_adjoint, ndft_fastsum, exact_trigonometric_matrix, exact_gaussian_matrix  # noqa: E402
 from .coeffs import (gaussian_analytic_coeffs, gaussian_interpolated_coeffs, interpolation_grid,  # noqa: E402
                      radial_interpolation_grid, interpolated_kernel_coeffs)
-from .nearfield import RegularizedKernel, nfft_nearfield, nfft_fastsum_nearfield, NfftNearfieldFunction  # noqa: E402
+from .nearfield import (RegularizedKernel, nfft_nearfield, nfft_fastsum_nearfield, NfftNearfieldFunction,  # noqa: E402
+                        nfft_nearfield_gradient, nfft_fastsum_nearfield_gradient, NfftNearfieldGradientFunction)
 from .matrices import GramMatrix, AdjacencyMatrix  # noqa: E402
 from .kernel import GaussianKernel  # noqa: E402
 from . import utils  # noqa: E402
@@ -24,7 +25,8 @@ from . import utils  # noqa: E402
 
 __all__ = ["nfft_adjoint", "nfft_forward", "nfft_fastsum", "nfft_toeplitz_kernel", "nfft_normal", "nfft_inverse",
            "NfftNormalFunction", "RegularizedKernel", "nfft_nearfield", "nfft_fastsum_nearfield",
-           "NfftNearfieldFunction", "ndft_forward", "ndft_adjoint", "ndft_fastsum",
+           "NfftNearfieldFunction", "nfft_nearfield_gradient", "nfft_fastsum_nearfield_gradient",
+           "NfftNearfieldGradientFunction", "ndft_forward", "ndft_adjoint", "ndft_fastsum",
            "exact_trigonometric_matrix", "exact_gaussian_matrix", "NfftAdjointFunction", "NfftForwardFunction",
            "NfftFastsumFunction", "gaussian_analytic_coeffs", "gaussian_interpolated_coeffs", "interpolation_grid",
            "radial_interpolation_grid", "interpolated_kernel_coeffs", "GramMatrix", "AdjacencyMatrix",

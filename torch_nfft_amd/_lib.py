@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NFFT_HIP_LIB") or os.path.join(_HERE, "libnfft_hip.so")
 CORE_PATH = os.path.join(_HERE, "core.so")
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 POINTS_IN_QUARTER_BALL = 1
 
 # every symbol include/nfft_hip.h declares
@@ -52,6 +52,8 @@ SYMBOLS = (
     "nfft_hip_nearfield_cells",
     "nfft_hip_nearfield_workspace_bytes",
     "nfft_hip_nearfield",
+    "nfft_hip_nearfield_gradient_workspace_bytes",
+    "nfft_hip_nearfield_gradient",
     "nfft_hip_gaussian_analytic_coeffs",
     "nfft_hip_interpolation_grid",
     "nfft_hip_coeffs_workspace_bytes",
@@ -188,6 +190,11 @@ def load():
     lib.nfft_hip_nearfield_workspace_bytes.restype = i64
     lib.nfft_hip_nearfield.argtypes = [ctypes.POINTER(NearfieldProblem), vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.nfft_hip_nearfield.restype = ci
+    lib.nfft_hip_nearfield_gradient_workspace_bytes.argtypes = [ctypes.POINTER(NearfieldProblem)]
+    lib.nfft_hip_nearfield_gradient_workspace_bytes.restype = i64
+    lib.nfft_hip_nearfield_gradient.argtypes = [ctypes.POINTER(NearfieldProblem), ctypes.c_int32, vp,
+                                                vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.nfft_hip_nearfield_gradient.restype = ci
     lib.nfft_hip_gaussian_analytic_coeffs.argtypes = [ctypes.c_double, i64, ctypes.c_int32, vp, vp]
     lib.nfft_hip_gaussian_analytic_coeffs.restype = ci
     lib.nfft_hip_interpolation_grid.argtypes = [i64, ctypes.c_int32, ci, vp, vp]

@@ -1530,4 +1530,54 @@ int nfft_hip_nearfield(const nfft_hip_nearfield_problem *p, const float *sources
     return launch_nearfield(p, sources, xr, source_start, targets, target_index, target_start, z, ws, s);
 }
 
+// ---- its gradient at the targets and the transpose ---------------------------------------------
+static int validate_nearfield_gradient(const nfft_hip_nearfield_problem *p)
+{
+    if (int rc = validate_nearfield(p)) return rc;
+    if (p->poly_terms < 2) {
+        set_error("Input mismatch: the near field's gradient needs poly_terms >= 2 (K_R must be differentiable at eps_I)");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+int64_t nfft_hip_nearfield_gradient_workspace_bytes(const nfft_hip_nearfield_problem *p)
+{
+    if (validate_nearfield_gradient(p)) return -1;
+    return nearfield_item_slots(p) * (int64_t)sizeof(int2) + 256;
+}
+
+int nfft_hip_nearfield_gradient(const nfft_hip_nearfield_problem *p, int32_t transpose, const double *gradient_poly,
+                                const float *sources, const float *xr, const int32_t *source_start, const float *targets,
+                                const int64_t *target_index, const int32_t *target_start, float *out, void *workspace,
+                                int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_nearfield_gradient(p)) return rc;
+    if (transpose != 0 && transpose != 1) { set_error("Input mismatch: transpose must be 0 or 1"); return NFFT_HIP_EINVAL; }
+    if (!gradient_poly) { set_error("Input mismatch: gradient_poly is null"); return NFFT_HIP_EINVAL; }
+    for (int e = 0; e < p->poly_terms - 1; ++e)
+        if (!(gradient_poly[e] == gradient_poly[e]) || gradient_poly[e] > 3e38 || gradient_poly[e] < -3e38) {
+            set_error("Input mismatch: gradient_poly is not finite");
+            return NFFT_HIP_EINVAL;
+        }
+    if (p->num_targets == 0 || p->num_columns == 0) return 0;
+    if (!out) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    if (p->num_sources == 0) {
+        const int64_t row = transpose ? p->num_columns : p->dim * p->num_columns;
+        NFFT_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(p->num_targets * row) * sizeof(float), s));
+        return 0;
+    }
+    if (!sources || !xr || !source_start || !targets || !target_index || !target_start) {
+        set_error("Input mismatch: null input");
+        return NFFT_HIP_EINVAL;
+    }
+    const int64_t need = nearfield_item_slots(p) * (int64_t)sizeof(int2) + 256;
+    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    return launch_nearfield_gradient(p, transpose, gradient_poly, sources, xr, source_start, targets, target_index,
+                                     target_start, out, ws, s);
+}
+
 }  // extern "C"

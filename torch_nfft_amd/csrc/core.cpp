@@ -814,6 +814,78 @@ at::Tensor nfft_nearfield(at::Tensor sources, at::Tensor targets, at::Tensor x, 
     return z.reshape(out_shape);
 }
 
+// The gradient of that sum at the targets and its transpose, g = (K' - T_I') / r:
+//   transpose = false: x [n_s, *cols] -> G [n_t, dim, *cols],  G[i, a] = sum_j g(r_ij^2) (t_i - s_j)[a] x[j]
+//   transpose = true:  x [n_t, dim, *cols] -> [n_s, *cols],    out[j] = sum_i g(r_ij^2) (t_i - s_j) . x[i]
+// poly: the p - 1 Horner coefficients of T_I'(r) / r in (r / eps_I)^2.  The output side of the pair kernel is the targets
+// for the gradient and the sources for the transpose: the two cell orders change places.
+at::Tensor nfft_nearfield_gradient(at::Tensor sources, at::Tensor targets, at::Tensor x,
+                                   c10::optional<at::Tensor> opt_source_batch, c10::optional<at::Tensor> opt_target_batch,
+                                   int64_t kernel, double c, double eps_I, at::ArrayRef<double> poly, bool transpose)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_nearfield_gradient is currently only implemented for GPU tensors");
+    const Points ps = check_points(sources, opt_source_batch, "(*out_batch)");
+    const bool same_batch = (!opt_source_batch.has_value() && !opt_target_batch.has_value()) ||
+                            (opt_source_batch.has_value() && opt_target_batch.has_value() &&
+                             opt_source_batch->is_same(*opt_target_batch));
+    const bool shared = sources.is_same(targets) && same_batch;
+    const Points pt = shared ? ps : check_points(targets, opt_target_batch, "(*out_batch)");
+    CHECK_INPUT(pt.dim == ps.dim);
+    CHECK_INPUT(pt.B == ps.B);
+    const Points &pin = transpose ? pt : ps, &pout = transpose ? ps : pt;  // streamed side, output side
+    const int64_t dim = ps.dim;
+    const bool real_input = real_dtype(x);
+    const int64_t lead = transpose ? 2 : 1;
+    CHECK_INPUT(x.dim() >= lead);
+    CHECK_INPUT(x.size(0) == pin.n);
+    if (transpose) CHECK_INPUT(x.size(1) == dim);
+    CHECK_INPUT(x.device() == sources.device() && targets.device() == sources.device());
+    CHECK_INPUT(poly.size() >= 1 && poly.size() <= 7);
+    int64_t C = 1;
+    std::vector<int64_t> out_shape{pout.n};
+    if (!transpose) out_shape.push_back(dim);
+    for (int64_t d = lead; d < x.dim(); ++d) {
+        C *= x.size(d);
+        out_shape.push_back(x.size(d));
+    }
+    nfft_hip_nearfield_problem q;
+    q.dim = (int32_t)dim;
+    q.kernel = (int32_t)kernel;
+    q.poly_terms = (int32_t)poly.size() + 1;
+    q.num_sources = pin.n;
+    q.num_targets = pout.n;
+    q.num_columns = real_input ? C : 2 * C;
+    q.batch_size = ps.B;
+    q.c = c;
+    q.eps_I = eps_I;
+    for (size_t e = 0; e < 8; ++e) q.poly[e] = 0.0;  // (T_I itself is not read)
+    double gpoly[8] = {0.0};
+    for (size_t e = 0; e < poly.size(); ++e) gpoly[e] = poly[e];
+    const int64_t G = nfft_hip_nearfield_cells(q.dim, eps_I, q.batch_size);
+    if (G < 0) check_rc(NFFT_HIP_EINVAL);
+    q.cells_per_axis = (int32_t)G;
+    const int64_t ws_bytes = nfft_hip_nearfield_gradient_workspace_bytes(&q);
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    if (ps.n == 0 || pt.n == 0 || C == 0) return at::zeros(out_shape, x.options());  // an empty sum: no launch
+    c10::DeviceGuard guard(x.device());
+    int64_t cells_per_set = 1;
+    for (int a = 0; a < q.dim; ++a) cells_per_set *= G;
+    const CellOrder oin = cell_order(pin, G, cells_per_set);
+    const CellOrder oout = shared ? oin : cell_order(pout, G, cells_per_set);
+    const int64_t in_row = (transpose ? dim : 1) * q.num_columns, out_row = (transpose ? 1 : dim) * q.num_columns;
+    const at::Tensor xc = x.contiguous();
+    const at::Tensor xr = (real_input ? xc : at::view_as_real(xc)).reshape({pin.n, in_row}).index_select(0, oin.order);
+    // (zeros: an output point whose coordinates are not numbers has no cell and is not written)
+    at::Tensor z = at::zeros({pout.n, out_row}, x.options().dtype(at::kFloat));
+    at::Tensor ws = byte_buffer(ws_bytes, x);
+    check_rc(nfft_hip_nearfield_gradient(&q, transpose ? 1 : 0, gpoly, oin.pos.data_ptr<float>(), xr.data_ptr<float>(),
+                                         oin.start.data_ptr<int32_t>(), oout.pos.data_ptr<float>(),
+                                         oout.order.data_ptr<int64_t>(), oout.start.data_ptr<int32_t>(), z.data_ptr<float>(),
+                                         ws.data_ptr(), ws_bytes, stream_of(x)));
+    if (!real_input) z = at::view_as_complex(z.reshape({pout.n, out_row / 2, 2}));
+    return z.reshape(out_shape);
+}
+
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
 at::TensorOptions current_device_options(at::ScalarType dtype)
 {
@@ -928,4 +1000,7 @@ TORCH_LIBRARY(torch_nfft, m)
     // not in the reference: the near-field pair sum of the fast summation for singular kernels (nfft_fastsum_nearfield)
     m.def("_nfft_nearfield(Tensor sources, Tensor targets, Tensor x, Tensor? source_batch, Tensor? target_batch, "
           "int kernel, float c, float eps_I, float[] poly) -> Tensor", &nfft_nearfield);
+    // ... and its gradient at the targets / the transpose of that (nfft_fastsum_nearfield_gradient)
+    m.def("_nfft_nearfield_gradient(Tensor sources, Tensor targets, Tensor x, Tensor? source_batch, Tensor? target_batch, "
+          "int kernel, float c, float eps_I, float[] poly, bool transpose) -> Tensor", &nfft_nearfield_gradient);
 }

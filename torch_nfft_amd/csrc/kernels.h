@@ -159,6 +159,12 @@ int launch_row_toeplitz(const Geom &g, float2 *spec, const float *K, int64_t pai
 int64_t nearfield_item_slots(const nfft_hip_nearfield_problem *p);
 int launch_nearfield(const nfft_hip_nearfield_problem *p, const float *src, const float *xr, const int *sstart,
                      const float *tgt, const int64_t *tindex, const int *tstart, float *z, void *items, hipStream_t stream);
+// nearfield_grad.hip (the near field's gradient at the targets and its transpose): arguments as
+// nfft_hip_nearfield_gradient -- `spos` / `in` / `sstart` the streamed side, `opos` / `oindex` / `ostart` the output side;
+// `items` as above
+int launch_nearfield_gradient(const nfft_hip_nearfield_problem *p, int transpose, const double *gradient_poly,
+                              const float *spos, const float *in, const int *sstart, const float *opos, const int64_t *oindex,
+                              const int *ostart, float *out, void *items, hipStream_t stream);
 
 // smallgrid.hip: transforms whose oversampled grid (<= 4096 cells) fits one workgroup's LDS -- one kernel per direction,
 // no point plan

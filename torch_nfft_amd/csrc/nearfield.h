@@ -1,0 +1,42 @@
+// What the two near-field pair kernels share (nearfield.hip: the value; nearfield_grad.hip: the
+// gradient at the targets and its transpose, section 7e): the sizes of a work item and of an LDS tile, the parameter
+// block and the work-item list.
+#pragma once
+#include "common.h"
+#include "kernels.h"
+
+namespace nfft {
+
+constexpr int kNearBlock = 128;  // output points of a work item = lanes of its workgroup (two waves)
+constexpr int kNearTile = 256;   // streamed points per LDS tile: 4 KiB of positions + 4 bytes per staged value each
+
+struct NearParams {
+    int dim, G, terms;
+    int64_t Cr;
+    float c2, inv_c, inv_c2;  // shape parameter: c^2, 1/c, 1/c^2
+    float eps2, inv_eps2;     // eps_I^2 and its inverse
+    float poly[8];            // the Horner coefficients in u = r^2 / eps_I^2, zero past `terms`
+};
+
+// the block of a problem with `terms` coefficients `poly` (float64 on the host, rounded once)
+inline NearParams near_params(const nfft_hip_nearfield_problem *p, const double *poly, int terms)
+{
+    NearParams q;
+    q.dim = p->dim;
+    q.G = p->cells_per_axis;
+    q.terms = terms;
+    q.Cr = p->num_columns;
+    q.c2 = (float)(p->c * p->c);
+    q.inv_c = p->c > 0.0 ? (float)(1.0 / p->c) : 0.f;
+    q.inv_c2 = p->c > 0.0 ? (float)(1.0 / (p->c * p->c)) : 0.f;
+    q.eps2 = (float)(p->eps_I * p->eps_I);
+    q.inv_eps2 = (float)(1.0 / (p->eps_I * p->eps_I));
+    for (int e = 0; e < 8; ++e) q.poly[e] = e < terms ? (float)poly[e] : 0.f;
+    return q;
+}
+
+// nearfield.hip: fills items[0 .. nearfield_item_slots(p)) with (cell, first output point) of every piece of kNearBlock
+// output points of one cell, -1 in the slots that stay empty; tstart is the output side's start table
+int launch_nearfield_items(const nfft_hip_nearfield_problem *p, const int *tstart, int2 *items, hipStream_t stream);
+
+}  // namespace nfft

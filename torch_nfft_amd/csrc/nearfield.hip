@@ -16,23 +16,11 @@
 //                          reads the same source (an LDS broadcast) and keeps its CC sums in registers.  The loop is bound by
 //                          the VALU: about 20 instructions and one transcendental per pair against one or two 16-byte LDS
 //                          broadcasts.  No atomics: a target's pairs are added in the order of the sorted sources.
-#include "common.h"
-#include "kernels.h"
+#include "nearfield.h"
 
 namespace nfft {
 
 namespace {
-
-constexpr int kNearBlock = 128;  // targets of a work item = lanes of its workgroup (two waves)
-constexpr int kNearTile = 256;   // sources per LDS tile: 4 KiB of positions + 4 CC bytes each
-
-struct NearParams {
-    int dim, G, terms;
-    int64_t Cr;
-    float c2, inv_c, inv_c2;  // shape parameter: c^2, 1/c, 1/c^2
-    float eps2, inv_eps2;     // eps_I^2 and its inverse
-    float poly[8];            // a_0 .. a_{terms-1}
-};
 
 // K(r) from r^2.  The kernels that are singular at 0 return 0 there: the self term is left out of the sum.
 template <int KERNEL>
@@ -174,27 +162,23 @@ int64_t nearfield_item_slots(const nfft_hip_nearfield_problem *p)
     return p->num_targets / kNearBlock + cells + 1;
 }
 
+int launch_nearfield_items(const nfft_hip_nearfield_problem *p, const int *tstart, int2 *items, hipStream_t stream)
+{
+    int64_t cells = p->batch_size;
+    for (int a = 0; a < p->dim; ++a) cells *= p->cells_per_axis;
+    NFFT_HIP_CHECK(hipMemsetAsync(items, 0xFF, (size_t)nearfield_item_slots(p) * sizeof(int2), stream));
+    hipLaunchKernelGGL(nearfield_items_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, tstart, (int)cells,
+                       items);
+    NFFT_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 int launch_nearfield(const nfft_hip_nearfield_problem *p, const float *src, const float *xr, const int *sstart,
                      const float *tgt, const int64_t *tindex, const int *tstart, float *z, void *items, hipStream_t stream)
 {
-    NearParams q;
-    q.dim = p->dim;
-    q.G = p->cells_per_axis;
-    q.terms = p->poly_terms;
-    q.Cr = p->num_columns;
-    q.c2 = (float)(p->c * p->c);
-    q.inv_c = p->c > 0.0 ? (float)(1.0 / p->c) : 0.f;
-    q.inv_c2 = p->c > 0.0 ? (float)(1.0 / (p->c * p->c)) : 0.f;
-    q.eps2 = (float)(p->eps_I * p->eps_I);
-    q.inv_eps2 = (float)(1.0 / (p->eps_I * p->eps_I));
-    for (int e = 0; e < 8; ++e) q.poly[e] = e < p->poly_terms ? (float)p->poly[e] : 0.f;
-    int64_t cells = p->batch_size;
-    for (int a = 0; a < p->dim; ++a) cells *= p->cells_per_axis;
+    const NearParams q = near_params(p, p->poly, p->poly_terms);
     const int64_t slots = nearfield_item_slots(p);
-    NFFT_HIP_CHECK(hipMemsetAsync(items, 0xFF, (size_t)slots * sizeof(int2), stream));
-    hipLaunchKernelGGL(nearfield_items_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, tstart, (int)cells,
-                       (int2 *)items);
-    NFFT_HIP_CHECK(hipGetLastError());
+    if (int rc = launch_nearfield_items(p, tstart, (int2 *)items, stream)) return rc;
     const int2 *it = (const int2 *)items;
     switch (p->kernel) {
     case NFFT_HIP_KERNEL_ONE_OVER_MODULUS: launch_pairs<NFFT_HIP_KERNEL_ONE_OVER_MODULUS>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;

@@ -10,7 +10,8 @@ end and is flat to order ``p - 1`` at ``1/2``, so that the periodic continuation
 near field, one native call (``ops.nfft_nearfield``).
 
 ``RegularizedKernel`` does the set-up in float64 on the host: every kernel is written once as a torch expression in ``r``
-and the derivatives come from ``torch.autograd.grad`` on it.  ``nfft_fastsum_nearfield`` is the sum itself.
+and the derivatives come from ``torch.autograd.grad`` on it.  ``nfft_fastsum_nearfield`` is the sum itself,
+``nfft_fastsum_nearfield_gradient`` its gradient at the targets (the field of the potential).
 """
 import math
 
@@ -18,7 +19,7 @@ import torch
 
 from . import ops
 from .coeffs import interpolated_kernel_coeffs
-from .nfft import nfft_fastsum
+from .nfft import nfft_adjoint, nfft_fastsum, nfft_forward
 
 
 # name -> (kernel id of include/nfft_hip.h, K(r, c) as a torch expression, singular at 0, c must be positive)
@@ -62,6 +63,7 @@ class RegularizedKernel:
                     the samples are even); with ``device="cpu"`` the same recipe as a float64 FFT on the host
     ``max_radius``  ``1/4 - eps_B/2``: every source and target must lie within it
     ``near_poly``   ``a_0 .. a_{p-1}`` float64
+    ``near_gradient_poly``  ``[p - 1]`` float64: ``T_I'(r) / r = sum_k near_gradient_poly[k] (r / eps_I)^(2k)``
     ``kern(r)``     ``K_R(r)`` in float64; ``kernel`` / ``inner`` / ``boundary`` are its three pieces
     """
 
@@ -89,6 +91,8 @@ class RegularizedKernel:
         self.eps_I, self.eps_B = eps_I, eps_B
         self.max_radius = 0.25 - eps_B / 2
         self.near_poly = self._inner_coefficients()
+        # d/dr sum_k a_k (r / eps_I)^(2k) = r (2 / eps_I^2) sum_{k >= 1} k a_k (r / eps_I)^(2 (k - 1))
+        self.near_gradient_poly = self.near_poly[1:] * torch.arange(1, p, dtype=torch.float64) * (2.0 / (eps_I * eps_I))
         self._bnd_poly = self._boundary_coefficients() if eps_B > 0.0 else None
         self.coeffs = self._coefficients(torch.device(device))
 
@@ -212,8 +216,8 @@ def nfft_fastsum_nearfield(x, kern, sources, targets=None, source_batch=None, ta
     The argument conventions are those of ``nfft_fastsum`` (``targets=None``: shared points; a real ``x`` gives a real
     ``y``), in torus coordinates: every source and target must lie within ``kern.max_radius`` of the origin (not
     checked).  Differentiable in ``x`` (the near field to any order, the far field once, like ``nfft_fastsum``).
-    ``sources``, ``targets`` and the batch vectors must not require grad (AssertionError): the near field's point
-    gradients need ``K'`` per kernel and are not implemented."""
+    ``sources``, ``targets`` and the batch vectors must not require grad (AssertionError); the gradient at the targets is
+    a function of its own, ``nfft_fastsum_nearfield_gradient``."""
     if targets is None:
         targets = sources
         target_batch = source_batch
@@ -226,3 +230,94 @@ def nfft_fastsum_nearfield(x, kern, sources, targets=None, source_batch=None, ta
             raise AssertionError("nfft_fastsum_nearfield is differentiable w.r.t. x only, but %s requires grad" % name)
     far = nfft_fastsum(x, kern.coeffs, sources, targets, source_batch, target_batch, cutoff=cutoff)
     return far + NfftNearfieldFunction.apply(x, kern, sources, targets, source_batch, target_batch)
+
+
+def _refuse_point_gradients(what, sources, targets, source_batch, target_batch):
+    for name, t in (("sources", sources), ("targets", targets), ("source_batch", source_batch),
+                    ("target_batch", target_batch)):
+        if t is not None and t.requires_grad:
+            raise AssertionError("%s is differentiable w.r.t. x only, but %s requires grad" % (what, name))
+
+
+class NfftNearfieldGradientFunction(torch.autograd.Function):
+    """``transpose=False``: G = the gradient of the near field at the targets applied to x, ``[n_t, dim, *cols]``;
+    ``transpose=True``: G^T applied to ``[n_t, dim, *cols]``, ``[n_s, *cols]``.  Both are linear in x and each is the
+    other's backward, so either can be differentiated in x to any order."""
+
+    @staticmethod
+    def forward(ctx, x, kern, sources, targets, source_batch, target_batch, transpose):
+        _refuse_point_gradients("the near field's gradient", sources, targets, source_batch, target_batch)
+        ctx.kern, ctx.transpose = kern, transpose
+        ctx.save_for_backward(sources, targets, source_batch, target_batch)
+        return ops.nfft_nearfield_gradient(sources, targets, x, source_batch, target_batch, kern.kernel_id, kern.c,
+                                           kern.eps_I, kern.near_gradient_poly.tolist(), transpose)
+
+    @staticmethod
+    def backward(ctx, dz):
+        sources, targets, source_batch, target_batch = ctx.saved_tensors
+        dx = NfftNearfieldGradientFunction.apply(dz, ctx.kern, sources, targets, source_batch, target_batch,
+                                                 not ctx.transpose)
+        return dx, None, None, None, None, None, None
+
+
+def _needs_smooth_join(what, kern):
+    if kern.p < 2:
+        raise ValueError("%s needs a RegularizedKernel with p >= 2: with p = 1 K_R is only continuous at eps_I" % what)
+
+
+def nfft_nearfield_gradient(x, kern, sources, targets=None, source_batch=None, target_batch=None, /, batch=None):
+    """``G_i = sum_{j: 0 < |t_i - s_j| < eps_I, same point set} (K'(r_ij) - T_I'(r_ij)) (t_i - s_j) / r_ij  x_j``,
+    ``[n_t, dim, *cols]``: the gradient of ``nfft_nearfield`` at the targets, the near part of
+    ``nfft_fastsum_nearfield_gradient`` on its own (same argument conventions; a pair with ``r = 0`` contributes zero)."""
+    _needs_smooth_join("nfft_nearfield_gradient", kern)
+    if targets is None:
+        targets = sources
+        target_batch = source_batch
+    if batch is not None:
+        source_batch = batch
+        target_batch = batch
+    return NfftNearfieldGradientFunction.apply(x, kern, sources, targets, source_batch, target_batch, False)
+
+
+def _far_gradient_coeffs(kern):
+    """``[N]*dim + [dim]`` complex64: ``(-2 pi i l_a) kern.coeffs`` for every axis a, the unpaired plane ``l_a = -N/2`` of
+    axis a zeroed (the derivative of a real trigonometric interpolant has no Nyquist term)"""
+    N, dim = kern.bandwidth, kern.dim
+    freq = torch.arange(-(N // 2), N // 2, dtype=torch.float32, device=kern.coeffs.device)
+    freq[0] = 0.0
+    out = []
+    for a in range(dim):
+        shape = [1] * dim
+        shape[a] = N
+        out.append(torch.complex(torch.zeros_like(kern.coeffs), kern.coeffs * (-2.0 * math.pi * freq).reshape(shape)))
+    return torch.stack(out, dim)
+
+
+def _far_gradient(x, kern, sources, targets, source_batch, target_batch, cutoff):
+    """forward_t(c' * adjoint_s(x)) with the dim gradient coefficient arrays as further columns: [n_t, dim, *cols]"""
+    N, dim = kern.bandwidth, kern.dim
+    band = nfft_adjoint(x, sources, source_batch, bandwidth=N, cutoff=cutoff)  # [B] + [N]*dim + cols
+    band = band.unsqueeze(1 + dim) * _far_gradient_coeffs(kern).reshape([1] + [N] * dim + [dim] + [1] * (x.dim() - 1))
+    return nfft_forward(band, targets, target_batch, cutoff=cutoff, real_output=not x.is_complex())
+
+
+def nfft_fastsum_nearfield_gradient(x, kern, sources, targets=None, source_batch=None, target_batch=None, /, batch=None,
+                                    cutoff=3):
+    """The field of ``nfft_fastsum_nearfield``'s potential: ``G_i = grad_{t_i} y_i = sum_j K'(r_ij) (t_i - s_j) / r_ij  x_j``
+    over the sources of target i's point set, ``[n_t, dim, *cols]`` with the dtype of ``x``.
+
+    The far part is the gradient of the trigonometric polynomial of ``K_R``: ``nfft_forward`` at the targets of
+    ``nfft_adjoint(x)`` at the sources times ``(-2 pi i l_a) kern.coeffs``, the ``dim`` axes as further columns; the near
+    part is ``nfft_nearfield_gradient``.  Arguments as for ``nfft_fastsum_nearfield``; ``kern.p >= 2`` (ValueError).
+    Differentiable in ``x`` (the near part to any order, the far part as far as the two transforms are); ``sources``,
+    ``targets`` and the batch vectors must not require grad (AssertionError)."""
+    _needs_smooth_join("nfft_fastsum_nearfield_gradient", kern)
+    if targets is None:
+        targets = sources
+        target_batch = source_batch
+    if batch is not None:
+        source_batch = batch
+        target_batch = batch
+    _refuse_point_gradients("nfft_fastsum_nearfield_gradient", sources, targets, source_batch, target_batch)
+    far = _far_gradient(x, kern, sources, targets, source_batch, target_batch, cutoff)
+    return far + NfftNearfieldGradientFunction.apply(x, kern, sources, targets, source_batch, target_batch, False)

@@ -144,6 +144,19 @@ def nfft_nearfield(sources, targets, x, source_batch, target_batch, kernel, c, e
                                 [float(a) for a in poly])
 
 
+def nfft_nearfield_gradient(sources, targets, x, source_batch, target_batch, kernel, c, eps_I, poly, transpose):
+    """torch_nfft::_nfft_nearfield_gradient(Tensor sources, Tensor targets, Tensor x, Tensor? source_batch,
+    Tensor? target_batch, int kernel, float c, float eps_I, float[] poly, bool transpose) -> Tensor (not in the reference):
+    the gradient of ``nfft_nearfield`` at the targets, ``G_i = sum_{j: 0 < r_ij < eps_I} g(r_ij^2) (t_i - s_j) x_j`` with
+    ``g(r^2) = (K'(r) - T_I'(r)) / r`` and ``T_I'(r) / r = sum_k poly[k] (r / eps_I)^(2k)`` (``p - 1`` coefficients:
+    ``RegularizedKernel.near_gradient_poly``).  ``transpose=False``: ``x`` ``[n_s, *cols]`` gives ``[n_t, dim, *cols]``;
+    ``transpose=True``: ``x`` ``[n_t, dim, *cols]`` gives ``[n_s, *cols]``, ``sum_i g(r_ij^2) (t_i - s_j) . x_i``.  Cell
+    ordering as for ``nfft_nearfield``; the pair sum is one native call (``nfft_hip_nearfield_gradient``; DESIGN.md section
+    7e)."""
+    return _ops._nfft_nearfield_gradient(sources, targets, x, source_batch, target_batch, int(kernel), float(c),
+                                         float(eps_I), [float(a) for a in poly], bool(transpose))
+
+
 class _on_device:
     """The coefficient operators create their output on the current device (like the reference, which has no
     device argument); ``device=`` selects it for the duration of the call."""
