@@ -3,7 +3,9 @@ the C3 size from a trace build
 (scripts/exp_build.sh spread_mfma.hip trace:torch_nfft_amd/csrc/spread_mfma.hip:"-DNFFT_HIP_TRACE", or the same with
 interp_stream.hip; NFFT_HIP_LIB=scripts/ubench/libnfft_trace.so).  Prints how busy the CUs are over the launch, the
 workgroups resident over time, the share of the per-item prologue and the tail, and saves the raw stamps as .npy.
-(The gather's stamps: entry, end of the item's set-up, end of its last wave; [5] = blocks of 32 points and points.)"""
+(The gather's stamps: entry, end of the item's set-up, end of its last wave; [5] = blocks of 32 points and points.  A
+trace build of interp_stream.hip also fills a second buffer, nfft_dbg_set_stream_phase: where the first producer and the
+first consumer wave of every item spend their time, printed for interior and edge column pencils separately.)"""
 import ctypes, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -33,6 +35,9 @@ gather = os.environ.get("KERNEL", "spread") == "interp"
 if gather:
     y = torch.empty(n, device="cuda")
     assert lib.nfft_dbg_set_stream_trace(p(trace)) == 0
+    phase = torch.zeros((nwg, 16), dtype=torch.int64, device="cuda") if hasattr(lib, "nfft_dbg_set_stream_phase") else None
+    if phase is not None:
+        assert lib.nfft_dbg_set_stream_phase(p(phase)) == 0
     _lib.check(lib.nfft_hip_spread(ctypes.byref(prob), p(plan), p(x), 1, p(grid), p(scratch), s))
     call = lambda: _lib.check(lib.nfft_hip_interpolate(ctypes.byref(prob), p(plan), p(grid), 1, p(y), s))
 else:
@@ -42,6 +47,8 @@ for it in range(3):
     call()
 torch.cuda.synchronize()
 trace.zero_()
+if gather and phase is not None:
+    phase.zero_()
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 call()
@@ -50,6 +57,7 @@ print("call: %.3f ms (%s + overflow launch)" % ((time.perf_counter() - t0) * 1e3
 t = trace.cpu().numpy().astype(np.int64)
 ran = t[:, 0] != 0
 t = t[ran]
+ph = phase.cpu().numpy().astype(np.float64)[ran] if gather and phase is not None else None
 out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
 os.makedirs(out, exist_ok=True)
 np.save(os.path.join(out, "%s_trace_%s.npy" % ("interp" if gather else "spread", os.environ.get("TRACE_TAG", "c3"))), t)
@@ -99,3 +107,23 @@ for a, b_ in zip(edges[:-1], edges[1:]):
     ov = np.clip(np.minimum(end[w], b_) - np.maximum(start[w], a), 0, None).sum() / (b_ - a)
     occ.append(ov)
 print("workgroups resident over time (20 bins): " + " ".join("%.0f" % o for o in occ))
+if gather:
+    # the fitted cost per staged slab (profiles/r08_graded_items.md: 2.05 us x slabs + 8 us)
+    if ph is not None and (ph[w][:, 5] > 0).any():
+        pw = ph[w]
+        sel = pw[:, 5] > 0
+        A = np.stack([pw[sel, 5] * 4, np.ones(sel.sum())], axis=1)  # (producer 0 stages a quarter of the item's planes)
+        coef = np.linalg.lstsq(A, dur[sel], rcond=None)[0]
+        print("fit: item us = %.3f x planes staged + %.1f" % (coef[0], coef[1]))
+        names = ["waiting for loads", "maximum", "waiting for the ring", "conversion + writes + publishing", "bookkeeping + issuing loads"]
+        for label, grp in (("interior pencils", sel & (pw[:, 6] == 0)), ("edge column pencils", sel & (pw[:, 6] != 0))):
+            if not grp.any():
+                continue
+            tot = pw[grp, :5].sum()
+            print("%s: %d items, %.0f planes per producer and item, %.0f ticks per plane; item us mean %.1f" % (
+                label, grp.sum(), pw[grp, 5].mean(), tot / pw[grp, 5].sum(), dur[grp].mean()))
+            print("  producer 0, ticks per plane: " + "; ".join("%s %.0f (%.0f %%)" % (
+                n_, pw[grp, k].sum() / pw[grp, 5].sum(), 100 * pw[grp, k].sum() / tot) for k, n_ in enumerate(names)))
+            cw, co, cb = pw[grp, 8].sum(), pw[grp, 9].sum(), pw[grp, 10].sum()
+            print("  consumer 0: waiting for ready %.1f %% of its time (%.0f ticks per block), everything else %.0f ticks per block" % (
+                100 * cw / max(cw + co, 1), cw / max(cb, 1), co / max(cb, 1)))

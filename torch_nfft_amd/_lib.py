@@ -212,6 +212,10 @@ def load():
     lib.nfft_hip_profile_stages.restype = None
     lib.nfft_hip_profile_collect.argtypes = [vp, vp, ci]
     lib.nfft_hip_profile_collect.restype = ci
+    # test entry of csrc/selftest.hip (not part of the C ABI: a library built from an older tree may lack it)
+    if hasattr(lib, "nfft_dbg_wave_reduce"):
+        lib.nfft_dbg_wave_reduce.argtypes = [ci, i64, vp, vp, vp]
+        lib.nfft_dbg_wave_reduce.restype = ci
     if lib.nfft_hip_abi_version() != ABI_VERSION:
         raise ImportError("torch_nfft_amd: ABI version mismatch in %s" % LIB_PATH)
     _lib = lib
@@ -253,6 +257,20 @@ def profile_collect():
     cnt = (ctypes.c_int64 * n)()
     check(load().nfft_hip_profile_collect(ms, cnt, n))
     return {STAGES[i]: (float(ms[i]), int(cnt[i])) for i in range(n)}
+
+
+def wave_reduce(kind, values):
+    """Test entry ``nfft_dbg_wave_reduce``: ``values`` is a 4-byte CUDA tensor of 64 * waves elements; wave w reduces
+    elements 64 w ... 64 w + 63 with ``wave_max_f32`` (kind "max_f32") or ``wave_min_i32`` (kind "min_i32") of
+    csrc/wave_reduce.h.  Returns one element per wave, same dtype."""
+    import torch
+    assert values.is_cuda and values.is_contiguous() and values.element_size() == 4 and values.numel() % 64 == 0
+    out = torch.empty(values.numel() // 64, dtype=values.dtype, device=values.device)
+    stream = torch.cuda.current_stream().cuda_stream
+    check(load().nfft_dbg_wave_reduce({"max_f32": 0, "min_i32": 1}[kind], values.numel() // 64,
+                                       ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                       ctypes.c_void_p(stream)))
+    return out
 
 
 def check_status(stream=None, synchronize=True):

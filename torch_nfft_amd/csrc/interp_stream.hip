@@ -7,8 +7,14 @@
 // chunk (all waves wait for the loads), barrier, every wave takes one block, barrier ... -- measured at config C3:
 // staging alone 0.44 ms, compute alone 1.30 ms, nothing overlaps (profiles/r02_experiments.md).  Here
 //   * 4 producer waves stage planes continuously: wave p takes the ring slots s = p (mod 4) of the item's sweep,
-//     loads the padded 32 x 64 tile (the next plane's loads are in flight while the current one is converted),
-//     scales it by its own power of two, f16-splits it into the ring slot z & 15 and publishes ready[slot] = z;
+//     loads the padded 32 x 64 tile, scales it by its own power of two, f16-splits it into the ring slot z & 15 and
+//     publishes ready[slot] = z.  A producer's per-plane chain holds ONE LDS round trip besides the eight fragment
+//     writes, and that one only when it has to wait: which planes it stages is a bit mask built at the item's set-up,
+//     the tile's maximum is reduced in registers (wave_reduce.h), the slowest consumer's progress is cached and read
+//     again (one read: the twelve progress words and the abort flag, reduced in registers) only when the cached value
+//     does not allow the slot, every address of a plane is formed at set-up, and two register tiles take turns so
+//     that the next plane's loads are in flight for the whole conversion of the current one (profiles/
+//     r11_gather_staging.md);
 //   * 12 consumer waves pull blocks from an LDS counter.  A block is 32 points of ONE chunk (17 - (2m+2) slabs, so its
 //     window is at most the 16 planes of the ring) and, when the plan is ordered by column group (common.h), of ONE
 //     group: its windows then lie inside two of the tile's four 16-column k-steps, which halves the MFMAs, the B
@@ -20,17 +26,21 @@
 //     A fragments of the next plane are requested as soon as the MFMAs that read a buffer are issued;
 //   * a wave claims its next block and fetches that block's points while it works on the current one;
 //   * a producer may overwrite slot z & 15 once every consumer's progress is beyond z - 16.  The slowest consumer
-//     needs planes below progress + 16 only, so the producers can always serve it: no cycle of waits.
+//     needs planes below progress + 16 only, so the producers can always serve it: no cycle of waits.  The producers
+//     judge this by a cached minimum of progress[]; progress only grows within an item, so a stale minimum only ever
+//     under-estimates it: it can send a producer to read the words again, never past a consumer.
 // Every spin loop is bounded (kSpinLimit): a logic error never hangs the GPU; the wave that runs out raises the
 // device's fault flag (common.h report_fault), everybody leaves the item, and the next entry point of the C ABI
 // returns NFFT_HIP_EKERNEL instead of handing out the unfinished rows as a result.
 #include <algorithm>
 #include <climits>
+#include <type_traits>
 
 #include "common.h"
 #include "kernels.h"
 #include "mfma_split.h"
 #include "range_items.h"
+#include "wave_reduce.h"
 
 namespace nfft {
 
@@ -53,9 +63,28 @@ __device__ unsigned long long *g_stream_trace = nullptr;
             atomicMax(NFFT_GTRACE_AT(6), now_);                                                                   \
         }                                                                                                         \
     } while (0)
+// Second buffer, sixteen words per workgroup (nfft_dbg_set_stream_phase): where the first producer wave and the first
+// consumer wave of an item spend their time, as sums of shader-clock ticks (s_memtime).  Producer, per staged plane: [0]
+// waiting for the plane's loads, [1] the tile's maximum, [2] waiting for the ring (progress), [3] conversion, fragment
+// writes and publishing, [4] bookkeeping: the next plane and issuing its loads; [5] planes staged, [6] 1 in an edge column
+// pencil.  Consumer: [8] waiting for ready, [9] everything else, [10] blocks.  (The stamps wait for the scalar cache, which
+// also drains the wave's LDS queue: the split is a guide to the order of magnitude of each part, not a cycle count.)
+__device__ unsigned long long *g_stream_phase = nullptr;
+#define NFFT_PHASE_AT(slot) (&g_stream_phase[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + (slot)])
+#define NFFT_PHASE(k)                                                                                             \
+    do {                                                                                                          \
+        if (phase_on) {                                                                                           \
+            const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                         \
+            ph[k] += now_ - ph_t;                                                                                 \
+            ph_t = now_;                                                                                          \
+        }                                                                                                         \
+    } while (0)
+#define NFFT_PHASE_WAIT_LOADS(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
 #else
 #define NFFT_GTRACE(slot, value) do { } while (0)
 #define NFFT_GTRACE_END() do { } while (0)
+#define NFFT_PHASE(k) do { } while (0)
+#define NFFT_PHASE_WAIT_LOADS(n) do { } while (0)
 #endif
 
 namespace {
@@ -64,7 +93,11 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kIsThreads = 1024;
 constexpr int kIsWaves = kIsThreads / 64;
-constexpr int kIsProducers = 4;      // measured at C3: 3 producers 1.50 ms, 4: 1.41, 5: 1.50 (each owns 16 / 4 ring slots)
+#ifndef NFFT_STREAM_PRODUCERS
+#define NFFT_STREAM_PRODUCERS 4
+#endif
+constexpr int kIsProducers = NFFT_STREAM_PRODUCERS;  // measured at C3: 3 producers 1.50 ms, 4: 1.41, 5: 1.50 (each owns 16 / 4 ring slots)
+static_assert(16 % kIsProducers == 0, "a ring slot has one owner: the producer count divides the ring");
 constexpr int kIsConsumers = kIsWaves - kIsProducers;
 constexpr int kIsRing = 16;          // resident planes: TC + 2m+1 = 16 for every cutoff of the wide tiling
 constexpr int kIsMaxSlabs = 160;     // slabs the chunks of one work item cover (<= kItemMaxSlabs + 2 TC)
@@ -113,6 +146,14 @@ __device__ __forceinline__ int lds_load(const int *p)
 __device__ __forceinline__ void lds_store(int *p, int v)
 {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// bit c of the 192-bit mask {w0, w1, w2} (arguments by value: a choice between captured words becomes one between their
+// addresses, and the words then live in scratch memory)
+__device__ __forceinline__ bool bit192(unsigned long long w0, unsigned long long w1, unsigned long long w2, int c)
+{
+    const unsigned long long w = c < 64 ? w0 : c < 128 ? w1 : w2;
+    return (w >> (c & 63)) & 1;
 }
 
 // NG: column groups of the plan (3, or 1 for plans without the group order: every block then spans all four k-steps)
@@ -222,118 +263,218 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
         // ================================ producer: planes z = z_begin + p, + 4, ... ================================
         const int p = wave - kIsConsumers;
         const int z_begin = k_begin * TC - m, z_end = (k_end - 1) * TC + SPAN - m;  // planes any chunk of the item needs
-        // a lane's 4 tasks of a plane: (row, group of 8 columns); 16 consecutive lanes = 16 consecutive rows of one
-        // column group -> consecutive 16-byte LDS slots on the way out, half rows of 128 contiguous bytes on the way in
-        auto needed = [&](const int z) {
-            // plane z is used by chunk k iff k TC - m <= z <= k TC + TC + m: at most three candidates
-            const int k_hi = min(k_end - 1, (z + m) / TC), k_lo = max(k_begin, (z - TC - m + TC - 1) / TC);
-            for (int k = k_lo; k <= k_hi; ++k) {
-                if (k < k_begin) continue;
-                const int lo = (k - k_begin) * TC, hi = min(lo + TC, nsl);
-                if (L.run_start[hi * NG] > L.run_start[lo * NG]) return true;
-            }
-            return false;
+        // ---- set-up of the sweep, once per item: everything below stays in registers ------------------------------
+        // (1) Which planes are mine to stage.  Chunk c of the item (slabs c TC ... c TC + TC - 1 of its range) uses the
+        // planes c TC ... c TC + SPAN - 1 of the sweep (counted from z_begin) iff it holds points; a ring slot belongs
+        // to ONE producer (slot mod kIsProducers): planes z and z + 16 share a slot, and only one wave staging them in
+        // order keeps a late plane z from overwriting (and un-publishing) plane z + 16.  Both go into one bit mask over
+        // the sweep's <= kIsMaxSlabs + 16 planes, which the loop walks with scalar bit scans: no LDS look-up per plane.
+        static_assert(kIsMaxSlabs + kIsRing <= 192, "three 64-bit words hold the sweep");
+        const int nchunks = k_end - k_begin;
+        const auto chunk_live = [&](const int c) {
+            if (c >= nchunks) return false;
+            const int lo = c * TC, hi = min(lo + TC, nsl);
+            return L.run_start[hi * NG] > L.run_start[lo * NG];
         };
-        auto load_plane = [&](const int z, f32x4 (&v)[8]) {
-            const int64_t gz = wrap(z, M);
+        const unsigned long long cm0 = __builtin_amdgcn_ballot_w64(chunk_live(lane)), cm1 = __builtin_amdgcn_ballot_w64(chunk_live(64 + lane)),
+                                 cm2 = __builtin_amdgcn_ballot_w64(chunk_live(128 + lane));
+        const auto plane_mine = [&](const int r) {
+            const int z = z_begin + r;
+            if (z >= z_end || ((z & (kIsRing - 1)) % kIsProducers) != p) return false;
+            const int c_hi = min(nchunks - 1, r / TC), c_lo = max(0, (r - SPAN + TC) / TC);
+            bool any = false;
+            for (int c = c_lo; c <= c_hi; ++c) any |= bit192(cm0, cm1, cm2, c);
+            return any;
+        };
+        const unsigned long long pm0 = __builtin_amdgcn_ballot_w64(plane_mine(lane)), pm1 = __builtin_amdgcn_ballot_w64(plane_mine(64 + lane)),
+                                 pm2 = __builtin_amdgcn_ballot_w64(plane_mine(128 + lane));
+        // first plane >= z (z >= z_begin) of this producer's sequence that some chunk needs; z_end: none
+        const auto next_needed = [&](const int z) {
+            const int r = z - z_begin;
+            unsigned long long w = r < 64 ? pm0 & (~0ull << r) : 0ull;
+            if (w) return z_begin + __builtin_ctzll(w);
+            w = r < 128 ? (r > 64 ? pm1 & (~0ull << (r - 64)) : pm1) : 0ull;
+            if (w) return z_begin + 64 + __builtin_ctzll(w);
+            w = r < 192 ? (r > 128 ? pm2 & (~0ull << (r - 128)) : pm2) : 0ull;
+            if (w) return z_begin + 128 + __builtin_ctzll(w);
+            return z_end;
+        };
+        // (2) Where a plane's values come from.  A lane's 4 tasks of a plane: (row, group of 8 columns); 16 consecutive
+        // lanes = 16 consecutive rows of one column group -> consecutive 16-byte LDS slots on the way out, half rows of
+        // 128 contiguous bytes on the way in.  Each task is two 16-byte halves; off[] is the half's offset inside a
+        // plane, rows and columns wrapped.  In the first and last column pencil a half may begin beyond column M - 1:
+        // it is still ONE vector load, at the wrapped address.  Only a half that straddles columns M - 1 | 0 is not
+        // contiguous -- at most one (column group, half) per lane, because a lane's halves are 4 ... 36 columns apart
+        // and M >= 64, so it is the same half of both tasks of that column group (rows r and r + 16).  Such a half is
+        // loaded as the row's last four columns, the lane loads the first four columns of its two rows on top (xoff[],
+        // two more vector loads in an edge pencil), and the half is put together in registers when the plane is
+        // converted: `before` = its columns in front of the wrap (1 ... 3).  Every load of a plane is a vector load
+        // into registers of its own from an address formed here: nothing between them to wait for.
+        int off[8], xoff[2] = {0, 0};
+        unsigned straddle = 0;
+        int before = 4;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int t = lane + 64 * i;
-                const int cg = ((t >> 4) & 3) + 4 * ((t >> 7) & 1), row = (t & 15) + 16 * ((t >> 6) & 1);
-                const int64_t g1 = wrap_near(tb1 - m + row, M);
-                const float *const grow = gplane + (gz * M + g1) * M;
-                const int c0 = tb2 - m + 8 * cg;
-                if (c0 >= 0 && c0 + 8 <= M) {
-                    v[2 * i] = *(const f32x4_dw *)(grow + c0);
-                    v[2 * i + 1] = *(const f32x4_dw *)(grow + c0 + 4);
-                } else {
-                    f32x4 a, c;
-                    a.x = grow[wrap_near(c0 + 0, M)]; a.y = grow[wrap_near(c0 + 1, M)];
-                    a.z = grow[wrap_near(c0 + 2, M)]; a.w = grow[wrap_near(c0 + 3, M)];
-                    c.x = grow[wrap_near(c0 + 4, M)]; c.y = grow[wrap_near(c0 + 5, M)];
-                    c.z = grow[wrap_near(c0 + 6, M)]; c.w = grow[wrap_near(c0 + 7, M)];
-                    v[2 * i] = a;
-                    v[2 * i + 1] = c;
+        for (int i = 0; i < 4; ++i) {
+            const int t = lane + 64 * i;
+            const int cg = ((t >> 4) & 3) + 4 * ((t >> 7) & 1), row = (t & 15) + 16 * ((t >> 6) & 1);
+            const int g1 = wrap_near(tb1 - m + row, M);
+            if (i < 2) xoff[i] = g1 * M;  // (the row of task i is the row of task i + 2)
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                const int w = wrap_near(tb2 - m + 8 * cg + 4 * hf, M);
+                off[2 * i + hf] = g1 * M + min(w, M - 4);
+                if (w + 4 > M) {
+                    straddle |= 1u << (2 * i + hf);
+                    before = M - w;
                 }
             }
-        };
-        // Next plane >= z of this producer's sequence that some chunk needs.  A ring slot belongs to ONE producer
-        // (slot mod kIsProducers): planes z and z + 16 share a slot, and only one wave staging them in order keeps a
-        // late plane z from overwriting (and un-publishing) plane z + 16.
-        auto next_needed = [&](int z) {
-            while (z < z_end && (((z & (kIsRing - 1)) % kIsProducers) != p || !needed(z))) ++z;
-            return z;
-        };
-        int z = next_needed(z_begin);
-        f32x4 cur[8], nxt[8];
-        if (z < z_end) load_plane(z, cur);
-        while (z < z_end) {
-            const int zn = next_needed(z + 1);
-            if (zn < z_end) load_plane(zn, nxt);
-            // power-of-two scale of the tile; odd planes are stored negated (un-negated through pinv): the MFMA
-            // accumulation truncates with a small sign-independent bias that cancels over alternating planes
-            float mx = 0.0f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-                mx = fmaxf(fmaxf(fmaxf(mx, fabsf(cur[e].x)), fabsf(cur[e].y)), fmaxf(fabsf(cur[e].z), fabsf(cur[e].w)));
-            for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-            float scale = 1.0f, inv = 1.0f;
-            if (mx > 1.0e-30f && mx < 3.0e38f) {
-                int ex;
-                frexpf(mx, &ex);
-                scale = ldexpf(1.0f, 11 - ex);
-                inv = ldexpf(1.0f, ex - 11);
-            }
-            const int slot = z & (kIsRing - 1);
-            if (slot & 1) { scale = -scale; inv = -inv; }
-            // the slot's previous plane, z - 16, must be behind every consumer
-            int spins = 0;
-            while (true) {
-                int lo = lane < kIsConsumers ? lds_load(&L.progress[lane]) : INT_MAX;
-                for (int off = 32; off >= 1; off >>= 1) lo = min(lo, __shfl_xor(lo, off));
-                if (lo > z - kIsRing || lds_load(&L.abort)) break;
-                if (++spins > kSpinLimit) {
-                    lds_store(&L.abort, 1);
-                    if (lane == 0) report_fault(status, kFaultStreamStall);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(4);
-            }
-            lds_acquire();
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int t = lane + 64 * i;
-                const int cg = ((t >> 4) & 3) + 4 * ((t >> 7) & 1), row = (t & 15) + 16 * ((t >> 6) & 1);
-                const f32x4 a = cur[2 * i], c = cur[2 * i + 1];
-                unsigned h0, h1, h2, h3, q0, q1, q2, q3;
-                split_pair(a.x * scale, a.y * scale, h0, q0);
-                split_pair(a.z * scale, a.w * scale, h1, q1);
-                split_pair(c.x * scale, c.y * scale, h2, q2);
-                split_pair(c.z * scale, c.w * scale, h3, q3);
-                const int ln = 32 * (cg & 1) + row;
-                L.frag[slot][cg >> 1][0][ln] = __builtin_bit_cast(f16x8, u32x4{h0, h1, h2, h3});
-                L.frag[slot][cg >> 1][1][ln] = __builtin_bit_cast(f16x8, u32x4{q0, q1, q2, q3});
-            }
-            if (lane == 0) L.pinv[slot] = inv * (1.0f / kOpScale);
-            lds_release();
-            if (lane == 0) lds_store(&L.ready[slot], z);
-            if (lds_load(&L.abort)) break;
-            // (every consumer gone: nobody reads what is left of the sweep)
-            {
-                int lo = lane < kIsConsumers ? lds_load(&L.progress[lane]) : INT_MAX;
-                for (int off = 32; off >= 1; off >>= 1) lo = min(lo, __shfl_xor(lo, off));
-                if (lo == INT_MAX) break;
-            }
-            z = zn;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) cur[e] = nxt[e];
         }
+        struct Tile {
+            f32x4 v[8];  // the 8 halves
+            f32x4 x[2];  // edge pencils: columns 0 ... 3 of the lane's two rows
+        };
+        // (3) The slowest consumer, as last seen.  progress[] only grows within an item (s0 - m at set-up, INT_MAX when
+        // a consumer is done), so a value read earlier is a lower bound of the present one: if IT already allows a slot
+        // the producer goes ahead without reading, and it reads again only when it would have to wait.  A stale value
+        // under-estimates progress -- it can make the producer read, never proceed early -- and a producer that reads
+        // sees what the per-plane poll saw before: the no-cycle argument of the header is unchanged.  One read serves
+        // everything: lanes 0 ... 11 take progress[lane], the others the abort flag as INT_MIN (raised) or INT_MAX, and
+        // the minimum is formed in registers (wave_reduce.h): INT_MIN = abort, INT_MAX = every consumer gone.
+        int lo_seen = z_begin;
+#ifdef NFFT_HIP_TRACE
+        const bool phase_on = !OVERFLOW && p == 0 && g_stream_phase;
+        unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, ph_t = __builtin_amdgcn_s_memtime();
+#endif
+        // The sweep, for interior (EDGE = false) and edge column pencils.  Two tiles take turns: while one is converted
+        // the loads of the next needed plane fill the other, and no value is copied between them.  Every path through
+        // the loop issues the same number of loads per plane (past the end of the sweep the current plane is requested
+        // again and dropped), so the wait in front of a tile's first use is "all but the loads issued after its own":
+        // a count the compiler can state.  (With loads under a condition, or a copy `cur = nxt` at the loop's end, every
+        // plane was waited for right after its loads were issued.)
+        const auto sweep = [&](auto edge_tag) {
+            constexpr bool EDGE = decltype(edge_tag)::value;
+            const auto load_plane = [&](const int z, Tile &t) {
+                const float *const base = gplane + (int64_t)wrap(z, M) * M * M;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) t.v[k] = *(const f32x4_dw *)(base + off[k]);
+                if constexpr (EDGE) {
+                    t.x[0] = *(const f32x4_dw *)(base + xoff[0]);
+                    t.x[1] = *(const f32x4_dw *)(base + xoff[1]);
+                }
+            };
+            // converts plane z from tile t into its ring slot and publishes it; false: leave the sweep
+            const auto stage = [&](const int z, Tile &t) {
+                NFFT_PHASE(4);
+                NFFT_PHASE_WAIT_LOADS(EDGE ? 10 : 8);  // (this tile's loads: all but the other tile's, issued after them)
+                NFFT_PHASE(0);
+                if constexpr (EDGE) {
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        if ((straddle >> k) & 1) {  // columns M - before ... M - 1 from v, then 0 ... from x
+                            const f32x4 a = t.v[k], c = t.x[(k >> 1) & 1];
+                            f32x4 r;
+                            r.x = before == 1 ? a.w : before == 2 ? a.z : a.y;
+                            r.y = before == 1 ? c.x : before == 2 ? a.w : a.z;
+                            r.z = before == 1 ? c.y : before == 2 ? c.x : a.w;
+                            r.w = before == 1 ? c.z : before == 2 ? c.y : c.x;
+                            t.v[k] = r;
+                        }
+                    }
+                }
+                // power-of-two scale of the tile; odd planes are stored negated (un-negated through pinv): the MFMA
+                // accumulation truncates with a small sign-independent bias that cancels over alternating planes
+                float mx = 0.0f;
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    mx = fmaxf(fmaxf(fmaxf(mx, fabsf(t.v[e].x)), fabsf(t.v[e].y)), fmaxf(fabsf(t.v[e].z), fabsf(t.v[e].w)));
+                mx = wave_max_f32(mx);
+                NFFT_PHASE(1);
+                float scale = 1.0f, inv = 1.0f;
+                if (mx > 1.0e-30f && mx < 3.0e38f) {
+                    int ex;
+                    frexpf(mx, &ex);
+                    scale = ldexpf(1.0f, 11 - ex);
+                    inv = ldexpf(1.0f, ex - 11);
+                }
+                const int slot = z & (kIsRing - 1);
+                if (slot & 1) { scale = -scale; inv = -inv; }
+                // the slot's previous plane, z - 16, must be behind every consumer
+                if (lo_seen <= z - kIsRing) {
+                    int spins = 0;
+                    while (true) {
+                        const int word = lds_load(lane < kIsConsumers ? &L.progress[lane] : &L.abort);
+                        lo_seen = wave_min_i32(lane < kIsConsumers ? word : word ? INT_MIN : INT_MAX);
+                        if (lo_seen > z - kIsRing || lo_seen == INT_MIN) break;
+                        if (++spins > kSpinLimit) {
+                            lds_store(&L.abort, 1);
+                            if (lane == 0) report_fault(status, kFaultStreamStall);
+                            lo_seen = INT_MIN;
+                            break;
+                        }
+                        __builtin_amdgcn_s_sleep(4);
+                    }
+                }
+                NFFT_PHASE(2);
+                // (abort: everybody leaves; every consumer gone: nobody reads what is left of the sweep)
+                if (lo_seen == INT_MIN || lo_seen == INT_MAX) return false;
+                lds_acquire();
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int tk = lane + 64 * i;
+                    const int cg = ((tk >> 4) & 3) + 4 * ((tk >> 7) & 1), row = (tk & 15) + 16 * ((tk >> 6) & 1);
+                    const f32x4 a = t.v[2 * i], c = t.v[2 * i + 1];
+                    unsigned h0, h1, h2, h3, q0, q1, q2, q3;
+                    split_pair(a.x * scale, a.y * scale, h0, q0);
+                    split_pair(a.z * scale, a.w * scale, h1, q1);
+                    split_pair(c.x * scale, c.y * scale, h2, q2);
+                    split_pair(c.z * scale, c.w * scale, h3, q3);
+                    const int ln = 32 * (cg & 1) + row;
+                    L.frag[slot][cg >> 1][0][ln] = __builtin_bit_cast(f16x8, u32x4{h0, h1, h2, h3});
+                    L.frag[slot][cg >> 1][1][ln] = __builtin_bit_cast(f16x8, u32x4{q0, q1, q2, q3});
+                }
+                if (lane == 0) L.pinv[slot] = inv * (1.0f / kOpScale);
+                lds_release();
+                if (lane == 0) lds_store(&L.ready[slot], z);
+                NFFT_PHASE(3);
+#ifdef NFFT_HIP_TRACE
+                ph[5] += 1;
+#endif
+                return true;
+            };
+            int z = next_needed(z_begin);
+            if (z >= z_end) return;
+            Tile ta, tb;
+            load_plane(z, ta);
+            while (true) {
+                int zn = next_needed(z + 1);
+                load_plane(zn < z_end ? zn : z, tb);
+                if (!stage(z, ta) || zn >= z_end) break;
+                z = zn;
+                zn = next_needed(z + 1);
+                load_plane(zn < z_end ? zn : z, ta);
+                if (!stage(z, tb) || zn >= z_end) break;
+                z = zn;
+            }
+        };
+        const bool edge_pencil = __builtin_amdgcn_ballot_w64(straddle != 0) != 0ull;  // (wave-uniform)
+        if (edge_pencil) sweep(std::true_type{});
+        else sweep(std::false_type{});
+#ifdef NFFT_HIP_TRACE
+        if (phase_on && lane == 0) {
+            for (int k = 0; k < 6; ++k) *NFFT_PHASE_AT(k) = ph[k];
+            *NFFT_PHASE_AT(6) = edge_pencil;
+        }
+#endif
     } else {
         // ================================ consumer: blocks from the queue ===========================================
         // A wave claims its next block while it still works on the current one and fetches that block's points (sorted
         // position, output index) early.  Near the end of the queue blocks are claimed only when the wave is ready
         // for them, so that no wave sits on a block while others run dry.
         int run = 0;  // run of the last claimed block's first point: only moves forward
+#ifdef NFFT_HIP_TRACE
+        const bool phase_on = !OVERFLOW && wave == 0 && g_stream_phase;
+        unsigned long long ph[3] = {0, 0, 0}, ph_t = __builtin_amdgcn_s_memtime();
+#endif
         auto claim = [&]() {
             // all 64 lanes add 1 (one ds_add of 64 per wave): the counter runs in units of 64
             return __builtin_amdgcn_readfirstlane(atomicAdd(&L.next_block, 1)) >> 6;
@@ -448,12 +589,17 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
                 const int zs = z_first + ((lane - z_first) & (kIsRing - 1));  // the plane of my window that lives in slot `lane`
                 const bool need = lane < kIsRing && zs <= z_last;
                 int spins = 0;
+                NFFT_PHASE(1);
                 while (true) {
                     const int v = need ? lds_load(&L.ready[lane]) : zs;
                     if (__builtin_amdgcn_ballot_w64(v != zs) == 0ull) break;
                     if (lds_load(&L.abort) || ++spins > kSpinLimit) { bail = true; break; }
                     __builtin_amdgcn_s_sleep(2);
                 }
+                NFFT_PHASE(0);
+#ifdef NFFT_HIP_TRACE
+                ph[2] += 1;
+#endif
                 lds_acquire();
             }
             if (bail) {
@@ -520,6 +666,14 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
             blk = nblk; idx = nidx; grp = ngrp; pj = npj;
             q0 = n0; q1 = n1; q2 = n2;
         }
+#ifdef NFFT_HIP_TRACE
+        NFFT_PHASE(1);
+        if (phase_on && lane == 0) {
+            *NFFT_PHASE_AT(8) = ph[0];
+            *NFFT_PHASE_AT(9) = ph[1];
+            *NFFT_PHASE_AT(10) = ph[2];
+        }
+#endif
         // nothing of the ring is mine any more: the producers may run to the end of their sweep
         lds_release();
         if (lane == 0) lds_store(&L.progress[wave], INT_MAX);
@@ -534,6 +688,10 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
 extern "C" int nfft_dbg_set_stream_trace(void *device_buffer)
 {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stream_trace), &device_buffer, sizeof(device_buffer));
+}
+extern "C" int nfft_dbg_set_stream_phase(void *device_buffer)  // 16 words per workgroup, as g_stream_trace's 8
+{
+    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stream_phase), &device_buffer, sizeof(device_buffer));
 }
 #endif
 

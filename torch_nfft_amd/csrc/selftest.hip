@@ -3,8 +3,11 @@
 // is built with -ffp-contract=fast; twice a compiler-fused residual broke one of these silently,
 // so they are written in inline asm and pinned here.  Not part of the C ABI of include/nfft_hip.h (no reference
 // counterpart); exported as nfft_dbg_eft for the test.
+// Second entry, nfft_dbg_wave_reduce: the register-only wave reductions of wave_reduce.h applied wave by wave to a
+// caller's buffer (tests/test_gpu_wave_reduce.py compares them with numpy as bit patterns).
 #include "common.h"
 #include "mfma_split.h"
+#include "wave_reduce.h"
 
 namespace nfft {
 namespace {
@@ -37,6 +40,17 @@ __global__ void __launch_bounds__(256) eft_kernel(int kind, int64_t n, int M, co
     }
 }
 
+// wave w reduces in[64 w ... 64 w + 63] to out[w]; kind 0: wave_max_f32, kind 1: wave_min_i32 (values as bit patterns)
+__global__ void __launch_bounds__(256) wave_reduce_kernel(int kind, int64_t waves, const unsigned *__restrict__ in, unsigned *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < waves; w += (int64_t)gridDim.x * 4) {  // (wave-uniform)
+        const unsigned v = in[w * 64 + lane];
+        const unsigned r = kind == 0 ? __float_as_uint(wave_max_f32(__uint_as_float(v))) : (unsigned)wave_min_i32((int)v);
+        if (lane == 0) out[w] = r;
+    }
+}
+
 } // namespace
 } // namespace nfft
 
@@ -47,5 +61,15 @@ extern "C" int nfft_dbg_eft(int kind, int64_t n, int M, const void *a, const voi
     const unsigned blocks = (unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
     hipLaunchKernelGGL(nfft::eft_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, kind, n, M, (const unsigned *)a,
                        (const unsigned *)b, (const unsigned *)c, (const unsigned *)d, (unsigned *)out0, (unsigned *)out1);
+    return (int)hipGetLastError();
+}
+
+extern "C" int nfft_dbg_wave_reduce(int kind, int64_t waves, const void *in, void *out, void *stream)
+{
+    if (waves <= 0) return 0;
+    if (kind != 0 && kind != 1) return 1;
+    const unsigned blocks = (unsigned)((waves + 3) / 4 > 4096 ? 4096 : (waves + 3) / 4);
+    hipLaunchKernelGGL(nfft::wave_reduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, kind, waves, (const unsigned *)in,
+                       (unsigned *)out);
     return (int)hipGetLastError();
 }
