@@ -352,6 +352,32 @@ int nfft_hip_nearfield_gradient(const nfft_hip_nearfield_problem *p, int32_t tra
                                 const int64_t *target_index, const int32_t *target_start, float *out, void *workspace,
                                 int64_t workspace_bytes, void *stream);
 
+/* ---- gradient of that near field with respect to the points ----
+ * For z = nfft_hip_nearfield(xr) and a loss L with dy = dL/dz [n_t, Cr], the pairs and g of nfft_hip_nearfield_gradient:
+ *   dL/dt_i[a] = sum_j g(r_ij^2) (t_i - s_j)[a] sum_c dy[i, c] xr[j, c]
+ *   dL/ds_j[a] = sum_i g(r_ij^2) (s_j - t_i)[a] sum_c xr[j, c] dy[i, c]
+ * Both are one sum, named by what the kernel does with its arguments: with the STREAMED side `streamed` (positions),
+ * `streamed_values` [p->num_sources, Cr], `streamed_start` and the OUTPUT side `output`, `output_values`
+ * [p->num_targets, Cr], `output_index`, `output_start`, all rows in cell order,
+ *   symmetric = 0:  out[output_index[i], a] = sum_j g(r_ij^2) (output_i - streamed_j)[a]
+ *                                             sum_c output_values[i, c] streamed_values[j, c]
+ * so the targets' gradient passes the sum's sources with xr as the streamed side and its targets with dy as the output
+ * side, and the sources' gradient passes them the other way round (targets with dy streamed, sources with xr the output
+ * side).  The difference vector is "output - streamed" in both: no sign to turn.
+ *   symmetric = 1:  the two sides are ONE point set in one cell order (p->num_sources == p->num_targets, the same
+ *                   positions and start table on both sides); the inner sum becomes
+ *                   sum_c output_values[i, c] streamed_values[j, c] + streamed_values[i, c] output_values[j, c]
+ *                   and out is the sum of the two gradients of point i (dy as output_values, xr as streamed_values).
+ * out is [p->num_targets, dim] float32.  gradient_poly, p->poly_terms (>= 2), p->poly, ordering by cell, start tables,
+ * determinism and the workspace are those of nfft_hip_nearfield_gradient.  No output points or no columns: nothing is
+ * done; no streamed points: out is zeroed. */
+int64_t nfft_hip_nearfield_point_gradient_workspace_bytes(const nfft_hip_nearfield_problem *p);
+int nfft_hip_nearfield_point_gradient(const nfft_hip_nearfield_problem *p, int32_t symmetric, const double *gradient_poly,
+                                      const float *streamed, const float *streamed_values, const int32_t *streamed_start,
+                                      const float *output, const float *output_values, const int64_t *output_index,
+                                      const int32_t *output_start, float *out, void *workspace, int64_t workspace_bytes,
+                                      void *stream);
+
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.
  *   gaussian_analytic_coeffs      float32:  prod_d sqrt(pi) sigma exp(-sigma^2 pi^2 l_d^2)      (kernel_coeffs.cu:6-30)

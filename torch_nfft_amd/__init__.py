@@ -17,7 +17,8 @@ from .ndft import ndft_forward, ndft_adjoint, ndft_fastsum, exact_trigonometric_
 from .coeffs import (gaussian_analytic_coeffs, gaussian_interpolated_coeffs, interpolation_grid,  # noqa: E402
                      radial_interpolation_grid, interpolated_kernel_coeffs)
 from .nearfield import (RegularizedKernel, nfft_nearfield, nfft_fastsum_nearfield, NfftNearfieldFunction,  # noqa: E402
-                        nfft_nearfield_gradient, nfft_fastsum_nearfield_gradient, NfftNearfieldGradientFunction)
+                        nfft_nearfield_gradient, nfft_fastsum_nearfield_gradient, NfftNearfieldGradientFunction,
+                        NfftNearfieldPointsFunction)
 from .matrices import GramMatrix, AdjacencyMatrix  # noqa: E402
 from .kernel import GaussianKernel  # noqa: E402
 from . import utils  # noqa: E402
@@ -26,7 +27,7 @@ from . import utils  # noqa: E402
 __all__ = ["nfft_adjoint", "nfft_forward", "nfft_fastsum", "nfft_toeplitz_kernel", "nfft_normal", "nfft_inverse",
            "NfftNormalFunction", "RegularizedKernel", "nfft_nearfield", "nfft_fastsum_nearfield",
            "NfftNearfieldFunction", "nfft_nearfield_gradient", "nfft_fastsum_nearfield_gradient",
-           "NfftNearfieldGradientFunction", "ndft_forward", "ndft_adjoint", "ndft_fastsum",
+           "NfftNearfieldGradientFunction", "NfftNearfieldPointsFunction", "ndft_forward", "ndft_adjoint", "ndft_fastsum",
            "exact_trigonometric_matrix", "exact_gaussian_matrix", "NfftAdjointFunction", "NfftForwardFunction",
            "NfftFastsumFunction", "gaussian_analytic_coeffs", "gaussian_interpolated_coeffs", "interpolation_grid",
            "radial_interpolation_grid", "interpolated_kernel_coeffs", "GramMatrix", "AdjacencyMatrix",

@@ -54,6 +54,8 @@ SYMBOLS = (
     "nfft_hip_nearfield",
     "nfft_hip_nearfield_gradient_workspace_bytes",
     "nfft_hip_nearfield_gradient",
+    "nfft_hip_nearfield_point_gradient_workspace_bytes",
+    "nfft_hip_nearfield_point_gradient",
     "nfft_hip_gaussian_analytic_coeffs",
     "nfft_hip_interpolation_grid",
     "nfft_hip_coeffs_workspace_bytes",
@@ -195,6 +197,11 @@ def load():
     lib.nfft_hip_nearfield_gradient.argtypes = [ctypes.POINTER(NearfieldProblem), ctypes.c_int32, vp,
                                                 vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.nfft_hip_nearfield_gradient.restype = ci
+    lib.nfft_hip_nearfield_point_gradient_workspace_bytes.argtypes = [ctypes.POINTER(NearfieldProblem)]
+    lib.nfft_hip_nearfield_point_gradient_workspace_bytes.restype = i64
+    lib.nfft_hip_nearfield_point_gradient.argtypes = [ctypes.POINTER(NearfieldProblem), ctypes.c_int32, vp,
+                                                      vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.nfft_hip_nearfield_point_gradient.restype = ci
     lib.nfft_hip_gaussian_analytic_coeffs.argtypes = [ctypes.c_double, i64, ctypes.c_int32, vp, vp]
     lib.nfft_hip_gaussian_analytic_coeffs.restype = ci
     lib.nfft_hip_interpolation_grid.argtypes = [i64, ctypes.c_int32, ci, vp, vp]

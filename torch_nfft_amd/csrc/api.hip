@@ -1580,4 +1580,48 @@ int nfft_hip_nearfield_gradient(const nfft_hip_nearfield_problem *p, int32_t tra
                                      target_start, out, ws, s);
 }
 
+// ---- its gradient with respect to the points ----------------------------------------------------
+int64_t nfft_hip_nearfield_point_gradient_workspace_bytes(const nfft_hip_nearfield_problem *p)
+{
+    if (validate_nearfield_gradient(p)) return -1;
+    return nearfield_item_slots(p) * (int64_t)sizeof(int2) + 256;
+}
+
+int nfft_hip_nearfield_point_gradient(const nfft_hip_nearfield_problem *p, int32_t symmetric, const double *gradient_poly,
+                                      const float *streamed, const float *streamed_values, const int32_t *streamed_start,
+                                      const float *output, const float *output_values, const int64_t *output_index,
+                                      const int32_t *output_start, float *out, void *workspace, int64_t workspace_bytes,
+                                      void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_nearfield_gradient(p)) return rc;
+    if (symmetric != 0 && symmetric != 1) { set_error("Input mismatch: symmetric must be 0 or 1"); return NFFT_HIP_EINVAL; }
+    if (symmetric && p->num_sources != p->num_targets) {
+        set_error("Input mismatch: a symmetric sweep needs one point set on both sides");
+        return NFFT_HIP_EINVAL;
+    }
+    if (!gradient_poly) { set_error("Input mismatch: gradient_poly is null"); return NFFT_HIP_EINVAL; }
+    for (int e = 0; e < p->poly_terms - 1; ++e)
+        if (!(gradient_poly[e] == gradient_poly[e]) || gradient_poly[e] > 3e38 || gradient_poly[e] < -3e38) {
+            set_error("Input mismatch: gradient_poly is not finite");
+            return NFFT_HIP_EINVAL;
+        }
+    if (p->num_targets == 0 || p->num_columns == 0) return 0;
+    if (!out) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    if (p->num_sources == 0) {
+        NFFT_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(p->num_targets * p->dim) * sizeof(float), s));
+        return 0;
+    }
+    if (!streamed || !streamed_values || !streamed_start || !output || !output_values || !output_index || !output_start) {
+        set_error("Input mismatch: null input");
+        return NFFT_HIP_EINVAL;
+    }
+    const int64_t need = nearfield_item_slots(p) * (int64_t)sizeof(int2) + 256;
+    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    return launch_nearfield_point_gradient(p, symmetric, gradient_poly, streamed, streamed_values, streamed_start, output,
+                                           output_values, output_index, output_start, out, ws, s);
+}
+
 }  // extern "C"

@@ -886,6 +886,95 @@ at::Tensor nfft_nearfield_gradient(at::Tensor sources, at::Tensor targets, at::T
     return z.reshape(out_shape);
 }
 
+// The gradient of that sum with respect to the points: for z = nfft_nearfield(x) and dy = dL/dz,
+//   dt[i, a] = sum_j g(r_ij^2) (t_i - s_j)[a] sum_c dy[i, c] x[j, c]      [n_t, dim]
+//   ds[j, a] = sum_i g(r_ij^2) (s_j - t_i)[a] sum_c x[j, c] dy[i, c]      [n_s, dim]
+// (ds, dt); a side that is not needed comes back empty.  Real and imaginary parts of complex values are columns.  Each
+// cell order is built once and serves both sweeps: for dt the sources are streamed and the targets are the output side,
+// for ds the other way round.  Shared points with both sides needed take ONE symmetric sweep: the total is returned as ds
+// and dt is zeros.  poly: the p - 1 Horner coefficients of T_I'(r) / r in (r / eps_I)^2.
+std::tuple<at::Tensor, at::Tensor> nfft_nearfield_point_gradient(at::Tensor sources, at::Tensor targets, at::Tensor x,
+                                                                 at::Tensor dy, c10::optional<at::Tensor> opt_source_batch,
+                                                                 c10::optional<at::Tensor> opt_target_batch, int64_t kernel,
+                                                                 double c, double eps_I, at::ArrayRef<double> poly,
+                                                                 bool need_sources, bool need_targets)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_nearfield_point_gradient is currently only implemented for GPU tensors");
+    const Points ps = check_points(sources, opt_source_batch, "(*out_batch)");
+    const bool same_batch = (!opt_source_batch.has_value() && !opt_target_batch.has_value()) ||
+                            (opt_source_batch.has_value() && opt_target_batch.has_value() &&
+                             opt_source_batch->is_same(*opt_target_batch));
+    const bool shared = sources.is_same(targets) && same_batch;
+    const Points pt = shared ? ps : check_points(targets, opt_target_batch, "(*out_batch)");
+    CHECK_INPUT(pt.dim == ps.dim);
+    CHECK_INPUT(pt.B == ps.B);
+    const int64_t dim = ps.dim;
+    const bool real_input = real_dtype(x);
+    CHECK_INPUT(dy.scalar_type() == x.scalar_type());
+    CHECK_INPUT(x.dim() >= 1 && dy.dim() == x.dim());
+    CHECK_INPUT(x.size(0) == ps.n && dy.size(0) == pt.n);
+    CHECK_INPUT(x.device() == sources.device() && targets.device() == sources.device() && dy.device() == sources.device());
+    CHECK_INPUT(poly.size() >= 1 && poly.size() <= 7);
+    int64_t C = 1;
+    for (int64_t d = 1; d < x.dim(); ++d) {
+        CHECK_INPUT(dy.size(d) == x.size(d));
+        C *= x.size(d);
+    }
+    nfft_hip_nearfield_problem q;
+    q.dim = (int32_t)dim;
+    q.kernel = (int32_t)kernel;
+    q.poly_terms = (int32_t)poly.size() + 1;
+    q.num_sources = ps.n;
+    q.num_targets = pt.n;
+    q.num_columns = real_input ? C : 2 * C;
+    q.batch_size = ps.B;
+    q.c = c;
+    q.eps_I = eps_I;
+    for (size_t e = 0; e < 8; ++e) q.poly[e] = 0.0;  // (T_I itself is not read)
+    double gpoly[8] = {0.0};
+    for (size_t e = 0; e < poly.size(); ++e) gpoly[e] = poly[e];
+    const int64_t G = nfft_hip_nearfield_cells(q.dim, eps_I, q.batch_size);
+    if (G < 0) check_rc(NFFT_HIP_EINVAL);
+    q.cells_per_axis = (int32_t)G;
+    if (nfft_hip_nearfield_point_gradient_workspace_bytes(&q) < 0) check_rc(NFFT_HIP_EINVAL);
+    const at::TensorOptions opts = sources.options();
+    const bool symmetric = shared && need_sources && need_targets;
+    // (zeros: an output point whose coordinates are not numbers has no cell and is not written)
+    at::Tensor ds = need_sources ? at::zeros({ps.n, dim}, opts) : at::empty({0, dim}, opts);
+    at::Tensor dt = need_targets ? at::zeros({pt.n, dim}, opts) : at::empty({0, dim}, opts);
+    if (ps.n == 0 || pt.n == 0 || C == 0 || (!need_sources && !need_targets)) return {ds, dt};  // empty sums: no launch
+    c10::DeviceGuard guard(x.device());
+    int64_t cells_per_set = 1;
+    for (int a = 0; a < q.dim; ++a) cells_per_set *= G;
+    const CellOrder os = cell_order(ps, G, cells_per_set);
+    const CellOrder ot = shared ? os : cell_order(pt, G, cells_per_set);
+    const at::Tensor xc = x.contiguous(), dyc = dy.contiguous();
+    const at::Tensor xr = (real_input ? xc : at::view_as_real(xc)).reshape({ps.n, q.num_columns}).index_select(0, os.order);
+    const at::Tensor dyr = (real_input ? dyc : at::view_as_real(dyc)).reshape({pt.n, q.num_columns}).index_select(0, ot.order);
+    // one sweep: the streamed side (order, values) and the output side (order, values, result)
+    auto sweep = [&](bool sym, const CellOrder &in, const at::Tensor &vin, const CellOrder &o, const at::Tensor &vout,
+                     at::Tensor &out) {
+        nfft_hip_nearfield_problem r = q;
+        r.num_sources = in.pos.size(0);
+        r.num_targets = o.pos.size(0);
+        const int64_t ws_bytes = nfft_hip_nearfield_point_gradient_workspace_bytes(&r);
+        if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+        at::Tensor ws = byte_buffer(ws_bytes, x);
+        check_rc(nfft_hip_nearfield_point_gradient(&r, sym ? 1 : 0, gpoly, in.pos.data_ptr<float>(), vin.data_ptr<float>(),
+                                                   in.start.data_ptr<int32_t>(), o.pos.data_ptr<float>(),
+                                                   vout.data_ptr<float>(), o.order.data_ptr<int64_t>(),
+                                                   o.start.data_ptr<int32_t>(), out.data_ptr<float>(), ws.data_ptr(), ws_bytes,
+                                                   stream_of(x)));
+    };
+    if (symmetric) {
+        sweep(true, os, xr, os, dyr, ds);
+        return {ds, dt};
+    }
+    if (need_targets) sweep(false, os, xr, ot, dyr, dt);
+    if (need_sources) sweep(false, ot, dyr, os, xr, ds);
+    return {ds, dt};
+}
+
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
 at::TensorOptions current_device_options(at::ScalarType dtype)
 {
@@ -1003,4 +1092,8 @@ TORCH_LIBRARY(torch_nfft, m)
     // ... and its gradient at the targets / the transpose of that (nfft_fastsum_nearfield_gradient)
     m.def("_nfft_nearfield_gradient(Tensor sources, Tensor targets, Tensor x, Tensor? source_batch, Tensor? target_batch, "
           "int kernel, float c, float eps_I, float[] poly, bool transpose) -> Tensor", &nfft_nearfield_gradient);
+    // ... and the gradient of the near-field sum with respect to its points, contracted with dy (point_gradients=True)
+    m.def("_nfft_nearfield_point_gradient(Tensor sources, Tensor targets, Tensor x, Tensor dy, Tensor? source_batch, "
+          "Tensor? target_batch, int kernel, float c, float eps_I, float[] poly, bool need_sources, bool need_targets) "
+          "-> (Tensor, Tensor)", &nfft_nearfield_point_gradient);
 }

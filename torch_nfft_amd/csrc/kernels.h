@@ -165,6 +165,13 @@ int launch_nearfield(const nfft_hip_nearfield_problem *p, const float *src, cons
 int launch_nearfield_gradient(const nfft_hip_nearfield_problem *p, int transpose, const double *gradient_poly,
                               const float *spos, const float *in, const int *sstart, const float *opos, const int64_t *oindex,
                               const int *ostart, float *out, void *items, hipStream_t stream);
+// nearfield_pgrad.hip (the near field's gradient with respect to the points): arguments as
+// nfft_hip_nearfield_point_gradient -- `spos` / `sval` / `sstart` the streamed side, `opos` / `oval` / `oindex` / `ostart`
+// the output side; `items` as above
+int launch_nearfield_point_gradient(const nfft_hip_nearfield_problem *p, int symmetric, const double *gradient_poly,
+                                    const float *spos, const float *sval, const int *sstart, const float *opos,
+                                    const float *oval, const int64_t *oindex, const int *ostart, float *out, void *items,
+                                    hipStream_t stream);
 
 // smallgrid.hip: transforms whose oversampled grid (<= 4096 cells) fits one workgroup's LDS -- one kernel per direction,
 // no point plan

@@ -1,6 +1,6 @@
-// What the two near-field pair kernels share (nearfield.hip: the value; nearfield_grad.hip: the
-// gradient at the targets and its transpose, section 7e): the sizes of a work item and of an LDS tile, the parameter
-// block and the work-item list.
+// What the near-field pair kernels share (nearfield.hip: the value; nearfield_grad.hip: the
+// gradient at the targets and its transpose, section 7e; nearfield_pgrad.hip: the gradient with respect to the points,
+// section 7f): the sizes of a work item and of an LDS tile, the parameter block, K'(r) / r and the work-item list.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -33,6 +33,30 @@ inline NearParams near_params(const nfft_hip_nearfield_problem *p, const double 
     q.inv_eps2 = (float)(1.0 / (p->eps_I * p->eps_I));
     for (int e = 0; e < 8; ++e) q.poly[e] = e < terms ? (float)poly[e] : 0.f;
     return q;
+}
+
+// K'(r) / r from r^2 > 0: one rsqrt, rcp, log or exp (the Laplacian RBF needs r itself as well: two)
+template <int KERNEL>
+__device__ __forceinline__ float kernel_slope(float r2, const NearParams &q)
+{
+    if (KERNEL == NFFT_HIP_KERNEL_ONE_OVER_MODULUS) {  // -r^-3
+        const float i = rsqrtf(r2);
+        return -(i * i) * i;
+    }
+    if (KERNEL == NFFT_HIP_KERNEL_ONE_OVER_SQUARE) {  // -2 r^-4
+        const float i = __builtin_amdgcn_rcpf(r2);
+        return -2.0f * (i * i);
+    }
+    if (KERNEL == NFFT_HIP_KERNEL_LOGARITHM) return __builtin_amdgcn_rcpf(r2);       // r^-2
+    if (KERNEL == NFFT_HIP_KERNEL_THINPLATE_SPLINE) return logf(r2) + 1.0f;           // 2 log r + 1
+    if (KERNEL == NFFT_HIP_KERNEL_MULTIQUADRIC) return rsqrtf(r2 + q.c2);             // (r^2 + c^2)^(-1/2)
+    if (KERNEL == NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC) {                             // -(r^2 + c^2)^(-3/2)
+        const float i = rsqrtf(r2 + q.c2);
+        return -(i * i) * i;
+    }
+    if (KERNEL == NFFT_HIP_KERNEL_GAUSSIAN) return -2.0f * q.inv_c2 * expf(-r2 * q.inv_c2);  // -(2 / c^2) e^(-r^2 / c^2)
+    const float i = rsqrtf(r2);  // NFFT_HIP_KERNEL_LAPLACIAN_RBF: -e^(-r / c) / (c r)
+    return -(q.inv_c * i) * expf(-(r2 * i) * q.inv_c);
 }
 
 // nearfield.hip: fills items[0 .. nearfield_item_slots(p)) with (cell, first output point) of every piece of kNearBlock

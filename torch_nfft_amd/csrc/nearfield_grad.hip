@@ -27,30 +27,6 @@ namespace {
 
 constexpr int kNearGradient = 0, kNearTranspose = 1;
 
-// K'(r) / r from r^2 > 0: one rsqrt, rcp, log or exp (the Laplacian RBF needs r itself as well: two)
-template <int KERNEL>
-__device__ __forceinline__ float kernel_slope(float r2, const NearParams &q)
-{
-    if (KERNEL == NFFT_HIP_KERNEL_ONE_OVER_MODULUS) {  // -r^-3
-        const float i = rsqrtf(r2);
-        return -(i * i) * i;
-    }
-    if (KERNEL == NFFT_HIP_KERNEL_ONE_OVER_SQUARE) {  // -2 r^-4
-        const float i = __builtin_amdgcn_rcpf(r2);
-        return -2.0f * (i * i);
-    }
-    if (KERNEL == NFFT_HIP_KERNEL_LOGARITHM) return __builtin_amdgcn_rcpf(r2);       // r^-2
-    if (KERNEL == NFFT_HIP_KERNEL_THINPLATE_SPLINE) return logf(r2) + 1.0f;           // 2 log r + 1
-    if (KERNEL == NFFT_HIP_KERNEL_MULTIQUADRIC) return rsqrtf(r2 + q.c2);             // (r^2 + c^2)^(-1/2)
-    if (KERNEL == NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC) {                             // -(r^2 + c^2)^(-3/2)
-        const float i = rsqrtf(r2 + q.c2);
-        return -(i * i) * i;
-    }
-    if (KERNEL == NFFT_HIP_KERNEL_GAUSSIAN) return -2.0f * q.inv_c2 * expf(-r2 * q.inv_c2);  // -(2 / c^2) e^(-r^2 / c^2)
-    const float i = rsqrtf(r2);  // NFFT_HIP_KERNEL_LAPLACIAN_RBF: -e^(-r / c) / (c r)
-    return -(q.inv_c * i) * expf(-(r2 * i) * q.inv_c);
-}
-
 // PT: Horner terms, 4 or 8; the coefficients past `terms` are zero, which leaves the sum of the others bit for bit.
 // in: [streamed points, Cr] (gradient) or [streamed points, dim, Cr] (transpose); out: [output points, dim, Cr] (gradient)
 // or [output points, Cr] (transpose), row oindex[i] for the sorted output point i.

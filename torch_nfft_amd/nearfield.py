@@ -196,19 +196,96 @@ class NfftNearfieldFunction(torch.autograd.Function):
         return dx, None, None, None, None, None
 
 
-def nfft_nearfield(x, kern, sources, targets=None, source_batch=None, target_batch=None, /, batch=None):
+class _NearfieldPointGradient(torch.autograd.Function):
+    """(ds, dt) of ``ops.nfft_nearfield_point_gradient`` as a node of the graph, so that a second derivative through the
+    point gradients is refused instead of being silently absent."""
+
+    @staticmethod
+    def forward(ctx, x, dz, kern, sources, targets, source_batch, target_batch, need_sources, need_targets):
+        ds, dt = ops.nfft_nearfield_point_gradient(sources, targets, x, dz, source_batch, target_batch, kern.kernel_id,
+                                                   kern.c, kern.eps_I, kern.near_gradient_poly.tolist(), need_sources,
+                                                   need_targets)
+        if not need_sources:
+            ctx.mark_non_differentiable(ds)
+        if not need_targets:
+            ctx.mark_non_differentiable(dt)
+        return ds, dt
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise RuntimeError("second derivatives with respect to the near field's points are not implemented: the point "
+                           "gradients of nfft_nearfield / nfft_fastsum_nearfield are first-order (differentiating them "
+                           "again needs K''(r))")
+
+
+class NfftNearfieldPointsFunction(torch.autograd.Function):
+    """``NfftNearfieldFunction`` for points that require grad (``point_gradients=True``).  The
+    forward is the same near-field call.  In the backward ``ds`` and ``dt`` come from one call of
+    ``ops.nfft_nearfield_point_gradient`` (first-order: differentiating them again raises a RuntimeError), and ``dx`` is
+    the near field of ``dz`` with the sides swapped -- through this Function again, so that it stays differentiable in
+    ``dz`` and, to first order, in the points.  Shared points (``targets is sources``) take one symmetric sweep; the
+    total arrives as the sources' gradient, zeros as the targets', and autograd adds the two."""
+
+    @staticmethod
+    def forward(ctx, x, kern, sources, targets, source_batch, target_batch):
+        for name, t in (("source_batch", source_batch), ("target_batch", target_batch)):
+            if t is not None and t.requires_grad:
+                raise AssertionError("the near field is not differentiable w.r.t. %s" % name)
+        ctx.kern = kern
+        ctx.shared = targets is sources
+        ctx.save_for_backward(x, sources, targets, source_batch, target_batch)
+        return ops.nfft_nearfield(sources, targets, x, source_batch, target_batch, kern.kernel_id, kern.c, kern.eps_I,
+                                  kern.near_poly.tolist())
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, sources, targets, source_batch, target_batch = ctx.saved_tensors
+        if ctx.shared:
+            targets = sources
+        dx = ds = dt = None
+        if ctx.needs_input_grad[0]:
+            dx = NfftNearfieldPointsFunction.apply(dz, ctx.kern, targets, sources, target_batch, source_batch)
+        need_s, need_t = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        if need_s or need_t:
+            ds, dt = _NearfieldPointGradient.apply(x, dz, ctx.kern, sources, targets, source_batch, target_batch, need_s,
+                                                   need_t)
+            ds, dt = (ds if need_s else None), (dt if need_t else None)
+        return dx, None, ds, dt, None, None
+
+
+def _near_function(what, point_gradients, kern, sources, targets, source_batch, target_batch):
+    """The Function of the near field: today's unless ``point_gradients`` and a point requires grad"""
+    for name, t in (("sources", sources), ("targets", targets), ("source_batch", source_batch),
+                    ("target_batch", target_batch)):
+        if t is None or not t.requires_grad:
+            continue
+        if name.endswith("_batch"):
+            raise AssertionError("%s is not differentiable w.r.t. the batch vectors, but %s requires grad" % (what, name))
+        if not point_gradients:
+            raise AssertionError("%s is differentiable w.r.t. x only, but %s (pass point_gradients=True) requires grad"
+                                 % (what, name))
+    if point_gradients and (sources.requires_grad or targets.requires_grad):
+        _needs_smooth_join("%s with point_gradients=True" % what, kern)
+        return NfftNearfieldPointsFunction
+    return NfftNearfieldFunction
+
+
+def nfft_nearfield(x, kern, sources, targets=None, source_batch=None, target_batch=None, /, batch=None, *,
+                   point_gradients=False):
     """``z_i = sum_{j: |t_i - s_j| < eps_I, same point set} (K(r_ij) - T_I(r_ij)) x_j``: the near field of
-    ``nfft_fastsum_nearfield`` on its own (same argument conventions)."""
+    ``nfft_fastsum_nearfield`` on its own (same argument conventions, ``point_gradients`` included)."""
     if targets is None:
         targets = sources
         target_batch = source_batch
     if batch is not None:
         source_batch = batch
         target_batch = batch
-    return NfftNearfieldFunction.apply(x, kern, sources, targets, source_batch, target_batch)
+    fn = _near_function("the near field", point_gradients, kern, sources, targets, source_batch, target_batch)
+    return fn.apply(x, kern, sources, targets, source_batch, target_batch)
 
 
-def nfft_fastsum_nearfield(x, kern, sources, targets=None, source_batch=None, target_batch=None, /, batch=None, cutoff=3):
+def nfft_fastsum_nearfield(x, kern, sources, targets=None, source_batch=None, target_batch=None, /, batch=None, cutoff=3,
+                           *, point_gradients=False):
     """Fast summation with a ``RegularizedKernel``:  ``y_i = sum_j K(|t_i - s_j|) x_j`` over the sources of target i's
     point set (for a kernel that is singular at 0 without the pairs ``s_j = t_i``), as
     ``nfft_fastsum(x, kern.coeffs, ...)`` plus the near field.
@@ -216,20 +293,24 @@ def nfft_fastsum_nearfield(x, kern, sources, targets=None, source_batch=None, ta
     The argument conventions are those of ``nfft_fastsum`` (``targets=None``: shared points; a real ``x`` gives a real
     ``y``), in torus coordinates: every source and target must lie within ``kern.max_radius`` of the origin (not
     checked).  Differentiable in ``x`` (the near field to any order, the far field once, like ``nfft_fastsum``).
-    ``sources``, ``targets`` and the batch vectors must not require grad (AssertionError); the gradient at the targets is
-    a function of its own, ``nfft_fastsum_nearfield_gradient``."""
+    By default ``sources``, ``targets`` and the batch vectors must not require grad (AssertionError); the gradient at the
+    targets is a function of its own, ``nfft_fastsum_nearfield_gradient``.
+
+    ``point_gradients=True`` (keyword only) lets ``sources`` and ``targets`` require grad: the far part is
+    ``nfft_fastsum``'s own gradient in the points, the near part one contracting pair sweep (one
+    symmetric sweep for shared points, whose ``.grad`` then holds the sum of both roles).  It is opt-in because callers and
+    tests rely on the refusal above; with no point requiring grad the result is bitwise the default's.  It needs
+    ``kern.p >= 2`` (ValueError), is first-order in the points (a second derivative through them raises a RuntimeError), and
+    the batch vectors still must not require grad."""
     if targets is None:
         targets = sources
         target_batch = source_batch
     if batch is not None:
         source_batch = batch
         target_batch = batch
-    for name, t in (("sources", sources), ("targets", targets), ("source_batch", source_batch),
-                    ("target_batch", target_batch)):
-        if t is not None and t.requires_grad:
-            raise AssertionError("nfft_fastsum_nearfield is differentiable w.r.t. x only, but %s requires grad" % name)
+    fn = _near_function("nfft_fastsum_nearfield", point_gradients, kern, sources, targets, source_batch, target_batch)
     far = nfft_fastsum(x, kern.coeffs, sources, targets, source_batch, target_batch, cutoff=cutoff)
-    return far + NfftNearfieldFunction.apply(x, kern, sources, targets, source_batch, target_batch)
+    return far + fn.apply(x, kern, sources, targets, source_batch, target_batch)
 
 
 def _refuse_point_gradients(what, sources, targets, source_batch, target_batch):

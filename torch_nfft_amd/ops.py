@@ -157,6 +157,22 @@ def nfft_nearfield_gradient(sources, targets, x, source_batch, target_batch, ker
                                          float(eps_I), [float(a) for a in poly], bool(transpose))
 
 
+def nfft_nearfield_point_gradient(sources, targets, x, dy, source_batch, target_batch, kernel, c, eps_I, poly, need_sources,
+                                  need_targets):
+    """torch_nfft::_nfft_nearfield_point_gradient(Tensor sources, Tensor targets, Tensor x, Tensor dy, Tensor? source_batch,
+    Tensor? target_batch, int kernel, float c, float eps_I, float[] poly, bool need_sources, bool need_targets) ->
+    (Tensor, Tensor) (not in the reference): the gradient of ``<dy, nfft_nearfield(x)>`` with respect to the points,
+    ``ds[j] = sum_i g(r_ij^2) (s_j - t_i) (x_j . dy_i)`` ``[n_s, dim]`` and ``dt[i] = sum_j g(r_ij^2) (t_i - s_j) (dy_i . x_j)``
+    ``[n_t, dim]`` over the pairs ``0 < r_ij < eps_I`` of one point set, ``g`` and ``poly`` as for
+    ``nfft_nearfield_gradient``; the dot products run over the real columns (real and imaginary parts of complex values).
+    A side that is not needed comes back empty.  Shared points (``targets`` is ``sources``, the same batch vector) with
+    both sides needed take one symmetric sweep: ``ds`` is the total and ``dt`` zeros.  One native call per sweep
+    (``nfft_hip_nearfield_point_gradient``)."""
+    return _ops._nfft_nearfield_point_gradient(sources, targets, x, dy, source_batch, target_batch, int(kernel), float(c),
+                                               float(eps_I), [float(a) for a in poly], bool(need_sources),
+                                               bool(need_targets))
+
+
 class _on_device:
     """The coefficient operators create their output on the current device (like the reference, which has no
     device argument); ``device=`` selects it for the duration of the call."""
