@@ -378,6 +378,42 @@ int nfft_hip_nearfield_point_gradient(const nfft_hip_nearfield_problem *p, int32
                                       const int32_t *output_start, float *out, void *workspace, int64_t workspace_bytes,
                                       void *stream);
 
+/* ---- near part of the Ewald sum for the periodic 1/r (no reference counterpart) ----
+ * The Coulomb sum over all images of the unit box is split with erf / erfc: the smooth part is summed on the whole torus
+ * with nfft_hip_fastsum (coefficients exp(-pi^2 |k|^2 / alpha^2) / (pi |k|^2), set up by the host side), and this entry
+ * point adds the short-ranged rest for ONE point set on both sides (targets are the sources), 3-D only:
+ *     z[i, c]     =  sum_{j in the point set of i, 0 < r_ij < r_cut} erfc(alpha r_ij) / r_ij  xr[j, c]
+ *     field[i, a, c] = -sum_j g(r_ij^2) d_ij[a] xr[j, c]   (with_field = 1; field [n, 3, Cr]; not touched otherwise)
+ * with g = K'(r) / r = -erfc(alpha r) / r^3 - (2 alpha / sqrt(pi)) exp(-alpha^2 r^2) / r^2.  The sum is PERIODIC: d_ij is
+ * the minimum image of points_i - points_j, d -= rint(d) on every axis, and r_ij its length.  Coincident points (r = 0,
+ * the point itself among them) weigh zero.  The points must already be reduced to [-1/2, 1/2)^3.
+ *
+ * The points come ORDERED BY CELL: cells_per_axis^3 cubes of edge 1 / cells_per_axis >= r_cut over the whole torus, cell
+ * index c_0 + G c_1 + G^2 c_2 with c_a = min(floor((pos_a + 1/2) G), G - 1), key = point set * G^3 + cell; the caller
+ * sorts by key (stably) and passes
+ *   points [n, 3] float32, xr [n, Cr] float32 (real columns; re, im interleaved for complex data) in that order
+ *   start  int32 [batch_size * G^3 + 1]: index of the first point with key >= entry
+ *   index  int64 [n]: the row of z (and of field) that sorted point i writes
+ * G >= 3 is required, so that the 27 wrapped neighbours of a cell are 27 distinct cells; hence r_cut <= 1/3.
+ * nfft_hip_ewald_near_cells proposes cells_per_axis: floor(1 / r_cut), lowered until batch_size * G^3 <= 2^20; -1 with
+ * "Input mismatch..." unless 0 < r_cut <= 1/3 (or if no G >= 3 fits that many point sets).
+ * No atomics: a point's pairs are added in the order of the sorted points (row by row of the wrapped walk), two calls
+ * give the same bits.  No points or no columns: nothing is done.  Workspace: the work items, as for nfft_hip_nearfield. */
+typedef struct nfft_hip_ewald_problem {
+    int32_t cells_per_axis; /* G >= 3 with 1 / G >= r_cut */
+    int32_t with_field;     /* 0: z only; 1: z and field */
+    int64_t num_points;
+    int64_t num_columns;    /* real columns Cr */
+    int64_t batch_size;
+    double alpha;           /* splitting parameter, > 0 */
+    double r_cut;           /* in (0, 1/3] */
+} nfft_hip_ewald_problem;
+int64_t nfft_hip_ewald_near_cells(double r_cut, int64_t batch_size);
+int64_t nfft_hip_ewald_near_workspace_bytes(const nfft_hip_ewald_problem *p);
+int nfft_hip_ewald_near(const nfft_hip_ewald_problem *p, const float *points, const float *xr, const int32_t *start,
+                        const int64_t *index, float *z, float *field, void *workspace, int64_t workspace_bytes,
+                        void *stream);
+
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.
  *   gaussian_analytic_coeffs      float32:  prod_d sqrt(pi) sigma exp(-sigma^2 pi^2 l_d^2)      (kernel_coeffs.cu:6-30)

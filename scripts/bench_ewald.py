@@ -1,0 +1,153 @@
+"""Times nfft_ewald and its wrapped pair sweep:
+
+    python scripts/bench_ewald.py [--points 100000 1000000] [--neighbours 100] [--tol 1e-5] [--reps 10]
+
+Charges uniform in the unit box, one real column, cutoff m = 4.  r_c is chosen for `neighbours` charges inside the sphere
+of radius r_c around a charge, n (4/3) pi r_c^3 = neighbours, and alpha and N by EwaldSplitting.from_tolerance(tol, r_c).
+Device-event medians of `reps` calls after two warm-up calls:
+  whole sum     nfft_ewald without and with the field
+  far field     nfft_fastsum with the splitting's coefficients (the value's far part)
+  near sweep    ops.nfft_ewald_near as a whole, without and with the field, and its pair loop on its own
+                (nfft_hip_ewald_near through the C ABI on the arrays that the operator's plumbing made, restated here)
+  yardstick     the existing 1/r value loop (nfft_hip_nearfield, kernel one_over_modulus, p = 4) on the same points
+                scaled into [-1/4, 1/4)^3 with eps_I = r_c / 2 and the same number of cells per axis: the same cells and
+                pairs except that its walk does not wrap
+  pairs         distance tests per call = sum over targets of the sources in the 27 cells around it (wrapped for the
+                Ewald sweep, clipped for the yardstick), and nanoseconds per tested pair for each loop
+One JSON line per problem size.
+"""
+import argparse
+import ctypes
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch_nfft_amd as tn  # noqa: E402
+from torch_nfft_amd import _lib  # noqa: E402
+
+
+def median_ms(fn, reps):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return float(np.median(times))
+
+
+def cell_order(pos, G, offset, scale):
+    """what core.so's cell orders do for one point set without a batch vector: cell = floor((pos + offset) * scale)"""
+    cell = ((pos + offset) * float(scale)).floor().clamp(0, G - 1).to(torch.int64)
+    key = cell[:, 0] + cell[:, 1] * G + cell[:, 2] * (G * G)
+    skey, order = torch.sort(key, stable=True)
+    start = torch.searchsorted(skey, torch.arange(G ** 3 + 1, device=pos.device), out_int32=True)
+    return pos.index_select(0, order), order, start
+
+
+def pairs_tested(v, G):
+    """(wrapped, clipped): targets of a cell x sources of the 27 cells around it, with and without the wrap"""
+    cells = np.clip(np.floor((v + np.float32(0.5)) * np.float32(G)), 0, G - 1).astype(np.int64)
+    count = np.zeros((G,) * 3, dtype=np.int64)
+    np.add.at(count, (cells[:, 0], cells[:, 1], cells[:, 2]), 1)
+    shifts = [(a, b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1)]
+    wrapped = sum(np.roll(count, s, axis=(0, 1, 2)) for s in shifts)
+    pad = np.zeros((G + 2,) * 3, dtype=np.int64)
+    pad[1:-1, 1:-1, 1:-1] = count
+    clipped = sum(pad[1 + a:G + 1 + a, 1 + b:G + 1 + b, 1 + c:G + 1 + c] for a, b, c in shifts)
+    return int((count * wrapped).sum()), int((count * clipped).sum())
+
+
+def run(lib, n, args):
+    m = 4
+    r_c = min((3.0 * args.neighbours / (4.0 * math.pi * n)) ** (1.0 / 3.0), 1.0 / 3.0)
+    sp = tn.EwaldSplitting.from_tolerance(args.tol, r_c)
+    rng = np.random.default_rng(0)
+    v = (rng.random((n, 3)) - 0.5).astype(np.float32)
+    v[v >= 0.5] = -0.5  # (rounded up to the face: the same point)
+    pos = torch.from_numpy(v).cuda()
+    q = torch.from_numpy(rng.standard_normal(n).astype(np.float32)).cuda()
+    G = int(lib.nfft_hip_ewald_near_cells(r_c, 1))
+    wrapped, clipped = pairs_tested(v, G)
+    whole = median_ms(lambda: tn.nfft_ewald(q, pos, splitting=sp, cutoff=m), args.reps)
+    whole_f = median_ms(lambda: tn.nfft_ewald(q, pos, splitting=sp, cutoff=m, field=True), args.reps)
+    far = median_ms(lambda: tn.nfft_fastsum(q, sp.coeffs, pos, cutoff=m), args.reps)
+    near = median_ms(lambda: tn.ops.nfft_ewald_near(pos, q, None, sp.alpha, r_c, False), args.reps)
+    near_f = median_ms(lambda: tn.ops.nfft_ewald_near(pos, q, None, sp.alpha, r_c, True), args.reps)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    # the Ewald pair loop on its own
+    spos, order, start = cell_order(pos, G, 0.5, G)
+    xs = q.index_select(0, order).reshape(n, 1).contiguous()
+    z, f = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+    loops = {}
+    for with_field in (0, 1):
+        p = _lib.EwaldProblem(cells_per_axis=G, with_field=with_field, num_points=n, num_columns=1, batch_size=1,
+                              alpha=sp.alpha, r_cut=r_c)
+        nbytes = lib.nfft_hip_ewald_near_workspace_bytes(ctypes.byref(p))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+
+        def loop():
+            _lib.check(lib.nfft_hip_ewald_near(ctypes.byref(p), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                               order.data_ptr(), z.data_ptr(), f.data_ptr(), ws.data_ptr(), nbytes, stream))
+
+        loops[with_field] = median_ms(loop, args.reps)
+    zo, fo = tn.ops.nfft_ewald_near(pos, q, None, sp.alpha, r_c, True)
+    assert torch.equal(zo, z[:, 0]) and torch.equal(fo, f), "the restated plumbing must give the operator's bits"
+
+    # the yardstick: the 1/r value loop of nfft_hip_nearfield on the same cells
+    kern = tn.RegularizedKernel("one_over_modulus", dim=3, bandwidth=64, p=4, eps_I=r_c / 2, eps_B=1.0 / 16.0, device="cpu")
+    half = pos * 0.5
+    hpos, horder, hstart = cell_order(half, G, 0.25, 2 * G)
+    hx = q.index_select(0, horder).reshape(n, 1).contiguous()
+    hz = torch.zeros(n, 1, device="cuda")
+    hq = _lib.NearfieldProblem(dim=3, kernel=kern.kernel_id, poly_terms=4, cells_per_axis=G, num_sources=n, num_targets=n,
+                               num_columns=1, batch_size=1, c=kern.c, eps_I=kern.eps_I)
+    for e, a in enumerate(kern.near_poly.tolist()):
+        hq.poly[e] = a
+    hbytes = lib.nfft_hip_nearfield_workspace_bytes(ctypes.byref(hq))
+    assert hbytes > 0, _lib.last_error()
+    hws = torch.empty(hbytes, dtype=torch.uint8, device="cuda")
+
+    def yardstick():
+        _lib.check(lib.nfft_hip_nearfield(ctypes.byref(hq), hpos.data_ptr(), hx.data_ptr(), hstart.data_ptr(), hpos.data_ptr(),
+                                          horder.data_ptr(), hstart.data_ptr(), hz.data_ptr(), hws.data_ptr(), hbytes, stream))
+
+    yard = median_ms(yardstick, args.reps)
+    tn.ops.check_status()
+    ns, ns_f, ns_y = loops[0] * 1e6 / wrapped, loops[1] * 1e6 / wrapped, yard * 1e6 / clipped
+    print(json.dumps({"bench": "ewald", "points": n, "neighbours": args.neighbours, "tol": args.tol, "r_cut": round(r_c, 5),
+                      "alpha": round(sp.alpha, 3), "N": sp.bandwidth, "m": m, "cells_per_axis": G,
+                      "ewald_ms": round(whole, 4), "ewald_field_ms": round(whole_f, 4), "far_ms": round(far, 4),
+                      "near_ms": round(near, 4), "near_field_ms": round(near_f, 4),
+                      "pair_loop_ms": round(loops[0], 4), "pair_loop_field_ms": round(loops[1], 4),
+                      "one_over_r_loop_ms": round(yard, 4), "pairs_tested": wrapped, "one_over_r_pairs_tested": clipped,
+                      "ns_per_pair": round(ns, 5), "ns_per_pair_field": round(ns_f, 5), "one_over_r_ns_per_pair": round(ns_y, 5),
+                      "value_over_one_over_r": round(ns / ns_y, 3), "field_over_one_over_r": round(ns_f / ns_y, 3)}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=int, nargs="+", default=[100000, 1000000])
+    ap.add_argument("--neighbours", type=float, default=100.0)
+    ap.add_argument("--tol", type=float, default=1e-5)
+    ap.add_argument("--reps", type=int, default=10)
+    args = ap.parse_args()
+    torch.cuda.set_device(0)
+    lib = _lib.load()
+    for n in args.points:
+        run(lib, n, args)
+
+
+if __name__ == "__main__":
+    main()

@@ -56,6 +56,9 @@ SYMBOLS = (
     "nfft_hip_nearfield_gradient",
     "nfft_hip_nearfield_point_gradient_workspace_bytes",
     "nfft_hip_nearfield_point_gradient",
+    "nfft_hip_ewald_near_cells",
+    "nfft_hip_ewald_near_workspace_bytes",
+    "nfft_hip_ewald_near",
     "nfft_hip_gaussian_analytic_coeffs",
     "nfft_hip_interpolation_grid",
     "nfft_hip_coeffs_workspace_bytes",
@@ -102,6 +105,19 @@ class NearfieldProblem(ctypes.Structure):
         ("c", ctypes.c_double),
         ("eps_I", ctypes.c_double),
         ("poly", ctypes.c_double * 8),
+    ]
+
+
+class EwaldProblem(ctypes.Structure):
+    """``nfft_hip_ewald_problem`` of include/nfft_hip.h."""
+    _fields_ = [
+        ("cells_per_axis", ctypes.c_int32),
+        ("with_field", ctypes.c_int32),
+        ("num_points", ctypes.c_int64),
+        ("num_columns", ctypes.c_int64),
+        ("batch_size", ctypes.c_int64),
+        ("alpha", ctypes.c_double),
+        ("r_cut", ctypes.c_double),
     ]
 
 
@@ -202,6 +218,12 @@ def load():
     lib.nfft_hip_nearfield_point_gradient.argtypes = [ctypes.POINTER(NearfieldProblem), ctypes.c_int32, vp,
                                                       vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.nfft_hip_nearfield_point_gradient.restype = ci
+    lib.nfft_hip_ewald_near_cells.argtypes = [ctypes.c_double, i64]
+    lib.nfft_hip_ewald_near_cells.restype = i64
+    lib.nfft_hip_ewald_near_workspace_bytes.argtypes = [ctypes.POINTER(EwaldProblem)]
+    lib.nfft_hip_ewald_near_workspace_bytes.restype = i64
+    lib.nfft_hip_ewald_near.argtypes = [ctypes.POINTER(EwaldProblem), vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.nfft_hip_ewald_near.restype = ci
     lib.nfft_hip_gaussian_analytic_coeffs.argtypes = [ctypes.c_double, i64, ctypes.c_int32, vp, vp]
     lib.nfft_hip_gaussian_analytic_coeffs.restype = ci
     lib.nfft_hip_interpolation_grid.argtypes = [i64, ctypes.c_int32, ci, vp, vp]

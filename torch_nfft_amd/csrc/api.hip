@@ -1625,3 +1625,74 @@ int nfft_hip_nearfield_point_gradient(const nfft_hip_nearfield_problem *p, int32
 }
 
 }  // extern "C"
+
+// ---- near part of the Ewald sum for the periodic 1/r ------------------------------------------
+namespace {
+
+int validate_ewald(const nfft_hip_ewald_problem *p)
+{
+    if (!p) { set_error("Input mismatch: null problem"); return NFFT_HIP_EINVAL; }
+    if (p->with_field != 0 && p->with_field != 1) { set_error("Input mismatch: with_field must be 0 or 1"); return NFFT_HIP_EINVAL; }
+    if (p->num_points < 0 || p->num_columns < 0 || p->batch_size < 1) {
+        set_error("Input mismatch: negative size");
+        return NFFT_HIP_EINVAL;
+    }
+    if (p->num_points >= (int64_t(1) << 31)) { set_error("Input mismatch: too many points"); return NFFT_HIP_EINVAL; }
+    if (!(p->alpha > 0.0) || !(p->alpha < 1e18)) { set_error("Input mismatch: alpha must be positive and finite"); return NFFT_HIP_EINVAL; }
+    if (!(p->r_cut > 0.0) || !(p->r_cut <= 1.0 / 3.0)) { set_error("Input mismatch: r_cut must lie in (0, 1/3]"); return NFFT_HIP_EINVAL; }
+    if (p->cells_per_axis < 3 || 1.0 / p->cells_per_axis < p->r_cut * (1.0 - 1e-12)) {
+        set_error("Input mismatch: cells must be at least 3 per axis with an edge 1 / cells_per_axis >= r_cut");
+        return NFFT_HIP_EINVAL;
+    }
+    if (p->batch_size > kNearMaxCells ||
+        p->batch_size * p->cells_per_axis * p->cells_per_axis * p->cells_per_axis > kNearMaxCells) {
+        set_error("Input mismatch: too many cells");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nfft_hip_ewald_near_cells(double r_cut, int64_t batch_size)
+{
+    if (!(r_cut > 0.0) || !(r_cut <= 1.0 / 3.0) || batch_size < 1) {
+        set_error("Input mismatch: ewald cells need r_cut in (0, 1/3] and batch_size >= 1");
+        return -1;
+    }
+    int64_t G = (int64_t)std::min(1.0 / r_cut, 1024.0);
+    while (G > 3 && 1.0 / (double)G < r_cut) --G;  // (the quotient may have been rounded up)
+    if (G < 3) G = 3;                              // (... or down, at r_cut = 1/3)
+    while (G > 3 && batch_size * G * G * G > kNearMaxCells) --G;
+    if (batch_size > kNearMaxCells || batch_size * G * G * G > kNearMaxCells) {
+        set_error("Input mismatch: too many point sets for a grid of 3 cells per axis");
+        return -1;
+    }
+    return G;
+}
+
+int64_t nfft_hip_ewald_near_workspace_bytes(const nfft_hip_ewald_problem *p)
+{
+    if (validate_ewald(p)) return -1;
+    return ewald_near_item_slots(p) * (int64_t)sizeof(int2) + 256;
+}
+
+int nfft_hip_ewald_near(const nfft_hip_ewald_problem *p, const float *points, const float *xr, const int32_t *start,
+                        const int64_t *index, float *z, float *field, void *workspace, int64_t workspace_bytes,
+                        void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_ewald(p)) return rc;
+    if (p->num_points == 0 || p->num_columns == 0) return 0;
+    if (!z) { set_error("Input mismatch: z is null"); return NFFT_HIP_EINVAL; }
+    if (p->with_field && !field) { set_error("Input mismatch: field is null"); return NFFT_HIP_EINVAL; }
+    if (!points || !xr || !start || !index) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    const int64_t need = ewald_near_item_slots(p) * (int64_t)sizeof(int2) + 256;
+    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    return launch_ewald_near(p, points, xr, start, index, z, field, ws, (hipStream_t)stream);
+}
+
+}  // extern "C"

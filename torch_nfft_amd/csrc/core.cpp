@@ -975,6 +975,80 @@ std::tuple<at::Tensor, at::Tensor> nfft_nearfield_point_gradient(at::Tensor sour
     return {ds, dt};
 }
 
+// ---- near part of the Ewald sum for the periodic 1/r (not in the reference) --------------------
+// cell_order's sibling for nfft_hip_ewald_near: `pos` already reduced to [-1/2, 1/2)^3, G^3 cells of edge 1/G over the whole
+// torus, the key of include/nfft_hip.h.  Same sort and search; cell_order's own arithmetic is left as it is.
+CellOrder torus_cell_order(const at::Tensor &pos, const at::Tensor &batch, int64_t B, int64_t G)
+{
+    const at::Tensor cell = ((pos + 0.5) * (double)G).floor().clamp(0, G - 1).to(at::kLong);
+    at::Tensor key = cell.select(1, 0) + cell.select(1, 1) * G + cell.select(1, 2) * (G * G);
+    if (batch.defined()) key = key + batch * (G * G * G);
+    const auto sorted = at::sort(key, /*stable=*/true, /*dim=*/0, /*descending=*/false);
+    CellOrder o;
+    o.order = std::get<1>(sorted);
+    o.start = at::searchsorted(std::get<0>(sorted), at::arange(B * G * G * G + 1, key.options()), /*out_int32=*/true);
+    o.pos = pos.index_select(0, o.order);
+    return o;
+}
+
+// (z, f): z[i] = sum_{j: same point set, 0 < r_ij < r_cut} erfc(alpha r_ij) / r_ij x[j] with r_ij the length of the minimum
+// image d_ij of pos_i - pos_j on the unit torus, x's type and shape; with_field: f[i, a] = -sum_j g(r_ij^2) d_ij[a] x[j],
+// [n, 3, *cols] (g = K'(r) / r of K = erfc(alpha r) / r), otherwise f is empty.  pos may hold any real values: they are
+// taken modulo 1.
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_near(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch,
+                                                   double alpha, double r_cut, bool with_field)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_near is currently only implemented for GPU tensors");
+    const Points p = check_points(pos, opt_batch, "batch");
+    CHECK_INPUT(p.dim == 3);
+    const bool real_input = real_dtype(x);
+    CHECK_INPUT(x.dim() >= 1);
+    CHECK_INPUT(x.size(0) == p.n);
+    CHECK_INPUT(x.device() == pos.device());
+    int64_t C = 1;
+    std::vector<int64_t> z_shape{p.n}, f_shape{p.n, 3};
+    for (int64_t d = 1; d < x.dim(); ++d) {
+        C *= x.size(d);
+        z_shape.push_back(x.size(d));
+        f_shape.push_back(x.size(d));
+    }
+    if (!with_field) f_shape = {0};
+    nfft_hip_ewald_problem q;
+    q.with_field = with_field ? 1 : 0;
+    q.num_points = p.n;
+    q.num_columns = real_input ? C : 2 * C;
+    q.batch_size = p.B;
+    q.alpha = alpha;
+    q.r_cut = r_cut;
+    const int64_t G = nfft_hip_ewald_near_cells(r_cut, q.batch_size);
+    if (G < 0) check_rc(NFFT_HIP_EINVAL);
+    q.cells_per_axis = (int32_t)G;
+    const int64_t ws_bytes = nfft_hip_ewald_near_workspace_bytes(&q);
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    if (p.n == 0 || C == 0) return {at::zeros(z_shape, x.options()), at::zeros(f_shape, x.options())};  // no launch
+    c10::DeviceGuard guard(x.device());
+    // p modulo 1 in [-1/2, 1/2): p - rint(p) is exact in float32 and equals p - floor(p + 1/2) wherever that sum is;
+    // what comes out as +1/2 is the point -1/2
+    at::Tensor red = p.pos - p.pos.round();
+    red = at::where(red >= 0.5, red - 1.0, red);
+    const CellOrder o = torus_cell_order(red, p.batch, p.B, G);
+    const at::Tensor xc = x.contiguous();
+    const at::Tensor xr = (real_input ? xc : at::view_as_real(xc)).reshape({p.n, q.num_columns}).index_select(0, o.order);
+    // (zeros: a point whose coordinates are not numbers has no cell and is not written)
+    const at::TensorOptions opts = x.options().dtype(at::kFloat);
+    at::Tensor z = at::zeros({p.n, q.num_columns}, opts);
+    at::Tensor f = with_field ? at::zeros({p.n, 3 * q.num_columns}, opts) : at::empty({0}, x.options());
+    at::Tensor ws = byte_buffer(ws_bytes, x);
+    check_rc(nfft_hip_ewald_near(&q, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
+                                 o.order.data_ptr<int64_t>(), z.data_ptr<float>(), with_field ? f.data_ptr<float>() : nullptr,
+                                 ws.data_ptr(), ws_bytes, stream_of(x)));
+    if (!real_input) {
+        z = at::view_as_complex(z.reshape({p.n, C, 2}));
+        if (with_field) f = at::view_as_complex(f.reshape({p.n, 3 * C, 2}));
+    }
+    return {z.reshape(z_shape), f.reshape(f_shape)};
+}
+
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
 at::TensorOptions current_device_options(at::ScalarType dtype)
 {
@@ -1096,4 +1170,7 @@ TORCH_LIBRARY(torch_nfft, m)
     m.def("_nfft_nearfield_point_gradient(Tensor sources, Tensor targets, Tensor x, Tensor dy, Tensor? source_batch, "
           "Tensor? target_batch, int kernel, float c, float eps_I, float[] poly, bool need_sources, bool need_targets) "
           "-> (Tensor, Tensor)", &nfft_nearfield_point_gradient);
+    // not in the reference: the wrapped pair sum erfc(alpha r) / r of the Ewald sum and its field (nfft_ewald)
+    m.def("_nfft_ewald_near(Tensor pos, Tensor x, Tensor? batch, float alpha, float r_cut, bool with_field) "
+          "-> (Tensor, Tensor)", &nfft_ewald_near);
 }

@@ -172,6 +172,11 @@ int launch_nearfield_point_gradient(const nfft_hip_nearfield_problem *p, int sym
                                     const float *spos, const float *sval, const int *sstart, const float *opos,
                                     const float *oval, const int64_t *oindex, const int *ostart, float *out, void *items,
                                     hipStream_t stream);
+// ewald_near.hip (the wrapped pair sum erfc(alpha r) / r of the Ewald sum and its field): arguments
+// as nfft_hip_ewald_near; `items`: ewald_near_item_slots(p) int2 of workspace for the work items
+int64_t ewald_near_item_slots(const nfft_hip_ewald_problem *p);
+int launch_ewald_near(const nfft_hip_ewald_problem *p, const float *pos, const float *xr, const int *start,
+                      const int64_t *index, float *z, float *f, void *items, hipStream_t stream);
 
 // smallgrid.hip: transforms whose oversampled grid (<= 4096 cells) fits one workgroup's LDS -- one kernel per direction,
 // no point plan

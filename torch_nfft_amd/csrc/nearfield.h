@@ -1,6 +1,7 @@
 // What the near-field pair kernels share (nearfield.hip: the value; nearfield_grad.hip: the
 // gradient at the targets and its transpose, section 7e; nearfield_pgrad.hip: the gradient with respect to the points,
-// section 7f): the sizes of a work item and of an LDS tile, the parameter block, K'(r) / r and the work-item list.
+// section 7f): the sizes of a work item and of an LDS tile, the parameter block, K'(r) / r and the work-item list.  The
+// wrapped pair kernel of the Ewald sum (ewald_near.hip, section 7g) takes the sizes and the work-item list from here too.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -62,5 +63,9 @@ __device__ __forceinline__ float kernel_slope(float r2, const NearParams &q)
 // nearfield.hip: fills items[0 .. nearfield_item_slots(p)) with (cell, first output point) of every piece of kNearBlock
 // output points of one cell, -1 in the slots that stay empty; tstart is the output side's start table
 int launch_nearfield_items(const nfft_hip_nearfield_problem *p, const int *tstart, int2 *items, hipStream_t stream);
+// the same for a table of `cells` cells (all point sets) over `num_targets` output points: nearfield_item_slots(cells,
+// num_targets) slots (ewald_near.hip cuts its full-box grid with it)
+int64_t nearfield_item_slots(int64_t cells, int64_t num_targets);
+int launch_nearfield_items(int64_t cells, int64_t num_targets, const int *tstart, int2 *items, hipStream_t stream);
 
 }  // namespace nfft

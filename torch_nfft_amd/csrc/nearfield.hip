@@ -155,22 +155,34 @@ void launch_pairs(const NearParams &q, int64_t slots, const int2 *items, const f
 
 }  // namespace
 
+namespace {
+int64_t nearfield_cells(const nfft_hip_nearfield_problem *p)
+{
+    int64_t cells = p->batch_size;
+    for (int a = 0; a < p->dim; ++a) cells *= p->cells_per_axis;
+    return cells;
+}
+}  // namespace
+
+int64_t nearfield_item_slots(int64_t cells, int64_t num_targets) { return num_targets / kNearBlock + cells + 1; }
+
 int64_t nearfield_item_slots(const nfft_hip_nearfield_problem *p)
 {
-    int64_t cells = p->batch_size;
-    for (int a = 0; a < p->dim; ++a) cells *= p->cells_per_axis;
-    return p->num_targets / kNearBlock + cells + 1;
+    return nearfield_item_slots(nearfield_cells(p), p->num_targets);
 }
 
-int launch_nearfield_items(const nfft_hip_nearfield_problem *p, const int *tstart, int2 *items, hipStream_t stream)
+int launch_nearfield_items(int64_t cells, int64_t num_targets, const int *tstart, int2 *items, hipStream_t stream)
 {
-    int64_t cells = p->batch_size;
-    for (int a = 0; a < p->dim; ++a) cells *= p->cells_per_axis;
-    NFFT_HIP_CHECK(hipMemsetAsync(items, 0xFF, (size_t)nearfield_item_slots(p) * sizeof(int2), stream));
+    NFFT_HIP_CHECK(hipMemsetAsync(items, 0xFF, (size_t)nearfield_item_slots(cells, num_targets) * sizeof(int2), stream));
     hipLaunchKernelGGL(nearfield_items_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, tstart, (int)cells,
                        items);
     NFFT_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+int launch_nearfield_items(const nfft_hip_nearfield_problem *p, const int *tstart, int2 *items, hipStream_t stream)
+{
+    return launch_nearfield_items(nearfield_cells(p), p->num_targets, tstart, items, stream);
 }
 
 int launch_nearfield(const nfft_hip_nearfield_problem *p, const float *src, const float *xr, const int *sstart,

@@ -173,6 +173,17 @@ def nfft_nearfield_point_gradient(sources, targets, x, dy, source_batch, target_
                                                bool(need_targets))
 
 
+def nfft_ewald_near(pos, x, batch, alpha, r_cut, with_field):
+    """torch_nfft::_nfft_ewald_near(Tensor pos, Tensor x, Tensor? batch, float alpha, float r_cut, bool with_field) ->
+    (Tensor, Tensor) (not in the reference): the near part of the Ewald sum on the unit torus,
+    ``z_i = sum_{j: 0 < r_ij < r_cut} erfc(alpha r_ij) / r_ij x_j`` over the points of i's point set with ``r_ij`` the
+    length of the minimum image ``d_ij`` of ``pos_i - pos_j`` (``pos`` ``[n, 3]``, taken modulo 1), and with
+    ``with_field`` ``f_i = -sum_j g(r_ij^2) d_ij x_j`` ``[n, 3, *cols]``, ``g = K'(r) / r`` of ``K = erfc(alpha r) / r``
+    (empty otherwise).  ``x`` ``[n, *cols]`` float32 or complex64.  One native call (``nfft_hip_ewald_near``; DESIGN.md
+    section 7g)."""
+    return _ops._nfft_ewald_near(pos, x, batch, float(alpha), float(r_cut), bool(with_field))
+
+
 class _on_device:
     """The coefficient operators create their output on the current device (like the reference, which has no
     device argument); ``device=`` selects it for the duration of the call."""
