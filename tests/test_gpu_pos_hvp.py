@@ -123,7 +123,7 @@ NATIVE = [  # d, N, n, cols, complex xhat, real_output, B, m
     (3, 32, 3000, (3,), False, True, 1, 8),
     (3, 32, 3000, (), True, False, 1, 1),         # narrow tiling
     (3, 64, 3000, (), True, False, 1, 4),         # wide 3-D tiling
-    (3, 64, 3000, (3,), False, False, 3, 8),      # wide tiling, several columns
+    (3, 64, 3000, (3,), False, False, 3, 8),      # W = 18 > 16: the narrow 8 x 16 tiling on the 128^3 grid, several columns
 ]
 
 
