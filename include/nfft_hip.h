@@ -414,6 +414,40 @@ int nfft_hip_ewald_near(const nfft_hip_ewald_problem *p, const float *points, co
                         const int64_t *index, float *z, float *field, void *workspace, int64_t workspace_bytes,
                         void *stream);
 
+/* ---- the same pair sum in an orthorhombic or triclinic box (no reference counterpart) ----
+ * The box is the lower-triangular matrix A whose rows are the lattice vectors,
+ *     a_1 = (A00, 0, 0), a_2 = (A10, A11, 0), a_3 = (A20, A21, A22),   box[6] = A00, A10, A11, A20, A21, A22,
+ * with a positive diagonal.  The points are FRACTIONAL, s in [-1/2, 1/2)^3 with Cartesian x = s A, and
+ *     d_ij = (ds - rint(ds)) A,  ds = s_i - s_j,   r_ij = |d_ij|,
+ * so alpha, r_cut, z and field (Cartesian components) are in the box's own units; the sums are those of
+ * nfft_hip_ewald_near.  The perpendicular width of the box along fractional axis a is w_a = 1 / |column a of A^-1|.
+ *
+ * The points come ORDERED BY CELL: cells[0] x cells[1] x cells[2] cells of fractional edge 1 / cells[a] with
+ * w_a / cells[a] >= r_cut, cell index c_0 + G_0 (c_1 + G_1 c_2) with c_a = min(floor((s_a + 1/2) G_a), G_a - 1),
+ * key = point set * G_0 G_1 G_2 + cell; points, xr, start (int32 [batch_size * G_0 G_1 G_2 + 1]) and index as for
+ * nfft_hip_ewald_near.  Every G_a >= 3 is required, hence r_cut <= min_a w_a / 3: then an image with |d| < r_cut has
+ * |ds_a| <= |d| / w_a < 1/3 on every axis, so the componentwise rint finds it, it is the only one, and it lies in one of
+ * the 27 wrapped neighbour cells.
+ * nfft_hip_ewald_box_cells proposes cells_out[a] = floor(w_a / r_cut), then lowers the largest entry first until
+ * batch_size * G_0 G_1 G_2 <= 2^20; it returns 0, or -1 with "Input mismatch..." for a non-positive diagonal, entries that
+ * are not finite, r_cut outside (0, min_a w_a / 3] or if no grid with every G_a >= 3 fits that many point sets.
+ * No atomics, two calls give the same bits; no points or no columns: nothing is done.  Workspace: the work items. */
+typedef struct nfft_hip_ewald_box_problem {
+    int32_t cells[3];    /* G_a >= 3 with w_a / G_a >= r_cut */
+    int32_t with_field;  /* 0: z only; 1: z and field */
+    int64_t num_points;
+    int64_t num_columns; /* real columns Cr */
+    int64_t batch_size;
+    double alpha;        /* splitting parameter, > 0 */
+    double r_cut;        /* in (0, min_a w_a / 3] */
+    double box[6];       /* A00, A10, A11, A20, A21, A22 */
+} nfft_hip_ewald_box_problem;
+int64_t nfft_hip_ewald_box_cells(const double *box, double r_cut, int64_t batch_size, int32_t *cells_out);
+int64_t nfft_hip_ewald_near_box_workspace_bytes(const nfft_hip_ewald_box_problem *p);
+int nfft_hip_ewald_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                            const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
+                            int64_t workspace_bytes, void *stream);
+
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.
  *   gaussian_analytic_coeffs      float32:  prod_d sqrt(pi) sigma exp(-sigma^2 pi^2 l_d^2)      (kernel_coeffs.cu:6-30)

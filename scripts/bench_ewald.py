@@ -15,6 +15,14 @@ Device-event medians of `reps` calls after two warm-up calls:
   pairs         distance tests per call = sum over targets of the sources in the 27 cells around it (wrapped for the
                 Ewald sweep, clipped for the yardstick), and nanoseconds per tested pair for each loop
 One JSON line per problem size.
+
+    python scripts/bench_ewald.py --box a,b,c | --box A00,A10,A11,A20,A21,A22 [...]
+
+times the same in an orthorhombic or triclinic box: charges uniform in the box (fractional
+positions), n (4/3) pi r_c^3 = neighbours V, EwaldSplitting.from_tolerance(tol, r_c, box=...); the whole sum, the far field,
+the near operator ops.nfft_ewald_near_box and its pair loop on its own (nfft_hip_ewald_near_box on restated plumbing), with
+the pairs tested and picoseconds per tested pair.  On the identity box (--box 1,1,1) the unit-cube pair loop runs on the same
+points as well: the same cells and pairs, three products and three FMAs fewer per tested pair.  No 1/r yardstick here.
 """
 import argparse
 import ctypes
@@ -66,6 +74,95 @@ def pairs_tested(v, G):
     pad[1:-1, 1:-1, 1:-1] = count
     clipped = sum(pad[1 + a:G + 1 + a, 1 + b:G + 1 + b, 1 + c:G + 1 + c] for a, b, c in shifts)
     return int((count * wrapped).sum()), int((count * clipped).sum())
+
+
+def box_cell_order(pos, G):
+    """cell_order for fractional positions in [-1/2, 1/2)^3 and a cell count per axis"""
+    key, stride = 0, 1
+    for a in range(3):
+        key = key + ((pos[:, a] + 0.5) * float(G[a])).floor().clamp(0, G[a] - 1).to(torch.int64) * stride
+        stride *= G[a]
+    skey, order = torch.sort(key, stable=True)
+    start = torch.searchsorted(skey, torch.arange(stride + 1, device=pos.device), out_int32=True)
+    return pos.index_select(0, order), order, start
+
+
+def box_pairs_tested(v, G):
+    """targets of a cell x sources of the 27 wrapped cells around it, G = (G0, G1, G2)"""
+    cells = [np.clip(np.floor((v[:, a] + np.float32(0.5)) * np.float32(G[a])), 0, G[a] - 1).astype(np.int64) for a in range(3)]
+    count = np.zeros(tuple(G), dtype=np.int64)
+    np.add.at(count, tuple(cells), 1)
+    wrapped = sum(np.roll(count, (a, b, c), axis=(0, 1, 2)) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1))
+    return int((count * wrapped).sum())
+
+
+def run_box(lib, n, args):
+    m = 4
+    box = args.box if len(args.box) == 6 else [args.box[0], 0.0, args.box[1], 0.0, 0.0, args.box[2]]
+    A = [[box[0], 0.0, 0.0], [box[1], box[2], 0.0], [box[3], box[4], box[5]]]
+    probe = tn.EwaldSplitting(1.0, 1e-3 * min(box[0], box[2], box[5]), 2, box=A, device="cpu")  # (volume and widths)
+    r_c = min((3.0 * args.neighbours * probe.volume / (4.0 * math.pi * n)) ** (1.0 / 3.0), min(probe.widths) / 3.0)
+    sp = tn.EwaldSplitting.from_tolerance(args.tol, r_c, box=A)
+    rng = np.random.default_rng(0)
+    v = (rng.random((n, 3)) - 0.5).astype(np.float32)
+    v[v >= 0.5] = -0.5  # (rounded up to the face: the same point)
+    pos = torch.from_numpy(v).cuda()
+    q = torch.from_numpy(rng.standard_normal(n).astype(np.float32)).cuda()
+    G = sp.cells
+    tested = box_pairs_tested(v, G)
+    whole = median_ms(lambda: tn.nfft_ewald(q, pos, splitting=sp, cutoff=m, fractional=True), args.reps)
+    whole_f = median_ms(lambda: tn.nfft_ewald(q, pos, splitting=sp, cutoff=m, field=True, fractional=True), args.reps)
+    far = median_ms(lambda: tn.nfft_fastsum(q, sp.coeffs, pos, cutoff=m), args.reps)
+    near = median_ms(lambda: tn.ops.nfft_ewald_near_box(pos, q, None, box, sp.alpha, r_c, False), args.reps)
+    near_f = median_ms(lambda: tn.ops.nfft_ewald_near_box(pos, q, None, box, sp.alpha, r_c, True), args.reps)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    spos, order, start = box_cell_order(pos, G)
+    xs = q.index_select(0, order).reshape(n, 1).contiguous()
+    z, f = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+    loops = {}
+    for with_field in (0, 1):
+        p = _lib.EwaldBoxProblem(cells=(ctypes.c_int32 * 3)(*G), with_field=with_field, num_points=n, num_columns=1,
+                                 batch_size=1, alpha=sp.alpha, r_cut=r_c, box=(ctypes.c_double * 6)(*box))
+        nbytes = lib.nfft_hip_ewald_near_box_workspace_bytes(ctypes.byref(p))
+        assert nbytes > 0, _lib.last_error()
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+
+        def loop():
+            _lib.check(lib.nfft_hip_ewald_near_box(ctypes.byref(p), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                                   order.data_ptr(), z.data_ptr(), f.data_ptr(), ws.data_ptr(), nbytes, stream))
+
+        loops[with_field] = median_ms(loop, args.reps)
+    zo, fo = tn.ops.nfft_ewald_near_box(pos, q, None, box, sp.alpha, r_c, True)
+    assert torch.equal(zo, z[:, 0]) and torch.equal(fo, f), "the restated plumbing must give the operator's bits"
+    out = {"bench": "ewald_box", "box": box, "points": n, "neighbours": args.neighbours, "tol": args.tol,
+           "r_cut": round(r_c, 5), "alpha": round(sp.alpha, 3), "N": sp.bandwidth, "m": m, "cells": list(G),
+           "ewald_ms": round(whole, 4), "ewald_field_ms": round(whole_f, 4), "far_ms": round(far, 4),
+           "near_ms": round(near, 4), "near_field_ms": round(near_f, 4),
+           "pair_loop_ms": round(loops[0], 4), "pair_loop_field_ms": round(loops[1], 4), "pairs_tested": tested,
+           "ps_per_pair": round(loops[0] * 1e9 / tested, 3), "ps_per_pair_field": round(loops[1] * 1e9 / tested, 3)}
+    if box == [1.0, 0.0, 1.0, 0.0, 0.0, 1.0] and G[0] == G[1] == G[2] == lib.nfft_hip_ewald_near_cells(r_c, 1):
+        # the unit-cube kernel on the same sorted points: the same cells, the same pairs
+        cube = {}
+        zc, fc = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+        for with_field in (0, 1):
+            p = _lib.EwaldProblem(cells_per_axis=G[0], with_field=with_field, num_points=n, num_columns=1, batch_size=1,
+                                  alpha=sp.alpha, r_cut=r_c)
+            nbytes = lib.nfft_hip_ewald_near_workspace_bytes(ctypes.byref(p))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+
+            def cube_loop():
+                _lib.check(lib.nfft_hip_ewald_near(ctypes.byref(p), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                                   order.data_ptr(), zc.data_ptr(), fc.data_ptr(), ws.data_ptr(), nbytes,
+                                                   stream))
+
+            cube[with_field] = median_ms(cube_loop, args.reps)
+        out.update({"cube_pair_loop_ms": round(cube[0], 4), "cube_pair_loop_field_ms": round(cube[1], 4),
+                    "cube_ps_per_pair": round(cube[0] * 1e9 / tested, 3),
+                    "cube_ps_per_pair_field": round(cube[1] * 1e9 / tested, 3),
+                    "box_over_cube": round(loops[0] / cube[0], 3), "box_over_cube_field": round(loops[1] / cube[1], 3),
+                    "max_abs_difference": float((z - zc).abs().max())})
+    tn.ops.check_status()
+    print(json.dumps(out))
 
 
 def run(lib, n, args):
@@ -142,11 +239,15 @@ def main():
     ap.add_argument("--neighbours", type=float, default=100.0)
     ap.add_argument("--tol", type=float, default=1e-5)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--box", type=lambda t: [float(e) for e in t.split(",")], default=None,
+                    help="a,b,c (orthorhombic) or A00,A10,A11,A20,A21,A22 (lower triangular, rows = lattice vectors)")
     args = ap.parse_args()
+    if args.box is not None and len(args.box) not in (3, 6):
+        ap.error("--box takes three or six comma-separated numbers")
     torch.cuda.set_device(0)
     lib = _lib.load()
     for n in args.points:
-        run(lib, n, args)
+        (run if args.box is None else run_box)(lib, n, args)
 
 
 if __name__ == "__main__":

@@ -59,6 +59,9 @@ SYMBOLS = (
     "nfft_hip_ewald_near_cells",
     "nfft_hip_ewald_near_workspace_bytes",
     "nfft_hip_ewald_near",
+    "nfft_hip_ewald_box_cells",
+    "nfft_hip_ewald_near_box_workspace_bytes",
+    "nfft_hip_ewald_near_box",
     "nfft_hip_gaussian_analytic_coeffs",
     "nfft_hip_interpolation_grid",
     "nfft_hip_coeffs_workspace_bytes",
@@ -118,6 +121,20 @@ class EwaldProblem(ctypes.Structure):
         ("batch_size", ctypes.c_int64),
         ("alpha", ctypes.c_double),
         ("r_cut", ctypes.c_double),
+    ]
+
+
+class EwaldBoxProblem(ctypes.Structure):
+    """``nfft_hip_ewald_box_problem`` of include/nfft_hip.h."""
+    _fields_ = [
+        ("cells", ctypes.c_int32 * 3),
+        ("with_field", ctypes.c_int32),
+        ("num_points", ctypes.c_int64),
+        ("num_columns", ctypes.c_int64),
+        ("batch_size", ctypes.c_int64),
+        ("alpha", ctypes.c_double),
+        ("r_cut", ctypes.c_double),
+        ("box", ctypes.c_double * 6),
     ]
 
 
@@ -224,6 +241,13 @@ def load():
     lib.nfft_hip_ewald_near_workspace_bytes.restype = i64
     lib.nfft_hip_ewald_near.argtypes = [ctypes.POINTER(EwaldProblem), vp, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.nfft_hip_ewald_near.restype = ci
+    lib.nfft_hip_ewald_box_cells.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_double, i64,
+                                             ctypes.POINTER(ctypes.c_int32)]
+    lib.nfft_hip_ewald_box_cells.restype = i64
+    lib.nfft_hip_ewald_near_box_workspace_bytes.argtypes = [ctypes.POINTER(EwaldBoxProblem)]
+    lib.nfft_hip_ewald_near_box_workspace_bytes.restype = i64
+    lib.nfft_hip_ewald_near_box.argtypes = [ctypes.POINTER(EwaldBoxProblem), vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.nfft_hip_ewald_near_box.restype = ci
     lib.nfft_hip_gaussian_analytic_coeffs.argtypes = [ctypes.c_double, i64, ctypes.c_int32, vp, vp]
     lib.nfft_hip_gaussian_analytic_coeffs.restype = ci
     lib.nfft_hip_interpolation_grid.argtypes = [i64, ctypes.c_int32, ci, vp, vp]

@@ -11,6 +11,7 @@
 #include "../../include/nfft_hip.h"
 
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -1693,6 +1694,128 @@ int nfft_hip_ewald_near(const nfft_hip_ewald_problem *p, const float *points, co
     if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
     char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
     return launch_ewald_near(p, points, xr, start, index, z, field, ws, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- the same pair sum in an orthorhombic or triclinic box ------------------------------------
+namespace {
+
+// perpendicular widths w_a = 1 / |column a of A^-1| of the box A00, A10, A11, A20, A21, A22; false unless every entry is
+// finite and the diagonal positive
+bool ewald_box_widths(const double *box, double *w)
+{
+    for (int e = 0; e < 6; ++e)
+        if (!(box[e] == box[e]) || box[e] > 1e300 || box[e] < -1e300) return false;
+    const double a00 = box[0], a10 = box[1], a11 = box[2], a20 = box[3], a21 = box[4], a22 = box[5];
+    if (!(a00 > 0.0) || !(a11 > 0.0) || !(a22 > 0.0)) return false;
+    // A^-1 is lower triangular too
+    const double i00 = 1.0 / a00, i11 = 1.0 / a11, i22 = 1.0 / a22;
+    const double i10 = -a10 * i00 * i11, i21 = -a21 * i11 * i22;
+    const double i20 = (a10 * a21 - a11 * a20) * i00 * i11 * i22;
+    w[0] = 1.0 / std::sqrt(i00 * i00 + i10 * i10 + i20 * i20);
+    w[1] = 1.0 / std::sqrt(i11 * i11 + i21 * i21);
+    w[2] = a22;
+    for (int a = 0; a < 3; ++a)
+        if (!(w[a] > 0.0) || !(w[a] < 1e300)) return false;
+    return true;
+}
+
+// r_cut in (0, min_a w_a / 3] (the quotient's last bit is not held against the caller)
+bool ewald_box_r_cut_ok(const double *w, double r_cut)
+{
+    const double wmin = std::min(w[0], std::min(w[1], w[2]));
+    return r_cut > 0.0 && r_cut * (1.0 - 1e-12) <= wmin / 3.0;
+}
+
+int validate_ewald_box(const nfft_hip_ewald_box_problem *p)
+{
+    if (!p) { set_error("Input mismatch: null problem"); return NFFT_HIP_EINVAL; }
+    if (p->with_field != 0 && p->with_field != 1) { set_error("Input mismatch: with_field must be 0 or 1"); return NFFT_HIP_EINVAL; }
+    if (p->num_points < 0 || p->num_columns < 0 || p->batch_size < 1) {
+        set_error("Input mismatch: negative size");
+        return NFFT_HIP_EINVAL;
+    }
+    if (p->num_points >= (int64_t(1) << 31)) { set_error("Input mismatch: too many points"); return NFFT_HIP_EINVAL; }
+    if (!(p->alpha > 0.0) || !(p->alpha < 1e18)) { set_error("Input mismatch: alpha must be positive and finite"); return NFFT_HIP_EINVAL; }
+    double w[3];
+    if (!ewald_box_widths(p->box, w)) {
+        set_error("Input mismatch: the box must be finite with a positive diagonal");
+        return NFFT_HIP_EINVAL;
+    }
+    if (!ewald_box_r_cut_ok(w, p->r_cut)) {
+        set_error("Input mismatch: r_cut must lie in (0, min w_a / 3] for the box's perpendicular widths w_a");
+        return NFFT_HIP_EINVAL;
+    }
+    int64_t cells = p->batch_size;
+    for (int a = 0; a < 3; ++a) {
+        if (p->cells[a] < 3 || p->cells[a] > 1024 || w[a] / p->cells[a] < p->r_cut * (1.0 - 1e-12)) {
+            set_error("Input mismatch: cells must be at least 3 per axis with a width w_a / cells[a] >= r_cut");
+            return NFFT_HIP_EINVAL;
+        }
+        cells = cells > kNearMaxCells ? cells : cells * p->cells[a];
+    }
+    if (cells > kNearMaxCells) { set_error("Input mismatch: too many cells"); return NFFT_HIP_EINVAL; }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nfft_hip_ewald_box_cells(const double *box, double r_cut, int64_t batch_size, int32_t *cells_out)
+{
+    double w[3];
+    if (!box || !cells_out) { set_error("Input mismatch: null input"); return -1; }
+    if (!ewald_box_widths(box, w)) {
+        set_error("Input mismatch: the box must be finite with a positive diagonal");
+        return -1;
+    }
+    if (!ewald_box_r_cut_ok(w, r_cut) || batch_size < 1) {
+        set_error("Input mismatch: ewald cells need r_cut in (0, min w_a / 3] and batch_size >= 1");
+        return -1;
+    }
+    int64_t G[3];
+    for (int a = 0; a < 3; ++a) {
+        G[a] = (int64_t)std::min(w[a] / r_cut, 1024.0);
+        while (G[a] > 3 && w[a] / (double)G[a] < r_cut) --G[a];  // (the quotient may have been rounded up)
+        if (G[a] < 3) G[a] = 3;                                  // (... or down, at r_cut = w_a / 3)
+    }
+    while (batch_size <= kNearMaxCells && batch_size * G[0] * G[1] * G[2] > kNearMaxCells) {
+        int a = 0;  // the largest count first
+        if (G[1] > G[a]) a = 1;
+        if (G[2] > G[a]) a = 2;
+        if (G[a] <= 3) break;
+        --G[a];
+    }
+    if (batch_size > kNearMaxCells || batch_size * G[0] * G[1] * G[2] > kNearMaxCells) {
+        set_error("Input mismatch: too many point sets for a grid of 3 cells per axis");
+        return -1;
+    }
+    for (int a = 0; a < 3; ++a) cells_out[a] = (int32_t)G[a];
+    return 0;
+}
+
+int64_t nfft_hip_ewald_near_box_workspace_bytes(const nfft_hip_ewald_box_problem *p)
+{
+    if (validate_ewald_box(p)) return -1;
+    return ewald_near_box_item_slots(p) * (int64_t)sizeof(int2) + 256;
+}
+
+int nfft_hip_ewald_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                            const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
+                            int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_ewald_box(p)) return rc;
+    if (p->num_points == 0 || p->num_columns == 0) return 0;
+    if (!z) { set_error("Input mismatch: z is null"); return NFFT_HIP_EINVAL; }
+    if (p->with_field && !field) { set_error("Input mismatch: field is null"); return NFFT_HIP_EINVAL; }
+    if (!points || !xr || !start || !index) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    const int64_t need = ewald_near_box_item_slots(p) * (int64_t)sizeof(int2) + 256;
+    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    return launch_ewald_near_box(p, points, xr, start, index, z, field, ws, (hipStream_t)stream);
 }
 
 }  // extern "C"

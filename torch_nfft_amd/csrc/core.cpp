@@ -1049,6 +1049,82 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_near(at::Tensor pos, at::Tensor x,
     return {z.reshape(z_shape), f.reshape(f_shape)};
 }
 
+// ---- the same pair sum in an orthorhombic or triclinic box (not in the reference) ---------------
+// torus_cell_order's sibling with a cell count per axis: `pos` fractional and already reduced to [-1/2, 1/2)^3, the key of
+// nfft_hip_ewald_near_box in include/nfft_hip.h
+CellOrder box_cell_order(const at::Tensor &pos, const at::Tensor &batch, int64_t B, const int32_t *G)
+{
+    at::Tensor key;
+    int64_t stride = 1;
+    for (int a = 0; a < 3; ++a) {
+        const at::Tensor cell = ((pos.select(1, a) + 0.5) * (double)G[a]).floor().clamp(0, G[a] - 1).to(at::kLong);
+        key = a == 0 ? cell : key + cell * stride;
+        stride *= G[a];
+    }
+    if (batch.defined()) key = key + batch * stride;
+    const auto sorted = at::sort(key, /*stable=*/true, /*dim=*/0, /*descending=*/false);
+    CellOrder o;
+    o.order = std::get<1>(sorted);
+    o.start = at::searchsorted(std::get<0>(sorted), at::arange(B * stride + 1, key.options()), /*out_int32=*/true);
+    o.pos = pos.index_select(0, o.order);
+    return o;
+}
+
+// (z, f) of nfft_ewald_near in the box A = box (A00, A10, A11, A20, A21, A22; rows = lattice vectors): pos holds FRACTIONAL
+// coordinates, taken modulo 1; r_ij is the length of d_ij = (ds - rint(ds)) A and f is Cartesian.
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_near_box(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch,
+                                                       std::vector<double> box, double alpha, double r_cut, bool with_field)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_near_box is currently only implemented for GPU tensors");
+    const Points p = check_points(pos, opt_batch, "batch");
+    CHECK_INPUT(p.dim == 3);
+    CHECK_INPUT(box.size() == 6);
+    const bool real_input = real_dtype(x);
+    CHECK_INPUT(x.dim() >= 1);
+    CHECK_INPUT(x.size(0) == p.n);
+    CHECK_INPUT(x.device() == pos.device());
+    int64_t C = 1;
+    std::vector<int64_t> z_shape{p.n}, f_shape{p.n, 3};
+    for (int64_t d = 1; d < x.dim(); ++d) {
+        C *= x.size(d);
+        z_shape.push_back(x.size(d));
+        f_shape.push_back(x.size(d));
+    }
+    if (!with_field) f_shape = {0};
+    nfft_hip_ewald_box_problem q;
+    q.with_field = with_field ? 1 : 0;
+    q.num_points = p.n;
+    q.num_columns = real_input ? C : 2 * C;
+    q.batch_size = p.B;
+    q.alpha = alpha;
+    q.r_cut = r_cut;
+    for (int e = 0; e < 6; ++e) q.box[e] = box[e];
+    if (nfft_hip_ewald_box_cells(q.box, r_cut, q.batch_size, q.cells) < 0) check_rc(NFFT_HIP_EINVAL);
+    const int64_t ws_bytes = nfft_hip_ewald_near_box_workspace_bytes(&q);
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    if (p.n == 0 || C == 0) return {at::zeros(z_shape, x.options()), at::zeros(f_shape, x.options())};  // no launch
+    c10::DeviceGuard guard(x.device());
+    // s modulo 1 in [-1/2, 1/2), as nfft_ewald_near does: what comes out as +1/2 is the point -1/2
+    at::Tensor red = p.pos - p.pos.round();
+    red = at::where(red >= 0.5, red - 1.0, red);
+    const CellOrder o = box_cell_order(red, p.batch, p.B, q.cells);
+    const at::Tensor xc = x.contiguous();
+    const at::Tensor xr = (real_input ? xc : at::view_as_real(xc)).reshape({p.n, q.num_columns}).index_select(0, o.order);
+    // (zeros: a point whose coordinates are not numbers has no cell and is not written)
+    const at::TensorOptions opts = x.options().dtype(at::kFloat);
+    at::Tensor z = at::zeros({p.n, q.num_columns}, opts);
+    at::Tensor f = with_field ? at::zeros({p.n, 3 * q.num_columns}, opts) : at::empty({0}, x.options());
+    at::Tensor ws = byte_buffer(ws_bytes, x);
+    check_rc(nfft_hip_ewald_near_box(&q, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
+                                     o.order.data_ptr<int64_t>(), z.data_ptr<float>(),
+                                     with_field ? f.data_ptr<float>() : nullptr, ws.data_ptr(), ws_bytes, stream_of(x)));
+    if (!real_input) {
+        z = at::view_as_complex(z.reshape({p.n, C, 2}));
+        if (with_field) f = at::view_as_complex(f.reshape({p.n, 3 * C, 2}));
+    }
+    return {z.reshape(z_shape), f.reshape(f_shape)};
+}
+
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
 at::TensorOptions current_device_options(at::ScalarType dtype)
 {
@@ -1173,4 +1249,7 @@ TORCH_LIBRARY(torch_nfft, m)
     // not in the reference: the wrapped pair sum erfc(alpha r) / r of the Ewald sum and its field (nfft_ewald)
     m.def("_nfft_ewald_near(Tensor pos, Tensor x, Tensor? batch, float alpha, float r_cut, bool with_field) "
           "-> (Tensor, Tensor)", &nfft_ewald_near);
+    // not in the reference: the same pair sum in an orthorhombic or triclinic box, on fractional positions
+    m.def("_nfft_ewald_near_box(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut, bool with_field) "
+          "-> (Tensor, Tensor)", &nfft_ewald_near_box);
 }

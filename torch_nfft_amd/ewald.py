@@ -13,35 +13,108 @@ The far part is ``nfft_fastsum`` on the whole torus with the coefficients ``b`` 
 unpaired planes ``k_a = -N/2`` zeroed so that a real ``q`` gives a real ``phi`` and the operator stays symmetric); the near
 part is one native pair sweep that wraps around the box (``ops.nfft_ewald_near``).  A box of length ``L`` is a rescaling
 that the caller does: ``phi_L(x) = phi_1(x / L) / L`` and ``E_L(x) = E_1(x / L) / L^2``.
+
+Orthorhombic and triclinic boxes: ``EwaldSplitting(..., box=A)`` with the lower-triangular matrix
+``A`` whose rows are the lattice vectors.  A Cartesian point is ``x = s A`` with fractional ``s`` in ``[-1/2, 1/2)^3``, the
+wave vector of the integer frequency ``k`` is ``kappa = A^-1 k``, ``V = det A``, and::
+
+    phi_i =   sum_{j != i, 0 < r_ij < r_c} q_j erfc(alpha r_ij) / r_ij          r_ij = |d_ij|, d_ij = (ds - rint(ds)) A, ds = s_i - s_j
+            + sum_{k != 0} b_k e^{2 pi i k.s_i} sum_j q_j e^{-2 pi i k.s_j}      b_k = exp(-pi^2 |kappa|^2 / alpha^2) / (pi V |kappa|^2)
+            - (2 alpha / sqrt(pi)) q_i - pi Q / (alpha^2 V)
+    E_i   = -grad_x phi_i                                                       (Cartesian)
+
+``alpha``, ``r_c``, ``phi`` and ``E`` are in the box's own Cartesian units.  The transforms run on the fractional
+coordinates with anisotropic coefficients; the pair sweep is ``ops.nfft_ewald_near_box``.
 """
+import ctypes
 import math
 
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import ops
+from . import _lib, ops
 from .nfft import nfft_adjoint, nfft_forward, nfft_fastsum
 
 MAX_R_CUT = 1.0 / 3.0  # the pair sweep needs 3 cells of edge >= r_cut per axis
 
 
+def _box_matrix(box):
+    """``box`` (length 3: the edges of an orthorhombic cell; or ``[3, 3]`` lower triangular, rows = lattice vectors) as a
+    float64 ``[3, 3]`` tensor on the host.  ValueError for another shape, entries that are not finite, entries above the
+    diagonal that are not zero or a diagonal that is not positive; AssertionError for a tensor that requires grad."""
+    if isinstance(box, torch.Tensor):
+        if box.requires_grad:
+            raise AssertionError("EwaldSplitting is not differentiable w.r.t. the box, but box requires grad")
+        A = box.detach().to(device="cpu", dtype=torch.float64)
+    else:
+        A = torch.as_tensor(box, dtype=torch.float64)
+    if A.shape == (3,):
+        A = torch.diag(A)
+    if A.shape != (3, 3):
+        raise ValueError("EwaldSplitting: box must have length 3 (orthorhombic) or be [3, 3] lower triangular")
+    if not bool(torch.isfinite(A).all()):
+        raise ValueError("EwaldSplitting: the entries of box must be finite")
+    if bool((torch.triu(A, 1) != 0).any()):
+        raise ValueError("EwaldSplitting: box must be lower triangular (rows = lattice vectors a_1 = (A00, 0, 0), "
+                         "a_2 = (A10, A11, 0), a_3); see the class docstring for a general cell")
+    if not bool((torch.diagonal(A) > 0).all()):
+        raise ValueError("EwaldSplitting: the diagonal of box must be positive")
+    return A.contiguous()
+
+
+def _box_inverse(A):
+    """``A^-1`` of the lower-triangular ``A`` (lower triangular too), in closed form"""
+    a00, a10, a11, a20, a21, a22 = (float(A[i, j]) for i, j in ((0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2)))
+    i00, i11, i22 = 1.0 / a00, 1.0 / a11, 1.0 / a22
+    return torch.tensor([[i00, 0.0, 0.0],
+                         [-a10 * i00 * i11, i11, 0.0],
+                         [(a10 * a21 - a11 * a20) * i00 * i11 * i22, -a21 * i11 * i22, i22]], dtype=torch.float64)
+
+
+def _box_widths(A):
+    """the perpendicular widths ``w_a = 1 / |column a of A^-1|`` of the cell along its three fractional axes"""
+    inv = _box_inverse(A)
+    return tuple(1.0 / math.sqrt(float((inv[:, a] * inv[:, a]).sum())) for a in range(3))
+
+
 class EwaldSplitting:
-    """The three parameters of the split and the far field's coefficients.
+    """The three parameters of the split, the box and the far field's coefficients.
 
     ``alpha > 0`` is the splitting parameter, ``r_cut`` in ``(0, 1/3]`` the radius of the pair sum, ``bandwidth`` (even)
     the number ``N`` of frequencies per axis.  ``coeffs`` is ``[N, N, N]`` float32 on ``device``: ``b_k`` at index
     ``k + N/2``, evaluated in float64 on the host, ``b_0 = 0`` and the unpaired planes ``k_a = -N/2`` zeroed.
-    ValueError for an odd or too small ``bandwidth``, ``alpha <= 0`` or ``r_cut`` outside ``(0, 1/3]``."""
+    ValueError for an odd or too small ``bandwidth``, ``alpha <= 0`` or ``r_cut`` outside ``(0, 1/3]``.
 
-    def __init__(self, alpha, r_cut, bandwidth, device="cuda"):
+    ``box`` is ``None`` (the unit cube), a sequence of three edges ``(Lx, Ly, Lz)`` (orthorhombic) or a ``[3, 3]``
+    lower-triangular matrix ``A`` whose rows are the lattice vectors ``a_1 = (A00, 0, 0)``, ``a_2 = (A10, A11, 0)``,
+    ``a_3 = (A20, A21, A22)`` with a positive diagonal (the LAMMPS / GROMACS convention).  ``alpha`` and ``r_cut`` are
+    then in the box's Cartesian units, ``r_cut`` at most ``min_a w_a / 3`` for the perpendicular widths
+    ``w_a = 1 / |column a of A^-1|``, and ``coeffs`` holds ``exp(-pi^2 |kappa|^2 / alpha^2) / (pi V |kappa|^2)`` with
+    ``kappa = A^-1 k``, ``V = det A``.  ValueError for entries above the diagonal that are not zero, a diagonal that is
+    not positive or ``r_cut > min_a w_a / 3``; a ``box`` tensor that requires grad is refused (AssertionError).
+
+    A general cell ``M`` (rows = lattice vectors, any orientation) is brought to this form by a QR factorisation of its
+    transpose: ``Q, R = qr(M^T)``, signs flipped so that ``diag R > 0`` (``Q <- Q D``, ``R <- D R``, ``D = diag(sign
+    R_ii)``), then ``box = R^T`` and the positions are rotated with it, ``pos <- pos Q``; fractional coordinates do not
+    change.  The field comes out in the rotated frame: ``E Q^T`` is the field in the original one.
+
+    Attributes: ``box`` (``[3, 3]`` float64 on the host, or ``None``), ``volume``, ``widths`` and ``cells`` (the cell counts
+    of the pair sweep for one point set)."""
+
+    def __init__(self, alpha, r_cut, bandwidth, box=None, device="cuda"):
         alpha, r_cut, N = float(alpha), float(r_cut), int(bandwidth)
         if N != bandwidth or N < 2 or N % 2:
             raise ValueError("EwaldSplitting: bandwidth must be even and >= 2")
         if not (alpha > 0.0 and math.isfinite(alpha)):
             raise ValueError("EwaldSplitting: alpha must be positive")
+        if box is not None:
+            self._init_box(alpha, r_cut, N, _box_matrix(box), device)
+            return
         if not 0.0 < r_cut <= MAX_R_CUT:
             raise ValueError("EwaldSplitting: r_cut must lie in (0, 1/3]")
         self.alpha, self.r_cut, self.bandwidth = alpha, r_cut, N
+        self.box, self.volume, self.widths = None, 1.0, (1.0, 1.0, 1.0)
+        self.cells = (int(_lib.load().nfft_hip_ewald_near_cells(r_cut, 1)),) * 3
         k = torch.arange(-(N // 2), N // 2, dtype=torch.float64)
         k2 = (k * k).reshape(N, 1, 1) + (k * k).reshape(1, N, 1) + (k * k).reshape(1, 1, N)
         b = torch.exp(-(math.pi / alpha) ** 2 * k2) / (math.pi * k2.clamp(min=1.0))
@@ -52,25 +125,91 @@ class EwaldSplitting:
         self.coeffs = b.to(torch.float32).to(torch.device(device)).contiguous()
         self._field_coeffs = None
 
+    def _init_box(self, alpha, r_cut, N, A, device):
+        widths = _box_widths(A)
+        if not 0.0 < r_cut <= min(widths) / 3.0:
+            raise ValueError("EwaldSplitting: r_cut must lie in (0, min w_a / 3] = (0, %.6g] for this box (perpendicular "
+                             "widths %.6g, %.6g, %.6g)" % ((min(widths) / 3.0,) + widths))
+        self.alpha, self.r_cut, self.bandwidth = alpha, r_cut, N
+        self.box, self.widths = A, widths
+        self.volume = float(A[0, 0] * A[1, 1] * A[2, 2])
+        cells = (ctypes.c_int32 * 3)()
+        six = (ctypes.c_double * 6)(*self.box6)
+        if _lib.load().nfft_hip_ewald_box_cells(six, r_cut, 1, cells) < 0:
+            raise ValueError("EwaldSplitting: " + _lib.last_error())
+        self.cells = tuple(int(c) for c in cells)
+        kappa = self._kappa()
+        k2 = (kappa * kappa).sum(3)
+        b = torch.exp(-(math.pi / alpha) ** 2 * k2) / (math.pi * self.volume * torch.where(k2 > 0, k2, torch.ones_like(k2)))
+        b[N // 2, N // 2, N // 2] = 0.0
+        b[0, :, :] = 0.0
+        b[:, 0, :] = 0.0
+        b[:, :, 0] = 0.0
+        self._b64 = b
+        self.coeffs = b.to(torch.float32).to(torch.device(device)).contiguous()
+        self._field_coeffs = None
+        self._on_device = {}
+
+    @property
+    def box6(self):
+        """``(A00, A10, A11, A20, A21, A22)``: the box as ``ops.nfft_ewald_near_box`` takes it"""
+        A = self.box
+        return tuple(float(A[i, j]) for i, j in ((0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2)))
+
+    def _kappa(self):
+        """``[N, N, N, 3]`` float64 on the host: the Cartesian wave vectors ``kappa_b = sum_a (A^-1)_ba k_a``"""
+        N = self.bandwidth
+        inv = _box_inverse(self.box)
+        k = torch.arange(-(N // 2), N // 2, dtype=torch.float64)
+        ks = (k.reshape(N, 1, 1), k.reshape(1, N, 1), k.reshape(1, 1, N))
+        return torch.stack([sum(float(inv[b, a]) * ks[a] for a in range(3)).expand(N, N, N) for b in range(3)], 3)
+
+    def _matrices(self, device):
+        """(``A`` float32, ``A^-1`` float64) on ``device``"""
+        key = str(device)
+        if key not in self._on_device:
+            self._on_device[key] = (self.box.to(torch.float32).to(device), _box_inverse(self.box).to(device))
+        return self._on_device[key]
+
     @classmethod
-    def from_tolerance(cls, tol, r_cut, device="cuda"):
+    def from_tolerance(cls, tol, r_cut, box=None, device="cuda"):
         """``alpha = sqrt(-ln tol) / r_cut`` and ``bandwidth`` the next even integer ``>= 2 alpha sqrt(-ln tol) / pi``:
         the two truncation factors -- ``erfc(alpha r_c) ~ e^(-alpha^2 r_c^2)`` of the pair sum at ``r_cut`` and
         ``e^(-pi^2 k^2 / alpha^2)`` of the far sum at ``k = N/2`` -- both set to ``tol``.  A rule of thumb, not a bound:
-        the errors of the two sums also carry the number of charges and the prefactors ``1/r`` and ``1/(pi k^2)``."""
+        the errors of the two sums also carry the number of charges and the prefactors ``1/r`` and ``1/(pi k^2)``.
+
+        With a ``box`` the plane ``k_a = N/2`` lies at the distance ``(N/2) / |a_a|`` from the origin of reciprocal space,
+        so ``bandwidth`` is the next even integer ``>= 2 alpha sqrt(-ln tol) max_a |a_a| / pi``.  The grid is cubic in
+        ``N``: the longest lattice vector sets ``N`` for all three axes."""
         tol = float(tol)
         if not 0.0 < tol < 1.0:
             raise ValueError("EwaldSplitting.from_tolerance: tol must lie in (0, 1)")
+        s = math.sqrt(-math.log(tol))
+        if box is not None:
+            A = _box_matrix(box)
+            if not 0.0 < float(r_cut) <= min(_box_widths(A)) / 3.0:
+                raise ValueError("EwaldSplitting: r_cut must lie in (0, min w_a / 3] for this box")
+            alpha = s / float(r_cut)
+            longest = max(math.sqrt(float((A[a] * A[a]).sum())) for a in range(3))
+            N = max(2, 2 * math.ceil(alpha * s * longest / math.pi))
+            return cls(alpha, r_cut, N, box=A, device=device)
         if not 0.0 < float(r_cut) <= MAX_R_CUT:
             raise ValueError("EwaldSplitting: r_cut must lie in (0, 1/3]")
-        s = math.sqrt(-math.log(tol))
         alpha = s / float(r_cut)
         N = max(2, 2 * math.ceil(alpha * s / math.pi))
         return cls(alpha, r_cut, N, device=device)
 
     def field_coeffs(self):
         """``[N, N, N, 4]`` complex64: ``b_k`` and, for the three axes, ``(+2 pi i k_a) b_k`` -- the coefficients of
-        ``phi`` and of ``E = -grad phi`` as four columns of one forward transform (built on first use)."""
+        ``phi`` and of ``E = -grad phi`` as four columns of one forward transform (built on first use).  With a box the
+        three are ``(+2 pi i kappa_b) b_k``, the Cartesian components, from the float64 values on the host."""
+        if self._field_coeffs is None and self.box is not None:
+            b = self._b64
+            cols = [torch.complex(b, torch.zeros_like(b))]
+            kappa = self._kappa()
+            for a in range(3):
+                cols.append(torch.complex(torch.zeros_like(b), 2.0 * math.pi * kappa[..., a] * b))
+            self._field_coeffs = torch.stack(cols, 3).to(torch.complex64).to(self.coeffs.device).contiguous()
         if self._field_coeffs is None:
             N, b = self.bandwidth, self.coeffs
             freq = 2.0 * math.pi * torch.arange(-(N // 2), N // 2, dtype=torch.float32, device=b.device)
@@ -94,7 +233,8 @@ def _set_sums(q, batch):
 
 
 def _ewald(q, pos, batch, splitting, cutoff, field):
-    """(phi, E or None) without autograd: far field, pair sweep, self and background terms"""
+    """(phi, E or None) without autograd: far field, pair sweep, self and background terms (with a box: ``pos`` fractional,
+    ``E`` Cartesian)"""
     N = splitting.bandwidth
     if field:
         cols = [1] * (q.dim() - 1)
@@ -104,8 +244,13 @@ def _ewald(q, pos, batch, splitting, cutoff, field):
         phi, E = far[:, 0], far[:, 1:]
     else:
         phi, E = nfft_fastsum(q, splitting.coeffs, pos, None, batch, None, cutoff=cutoff), None
-    z, f = ops.nfft_ewald_near(pos, q, batch, splitting.alpha, splitting.r_cut, field)
     alpha = splitting.alpha
+    if splitting.box is not None:
+        z, f = ops.nfft_ewald_near_box(pos, q, batch, splitting.box6, alpha, splitting.r_cut, field)
+        background = math.pi / (alpha * alpha * splitting.volume)
+        phi = phi + z - (2.0 * alpha / math.sqrt(math.pi)) * q - background * _set_sums(q, batch)[1]
+        return phi, (E + f if field else None)
+    z, f = ops.nfft_ewald_near(pos, q, batch, splitting.alpha, splitting.r_cut, field)
     phi = phi + z - (2.0 * alpha / math.sqrt(math.pi)) * q - (math.pi / (alpha * alpha)) * _set_sums(q, batch)[1]
     return phi, (E + f if field else None)
 
@@ -114,7 +259,9 @@ class NfftEwaldFunction(torch.autograd.Function):
     """``(phi, E)`` of ``nfft_ewald`` (``E`` empty without ``field``).  The operator ``q -> phi`` is real symmetric, so for
     ``g = dL/dphi`` the gradient in ``q`` is the operator applied to ``g``, and the gradient in the positions is
     ``dL/dpos_i = -sum_c (g_ic E[q_c]_i + q_ic E[g_c]_i)``: one field evaluation with ``q`` and ``g`` side by side as
-    columns.  First order only (``once_differentiable``); ``E`` is not differentiable."""
+    columns.  First order only (``once_differentiable``); ``E`` is not differentiable.  With a box ``pos`` holds the
+    fractional coordinates ``s`` (``x = s A``), ``E`` is Cartesian, the formula gives ``dL/dx`` and the backward returns
+    ``dL/ds = (dL/dx) A^T``."""
 
     @staticmethod
     def forward(ctx, q, pos, batch, splitting, cutoff, field):
@@ -141,6 +288,8 @@ class NfftEwaldFunction(torch.autograd.Function):
             w = g.unsqueeze(1).conj() * E[:, :, 0] + q.unsqueeze(1).conj() * E[:, :, 1]
             w = w.real if w.is_complex() else w
             dpos = -w.reshape(w.size(0), 3, math.prod(w.shape[2:])).sum(2)
+            if ctx.splitting.box is not None:
+                dpos = dpos @ ctx.splitting._matrices(dpos.device)[0].t()
         elif need_q:
             dq = _ewald(g, pos, batch, ctx.splitting, ctx.cutoff, False)[0]
         return dq if need_q else None, dpos, None, None, None, None
@@ -155,7 +304,18 @@ def _check(what, q, pos, batch, splitting):
         raise AssertionError("%s is differentiable w.r.t. q and pos only, but batch requires grad" % what)
 
 
-def nfft_ewald(q, pos, batch=None, /, splitting=None, cutoff=4, field=False):
+def _fractional(what, pos, splitting, fractional):
+    """the positions as the Function takes them: as they are without a box, fractional with one"""
+    if splitting.box is None:
+        if fractional:
+            raise ValueError("%s: fractional=True needs an EwaldSplitting with a box" % what)
+        return pos
+    if fractional:
+        return pos
+    return (pos.double() @ splitting._matrices(pos.device)[1]).float()
+
+
+def nfft_ewald(q, pos, batch=None, /, splitting=None, cutoff=4, field=False, fractional=False):
     """The periodic Coulomb potential ``phi_i = sum'_{j, n} q_j / |x_i - x_j + n|`` of the charges ``q`` ``[n, *cols]``
     (float32 or complex64) at ``pos`` ``[n, 3]`` in the unit box, over the charges of i's point set (``batch``: sorted
     point-set indices, as everywhere) and all their periodic images, in the Ewald sense: the self pair is left out, and
@@ -168,16 +328,26 @@ def nfft_ewald(q, pos, batch=None, /, splitting=None, cutoff=4, field=False):
     native pair sweep, then the self and background terms.
 
     Differentiable once in ``q`` and ``pos`` (for ``U = nfft_ewald_energy``, ``-dU/dpos_i = q_i E_i``); ``E`` itself is not
-    differentiable, a second derivative raises a RuntimeError, and ``batch`` must not require grad (AssertionError)."""
+    differentiable, a second derivative raises a RuntimeError, and ``batch`` must not require grad (AssertionError).
+
+    With ``splitting.box`` set the charges live in that box: ``pos`` is Cartesian, ``x = s A``, taken modulo the lattice
+    (converted in float64, ``s = pos A^-1``, and rounded to float32), or with ``fractional=True`` the fractional
+    coordinates ``s`` themselves, taken modulo 1.  ``phi`` and ``E`` are in the box's units and ``E`` is always Cartesian;
+    the gradient comes back in the coordinates that were passed (``dL/ds = (dL/dx) A^T``).  Without a box ``fractional``
+    must stay False (ValueError)."""
     _check("nfft_ewald", q, pos, batch, splitting)
+    pos = _fractional("nfft_ewald", pos, splitting, fractional)
     phi, E = NfftEwaldFunction.apply(q, pos, batch, splitting, int(cutoff), bool(field))
     return (phi, E) if field else phi
 
 
-def nfft_ewald_energy(q, pos, batch=None, /, splitting=None, cutoff=4):
+def nfft_ewald_energy(q, pos, batch=None, /, splitting=None, cutoff=4, fractional=False):
     """``U_b = 1/2 sum_{i in point set b} q_i phi_i`` with ``phi = nfft_ewald(q, pos, batch, ...)``: ``[B, *cols]``, one
     energy per point set and column (bilinear in ``q``: no conjugate for complex charges).  Its gradient in ``pos`` is
-    minus the force, ``dU/dpos_i = -q_i E_i`` summed over the columns."""
+    minus the force, ``dU/dpos_i = -q_i E_i`` summed over the columns (Cartesian ``pos`` in a box; ``fractional`` as for
+    ``nfft_ewald``)."""
     _check("nfft_ewald_energy", q, pos, batch, splitting)
-    phi = nfft_ewald(q, pos, batch, splitting=splitting, cutoff=cutoff)
+    if splitting.box is None and fractional:
+        raise ValueError("nfft_ewald_energy: fractional=True needs an EwaldSplitting with a box")
+    phi = nfft_ewald(q, pos, batch, splitting=splitting, cutoff=cutoff, fractional=fractional)
     return 0.5 * _set_sums(q * phi, batch)[0]

@@ -184,6 +184,16 @@ def nfft_ewald_near(pos, x, batch, alpha, r_cut, with_field):
     return _ops._nfft_ewald_near(pos, x, batch, float(alpha), float(r_cut), bool(with_field))
 
 
+def nfft_ewald_near_box(pos, x, batch, box, alpha, r_cut, with_field):
+    """torch_nfft::_nfft_ewald_near_box(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut,
+    bool with_field) -> (Tensor, Tensor) (not in the reference): ``nfft_ewald_near`` in the box whose lower-triangular
+    matrix ``A`` (rows = lattice vectors) is ``box = (A00, A10, A11, A20, A21, A22)``.  ``pos`` ``[n, 3]`` holds FRACTIONAL
+    coordinates, taken modulo 1; ``r_ij`` is the length of ``d_ij = (ds - rint(ds)) A``, ``ds = pos_i - pos_j``, so ``alpha``,
+    ``r_cut`` (at most a third of the box's smallest perpendicular width), ``z`` and the Cartesian ``f`` are in the box's
+    own units.  One native call (``nfft_hip_ewald_near_box``)."""
+    return _ops._nfft_ewald_near_box(pos, x, batch, [float(a) for a in box], float(alpha), float(r_cut), bool(with_field))
+
+
 class _on_device:
     """The coefficient operators create their output on the current device (like the reference, which has no
     device argument); ``device=`` selects it for the duration of the call."""
