@@ -173,7 +173,9 @@ for name, (N, m, sizes, cols, kind) in sorted(cases.items()):
         per_pencil = np.bincount(entries[:items[-1], 0], minlength=int(info[4]) * int(info[5]))
         items.append([int(per_pencil.min()), int(per_pencil.max()), int(info[1])])
     ops.check_status()
-    out[name] = {"errors": errs, "items": items}
+    # the gathers of the two forward transforms (2 cols and cols real planes per point set) by api.hip plan_route
+    gathers = [_lib.route(prob, 2 * cols).gather, _lib.route(prob, cols).gather]
+    out[name] = {"errors": errs, "items": items, "gathers": gathers}
 print("RESULT " + json.dumps(out))
 '''
 
@@ -197,6 +199,13 @@ def test_results_and_lists(case_dir, variant):
         print(variant, name, "adjoint %.2e forward %.2e forward(real) %.2e" % tuple(res[name]["errors"]), "items", res[name]["items"])
     for name in sorted(res):
         assert max(res[name]["errors"]) < T1W, (name, res[name])
+    # which gather ran: from four real planes per point set up the wave-per-column kernel whatever the switches say, below that
+    # the streamed one where NFFT_HIP_STREAM_MIN forces it, else the plane ring -- so with two columns (n64_m2_pair,
+    # n64_m4_two_sets) only the real-output transform reaches the streamed gather, and n64_m4_six_cols never does
+    few = "stream" if "NFFT_HIP_STREAM_MIN" in VARIANTS[variant] else "ring"
+    for name in sorted(res):
+        cols = CASES[name][3]
+        assert res[name]["gathers"] == ["cols" if 2 * cols >= 4 else few, "cols" if cols >= 4 else few], (name, res[name]["gathers"])
     # the equal cut: four items for every pencil; the graded cut (NFFT_HIP_GRADE=2): light edge pencils get fewer items,
     # not smaller ones
     lo, hi, _ = res["n64_m4_uniform"]["items"][1]

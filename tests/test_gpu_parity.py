@@ -35,6 +35,13 @@ def dev(a):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
+def route_of(d, n, C, B, N, m, Cr):
+    """The route of a problem of n points in B sets with C columns whose calls have Cr real planes per point set: csrc/api.hip
+    plan_route through the test entry nfft_dbg_route, so that a test can assert that it reaches the kernels it names."""
+    from torch_nfft_amd import _lib
+    return _lib.route(_lib.Problem(d, n, C, B, N, m), Cr)
+
+
 def host(t):
     return t.detach().cpu().numpy()
 
@@ -216,11 +223,12 @@ def test_edge_points_periodic_wrap(tn):
     assert rel_l2(host(yf), ndft.ndft_forward(host(ya), pos, None)) < T2[4]
 
 
-@pytest.mark.parametrize("N,m", [(32, 4), (32, 2), (40, 7), (64, 5)])
+@pytest.mark.parametrize("N,m", [(40, 4), (40, 2), (40, 7), (64, 5)])
 def test_edge_cases_wide_tiling(tn, N, m):
     """The same edge cases on grids that take the matrix-core kernels (3-D, 2N >= 64, m <= 7): torus boundary, exact
     grid nodes, out-of-range points, a single point, empty point sets between populated ones, every point in one cell,
-    several columns, complex coefficients."""
+    several columns, complex coefficients.  (N = 40 is the smallest such grid for a few hundred points: the 64^3 grid of
+    N = 32 takes the narrow tiling below 30 000 points, api.hip prefer_narrow.)"""
     rng = np.random.default_rng(900 + N + m)
     edge = np.array([[-0.5, -0.5, -0.5], [0.49999997, 0.49999997, 0.49999997], [0.0, 0.0, 0.0],
                      [-0.5, 0.25, 0.125], [0.25, -0.5, 0.49999997], [0.46875, -0.46875, 0.0],
@@ -235,6 +243,8 @@ def test_edge_cases_wide_tiling(tn, N, m):
     batch[n // 2:] = 3
     batch[-1] = 4
     x = (rng.standard_normal((n, 2)) + 1j * rng.standard_normal((n, 2))).astype(np.complex64)
+    for r in (route_of(3, n, 2, 5, N, m, 4), route_of(3, 1, 1, 1, N, m, 1)):
+        assert r.wide and r.spread == "mfma" and r.gather in ("cols", "ring"), r
     ya = tn.nfft_adjoint(dev(x), dev(pos), dev(batch), bandwidth=N, cutoff=m)
     assert ya.shape == (5, N, N, N, 2)
     assert float(ya[1].abs().max()) == 0.0 and float(ya[2].abs().max()) == 0.0
@@ -247,17 +257,21 @@ def test_edge_cases_wide_tiling(tn, N, m):
 
 
 def test_many_small_point_sets_wide_tiling(tn):
-    """1 500 point sets of a few points each on a 64^3 grid: more first-level sort bins than fit the LDS histogram, so
+    """1 500 point sets of a few points each on an 80^3 grid (the 64^3 grid of N = 32 takes the narrow tiling at m = 3 and
+    for so few points, api.hip prefer_narrow): more first-level sort bins than fit the LDS histogram, so
     the plan takes the one-level (global-atomic) binning path -- its work list is built from the one-level bins -- under the matrix-core
     kernels; checked on a sample of the point sets against the oracle."""
     rng = np.random.default_rng(123)
-    B, N, m = 1500, 32, 3
+    B, N, m = 1500, 40, 3
     counts = rng.integers(0, 9, size=B)
     counts[-1] = 3  # batch_size comes from the last index
     batch = np.repeat(np.arange(B), counts).astype(np.int64)
     n = batch.shape[0]
     pos = (rng.random((n, 3)) - 0.5).astype(np.float32)
     x = rng.standard_normal(n).astype(np.float32)
+    for Cr in (1, 2):  # (the adjoint of real x, the forward transform to complex y)
+        r = route_of(3, n, 1, B, N, m, Cr)
+        assert r.wide and r.spread == "mfma" and r.gather == "ring", r
     y = tn.nfft_adjoint(dev(x), dev(pos), dev(batch), bandwidth=N, cutoff=m)
     assert y.shape == (B, N, N, N)
     xh = (rng.standard_normal((B, N, N, N)) + 1j * rng.standard_normal((B, N, N, N))).astype(np.complex64)
@@ -834,9 +848,11 @@ def test_forward_many_columns_wave_per_column(tn, monkeypatch, C, complex_out, c
     """From 4 real planes per point set the forward gather runs one wave per column (interp_cols.hip): column counts
     that do not fill the last group of 8, chunks of planes that start in the middle of a group and of a point set,
     a pencil holding far more than one group of 384 points (several plane sweeps), empty point sets, points on the
-    torus boundary -- forward transform against the float64 algorithm restatement, per column."""
+    torus boundary -- forward transform against the float64 algorithm restatement, per column.  The case of 3 real planes
+    stays below the limit and takes the plane-ring kernel.  (N = 40: the wave-per-column kernel needs the wide tiling,
+    which the 64^3 grid of N = 32 does not get for 9 003 points, api.hip prefer_narrow.)"""
     rng = np.random.default_rng(600 + C + m)
-    N, B = 32, 4
+    N, B = 40, 4
     n_dense, n_rest = 6000, 3000
     dense = (0.02 * rng.standard_normal((n_dense, 3)) + np.array([0.11, -0.23, 0.37])).astype(np.float32)
     edge = np.array([[-0.5, -0.5, -0.5], [0.49999997, 0.49999997, 0.49999997], [0.0, 0.0, 0.0]], np.float32)
@@ -850,7 +866,11 @@ def test_forward_many_columns_wave_per_column(tn, monkeypatch, C, complex_out, c
     if complex_out:
         xh = (xh + 1j * rng.standard_normal(shape)).astype(np.complex64)
     if chunk_planes is not None:
-        monkeypatch.setenv("NFFT_HIP_CHUNK_BYTES", str(chunk_planes * (64 ** 3 * 4 + 64 * 64 * 33 * 8) + 8))
+        # (a plane of the chunk: the real grid + the half spectrum; M = 80 has no column passes and so no scratch of theirs)
+        monkeypatch.setenv("NFFT_HIP_CHUNK_BYTES", str(chunk_planes * (80 ** 3 * 4 + 80 * 80 * 41 * 8) + 8))
+    Cr = C * (2 if complex_out else 1)
+    r = route_of(3, n, C, B, N, m, Cr)
+    assert r.wide and r.gather == ("cols" if Cr >= 4 else "ring"), r
     y = host(tn.nfft_forward(dev(xh), dev(pos), dev(batch), cutoff=m, real_output=not complex_out))
     ref = nfft_ref.nfft_forward(xh, pos, batch, m=m, real_output=not complex_out)
     assert y.shape == (n, C)
@@ -868,15 +888,20 @@ def test_streamed_gather_and_column_groups_on_small_problems(env_extra, columns)
     slabs, windows of 4 ... 16 taps), grids whose last pencil is partial, points on pencil and group boundaries, a dense
     cluster (cut pieces), empty regions, two point sets: adjoint and forward vs the float64 oracle.  The third case has
     three coefficient columns, which permute the coefficients in a pass of their own (one or two are read inside the
-    spreading kernel)."""
+    spreading kernel).  NFFT_HIP_SMALL_NARROW=0 keeps the 64^3 grids (N = 32) on the wide tiling.  The forward transform
+    of all columns has 4 or 6 real planes per point set and runs one wave per column (on the column-group plan); the
+    forward transform of the first column alone has 2 and takes the streamed gather.  The child asserts all of this
+    through nfft_dbg_route."""
     import subprocess
     import sys
     code = r'''
 import numpy as np, torch, sys
 sys.path.insert(0, %r)
 import torch_nfft_amd as tn
+from torch_nfft_amd import _lib
 from oracle import nfft_ref
 worst = 0.0
+streamed = %r
 for case, (N, m, n, nsets) in enumerate([(32, 1, 3000, 1), (32, 2, 3000, 1), (64, 3, 5000, 1), (64, 4, 6000, 2), (32, 5, 3000, 1),
                                          (64, 6, 4000, 1), (32, 7, 2500, 1), (80, 4, 5000, 1)]):
     rng = np.random.default_rng(100 + case)
@@ -896,19 +921,27 @@ for case, (N, m, n, nsets) in enumerate([(32, 1, 3000, 1), (32, 2, 3000, 1), (64
     if nsets == 2:
         batch = (np.arange(n) >= n // 3).astype(np.int64)
         bt = torch.from_numpy(batch).cuda()
-    x = rng.standard_normal((n, %d)).astype(np.float32)
+    columns = %d
+    x = rng.standard_normal((n, columns)).astype(np.float32)
     xt, pt = torch.from_numpy(x).cuda(), torch.from_numpy(pos).cuda()
+    ra, rf, r1 = (_lib.route(_lib.Problem(3, n, C, nsets, N, m), Cr) for C, Cr in ((columns, columns), (columns, 2 * columns), (1, 2)))
+    assert ra.wide and ra.spread == "mfma" and ra.x_through_plan == (columns <= 2) and ra.column_groups == streamed[1], ra
+    assert rf.wide and rf.gather == "cols" and rf.column_groups == streamed[1], rf
+    assert r1.wide and r1.gather == streamed[0] and r1.column_groups == streamed[1], r1
     y = tn.nfft_adjoint(xt, pt, bt, bandwidth=N, cutoff=m)
     ref = nfft_ref.nfft_adjoint(x, pos, batch, N=N, m=m)
     e1 = np.linalg.norm(y.cpu().numpy() - ref) / np.linalg.norm(ref)
     f = tn.nfft_forward(y, pt, bt, cutoff=m)
     reff = nfft_ref.nfft_forward(y.cpu().numpy(), pos, batch, m=m)
     e2 = np.linalg.norm(f.cpu().numpy() - reff) / np.linalg.norm(reff)
-    print("CASE", N, m, n, nsets, e1, e2)
-    worst = max(worst, e1, e2)
+    f1 = tn.nfft_forward(y[..., :1].contiguous(), pt, bt, cutoff=m)
+    e3 = np.linalg.norm(f1.cpu().numpy() - reff[:, :1]) / np.linalg.norm(reff[:, :1])
+    print("CASE", N, m, n, nsets, e1, e2, e3)
+    worst = max(worst, e1, e2, e3)
 print("RESULT", worst)
-''' % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), columns)
-    env = dict(os.environ, **env_extra)
+''' % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+       ("stream", 3 if env_extra.get("NFFT_HIP_COLGROUPS") != "0" else 1) if "NFFT_HIP_STREAM_MIN" in env_extra else ("ring", 1), columns)
+    env = dict(os.environ, NFFT_HIP_SMALL_NARROW="0", **env_extra)
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:] + out.stdout[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("RESULT")][0].split()

@@ -5,6 +5,7 @@ tests) and the torch operator registry ``core.so`` built on top of it (``csrc/co
 
 The product path has no CPU fallback: if a library is missing or lacks a symbol the import fails loudly.
 """
+import collections
 import ctypes
 import os
 
@@ -269,6 +270,13 @@ def load():
     if hasattr(lib, "nfft_dbg_wave_reduce"):
         lib.nfft_dbg_wave_reduce.argtypes = [ci, i64, vp, vp, vp]
         lib.nfft_dbg_wave_reduce.restype = ci
+    # test entries of csrc/api.hip (not part of the C ABI either)
+    if hasattr(lib, "nfft_dbg_route"):
+        lib.nfft_dbg_route.argtypes = [P, i64, vp]
+        lib.nfft_dbg_route.restype = ci
+    if hasattr(lib, "nfft_dbg_work_list"):
+        lib.nfft_dbg_work_list.argtypes = [P, vp, ci, vp, vp, vp, i64, vp]
+        lib.nfft_dbg_work_list.restype = ci
     if lib.nfft_hip_abi_version() != ABI_VERSION:
         raise ImportError("torch_nfft_amd: ABI version mismatch in %s" % LIB_PATH)
     _lib = lib
@@ -324,6 +332,23 @@ def wave_reduce(kind, values):
                                        ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(out.data_ptr()),
                                        ctypes.c_void_p(stream)))
     return out
+
+
+SPREAD_MODES = ("lds", "mfma", "reg")               # csrc/common.h SpreadMode
+GATHER_KERNELS = ("cols", "stream", "ring", "lanes")  # csrc/api.hip GatherKernel
+Route = collections.namedtuple("Route", "wide owned pair spread x_through_plan gather column_groups small_grid")
+
+
+def route(problem, real_columns):
+    """Test entry ``nfft_dbg_route``: the route csrc/api.hip plan_route gives ``problem`` (a Problem) for calls with
+    ``real_columns`` real planes per point set -- the tiling (wide, owned, pair: booleans), the spreading kernel
+    ("lds" / "mfma" / "reg"), whether it reads x through the plan, the gather ("cols": wave per column, "stream", "ring",
+    "lanes": lane per point), the column groups of the plan (1 or 3), and whether a call WITHOUT a plan would take the
+    one-kernel small-grid path instead of all this.  Host code only; the process's NFFT_HIP_* switches apply."""
+    out = (ctypes.c_int32 * 8)()
+    check(load().nfft_dbg_route(ctypes.byref(problem), real_columns, out))
+    return Route(bool(out[0]), bool(out[1]), bool(out[2]), SPREAD_MODES[out[3]], bool(out[4]), GATHER_KERNELS[out[5]],
+                 int(out[6]), bool(out[7]))
 
 
 def check_status(stream=None, synchronize=True):

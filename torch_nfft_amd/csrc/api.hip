@@ -719,6 +719,26 @@ int nfft_dbg_work_list(const nfft_hip_problem *p, const void *plan, int which, i
     return 0;
 }
 
+// Test entry (tests/test_route.py, tests/test_gpu_value_widths.py; not part of the C ABI either): the route plan_route gives
+// a problem whose calls have `real_columns` real planes per point set.  out[8] = {g.wide, owned, spread_geom().pair, spread
+// (SpreadMode), x_through_plan, gather (GatherKernel), g.CG, 1 if a call without a plan takes the one-kernel path of
+// small_grid_route}.  Host code only: no launch, no device memory.
+int nfft_dbg_route(const nfft_hip_problem *p, int64_t real_columns, int32_t *out)
+{
+    if (int rc = validate(p)) return rc;
+    if (!out || real_columns < 0) { set_error("Input mismatch: no route"); return NFFT_HIP_EINVAL; }
+    const Route r = plan_route(p, real_columns);
+    out[0] = r.g.wide;
+    out[1] = r.owned ? 1 : 0;
+    out[2] = r.spread_geom().pair;
+    out[3] = (int32_t)r.spread;
+    out[4] = r.x_through_plan ? 1 : 0;
+    out[5] = (int32_t)r.gather;
+    out[6] = r.g.CG;
+    out[7] = small_grid_route(p) ? 1 : 0;
+    return 0;
+}
+
 int64_t nfft_hip_spread_scratch_bytes(const nfft_hip_problem *p, int64_t real_columns)
 {
     if (validate(p) || real_columns < 0) return -1;

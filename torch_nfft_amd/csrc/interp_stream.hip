@@ -539,19 +539,26 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
             const int ks0 = NG == 3 ? grp : 0;  // first k-step of the block's group
 
             // B fragments: psi2 of my point on the padded columns 16 (ks0 + ks) + 8 h + jj (zero outside the window).
-            // d = f2 + m - l2 with l2 = column - o2: one subtraction from a per-lane base per value; the scale 2^11 of
-            // the operand rides in the exponent; padding lanes get a base far outside every window.
+            // d = f2 + k with the integer k = m - l2, l2 = column - o2: k is the exact difference of a per-lane base and the
+            // column, and the exponent sc d^2 + 11 is evaluated as k (sc k + 2 sc f2) + (sc f2^2 + 11) -- the same three
+            // packed instructions per pair of taps as forming d = (f2 + base) - column and squaring it, which rounded the
+            // fraction to the ulp of the base (up to 60 columns into the tile: 2^-18 from column 32 on), an error of up to
+            // 2e-5 in the taps of the points at the far end of a pencil and 2.3e-6 in their outputs at m = 1
+            // (profiles/r14_value_widths.md).  The scale 2^11 of the operand rides in the exponent; padding lanes get a
+            // base far outside every window.
             u32x4 bh[NKS], bl[NKS];
             const int o2h = c2 - tb2 - 8 * h - 16 * ks0;  // padded column of tap 0, minus this lane's column offset
-            const float dbase2 = valid ? f2 + (float)(m + o2h) : 1.0e4f;
+            const float kbase2 = valid ? (float)(m + o2h) : 1.0e4f;
+            const float lin2 = 2.0f * sc * f2, con2 = fmaf(sc * f2, f2, 11.0f);
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks) {
                 // (packed fp32 math: two values per VALU instruction for the three arithmetic steps)
                 float w[8];
 #pragma unroll
                 for (int jj = 0; jj < 8; jj += 2) {
-                    const f32x2 d = f32x2{dbase2, dbase2} - f32x2{(float)(16 * ks + jj), (float)(16 * ks + jj + 1)};
-                    const f32x2 arg = __builtin_elementwise_fma(d * d, f32x2{sc, sc}, f32x2{11.0f, 11.0f});
+                    const f32x2 k = f32x2{kbase2, kbase2} - f32x2{(float)(16 * ks + jj), (float)(16 * ks + jj + 1)};
+                    const f32x2 arg = __builtin_elementwise_fma(k, __builtin_elementwise_fma(k, f32x2{sc, sc}, f32x2{lin2, lin2}),
+                                                                f32x2{con2, con2});
                     const float e0 = __builtin_amdgcn_exp2f(arg.x), e1 = __builtin_amdgcn_exp2f(arg.y);  // exp2(sc d^2) * kOpScale
                     w[jj] = (unsigned)(16 * ks + jj - o2h) < (unsigned)W ? e0 : 0.0f;
                     w[jj + 1] = (unsigned)(16 * ks + jj + 1 - o2h) < (unsigned)W ? e1 : 0.0f;
@@ -568,12 +575,14 @@ interp_stream_kernel(const Geom g, const int *__restrict__ tile_offsets, const i
             // kept as pairs (registers 2 p, 2 p + 1) for the packed FMAs of the reduction
             f32x2 w1[8];
             const int o1h = c1 - tb1 - 4 * h;
-            const float dbase1 = f1 + (float)(m + o1h);
+            const float kbase1 = (float)(m + o1h);  // (the integer part first, as above)
+            const float lin1 = 2.0f * sc * f1, con1 = sc * f1 * f1;
 #pragma unroll
             for (int p = 0; p < 8; ++p) {
                 const int rq0 = ((2 * p) & 3) + 8 * ((2 * p) >> 2), rq1 = rq0 + 1;
-                const f32x2 d = f32x2{dbase1, dbase1} - f32x2{(float)rq0, (float)rq1};
-                const f32x2 arg = d * d * f32x2{sc, sc};
+                const f32x2 k = f32x2{kbase1, kbase1} - f32x2{(float)rq0, (float)rq1};
+                const f32x2 arg = __builtin_elementwise_fma(k, __builtin_elementwise_fma(k, f32x2{sc, sc}, f32x2{lin1, lin1}),
+                                                            f32x2{con1, con1});
                 const float e0 = __builtin_amdgcn_exp2f(arg.x), e1 = __builtin_amdgcn_exp2f(arg.y);
                 w1[p].x = (unsigned)(rq0 - o1h) < (unsigned)W ? e0 : 0.0f;
                 w1[p].y = (unsigned)(rq1 - o1h) < (unsigned)W ? e1 : 0.0f;
