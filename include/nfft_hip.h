@@ -448,6 +448,40 @@ int nfft_hip_ewald_near_box(const nfft_hip_ewald_box_problem *p, const float *po
                             const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
                             int64_t workspace_bytes, void *stream);
 
+/* ---- virial tensor of the Ewald sum (no reference counterpart) ----
+ * For the homogeneous strain A -> A (1 + eps) at fixed fractional coordinates the virial W_ab = -dU / d eps_ab of the
+ * energy U = 1/2 sum_i q_i phi_i is a pair sum, a sum over the frequencies and a background term.  These two entry points
+ * give the first two, each with its share of the energy in front: seven numbers per point set and column, in the order
+ *     energy, xx, yy, zz, yz, xz, xy,
+ * in float64 [batch_size, 7, columns].  The background term -pi Q^2 / (2 alpha^2 V) delta_ab and the self term are the
+ * caller's.  Real data only: the energy is bilinear, and for complex charges it is not |S_k|^2 that enters.
+ *
+ * nfft_hip_ewald_virial_near: points, xr and start as for nfft_hip_ewald_near_box (fractional, reduced to [-1/2, 1/2)^3,
+ * ordered by cell; with_field is not used and must be 0 or 1),
+ *     out[b, 0, c] = 1/2 sum_{i in set b} xr[i, c] sum_{j: 0 < r_ij < r_cut} erfc(alpha r_ij) / r_ij  xr[j, c]
+ *     out[b, e, c] = 1/2 sum_i xr[i, c] sum_j (-g(r_ij^2)) d_ij[a] d_ij[b] xr[j, c]
+ * with g and d_ij as above.  The unit cube is the box 1, 0, 1, 0, 0, 1.  num_columns < 2^21 and batch_size * num_columns
+ * < 2^31 are required.  With no points the output is set to zero; with no
+ * columns nothing is done.
+ *
+ * nfft_hip_ewald_virial_far: band [batch_size, N, N, N, num_columns] complex64 (the adjoint transform of the charges,
+ * index k + N/2), coeffs [N, N, N] float32 (b_k; cells with b_k = 0 are skipped), box_inverse[6] = the lower triangle
+ * I00, I10, I11, I20, I21, I22 of A^-1 (kappa = A^-1 k), pi2_over_alpha2 = pi^2 / alpha^2,
+ *     out[b, 0, c] = 1/2 sum_k b_k |band_k|^2
+ *     out[b, e, c] = 1/2 sum_k b_k |band_k|^2 (delta_ab - 2 (1 / |kappa|^2 + pi^2 / alpha^2) kappa_a kappa_b).
+ * band needs the 8-byte alignment of complex64 only; when it is 16-byte aligned, cells of two or four columns are read
+ * with 16-byte loads.  N even, 2 <= N <= 2048; 1 <= batch_size < 2^14 and batch_size * num_columns < 2^21.
+ *
+ * Both reduce in two levels (one partial per work item or workgroup in the workspace, then one workgroup per point set and
+ * column), in float64 and without atomics: two calls give the same bits. */
+int64_t nfft_hip_ewald_virial_near_workspace_bytes(const nfft_hip_ewald_box_problem *p);
+int nfft_hip_ewald_virial_near(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                               const int32_t *start, double *out, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t nfft_hip_ewald_virial_far_workspace_bytes(int64_t N, int64_t batch_size, int64_t num_columns);
+int nfft_hip_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
+                              const double *box_inverse, double pi2_over_alpha2, double *out, void *workspace,
+                              int64_t workspace_bytes, void *stream);
+
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.
  *   gaussian_analytic_coeffs      float32:  prod_d sqrt(pi) sigma exp(-sigma^2 pi^2 l_d^2)      (kernel_coeffs.cu:6-30)

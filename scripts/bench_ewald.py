@@ -23,6 +23,14 @@ positions), n (4/3) pi r_c^3 = neighbours V, EwaldSplitting.from_tolerance(tol, 
 the near operator ops.nfft_ewald_near_box and its pair loop on its own (nfft_hip_ewald_near_box on restated plumbing), with
 the pairs tested and picoseconds per tested pair.  On the identity box (--box 1,1,1) the unit-cube pair loop runs on the same
 points as well: the same cells and pairs, three products and three FMAs fewer per tested pair.  No 1/r yardstick here.
+
+    python scripts/bench_ewald.py --virial [--box ...] [...]
+
+adds, after each of the rows above and in the same process, a row for the virial tensor in the same
+box (the identity box without --box) on the same charges: nfft_ewald_virial beside nfft_ewald(field=True); the pair loop of
+the virial kernel (nfft_hip_ewald_virial_near on restated plumbing, its second-level sum included) beside the field loop,
+in picoseconds per tested pair; and the far reduction (ops.nfft_ewald_virial_far) beside the torch composition
+((band.abs() ** 2)[..., None] * coef7).sum(...) on the same band, with the bytes of band per second that each reaches.
 """
 import argparse
 import ctypes
@@ -165,6 +173,78 @@ def run_box(lib, n, args):
     print(json.dumps(out))
 
 
+def run_virial(lib, n, args):
+    m = 4
+    box = [1.0, 0.0, 1.0, 0.0, 0.0, 1.0] if args.box is None else \
+        (args.box if len(args.box) == 6 else [args.box[0], 0.0, args.box[1], 0.0, 0.0, args.box[2]])
+    A = [[box[0], 0.0, 0.0], [box[1], box[2], 0.0], [box[3], box[4], box[5]]]
+    probe = tn.EwaldSplitting(1.0, 1e-3 * min(box[0], box[2], box[5]), 2, box=A, device="cpu")  # (volume and widths)
+    r_c = min((3.0 * args.neighbours * probe.volume / (4.0 * math.pi * n)) ** (1.0 / 3.0), min(probe.widths) / 3.0)
+    sp = tn.EwaldSplitting.from_tolerance(args.tol, r_c, box=A)
+    rng = np.random.default_rng(0)
+    v = (rng.random((n, 3)) - 0.5).astype(np.float32)
+    v[v >= 0.5] = -0.5  # (rounded up to the face: the same point)
+    pos = torch.from_numpy(v).cuda()
+    q = torch.from_numpy(rng.standard_normal(n).astype(np.float32)).cuda()
+    G, N = sp.cells, sp.bandwidth
+    tested = box_pairs_tested(v, G)
+    field = median_ms(lambda: tn.nfft_ewald(q, pos, splitting=sp, cutoff=m, field=True, fractional=True), args.reps)
+    virial = median_ms(lambda: tn.nfft_ewald_virial(q, pos, splitting=sp, cutoff=m, fractional=True), args.reps)
+    adjoint = median_ms(lambda: tn.nfft_adjoint(q, pos, bandwidth=N, cutoff=m), args.reps)
+    near_op = median_ms(lambda: tn.ops.nfft_ewald_virial_near(pos, q, None, box, sp.alpha, r_c), args.reps)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    spos, order, start = box_cell_order(pos, G)
+    xs = q.index_select(0, order).reshape(n, 1).contiguous()
+    z, f = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+    p = _lib.EwaldBoxProblem(cells=(ctypes.c_int32 * 3)(*G), with_field=1, num_points=n, num_columns=1, batch_size=1,
+                             alpha=sp.alpha, r_cut=r_c, box=(ctypes.c_double * 6)(*box))
+    nbytes = lib.nfft_hip_ewald_near_box_workspace_bytes(ctypes.byref(p))
+    vbytes = lib.nfft_hip_ewald_virial_near_workspace_bytes(ctypes.byref(p))
+    assert nbytes > 0 and vbytes > 0, _lib.last_error()
+    ws, vws = torch.empty(nbytes, dtype=torch.uint8, device="cuda"), torch.empty(vbytes, dtype=torch.uint8, device="cuda")
+    seven = torch.zeros(1, 7, 1, dtype=torch.float64, device="cuda")
+
+    def field_loop():
+        _lib.check(lib.nfft_hip_ewald_near_box(ctypes.byref(p), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                               order.data_ptr(), z.data_ptr(), f.data_ptr(), ws.data_ptr(), nbytes, stream))
+
+    def virial_loop():
+        _lib.check(lib.nfft_hip_ewald_virial_near(ctypes.byref(p), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                                  seven.data_ptr(), vws.data_ptr(), vbytes, stream))
+
+    loop_f, loop_v = median_ms(field_loop, args.reps), median_ms(virial_loop, args.reps)
+    assert torch.equal(tn.ops.nfft_ewald_virial_near(pos, q, None, box, sp.alpha, r_c), seven[:, :, 0]), \
+        "the restated plumbing must give the operator's bits"
+    # the far reduction beside the torch composition on the same band
+    band = tn.nfft_adjoint(q, pos, bandwidth=N, cutoff=m)  # [1, N, N, N]
+    kappa = sp._kappa()
+    k2 = (kappa * kappa).sum(3)
+    fac = -2.0 * (1.0 / torch.where(k2 > 0, k2, torch.ones_like(k2)) + (math.pi / sp.alpha) ** 2)
+    coef7 = [torch.ones_like(k2)] + [1.0 + fac * kappa[..., a] * kappa[..., a] for a in range(3)] + \
+            [fac * kappa[..., a] * kappa[..., b] for a, b in ((1, 2), (0, 2), (0, 1))]
+    coef7 = (0.5 * sp._b64.unsqueeze(3) * torch.stack(coef7, 3)).to(torch.float32).cuda()  # [N, N, N, 7]
+    far_v = median_ms(lambda: tn.ops.nfft_ewald_virial_far(band, sp.coeffs, box, sp.alpha), args.reps)
+    far_t = median_ms(lambda: ((band.abs() ** 2)[..., None] * coef7).sum((1, 2, 3)), args.reps)
+    got = tn.ops.nfft_ewald_virial_far(band, sp.coeffs, box, sp.alpha)
+    want = ((band.abs() ** 2)[..., None] * coef7).sum((1, 2, 3)).double()
+    tn.ops.check_status()
+    band_bytes = band.numel() * 8
+    print(json.dumps({"bench": "ewald_virial", "box": box, "points": n, "neighbours": args.neighbours, "tol": args.tol,
+                      "r_cut": round(r_c, 5), "alpha": round(sp.alpha, 3), "N": N, "m": m, "cells": list(G),
+                      "ewald_field_ms": round(field, 4), "ewald_virial_ms": round(virial, 4),
+                      "virial_over_field": round(virial / field, 3), "adjoint_ms": round(adjoint, 4),
+                      "virial_near_ms": round(near_op, 4), "pair_loop_field_ms": round(loop_f, 4),
+                      "pair_loop_virial_ms": round(loop_v, 4), "pairs_tested": tested,
+                      "ps_per_pair_field": round(loop_f * 1e9 / tested, 3),
+                      "ps_per_pair_virial": round(loop_v * 1e9 / tested, 3),
+                      "virial_loop_over_field_loop": round(loop_v / loop_f, 3),
+                      "far_reduction_ms": round(far_v, 4), "far_torch_ms": round(far_t, 4),
+                      "torch_over_far_reduction": round(far_t / far_v, 2),
+                      "far_reduction_GBps": round(band_bytes / far_v * 1e-6, 1),
+                      "far_torch_GBps": round(band_bytes / far_t * 1e-6, 1),
+                      "far_rel_difference": float((got - want).norm() / want.norm())}))
+
+
 def run(lib, n, args):
     m = 4
     r_c = min((3.0 * args.neighbours / (4.0 * math.pi * n)) ** (1.0 / 3.0), 1.0 / 3.0)
@@ -241,6 +321,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--box", type=lambda t: [float(e) for e in t.split(",")], default=None,
                     help="a,b,c (orthorhombic) or A00,A10,A11,A20,A21,A22 (lower triangular, rows = lattice vectors)")
+    ap.add_argument("--virial", action="store_true", help="add a row for nfft_ewald_virial and its two reductions")
     args = ap.parse_args()
     if args.box is not None and len(args.box) not in (3, 6):
         ap.error("--box takes three or six comma-separated numbers")
@@ -248,6 +329,8 @@ def main():
     lib = _lib.load()
     for n in args.points:
         (run if args.box is None else run_box)(lib, n, args)
+        if args.virial:
+            run_virial(lib, n, args)
 
 
 if __name__ == "__main__":

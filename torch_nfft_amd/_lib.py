@@ -63,6 +63,10 @@ SYMBOLS = (
     "nfft_hip_ewald_box_cells",
     "nfft_hip_ewald_near_box_workspace_bytes",
     "nfft_hip_ewald_near_box",
+    "nfft_hip_ewald_virial_near_workspace_bytes",
+    "nfft_hip_ewald_virial_near",
+    "nfft_hip_ewald_virial_far_workspace_bytes",
+    "nfft_hip_ewald_virial_far",
     "nfft_hip_gaussian_analytic_coeffs",
     "nfft_hip_interpolation_grid",
     "nfft_hip_coeffs_workspace_bytes",
@@ -249,6 +253,15 @@ def load():
     lib.nfft_hip_ewald_near_box_workspace_bytes.restype = i64
     lib.nfft_hip_ewald_near_box.argtypes = [ctypes.POINTER(EwaldBoxProblem), vp, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.nfft_hip_ewald_near_box.restype = ci
+    lib.nfft_hip_ewald_virial_near_workspace_bytes.argtypes = [ctypes.POINTER(EwaldBoxProblem)]
+    lib.nfft_hip_ewald_virial_near_workspace_bytes.restype = i64
+    lib.nfft_hip_ewald_virial_near.argtypes = [ctypes.POINTER(EwaldBoxProblem), vp, vp, vp, vp, vp, i64, vp]
+    lib.nfft_hip_ewald_virial_near.restype = ci
+    lib.nfft_hip_ewald_virial_far_workspace_bytes.argtypes = [i64, i64, i64]
+    lib.nfft_hip_ewald_virial_far_workspace_bytes.restype = i64
+    lib.nfft_hip_ewald_virial_far.argtypes = [i64, i64, i64, vp, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_double, vp,
+                                              vp, i64, vp]
+    lib.nfft_hip_ewald_virial_far.restype = ci
     lib.nfft_hip_gaussian_analytic_coeffs.argtypes = [ctypes.c_double, i64, ctypes.c_int32, vp, vp]
     lib.nfft_hip_gaussian_analytic_coeffs.restype = ci
     lib.nfft_hip_interpolation_grid.argtypes = [i64, ctypes.c_int32, ci, vp, vp]

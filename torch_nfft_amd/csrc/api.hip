@@ -1839,3 +1839,94 @@ int nfft_hip_ewald_near_box(const nfft_hip_ewald_box_problem *p, const float *po
 }
 
 }  // extern "C"
+
+// ---- virial tensor of the Ewald sum -----------------------------------------------------------
+namespace {
+
+int validate_virial_far(int64_t N, int64_t batch_size, int64_t num_columns)
+{
+    if (N < 2 || N > 2048 || N % 2) { set_error("Input mismatch: N must be even with 2 <= N <= 2048"); return NFFT_HIP_EINVAL; }
+    // (the launches: 1024 workgroups per point set at most, one workgroup per point set and column)
+    if (batch_size < 1 || batch_size >= (int64_t(1) << 14) || num_columns < 0 || num_columns >= (int64_t(1) << 21) ||
+        batch_size * num_columns >= (int64_t(1) << 21)) {
+        set_error("Input mismatch: 1 <= batch_size < 2^14, num_columns >= 0 and batch_size * num_columns < 2^21 are required");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+// the box problem's own checks, and the second level's launch: one workgroup per point set and column
+int validate_virial_near(const nfft_hip_ewald_box_problem *p)
+{
+    if (int rc = validate_ewald_box(p)) return rc;
+    if (p->num_columns >= (int64_t(1) << 21) || p->batch_size * p->num_columns >= (int64_t(1) << 31)) {
+        set_error("Input mismatch: num_columns < 2^21 and batch_size * num_columns < 2^31 are required");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nfft_hip_ewald_virial_near_workspace_bytes(const nfft_hip_ewald_box_problem *p)
+{
+    if (validate_virial_near(p)) return -1;
+    return ewald_virial_near_workspace(p) + 256;
+}
+
+int nfft_hip_ewald_virial_near(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                               const int32_t *start, double *out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_virial_near(p)) return rc;
+    if (p->num_columns == 0) return 0;
+    if (!out) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
+    if (p->num_points == 0) {
+        NFFT_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(p->batch_size * 7 * p->num_columns) * sizeof(double), (hipStream_t)stream));
+        return 0;
+    }
+    if (!points || !xr || !start) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    const int64_t need = ewald_virial_near_workspace(p) + 256;
+    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    return launch_ewald_virial_near(p, points, xr, start, out, ws, (hipStream_t)stream);
+}
+
+int64_t nfft_hip_ewald_virial_far_workspace_bytes(int64_t N, int64_t batch_size, int64_t num_columns)
+{
+    if (validate_virial_far(N, batch_size, num_columns)) return -1;
+    return ewald_virial_far_workspace(N, batch_size, num_columns) + 256;
+}
+
+int nfft_hip_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
+                              const double *box_inverse, double pi2_over_alpha2, double *out, void *workspace,
+                              int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_virial_far(N, batch_size, num_columns)) return rc;
+    if (!box_inverse) { set_error("Input mismatch: box_inverse is null"); return NFFT_HIP_EINVAL; }
+    for (int e = 0; e < 6; ++e)
+        if (!(box_inverse[e] == box_inverse[e]) || box_inverse[e] > 1e300 || box_inverse[e] < -1e300) {
+            set_error("Input mismatch: the entries of box_inverse must be finite");
+            return NFFT_HIP_EINVAL;
+        }
+    if (!(box_inverse[0] > 0.0) || !(box_inverse[2] > 0.0) || !(box_inverse[5] > 0.0)) {
+        set_error("Input mismatch: the diagonal of box_inverse must be positive");
+        return NFFT_HIP_EINVAL;
+    }
+    if (!(pi2_over_alpha2 > 0.0) || !(pi2_over_alpha2 < 1e300)) {
+        set_error("Input mismatch: pi2_over_alpha2 must be positive and finite");
+        return NFFT_HIP_EINVAL;
+    }
+    if (num_columns == 0) return 0;
+    if (!band || !coeffs || !out) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    const int64_t need = ewald_virial_far_workspace(N, batch_size, num_columns) + 256;
+    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    return launch_ewald_virial_far(N, batch_size, num_columns, band, coeffs, box_inverse, pi2_over_alpha2, out, ws,
+                                   (hipStream_t)stream);
+}
+
+}  // extern "C"

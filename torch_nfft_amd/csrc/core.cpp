@@ -1125,6 +1125,91 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_near_box(at::Tensor pos, at::Tenso
     return {z.reshape(z_shape), f.reshape(f_shape)};
 }
 
+// ---- virial tensor of the Ewald sum (not in the reference) --------------------------------------
+// [B, 7, *cols] float64: per point set and column the near part of the energy and of the virial W_ab = -dU / d eps_ab
+// (xx, yy, zz, yz, xz, xy) of the real charges x at the FRACTIONAL positions pos in the box A = box, taken modulo 1 and
+// ordered by cell exactly as nfft_ewald_near_box does
+at::Tensor nfft_ewald_virial_near(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch, std::vector<double> box,
+                                  double alpha, double r_cut)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_virial_near is currently only implemented for GPU tensors");
+    const Points p = check_points(pos, opt_batch, "batch");
+    CHECK_INPUT(p.dim == 3);
+    CHECK_INPUT(box.size() == 6);
+    CHECK_INPUT(x.scalar_type() == at::kFloat);  // (the energy is bilinear: real charges only)
+    CHECK_INPUT(x.dim() >= 1);
+    CHECK_INPUT(x.size(0) == p.n);
+    CHECK_INPUT(x.device() == pos.device());
+    int64_t C = 1;
+    std::vector<int64_t> shape{p.B, 7};
+    for (int64_t d = 1; d < x.dim(); ++d) {
+        C *= x.size(d);
+        shape.push_back(x.size(d));
+    }
+    nfft_hip_ewald_box_problem q;
+    q.with_field = 0;
+    q.num_points = p.n;
+    q.num_columns = C;
+    q.batch_size = p.B;
+    q.alpha = alpha;
+    q.r_cut = r_cut;
+    for (int e = 0; e < 6; ++e) q.box[e] = box[e];
+    if (nfft_hip_ewald_box_cells(q.box, r_cut, q.batch_size, q.cells) < 0) check_rc(NFFT_HIP_EINVAL);
+    const int64_t ws_bytes = nfft_hip_ewald_virial_near_workspace_bytes(&q);
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    const at::TensorOptions opts = x.options().dtype(at::kDouble);
+    if (p.n == 0 || C == 0) return at::zeros(shape, opts);  // no launch
+    c10::DeviceGuard guard(x.device());
+    // s modulo 1 in [-1/2, 1/2), as nfft_ewald_near does: what comes out as +1/2 is the point -1/2
+    at::Tensor red = p.pos - p.pos.round();
+    red = at::where(red >= 0.5, red - 1.0, red);
+    const CellOrder o = box_cell_order(red, p.batch, p.B, q.cells);
+    const at::Tensor xr = x.contiguous().reshape({p.n, C}).index_select(0, o.order);
+    at::Tensor out = at::zeros({p.B, 7, C}, opts);
+    at::Tensor ws = byte_buffer(ws_bytes, x);
+    check_rc(nfft_hip_ewald_virial_near(&q, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
+                                        out.data_ptr<double>(), ws.data_ptr(), ws_bytes, stream_of(x)));
+    return out.reshape(shape);
+}
+
+// [B, 7, *cols] float64: the far part of the same from band [B, N, N, N, *cols] complex64 (nfft_adjoint of the charges)
+// and the splitting's coeffs [N, N, N] float32; kappa = A^-1 k is formed in the kernel from box and the index
+at::Tensor nfft_ewald_virial_far(at::Tensor band, at::Tensor coeffs, std::vector<double> box, double alpha)
+{
+    TORCH_CHECK(band.is_cuda(), "torch_nfft._nfft_ewald_virial_far is currently only implemented for GPU tensors");
+    CHECK_INPUT(band.scalar_type() == at::kComplexFloat);
+    CHECK_INPUT(coeffs.scalar_type() == at::kFloat);
+    CHECK_INPUT(coeffs.device() == band.device());
+    CHECK_INPUT(box.size() == 6);
+    CHECK_INPUT(band.dim() >= 4 && coeffs.dim() == 3);
+    const int64_t B = band.size(0), N = band.size(1);
+    for (int64_t d = 0; d < 3; ++d) CHECK_INPUT(band.size(1 + d) == N && coeffs.size(d) == N);
+    CHECK_INPUT(alpha > 0.0);
+    int64_t C = 1;
+    std::vector<int64_t> shape{B, 7};
+    for (int64_t d = 4; d < band.dim(); ++d) {
+        C *= band.size(d);
+        shape.push_back(band.size(d));
+    }
+    const at::TensorOptions opts = band.options().dtype(at::kDouble);
+    if (B == 0) return at::zeros(shape, opts);
+    const double a00 = box[0], a10 = box[1], a11 = box[2], a20 = box[3], a21 = box[4], a22 = box[5];
+    CHECK_INPUT(a00 > 0.0 && a11 > 0.0 && a22 > 0.0);
+    const double i00 = 1.0 / a00, i11 = 1.0 / a11, i22 = 1.0 / a22;
+    const double inv[6] = {i00, -a10 * i00 * i11, i11, (a10 * a21 - a11 * a20) * i00 * i11 * i22, -a21 * i11 * i22, i22};
+    const int64_t ws_bytes = nfft_hip_ewald_virial_far_workspace_bytes(N, B, C);
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    if (C == 0) return at::zeros(shape, opts);  // no launch
+    c10::DeviceGuard guard(band.device());
+    const at::Tensor bc = band.contiguous(), cc = coeffs.contiguous();
+    at::Tensor out = at::zeros({B, 7, C}, opts);
+    at::Tensor ws = byte_buffer(ws_bytes, band);
+    const double pi = 3.14159265358979323846;
+    check_rc(nfft_hip_ewald_virial_far(N, B, C, bc.data_ptr(), cc.data_ptr<float>(), inv, pi * pi / (alpha * alpha),
+                                       out.data_ptr<double>(), ws.data_ptr(), ws_bytes, stream_of(band)));
+    return out.reshape(shape);
+}
+
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
 at::TensorOptions current_device_options(at::ScalarType dtype)
 {
@@ -1252,4 +1337,8 @@ TORCH_LIBRARY(torch_nfft, m)
     // not in the reference: the same pair sum in an orthorhombic or triclinic box, on fractional positions
     m.def("_nfft_ewald_near_box(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut, bool with_field) "
           "-> (Tensor, Tensor)", &nfft_ewald_near_box);
+    // not in the reference: the pair and the spectral reduction of the Ewald sum's virial tensor (nfft_ewald_virial)
+    m.def("_nfft_ewald_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut) -> Tensor",
+          &nfft_ewald_virial_near);
+    m.def("_nfft_ewald_virial_far(Tensor band, Tensor coeffs, float[] box, float alpha) -> Tensor", &nfft_ewald_virial_far);
 }

@@ -1,0 +1,437 @@
+// Virial tensor of the Ewald sum for the periodic 1/r: the two reductions that the potential and
+// field kernels do not do.  For the homogeneous strain A -> A (1 + eps) at fixed fractional coordinates,
+// W_ab = -dU / d eps_ab is the sum of a pair part, a spectral part and the background term (added by the host side):
+//
+//     near[b, 0, c]  = 1/2 sum_{i in set b} x_ic sum_{j: 0 < r_ij < r_c} erfc(alpha r_ij) / r_ij  x_jc          (energy)
+//     near[b, e, c]  = 1/2 sum_i x_ic sum_j (-g(r_ij^2)) d_ij,a d_ij,b x_jc,   e = 1 .. 6: ab = xx, yy, zz, yz, xz, xy
+//     far[b, 0, c]   = 1/2 sum_k b_k |band_k|^2                                                                  (energy)
+//     far[b, e, c]   = 1/2 sum_k b_k |band_k|^2 (delta_ab - 2 (1 / |kappa|^2 + pi^2 / alpha^2) kappa_a kappa_b)
+//
+// with g = K'(r) / r for K = erfc(alpha r) / r, d_ij = (ds - rint(ds)) A and kappa = A^-1 k, as in ewald_near_box.hip.
+//
+// ewald_virial_near_kernel  the frame of ewald_near_box_kernel<CC, true> -- the same items, lanes, LDS tiles, 27-cell walk,
+//                           wrap and branch -- with seven sums per column in place of four and no store per point: at the
+//                           end a lane multiplies its sums by x_i / 2 of its own target (exactly zero for a lane without
+//                           one), in float64 from there on, and the workgroup adds its lanes: a butterfly inside each
+//                           wave, then the waves in order.  One partial [7, Cr] float64 per item slot.
+// ewald_virial_far_kernel   one thread per grid cell, the columns innermost as stored: kappa from the index, the seven
+//                           weights in float64 once per cell, |band|^2 per column, float64 sums per thread, the same
+//                           workgroup sum.  One partial [7, C] per workgroup.  Cells with b_k = 0 (k = 0, the zeroed
+//                           planes k_a = -N/2) are skipped.
+// virial_sum_kernel         second level of both: one workgroup per (point set, column) adds that set's partials, each
+//                           thread a fixed stride of them in order, then the workgroup sum.
+//
+// No atomics anywhere and every order of addition is fixed by the launch geometry: two calls give the same bits.
+#include "nearfield.h"
+
+namespace nfft {
+
+namespace {
+
+constexpr int kVirialTerms = 7;    // energy, xx, yy, zz, yz, xz, xy
+constexpr int kVirialBlock = 256;  // lanes of the far kernel and of the second level
+constexpr int kVirialFarBlocks = 1024;  // workgroups per point set of the far kernel, at most
+
+// v summed over the 64 lanes of a wave, the same bits in every lane (a + b and b + a are the same number); every lane
+// of the wave must be here
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+struct VirialNearParams {
+    int G0, G1, G2;
+    int64_t Cr;
+    float alpha, neg_alpha2, rc2, slope;  // alpha, -alpha^2, r_c^2, 2 alpha / sqrt(pi)
+    float a00, a10, a11, a20, a21, a22;   // the lower triangle of A
+};
+
+template <int CC>
+__global__ void __launch_bounds__(kNearBlock) ewald_virial_near_kernel(VirialNearParams q, const int2 *__restrict__ items,
+                                                                       const float *__restrict__ pos,
+                                                                       const float *__restrict__ xr,
+                                                                       const int *__restrict__ start,
+                                                                       double *__restrict__ partial)
+{
+    __shared__ float4 s_pos[kNearTile];
+    __shared__ __attribute__((aligned(16))) float s_x[kNearTile * CC];
+    __shared__ double s_red[kNearBlock / 64][kVirialTerms * CC];
+    const int2 item = items[blockIdx.x];
+    if (item.x < 0) return;  // (uniform: an empty slot; the second level skips it)
+    const int tid = threadIdx.x;
+    const int k = item.x;
+    const int tend = min(item.y + kNearBlock, start[k + 1]);
+    const int ti = item.y + tid;
+    const bool active = ti < tend;
+    const bool wave_active = item.y + (tid & ~63) < tend;
+    const int G0 = q.G0, G1 = q.G1, G2 = q.G2;
+    const int c0 = k % G0, c1 = (k / G0) % G1, c2 = (k / (G0 * G1)) % G2;
+    const int set0 = k - (c2 * G1 + c1) * G0 - c0;  // first cell of the point set
+    // (a lane without a target sums pairs of the origin; its sums are replaced by zero before the reduction)
+    float tx = 0.f, ty = 0.f, tz = 0.f;
+    if (active) {
+        const float *tp = pos + (int64_t)ti * 3;
+        tx = tp[0];
+        ty = tp[1];
+        tz = tp[2];
+    }
+    // the cells c0 - 1 .. c0 + 1 of a row as ranges of cells [lo, hi): one inside the row, two at its ends
+    const bool split = c0 == 0 || c0 == G0 - 1;
+    const int lo0 = c0 == 0 ? G0 - 1 : (c0 == G0 - 1 ? 0 : c0 - 1);
+    const int hi0 = c0 == 0 ? G0 : (c0 == G0 - 1 ? 1 : c0 + 2);
+    const int lo1 = c0 == 0 ? 0 : G0 - 2;
+    const int hi1 = c0 == 0 ? 2 : G0;
+    for (int64_t col0 = 0; col0 < q.Cr; col0 += CC) {
+        float acc[kVirialTerms][CC];
+#pragma unroll
+        for (int e = 0; e < kVirialTerms; ++e)
+#pragma unroll
+            for (int c = 0; c < CC; ++c) acc[e][c] = 0.f;
+        for (int d2 = -1; d2 <= 1; ++d2) {
+            const int w2 = c2 + d2 < 0 ? G2 - 1 : (c2 + d2 >= G2 ? 0 : c2 + d2);
+            for (int d1 = -1; d1 <= 1; ++d1) {
+                const int w1 = c1 + d1 < 0 ? G1 - 1 : (c1 + d1 >= G1 ? 0 : c1 + d1);
+                const int row = set0 + (w2 * G1 + w1) * G0;
+                for (int part = 0; part < (split ? 2 : 1); ++part) {
+                    const int first = start[row + (part ? lo1 : lo0)];
+                    const int last = start[row + (part ? hi1 : hi0)];
+                    for (int t0 = first; t0 < last; t0 += kNearTile) {
+                        const int cnt = min(kNearTile, last - t0);
+                        __syncthreads();
+                        for (int j = tid; j < cnt; j += kNearBlock) {
+                            const float *sp = pos + (int64_t)(t0 + j) * 3;
+                            s_pos[j] = make_float4(sp[0], sp[1], sp[2], 0.f);
+                            const float *xp = xr + (int64_t)(t0 + j) * q.Cr + col0;
+#pragma unroll
+                            for (int c = 0; c < CC; ++c) s_x[j * CC + c] = col0 + c < q.Cr ? xp[c] : 0.f;
+                        }
+                        __syncthreads();
+                        if (!wave_active) continue;
+#pragma unroll 2
+                        for (int j = 0; j < cnt; ++j) {
+                            const float4 s = s_pos[j];
+                            float s0 = tx - s.x, s1 = ty - s.y, s2 = tz - s.z;
+                            s0 -= rintf(s0);
+                            s1 -= rintf(s1);
+                            s2 -= rintf(s2);
+                            // d = ds A, A lower triangular with rows = lattice vectors
+                            const float dx = fmaf(s2, q.a20, fmaf(s1, q.a10, s0 * q.a00));
+                            const float dy = fmaf(s2, q.a21, s1 * q.a11);
+                            const float dz = s2 * q.a22;
+                            const float rr = dx * dx + dy * dy + dz * dz;
+                            // the lanes that fail the test sit the expansion out
+                            if (!(rr > 0.f && rr < q.rc2)) continue;
+                            const float ir = rsqrtf(rr);
+                            const float w = erfcf(q.alpha * (rr * ir)) * ir;  // erfc(alpha r) / r
+                            // -g = (erfc(alpha r) / r + (2 alpha / sqrt(pi)) e^(-alpha^2 r^2)) / r^2
+                            const float mg = (w + q.slope * __expf(q.neg_alpha2 * rr)) * (ir * ir);
+                            const float gx = mg * dx, gy = mg * dy, gz = mg * dz;
+                            const float pxx = gx * dx, pyy = gy * dy, pzz = gz * dz;
+                            const float pyz = gy * dz, pxz = gx * dz, pxy = gx * dy;
+#pragma unroll
+                            for (int c = 0; c < CC; ++c) {
+                                const float v = s_x[j * CC + c];
+                                acc[0][c] += w * v;
+                                acc[1][c] += pxx * v;
+                                acc[2][c] += pyy * v;
+                                acc[3][c] += pzz * v;
+                                acc[4][c] += pyz * v;
+                                acc[5][c] += pxz * v;
+                                acc[6][c] += pxy * v;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        // x_i / 2 of the lane's own target, float64 from here on; a lane without a target adds exactly zero
+        double red[kVirialTerms][CC];
+#pragma unroll
+        for (int c = 0; c < CC; ++c) {
+            const bool live = active && col0 + c < q.Cr;
+            const double h = live ? 0.5 * (double)xr[(int64_t)ti * q.Cr + col0 + c] : 0.0;
+#pragma unroll
+            for (int e = 0; e < kVirialTerms; ++e) red[e][c] = live ? h * (double)acc[e][c] : 0.0;
+        }
+        __syncthreads();  // (s_red of the pass before has been read)
+#pragma unroll
+        for (int e = 0; e < kVirialTerms; ++e)
+#pragma unroll
+            for (int c = 0; c < CC; ++c) {
+                const double v = wave_sum_f64(red[e][c]);
+                if ((tid & 63) == 0) s_red[tid >> 6][e * CC + c] = v;
+            }
+        __syncthreads();
+        if (tid < kVirialTerms * CC) {
+            const int e = tid / CC, c = tid % CC;
+            if (col0 + c < q.Cr) {
+                double v = s_red[0][tid];
+#pragma unroll
+                for (int w = 1; w < kNearBlock / 64; ++w) v += s_red[w][tid];
+                partial[((int64_t)blockIdx.x * kVirialTerms + e) * q.Cr + col0 + c] = v;
+            }
+        }
+    }
+}
+
+struct VirialFarParams {
+    int N, blocks;  // frequencies per axis; workgroups per point set
+    int wide;       // band is 16-byte aligned: a cell of two or four columns is read with 16-byte loads
+    int64_t C;
+    double i00, i10, i11, i20, i21, i22;  // the lower triangle of A^-1
+    double p2a2;                          // pi^2 / alpha^2
+};
+
+template <int CC>
+__global__ void __launch_bounds__(kVirialBlock) ewald_virial_far_kernel(VirialFarParams q, const float2 *__restrict__ band,
+                                                                        const float *__restrict__ coeffs,
+                                                                        double *__restrict__ partial)
+{
+    __shared__ double s_red[kVirialBlock / 64][kVirialTerms * CC];
+    const int tid = threadIdx.x;
+    const int N = q.N, half = q.N / 2;
+    const int64_t cells = (int64_t)N * N * N;
+    const int set = blockIdx.x / q.blocks, blk = blockIdx.x % q.blocks;  // (point set, workgroup within it)
+    const float2 *bb = band + (int64_t)set * cells * q.C;
+    for (int64_t col0 = 0; col0 < q.C; col0 += CC) {
+        double acc[kVirialTerms][CC];
+#pragma unroll
+        for (int e = 0; e < kVirialTerms; ++e)
+#pragma unroll
+            for (int c = 0; c < CC; ++c) acc[e][c] = 0.0;
+        // the cells blk * 256 + tid, + stride, + 2 stride, ...: their index (i0, i1, i2) is kept beside them and advanced
+        // by the stride's own digits with carries, so that no division runs per cell
+        const int stride = q.blocks * kVirialBlock;
+        const unsigned first = (unsigned)blk * kVirialBlock + tid;
+        int i2 = (int)(first % (unsigned)N), i1 = (int)((first / (unsigned)N) % (unsigned)N), i0 = (int)(first / ((unsigned)N * N));
+        const int s2 = stride % N, s1 = (stride / N) % N, s0 = stride / (N * N);
+        for (int64_t cell = first; cell < cells; cell += stride) {
+            const float bk = coeffs[cell];
+            const int k0 = i0 - half, k1 = i1 - half, k2 = i2 - half;
+            i2 += s2;
+            if (i2 >= N) {
+                i2 -= N;
+                ++i1;
+            }
+            i1 += s1;
+            if (i1 >= N) {
+                i1 -= N;
+                ++i0;
+            }
+            i0 += s0;
+            if (bk == 0.f) continue;  // k = 0 and the zeroed planes k_a = -N/2
+            // kappa = A^-1 k, A^-1 lower triangular
+            const double kx = q.i00 * k0;
+            const double ky = q.i10 * k0 + q.i11 * k1;
+            const double kz = q.i20 * k0 + q.i21 * k1 + q.i22 * k2;
+            const double kk = kx * kx + ky * ky + kz * kz;
+            const double b = (double)bk;
+            const double t = -2.0 * (1.0 / kk + q.p2a2) * b;
+            double wgt[kVirialTerms];
+            wgt[0] = b;
+            wgt[1] = b + t * kx * kx;
+            wgt[2] = b + t * ky * ky;
+            wgt[3] = b + t * kz * kz;
+            wgt[4] = t * ky * kz;
+            wgt[5] = t * kx * kz;
+            wgt[6] = t * kx * ky;
+            float2 v[CC];
+            const float2 *bp = bb + cell * q.C + col0;
+            bool loaded = false;
+            if constexpr (CC == 2) {
+                if (q.C == 2 && q.wide) {  // (16 bytes per cell, aligned: one load)
+                    const float4 u = *reinterpret_cast<const float4 *>(bp);
+                    v[0] = make_float2(u.x, u.y);
+                    v[1] = make_float2(u.z, u.w);
+                    loaded = true;
+                }
+            }
+            if constexpr (CC == 4) {
+                if (q.C == 4 && q.wide) {  // (32 bytes per cell, aligned: two loads)
+                    const float4 u0 = reinterpret_cast<const float4 *>(bp)[0], u1 = reinterpret_cast<const float4 *>(bp)[1];
+                    v[0] = make_float2(u0.x, u0.y);
+                    v[1] = make_float2(u0.z, u0.w);
+                    v[2] = make_float2(u1.x, u1.y);
+                    v[3] = make_float2(u1.z, u1.w);
+                    loaded = true;
+                }
+            }
+            if (!loaded) {
+#pragma unroll
+                for (int c = 0; c < CC; ++c) v[c] = col0 + c < q.C ? bp[c] : make_float2(0.f, 0.f);
+            }
+#pragma unroll
+            for (int c = 0; c < CC; ++c) {
+                const double p = (double)v[c].x * (double)v[c].x + (double)v[c].y * (double)v[c].y;
+#pragma unroll
+                for (int e = 0; e < kVirialTerms; ++e) acc[e][c] += wgt[e] * p;
+            }
+        }
+        __syncthreads();  // (s_red of the pass before has been read)
+#pragma unroll
+        for (int e = 0; e < kVirialTerms; ++e)
+#pragma unroll
+            for (int c = 0; c < CC; ++c) {
+                const double v = wave_sum_f64(acc[e][c]);
+                if ((tid & 63) == 0) s_red[tid >> 6][e * CC + c] = v;
+            }
+        __syncthreads();
+        if (tid < kVirialTerms * CC) {
+            const int e = tid / CC, c = tid % CC;
+            if (col0 + c < q.C) {
+                double v = s_red[0][tid];
+#pragma unroll
+                for (int w = 1; w < kVirialBlock / 64; ++w) v += s_red[w][tid];
+                partial[((int64_t)blockIdx.x * kVirialTerms + e) * q.C + col0 + c] = 0.5 * v;
+            }
+        }
+    }
+}
+
+// out[b, e, c] = sum of partial[row, e, c] over the rows of point set b, column c (one workgroup each,
+// blockIdx.x = b C + c).
+// items == nullptr: the rows are b * rows_per_set ... (b + 1) * rows_per_set.  Otherwise the rows are the item slots of the
+// set's cells: slot = first point / kNearBlock + cell + piece grows with the cell, so they are the slots from that of the
+// set's first cell up to that of the next set's first cell.  The last slot of a cell lies before the first slot of the next
+// cell, so that range holds items of set b (item.x / cells_per_set == b) and empty slots (item.x < 0, skipped), no others.
+__global__ void __launch_bounds__(kVirialBlock) virial_sum_kernel(const double *__restrict__ partial, int64_t C,
+                                                                  int rows_per_set, const int2 *__restrict__ items,
+                                                                  const int *__restrict__ start, int cells_per_set,
+                                                                  double *__restrict__ out)
+{
+    __shared__ double s_red[kVirialBlock / 64];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x / C, c = blockIdx.x % C;
+    int64_t lo, hi;
+    if (items) {
+        const int64_t k0 = b * cells_per_set, k1 = (b + 1) * cells_per_set;
+        lo = start[k0] / kNearBlock + k0;
+        hi = start[k1] / kNearBlock + k1;
+    } else {
+        lo = b * rows_per_set;
+        hi = lo + rows_per_set;
+    }
+    for (int e = 0; e < kVirialTerms; ++e) {
+        double v = 0.0;
+        for (int64_t row = lo + tid; row < hi; row += kVirialBlock) {
+            if (items) {
+                const int cell = items[row].x;
+                if (cell < 0) continue;
+            }
+            v += partial[(row * kVirialTerms + e) * C + c];
+        }
+        v = wave_sum_f64(v);
+        __syncthreads();  // (s_red of the term before has been read)
+        if ((tid & 63) == 0) s_red[tid >> 6] = v;
+        __syncthreads();
+        if (tid == 0) {
+            double r = s_red[0];
+#pragma unroll
+            for (int w = 1; w < kVirialBlock / 64; ++w) r += s_red[w];
+            out[(b * kVirialTerms + e) * C + c] = r;
+        }
+    }
+}
+
+int64_t virial_cells(const nfft_hip_ewald_box_problem *p)
+{
+    return p->batch_size * p->cells[0] * p->cells[1] * p->cells[2];
+}
+
+int virial_far_blocks(int64_t N)
+{
+    const int64_t cells = N * N * N;
+    return (int)std::min<int64_t>((cells + kVirialBlock - 1) / kVirialBlock, kVirialFarBlocks);
+}
+
+int64_t round256(int64_t bytes) { return (bytes + 255) & ~int64_t(255); }
+
+}  // namespace
+
+int64_t ewald_virial_near_item_slots(const nfft_hip_ewald_box_problem *p)
+{
+    return nearfield_item_slots(virial_cells(p), p->num_points);
+}
+
+int64_t ewald_virial_near_workspace(const nfft_hip_ewald_box_problem *p)
+{
+    const int64_t slots = ewald_virial_near_item_slots(p);
+    return round256(slots * (int64_t)sizeof(int2)) + slots * kVirialTerms * p->num_columns * (int64_t)sizeof(double);
+}
+
+int launch_ewald_virial_near(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xr, const int *start,
+                             double *out, void *workspace, hipStream_t stream)
+{
+    VirialNearParams q;
+    q.G0 = p->cells[0];
+    q.G1 = p->cells[1];
+    q.G2 = p->cells[2];
+    q.Cr = p->num_columns;
+    q.alpha = (float)p->alpha;
+    q.neg_alpha2 = (float)(-p->alpha * p->alpha);
+    q.rc2 = (float)(p->r_cut * p->r_cut);
+    q.slope = (float)(2.0 * p->alpha / 1.7724538509055160273);
+    q.a00 = (float)p->box[0];
+    q.a10 = (float)p->box[1];
+    q.a11 = (float)p->box[2];
+    q.a20 = (float)p->box[3];
+    q.a21 = (float)p->box[4];
+    q.a22 = (float)p->box[5];
+    const int64_t slots = ewald_virial_near_item_slots(p);
+    int2 *items = (int2 *)workspace;
+    double *partial = (double *)((char *)workspace + round256(slots * (int64_t)sizeof(int2)));
+    if (int rc = launch_nearfield_items(virial_cells(p), p->num_points, start, items, stream)) return rc;
+    const dim3 grid((unsigned)slots), block(kNearBlock);
+#define EWALD_VIRIAL_LAUNCH(CC) \
+    hipLaunchKernelGGL((ewald_virial_near_kernel<CC>), grid, block, 0, stream, q, (const int2 *)items, pos, xr, start, partial)
+    if (q.Cr == 1) EWALD_VIRIAL_LAUNCH(1);
+    else if (q.Cr == 2) EWALD_VIRIAL_LAUNCH(2);
+    else EWALD_VIRIAL_LAUNCH(4);
+#undef EWALD_VIRIAL_LAUNCH
+    NFFT_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(virial_sum_kernel, dim3((unsigned)(p->batch_size * q.Cr)), dim3(kVirialBlock), 0, stream,
+                       (const double *)partial, q.Cr, 0, (const int2 *)items, start,
+                       (int)(p->cells[0] * p->cells[1] * p->cells[2]), out);
+    NFFT_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int64_t ewald_virial_far_workspace(int64_t N, int64_t batch_size, int64_t num_columns)
+{
+    return batch_size * virial_far_blocks(N) * kVirialTerms * num_columns * (int64_t)sizeof(double);
+}
+
+int launch_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
+                            const double *box_inverse, double pi2_over_alpha2, double *out, void *workspace,
+                            hipStream_t stream)
+{
+    VirialFarParams q;
+    q.N = (int)N;
+    q.blocks = virial_far_blocks(N);
+    q.C = num_columns;
+    q.wide = ((uintptr_t)band & 15) == 0 ? 1 : 0;  // (otherwise 8-byte loads, which complex64 data always allows)
+    q.i00 = box_inverse[0];
+    q.i10 = box_inverse[1];
+    q.i11 = box_inverse[2];
+    q.i20 = box_inverse[3];
+    q.i21 = box_inverse[4];
+    q.i22 = box_inverse[5];
+    q.p2a2 = pi2_over_alpha2;
+    double *partial = (double *)workspace;
+    const dim3 grid((unsigned)(q.blocks * batch_size)), block(kVirialBlock);
+#define EWALD_VIRIAL_FAR_LAUNCH(CC) \
+    hipLaunchKernelGGL((ewald_virial_far_kernel<CC>), grid, block, 0, stream, q, (const float2 *)band, coeffs, partial)
+    if (q.C == 1) EWALD_VIRIAL_FAR_LAUNCH(1);
+    else if (q.C == 2) EWALD_VIRIAL_FAR_LAUNCH(2);
+    else EWALD_VIRIAL_FAR_LAUNCH(4);
+#undef EWALD_VIRIAL_FAR_LAUNCH
+    NFFT_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(virial_sum_kernel, dim3((unsigned)(batch_size * q.C)), dim3(kVirialBlock), 0, stream,
+                       (const double *)partial, q.C, q.blocks, (const int2 *)nullptr, (const int *)nullptr, 0, out);
+    NFFT_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace nfft

@@ -182,6 +182,17 @@ int launch_ewald_near(const nfft_hip_ewald_problem *p, const float *pos, const f
 int64_t ewald_near_box_item_slots(const nfft_hip_ewald_box_problem *p);
 int launch_ewald_near_box(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xr, const int *start,
                           const int64_t *index, float *z, float *f, void *items, hipStream_t stream);
+// ewald_virial.hip (the virial tensor of the Ewald sum): the pair reduction, arguments as
+// nfft_hip_ewald_virial_near, `workspace`: ewald_virial_near_workspace(p) bytes, 256-byte aligned (the work items, then one
+// partial per item slot); and the spectral reduction, arguments as nfft_hip_ewald_virial_far, `workspace`:
+// ewald_virial_far_workspace(...) bytes, 8-byte aligned
+int64_t ewald_virial_near_workspace(const nfft_hip_ewald_box_problem *p);
+int launch_ewald_virial_near(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xr, const int *start,
+                             double *out, void *workspace, hipStream_t stream);
+int64_t ewald_virial_far_workspace(int64_t N, int64_t batch_size, int64_t num_columns);
+int launch_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
+                            const double *box_inverse, double pi2_over_alpha2, double *out, void *workspace,
+                            hipStream_t stream);
 
 // smallgrid.hip: transforms whose oversampled grid (<= 4096 cells) fits one workgroup's LDS -- one kernel per direction,
 // no point plan

@@ -25,6 +25,16 @@ wave vector of the integer frequency ``k`` is ``kappa = A^-1 k``, ``V = det A``,
 
 ``alpha``, ``r_c``, ``phi`` and ``E`` are in the box's own Cartesian units.  The transforms run on the fractional
 coordinates with anisotropic coefficients; the pair sweep is ``ops.nfft_ewald_near_box``.
+
+The virial tensor: for the homogeneous strain ``A -> A (1 + eps)`` at fixed fractional coordinates,
+``W_ab = -dU / d eps_ab`` of the energy ``U = 1/2 sum_i q_i phi_i`` is::
+
+    W_ab =   1/2 sum_i q_i sum_{j: 0 < r_ij < r_c} (-g(r_ij^2)) d_ij,a d_ij,b q_j                       g = K'(r) / r, K = erfc(alpha r) / r
+           + 1/2 sum_{k != 0} b_k |S_k|^2 (delta_ab - 2 (1 / |kappa|^2 + pi^2 / alpha^2) kappa_a kappa_b)  S_k = sum_j q_j e^{-2 pi i k.s_j}
+           - pi Q^2 / (2 alpha^2 V) delta_ab
+
+``W`` is symmetric, ``tr W = U`` for the converged sum, ``W / V`` is the Coulomb part of the pressure tensor and
+``dU/dA = -A^-T W`` at fixed ``s`` (``nfft_ewald_virial``, ``virial_to_box_gradient``).
 """
 import ctypes
 import math
@@ -295,13 +305,15 @@ class NfftEwaldFunction(torch.autograd.Function):
         return dq if need_q else None, dpos, None, None, None, None
 
 
-def _check(what, q, pos, batch, splitting):
+def _check(what, q, pos, batch, splitting, differentiable=True):
     if not isinstance(splitting, EwaldSplitting):
         raise TypeError("%s: splitting must be an EwaldSplitting" % what)
     if pos.dim() != 2 or pos.size(1) != 3:
         raise ValueError("%s: the periodic 1/r sum is three-dimensional, pos must be [n, 3]" % what)
     if batch is not None and batch.requires_grad:
-        raise AssertionError("%s is differentiable w.r.t. q and pos only, but batch requires grad" % what)
+        if differentiable:
+            raise AssertionError("%s is differentiable w.r.t. q and pos only, but batch requires grad" % what)
+        raise AssertionError("%s: batch holds point-set indices and must not require grad" % what)
 
 
 def _fractional(what, pos, splitting, fractional):
@@ -351,3 +363,64 @@ def nfft_ewald_energy(q, pos, batch=None, /, splitting=None, cutoff=4, fractiona
         raise ValueError("nfft_ewald_energy: fractional=True needs an EwaldSplitting with a box")
     phi = nfft_ewald(q, pos, batch, splitting=splitting, cutoff=cutoff, fractional=fractional)
     return 0.5 * _set_sums(q * phi, batch)[0]
+
+
+_IDENTITY6 = (1.0, 0.0, 1.0, 0.0, 0.0, 1.0)
+_VOIGT = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))  # the order of the two native reductions after the energy
+
+
+def nfft_ewald_virial(q, pos, batch=None, /, splitting=None, cutoff=4, fractional=False):
+    """``(U, W)``: the energy ``U_b = 1/2 sum_{i in point set b} q_i phi_i`` ``[B, *cols]`` of ``nfft_ewald_energy`` and
+    the virial tensor ``W_ab = -dU / d eps_ab`` ``[B, 3, 3, *cols]`` for the homogeneous strain ``A -> A (1 + eps)`` of the
+    box at fixed fractional coordinates, per point set and column, both with the dtype of ``q``.  ``W`` is symmetric and
+    in the box's units (energy); ``tr W = U`` up to the truncation of the sum; ``W / splitting.volume`` is the Coulomb part
+    of the pressure tensor, and ``virial_to_box_gradient(W, splitting.box)`` the gradient of ``U`` in the box's entries.
+
+    ``q`` ``[n, *cols]`` must be real (float32): the energy is bilinear and for complex charges the far part is not
+    ``|S_k|^2`` (ValueError).  ``pos``, ``batch``, ``splitting``, ``cutoff`` and ``fractional`` are those of ``nfft_ewald``;
+    without a box the cell is the unit cube.
+
+    One adjoint transform, then two native reductions -- over the frequencies of its output and over the pairs within
+    ``r_cut`` -- in float64 and without atomics (they give the same bits on every call; the transform before them spreads
+    with float atomics, so the whole does not); the self term ``-(alpha / sqrt(pi))
+    sum q_i^2`` (in ``U`` only: it has no strain in it) and the background ``-pi Q^2 / (2 alpha^2 V)`` (in ``U`` and on the
+    diagonal of ``W``) are added in float64 before the cast.
+
+    Runs under ``torch.no_grad()``: ``U`` and ``W`` are constants to autograd.  Inputs that require grad are accepted and
+    get no gradient from here (use ``nfft_ewald_energy`` for forces); ``batch`` must not require grad (AssertionError)."""
+    _check("nfft_ewald_virial", q, pos, batch, splitting, differentiable=False)
+    if q.is_complex():
+        raise ValueError("nfft_ewald_virial: the charges must be real (the energy is bilinear in q)")
+    with torch.no_grad():
+        q, pos = q.detach(), pos.detach()
+        pos = _fractional("nfft_ewald_virial", pos, splitting, fractional)
+        alpha, N = splitting.alpha, splitting.bandwidth
+        box6 = _IDENTITY6 if splitting.box is None else splitting.box6
+        band = nfft_adjoint(q, pos, batch, bandwidth=N, cutoff=int(cutoff))  # [B, N, N, N, *cols]
+        seven = ops.nfft_ewald_virial_far(band, splitting.coeffs, box6, alpha)
+        seven = seven + ops.nfft_ewald_virial_near(pos, q, batch, box6, alpha, splitting.r_cut)  # [B, 7, *cols] float64
+        q64 = q.double()
+        total = _set_sums(q64, batch)[0]
+        background = (math.pi / (2.0 * alpha * alpha * splitting.volume)) * total * total
+        U = seven[:, 0] - (alpha / math.sqrt(math.pi)) * _set_sums(q64 * q64, batch)[0] - background
+        W = seven.new_zeros((seven.size(0), 3, 3) + tuple(seven.shape[2:]))
+        for e, (a, b) in enumerate(_VOIGT):
+            W[:, a, b] = seven[:, 1 + e]
+            W[:, b, a] = seven[:, 1 + e]
+        for a in range(3):
+            W[:, a, a] -= background
+        return U.to(q.dtype), W.to(q.dtype)
+
+
+def virial_to_box_gradient(W, box):
+    """``dU/dA`` at fixed fractional coordinates from the virial ``W`` ``[B, 3, 3, *cols]`` of ``nfft_ewald_virial``:
+    ``tril(-A^-T W)`` ``[B, 3, 3, *cols]``, the six free entries of the lower-triangular box ``A`` (zeros above the
+    diagonal).  ``box`` as ``EwaldSplitting`` takes it (three edges or ``[3, 3]`` lower triangular); ``None`` is the unit
+    cube.  Pure torch, on the device and in the dtype of ``W``."""
+    if W.dim() < 3 or W.size(1) != 3 or W.size(2) != 3:
+        raise ValueError("virial_to_box_gradient: W must be [B, 3, 3, *cols]")
+    inv = torch.eye(3, dtype=torch.float64) if box is None else _box_inverse(_box_matrix(box))
+    inv = inv.to(device=W.device, dtype=W.dtype)
+    g = -torch.einsum("ki,bkj...->bij...", inv, W)  # -(A^-T W)_ij = -sum_k (A^-1)_ki W_kj
+    mask = torch.tril(torch.ones(3, 3, dtype=W.dtype, device=W.device))
+    return g * mask.reshape((1, 3, 3) + (1,) * (W.dim() - 3))

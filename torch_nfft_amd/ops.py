@@ -194,6 +194,32 @@ def nfft_ewald_near_box(pos, x, batch, box, alpha, r_cut, with_field):
     return _ops._nfft_ewald_near_box(pos, x, batch, [float(a) for a in box], float(alpha), float(r_cut), bool(with_field))
 
 
+def nfft_ewald_virial_near(pos, x, batch, box, alpha, r_cut):
+    """torch_nfft::_nfft_ewald_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut) ->
+    Tensor (not in the reference): the pair part of the Ewald energy and of the virial tensor ``W_ab = -dU / d eps_ab``,
+    ``[B, 7, *cols]`` float64 in the order energy, xx, yy, zz, yz, xz, xy::
+
+        out[b, 0] = 1/2 sum_{i in set b} x_i sum_{j: 0 < r_ij < r_cut} erfc(alpha r_ij) / r_ij  x_j
+        out[b, e] = 1/2 sum_i x_i sum_j (-g(r_ij^2)) d_ij[a] d_ij[b] x_j
+
+    ``pos`` fractional (any real values, taken modulo 1), ``x`` ``[n, *cols]`` float32 (real charges only), ``box`` the six
+    numbers of ``nfft_ewald_near_box`` (the unit cube: ``1, 0, 1, 0, 0, 1``).  One native call
+    (``nfft_hip_ewald_virial_near``), no atomics: two calls give the same bits."""
+    return _ops._nfft_ewald_virial_near(pos, x, batch, [float(a) for a in box], float(alpha), float(r_cut))
+
+
+def nfft_ewald_virial_far(band, coeffs, box, alpha):
+    """torch_nfft::_nfft_ewald_virial_far(Tensor band, Tensor coeffs, float[] box, float alpha) -> Tensor (not in the
+    reference): the spectral part of the same, ``[B, 7, *cols]`` float64, from ``band`` ``[B, N, N, N, *cols]`` complex64
+    (``nfft_adjoint`` of the charges) and the splitting's ``coeffs`` ``[N, N, N]`` float32::
+
+        out[b, 0] = 1/2 sum_k b_k |band_k|^2
+        out[b, e] = 1/2 sum_k b_k |band_k|^2 (delta_ab - 2 (1 / |kappa|^2 + pi^2 / alpha^2) kappa_a kappa_b),  kappa = A^-1 k
+
+    One native call (``nfft_hip_ewald_virial_far``), one pass over ``band``, no atomics."""
+    return _ops._nfft_ewald_virial_far(band, coeffs, [float(a) for a in box], float(alpha))
+
+
 class _on_device:
     """The coefficient operators create their output on the current device (like the reference, which has no
     device argument); ``device=`` selects it for the duration of the call."""
