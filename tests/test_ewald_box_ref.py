@@ -328,33 +328,14 @@ def test_c_abi_validation_without_gpu():
 
 
 def test_pair_kernel_resource_usage():
-    """every instantiation <CC, FIELD> of the box pair kernel: no scratch and no spills (the library's own flags; VGPRs
-    are recorded in DESIGN.md section 7h, not gated)"""
-    import importlib.util
-    import os
+    """every instantiation <CC, FIELD, BOX = true> of the Ewald pair kernel: no scratch and no spills (the library's own
+    flags; VGPRs are recorded in DESIGN.md section 7h, not gated)"""
     import re
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("_nfft_hip_build", os.path.join(root, "torch_nfft_amd", "build.py"))
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
-    assert "ewald_near_box.hip" in build.SOURCES
-    cmd = [build.HIPCC] + build.FLAGS + ["--cuda-device-only", "-x", "hip", "-c",
-                                         os.path.join(build.CSRC, "ewald_near_box.hip"), "-o", os.devnull,
-                                         "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    usage, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = usage.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+    from resource_usage import resource_usage
+    usage = resource_usage("ewald_near.hip")
     by = {}
     for name, u in usage.items():
-        m = re.search(r"ewald_near_box_kernelILi(\d)ELb(\d)EE", name)
+        m = re.search(r"ewald_near_kernelILi(\d)ELb(\d)ELb1EE", name)
         if m:
             by[(int(m.group(1)), int(m.group(2)))] = u
     assert set(by) == {(cc, f) for cc in (1, 2, 4) for f in (0, 1)}

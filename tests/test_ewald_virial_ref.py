@@ -310,27 +310,9 @@ def test_c_abi_validation_without_gpu():
 def test_kernel_resource_usage():
     """every instantiation of the two reduction kernels: no scratch and no spills (the library's own flags; the VGPR and
     LDS figures are recorded in DESIGN.md section 7i, not gated)"""
-    import importlib.util
-    import os
     import re
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("_nfft_hip_build", os.path.join(root, "torch_nfft_amd", "build.py"))
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
-    assert "ewald_virial.hip" in build.SOURCES
-    cmd = [build.HIPCC] + build.FLAGS + ["--cuda-device-only", "-x", "hip", "-c", os.path.join(build.CSRC, "ewald_virial.hip"),
-                                         "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    usage, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = usage.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+    from resource_usage import resource_usage
+    usage = resource_usage("ewald_virial.hip")
     seen = set()
     for name, u in sorted(usage.items()):
         m = re.search(r"(ewald_virial_near_kernel|ewald_virial_far_kernel)ILi(\d)E|(virial_sum_kernel)", name)

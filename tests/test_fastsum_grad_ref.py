@@ -10,13 +10,13 @@ transform).  Also the C ABI and the operator schemas without a device, and the r
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import test_pos_grad_ref as ref
+from resource_usage import resource_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -113,32 +113,12 @@ def test_operator_schemas_and_cpu_rejection():
 
 # ---- resource usage of the value-writing gather ---------------------------------------------------------------------
 
-def _resource_usage(src):
-    """{kernel name: {field: value}} from hipcc -Rpass-analysis=kernel-resource-usage (the library's own flags)."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("_nfft_hip_build", os.path.join(ROOT, "torch_nfft_amd", "build.py"))
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
-    cmd = [build.HIPCC] + build.FLAGS + ["--cuda-device-only", "-x", "hip", "-c", src, "-o", os.devnull,
-                                         "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    usage, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = usage.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return usage
-
 
 def test_value_gather_resource_usage():
     """Every instantiation of the value-writing gather: no scratch, no VGPR spills, and at least the occupancy of the
     gradient-only kernel with the same <DIM, W, WIDE>.  SGPR spills (into VGPR lanes, no memory) only where the occupancy
     would drop without them: the 2-D m = 2 kernel (lane_gather.h GatherCfg::WPE_VALUE)."""
-    usage = _resource_usage(os.path.join(ROOT, "torch_nfft_amd", "csrc", "interp_grad.hip"))
+    usage = resource_usage("interp_grad.hip")
     # mangled: ...interp_grad_kernelILi<DIM>ELi<W>ELb<WIDE>ELb<VALUE>EE...
     pat = re.compile(r"interp_grad_kernelILi(\d)ELi(\d+)ELb([01])ELb([01])EE")
     by = {}

@@ -4,7 +4,6 @@ torch_nfft_amd/nearfield.py against the restatement, the refusals, the C ABI's v
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import torch
 import nearfield_gradient_ref as ng
 import nearfield_ref as nr
 from conftest import rel_l2
+from resource_usage import resource_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -182,32 +182,10 @@ def test_c_abi_validation_without_gpu():
     assert call(ok, 0, gp) == _lib.EINVAL and _lib.last_error().startswith("Input mismatch")
 
 
-def _resource_usage(src):
-    """{kernel name: {field: value}} from hipcc -Rpass-analysis=kernel-resource-usage (the library's own flags)."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("_nfft_hip_build", os.path.join(ROOT, "torch_nfft_amd", "build.py"))
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
-    assert "nearfield_grad.hip" in build.SOURCES
-    cmd = [build.HIPCC] + build.FLAGS + ["--cuda-device-only", "-x", "hip", "-c", src, "-o", os.devnull,
-                                         "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    usage, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = usage.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return usage
-
-
 def test_pair_kernel_resource_usage():
     """Every instantiation <KERNEL, CC, PT, MODE> of the gradient pair kernel: no scratch and no spills of either kind.
     (VGPRs and occupancies are recorded in DESIGN.md section 7e, not gated.)"""
-    usage = _resource_usage(os.path.join(ROOT, "torch_nfft_amd", "csrc", "nearfield_grad.hip"))
+    usage = resource_usage("nearfield_grad.hip")
     pat = re.compile(r"nearfield_grad_kernelILi(\d)ELi(\d)ELi(\d)ELi(\d)EE")
     by = {}
     for name, u in usage.items():

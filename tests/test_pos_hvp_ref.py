@@ -198,8 +198,8 @@ def test_hvp_gather_resource_usage():
     """Every instantiation of interp_hvp_kernel: no scratch, no VGPR spills, and the occupancy of interp_grad_kernel with
     the same <DIM, W, WIDE> except one wave less for the three kernels GatherCfg::WPE_HVP names.  SGPR spills (into VGPR
     lanes, no memory) only for 2-D m = 1, 2."""
-    from test_fastsum_grad_ref import _resource_usage
-    usage = _resource_usage(os.path.join(ROOT, "torch_nfft_amd", "csrc", "interp_grad.hip"))
+    from resource_usage import resource_usage
+    usage = resource_usage("interp_grad.hip")
     pg = re.compile(r"interp_grad_kernelILi(\d)ELi(\d+)ELb([01])ELb0EE")
     ph = re.compile(r"interp_hvp_kernelILi(\d)ELi(\d+)ELb([01])EE")
     grad, hvp = {}, {}
@@ -219,8 +219,8 @@ def test_hvp_gather_resource_usage():
 def test_derivative_spreading_resource_usage():
     """spread_kernel<DIM, W, DERIV = true>: no scratch, no VGPR spills and the occupancy of the plain spreading kernel of the
     same <DIM, W>.  The 3-D kernels from m = 5 on keep some SGPRs in VGPR lanes (no memory)."""
-    from test_fastsum_grad_ref import _resource_usage
-    usage = _resource_usage(os.path.join(ROOT, "torch_nfft_amd", "csrc", "spread.hip"))
+    from resource_usage import resource_usage
+    usage = resource_usage("spread.hip")
     pat = re.compile(r"spread_kernelILi(\d)ELi(\d+)ELb([01])EE")
     by = {}
     for name, u in usage.items():

@@ -7,10 +7,11 @@
 //     far[b, 0, c]   = 1/2 sum_k b_k |band_k|^2                                                                  (energy)
 //     far[b, e, c]   = 1/2 sum_k b_k |band_k|^2 (delta_ab - 2 (1 / |kappa|^2 + pi^2 / alpha^2) kappa_a kappa_b)
 //
-// with g = K'(r) / r for K = erfc(alpha r) / r, d_ij = (ds - rint(ds)) A and kappa = A^-1 k, as in ewald_near_box.hip.
+// with g = K'(r) / r for K = erfc(alpha r) / r, d_ij = (ds - rint(ds)) A and kappa = A^-1 k, as in ewald_near.hip.
 //
-// ewald_virial_near_kernel  the frame of ewald_near_box_kernel<CC, true> -- the same items, lanes, LDS tiles, 27-cell walk,
-//                           wrap and branch -- with seven sums per column in place of four and no store per point: at the
+// ewald_virial_near_kernel  on the frame of pair_frame.h like ewald_near_kernel<CC, true, true> -- the same items, lanes, LDS
+//                           tiles, 27-cell walk, image, branch and pair weights -- with seven sums per column in place of
+//                           four and no store per point: at the
 //                           end a lane multiplies its sums by x_i / 2 of its own target (exactly zero for a lane without
 //                           one), in float64 from there on, and the workgroup adds its lanes: a butterfly inside each
 //                           wave, then the waves in order.  One partial [7, Cr] float64 per item slot.
@@ -22,7 +23,7 @@
 //                           thread a fixed stride of them in order, then the workgroup sum.
 //
 // No atomics anywhere and every order of addition is fixed by the launch geometry: two calls give the same bits.
-#include "nearfield.h"
+#include "pair_frame.h"
 
 namespace nfft {
 
@@ -32,24 +33,8 @@ constexpr int kVirialTerms = 7;    // energy, xx, yy, zz, yz, xz, xy
 constexpr int kVirialBlock = 256;  // lanes of the far kernel and of the second level
 constexpr int kVirialFarBlocks = 1024;  // workgroups per point set of the far kernel, at most
 
-// v summed over the 64 lanes of a wave, the same bits in every lane (a + b and b + a are the same number); every lane
-// of the wave must be here
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-struct VirialNearParams {
-    int G0, G1, G2;
-    int64_t Cr;
-    float alpha, neg_alpha2, rc2, slope;  // alpha, -alpha^2, r_c^2, 2 alpha / sqrt(pi)
-    float a00, a10, a11, a20, a21, a22;   // the lower triangle of A
-};
-
 template <int CC>
-__global__ void __launch_bounds__(kNearBlock) ewald_virial_near_kernel(VirialNearParams q, const int2 *__restrict__ items,
+__global__ void __launch_bounds__(kNearBlock) ewald_virial_near_kernel(EwaldPairParams q, const int2 *__restrict__ items,
                                                                        const float *__restrict__ pos,
                                                                        const float *__restrict__ xr,
                                                                        const int *__restrict__ start,
@@ -60,118 +45,54 @@ __global__ void __launch_bounds__(kNearBlock) ewald_virial_near_kernel(VirialNea
     __shared__ double s_red[kNearBlock / 64][kVirialTerms * CC];
     const int2 item = items[blockIdx.x];
     if (item.x < 0) return;  // (uniform: an empty slot; the second level skips it)
-    const int tid = threadIdx.x;
-    const int k = item.x;
-    const int tend = min(item.y + kNearBlock, start[k + 1]);
-    const int ti = item.y + tid;
-    const bool active = ti < tend;
-    const bool wave_active = item.y + (tid & ~63) < tend;
-    const int G0 = q.G0, G1 = q.G1, G2 = q.G2;
-    const int c0 = k % G0, c1 = (k / G0) % G1, c2 = (k / (G0 * G1)) % G2;
-    const int set0 = k - (c2 * G1 + c1) * G0 - c0;  // first cell of the point set
+    const PairLane lane = pair_lane(item, start);
+    const WrappedWalk walk(lane.cell, q.G0, q.G1, q.G2);
     // (a lane without a target sums pairs of the origin; its sums are replaced by zero before the reduction)
-    float tx = 0.f, ty = 0.f, tz = 0.f;
-    if (active) {
-        const float *tp = pos + (int64_t)ti * 3;
-        tx = tp[0];
-        ty = tp[1];
-        tz = tp[2];
-    }
-    // the cells c0 - 1 .. c0 + 1 of a row as ranges of cells [lo, hi): one inside the row, two at its ends
-    const bool split = c0 == 0 || c0 == G0 - 1;
-    const int lo0 = c0 == 0 ? G0 - 1 : (c0 == G0 - 1 ? 0 : c0 - 1);
-    const int hi0 = c0 == 0 ? G0 : (c0 == G0 - 1 ? 1 : c0 + 2);
-    const int lo1 = c0 == 0 ? 0 : G0 - 2;
-    const int hi1 = c0 == 0 ? 2 : G0;
+    const float4 t = lane_position(lane, pos, 3, 0.f);
     for (int64_t col0 = 0; col0 < q.Cr; col0 += CC) {
         float acc[kVirialTerms][CC];
 #pragma unroll
         for (int e = 0; e < kVirialTerms; ++e)
 #pragma unroll
             for (int c = 0; c < CC; ++c) acc[e][c] = 0.f;
-        for (int d2 = -1; d2 <= 1; ++d2) {
-            const int w2 = c2 + d2 < 0 ? G2 - 1 : (c2 + d2 >= G2 ? 0 : c2 + d2);
-            for (int d1 = -1; d1 <= 1; ++d1) {
-                const int w1 = c1 + d1 < 0 ? G1 - 1 : (c1 + d1 >= G1 ? 0 : c1 + d1);
-                const int row = set0 + (w2 * G1 + w1) * G0;
-                for (int part = 0; part < (split ? 2 : 1); ++part) {
-                    const int first = start[row + (part ? lo1 : lo0)];
-                    const int last = start[row + (part ? hi1 : hi0)];
-                    for (int t0 = first; t0 < last; t0 += kNearTile) {
-                        const int cnt = min(kNearTile, last - t0);
-                        __syncthreads();
-                        for (int j = tid; j < cnt; j += kNearBlock) {
-                            const float *sp = pos + (int64_t)(t0 + j) * 3;
-                            s_pos[j] = make_float4(sp[0], sp[1], sp[2], 0.f);
-                            const float *xp = xr + (int64_t)(t0 + j) * q.Cr + col0;
+        const StageColumns<CC> stage = {s_x, xr, q.Cr, col0};
+        walk(start, [&](int first, int last) {
+            sweep_range<2>(first, last, lane, s_pos, pos, 3, stage, [&](int j) {
+                const PairSep d = ewald_image<true>(t, s_pos[j], q);
+                // the lanes that fail the test sit the expansion out
+                if (!(d.rr > 0.f && d.rr < q.rc2)) return;
+                const EwaldPairWeight e(d.rr, q);
+                const float w = e.w, mg = e.mg(q);
+                const float gx = mg * d.dx, gy = mg * d.dy, gz = mg * d.dz;
+                const float pxx = gx * d.dx, pyy = gy * d.dy, pzz = gz * d.dz;
+                const float pyz = gy * d.dz, pxz = gx * d.dz, pxy = gx * d.dy;
 #pragma unroll
-                            for (int c = 0; c < CC; ++c) s_x[j * CC + c] = col0 + c < q.Cr ? xp[c] : 0.f;
-                        }
-                        __syncthreads();
-                        if (!wave_active) continue;
-#pragma unroll 2
-                        for (int j = 0; j < cnt; ++j) {
-                            const float4 s = s_pos[j];
-                            float s0 = tx - s.x, s1 = ty - s.y, s2 = tz - s.z;
-                            s0 -= rintf(s0);
-                            s1 -= rintf(s1);
-                            s2 -= rintf(s2);
-                            // d = ds A, A lower triangular with rows = lattice vectors
-                            const float dx = fmaf(s2, q.a20, fmaf(s1, q.a10, s0 * q.a00));
-                            const float dy = fmaf(s2, q.a21, s1 * q.a11);
-                            const float dz = s2 * q.a22;
-                            const float rr = dx * dx + dy * dy + dz * dz;
-                            // the lanes that fail the test sit the expansion out
-                            if (!(rr > 0.f && rr < q.rc2)) continue;
-                            const float ir = rsqrtf(rr);
-                            const float w = erfcf(q.alpha * (rr * ir)) * ir;  // erfc(alpha r) / r
-                            // -g = (erfc(alpha r) / r + (2 alpha / sqrt(pi)) e^(-alpha^2 r^2)) / r^2
-                            const float mg = (w + q.slope * __expf(q.neg_alpha2 * rr)) * (ir * ir);
-                            const float gx = mg * dx, gy = mg * dy, gz = mg * dz;
-                            const float pxx = gx * dx, pyy = gy * dy, pzz = gz * dz;
-                            const float pyz = gy * dz, pxz = gx * dz, pxy = gx * dy;
-#pragma unroll
-                            for (int c = 0; c < CC; ++c) {
-                                const float v = s_x[j * CC + c];
-                                acc[0][c] += w * v;
-                                acc[1][c] += pxx * v;
-                                acc[2][c] += pyy * v;
-                                acc[3][c] += pzz * v;
-                                acc[4][c] += pyz * v;
-                                acc[5][c] += pxz * v;
-                                acc[6][c] += pxy * v;
-                            }
-                        }
-                    }
+                for (int c = 0; c < CC; ++c) {
+                    const float v = s_x[j * CC + c];
+                    acc[0][c] += w * v;
+                    acc[1][c] += pxx * v;
+                    acc[2][c] += pyy * v;
+                    acc[3][c] += pzz * v;
+                    acc[4][c] += pyz * v;
+                    acc[5][c] += pxz * v;
+                    acc[6][c] += pxy * v;
                 }
-            }
-        }
+            });
+        });
         // x_i / 2 of the lane's own target, float64 from here on; a lane without a target adds exactly zero
-        double red[kVirialTerms][CC];
+        double red[kVirialTerms * CC];
 #pragma unroll
         for (int c = 0; c < CC; ++c) {
-            const bool live = active && col0 + c < q.Cr;
-            const double h = live ? 0.5 * (double)xr[(int64_t)ti * q.Cr + col0 + c] : 0.0;
+            const bool live = lane.active && col0 + c < q.Cr;
+            const double h = live ? 0.5 * (double)xr[(int64_t)lane.ti * q.Cr + col0 + c] : 0.0;
 #pragma unroll
-            for (int e = 0; e < kVirialTerms; ++e) red[e][c] = live ? h * (double)acc[e][c] : 0.0;
+            for (int e = 0; e < kVirialTerms; ++e) red[e * CC + c] = live ? h * (double)acc[e][c] : 0.0;
         }
-        __syncthreads();  // (s_red of the pass before has been read)
-#pragma unroll
-        for (int e = 0; e < kVirialTerms; ++e)
-#pragma unroll
-            for (int c = 0; c < CC; ++c) {
-                const double v = wave_sum_f64(red[e][c]);
-                if ((tid & 63) == 0) s_red[tid >> 6][e * CC + c] = v;
-            }
-        __syncthreads();
+        const double v = block_sum_f64(red, s_red);
+        const int tid = threadIdx.x;
         if (tid < kVirialTerms * CC) {
             const int e = tid / CC, c = tid % CC;
-            if (col0 + c < q.Cr) {
-                double v = s_red[0][tid];
-#pragma unroll
-                for (int w = 1; w < kNearBlock / 64; ++w) v += s_red[w][tid];
-                partial[((int64_t)blockIdx.x * kVirialTerms + e) * q.Cr + col0 + c] = v;
-            }
+            if (col0 + c < q.Cr) partial[((int64_t)blockIdx.x * kVirialTerms + e) * q.Cr + col0 + c] = v;
         }
     }
 }
@@ -196,11 +117,9 @@ __global__ void __launch_bounds__(kVirialBlock) ewald_virial_far_kernel(VirialFa
     const int set = blockIdx.x / q.blocks, blk = blockIdx.x % q.blocks;  // (point set, workgroup within it)
     const float2 *bb = band + (int64_t)set * cells * q.C;
     for (int64_t col0 = 0; col0 < q.C; col0 += CC) {
-        double acc[kVirialTerms][CC];
+        double acc[kVirialTerms * CC];
 #pragma unroll
-        for (int e = 0; e < kVirialTerms; ++e)
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[e][c] = 0.0;
+        for (int n = 0; n < kVirialTerms * CC; ++n) acc[n] = 0.0;
         // the cells blk * 256 + tid, + stride, + 2 stride, ...: their index (i0, i1, i2) is kept beside them and advanced
         // by the stride's own digits with carries, so that no division runs per cell
         const int stride = q.blocks * kVirialBlock;
@@ -266,26 +185,13 @@ __global__ void __launch_bounds__(kVirialBlock) ewald_virial_far_kernel(VirialFa
             for (int c = 0; c < CC; ++c) {
                 const double p = (double)v[c].x * (double)v[c].x + (double)v[c].y * (double)v[c].y;
 #pragma unroll
-                for (int e = 0; e < kVirialTerms; ++e) acc[e][c] += wgt[e] * p;
+                for (int e = 0; e < kVirialTerms; ++e) acc[e * CC + c] += wgt[e] * p;
             }
         }
-        __syncthreads();  // (s_red of the pass before has been read)
-#pragma unroll
-        for (int e = 0; e < kVirialTerms; ++e)
-#pragma unroll
-            for (int c = 0; c < CC; ++c) {
-                const double v = wave_sum_f64(acc[e][c]);
-                if ((tid & 63) == 0) s_red[tid >> 6][e * CC + c] = v;
-            }
-        __syncthreads();
+        const double v = block_sum_f64(acc, s_red);
         if (tid < kVirialTerms * CC) {
             const int e = tid / CC, c = tid % CC;
-            if (col0 + c < q.C) {
-                double v = s_red[0][tid];
-#pragma unroll
-                for (int w = 1; w < kVirialBlock / 64; ++w) v += s_red[w][tid];
-                partial[((int64_t)blockIdx.x * kVirialTerms + e) * q.C + col0 + c] = 0.5 * v;
-            }
+            if (col0 + c < q.C) partial[((int64_t)blockIdx.x * kVirialTerms + e) * q.C + col0 + c] = 0.5 * v;
         }
     }
 }
@@ -301,7 +207,7 @@ __global__ void __launch_bounds__(kVirialBlock) virial_sum_kernel(const double *
                                                                   const int *__restrict__ start, int cells_per_set,
                                                                   double *__restrict__ out)
 {
-    __shared__ double s_red[kVirialBlock / 64];
+    __shared__ double s_red[kVirialBlock / 64][1];
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x / C, c = blockIdx.x % C;
     int64_t lo, hi;
@@ -322,16 +228,9 @@ __global__ void __launch_bounds__(kVirialBlock) virial_sum_kernel(const double *
             }
             v += partial[(row * kVirialTerms + e) * C + c];
         }
-        v = wave_sum_f64(v);
-        __syncthreads();  // (s_red of the term before has been read)
-        if ((tid & 63) == 0) s_red[tid >> 6] = v;
-        __syncthreads();
-        if (tid == 0) {
-            double r = s_red[0];
-#pragma unroll
-            for (int w = 1; w < kVirialBlock / 64; ++w) r += s_red[w];
-            out[(b * kVirialTerms + e) * C + c] = r;
-        }
+        const double sum[1] = {v};
+        const double r = block_sum_f64(sum, s_red);
+        if (tid == 0) out[(b * kVirialTerms + e) * C + c] = r;
     }
 }
 
@@ -364,32 +263,16 @@ int64_t ewald_virial_near_workspace(const nfft_hip_ewald_box_problem *p)
 int launch_ewald_virial_near(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xr, const int *start,
                              double *out, void *workspace, hipStream_t stream)
 {
-    VirialNearParams q;
-    q.G0 = p->cells[0];
-    q.G1 = p->cells[1];
-    q.G2 = p->cells[2];
-    q.Cr = p->num_columns;
-    q.alpha = (float)p->alpha;
-    q.neg_alpha2 = (float)(-p->alpha * p->alpha);
-    q.rc2 = (float)(p->r_cut * p->r_cut);
-    q.slope = (float)(2.0 * p->alpha / 1.7724538509055160273);
-    q.a00 = (float)p->box[0];
-    q.a10 = (float)p->box[1];
-    q.a11 = (float)p->box[2];
-    q.a20 = (float)p->box[3];
-    q.a21 = (float)p->box[4];
-    q.a22 = (float)p->box[5];
+    const EwaldPairParams q = ewald_pair_params(p->cells[0], p->cells[1], p->cells[2], p->num_columns, p->alpha, p->r_cut, p->box);
     const int64_t slots = ewald_virial_near_item_slots(p);
     int2 *items = (int2 *)workspace;
     double *partial = (double *)((char *)workspace + round256(slots * (int64_t)sizeof(int2)));
     if (int rc = launch_nearfield_items(virial_cells(p), p->num_points, start, items, stream)) return rc;
     const dim3 grid((unsigned)slots), block(kNearBlock);
-#define EWALD_VIRIAL_LAUNCH(CC) \
-    hipLaunchKernelGGL((ewald_virial_near_kernel<CC>), grid, block, 0, stream, q, (const int2 *)items, pos, xr, start, partial)
-    if (q.Cr == 1) EWALD_VIRIAL_LAUNCH(1);
-    else if (q.Cr == 2) EWALD_VIRIAL_LAUNCH(2);
-    else EWALD_VIRIAL_LAUNCH(4);
-#undef EWALD_VIRIAL_LAUNCH
+    dispatch_columns(q.Cr, [&](auto CC) {
+        hipLaunchKernelGGL((ewald_virial_near_kernel<CC()>), grid, block, 0, stream, q, (const int2 *)items, pos, xr, start,
+                           partial);
+    });
     NFFT_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(virial_sum_kernel, dim3((unsigned)(p->batch_size * q.Cr)), dim3(kVirialBlock), 0, stream,
                        (const double *)partial, q.Cr, 0, (const int2 *)items, start,
@@ -421,12 +304,9 @@ int launch_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, 
     q.p2a2 = pi2_over_alpha2;
     double *partial = (double *)workspace;
     const dim3 grid((unsigned)(q.blocks * batch_size)), block(kVirialBlock);
-#define EWALD_VIRIAL_FAR_LAUNCH(CC) \
-    hipLaunchKernelGGL((ewald_virial_far_kernel<CC>), grid, block, 0, stream, q, (const float2 *)band, coeffs, partial)
-    if (q.C == 1) EWALD_VIRIAL_FAR_LAUNCH(1);
-    else if (q.C == 2) EWALD_VIRIAL_FAR_LAUNCH(2);
-    else EWALD_VIRIAL_FAR_LAUNCH(4);
-#undef EWALD_VIRIAL_FAR_LAUNCH
+    dispatch_columns(q.C, [&](auto CC) {
+        hipLaunchKernelGGL((ewald_virial_far_kernel<CC()>), grid, block, 0, stream, q, (const float2 *)band, coeffs, partial);
+    });
     NFFT_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(virial_sum_kernel, dim3((unsigned)(batch_size * q.C)), dim3(kVirialBlock), 0, stream,
                        (const double *)partial, q.C, q.blocks, (const int2 *)nullptr, (const int *)nullptr, 0, out);

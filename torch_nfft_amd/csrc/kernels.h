@@ -177,7 +177,7 @@ int launch_nearfield_point_gradient(const nfft_hip_nearfield_problem *p, int sym
 int64_t ewald_near_item_slots(const nfft_hip_ewald_problem *p);
 int launch_ewald_near(const nfft_hip_ewald_problem *p, const float *pos, const float *xr, const int *start,
                       const int64_t *index, float *z, float *f, void *items, hipStream_t stream);
-// ewald_near_box.hip (the same pair sum in an orthorhombic or triclinic box, on fractional positions, DESIGN.md section
+// ewald_near.hip again (the same pair sum in an orthorhombic or triclinic box, on fractional positions, DESIGN.md section
 // 7h): arguments as nfft_hip_ewald_near_box; `items`: ewald_near_box_item_slots(p) int2 of workspace
 int64_t ewald_near_box_item_slots(const nfft_hip_ewald_box_problem *p);
 int launch_ewald_near_box(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xr, const int *start,

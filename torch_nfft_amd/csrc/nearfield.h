@@ -1,7 +1,8 @@
-// What the near-field pair kernels share (nearfield.hip: the value; nearfield_grad.hip: the
-// gradient at the targets and its transpose, section 7e; nearfield_pgrad.hip: the gradient with respect to the points,
-// section 7f): the sizes of a work item and of an LDS tile, the parameter block, K'(r) / r and the work-item list.  The
-// wrapped pair kernel of the Ewald sum (ewald_near.hip, section 7g) takes the sizes and the work-item list from here too.
+// What the near-field pair kernels share besides their frame (nearfield.hip: the value, DESIGN.md section 7d;
+// nearfield_grad.hip: the gradient at the targets and its transpose, section 7e; nearfield_pgrad.hip: the gradient with
+// respect to the points, section 7f): the sizes of a work item and of an LDS tile, the parameter block, K'(r) / r and the
+// work-item list.  The wrapped pair kernels of the Ewald sum (ewald_near.hip, ewald_virial.hip, sections 7g-7i) take the
+// sizes and the work-item list from here too.  The frame itself -- lane decode, walks, tile sweep -- is pair_frame.h.
 #pragma once
 #include "common.h"
 #include "kernels.h"

@@ -11,12 +11,13 @@
 // the walk is over 3^(dim-1) contiguous source ranges ("rows").
 //
 // nearfield_items_kernel   one thread per cell: cuts the cell's targets into work items of kNearBlock
-// nearfield_kernel         the tiled N-body loop.  A workgroup owns one item, a lane one target; the sources of a row
-//                          stream through LDS in tiles of kNearTile (position as one float4, CC columns of x); every lane
-//                          reads the same source (an LDS broadcast) and keeps its CC sums in registers.  The loop is bound by
+// nearfield_kernel         the tiled N-body loop on the frame of pair_frame.h.  A workgroup owns one item, a lane one
+//                          target; the sources of a row stream through LDS in tiles of kNearTile (position as one float4,
+//                          CC columns of x); every lane reads the same source (an LDS broadcast) and keeps its CC sums in
+//                          registers: its own are the pair weight K - T_I and one sum per column.  The loop is bound by
 //                          the VALU: about 20 instructions and one transcendental per pair against one or two 16-byte LDS
 //                          broadcasts.  No atomics: a target's pairs are added in the order of the sorted sources.
-#include "nearfield.h"
+#include "pair_frame.h"
 
 namespace nfft {
 
@@ -60,25 +61,10 @@ __global__ void __launch_bounds__(kNearBlock) nearfield_kernel(NearParams q, con
     __shared__ __attribute__((aligned(16))) float s_x[kNearTile * CC];
     const int2 item = items[blockIdx.x];
     if (item.x < 0) return;  // (uniform: an empty slot)
-    const int tid = threadIdx.x;
-    const int k = item.x;
-    const int tend = min(item.y + kNearBlock, tstart[k + 1]);
-    const int ti = item.y + tid;
-    const bool active = ti < tend;
-    const bool wave_active = item.y + (tid & ~63) < tend;
-    const int G = q.G;
-    const int c0 = k % G;
-    const int c1 = q.dim >= 2 ? (k / G) % G : 0;
-    const int c2 = q.dim >= 3 ? (k / (G * G)) % G : 0;
+    const PairLane lane = pair_lane(item, tstart);
+    const OpenWalk walk(lane.cell, q.dim, q.G);
     // a lane without a target sits far away: every pair fails the distance test
-    float tx = 1e9f, ty = 0.f, tz = 0.f;
-    if (active) {
-        const float *tp = tgt + (int64_t)ti * q.dim;
-        tx = tp[0];
-        if (q.dim >= 2) ty = tp[1];
-        if (q.dim >= 3) tz = tp[2];
-    }
-    const int r1 = q.dim >= 2 ? 1 : 0, r2 = q.dim >= 3 ? 1 : 0;
+    const float4 t = lane_position(lane, tgt, q.dim, 1e9f);
     float a[PT];
 #pragma unroll
     for (int e = 0; e < PT; ++e) a[e] = q.poly[e];
@@ -86,71 +72,23 @@ __global__ void __launch_bounds__(kNearBlock) nearfield_kernel(NearParams q, con
         float acc[CC];
 #pragma unroll
         for (int c = 0; c < CC; ++c) acc[c] = 0.f;
-        for (int d2 = -r2; d2 <= r2; ++d2) {
-            if (c2 + d2 < 0 || c2 + d2 >= G) continue;
-            for (int d1 = -r1; d1 <= r1; ++d1) {
-                if (c1 + d1 < 0 || c1 + d1 >= G) continue;
-                const int row = k + (d2 * G + d1) * G;
-                const int first = sstart[row - (c0 > 0 ? 1 : 0)];
-                const int last = sstart[row + (c0 < G - 1 ? 1 : 0) + 1];
-                for (int t0 = first; t0 < last; t0 += kNearTile) {
-                    const int cnt = min(kNearTile, last - t0);
-                    __syncthreads();
-                    for (int j = tid; j < cnt; j += kNearBlock) {
-                        const float *sp = src + (int64_t)(t0 + j) * q.dim;
-                        float4 v = make_float4(sp[0], 0.f, 0.f, 0.f);
-                        if (q.dim >= 2) v.y = sp[1];
-                        if (q.dim >= 3) v.z = sp[2];
-                        s_pos[j] = v;
-                        const float *xp = xr + (int64_t)(t0 + j) * q.Cr + col0;
+        const StageColumns<CC> stage = {s_x, xr, q.Cr, col0};
+        walk(sstart, [&](int first, int last) {
+            sweep_range<4>(first, last, lane, s_pos, src, q.dim, stage, [&](int j) {
+                const PairSep d = open_sep(t, s_pos[j]);
+                const float ti = horner(a, d.rr * q.inv_eps2);
+                const float w = d.rr < q.eps2 ? kernel_value<KERNEL>(d.rr, q) - ti : 0.f;
 #pragma unroll
-                        for (int c = 0; c < CC; ++c) s_x[j * CC + c] = col0 + c < q.Cr ? xp[c] : 0.f;
-                    }
-                    __syncthreads();
-                    if (!wave_active) continue;
-#pragma unroll 4
-                    for (int j = 0; j < cnt; ++j) {
-                        const float4 s = s_pos[j];
-                        const float dx = tx - s.x, dy = ty - s.y, dz = tz - s.z;
-                        const float rr = dx * dx + dy * dy + dz * dz;
-                        const float u = rr * q.inv_eps2;
-                        float t = a[PT - 1];
-#pragma unroll
-                        for (int e = PT - 2; e >= 0; --e) t = t * u + a[e];
-                        const float w = rr < q.eps2 ? kernel_value<KERNEL>(rr, q) - t : 0.f;
-#pragma unroll
-                        for (int c = 0; c < CC; ++c) acc[c] += w * s_x[j * CC + c];
-                    }
-                }
-            }
-        }
-        if (active) {
-            float *zp = z + tindex[ti] * q.Cr + col0;
+                for (int c = 0; c < CC; ++c) acc[c] += w * s_x[j * CC + c];
+            });
+        });
+        if (lane.active) {
+            float *zp = z + tindex[lane.ti] * q.Cr + col0;
 #pragma unroll
             for (int c = 0; c < CC; ++c)
                 if (col0 + c < q.Cr) zp[c] = acc[c];
         }
     }
-}
-
-template <int KERNEL>
-void launch_pairs(const NearParams &q, int64_t slots, const int2 *items, const float *src, const float *xr, const int *sstart,
-                  const float *tgt, const int64_t *tindex, const int *tstart, float *z, hipStream_t stream)
-{
-    const dim3 grid((unsigned)slots), block(kNearBlock);
-#define NEAR_LAUNCH(CC, PT)                                                                                             \
-    hipLaunchKernelGGL((nearfield_kernel<KERNEL, CC, PT>), grid, block, 0, stream, q, items, src, xr, sstart, tgt, tindex, \
-                       tstart, z)
-    if (q.terms <= 4) {
-        if (q.Cr == 1) NEAR_LAUNCH(1, 4);
-        else if (q.Cr == 2) NEAR_LAUNCH(2, 4);
-        else NEAR_LAUNCH(4, 4);
-    } else {
-        if (q.Cr == 1) NEAR_LAUNCH(1, 8);
-        else if (q.Cr == 2) NEAR_LAUNCH(2, 8);
-        else NEAR_LAUNCH(4, 8);
-    }
-#undef NEAR_LAUNCH
 }
 
 }  // namespace
@@ -191,17 +129,15 @@ int launch_nearfield(const nfft_hip_nearfield_problem *p, const float *src, cons
     const NearParams q = near_params(p, p->poly, p->poly_terms);
     const int64_t slots = nearfield_item_slots(p);
     if (int rc = launch_nearfield_items(p, tstart, (int2 *)items, stream)) return rc;
-    const int2 *it = (const int2 *)items;
-    switch (p->kernel) {
-    case NFFT_HIP_KERNEL_ONE_OVER_MODULUS: launch_pairs<NFFT_HIP_KERNEL_ONE_OVER_MODULUS>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
-    case NFFT_HIP_KERNEL_ONE_OVER_SQUARE: launch_pairs<NFFT_HIP_KERNEL_ONE_OVER_SQUARE>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
-    case NFFT_HIP_KERNEL_LOGARITHM: launch_pairs<NFFT_HIP_KERNEL_LOGARITHM>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
-    case NFFT_HIP_KERNEL_THINPLATE_SPLINE: launch_pairs<NFFT_HIP_KERNEL_THINPLATE_SPLINE>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
-    case NFFT_HIP_KERNEL_MULTIQUADRIC: launch_pairs<NFFT_HIP_KERNEL_MULTIQUADRIC>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
-    case NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC: launch_pairs<NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
-    case NFFT_HIP_KERNEL_GAUSSIAN: launch_pairs<NFFT_HIP_KERNEL_GAUSSIAN>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
-    default: launch_pairs<NFFT_HIP_KERNEL_LAPLACIAN_RBF>(q, slots, it, src, xr, sstart, tgt, tindex, tstart, z, stream); break;
-    }
+    const dim3 grid((unsigned)slots), block(kNearBlock);
+    dispatch_kernel(p->kernel, [&](auto K) {
+        dispatch_columns(q.Cr, [&](auto CC) {
+            dispatch_terms(q.terms, [&](auto PT) {
+                hipLaunchKernelGGL((nearfield_kernel<K(), CC(), PT()>), grid, block, 0, stream, q, (const int2 *)items, src, xr,
+                                   sstart, tgt, tindex, tstart, z);
+            });
+        });
+    });
     NFFT_HIP_CHECK(hipGetLastError());
     return 0;
 }

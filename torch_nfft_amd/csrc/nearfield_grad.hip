@@ -8,10 +8,13 @@
 // T_I'(r) / r = (2 / eps_I^2) sum_{k >= 1} k a_k u^(k-1), u = r^2 / eps_I^2, a Horner form whose coefficients the host
 // makes in float64.  No reference counterpart.
 //
-// The design is the value kernel's (nearfield.hip): a work item is up to kNearBlock cell-sorted output points of one cell,
-// a lane owns one output point, the streamed points of 3^(dim-1) contiguous rows of cells pass through LDS in tiles of
-// kNearTile, every lane reads the same streamed point (an LDS broadcast) and sums in registers in the sorted order.  No
-// atomics.
+// The design is that of the frame in pair_frame.h: a work item is up to kNearBlock cell-sorted output
+// points of one cell, a lane owns one output point, the streamed points of 3^(dim-1) contiguous rows of cells pass through
+// LDS in tiles of kNearTile, every lane reads the same streamed point (an LDS broadcast) and sums in registers in the sorted
+// order.  No atomics.  The device code is WRITTEN OUT here and does not use the frame's templates: ported, its pair loops
+// were the same instructions (some v_fma_f32 encoded as v_fmac_f32) and yet two of its timed rows fell outside the margin
+// of the comparison with the code as it stands here (profiles/r16_pair_frame.md), so it stays as it was.  A fix to the
+// frame's lane decode, open walk or tile sweep has to be repeated in this file.  Only the launch uses pair_frame.h.
 //   gradient    output = targets, streamed = sources: LDS holds the position and CC columns of x; 3 CC sums per lane,
 //               dim CC of them stored to out[row, a, col]
 //   transpose   output = sources, streamed = targets: LDS holds the position and 3 CC values of v (axes past dim are
@@ -19,13 +22,13 @@
 //               "output - streamed" is s_j - t_i and the weight changes its sign.
 // A pair with r = 0 weighs exactly zero (its difference vector is zero; K'(r) / r is not finite there), like the pairs at
 // or beyond eps_I: selected, not branched over.
-#include "nearfield.h"
+#include "pair_frame.h"
 
 namespace nfft {
 
 namespace {
 
-constexpr int kNearGradient = 0, kNearTranspose = 1;
+constexpr int kNearTranspose = 1;  // MODE: 0 the gradient, 1 its transpose
 
 // PT: Horner terms, 4 or 8; the coefficients past `terms` are zero, which leaves the sum of the others bit for bit.
 // in: [streamed points, Cr] (gradient) or [streamed points, dim, Cr] (transpose); out: [output points, dim, Cr] (gradient)
@@ -149,44 +152,6 @@ __global__ void __launch_bounds__(kNearBlock) nearfield_grad_kernel(NearParams q
     }
 }
 
-template <int KERNEL, int MODE>
-void launch_grad_pairs(const NearParams &q, int64_t slots, const int2 *items, const float *spos, const float *in,
-                       const int *sstart, const float *opos, const int64_t *oindex, const int *ostart, float *out,
-                       hipStream_t stream)
-{
-    const dim3 grid((unsigned)slots), block(kNearBlock);
-#define NEAR_LAUNCH(CC, PT)                                                                                                 \
-    hipLaunchKernelGGL((nearfield_grad_kernel<KERNEL, CC, PT, MODE>), grid, block, 0, stream, q, items, spos, in, sstart, opos, \
-                       oindex, ostart, out)
-    if (q.terms <= 4) {
-        if (q.Cr == 1) NEAR_LAUNCH(1, 4);
-        else if (q.Cr == 2) NEAR_LAUNCH(2, 4);
-        else NEAR_LAUNCH(4, 4);
-    } else {
-        if (q.Cr == 1) NEAR_LAUNCH(1, 8);
-        else if (q.Cr == 2) NEAR_LAUNCH(2, 8);
-        else NEAR_LAUNCH(4, 8);
-    }
-#undef NEAR_LAUNCH
-}
-
-template <int MODE>
-void launch_grad_kernel(int kernel, const NearParams &q, int64_t slots, const int2 *it, const float *spos, const float *in,
-                        const int *sstart, const float *opos, const int64_t *oindex, const int *ostart, float *out,
-                        hipStream_t stream)
-{
-    switch (kernel) {
-    case NFFT_HIP_KERNEL_ONE_OVER_MODULUS: launch_grad_pairs<NFFT_HIP_KERNEL_ONE_OVER_MODULUS, MODE>(q, slots, it, spos, in, sstart, opos, oindex, ostart, out, stream); break;
-    case NFFT_HIP_KERNEL_ONE_OVER_SQUARE: launch_grad_pairs<NFFT_HIP_KERNEL_ONE_OVER_SQUARE, MODE>(q, slots, it, spos, in, sstart, opos, oindex, ostart, out, stream); break;
-    case NFFT_HIP_KERNEL_LOGARITHM: launch_grad_pairs<NFFT_HIP_KERNEL_LOGARITHM, MODE>(q, slots, it, spos, in, sstart, opos, oindex, ostart, out, stream); break;
-    case NFFT_HIP_KERNEL_THINPLATE_SPLINE: launch_grad_pairs<NFFT_HIP_KERNEL_THINPLATE_SPLINE, MODE>(q, slots, it, spos, in, sstart, opos, oindex, ostart, out, stream); break;
-    case NFFT_HIP_KERNEL_MULTIQUADRIC: launch_grad_pairs<NFFT_HIP_KERNEL_MULTIQUADRIC, MODE>(q, slots, it, spos, in, sstart, opos, oindex, ostart, out, stream); break;
-    case NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC: launch_grad_pairs<NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC, MODE>(q, slots, it, spos, in, sstart, opos, oindex, ostart, out, stream); break;
-    case NFFT_HIP_KERNEL_GAUSSIAN: launch_grad_pairs<NFFT_HIP_KERNEL_GAUSSIAN, MODE>(q, slots, it, spos, in, sstart, opos, oindex, ostart, out, stream); break;
-    default: launch_grad_pairs<NFFT_HIP_KERNEL_LAPLACIAN_RBF, MODE>(q, slots, it, spos, in, sstart, opos, oindex, ostart, out, stream); break;
-    }
-}
-
 }  // namespace
 
 int launch_nearfield_gradient(const nfft_hip_nearfield_problem *p, int transpose, const double *gradient_poly,
@@ -196,9 +161,17 @@ int launch_nearfield_gradient(const nfft_hip_nearfield_problem *p, int transpose
     const NearParams q = near_params(p, gradient_poly, p->poly_terms - 1);
     const int64_t slots = nearfield_item_slots(p);
     if (int rc = launch_nearfield_items(p, ostart, (int2 *)items, stream)) return rc;
-    const int2 *it = (const int2 *)items;
-    if (transpose) launch_grad_kernel<kNearTranspose>(p->kernel, q, slots, it, spos, in, sstart, opos, oindex, ostart, out, stream);
-    else launch_grad_kernel<kNearGradient>(p->kernel, q, slots, it, spos, in, sstart, opos, oindex, ostart, out, stream);
+    const dim3 grid((unsigned)slots), block(kNearBlock);
+    dispatch_flag(transpose != 0, [&](auto MODE) {
+        dispatch_kernel(p->kernel, [&](auto K) {
+            dispatch_columns(q.Cr, [&](auto CC) {
+                dispatch_terms(q.terms, [&](auto PT) {
+                    hipLaunchKernelGGL((nearfield_grad_kernel<K(), CC(), PT(), MODE()>), grid, block, 0, stream, q,
+                                       (const int2 *)items, spos, in, sstart, opos, oindex, ostart, out);
+                });
+            });
+        });
+    });
     NFFT_HIP_CHECK(hipGetLastError());
     return 0;
 }

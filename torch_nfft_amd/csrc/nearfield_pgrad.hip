@@ -13,12 +13,14 @@
 //             sum of the two gradients of point i.
 // No reference counterpart.
 //
-// The frame is the one of nearfield.hip and nearfield_grad.hip: a work item is up to kNearBlock cell-sorted output points of
-// one cell, a lane owns one output point, the streamed points of 3^(dim-1) contiguous rows of cells pass through LDS in tiles
-// of kNearTile, every lane reads the same streamed point (an LDS broadcast) and sums in registers in the sorted order.  No
-// atomics.  Three sums per lane whatever the number of columns: they are zeroed once, and every pass of CC columns reloads
+// The kernel stands on the frame of pair_frame.h -- the lane decode, the open walk, the positions,
+// the Horner form, sums in registers in the sorted order, no atomics -- except for the tile sweep, which is WRITTEN OUT
+// here with its flat staging of SV values per streamed point: through sweep_range the compiler orders the LDS reads of the
+// symmetric CC = 4 loop differently and that loop measured 2 % slower (profiles/r16_pair_frame.md).  A change to
+// sweep_range has to be repeated in this file.  Its own: three sums per lane whatever the number of columns: they are
+// zeroed once, and every pass of CC columns reloads
 // u and v and keeps adding, so a point's result stays one sum in one fixed order.
-#include "nearfield.h"
+#include "pair_frame.h"
 
 namespace nfft {
 
@@ -41,25 +43,11 @@ __global__ void __launch_bounds__(kNearBlock) nearfield_pgrad_kernel(NearParams 
     __shared__ __attribute__((aligned(16))) float s_v[kNearTile * SV];
     const int2 item = items[blockIdx.x];
     if (item.x < 0) return;  // (uniform: an empty slot)
+    const PairLane lane = pair_lane(item, ostart);
     const int tid = threadIdx.x;
-    const int k = item.x;
-    const int tend = min(item.y + kNearBlock, ostart[k + 1]);
-    const int ti = item.y + tid;
-    const bool active = ti < tend;
-    const bool wave_active = item.y + (tid & ~63) < tend;
-    const int G = q.G;
-    const int c0 = k % G;
-    const int c1 = q.dim >= 2 ? (k / G) % G : 0;
-    const int c2 = q.dim >= 3 ? (k / (G * G)) % G : 0;
+    const OpenWalk walk(lane.cell, q.dim, q.G);
     // a lane without an output point sits far away: every pair fails the distance test
-    float tx = 1e9f, ty = 0.f, tz = 0.f;
-    if (active) {
-        const float *tp = opos + (int64_t)ti * q.dim;
-        tx = tp[0];
-        if (q.dim >= 2) ty = tp[1];
-        if (q.dim >= 3) tz = tp[2];
-    }
-    const int r1 = q.dim >= 2 ? 1 : 0, r2 = q.dim >= 3 ? 1 : 0;
+    const float4 t = lane_position(lane, opos, q.dim, 1e9f);
     float a[PT];
 #pragma unroll
     for (int e = 0; e < PT; ++e) a[e] = q.poly[e];
@@ -71,107 +59,53 @@ __global__ void __launch_bounds__(kNearBlock) nearfield_pgrad_kernel(NearParams 
         for (int e = 0; e < SV; ++e) {
             const int c = e < CC ? e : e - CC;
             const float *src = e < CC ? oval : sval;
-            own[e] = active && col0 + c < q.Cr ? src[(int64_t)ti * q.Cr + col0 + c] : 0.f;
+            own[e] = lane.active && col0 + c < q.Cr ? src[(int64_t)lane.ti * q.Cr + col0 + c] : 0.f;
         }
-        for (int d2 = -r2; d2 <= r2; ++d2) {
-            if (c2 + d2 < 0 || c2 + d2 >= G) continue;
-            for (int d1 = -r1; d1 <= r1; ++d1) {
-                if (c1 + d1 < 0 || c1 + d1 >= G) continue;
-                const int row = k + (d2 * G + d1) * G;
-                const int first = sstart[row - (c0 > 0 ? 1 : 0)];
-                const int last = sstart[row + (c0 < G - 1 ? 1 : 0) + 1];
-                for (int t0 = first; t0 < last; t0 += kNearTile) {
-                    const int cnt = min(kNearTile, last - t0);
-                    __syncthreads();
-                    for (int j = tid; j < cnt; j += kNearBlock) {
-                        const float *sp = spos + (int64_t)(t0 + j) * q.dim;
-                        float4 v = make_float4(sp[0], 0.f, 0.f, 0.f);
-                        if (q.dim >= 2) v.y = sp[1];
-                        if (q.dim >= 3) v.z = sp[2];
-                        s_pos[j] = v;
-                    }
-                    // the staged values, one per lane and step: element e of the streamed point j is v[e] for e < CC and
-                    // (SYM) u[e - CC] behind it
-                    for (int idx = tid; idx < cnt * SV; idx += kNearBlock) {
-                        const int j = idx / SV, e = idx - j * SV;
-                        const bool second = SYM != 0 && e >= CC;
-                        const int c = second ? e - CC : e;
-                        const float *src = second ? oval : sval;
-                        s_v[idx] = col0 + c < q.Cr ? src[(int64_t)(t0 + j) * q.Cr + col0 + c] : 0.f;
-                    }
-                    __syncthreads();
-                    if (!wave_active) continue;
+        walk(sstart, [&](int first, int last) {
+            for (int t0 = first; t0 < last; t0 += kNearTile) {
+                const int cnt = min(kNearTile, last - t0);
+                __syncthreads();
+                for (int j = tid; j < cnt; j += kNearBlock) s_pos[j] = load_position(spos, t0 + j, q.dim);
+                // the staged values, one per lane and step: element e of the streamed point j is v[e] for e < CC and
+                // (SYM) u[e - CC] behind it
+                for (int idx = tid; idx < cnt * SV; idx += kNearBlock) {
+                    const int j = idx / SV, e = idx - j * SV;
+                    const bool second = SYM != 0 && e >= CC;
+                    const int c = second ? e - CC : e;
+                    const float *src = second ? oval : sval;
+                    s_v[idx] = col0 + c < q.Cr ? src[(int64_t)(t0 + j) * q.Cr + col0 + c] : 0.f;
+                }
+                __syncthreads();
+                if (!lane.wave_active) continue;
 #pragma unroll kUnroll
-                    for (int j = 0; j < cnt; ++j) {
-                        const float4 s = s_pos[j];
-                        const float dx = tx - s.x, dy = ty - s.y, dz = tz - s.z;
-                        const float rr = dx * dx + dy * dy + dz * dz;
-                        const float u = rr * q.inv_eps2;
-                        float t = a[PT - 1];
+                for (int j = 0; j < cnt; ++j) {
+                    const float4 s = s_pos[j];
+                    const float dx = t.x - s.x, dy = t.y - s.y, dz = t.z - s.z;
+                    const float rr = dx * dx + dy * dy + dz * dz;
+                    const float ti = horner(a, rr * q.inv_eps2);
+                    const float g = kernel_slope<KERNEL>(rr, q);
+                    const float w = rr < q.eps2 && rr > 0.f ? g - ti : 0.f;
+                    // u_i . v_j (+ v_i . u_j): the lane's u meets the staged v, its v the staged u
+                    float dot = 0.f;
 #pragma unroll
-                        for (int e = PT - 2; e >= 0; --e) t = t * u + a[e];
-                        const float g = kernel_slope<KERNEL>(rr, q);
-                        const float w = rr < q.eps2 && rr > 0.f ? g - t : 0.f;
-                        // u_i . v_j (+ v_i . u_j): the lane's u meets the staged v, its v the staged u
-                        float dot = 0.f;
+                    for (int c = 0; c < CC; ++c) dot += own[c] * s_v[j * SV + c];
+                    if constexpr (SYM != 0) {
 #pragma unroll
-                        for (int c = 0; c < CC; ++c) dot += own[c] * s_v[j * SV + c];
-                        if constexpr (SYM != 0) {
-#pragma unroll
-                            for (int c = 0; c < CC; ++c) dot += own[CC + c] * s_v[j * SV + CC + c];
-                        }
-                        const float wd = w * dot;
-                        acc0 += wd * dx;
-                        acc1 += wd * dy;
-                        acc2 += wd * dz;
+                        for (int c = 0; c < CC; ++c) dot += own[CC + c] * s_v[j * SV + CC + c];
                     }
+                    const float wd = w * dot;
+                    acc0 += wd * dx;
+                    acc1 += wd * dy;
+                    acc2 += wd * dz;
                 }
             }
-        }
+        });
     }
-    if (active) {
-        float *zp = out + oindex[ti] * q.dim;
+    if (lane.active) {
+        float *zp = out + oindex[lane.ti] * q.dim;
         zp[0] = acc0;
         if (q.dim >= 2) zp[1] = acc1;
         if (q.dim >= 3) zp[2] = acc2;
-    }
-}
-
-template <int KERNEL, int SYM>
-void launch_pgrad_pairs(const NearParams &q, int64_t slots, const int2 *items, const float *spos, const float *sval,
-                        const int *sstart, const float *opos, const float *oval, const int64_t *oindex, const int *ostart,
-                        float *out, hipStream_t stream)
-{
-    const dim3 grid((unsigned)slots), block(kNearBlock);
-#define NEAR_LAUNCH(CC, PT)                                                                                                  \
-    hipLaunchKernelGGL((nearfield_pgrad_kernel<KERNEL, CC, PT, SYM>), grid, block, 0, stream, q, items, spos, sval, sstart, opos, \
-                       oval, oindex, ostart, out)
-    if (q.terms <= 4) {
-        if (q.Cr == 1) NEAR_LAUNCH(1, 4);
-        else if (q.Cr == 2) NEAR_LAUNCH(2, 4);
-        else NEAR_LAUNCH(4, 4);
-    } else {
-        if (q.Cr == 1) NEAR_LAUNCH(1, 8);
-        else if (q.Cr == 2) NEAR_LAUNCH(2, 8);
-        else NEAR_LAUNCH(4, 8);
-    }
-#undef NEAR_LAUNCH
-}
-
-template <int SYM>
-void launch_pgrad_kernel(int kernel, const NearParams &q, int64_t slots, const int2 *it, const float *spos, const float *sval,
-                         const int *sstart, const float *opos, const float *oval, const int64_t *oindex, const int *ostart,
-                         float *out, hipStream_t stream)
-{
-    switch (kernel) {
-    case NFFT_HIP_KERNEL_ONE_OVER_MODULUS: launch_pgrad_pairs<NFFT_HIP_KERNEL_ONE_OVER_MODULUS, SYM>(q, slots, it, spos, sval, sstart, opos, oval, oindex, ostart, out, stream); break;
-    case NFFT_HIP_KERNEL_ONE_OVER_SQUARE: launch_pgrad_pairs<NFFT_HIP_KERNEL_ONE_OVER_SQUARE, SYM>(q, slots, it, spos, sval, sstart, opos, oval, oindex, ostart, out, stream); break;
-    case NFFT_HIP_KERNEL_LOGARITHM: launch_pgrad_pairs<NFFT_HIP_KERNEL_LOGARITHM, SYM>(q, slots, it, spos, sval, sstart, opos, oval, oindex, ostart, out, stream); break;
-    case NFFT_HIP_KERNEL_THINPLATE_SPLINE: launch_pgrad_pairs<NFFT_HIP_KERNEL_THINPLATE_SPLINE, SYM>(q, slots, it, spos, sval, sstart, opos, oval, oindex, ostart, out, stream); break;
-    case NFFT_HIP_KERNEL_MULTIQUADRIC: launch_pgrad_pairs<NFFT_HIP_KERNEL_MULTIQUADRIC, SYM>(q, slots, it, spos, sval, sstart, opos, oval, oindex, ostart, out, stream); break;
-    case NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC: launch_pgrad_pairs<NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC, SYM>(q, slots, it, spos, sval, sstart, opos, oval, oindex, ostart, out, stream); break;
-    case NFFT_HIP_KERNEL_GAUSSIAN: launch_pgrad_pairs<NFFT_HIP_KERNEL_GAUSSIAN, SYM>(q, slots, it, spos, sval, sstart, opos, oval, oindex, ostart, out, stream); break;
-    default: launch_pgrad_pairs<NFFT_HIP_KERNEL_LAPLACIAN_RBF, SYM>(q, slots, it, spos, sval, sstart, opos, oval, oindex, ostart, out, stream); break;
     }
 }
 
@@ -185,9 +119,17 @@ int launch_nearfield_point_gradient(const nfft_hip_nearfield_problem *p, int sym
     const NearParams q = near_params(p, gradient_poly, p->poly_terms - 1);
     const int64_t slots = nearfield_item_slots(p);
     if (int rc = launch_nearfield_items(p, ostart, (int2 *)items, stream)) return rc;
-    const int2 *it = (const int2 *)items;
-    if (symmetric) launch_pgrad_kernel<1>(p->kernel, q, slots, it, spos, sval, sstart, opos, oval, oindex, ostart, out, stream);
-    else launch_pgrad_kernel<0>(p->kernel, q, slots, it, spos, sval, sstart, opos, oval, oindex, ostart, out, stream);
+    const dim3 grid((unsigned)slots), block(kNearBlock);
+    dispatch_flag(symmetric != 0, [&](auto SYM) {
+        dispatch_kernel(p->kernel, [&](auto K) {
+            dispatch_columns(q.Cr, [&](auto CC) {
+                dispatch_terms(q.terms, [&](auto PT) {
+                    hipLaunchKernelGGL((nearfield_pgrad_kernel<K(), CC(), PT(), SYM()>), grid, block, 0, stream, q,
+                                       (const int2 *)items, spos, sval, sstart, opos, oval, oindex, ostart, out);
+                });
+            });
+        });
+    });
     NFFT_HIP_CHECK(hipGetLastError());
     return 0;
 }
