@@ -290,6 +290,12 @@ def load():
     if hasattr(lib, "nfft_dbg_work_list"):
         lib.nfft_dbg_work_list.argtypes = [P, vp, ci, vp, vp, vp, i64, vp]
         lib.nfft_dbg_work_list.restype = ci
+    if hasattr(lib, "nfft_dbg_fft_route"):
+        lib.nfft_dbg_fft_route.argtypes = [P, ci, ci, ci, i64, vp]
+        lib.nfft_dbg_fft_route.restype = ci
+    if hasattr(lib, "nfft_dbg_fft_stage"):
+        lib.nfft_dbg_fft_stage.argtypes = [P, ci, ci, ci, vp, vp, vp, ci, vp, i64, vp]
+        lib.nfft_dbg_fft_stage.restype = ci
     if lib.nfft_hip_abi_version() != ABI_VERSION:
         raise ImportError("torch_nfft_amd: ABI version mismatch in %s" % LIB_PATH)
     _lib = lib
@@ -362,6 +368,62 @@ def route(problem, real_columns):
     check(load().nfft_dbg_route(ctypes.byref(problem), real_columns, out))
     return Route(bool(out[0]), bool(out[1]), bool(out[2]), SPREAD_MODES[out[3]], bool(out[4]), GATHER_KERNELS[out[5]],
                  int(out[6]), bool(out[7]))
+
+
+FFT_ROUTES = ("full", "roc_rows", "own_planar", "own_ci")  # csrc/api.hip FftRoute
+FftRouteRecord = collections.namedtuple(
+    "FftRouteRecord", "fft ci chunk_planes total_planes chunk_fft nc_axis1 nc_axis0 nc_forward specialised")
+
+
+def fft_route(problem, adjoint, x_is_complex, real_output, chunk_np=0):
+    """Test entry ``nfft_dbg_fft_route``: what csrc/api.hip make_route decides for the FFT stage of an adjoint
+    (``adjoint`` true) or a forward transform of ``problem`` -- ``fft`` ("full": rocFFT + the roll-off kernel, "roc_rows":
+    rocFFT rows + column passes, "own_planar": own rows + planar column passes), ``ci`` (chunks of >= 32 planes go
+    column-innermost), the chunk size and plane count, and for a chunk of ``chunk_np`` planes (0: a full chunk) its route
+    ``chunk_fft`` ("own_ci" where it goes column-innermost) and the tile widths make_col_geom gives its launches:
+    ``nc_axis1`` / ``nc_axis0`` for an adjoint, ``nc_forward`` for a forward transform, 0 where no such launch runs;
+    ``specialised``: one flag per launch kind (axis1, axis0, forward), true where col_dispatch takes a compile-time
+    instantiation.  Host code only; NFFT_HIP_CHUNK_BYTES and NFFT_HIP_NO_COLFFT apply as in the calls."""
+    out = (ctypes.c_int64 * 11)()
+    check(load().nfft_dbg_fft_route(ctypes.byref(problem), 1 if adjoint else 0, 1 if x_is_complex else 0,
+                                     1 if real_output else 0, chunk_np, out))
+    return FftRouteRecord(FFT_ROUTES[out[0]], bool(out[1]), int(out[2]), int(out[3]), FFT_ROUTES[out[4]], int(out[5]),
+                          int(out[7]), int(out[9]), (bool(out[6]), bool(out[8]), bool(out[10])))
+
+
+def fft_stage(problem, adjoint, x_is_complex, real_output, planes, band, mult=None):
+    """Test entry ``nfft_dbg_fft_stage``: the FFT stage alone, through make_route and the chunk loop of the operators.
+    ``planes``: float32 CUDA tensor [B * C * ppc, (2N)^d] (ppc = 2 for a complex x of an adjoint / a complex y of a
+    forward transform, (re, im) adjacent); ``band``: [B, N^d, C] float32 or complex64.  Adjoint: planes -> band (times the
+    per-frequency factor ``mult`` [N^d], float32 or complex64, if given); forward: band -> planes.  Writes in place."""
+    import torch
+    assert planes.is_cuda and planes.is_contiguous() and planes.dtype == torch.float32
+    assert band.is_cuda and band.is_contiguous()
+    if adjoint:
+        assert band.dtype == (torch.float32 if real_output else torch.complex64)
+    else:
+        assert band.dtype == (torch.complex64 if x_is_complex else torch.float32)
+    ppc = (2 if x_is_complex else 1) if adjoint else (1 if real_output else 2)
+    columns = problem.batch_size * problem.num_columns
+    assert planes.numel() == columns * ppc * (2 * problem.N) ** problem.dim
+    assert band.numel() == columns * problem.N ** problem.dim
+    assert mult is None or mult.numel() == problem.N ** problem.dim
+    lib = load()
+    need = (lib.nfft_hip_adjoint_workspace_bytes if adjoint else lib.nfft_hip_forward_workspace_bytes)(
+        ctypes.byref(problem), 1 if x_is_complex else 0, 1 if real_output else 0)
+    if need < 0:
+        check(EINVAL)
+    ws = torch.empty(need, dtype=torch.uint8, device=planes.device)
+    kind = 0
+    if mult is not None:
+        assert adjoint and mult.is_cuda and mult.is_contiguous()
+        kind = {torch.float32: 1, torch.complex64: 2}[mult.dtype]
+    stream = torch.cuda.current_stream().cuda_stream
+    check(lib.nfft_dbg_fft_stage(ctypes.byref(problem), 1 if adjoint else 0, 1 if x_is_complex else 0,
+                                 1 if real_output else 0, ctypes.c_void_p(planes.data_ptr()),
+                                 ctypes.c_void_p(band.data_ptr()), ctypes.c_void_p(mult.data_ptr() if kind else None),
+                                 kind, ctypes.c_void_p(ws.data_ptr()), need, ctypes.c_void_p(stream)))
+    check_status()
 
 
 def check_status(stream=None, synchronize=True):

@@ -361,9 +361,10 @@ bool hvp_fused_dxhat(const Route &ra)
 // The whole route of an adjoint (x: ppc real planes per column), a forward transform (y: ppc real planes per column) or
 // an application of the Toeplitz normal operator (the forward FFT stage, the product with the
 // kernel grid and the adjoint FFT stage on the same chunk of planes -- no points, no plan, and no roll-off in either
-// stage), the chunk size and the workspace carve included.
+// stage), the chunk size and the workspace carve included.  size_fft_work = false (nfft_dbg_fft_route only: no device needed)
+// leaves rocFFT's work area out: every decision is made as usual, but `total` is no workspace size then.
 enum RouteKind { kRouteForward, kRouteAdjoint, kRouteToeplitz };
-int make_route(const nfft_hip_problem *p, int ppc, RouteKind kind, Route &r)
+int make_route(const nfft_hip_problem *p, int ppc, RouteKind kind, Route &r, bool size_fft_work = true)
 {
     const bool adjoint = kind == kRouteAdjoint, toeplitz = kind == kRouteToeplitz;
     if (toeplitz) {
@@ -398,7 +399,7 @@ int make_route(const nfft_hip_problem *p, int ppc, RouteKind kind, Route &r)
     if (chunk > 32768) chunk = 32768 - 32768 % ppc;  // blockIdx.y limit
     r.chunk_planes = chunk;
     r.work_bytes = 0;
-    if (r.total_planes > 0) {
+    if (r.total_planes > 0 && size_fft_work) {
         // plans for the full chunk and for the remainder chunk (the normal operator runs both directions)
         const FftKind kinds[2] = {fkind, colfft ? kR2CRows : kR2C};
         const int64_t rem = r.total_planes % chunk;
@@ -736,6 +737,73 @@ int nfft_dbg_route(const nfft_hip_problem *p, int64_t real_columns, int32_t *out
     out[5] = (int32_t)r.gather;
     out[6] = r.g.CG;
     out[7] = small_grid_route(p) ? 1 : 0;
+    return 0;
+}
+
+// make_route as adjoint_impl / forward_impl call it (planes per column: of x for an adjoint, of y for a forward transform)
+static int stage_route(const nfft_hip_problem *p, int adjoint, int x_is_complex, int real_output, Route &r, bool size_fft_work)
+{
+    if (adjoint) return make_route(p, x_is_complex ? 2 : 1, kRouteAdjoint, r, size_fft_work);
+    return make_route(p, real_output ? 1 : 2, kRouteForward, r, size_fft_work);
+}
+
+// Test entry (tests/test_route.py, tests/test_gpu_fft_stage.py; not part of the C ABI either): what make_route decides for
+// the FFT stage of an adjoint (adjoint != 0) or a forward transform, under the process's NFFT_HIP_CHUNK_BYTES and
+// NFFT_HIP_NO_COLFFT, and what a chunk of `chunk_np` planes (<= 0: chunk_planes) runs.  out[11] = {fft (FftRoute), ci,
+// chunk_planes, total_planes, chunk_fft(chunk_np), then {NC, 1 if col_dispatch takes a compile-time instantiation} of the
+// adjoint's axis-1 pass, of its axis-0 pass and of the forward passes (colfft.hip colfft_tile_widths: the adjoint pairs
+// are 0 for a forward route and the forward pair for an adjoint one, all are 0 on kFftFull)}.  Host code only: no launch,
+// no device memory (make_route without rocFFT's work-area query).
+int nfft_dbg_fft_route(const nfft_hip_problem *p, int adjoint, int x_is_complex, int real_output, int64_t chunk_np, int64_t *out)
+{
+    if (int rc = validate(p)) return rc;
+    if (!out) { set_error("Input mismatch: no route"); return NFFT_HIP_EINVAL; }
+    Route r;
+    if (int rc = stage_route(p, adjoint, x_is_complex, real_output, r, false)) return rc;
+    const int64_t np = chunk_np > 0 ? chunk_np : r.chunk_planes;
+    const FftRoute route = r.chunk_fft(np);
+    int32_t nc[6] = {0, 0, 0, 0, 0, 0};
+    if (route != kFftFull) colfft_tile_widths(r.g, route == kFftOwnPlanar, route == kFftOwnCi, x_is_complex, np, nc);
+    out[0] = (int64_t)r.fft;
+    out[1] = r.ci ? 1 : 0;
+    out[2] = r.chunk_planes;
+    out[3] = r.total_planes;
+    out[4] = (int64_t)route;
+    for (int i = 0; i < 6; ++i) out[5 + i] = (i < 4) == (adjoint != 0) ? nc[i] : 0;
+    return 0;
+}
+
+// Test entry (tests/test_gpu_fft_stage.py; not part of the C ABI either): the FFT stage alone, on the Route and through
+// the chunk loop of adjoint_impl / forward_impl, with a copy between the caller's planes and the chunk's grids where
+// those spread or gather.  adjoint != 0: planes [B * C * ppc, (2N)^d] real grids -> band = y [B, N^d, C] (mult / mult_kind
+// as in the fastsum); else band = xhat [B, N^d, C] -> planes.  The workspace is that of nfft_hip_adjoint_workspace_bytes /
+// nfft_hip_forward_workspace_bytes.  Never the one-kernel path of small_grid_route (tests/test_gpu_smallgrid.py).
+int nfft_dbg_fft_stage(const nfft_hip_problem *p, int adjoint, int x_is_complex, int real_output, void *planes, void *band,
+                       const void *mult, int mult_kind, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;
+    if (int rc = validate(p)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Route r;
+    if (int rc = stage_route(p, adjoint, x_is_complex, real_output, r, true)) return rc;
+    if (r.total_planes == 0) return 0;
+    if (!planes || !band) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    if (!workspace || workspace_bytes < r.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    float *grid = (float *)(ws + r.off_grid);
+    float2 *spec = (float2 *)(ws + r.off_spec);
+    for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes) {
+        const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
+        float *mine = (float *)planes + p0 * r.g.cells;
+        const size_t bytes = (size_t)(np * r.g.cells * 4);
+        if (adjoint) {
+            NFFT_HIP_CHECK(hipMemcpyAsync(grid, mine, bytes, hipMemcpyDeviceToDevice, s));
+            if (int rc = fft_adjoint_chunk(r, ws, grid, spec, x_is_complex, real_output, p0, np, band, mult, mult_kind, s)) return rc;
+        } else {
+            if (int rc = fft_forward_chunk(r, ws, band, x_is_complex, real_output, p0, np, grid, spec, s)) return rc;
+            NFFT_HIP_CHECK(hipMemcpyAsync(mine, grid, bytes, hipMemcpyDeviceToDevice, s));
+        }
+    }
     return 0;
 }
 

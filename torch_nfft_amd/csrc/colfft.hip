@@ -1510,6 +1510,25 @@ int launch_colfft_adjoint_ci(const Geom &g, const float2 *spec, void *scratch, i
     return 0;
 }
 
+// For the test entry nfft_dbg_fft_route (api.hip): the tile widths of the column-pass launches above for a chunk of
+// `nplanes` planes, from the same make_col_geom / make_ci_geom calls, and whether col_dispatch takes a compile-time
+// instantiation.  out[6] = {NC, specialised} of the adjoint's axis-1 pass (3-D only, else 0), of its axis-0 pass
+// (x_is_complex: two tile buffers, one launch plane per column) and of the forward passes.
+void colfft_tile_widths(const Geom &g, bool compact, bool ci, int x_is_complex, int64_t nplanes, int32_t *out)
+{
+    const bool two = x_is_complex != 0;
+    const ColGeom geoms[3] = {ci ? make_ci_geom(g) : make_col_geom(g, false, compact),
+                              ci ? make_ci_geom(g) : make_col_geom(g, two, compact, nplanes / (two ? 2 : 1)),
+                              ci ? make_ci_geom(g) : make_col_geom(g, false, compact, nplanes)};
+    for (int i = 0; i < 3; ++i) {
+        int specialised = 0;
+        if (!ci) col_dispatch(geoms[i], [&](auto lm, auto) { specialised = decltype(lm)::value != 0; });
+        out[2 * i] = geoms[i].NC;
+        out[2 * i + 1] = specialised;
+    }
+    if (g.dim == 2) out[0] = out[1] = 0;
+}
+
 // xhat [B, N^3, C] -> T' -> S'
 int launch_colfft_forward_ci(const Geom &g, const void *xhat, float2 *spec, void *scratch, int64_t C, int x_is_complex,
                              int real_output, int64_t plane0, int64_t nplanes, hipStream_t stream)

@@ -128,6 +128,9 @@ int launch_colfft_adjoint_ci(const Geom &g, const float2 *spec, void *scratch, i
                              hipStream_t stream);
 int launch_colfft_forward_ci(const Geom &g, const void *xhat, float2 *spec, void *scratch, int64_t C, int x_is_complex,
                              int real_output, int64_t plane0, int64_t nplanes, hipStream_t stream);
+// test support (api.hip nfft_dbg_fft_route): out[6] = {NC, 1 if a compile-time instantiation runs} of the adjoint's axis-1
+// pass, of its axis-0 pass and of the forward passes for a chunk of nplanes planes (`ci`: the column-innermost launches)
+void colfft_tile_widths(const Geom &g, bool compact, bool ci, int x_is_complex, int64_t nplanes, int32_t *out);
 // planar [ncols][N^d] <-> column-interleaved [B, N^d, C] copies (tiled transposes) for the column passes with C > 1
 int launch_column_layout(bool to_interleaved, const void *src, void *dst, int64_t K, int64_t C, int64_t col0,
                          int64_t ncols, int elem_bytes, hipStream_t stream);
