@@ -166,3 +166,70 @@ def test_bench_self_launches_ranks_before_touching_the_gpu(monkeypatch):
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     assert cmd[-6:] == ["--gpus", "4", "--steps", "3", "--warmup", "1"]
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def _pair_family_cases():
+    """(name, size query, call with (workspace, bytes)) of the seven pair-family entry points of include/nfft_hip.h on their
+    smallest problems: 8 points, 1 column, 1 and 2 point sets; eps_I = 0.125; r_cut = 1/3; the unit box and a triclinic one."""
+    from torch_nfft_amd import _lib
+    lib = _lib.load()
+    # any non-null address: a call that refuses its workspace returns before it reads its arguments or launches anything
+    dummy = ctypes.create_string_buffer(64)
+    a = ctypes.cast(dummy, ctypes.c_void_p)
+    gpoly = (ctypes.c_double * 8)(1.0)
+    cases = []
+    for B in (1, 2):
+        q = _lib.NearfieldProblem(3, 0, 2, 0, 8, 8, 1, B, 0.0, 0.125, (ctypes.c_double * 8)(1.0, 0.5))
+        q.cells_per_axis = lib.nfft_hip_nearfield_cells(3, 0.125, B)
+        Q = ctypes.byref(q)
+        cases += [
+            ("nearfield B=%d" % B, lambda Q=Q: lib.nfft_hip_nearfield_workspace_bytes(Q),
+             lambda ws, n, Q=Q: lib.nfft_hip_nearfield(Q, a, a, a, a, a, a, a, ws, n, None)),
+            ("nearfield_gradient B=%d" % B, lambda Q=Q: lib.nfft_hip_nearfield_gradient_workspace_bytes(Q),
+             lambda ws, n, Q=Q: lib.nfft_hip_nearfield_gradient(Q, 0, gpoly, a, a, a, a, a, a, a, ws, n, None)),
+            ("nearfield_point_gradient B=%d" % B, lambda Q=Q: lib.nfft_hip_nearfield_point_gradient_workspace_bytes(Q),
+             lambda ws, n, Q=Q: lib.nfft_hip_nearfield_point_gradient(Q, 0, gpoly, a, a, a, a, a, a, a, a, ws, n, None)),
+        ]
+        e = _lib.EwaldProblem(lib.nfft_hip_ewald_near_cells(1.0 / 3.0, B), 1, 8, 1, B, 2.0, 1.0 / 3.0)
+        E = ctypes.byref(e)
+        cases.append(("ewald_near B=%d" % B, lambda E=E: lib.nfft_hip_ewald_near_workspace_bytes(E),
+                      lambda ws, n, E=E: lib.nfft_hip_ewald_near(E, a, a, a, a, a, a, ws, n, None)))
+        cases.append(("ewald_virial_far B=%d" % B, lambda B=B: lib.nfft_hip_ewald_virial_far_workspace_bytes(16, B, 1),
+                      lambda ws, n, B=B: lib.nfft_hip_ewald_virial_far(16, B, 1, a, a, (ctypes.c_double * 6)(1, 0, 1, 0, 0, 1), 2.5,
+                                                                        a, ws, n, None)))
+    for name, B, box in (("unit", 1, (1, 0, 1, 0, 0, 1)), ("triclinic", 2, (1.5, 0.25, 1.25, -0.5, 0.125, 2.0))):
+        b = _lib.EwaldBoxProblem((ctypes.c_int32 * 3)(), 1, 8, 1, B, 2.0, 1.0 / 3.0, (ctypes.c_double * 6)(*box))
+        assert lib.nfft_hip_ewald_box_cells(b.box, b.r_cut, B, b.cells) == 0
+        Bx = ctypes.byref(b)
+        cases.append(("ewald_near_box %s" % name, lambda Bx=Bx: lib.nfft_hip_ewald_near_box_workspace_bytes(Bx),
+                      lambda ws, n, Bx=Bx: lib.nfft_hip_ewald_near_box(Bx, a, a, a, a, a, a, ws, n, None)))
+        cases.append(("ewald_virial_near %s" % name, lambda Bx=Bx: lib.nfft_hip_ewald_virial_near_workspace_bytes(Bx),
+                      lambda ws, n, Bx=Bx: lib.nfft_hip_ewald_virial_near(Bx, a, a, a, a, ws, n, None)))
+    return cases, (dummy, gpoly)
+
+
+# what the library returned before the size queries and the calls shared one function per family
+PAIR_FAMILY_BYTES = {
+    "nearfield B=1": 776, "nearfield_gradient B=1": 776, "nearfield_point_gradient B=1": 776,
+    "nearfield B=2": 1288, "nearfield_gradient B=2": 1288, "nearfield_point_gradient B=2": 1288,
+    "ewald_near B=1": 480, "ewald_near B=2": 696,
+    "ewald_near_box unit": 480, "ewald_near_box triclinic": 1416,
+    "ewald_virial_near unit": 2080, "ewald_virial_near triclinic": 9656,
+    "ewald_virial_far B=1": 1152, "ewald_virial_far B=2": 2048,
+}
+
+
+def test_pair_family_workspace_queries_and_refusals():
+    """Every pair family sizes its workspace in one place: the query returns the recorded size, and the matching call
+    refuses a null workspace and one byte less than that size with EWORKSPACE.  No device, no rocFFT."""
+    from torch_nfft_amd import _lib
+    cases, keep = _pair_family_cases()
+    assert sorted(name for name, _, _ in cases) == sorted(PAIR_FAMILY_BYTES)
+    short = ctypes.create_string_buffer(1 << 16)
+    for name, query, call in cases:
+        need = query()
+        assert need == PAIR_FAMILY_BYTES[name], (name, need)
+        assert need - 1 <= len(short)
+        for ws, nbytes in ((None, need), (ctypes.cast(short, ctypes.c_void_p), need - 1)):
+            assert call(ws, nbytes) == _lib.EWORKSPACE, name
+            assert _lib.last_error() == "workspace too small", name

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.h"
+#include "host_util.h"
 #include "kernels.h"
 #include "range_items.h"
 
@@ -138,9 +139,7 @@ int *device_status_block()
     return (int *)d;
 }
 
-// Faults the kernels of the current device have reported since the last look: sets the error text, clears the flags and
-// returns NFFT_HIP_EKERNEL (NFFT_HIP_EINVAL for a bad batch vector); 0 when there is none.
-static int take_pending_fault()
+int take_pending_fault()
 {
     int *host = status_host_blocks();
     const int dev = current_device();
@@ -295,7 +294,8 @@ struct Route {
     bool ci;                // several columns on a grid the column-innermost passes take
     bool toeplitz_fused;    // normal operator: both row passes and the product with K in one kernel (toeplitz_fused_chunk)
     int64_t C, ppc, total_planes, chunk_planes, half_cells;
-    int64_t off_plan, off_xs, off_xmax, off_grid, off_spec, off_col, off_work, off_tickets, work_bytes, total;
+    // the workspace carve; off_part and the `end` it continues from: forward_grad_route
+    int64_t off_plan, off_xs, off_xmax, off_grid, off_spec, off_col, off_work, off_tickets, off_part, work_bytes, end, total;
 
     const Geom &spread_geom() const { return owned ? go : g; }
     const PlanLayout &spread_layout() const { return owned ? Lo : L; }
@@ -303,6 +303,38 @@ struct Route {
     // the column-innermost passes need at least two groups of 16 planes
     FftRoute chunk_fft(int64_t np) const { return fft == kFftOwnPlanar && ci && np >= 32 ? kFftOwnCi : fft; }
 };
+
+// body(p0, np) for every chunk of planes [p0, p0 + np) of the route, in order; stops at the first non-zero return code
+template <class F>
+int for_chunks(const Route &r, F &&body)
+{
+    for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes)
+        if (int rc = body(p0, std::min(r.chunk_planes, r.total_planes - p0))) return rc;
+    return 0;
+}
+
+// bytes of a band spectrum [B, N^dim, C] complex64
+int64_t band_size_of(const nfft_hip_problem *p)
+{
+    int64_t band = p->batch_size * p->num_columns * 8;
+    for (int d = 0; d < p->dim; ++d) band *= p->N;
+    return band;
+}
+
+// The least workspace of a gradient gather, the partial gradients plus one chunk of grid planes: a missing workspace, or
+// one below this, is refused before the route makes its rocFFT plans.
+int64_t grad_least_bytes(const nfft_hip_problem *p, int real_output)
+{
+    const int64_t Cr = p->num_columns * (real_output ? 1 : 2);
+    return (Cr > 1 ? Cr * p->num_points * p->dim * 4 : 0) + problem_geom(p).cells * 4 * (real_output ? 1 : 2);
+}
+
+// fastsum geometry: every point within radius 1/4 (the kernel is only defined there)
+void quarter_ball(const nfft_hip_problem *in, nfft_hip_problem &out)
+{
+    out = *in;
+    out.flags |= NFFT_HIP_POINTS_IN_QUARTER_BALL;
+}
 
 // Plans and point-side kernels of a problem whose calls have Cr real planes per point set.
 Route plan_route(const nfft_hip_problem *p, int64_t Cr)
@@ -380,8 +412,7 @@ int make_route(const nfft_hip_problem *p, int ppc, RouteKind kind, Route &r, boo
     r.C = p->num_columns;
     r.ppc = ppc;
     r.total_planes = r.B * r.Cr;
-    r.half_cells = (int64_t)(r.g.M / 2 + 1);
-    for (int a = 0; a < 2; ++a) r.half_cells *= r.g.Ma[a];
+    r.half_cells = half_cells_of(r.g);
     const bool colfft = colfft_supported(r.g) && colfft_enabled();
     r.fft = !colfft ? kFftFull : rowfft_supported(r.g) ? kFftOwnPlanar : kFftRocRows;
     r.ci = r.C > 1 && colfft_ci_supported(r.g);
@@ -414,19 +445,20 @@ int make_route(const nfft_hip_problem *p, int ppc, RouteKind kind, Route &r, boo
         }
     }
     const bool need_xs = adjoint;
-    int64_t o = 0;
-    r.off_plan = o; o = align_up(o + r.plan_bytes, 256);
-    r.off_xs = o;   o = align_up(o + (need_xs ? (align_up(r.spread_layout().cap * r.Cr, 64) + 64) * 4 : 0), 256);
-    r.off_xmax = o; o = align_up(o + (need_xs ? r.total_planes * 4 : 0), 256);
+    Carve c;
+    r.off_plan = c.take(r.plan_bytes);
+    r.off_xs = c.take(need_xs ? (align_up(r.spread_layout().cap * r.Cr, 64) + 64) * 4 : 0);
+    r.off_xmax = c.take(need_xs ? r.total_planes * 4 : 0);
     // (the fused normal operator keeps its grid rows in LDS)
-    r.off_grid = o; o = align_up(o + (r.toeplitz_fused ? 0 : chunk * r.g.cells * 4), 256);
-    r.off_spec = o; o = align_up(o + chunk * r.half_cells * 8, 256);
+    r.off_grid = c.take(r.toeplitz_fused ? 0 : chunk * r.g.cells * 4);
+    r.off_spec = c.take(chunk * r.half_cells * 8);
     // (several columns: the column-innermost passes work on whole groups of 16 planes)
-    r.off_col = o;  o = align_up(o + (colfft ? colfft_scratch_bytes(r.g, r.C > 1 ? colfft_ci_planes(chunk) : chunk) : 0), 256);
-    r.off_work = o; o = align_up(o + r.work_bytes, 256);
+    r.off_col = c.take(colfft ? colfft_scratch_bytes(r.g, r.C > 1 ? colfft_ci_planes(chunk) : chunk) : 0);
+    r.off_work = c.take(r.work_bytes);
     // (the counters of the persistent work-list launches: every launch of the call in turn, on its stream)
-    r.off_tickets = o; o = align_up(o + kTicketPlanes * 4, 256);
-    r.total = o + 256;
+    r.off_tickets = c.take(kTicketPlanes * 4);
+    r.end = c.end();
+    r.total = c.total();
     return 0;
 }
 
@@ -788,23 +820,21 @@ int nfft_dbg_fft_stage(const nfft_hip_problem *p, int adjoint, int x_is_complex,
     if (int rc = stage_route(p, adjoint, x_is_complex, real_output, r, true)) return rc;
     if (r.total_planes == 0) return 0;
     if (!planes || !band) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    if (!workspace || workspace_bytes < r.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    char *ws = workspace_base(workspace, workspace_bytes, r.total);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
     float *grid = (float *)(ws + r.off_grid);
     float2 *spec = (float2 *)(ws + r.off_spec);
-    for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes) {
-        const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
+    return for_chunks(r, [&](int64_t p0, int64_t np) -> int {
         float *mine = (float *)planes + p0 * r.g.cells;
         const size_t bytes = (size_t)(np * r.g.cells * 4);
         if (adjoint) {
             NFFT_HIP_CHECK(hipMemcpyAsync(grid, mine, bytes, hipMemcpyDeviceToDevice, s));
-            if (int rc = fft_adjoint_chunk(r, ws, grid, spec, x_is_complex, real_output, p0, np, band, mult, mult_kind, s)) return rc;
-        } else {
-            if (int rc = fft_forward_chunk(r, ws, band, x_is_complex, real_output, p0, np, grid, spec, s)) return rc;
-            NFFT_HIP_CHECK(hipMemcpyAsync(mine, grid, bytes, hipMemcpyDeviceToDevice, s));
+            return fft_adjoint_chunk(r, ws, grid, spec, x_is_complex, real_output, p0, np, band, mult, mult_kind, s);
         }
-    }
-    return 0;
+        if (int rc = fft_forward_chunk(r, ws, band, x_is_complex, real_output, p0, np, grid, spec, s)) return rc;
+        NFFT_HIP_CHECK(hipMemcpyAsync(mine, grid, bytes, hipMemcpyDeviceToDevice, s));
+        return 0;
+    });
 }
 
 int64_t nfft_hip_spread_scratch_bytes(const nfft_hip_problem *p, int64_t real_columns)
@@ -866,8 +896,8 @@ static int adjoint_impl(const nfft_hip_problem *p, const float *pos, const int64
     if (r.total_planes == 0) return 0;
     if (!y) { set_error("Input mismatch: y is null"); return NFFT_HIP_EINVAL; }
     if (r.n > 0 && ((!pos && !ext_plan) || !x)) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    if (!workspace || workspace_bytes < r.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    char *ws = workspace_base(workspace, workspace_bytes, r.total);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
     const void *plan = ext_plan;
     float *xs = (float *)(ws + r.off_xs);
     unsigned *xmax = (unsigned *)(ws + r.off_xmax);
@@ -890,13 +920,11 @@ static int adjoint_impl(const nfft_hip_problem *p, const float *pos, const int64
         if (int rc = launch_gather_rows(r.spread_geom(), r.spread_layout(), r.spread_plan(plan), r.n, (const float *)x, r.Cr, xs, s))
             return rc;
     }
-    for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes) {
-        const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
+    return for_chunks(r, [&](int64_t p0, int64_t np) -> int {
         if (int rc = spread_chunk(r, plan, r.x_through_plan ? (const float *)x : nullptr, xs, xmax, p0, np, grid, tickets, s))
             return rc;
-        if (int rc = fft_adjoint_chunk(r, ws, grid, spec, x_is_complex, real_output, p0, np, y, mult, mult_kind, s)) return rc;
-    }
-    return 0;
+        return fft_adjoint_chunk(r, ws, grid, spec, x_is_complex, real_output, p0, np, y, mult, mult_kind, s);
+    });
 }
 
 static int forward_impl(const nfft_hip_problem *p, const float *pos, const int64_t *batch, const void *ext_plan,
@@ -916,8 +944,8 @@ static int forward_impl(const nfft_hip_problem *p, const float *pos, const int64
     if (int rc = make_route(p, real_output ? 1 : 2, kRouteForward, r)) return rc;
     if (r.total_planes == 0 || r.n == 0) return 0;
     if (!y || (!pos && !ext_plan) || !xhat) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    if (!workspace || workspace_bytes < r.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    char *ws = workspace_base(workspace, workspace_bytes, r.total);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
     const void *plan = ext_plan;
     float *grid = (float *)(ws + r.off_grid);
     float2 *spec = (float2 *)(ws + r.off_spec);
@@ -929,13 +957,11 @@ static int forward_impl(const nfft_hip_problem *p, const float *pos, const int64
         if (int rc = launch_plan_points(r.g, r.L, pos, batch, r.n, r.B, ws + r.off_plan, s)) return rc;
         plan = ws + r.off_plan;
     }
-    for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes) {
-        const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
+    return for_chunks(r, [&](int64_t p0, int64_t np) -> int {
         if (int rc = fft_forward_chunk(r, ws, xhat, x_is_complex, real_output, p0, np, grid, spec, s)) return rc;
         StageTimer t(kStageInterp, s);
-        if (int rc = gather_chunk(r, plan, grid, p0, np, (float *)y, tickets, s)) return rc;
-    }
-    return 0;
+        return gather_chunk(r, plan, grid, p0, np, (float *)y, tickets, s);
+    });
 }
 
 int nfft_hip_adjoint(const nfft_hip_problem *p, const float *pos, const void *x, int x_is_complex,
@@ -974,14 +1000,15 @@ int nfft_hip_forward_planned(const nfft_hip_problem *p, const void *plan, const 
 
 // ---- gradient with respect to the points ---------------------------------------------------------
 namespace {
-// Workspace of nfft_hip_forward_grad_points: the forward transform's (its route, unchanged) and, with two or more real
-// planes per point set, the per-plane partial gradients [Cr, n, dim] that grad_reduce sums in plane order.
-int forward_grad_route(const nfft_hip_problem *p, int real_output, Route &r, int64_t &off_part, int64_t &total)
+// Route of nfft_hip_forward_grad_points: the forward transform's, its workspace extended, with two or more real planes per
+// point set, by the per-plane partial gradients [Cr, n, dim] that grad_reduce sums in plane order.
+int forward_grad_route(const nfft_hip_problem *p, int real_output, Route &r)
 {
     if (int rc = make_route(p, real_output ? 1 : 2, kRouteForward, r)) return rc;
-    off_part = r.total - 256;  // (make_route's total is its aligned end + 256 bytes of slack for the base alignment)
-    const int64_t part = r.Cr > 1 ? align_up(r.Cr * r.n * p->dim * 4, 256) : 0;
-    total = off_part + part + 256;
+    Carve c(r.end);
+    r.off_part = c.take(r.Cr > 1 ? r.Cr * r.n * p->dim * 4 : 0);
+    r.end = c.end();
+    r.total = c.total();
     return 0;
 }
 } // namespace
@@ -991,9 +1018,8 @@ int64_t nfft_hip_forward_grad_workspace_bytes(const nfft_hip_problem *p, int x_i
     (void)x_is_complex;
     if (validate(p)) return -1;
     Route r;
-    int64_t off_part = 0, total = 0;
-    if (forward_grad_route(p, real_output, r, off_part, total)) return -1;
-    return total;
+    if (forward_grad_route(p, real_output, r)) return -1;
+    return r.total;
 }
 
 namespace {
@@ -1004,16 +1030,10 @@ int forward_grad_impl(const nfft_hip_problem *p, const void *plan, const void *x
 {
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate(p)) return rc;
-    if (p->num_points > 0 && p->num_columns > 0) {
-        // a missing workspace, or one below the partial gradients plus one chunk of grid planes, is refused before the
-        // route makes its rocFFT plans
-        const int64_t Cr = p->num_columns * (real_output ? 1 : 2);
-        const int64_t least = (Cr > 1 ? Cr * p->num_points * p->dim * 4 : 0) + problem_geom(p).cells * 4 * (real_output ? 1 : 2);
-        if (!workspace || workspace_bytes < least) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    }
+    if (p->num_points > 0 && p->num_columns > 0 && !workspace_base(workspace, workspace_bytes, grad_least_bytes(p, real_output)))
+        return NFFT_HIP_EWORKSPACE;
     Route r;
-    int64_t off_part = 0, total = 0;
-    if (int rc = forward_grad_route(p, real_output, r, off_part, total)) return rc;
+    if (int rc = forward_grad_route(p, real_output, r)) return rc;
     if (r.n == 0) return 0;
     if (!dpos) { set_error("Input mismatch: dpos is null"); return NFFT_HIP_EINVAL; }
     if (r.total_planes == 0) {  // no columns: the transform is empty and so is its gradient
@@ -1021,23 +1041,19 @@ int forward_grad_impl(const nfft_hip_problem *p, const void *plan, const void *x
         return 0;
     }
     if (!plan || !xhat || !w) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    if (!workspace || workspace_bytes < total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    char *ws = workspace_base(workspace, workspace_bytes, r.total);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
     float *grid = (float *)(ws + r.off_grid);
     float2 *spec = (float2 *)(ws + r.off_spec);
-    float *part = r.Cr > 1 ? (float *)(ws + off_part) : dpos;  // one plane per set: the kernel writes dpos itself
-    for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes) {
-        const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
+    float *part = r.Cr > 1 ? (float *)(ws + r.off_part) : dpos;  // one plane per set: the kernel writes dpos itself
+    const int rc = for_chunks(r, [&](int64_t p0, int64_t np) -> int {
         if (int rc = fft_forward_chunk(r, ws, xhat, x_is_complex, real_output, p0, np, grid, spec, s)) return rc;
         StageTimer t(kStageInterp, s);
-        if (y) {
-            if (int rc = launch_interp_value_grad(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, w, part, y, s)) return rc;
-        } else {
-            if (int rc = launch_interp_grad(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, w, part, s)) return rc;
-        }
-    }
-    if (r.Cr > 1) return launch_grad_reduce(part, r.n * p->dim, r.Cr, dpos, s);
-    return 0;
+        if (y) return launch_interp_value_grad(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, w, part, y, s);
+        return launch_interp_grad(r.g, r.L, plan, grid, r.n, r.Cr, p0, np, w, part, s);
+    });
+    if (rc || r.Cr < 2) return rc;
+    return launch_grad_reduce(part, r.n * p->dim, r.Cr, dpos, s);
 }
 } // namespace
 
@@ -1064,21 +1080,17 @@ namespace {
 // an adjoint of the same problem (u = omega v_a as its input: complex unless real_output) + u [n, Cr] + its output
 // [B, N^dim, C] complex.
 struct HvpCarve {
-    int64_t grad_total, adj_total, off_u, off_y, total;
+    Route grad, adj;
+    int64_t off_u, off_y, total;
 };
 int hvp_carve(const nfft_hip_problem *p, int real_output, HvpCarve &h)
 {
-    Route r;
-    int64_t off_part = 0;
-    if (int rc = forward_grad_route(p, real_output, r, off_part, h.grad_total)) return rc;
-    Route ra;
-    if (int rc = make_route(p, real_output ? 1 : 2, kRouteAdjoint, ra)) return rc;
-    h.adj_total = ra.total;
-    int64_t spec = p->batch_size * p->num_columns;
-    for (int a = 0; a < p->dim; ++a) spec *= p->N;
-    h.off_u = align_up(h.adj_total, 256);
-    h.off_y = align_up(h.off_u + p->num_points * r.Cr * 4, 256);
-    h.total = std::max(h.grad_total, h.off_y + spec * 8 + 256);
+    if (int rc = forward_grad_route(p, real_output, h.grad)) return rc;
+    if (int rc = make_route(p, real_output ? 1 : 2, kRouteAdjoint, h.adj)) return rc;
+    Carve c(h.adj.total);
+    h.off_u = c.take(p->num_points * h.adj.Cr * 4);
+    h.off_y = c.take(band_size_of(p));
+    h.total = std::max(h.grad.total, c.total());
     return 0;
 }
 } // namespace
@@ -1102,67 +1114,54 @@ int nfft_hip_forward_grad_points_backward_planned(const nfft_hip_problem *p, con
     hipStream_t s = (hipStream_t)stream;
     if (!dxhat && !dw && !dpos) return 0;
     const int64_t n = p->num_points, C = p->num_columns, Cr = C * (real_output ? 1 : 2);
-    int64_t spec = p->batch_size * C;
-    for (int a = 0; a < p->dim; ++a) spec *= p->N;
     if (n == 0 || C == 0) {  // no points or no columns: G is empty or identically zero, and so is every derivative of it
-        if (dxhat) NFFT_HIP_CHECK(hipMemsetAsync(dxhat, 0, (size_t)(spec * (x_is_complex ? 8 : 4)), s));
+        if (dxhat) NFFT_HIP_CHECK(hipMemsetAsync(dxhat, 0, (size_t)(band_size_of(p) / (x_is_complex ? 1 : 2)), s));
         if (dpos) NFFT_HIP_CHECK(hipMemsetAsync(dpos, 0, (size_t)(n * p->dim * 4), s));
         return 0;  // (dw has n * Cr = 0 elements)
     }
     if (!plan || !xhat || !v || ((dpos || dxhat) && !w)) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    {
-        // a missing workspace, or one below the partial gradients plus one chunk of grid planes, is refused before the
-        // routes make their rocFFT plans (as in forward_grad_impl)
-        const int64_t least = (Cr > 1 ? Cr * n * p->dim * 4 : 0) + problem_geom(p).cells * 4 * (real_output ? 1 : 2);
-        if (!workspace || workspace_bytes < least) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    }
+    if (!workspace_base(workspace, workspace_bytes, grad_least_bytes(p, real_output))) return NFFT_HIP_EWORKSPACE;
     HvpCarve h;
     if (int rc = hvp_carve(p, real_output, h)) return rc;
-    if (workspace_bytes < h.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    char *ws = workspace_base(workspace, workspace_bytes, h.total);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
     if (dw || dpos) {
         // the moment gather on the forward transform's grid, chunk by chunk as the gradient gather runs
-        Route r;
-        int64_t off_part = 0, total = 0;
-        if (int rc = forward_grad_route(p, real_output, r, off_part, total)) return rc;
+        const Route &r = h.grad;
         float *grid = (float *)(ws + r.off_grid);
         float2 *spec_buf = (float2 *)(ws + r.off_spec);
-        float *part = !dpos ? nullptr : r.Cr > 1 ? (float *)(ws + off_part) : dpos;
-        for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes) {
-            const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
-            if (int rc = fft_forward_chunk(r, ws, xhat, x_is_complex, real_output, p0, np, grid, spec_buf, s)) return rc;
-            StageTimer t(kStageInterp, s);
-            if (int rc = launch_interp_hvp(r.g, r.L, plan, grid, n, r.Cr, p0, np, w, v, dw, part, s)) return rc;
-        }
+        float *part = !dpos ? nullptr : r.Cr > 1 ? (float *)(ws + r.off_part) : dpos;
+        if (int rc = for_chunks(r, [&](int64_t p0, int64_t np) -> int {
+                if (int rc = fft_forward_chunk(r, ws, xhat, x_is_complex, real_output, p0, np, grid, spec_buf, s)) return rc;
+                StageTimer t(kStageInterp, s);
+                return launch_interp_hvp(r.g, r.L, plan, grid, n, r.Cr, p0, np, w, v, dw, part, s);
+            }))
+            return rc;
         if (dpos && r.Cr > 1)
             if (int rc = launch_grad_reduce(part, n * p->dim, r.Cr, dpos, s)) return rc;
     }
     if (dxhat) {
-        Route ra;
-        if (int rc = make_route(p, real_output ? 1 : 2, kRouteAdjoint, ra)) return rc;
+        const Route &ra = h.adj;
         if (hvp_fused_dxhat(ra)) {
             // the derivative spreading of w, then the adjoint's own FFT stage and roll-off, chunk by chunk
             float *grid = (float *)(ws + ra.off_grid);
             float2 *spec_buf = (float2 *)(ws + ra.off_spec);
-            for (int64_t p0 = 0; p0 < ra.total_planes; p0 += ra.chunk_planes) {
-                const int64_t np = std::min(ra.chunk_planes, ra.total_planes - p0);
+            return for_chunks(ra, [&](int64_t p0, int64_t np) -> int {
                 { StageTimer t(kStageZero, s); NFFT_HIP_CHECK(hipMemsetAsync(grid, 0, (size_t)(np * ra.g.cells * 4), s)); }
                 {
                     StageTimer t(kStageSpread, s);
                     if (int rc = launch_spread_deriv(ra.g, ra.L, plan, w, v, n, ra.Cr, p0, np, grid, s)) return rc;
                 }
-                if (int rc = fft_adjoint_chunk(ra, ws, grid, spec_buf, real_output ? 0 : 1, x_is_complex ? 0 : 1, p0, np, dxhat,
-                                               nullptr, 0, s))
-                    return rc;
-            }
-            return 0;
+                return fft_adjoint_chunk(ra, ws, grid, spec_buf, real_output ? 0 : 1, x_is_complex ? 0 : 1, p0, np, dxhat,
+                                         nullptr, 0, s);
+            });
         }
         // sum_a 2 pi i k_a adjoint(omega v_a), axes in order (hvp_spectral.hip)
         float *u = (float *)(ws + h.off_u);
         void *y = ws + h.off_y;
         for (int a = 0; a < p->dim; ++a) {
             if (int rc = launch_hvp_stage(w, v, n, Cr, p->dim, a, u, s)) return rc;
-            if (int rc = adjoint_impl(p, nullptr, nullptr, plan, u, real_output ? 0 : 1, 0, y, ws, h.adj_total, stream)) return rc;
+            if (int rc = adjoint_impl(p, nullptr, nullptr, plan, u, real_output ? 0 : 1, 0, y, ws, ra.total, stream)) return rc;
             if (int rc = launch_hvp_combine(y, p->batch_size, p->N, p->dim, C, a, a > 0, x_is_complex, dxhat, s)) return rc;
         }
     }
@@ -1173,15 +1172,8 @@ int nfft_hip_forward_grad_points_backward_planned(const nfft_hip_problem *p, con
 namespace {
 struct FastsumCarve {
     Route src, tgt;  // adjoint at the sources, forward transform at the targets
-    int64_t band_size, band_bytes, plan_s, plan_t, inner, off_band, off_plan_s, off_plan_t, off_inner, total;
+    int64_t band_size, inner, off_band, off_plan_s, off_plan_t, off_inner, total;
 };
-// bytes of a band spectrum [B, N^dim, C] complex64
-int64_t band_size_of(const nfft_hip_problem *p)
-{
-    int64_t band = p->batch_size * p->num_columns * 8;
-    for (int d = 0; d < p->dim; ++d) band *= p->N;
-    return band;
-}
 int fastsum_check(const nfft_hip_problem *src, const nfft_hip_problem *tgt)
 {
     if (int rc = validate(src)) return rc;
@@ -1199,16 +1191,13 @@ int fastsum_carve(const nfft_hip_problem *src, const nfft_hip_problem *tgt, int 
     if (int rc = make_route(src, x_is_complex ? 2 : 1, kRouteAdjoint, f.src)) return rc;
     if (int rc = make_route(tgt, x_is_complex ? 2 : 1, kRouteForward, f.tgt)) return rc;
     f.band_size = band_size_of(src);
-    f.band_bytes = align_up(f.band_size, 256);
-    f.plan_s = own_plans ? align_up(f.src.plan_bytes, 256) : 0;
-    f.plan_t = own_plans && !shared_points ? align_up(f.tgt.plan_bytes, 256) : 0;
     f.inner = std::max(f.src.total, f.tgt.total);
-    int64_t o = 0;
-    f.off_band = o;   o += f.band_bytes;
-    f.off_plan_s = o; o += f.plan_s;
-    f.off_plan_t = o; o += f.plan_t;
-    f.off_inner = o;  o += f.inner;
-    f.total = o + 256;
+    Carve c;
+    f.off_band = c.take(f.band_size);
+    f.off_plan_s = c.take(own_plans ? f.src.plan_bytes : 0);
+    f.off_plan_t = c.take(own_plans && !shared_points ? f.tgt.plan_bytes : 0);
+    f.off_inner = c.take(f.inner);
+    f.total = c.total();
     return 0;
 }
 int fastsum_impl(const nfft_hip_problem *src_in, const float *sources, const int64_t *source_batch,
@@ -1219,9 +1208,9 @@ int fastsum_impl(const nfft_hip_problem *src_in, const float *sources, const int
 {
     if (!src_in || !tgt_in) { set_error("Input mismatch: null problem"); return NFFT_HIP_EINVAL; }
     // fastsum geometry: every point within radius 1/4 (the kernel is only defined there)
-    nfft_hip_problem src_q = *src_in, tgt_q = *tgt_in;
-    src_q.flags |= NFFT_HIP_POINTS_IN_QUARTER_BALL;
-    tgt_q.flags |= NFFT_HIP_POINTS_IN_QUARTER_BALL;
+    nfft_hip_problem src_q, tgt_q;
+    quarter_ball(src_in, src_q);
+    quarter_ball(tgt_in, tgt_q);
     const nfft_hip_problem *src = &src_q, *tgt = &tgt_q;
     if (int rc = fastsum_check(src, tgt)) return rc;
     const bool own_plans = source_plan == nullptr;
@@ -1231,28 +1220,17 @@ int fastsum_impl(const nfft_hip_problem *src_in, const float *sources, const int
     if (int rc = fastsum_carve(src, tgt, x_is_complex, own_plans, shared, f)) return rc;
     if (tgt->num_points == 0 || src->num_columns == 0) return 0;
     if (!coeffs || !y) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    if (!workspace || workspace_bytes < f.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    char *ws = workspace_base(workspace, workspace_bytes, f.total);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     // problems whose grid fits one workgroup's LDS: adjoint (with the kernel's coefficients folded into its roll-off)
     // and forward transform are one fused kernel each on the caller's points -- no plans (smallgrid.hip)
     const bool fused1d = own_plans && small_grid_route(src) && small_grid_route(tgt);
-    if (fused1d) {
-        if (src->num_points > 0 && !sources) { set_error("Input mismatch: sources is null"); return NFFT_HIP_EINVAL; }
-        if (!targets) { set_error("Input mismatch: targets is null"); return NFFT_HIP_EINVAL; }
-        // (band_out: the caller keeps the band spectrum, the carve's band is not used)
-        void *band1 = band_out ? band_out : ws + f.off_band;
-        if (src->num_points == 0) {
-            NFFT_HIP_CHECK(hipMemsetAsync(band1, 0, (size_t)f.band_size, s));
-        } else {
-            if (int rc = adjoint_impl(src, sources, source_batch, nullptr, x, x_is_complex, 0, band1, nullptr, 0, stream,
-                                      coeffs, coeffs_are_complex ? 2 : 1)) return rc;
-        }
-        return forward_impl(tgt, targets, target_batch, nullptr, band1, 1, x_is_complex ? 0 : 1, y, nullptr, 0, stream);
-    }
     if (own_plans) {
         if (src->num_points > 0 && !sources) { set_error("Input mismatch: sources is null"); return NFFT_HIP_EINVAL; }
         if (!targets) { set_error("Input mismatch: targets is null"); return NFFT_HIP_EINVAL; }
+    }
+    if (own_plans && !fused1d) {
         {
             StageTimer t(kStagePlan, s);
             if (int rc = build_plans(f.src, sources, source_batch, ws + f.off_plan_s, s)) return rc;
@@ -1264,18 +1242,23 @@ int fastsum_impl(const nfft_hip_problem *src_in, const float *sources, const int
             if (int rc = build_plans(f.tgt, targets, target_batch, ws + f.off_plan_t, s)) return rc;
             target_plan = ws + f.off_plan_t;
         }
+        sources = targets = nullptr;  // (the transforms run on the plans)
+        source_batch = target_batch = nullptr;
     }
+    // (the fused kernels run on the caller's points and need no workspace)
+    void *inner = fused1d ? nullptr : ws + f.off_inner;
+    const int64_t inner_bytes = fused1d ? 0 : f.inner;
+    // (band_out: the caller keeps the band spectrum, the carve's band is not used)
     void *band = band_out ? band_out : ws + f.off_band;
     if (src->num_points == 0) {
         NFFT_HIP_CHECK(hipMemsetAsync(band, 0, (size_t)f.band_size, s));
     } else {
         // adjoint of the sources; the kernel's Fourier coefficients are multiplied in by the last spectral pass
-        if (int rc = adjoint_impl(src, nullptr, nullptr, source_plan, x, x_is_complex, 0, band, ws + f.off_inner, f.inner,
-                                  stream, coeffs, coeffs_are_complex ? 2 : 1)) return rc;
+        if (int rc = adjoint_impl(src, sources, source_batch, source_plan, x, x_is_complex, 0, band, inner, inner_bytes, stream,
+                                  coeffs, coeffs_are_complex ? 2 : 1)) return rc;
     }
     // forward transform at the targets; real coefficients give a real result (core_cuda.cu:817-821)
-    return forward_impl(tgt, nullptr, nullptr, target_plan, band, 1, x_is_complex ? 0 : 1, y, ws + f.off_inner, f.inner,
-                        stream);
+    return forward_impl(tgt, targets, target_batch, target_plan, band, 1, x_is_complex ? 0 : 1, y, inner, inner_bytes, stream);
 }
 } // namespace
 
@@ -1283,9 +1266,9 @@ int64_t nfft_hip_fastsum_workspace_bytes(const nfft_hip_problem *src, const nfft
                                          int shared_points, int planned)
 {
     if (!src || !tgt) return -1;
-    nfft_hip_problem s = *src, t = *tgt;
-    s.flags |= NFFT_HIP_POINTS_IN_QUARTER_BALL;
-    t.flags |= NFFT_HIP_POINTS_IN_QUARTER_BALL;
+    nfft_hip_problem s, t;
+    quarter_ball(src, s);
+    quarter_ball(tgt, t);
     if (fastsum_check(&s, &t)) return -1;
     FastsumCarve f;
     if (fastsum_carve(&s, &t, x_is_complex, planned == 0, shared_points != 0, f)) return -1;
@@ -1347,20 +1330,15 @@ int fastsum_grad_carve(const nfft_hip_problem *src, const nfft_hip_problem *tgt,
     f.inner = adj.total;
     for (const nfft_hip_problem *p : {src, tgt}) {
         Route r;
-        int64_t off_part = 0, total = 0;
-        if (int rc = forward_grad_route(p, x_is_complex ? 0 : 1, r, off_part, total)) return rc;
-        f.inner = std::max(f.inner, total);
+        if (int rc = forward_grad_route(p, x_is_complex ? 0 : 1, r)) return rc;
+        f.inner = std::max(f.inner, r.total);
     }
     f.band_size = band_size_of(src);
-    f.off_h = 0;
-    f.off_inner = align_up(f.band_size, 256);
-    f.total = f.off_inner + f.inner + 256;
+    Carve c;
+    f.off_h = c.take(f.band_size);
+    f.off_inner = c.take(f.inner);
+    f.total = c.total();
     return 0;
-}
-void quarter_ball(const nfft_hip_problem *in, nfft_hip_problem &out)
-{
-    out = *in;
-    out.flags |= NFFT_HIP_POINTS_IN_QUARTER_BALL;
 }
 } // namespace
 
@@ -1402,7 +1380,7 @@ int nfft_hip_fastsum_backward_planned(const nfft_hip_problem *src_in, const void
     if (work) {
         // refused before any route makes its rocFFT plans: the grid H plus one grid plane per real plane of a column
         const int64_t least = align_up(band_size_of(src), 256) + problem_geom(src).cells * 4 * (x_is_complex ? 2 : 1);
-        if (!workspace || workspace_bytes < least) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+        if (!workspace_base(workspace, workspace_bytes, least)) return NFFT_HIP_EWORKSPACE;
     }
     // nothing to gather (no columns, or one side empty: the sum and every gradient of it are zero)
     if (!work) {
@@ -1417,8 +1395,8 @@ int nfft_hip_fastsum_backward_planned(const nfft_hip_problem *src_in, const void
     }
     FastsumGradCarve f;
     if (int rc = fastsum_grad_carve(src, tgt, x_is_complex, f)) return rc;
-    if (!workspace || workspace_bytes < f.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    char *ws = workspace_base(workspace, workspace_bytes, f.total);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
     void *inner = ws + f.off_inner;
     if (sources_side) {
         // H = coeffs * A_t(dy): the adjoint at the targets with the coefficients folded into its roll-off, as fastsum_impl
@@ -1450,18 +1428,17 @@ namespace {
 // Workspace of the kernel-grid set-up: the half spectrum of K for all point sets + rocFFT's work area.
 struct ToeplitzKernelCarve {
     Geom g;
-    int64_t half_cells, off_spec, off_work, work_bytes, total;
+    int64_t off_spec, off_work, work_bytes, total;
 };
 int toeplitz_kernel_carve(const nfft_hip_problem *p, ToeplitzKernelCarve &c)
 {
     c.g = make_geom(p->dim, p->N, p->m);
-    c.half_cells = c.g.M / 2 + 1;
-    for (int a = 0; a < 2; ++a) c.half_cells *= c.g.Ma[a];
     c.work_bytes = fft_work_bytes(kC2R, c.g.dim, c.g.M, p->batch_size);
     if (c.work_bytes < 0) return NFFT_HIP_EFFT;
-    c.off_spec = 0;
-    c.off_work = align_up(p->batch_size * c.half_cells * 8, 256);
-    c.total = c.off_work + align_up(c.work_bytes, 256) + 256;
+    Carve carve;
+    c.off_spec = carve.take(p->batch_size * half_cells_of(c.g) * 8);
+    c.off_work = carve.take(c.work_bytes);
+    c.total = carve.total();
     return 0;
 }
 bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; }
@@ -1485,8 +1462,8 @@ int nfft_hip_toeplitz_kernel(const nfft_hip_problem *p, const void *t, float *K,
     if (!t || !K) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
     ToeplitzKernelCarve c;
     if (int rc = toeplitz_kernel_carve(p, c)) return rc;
-    if (!workspace || workspace_bytes < c.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    char *ws = workspace_base(workspace, workspace_bytes, c.total);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float2 *spec = (float2 *)(ws + c.off_spec);
     if (int rc = launch_toeplitz_spectrum(c.g, (const float2 *)t, p->batch_size, spec, s)) return rc;
@@ -1513,488 +1490,20 @@ int nfft_hip_toeplitz_apply(const nfft_hip_problem *p, const float *K, const voi
     // the grid of x is complex whether x is or not: two real planes per column through both FFT stages
     Route r;
     if (int rc = make_route(p, 2, kRouteToeplitz, r)) return rc;
-    if (!workspace || workspace_bytes < r.total) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
+    char *ws = workspace_base(workspace, workspace_bytes, r.total);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float *grid = (float *)(ws + r.off_grid);
     float2 *spec = (float2 *)(ws + r.off_spec);
-    for (int64_t p0 = 0; p0 < r.total_planes; p0 += r.chunk_planes) {
-        const int64_t np = std::min(r.chunk_planes, r.total_planes - p0);
-        if (r.toeplitz_fused) {
-            if (int rc = toeplitz_fused_chunk(r, ws, xhat, x_is_complex, K, p0, np, spec, y, s)) return rc;
-            continue;
-        }
+    return for_chunks(r, [&](int64_t p0, int64_t np) -> int {
+        if (r.toeplitz_fused) return toeplitz_fused_chunk(r, ws, xhat, x_is_complex, K, p0, np, spec, y, s);
         if (int rc = fft_forward_chunk(r, ws, xhat, x_is_complex, 0, p0, np, grid, spec, s)) return rc;
         {
             StageTimer t(kStageMultiply, s);
             if (int rc = launch_toeplitz_multiply(r.g, grid, K, r.Cr, p0, np, s)) return rc;
         }
-        if (int rc = fft_adjoint_chunk(r, ws, grid, spec, 1, 0, p0, np, y, nullptr, 0, s)) return rc;
-    }
-    return 0;
+        return fft_adjoint_chunk(r, ws, grid, spec, 1, 0, p0, np, y, nullptr, 0, s);
+    });
 }
 
 } // extern "C"
-
-// ---- near field of the fast summation for singular kernels ------------------------------------
-namespace {
-constexpr int64_t kNearMaxCells = int64_t(1) << 20;
-
-int validate_nearfield(const nfft_hip_nearfield_problem *p)
-{
-    if (!p) { set_error("Input mismatch: null problem"); return NFFT_HIP_EINVAL; }
-    if (p->dim < 1 || p->dim > 3) { set_error("Input mismatch: dim must be 1, 2 or 3"); return NFFT_HIP_EINVAL; }
-    if (p->kernel < 0 || p->kernel > NFFT_HIP_KERNEL_LAPLACIAN_RBF) { set_error("Input mismatch: unknown kernel"); return NFFT_HIP_EINVAL; }
-    if (p->poly_terms < 1 || p->poly_terms > 8) { set_error("Input mismatch: poly_terms must be in 1..8"); return NFFT_HIP_EINVAL; }
-    if (p->num_sources < 0 || p->num_targets < 0 || p->num_columns < 0 || p->batch_size < 1) {
-        set_error("Input mismatch: negative size");
-        return NFFT_HIP_EINVAL;
-    }
-    if (p->num_sources >= (int64_t(1) << 31) || p->num_targets >= (int64_t(1) << 31)) {
-        set_error("Input mismatch: too many points");
-        return NFFT_HIP_EINVAL;
-    }
-    if (!(p->eps_I > 0.0) || !(p->eps_I < 0.5)) { set_error("Input mismatch: eps_I must lie in (0, 1/2)"); return NFFT_HIP_EINVAL; }
-    if (p->cells_per_axis < 1 || 0.5 / p->cells_per_axis < p->eps_I * (1.0 - 1e-12)) {
-        set_error("Input mismatch: cells must have an edge 1 / (2 cells_per_axis) >= eps_I");
-        return NFFT_HIP_EINVAL;
-    }
-    int64_t cells = p->batch_size;
-    for (int a = 0; a < p->dim && cells <= kNearMaxCells; ++a) cells *= p->cells_per_axis;
-    if (cells > kNearMaxCells && p->cells_per_axis > 1) { set_error("Input mismatch: too many cells"); return NFFT_HIP_EINVAL; }
-    if (cells >= (int64_t(1) << 30)) { set_error("Input mismatch: too many point sets"); return NFFT_HIP_EINVAL; }
-    const bool needs_c = p->kernel >= NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC;
-    if (!(p->c >= 0.0) || (needs_c && !(p->c > 0.0))) { set_error("Input mismatch: the shape parameter c must be positive"); return NFFT_HIP_EINVAL; }
-    for (int e = 0; e < p->poly_terms; ++e)
-        if (!(p->poly[e] == p->poly[e]) || p->poly[e] > 3e38 || p->poly[e] < -3e38) {
-            set_error("Input mismatch: poly is not finite");
-            return NFFT_HIP_EINVAL;
-        }
-    return 0;
-}
-
-} // namespace
-
-extern "C" {
-
-int64_t nfft_hip_nearfield_cells(int32_t dim, double eps_I, int64_t batch_size)
-{
-    if (dim < 1 || dim > 3 || !(eps_I > 0.0) || !(eps_I < 0.5) || batch_size < 1) {
-        set_error("Input mismatch: nearfield cells need dim in 1..3, eps_I in (0, 1/2) and batch_size >= 1");
-        return -1;
-    }
-    int64_t G = (int64_t)std::min(0.5 / eps_I, 1048576.0);
-    while (G > 1 && 0.5 / (double)G < eps_I) --G;  // (the quotient may have been rounded up)
-    auto cells = [&](int64_t g) { int64_t c = batch_size; for (int a = 0; a < dim; ++a) c *= g; return c; };
-    while (G > 1 && cells(G) > kNearMaxCells) G = G > 64 ? G / 2 : G - 1;
-    return G < 1 ? 1 : G;
-}
-
-int64_t nfft_hip_nearfield_workspace_bytes(const nfft_hip_nearfield_problem *p)
-{
-    if (validate_nearfield(p)) return -1;
-    return nearfield_item_slots(p) * (int64_t)sizeof(int2) + 256;
-}
-
-int nfft_hip_nearfield(const nfft_hip_nearfield_problem *p, const float *sources, const float *xr,
-                       const int32_t *source_start, const float *targets, const int64_t *target_index,
-                       const int32_t *target_start, float *z, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
-    if (int rc = validate_nearfield(p)) return rc;
-    if (p->num_targets == 0 || p->num_columns == 0) return 0;
-    if (!z) { set_error("Input mismatch: z is null"); return NFFT_HIP_EINVAL; }
-    hipStream_t s = (hipStream_t)stream;
-    if (p->num_sources == 0) {
-        NFFT_HIP_CHECK(hipMemsetAsync(z, 0, (size_t)(p->num_targets * p->num_columns) * sizeof(float), s));
-        return 0;
-    }
-    if (!sources || !xr || !source_start || !targets || !target_index || !target_start) {
-        set_error("Input mismatch: null input");
-        return NFFT_HIP_EINVAL;
-    }
-    const int64_t need = nearfield_item_slots(p) * (int64_t)sizeof(int2) + 256;
-    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
-    return launch_nearfield(p, sources, xr, source_start, targets, target_index, target_start, z, ws, s);
-}
-
-// ---- its gradient at the targets and the transpose ---------------------------------------------
-static int validate_nearfield_gradient(const nfft_hip_nearfield_problem *p)
-{
-    if (int rc = validate_nearfield(p)) return rc;
-    if (p->poly_terms < 2) {
-        set_error("Input mismatch: the near field's gradient needs poly_terms >= 2 (K_R must be differentiable at eps_I)");
-        return NFFT_HIP_EINVAL;
-    }
-    return 0;
-}
-
-int64_t nfft_hip_nearfield_gradient_workspace_bytes(const nfft_hip_nearfield_problem *p)
-{
-    if (validate_nearfield_gradient(p)) return -1;
-    return nearfield_item_slots(p) * (int64_t)sizeof(int2) + 256;
-}
-
-int nfft_hip_nearfield_gradient(const nfft_hip_nearfield_problem *p, int32_t transpose, const double *gradient_poly,
-                                const float *sources, const float *xr, const int32_t *source_start, const float *targets,
-                                const int64_t *target_index, const int32_t *target_start, float *out, void *workspace,
-                                int64_t workspace_bytes, void *stream)
-{
-    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
-    if (int rc = validate_nearfield_gradient(p)) return rc;
-    if (transpose != 0 && transpose != 1) { set_error("Input mismatch: transpose must be 0 or 1"); return NFFT_HIP_EINVAL; }
-    if (!gradient_poly) { set_error("Input mismatch: gradient_poly is null"); return NFFT_HIP_EINVAL; }
-    for (int e = 0; e < p->poly_terms - 1; ++e)
-        if (!(gradient_poly[e] == gradient_poly[e]) || gradient_poly[e] > 3e38 || gradient_poly[e] < -3e38) {
-            set_error("Input mismatch: gradient_poly is not finite");
-            return NFFT_HIP_EINVAL;
-        }
-    if (p->num_targets == 0 || p->num_columns == 0) return 0;
-    if (!out) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
-    hipStream_t s = (hipStream_t)stream;
-    if (p->num_sources == 0) {
-        const int64_t row = transpose ? p->num_columns : p->dim * p->num_columns;
-        NFFT_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(p->num_targets * row) * sizeof(float), s));
-        return 0;
-    }
-    if (!sources || !xr || !source_start || !targets || !target_index || !target_start) {
-        set_error("Input mismatch: null input");
-        return NFFT_HIP_EINVAL;
-    }
-    const int64_t need = nearfield_item_slots(p) * (int64_t)sizeof(int2) + 256;
-    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
-    return launch_nearfield_gradient(p, transpose, gradient_poly, sources, xr, source_start, targets, target_index,
-                                     target_start, out, ws, s);
-}
-
-// ---- its gradient with respect to the points ----------------------------------------------------
-int64_t nfft_hip_nearfield_point_gradient_workspace_bytes(const nfft_hip_nearfield_problem *p)
-{
-    if (validate_nearfield_gradient(p)) return -1;
-    return nearfield_item_slots(p) * (int64_t)sizeof(int2) + 256;
-}
-
-int nfft_hip_nearfield_point_gradient(const nfft_hip_nearfield_problem *p, int32_t symmetric, const double *gradient_poly,
-                                      const float *streamed, const float *streamed_values, const int32_t *streamed_start,
-                                      const float *output, const float *output_values, const int64_t *output_index,
-                                      const int32_t *output_start, float *out, void *workspace, int64_t workspace_bytes,
-                                      void *stream)
-{
-    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
-    if (int rc = validate_nearfield_gradient(p)) return rc;
-    if (symmetric != 0 && symmetric != 1) { set_error("Input mismatch: symmetric must be 0 or 1"); return NFFT_HIP_EINVAL; }
-    if (symmetric && p->num_sources != p->num_targets) {
-        set_error("Input mismatch: a symmetric sweep needs one point set on both sides");
-        return NFFT_HIP_EINVAL;
-    }
-    if (!gradient_poly) { set_error("Input mismatch: gradient_poly is null"); return NFFT_HIP_EINVAL; }
-    for (int e = 0; e < p->poly_terms - 1; ++e)
-        if (!(gradient_poly[e] == gradient_poly[e]) || gradient_poly[e] > 3e38 || gradient_poly[e] < -3e38) {
-            set_error("Input mismatch: gradient_poly is not finite");
-            return NFFT_HIP_EINVAL;
-        }
-    if (p->num_targets == 0 || p->num_columns == 0) return 0;
-    if (!out) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
-    hipStream_t s = (hipStream_t)stream;
-    if (p->num_sources == 0) {
-        NFFT_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(p->num_targets * p->dim) * sizeof(float), s));
-        return 0;
-    }
-    if (!streamed || !streamed_values || !streamed_start || !output || !output_values || !output_index || !output_start) {
-        set_error("Input mismatch: null input");
-        return NFFT_HIP_EINVAL;
-    }
-    const int64_t need = nearfield_item_slots(p) * (int64_t)sizeof(int2) + 256;
-    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
-    return launch_nearfield_point_gradient(p, symmetric, gradient_poly, streamed, streamed_values, streamed_start, output,
-                                           output_values, output_index, output_start, out, ws, s);
-}
-
-}  // extern "C"
-
-// ---- near part of the Ewald sum for the periodic 1/r ------------------------------------------
-namespace {
-
-int validate_ewald(const nfft_hip_ewald_problem *p)
-{
-    if (!p) { set_error("Input mismatch: null problem"); return NFFT_HIP_EINVAL; }
-    if (p->with_field != 0 && p->with_field != 1) { set_error("Input mismatch: with_field must be 0 or 1"); return NFFT_HIP_EINVAL; }
-    if (p->num_points < 0 || p->num_columns < 0 || p->batch_size < 1) {
-        set_error("Input mismatch: negative size");
-        return NFFT_HIP_EINVAL;
-    }
-    if (p->num_points >= (int64_t(1) << 31)) { set_error("Input mismatch: too many points"); return NFFT_HIP_EINVAL; }
-    if (!(p->alpha > 0.0) || !(p->alpha < 1e18)) { set_error("Input mismatch: alpha must be positive and finite"); return NFFT_HIP_EINVAL; }
-    if (!(p->r_cut > 0.0) || !(p->r_cut <= 1.0 / 3.0)) { set_error("Input mismatch: r_cut must lie in (0, 1/3]"); return NFFT_HIP_EINVAL; }
-    if (p->cells_per_axis < 3 || 1.0 / p->cells_per_axis < p->r_cut * (1.0 - 1e-12)) {
-        set_error("Input mismatch: cells must be at least 3 per axis with an edge 1 / cells_per_axis >= r_cut");
-        return NFFT_HIP_EINVAL;
-    }
-    if (p->batch_size > kNearMaxCells ||
-        p->batch_size * p->cells_per_axis * p->cells_per_axis * p->cells_per_axis > kNearMaxCells) {
-        set_error("Input mismatch: too many cells");
-        return NFFT_HIP_EINVAL;
-    }
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int64_t nfft_hip_ewald_near_cells(double r_cut, int64_t batch_size)
-{
-    if (!(r_cut > 0.0) || !(r_cut <= 1.0 / 3.0) || batch_size < 1) {
-        set_error("Input mismatch: ewald cells need r_cut in (0, 1/3] and batch_size >= 1");
-        return -1;
-    }
-    int64_t G = (int64_t)std::min(1.0 / r_cut, 1024.0);
-    while (G > 3 && 1.0 / (double)G < r_cut) --G;  // (the quotient may have been rounded up)
-    if (G < 3) G = 3;                              // (... or down, at r_cut = 1/3)
-    while (G > 3 && batch_size * G * G * G > kNearMaxCells) --G;
-    if (batch_size > kNearMaxCells || batch_size * G * G * G > kNearMaxCells) {
-        set_error("Input mismatch: too many point sets for a grid of 3 cells per axis");
-        return -1;
-    }
-    return G;
-}
-
-int64_t nfft_hip_ewald_near_workspace_bytes(const nfft_hip_ewald_problem *p)
-{
-    if (validate_ewald(p)) return -1;
-    return ewald_near_item_slots(p) * (int64_t)sizeof(int2) + 256;
-}
-
-int nfft_hip_ewald_near(const nfft_hip_ewald_problem *p, const float *points, const float *xr, const int32_t *start,
-                        const int64_t *index, float *z, float *field, void *workspace, int64_t workspace_bytes,
-                        void *stream)
-{
-    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
-    if (int rc = validate_ewald(p)) return rc;
-    if (p->num_points == 0 || p->num_columns == 0) return 0;
-    if (!z) { set_error("Input mismatch: z is null"); return NFFT_HIP_EINVAL; }
-    if (p->with_field && !field) { set_error("Input mismatch: field is null"); return NFFT_HIP_EINVAL; }
-    if (!points || !xr || !start || !index) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    const int64_t need = ewald_near_item_slots(p) * (int64_t)sizeof(int2) + 256;
-    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
-    return launch_ewald_near(p, points, xr, start, index, z, field, ws, (hipStream_t)stream);
-}
-
-}  // extern "C"
-
-// ---- the same pair sum in an orthorhombic or triclinic box ------------------------------------
-namespace {
-
-// perpendicular widths w_a = 1 / |column a of A^-1| of the box A00, A10, A11, A20, A21, A22; false unless every entry is
-// finite and the diagonal positive
-bool ewald_box_widths(const double *box, double *w)
-{
-    for (int e = 0; e < 6; ++e)
-        if (!(box[e] == box[e]) || box[e] > 1e300 || box[e] < -1e300) return false;
-    const double a00 = box[0], a10 = box[1], a11 = box[2], a20 = box[3], a21 = box[4], a22 = box[5];
-    if (!(a00 > 0.0) || !(a11 > 0.0) || !(a22 > 0.0)) return false;
-    // A^-1 is lower triangular too
-    const double i00 = 1.0 / a00, i11 = 1.0 / a11, i22 = 1.0 / a22;
-    const double i10 = -a10 * i00 * i11, i21 = -a21 * i11 * i22;
-    const double i20 = (a10 * a21 - a11 * a20) * i00 * i11 * i22;
-    w[0] = 1.0 / std::sqrt(i00 * i00 + i10 * i10 + i20 * i20);
-    w[1] = 1.0 / std::sqrt(i11 * i11 + i21 * i21);
-    w[2] = a22;
-    for (int a = 0; a < 3; ++a)
-        if (!(w[a] > 0.0) || !(w[a] < 1e300)) return false;
-    return true;
-}
-
-// r_cut in (0, min_a w_a / 3] (the quotient's last bit is not held against the caller)
-bool ewald_box_r_cut_ok(const double *w, double r_cut)
-{
-    const double wmin = std::min(w[0], std::min(w[1], w[2]));
-    return r_cut > 0.0 && r_cut * (1.0 - 1e-12) <= wmin / 3.0;
-}
-
-int validate_ewald_box(const nfft_hip_ewald_box_problem *p)
-{
-    if (!p) { set_error("Input mismatch: null problem"); return NFFT_HIP_EINVAL; }
-    if (p->with_field != 0 && p->with_field != 1) { set_error("Input mismatch: with_field must be 0 or 1"); return NFFT_HIP_EINVAL; }
-    if (p->num_points < 0 || p->num_columns < 0 || p->batch_size < 1) {
-        set_error("Input mismatch: negative size");
-        return NFFT_HIP_EINVAL;
-    }
-    if (p->num_points >= (int64_t(1) << 31)) { set_error("Input mismatch: too many points"); return NFFT_HIP_EINVAL; }
-    if (!(p->alpha > 0.0) || !(p->alpha < 1e18)) { set_error("Input mismatch: alpha must be positive and finite"); return NFFT_HIP_EINVAL; }
-    double w[3];
-    if (!ewald_box_widths(p->box, w)) {
-        set_error("Input mismatch: the box must be finite with a positive diagonal");
-        return NFFT_HIP_EINVAL;
-    }
-    if (!ewald_box_r_cut_ok(w, p->r_cut)) {
-        set_error("Input mismatch: r_cut must lie in (0, min w_a / 3] for the box's perpendicular widths w_a");
-        return NFFT_HIP_EINVAL;
-    }
-    int64_t cells = p->batch_size;
-    for (int a = 0; a < 3; ++a) {
-        if (p->cells[a] < 3 || p->cells[a] > 1024 || w[a] / p->cells[a] < p->r_cut * (1.0 - 1e-12)) {
-            set_error("Input mismatch: cells must be at least 3 per axis with a width w_a / cells[a] >= r_cut");
-            return NFFT_HIP_EINVAL;
-        }
-        cells = cells > kNearMaxCells ? cells : cells * p->cells[a];
-    }
-    if (cells > kNearMaxCells) { set_error("Input mismatch: too many cells"); return NFFT_HIP_EINVAL; }
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int64_t nfft_hip_ewald_box_cells(const double *box, double r_cut, int64_t batch_size, int32_t *cells_out)
-{
-    double w[3];
-    if (!box || !cells_out) { set_error("Input mismatch: null input"); return -1; }
-    if (!ewald_box_widths(box, w)) {
-        set_error("Input mismatch: the box must be finite with a positive diagonal");
-        return -1;
-    }
-    if (!ewald_box_r_cut_ok(w, r_cut) || batch_size < 1) {
-        set_error("Input mismatch: ewald cells need r_cut in (0, min w_a / 3] and batch_size >= 1");
-        return -1;
-    }
-    int64_t G[3];
-    for (int a = 0; a < 3; ++a) {
-        G[a] = (int64_t)std::min(w[a] / r_cut, 1024.0);
-        while (G[a] > 3 && w[a] / (double)G[a] < r_cut) --G[a];  // (the quotient may have been rounded up)
-        if (G[a] < 3) G[a] = 3;                                  // (... or down, at r_cut = w_a / 3)
-    }
-    while (batch_size <= kNearMaxCells && batch_size * G[0] * G[1] * G[2] > kNearMaxCells) {
-        int a = 0;  // the largest count first
-        if (G[1] > G[a]) a = 1;
-        if (G[2] > G[a]) a = 2;
-        if (G[a] <= 3) break;
-        --G[a];
-    }
-    if (batch_size > kNearMaxCells || batch_size * G[0] * G[1] * G[2] > kNearMaxCells) {
-        set_error("Input mismatch: too many point sets for a grid of 3 cells per axis");
-        return -1;
-    }
-    for (int a = 0; a < 3; ++a) cells_out[a] = (int32_t)G[a];
-    return 0;
-}
-
-int64_t nfft_hip_ewald_near_box_workspace_bytes(const nfft_hip_ewald_box_problem *p)
-{
-    if (validate_ewald_box(p)) return -1;
-    return ewald_near_box_item_slots(p) * (int64_t)sizeof(int2) + 256;
-}
-
-int nfft_hip_ewald_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
-                            const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
-                            int64_t workspace_bytes, void *stream)
-{
-    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
-    if (int rc = validate_ewald_box(p)) return rc;
-    if (p->num_points == 0 || p->num_columns == 0) return 0;
-    if (!z) { set_error("Input mismatch: z is null"); return NFFT_HIP_EINVAL; }
-    if (p->with_field && !field) { set_error("Input mismatch: field is null"); return NFFT_HIP_EINVAL; }
-    if (!points || !xr || !start || !index) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    const int64_t need = ewald_near_box_item_slots(p) * (int64_t)sizeof(int2) + 256;
-    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
-    return launch_ewald_near_box(p, points, xr, start, index, z, field, ws, (hipStream_t)stream);
-}
-
-}  // extern "C"
-
-// ---- virial tensor of the Ewald sum -----------------------------------------------------------
-namespace {
-
-int validate_virial_far(int64_t N, int64_t batch_size, int64_t num_columns)
-{
-    if (N < 2 || N > 2048 || N % 2) { set_error("Input mismatch: N must be even with 2 <= N <= 2048"); return NFFT_HIP_EINVAL; }
-    // (the launches: 1024 workgroups per point set at most, one workgroup per point set and column)
-    if (batch_size < 1 || batch_size >= (int64_t(1) << 14) || num_columns < 0 || num_columns >= (int64_t(1) << 21) ||
-        batch_size * num_columns >= (int64_t(1) << 21)) {
-        set_error("Input mismatch: 1 <= batch_size < 2^14, num_columns >= 0 and batch_size * num_columns < 2^21 are required");
-        return NFFT_HIP_EINVAL;
-    }
-    return 0;
-}
-
-// the box problem's own checks, and the second level's launch: one workgroup per point set and column
-int validate_virial_near(const nfft_hip_ewald_box_problem *p)
-{
-    if (int rc = validate_ewald_box(p)) return rc;
-    if (p->num_columns >= (int64_t(1) << 21) || p->batch_size * p->num_columns >= (int64_t(1) << 31)) {
-        set_error("Input mismatch: num_columns < 2^21 and batch_size * num_columns < 2^31 are required");
-        return NFFT_HIP_EINVAL;
-    }
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int64_t nfft_hip_ewald_virial_near_workspace_bytes(const nfft_hip_ewald_box_problem *p)
-{
-    if (validate_virial_near(p)) return -1;
-    return ewald_virial_near_workspace(p) + 256;
-}
-
-int nfft_hip_ewald_virial_near(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
-                               const int32_t *start, double *out, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
-    if (int rc = validate_virial_near(p)) return rc;
-    if (p->num_columns == 0) return 0;
-    if (!out) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
-    if (p->num_points == 0) {
-        NFFT_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(p->batch_size * 7 * p->num_columns) * sizeof(double), (hipStream_t)stream));
-        return 0;
-    }
-    if (!points || !xr || !start) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    const int64_t need = ewald_virial_near_workspace(p) + 256;
-    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
-    return launch_ewald_virial_near(p, points, xr, start, out, ws, (hipStream_t)stream);
-}
-
-int64_t nfft_hip_ewald_virial_far_workspace_bytes(int64_t N, int64_t batch_size, int64_t num_columns)
-{
-    if (validate_virial_far(N, batch_size, num_columns)) return -1;
-    return ewald_virial_far_workspace(N, batch_size, num_columns) + 256;
-}
-
-int nfft_hip_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
-                              const double *box_inverse, double pi2_over_alpha2, double *out, void *workspace,
-                              int64_t workspace_bytes, void *stream)
-{
-    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
-    if (int rc = validate_virial_far(N, batch_size, num_columns)) return rc;
-    if (!box_inverse) { set_error("Input mismatch: box_inverse is null"); return NFFT_HIP_EINVAL; }
-    for (int e = 0; e < 6; ++e)
-        if (!(box_inverse[e] == box_inverse[e]) || box_inverse[e] > 1e300 || box_inverse[e] < -1e300) {
-            set_error("Input mismatch: the entries of box_inverse must be finite");
-            return NFFT_HIP_EINVAL;
-        }
-    if (!(box_inverse[0] > 0.0) || !(box_inverse[2] > 0.0) || !(box_inverse[5] > 0.0)) {
-        set_error("Input mismatch: the diagonal of box_inverse must be positive");
-        return NFFT_HIP_EINVAL;
-    }
-    if (!(pi2_over_alpha2 > 0.0) || !(pi2_over_alpha2 < 1e300)) {
-        set_error("Input mismatch: pi2_over_alpha2 must be positive and finite");
-        return NFFT_HIP_EINVAL;
-    }
-    if (num_columns == 0) return 0;
-    if (!band || !coeffs || !out) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    const int64_t need = ewald_virial_far_workspace(N, batch_size, num_columns) + 256;
-    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
-    char *ws = (char *)(((uintptr_t)workspace + 255) & ~uintptr_t(255));
-    return launch_ewald_virial_far(N, batch_size, num_columns, band, coeffs, box_inverse, pi2_over_alpha2, out, ws,
-                                   (hipStream_t)stream);
-}
-
-}  // extern "C"

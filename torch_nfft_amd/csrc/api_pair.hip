@@ -1,0 +1,448 @@
+// C-ABI entry points of the pair kernels (include/nfft_hip.h): the near field of the fast summation for singular kernels,
+// the near part of the Ewald sum on the torus and in a box, the virial reductions.  They share only the error plumbing and
+// the workspace conventions (host_util.h) with the transforms of api.hip.
+#include "../../include/nfft_hip.h"
+
+#include <cmath>
+
+#include "common.h"
+#include "host_util.h"
+#include "kernels.h"
+
+using namespace nfft;
+
+// ---- near field of the fast summation for singular kernels ------------------------------------
+namespace {
+constexpr int64_t kNearMaxCells = int64_t(1) << 20;
+
+int validate_nearfield(const nfft_hip_nearfield_problem *p)
+{
+    if (!p) { set_error("Input mismatch: null problem"); return NFFT_HIP_EINVAL; }
+    if (p->dim < 1 || p->dim > 3) { set_error("Input mismatch: dim must be 1, 2 or 3"); return NFFT_HIP_EINVAL; }
+    if (p->kernel < 0 || p->kernel > NFFT_HIP_KERNEL_LAPLACIAN_RBF) { set_error("Input mismatch: unknown kernel"); return NFFT_HIP_EINVAL; }
+    if (p->poly_terms < 1 || p->poly_terms > 8) { set_error("Input mismatch: poly_terms must be in 1..8"); return NFFT_HIP_EINVAL; }
+    if (p->num_sources < 0 || p->num_targets < 0 || p->num_columns < 0 || p->batch_size < 1) {
+        set_error("Input mismatch: negative size");
+        return NFFT_HIP_EINVAL;
+    }
+    if (p->num_sources >= (int64_t(1) << 31) || p->num_targets >= (int64_t(1) << 31)) {
+        set_error("Input mismatch: too many points");
+        return NFFT_HIP_EINVAL;
+    }
+    if (!(p->eps_I > 0.0) || !(p->eps_I < 0.5)) { set_error("Input mismatch: eps_I must lie in (0, 1/2)"); return NFFT_HIP_EINVAL; }
+    if (p->cells_per_axis < 1 || 0.5 / p->cells_per_axis < p->eps_I * (1.0 - 1e-12)) {
+        set_error("Input mismatch: cells must have an edge 1 / (2 cells_per_axis) >= eps_I");
+        return NFFT_HIP_EINVAL;
+    }
+    int64_t cells = p->batch_size;
+    for (int a = 0; a < p->dim && cells <= kNearMaxCells; ++a) cells *= p->cells_per_axis;
+    if (cells > kNearMaxCells && p->cells_per_axis > 1) { set_error("Input mismatch: too many cells"); return NFFT_HIP_EINVAL; }
+    if (cells >= (int64_t(1) << 30)) { set_error("Input mismatch: too many point sets"); return NFFT_HIP_EINVAL; }
+    const bool needs_c = p->kernel >= NFFT_HIP_KERNEL_INVERSE_MULTIQUADRIC;
+    if (!(p->c >= 0.0) || (needs_c && !(p->c > 0.0))) { set_error("Input mismatch: the shape parameter c must be positive"); return NFFT_HIP_EINVAL; }
+    if (!all_finite(p->poly, p->poly_terms, 3e38)) { set_error("Input mismatch: poly is not finite"); return NFFT_HIP_EINVAL; }
+    return 0;
+}
+
+int64_t nearfield_need(const nfft_hip_nearfield_problem *p) { return nearfield_item_slots(p) * (int64_t)sizeof(int2) + 256; }
+
+int check_gradient_poly(const nfft_hip_nearfield_problem *p, const double *gradient_poly)
+{
+    if (!gradient_poly) { set_error("Input mismatch: gradient_poly is null"); return NFFT_HIP_EINVAL; }
+    if (!all_finite(gradient_poly, p->poly_terms - 1, 3e38)) {
+        set_error("Input mismatch: gradient_poly is not finite");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+// what the torus problem and the box problem have in common: with_field, the sizes, the point count and alpha
+template <class Problem>
+int validate_ewald_head(const Problem *p)
+{
+    if (!p) { set_error("Input mismatch: null problem"); return NFFT_HIP_EINVAL; }
+    if (p->with_field != 0 && p->with_field != 1) { set_error("Input mismatch: with_field must be 0 or 1"); return NFFT_HIP_EINVAL; }
+    if (p->num_points < 0 || p->num_columns < 0 || p->batch_size < 1) {
+        set_error("Input mismatch: negative size");
+        return NFFT_HIP_EINVAL;
+    }
+    if (p->num_points >= (int64_t(1) << 31)) { set_error("Input mismatch: too many points"); return NFFT_HIP_EINVAL; }
+    if (!(p->alpha > 0.0) || !(p->alpha < 1e18)) { set_error("Input mismatch: alpha must be positive and finite"); return NFFT_HIP_EINVAL; }
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int64_t nfft_hip_nearfield_cells(int32_t dim, double eps_I, int64_t batch_size)
+{
+    if (dim < 1 || dim > 3 || !(eps_I > 0.0) || !(eps_I < 0.5) || batch_size < 1) {
+        set_error("Input mismatch: nearfield cells need dim in 1..3, eps_I in (0, 1/2) and batch_size >= 1");
+        return -1;
+    }
+    int64_t G = (int64_t)std::min(0.5 / eps_I, 1048576.0);
+    while (G > 1 && 0.5 / (double)G < eps_I) --G;  // (the quotient may have been rounded up)
+    auto cells = [&](int64_t g) { int64_t c = batch_size; for (int a = 0; a < dim; ++a) c *= g; return c; };
+    while (G > 1 && cells(G) > kNearMaxCells) G = G > 64 ? G / 2 : G - 1;
+    return G < 1 ? 1 : G;
+}
+
+int64_t nfft_hip_nearfield_workspace_bytes(const nfft_hip_nearfield_problem *p)
+{
+    if (validate_nearfield(p)) return -1;
+    return nearfield_need(p);
+}
+
+int nfft_hip_nearfield(const nfft_hip_nearfield_problem *p, const float *sources, const float *xr,
+                       const int32_t *source_start, const float *targets, const int64_t *target_index,
+                       const int32_t *target_start, float *z, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_nearfield(p)) return rc;
+    if (p->num_targets == 0 || p->num_columns == 0) return 0;
+    if (!z) { set_error("Input mismatch: z is null"); return NFFT_HIP_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    if (p->num_sources == 0) {
+        NFFT_HIP_CHECK(hipMemsetAsync(z, 0, (size_t)(p->num_targets * p->num_columns) * sizeof(float), s));
+        return 0;
+    }
+    if (!sources || !xr || !source_start || !targets || !target_index || !target_start) {
+        set_error("Input mismatch: null input");
+        return NFFT_HIP_EINVAL;
+    }
+    char *ws = workspace_base(workspace, workspace_bytes, nearfield_need(p));
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_nearfield(p, sources, xr, source_start, targets, target_index, target_start, z, ws, s);
+}
+
+// ---- its gradient at the targets and the transpose ---------------------------------------------
+static int validate_nearfield_gradient(const nfft_hip_nearfield_problem *p)
+{
+    if (int rc = validate_nearfield(p)) return rc;
+    if (p->poly_terms < 2) {
+        set_error("Input mismatch: the near field's gradient needs poly_terms >= 2 (K_R must be differentiable at eps_I)");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+int64_t nfft_hip_nearfield_gradient_workspace_bytes(const nfft_hip_nearfield_problem *p)
+{
+    if (validate_nearfield_gradient(p)) return -1;
+    return nearfield_need(p);
+}
+
+int nfft_hip_nearfield_gradient(const nfft_hip_nearfield_problem *p, int32_t transpose, const double *gradient_poly,
+                                const float *sources, const float *xr, const int32_t *source_start, const float *targets,
+                                const int64_t *target_index, const int32_t *target_start, float *out, void *workspace,
+                                int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_nearfield_gradient(p)) return rc;
+    if (transpose != 0 && transpose != 1) { set_error("Input mismatch: transpose must be 0 or 1"); return NFFT_HIP_EINVAL; }
+    if (int rc = check_gradient_poly(p, gradient_poly)) return rc;
+    if (p->num_targets == 0 || p->num_columns == 0) return 0;
+    if (!out) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    if (p->num_sources == 0) {
+        const int64_t row = transpose ? p->num_columns : p->dim * p->num_columns;
+        NFFT_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(p->num_targets * row) * sizeof(float), s));
+        return 0;
+    }
+    if (!sources || !xr || !source_start || !targets || !target_index || !target_start) {
+        set_error("Input mismatch: null input");
+        return NFFT_HIP_EINVAL;
+    }
+    char *ws = workspace_base(workspace, workspace_bytes, nearfield_need(p));
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_nearfield_gradient(p, transpose, gradient_poly, sources, xr, source_start, targets, target_index,
+                                     target_start, out, ws, s);
+}
+
+// ---- its gradient with respect to the points ----------------------------------------------------
+int64_t nfft_hip_nearfield_point_gradient_workspace_bytes(const nfft_hip_nearfield_problem *p)
+{
+    if (validate_nearfield_gradient(p)) return -1;
+    return nearfield_need(p);
+}
+
+int nfft_hip_nearfield_point_gradient(const nfft_hip_nearfield_problem *p, int32_t symmetric, const double *gradient_poly,
+                                      const float *streamed, const float *streamed_values, const int32_t *streamed_start,
+                                      const float *output, const float *output_values, const int64_t *output_index,
+                                      const int32_t *output_start, float *out, void *workspace, int64_t workspace_bytes,
+                                      void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_nearfield_gradient(p)) return rc;
+    if (symmetric != 0 && symmetric != 1) { set_error("Input mismatch: symmetric must be 0 or 1"); return NFFT_HIP_EINVAL; }
+    if (symmetric && p->num_sources != p->num_targets) {
+        set_error("Input mismatch: a symmetric sweep needs one point set on both sides");
+        return NFFT_HIP_EINVAL;
+    }
+    if (int rc = check_gradient_poly(p, gradient_poly)) return rc;
+    if (p->num_targets == 0 || p->num_columns == 0) return 0;
+    if (!out) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    if (p->num_sources == 0) {
+        NFFT_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(p->num_targets * p->dim) * sizeof(float), s));
+        return 0;
+    }
+    if (!streamed || !streamed_values || !streamed_start || !output || !output_values || !output_index || !output_start) {
+        set_error("Input mismatch: null input");
+        return NFFT_HIP_EINVAL;
+    }
+    char *ws = workspace_base(workspace, workspace_bytes, nearfield_need(p));
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_nearfield_point_gradient(p, symmetric, gradient_poly, streamed, streamed_values, streamed_start, output,
+                                           output_values, output_index, output_start, out, ws, s);
+}
+
+// ---- near part of the Ewald sum for the periodic 1/r ------------------------------------------
+static int validate_ewald(const nfft_hip_ewald_problem *p)
+{
+    if (int rc = validate_ewald_head(p)) return rc;
+    if (!(p->r_cut > 0.0) || !(p->r_cut <= 1.0 / 3.0)) { set_error("Input mismatch: r_cut must lie in (0, 1/3]"); return NFFT_HIP_EINVAL; }
+    if (p->cells_per_axis < 3 || 1.0 / p->cells_per_axis < p->r_cut * (1.0 - 1e-12)) {
+        set_error("Input mismatch: cells must be at least 3 per axis with an edge 1 / cells_per_axis >= r_cut");
+        return NFFT_HIP_EINVAL;
+    }
+    if (p->batch_size > kNearMaxCells ||
+        p->batch_size * p->cells_per_axis * p->cells_per_axis * p->cells_per_axis > kNearMaxCells) {
+        set_error("Input mismatch: too many cells");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+static int64_t ewald_near_need(const nfft_hip_ewald_problem *p) { return ewald_near_item_slots(p) * (int64_t)sizeof(int2) + 256; }
+
+int64_t nfft_hip_ewald_near_cells(double r_cut, int64_t batch_size)
+{
+    if (!(r_cut > 0.0) || !(r_cut <= 1.0 / 3.0) || batch_size < 1) {
+        set_error("Input mismatch: ewald cells need r_cut in (0, 1/3] and batch_size >= 1");
+        return -1;
+    }
+    int64_t G = (int64_t)std::min(1.0 / r_cut, 1024.0);
+    while (G > 3 && 1.0 / (double)G < r_cut) --G;  // (the quotient may have been rounded up)
+    if (G < 3) G = 3;                              // (... or down, at r_cut = 1/3)
+    while (G > 3 && batch_size * G * G * G > kNearMaxCells) --G;
+    if (batch_size > kNearMaxCells || batch_size * G * G * G > kNearMaxCells) {
+        set_error("Input mismatch: too many point sets for a grid of 3 cells per axis");
+        return -1;
+    }
+    return G;
+}
+
+int64_t nfft_hip_ewald_near_workspace_bytes(const nfft_hip_ewald_problem *p)
+{
+    if (validate_ewald(p)) return -1;
+    return ewald_near_need(p);
+}
+
+int nfft_hip_ewald_near(const nfft_hip_ewald_problem *p, const float *points, const float *xr, const int32_t *start,
+                        const int64_t *index, float *z, float *field, void *workspace, int64_t workspace_bytes,
+                        void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_ewald(p)) return rc;
+    if (p->num_points == 0 || p->num_columns == 0) return 0;
+    if (!z) { set_error("Input mismatch: z is null"); return NFFT_HIP_EINVAL; }
+    if (p->with_field && !field) { set_error("Input mismatch: field is null"); return NFFT_HIP_EINVAL; }
+    if (!points || !xr || !start || !index) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    char *ws = workspace_base(workspace, workspace_bytes, ewald_near_need(p));
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_ewald_near(p, points, xr, start, index, z, field, ws, (hipStream_t)stream);
+}
+
+// ---- the same pair sum in an orthorhombic or triclinic box ------------------------------------
+// perpendicular widths w_a = 1 / |column a of A^-1| of the box A00, A10, A11, A20, A21, A22; false unless every entry is
+// finite and the diagonal positive
+static bool ewald_box_widths(const double *box, double *w)
+{
+    if (!all_finite(box, 6, 1e300)) return false;
+    const double a00 = box[0], a10 = box[1], a11 = box[2], a20 = box[3], a21 = box[4], a22 = box[5];
+    if (!(a00 > 0.0) || !(a11 > 0.0) || !(a22 > 0.0)) return false;
+    // A^-1 is lower triangular too
+    const double i00 = 1.0 / a00, i11 = 1.0 / a11, i22 = 1.0 / a22;
+    const double i10 = -a10 * i00 * i11, i21 = -a21 * i11 * i22;
+    const double i20 = (a10 * a21 - a11 * a20) * i00 * i11 * i22;
+    w[0] = 1.0 / std::sqrt(i00 * i00 + i10 * i10 + i20 * i20);
+    w[1] = 1.0 / std::sqrt(i11 * i11 + i21 * i21);
+    w[2] = a22;
+    for (int a = 0; a < 3; ++a)
+        if (!(w[a] > 0.0) || !(w[a] < 1e300)) return false;
+    return true;
+}
+
+// r_cut in (0, min_a w_a / 3] (the quotient's last bit is not held against the caller)
+static bool ewald_box_r_cut_ok(const double *w, double r_cut)
+{
+    const double wmin = std::min(w[0], std::min(w[1], w[2]));
+    return r_cut > 0.0 && r_cut * (1.0 - 1e-12) <= wmin / 3.0;
+}
+
+static int validate_ewald_box(const nfft_hip_ewald_box_problem *p)
+{
+    if (int rc = validate_ewald_head(p)) return rc;
+    double w[3];
+    if (!ewald_box_widths(p->box, w)) {
+        set_error("Input mismatch: the box must be finite with a positive diagonal");
+        return NFFT_HIP_EINVAL;
+    }
+    if (!ewald_box_r_cut_ok(w, p->r_cut)) {
+        set_error("Input mismatch: r_cut must lie in (0, min w_a / 3] for the box's perpendicular widths w_a");
+        return NFFT_HIP_EINVAL;
+    }
+    int64_t cells = p->batch_size;
+    for (int a = 0; a < 3; ++a) {
+        if (p->cells[a] < 3 || p->cells[a] > 1024 || w[a] / p->cells[a] < p->r_cut * (1.0 - 1e-12)) {
+            set_error("Input mismatch: cells must be at least 3 per axis with a width w_a / cells[a] >= r_cut");
+            return NFFT_HIP_EINVAL;
+        }
+        cells = cells > kNearMaxCells ? cells : cells * p->cells[a];
+    }
+    if (cells > kNearMaxCells) { set_error("Input mismatch: too many cells"); return NFFT_HIP_EINVAL; }
+    return 0;
+}
+
+static int64_t ewald_box_need(const nfft_hip_ewald_box_problem *p) { return ewald_near_box_item_slots(p) * (int64_t)sizeof(int2) + 256; }
+
+int64_t nfft_hip_ewald_box_cells(const double *box, double r_cut, int64_t batch_size, int32_t *cells_out)
+{
+    double w[3];
+    if (!box || !cells_out) { set_error("Input mismatch: null input"); return -1; }
+    if (!ewald_box_widths(box, w)) {
+        set_error("Input mismatch: the box must be finite with a positive diagonal");
+        return -1;
+    }
+    if (!ewald_box_r_cut_ok(w, r_cut) || batch_size < 1) {
+        set_error("Input mismatch: ewald cells need r_cut in (0, min w_a / 3] and batch_size >= 1");
+        return -1;
+    }
+    int64_t G[3];
+    for (int a = 0; a < 3; ++a) {
+        G[a] = (int64_t)std::min(w[a] / r_cut, 1024.0);
+        while (G[a] > 3 && w[a] / (double)G[a] < r_cut) --G[a];  // (the quotient may have been rounded up)
+        if (G[a] < 3) G[a] = 3;                                  // (... or down, at r_cut = w_a / 3)
+    }
+    while (batch_size <= kNearMaxCells && batch_size * G[0] * G[1] * G[2] > kNearMaxCells) {
+        int a = 0;  // the largest count first
+        if (G[1] > G[a]) a = 1;
+        if (G[2] > G[a]) a = 2;
+        if (G[a] <= 3) break;
+        --G[a];
+    }
+    if (batch_size > kNearMaxCells || batch_size * G[0] * G[1] * G[2] > kNearMaxCells) {
+        set_error("Input mismatch: too many point sets for a grid of 3 cells per axis");
+        return -1;
+    }
+    for (int a = 0; a < 3; ++a) cells_out[a] = (int32_t)G[a];
+    return 0;
+}
+
+int64_t nfft_hip_ewald_near_box_workspace_bytes(const nfft_hip_ewald_box_problem *p)
+{
+    if (validate_ewald_box(p)) return -1;
+    return ewald_box_need(p);
+}
+
+int nfft_hip_ewald_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                            const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
+                            int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_ewald_box(p)) return rc;
+    if (p->num_points == 0 || p->num_columns == 0) return 0;
+    if (!z) { set_error("Input mismatch: z is null"); return NFFT_HIP_EINVAL; }
+    if (p->with_field && !field) { set_error("Input mismatch: field is null"); return NFFT_HIP_EINVAL; }
+    if (!points || !xr || !start || !index) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    char *ws = workspace_base(workspace, workspace_bytes, ewald_box_need(p));
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_ewald_near_box(p, points, xr, start, index, z, field, ws, (hipStream_t)stream);
+}
+
+// ---- virial tensor of the Ewald sum -----------------------------------------------------------
+static int validate_virial_far(int64_t N, int64_t batch_size, int64_t num_columns)
+{
+    if (N < 2 || N > 2048 || N % 2) { set_error("Input mismatch: N must be even with 2 <= N <= 2048"); return NFFT_HIP_EINVAL; }
+    // (the launches: 1024 workgroups per point set at most, one workgroup per point set and column)
+    if (batch_size < 1 || batch_size >= (int64_t(1) << 14) || num_columns < 0 || num_columns >= (int64_t(1) << 21) ||
+        batch_size * num_columns >= (int64_t(1) << 21)) {
+        set_error("Input mismatch: 1 <= batch_size < 2^14, num_columns >= 0 and batch_size * num_columns < 2^21 are required");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+// the box problem's own checks, and the second level's launch: one workgroup per point set and column
+static int validate_virial_near(const nfft_hip_ewald_box_problem *p)
+{
+    if (int rc = validate_ewald_box(p)) return rc;
+    if (p->num_columns >= (int64_t(1) << 21) || p->batch_size * p->num_columns >= (int64_t(1) << 31)) {
+        set_error("Input mismatch: num_columns < 2^21 and batch_size * num_columns < 2^31 are required");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+static int64_t virial_near_need(const nfft_hip_ewald_box_problem *p) { return ewald_virial_near_workspace(p) + 256; }
+static int64_t virial_far_need(int64_t N, int64_t B, int64_t C) { return ewald_virial_far_workspace(N, B, C) + 256; }
+
+int64_t nfft_hip_ewald_virial_near_workspace_bytes(const nfft_hip_ewald_box_problem *p)
+{
+    if (validate_virial_near(p)) return -1;
+    return virial_near_need(p);
+}
+
+int nfft_hip_ewald_virial_near(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                               const int32_t *start, double *out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_virial_near(p)) return rc;
+    if (p->num_columns == 0) return 0;
+    if (!out) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
+    if (p->num_points == 0) {
+        NFFT_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(p->batch_size * 7 * p->num_columns) * sizeof(double), (hipStream_t)stream));
+        return 0;
+    }
+    if (!points || !xr || !start) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    char *ws = workspace_base(workspace, workspace_bytes, virial_near_need(p));
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_ewald_virial_near(p, points, xr, start, out, ws, (hipStream_t)stream);
+}
+
+int64_t nfft_hip_ewald_virial_far_workspace_bytes(int64_t N, int64_t batch_size, int64_t num_columns)
+{
+    if (validate_virial_far(N, batch_size, num_columns)) return -1;
+    return virial_far_need(N, batch_size, num_columns);
+}
+
+int nfft_hip_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
+                              const double *box_inverse, double pi2_over_alpha2, double *out, void *workspace,
+                              int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_virial_far(N, batch_size, num_columns)) return rc;
+    if (!box_inverse) { set_error("Input mismatch: box_inverse is null"); return NFFT_HIP_EINVAL; }
+    if (!all_finite(box_inverse, 6, 1e300)) {
+        set_error("Input mismatch: the entries of box_inverse must be finite");
+        return NFFT_HIP_EINVAL;
+    }
+    if (!(box_inverse[0] > 0.0) || !(box_inverse[2] > 0.0) || !(box_inverse[5] > 0.0)) {
+        set_error("Input mismatch: the diagonal of box_inverse must be positive");
+        return NFFT_HIP_EINVAL;
+    }
+    if (!(pi2_over_alpha2 > 0.0) || !(pi2_over_alpha2 < 1e300)) {
+        set_error("Input mismatch: pi2_over_alpha2 must be positive and finite");
+        return NFFT_HIP_EINVAL;
+    }
+    if (num_columns == 0) return 0;
+    if (!band || !coeffs || !out) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    char *ws = workspace_base(workspace, workspace_bytes, virial_far_need(N, batch_size, num_columns));
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_ewald_virial_far(N, batch_size, num_columns, band, coeffs, box_inverse, pi2_over_alpha2, out, ws,
+                                   (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -15,6 +15,7 @@
 #include "../../include/nfft_hip.h"
 
 #include "common.h"
+#include "host_util.h"
 #include "kernels.h"
 
 namespace nfft {
@@ -132,7 +133,8 @@ int fft_coeffs(const void *values, int mode, float sigma2, int64_t N, int dim, f
     const int64_t wb = fft_work_bytes(kC2CForward, dim, (int)N, 1);
     if (wb < 0) return NFFT_HIP_EFFT;
     const int64_t need = align_up(total * 8, 256) + wb;
-    if (!workspace || workspace_bytes < need) { set_error("workspace too small"); return NFFT_HIP_EWORKSPACE; }
+    // (only the check: this workspace is used from the caller's own base, and `need` has no slack for an aligned one)
+    if (!workspace_base(workspace, workspace_bytes, need)) return NFFT_HIP_EWORKSPACE;
     float2 *b = (float2 *)workspace;
     void *work = (char *)workspace + align_up(total * 8, 256);
     hipLaunchKernelGGL(fill_shifted_kernel, dim3(blocks_for(total)), dim3(256), 0, s, b, values, mode, sigma2, (int)N, dim, total);

@@ -31,6 +31,9 @@ void set_error(const std::string &msg);
 enum DeviceFault { kFaultStreamStall = 0, kFaultBatchIndex = 1, kFaultBatchOrder = 2, kFaultStalePlan = 3, kNumFaults = 4 };
 constexpr int kStatusInts = 16;  // ints per device block (a 64-byte line)
 int *device_status_block();      // api.hip: device-visible address of the current device's block (nullptr: none)
+// api.hip: faults the kernels of the current device have reported since the last look: sets the error text, clears the
+// flags and returns NFFT_HIP_EKERNEL (NFFT_HIP_EINVAL for a bad batch vector); 0 when there is none
+int take_pending_fault();
 
 // ---- tiling of the oversampled grid --------------------------------------
 // Internally every problem is 3-D with axes (a0, a1, a2); a2 is the fastest

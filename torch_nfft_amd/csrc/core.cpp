@@ -162,6 +162,86 @@ nfft_hip_problem problem(const Points &p, int64_t C, int64_t N, int64_t m, int32
     return q;
 }
 
+// The workspace of a native call from its size query.  A negative size raises what the query reported: an input error where
+// the text says so, else a failed rocFFT plan.
+at::Tensor workspace_or_raise(int64_t ws_bytes, const at::Tensor &like)
+{
+    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
+    return byte_buffer(ws_bytes, like);
+}
+
+// A coefficient tensor: its bandwidth (spectral only), columns per row, type and trailing (column) shape
+struct Coeffs {
+    int64_t N = 0, C = 1;
+    bool real_input = true;
+    std::vector<int64_t> cols;
+    int64_t Cr() const { return real_input ? C : 2 * C; }  // real columns: a complex value is two
+    std::vector<int64_t> shape(std::vector<int64_t> lead) const { lead.insert(lead.end(), cols.begin(), cols.end()); return lead; }
+};
+
+// check_spectral_coeffs_input (core_cuda.cu:89-115): x [B, N, ..., N, *cols]
+Coeffs check_spectral(const at::Tensor &x, const Points &p)
+{
+    Coeffs c;
+    c.real_input = real_dtype(x);
+    CHECK_INPUT(x.dim() >= p.dim + 1);
+    CHECK_INPUT(x.size(0) == p.B);
+    CHECK_INPUT(x.device() == p.pos.device());
+    c.N = x.size(1);
+    CHECK_INPUT(c.N >= 2);
+    for (int d = 2; d <= p.dim; ++d) CHECK_INPUT(x.size(d) == c.N);
+    for (int64_t d = p.dim + 1; d < x.dim(); ++d) {
+        c.C *= x.size(d);
+        c.cols.push_back(x.size(d));
+    }
+    return c;
+}
+
+// check_spatial_coeffs_input (core_cuda.cu:69-86): x [n, ...] with `lead` leading dimensions before the columns
+Coeffs check_spatial(const at::Tensor &x, int64_t n, int64_t lead = 1)
+{
+    Coeffs c;
+    c.real_input = real_dtype(x);
+    CHECK_INPUT(x.dim() >= lead);
+    CHECK_INPUT(x.size(0) == n);
+    for (int64_t d = lead; d < x.dim(); ++d) {
+        c.C *= x.size(d);
+        c.cols.push_back(x.size(d));
+    }
+    return c;
+}
+
+// Sources and targets of a pair sum, checked as the reference's fastsum does (core_cuda.cu:552-568): one point set on both
+// sides (the same tensors) is checked once.
+struct PointPair { Points ps, pt; bool shared; };
+PointPair check_point_pair(const at::Tensor &sources, const at::Tensor &targets, const c10::optional<at::Tensor> &opt_source_batch,
+                           const c10::optional<at::Tensor> &opt_target_batch)
+{
+    PointPair pp;
+    pp.ps = check_points(sources, opt_source_batch, "(*out_batch)");
+    const bool same_batch = (!opt_source_batch.has_value() && !opt_target_batch.has_value()) ||
+                            (opt_source_batch.has_value() && opt_target_batch.has_value() &&
+                             opt_source_batch->is_same(*opt_target_batch));
+    pp.shared = sources.is_same(targets) && same_batch;
+    pp.pt = pp.shared ? pp.ps : check_points(targets, opt_target_batch, "(*out_batch)");
+    CHECK_INPUT(pp.pt.dim == pp.ps.dim);
+    CHECK_INPUT(pp.pt.B == pp.ps.B);
+    return pp;
+}
+
+// rows [n, row] float32 of x (complex values: real and imaginary parts as columns) in the order `order`
+at::Tensor real_rows(const at::Tensor &x, bool real_input, int64_t n, int64_t row, const at::Tensor &order)
+{
+    const at::Tensor xc = x.contiguous();
+    return (real_input ? xc : at::view_as_real(xc)).reshape({n, row}).index_select(0, order);
+}
+
+// the way back: z [n, row] float32 (n > 0) as x's type in `shape`
+at::Tensor complex_back(const at::Tensor &z, bool real_input, const std::vector<int64_t> &shape)
+{
+    return (real_input ? z : at::view_as_complex(z.reshape({z.size(0), -1, 2}))).reshape(shape);
+}
+
 // ---- point-plan cache -------------------------------------------------------------------------------------
 // The tile-sorted copy of the points depends only on (pos, batch, N, m).  Adjoint <-> forward pairs on the same
 // points (autograd backward, a forward fed by an adjoint, fastsum -- the reference exploits
@@ -347,32 +427,25 @@ at::Tensor nfft_adjoint(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> 
 {
     TORCH_CHECK(x.is_cuda(), "torch_nfft.nfft_adjoint is currently only implemented for GPU tensors");
     const Points p = check_points(pos, opt_batch, "(*out_batch)");
-    const bool real_input = real_dtype(x);  // check_spatial_coeffs_input, core_cuda.cu:69-86
-    CHECK_INPUT(x.dim() >= 1);
-    CHECK_INPUT(x.size(0) == p.n);
+    const Coeffs c = check_spatial(x, p.n);
     CHECK_INPUT(x.device() == pos.device());
-    int64_t C = 1;
-    for (int64_t d = 1; d < x.dim(); ++d) C *= x.size(d);
-    std::vector<int64_t> shape{p.B};  // core_cuda.cu:298-304
-    for (int d = 0; d < p.dim; ++d) shape.push_back(N);
-    for (int64_t d = 1; d < x.dim(); ++d) shape.push_back(x.size(d));
-    at::Tensor y = at::empty(shape, x.options().dtype(real_output ? at::kFloat : at::kComplexFloat));
+    std::vector<int64_t> band{p.B};  // core_cuda.cu:298-304
+    band.insert(band.end(), (size_t)p.dim, N);
+    at::Tensor y = at::empty(c.shape(band), x.options().dtype(real_output ? at::kFloat : at::kComplexFloat));
     if (y.numel() == 0) return y;
     const at::Tensor xc = x.contiguous();
-    const nfft_hip_problem q = problem(p, C, N, m);
+    const nfft_hip_problem q = problem(p, c.C, N, m);
     c10::DeviceGuard guard(x.device());
     if (!nfft_hip_plan_needed(&q)) {  // one fused kernel on the caller's points: no plan, no workspace
-        check_rc(nfft_hip_adjoint(&q, p.pos.data_ptr<float>(), xc.data_ptr(), real_input ? 0 : 1,
+        check_rc(nfft_hip_adjoint(&q, p.pos.data_ptr<float>(), xc.data_ptr(), c.real_input ? 0 : 1,
                                   p.batch.defined() ? p.batch.data_ptr<int64_t>() : nullptr, real_output ? 1 : 0,
                                   y.data_ptr(), nullptr, 0, stream_of(x)));
         return y;
     }
-    const int64_t ws_bytes = nfft_hip_adjoint_workspace_bytes(&q, real_input ? 0 : 1, real_output ? 1 : 0);
-    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
-    at::Tensor ws = byte_buffer(ws_bytes, x);
+    at::Tensor ws = workspace_or_raise(nfft_hip_adjoint_workspace_bytes(&q, c.real_input ? 0 : 1, real_output ? 1 : 0), x);
     const at::Tensor plan = get_plan(p, q);
-    check_rc(nfft_hip_adjoint_planned(&q, plan.data_ptr(), xc.data_ptr(), real_input ? 0 : 1, real_output ? 1 : 0,
-                                      y.data_ptr(), ws.data_ptr(), ws_bytes, stream_of(x)));
+    check_rc(nfft_hip_adjoint_planned(&q, plan.data_ptr(), xc.data_ptr(), c.real_input ? 0 : 1, real_output ? 1 : 0,
+                                      y.data_ptr(), ws.data_ptr(), ws.numel(), stream_of(x)));
     return y;
 }
 
@@ -381,36 +454,22 @@ at::Tensor nfft_forward(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> 
 {
     TORCH_CHECK(x.is_cuda(), "torch_nfft.nfft_forward is currently only implemented for GPU tensors");
     const Points p = check_points(pos, opt_batch, "(*out_batch)");
-    const bool real_input = real_dtype(x);  // check_spectral_coeffs_input, core_cuda.cu:89-115
-    CHECK_INPUT(x.dim() >= p.dim + 1);
-    CHECK_INPUT(x.size(0) == p.B);
-    CHECK_INPUT(x.device() == pos.device());
-    const int64_t N = x.size(1);
-    CHECK_INPUT(N >= 2);
-    for (int d = 2; d <= p.dim; ++d) CHECK_INPUT(x.size(d) == N);
-    int64_t C = 1;
-    std::vector<int64_t> shape{p.n};
-    for (int64_t d = p.dim + 1; d < x.dim(); ++d) {
-        C *= x.size(d);
-        shape.push_back(x.size(d));
-    }
-    at::Tensor y = at::empty(shape, x.options().dtype(real_output ? at::kFloat : at::kComplexFloat));
+    const Coeffs c = check_spectral(x, p);
+    at::Tensor y = at::empty(c.shape({p.n}), x.options().dtype(real_output ? at::kFloat : at::kComplexFloat));
     if (y.numel() == 0) return y;
     const at::Tensor xc = x.contiguous();
-    const nfft_hip_problem q = problem(p, C, N, m);
+    const nfft_hip_problem q = problem(p, c.C, c.N, m);
     c10::DeviceGuard guard(x.device());
     if (!nfft_hip_plan_needed(&q)) {
-        check_rc(nfft_hip_forward(&q, p.pos.data_ptr<float>(), xc.data_ptr(), real_input ? 0 : 1,
+        check_rc(nfft_hip_forward(&q, p.pos.data_ptr<float>(), xc.data_ptr(), c.real_input ? 0 : 1,
                                   p.batch.defined() ? p.batch.data_ptr<int64_t>() : nullptr, real_output ? 1 : 0,
                                   y.data_ptr(), nullptr, 0, stream_of(x)));
         return y;
     }
-    const int64_t ws_bytes = nfft_hip_forward_workspace_bytes(&q, real_input ? 0 : 1, real_output ? 1 : 0);
-    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
-    at::Tensor ws = byte_buffer(ws_bytes, x);
+    at::Tensor ws = workspace_or_raise(nfft_hip_forward_workspace_bytes(&q, c.real_input ? 0 : 1, real_output ? 1 : 0), x);
     const at::Tensor plan = get_plan(p, q);
-    check_rc(nfft_hip_forward_planned(&q, plan.data_ptr(), xc.data_ptr(), real_input ? 0 : 1, real_output ? 1 : 0,
-                                      y.data_ptr(), ws.data_ptr(), ws_bytes, stream_of(x)));
+    check_rc(nfft_hip_forward_planned(&q, plan.data_ptr(), xc.data_ptr(), c.real_input ? 0 : 1, real_output ? 1 : 0,
+                                      y.data_ptr(), ws.data_ptr(), ws.numel(), stream_of(x)));
     return y;
 }
 
@@ -423,16 +482,8 @@ at::Tensor nfft_forward_grad_points(at::Tensor pos, at::Tensor x, c10::optional<
 {
     TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_forward_grad_points is only implemented for GPU tensors");
     const Points p = check_points(pos, opt_batch, "(*out_batch)");
-    const bool real_input = real_dtype(x);
-    CHECK_INPUT(x.dim() >= p.dim + 1);
-    CHECK_INPUT(x.size(0) == p.B);
-    CHECK_INPUT(x.device() == pos.device());
-    const int64_t N = x.size(1);
-    CHECK_INPUT(N >= 2);
-    for (int d = 2; d <= p.dim; ++d) CHECK_INPUT(x.size(d) == N);
-    int64_t C = 1;
-    for (int64_t d = p.dim + 1; d < x.dim(); ++d) C *= x.size(d);
-    const int64_t Cr = real_output ? C : 2 * C;
+    const Coeffs c = check_spectral(x, p);
+    const int64_t C = c.C, Cr = real_output ? C : 2 * C;
     CHECK_INPUT(w.is_cuda() && w.device() == pos.device());
     CHECK_INPUT(w.scalar_type() == at::kFloat);
     CHECK_INPUT(w.numel() == p.n * Cr);
@@ -440,15 +491,13 @@ at::Tensor nfft_forward_grad_points(at::Tensor pos, at::Tensor x, c10::optional<
     if (p.n == 0) return dpos;
     if (C == 0) return dpos.zero_();
     const at::Tensor xc = x.contiguous(), wc = w.contiguous();
-    const nfft_hip_problem q = problem(p, C, N, m);
+    const nfft_hip_problem q = problem(p, C, c.N, m);
     c10::DeviceGuard guard(x.device());
-    const int64_t ws_bytes = nfft_hip_forward_grad_workspace_bytes(&q, real_input ? 0 : 1, real_output ? 1 : 0);
-    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
-    at::Tensor ws = byte_buffer(ws_bytes, x);
+    at::Tensor ws = workspace_or_raise(nfft_hip_forward_grad_workspace_bytes(&q, c.real_input ? 0 : 1, real_output ? 1 : 0), x);
     const at::Tensor plan = get_plan(p, q);
-    check_rc(nfft_hip_forward_grad_points_planned(&q, plan.data_ptr(), xc.data_ptr(), real_input ? 0 : 1,
+    check_rc(nfft_hip_forward_grad_points_planned(&q, plan.data_ptr(), xc.data_ptr(), c.real_input ? 0 : 1,
                                                   real_output ? 1 : 0, wc.data_ptr<float>(), dpos.data_ptr<float>(),
-                                                  ws.data_ptr(), ws_bytes, stream_of(x)));
+                                                  ws.data_ptr(), ws.numel(), stream_of(x)));
     return dpos;
 }
 
@@ -462,16 +511,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> nfft_forward_grad_points_backward
 {
     TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_forward_grad_points_backward is only implemented for GPU tensors");
     const Points p = check_points(pos, opt_batch, "(*out_batch)");
-    const bool real_input = real_dtype(x);
-    CHECK_INPUT(x.dim() >= p.dim + 1);
-    CHECK_INPUT(x.size(0) == p.B);
-    CHECK_INPUT(x.device() == pos.device());
-    const int64_t N = x.size(1);
-    CHECK_INPUT(N >= 2);
-    for (int d = 2; d <= p.dim; ++d) CHECK_INPUT(x.size(d) == N);
-    int64_t C = 1;
-    for (int64_t d = p.dim + 1; d < x.dim(); ++d) C *= x.size(d);
-    const int64_t Cr = real_output ? C : 2 * C;
+    const Coeffs c = check_spectral(x, p);
+    const int64_t C = c.C, Cr = real_output ? C : 2 * C;
     CHECK_INPUT(w.is_cuda() && w.device() == pos.device());
     CHECK_INPUT(w.scalar_type() == at::kFloat);
     CHECK_INPUT(w.numel() == p.n * Cr);
@@ -489,23 +530,21 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> nfft_forward_grad_points_backward
         return {dx, dw, dp};
     }
     const at::Tensor xc = x.contiguous(), wc = w.contiguous(), vc = v.contiguous();
-    const nfft_hip_problem q = problem(p, C, N, m);
+    const nfft_hip_problem q = problem(p, C, c.N, m);
     c10::DeviceGuard guard(x.device());
-    const int64_t ws_bytes = nfft_hip_forward_grad_points_backward_workspace_bytes(&q, real_input ? 0 : 1, real_output ? 1 : 0);
-    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
-    at::Tensor ws = byte_buffer(ws_bytes, x);
+    at::Tensor ws = workspace_or_raise(
+        nfft_hip_forward_grad_points_backward_workspace_bytes(&q, c.real_input ? 0 : 1, real_output ? 1 : 0), x);
     const at::Tensor plan = get_plan(p, q);
     check_rc(nfft_hip_forward_grad_points_backward_planned(
-        &q, plan.data_ptr(), xc.data_ptr(), real_input ? 0 : 1, real_output ? 1 : 0, wc.data_ptr<float>(),
+        &q, plan.data_ptr(), xc.data_ptr(), c.real_input ? 0 : 1, real_output ? 1 : 0, wc.data_ptr<float>(),
         vc.data_ptr<float>(), need_xhat ? dx.data_ptr() : nullptr, need_w ? dw.data_ptr<float>() : nullptr,
-        need_pos ? dp.data_ptr<float>() : nullptr, ws.data_ptr(), ws_bytes, stream_of(x)));
+        need_pos ? dp.data_ptr<float>() : nullptr, ws.data_ptr(), ws.numel(), stream_of(x)));
     return {dx, dw, dp};
 }
 
 // Inputs of a fast summation, checked as the reference does (core_cuda.cu:535-590), and its two problems.
-struct Fastsum {
-    Points ps, pt;
-    bool shared, real_coeffs, real_input;
+struct Fastsum : PointPair {
+    bool real_coeffs, real_input;
     int64_t N, C;
     std::vector<int64_t> out_shape;  // [n_t, *x.shape[1:]]
     nfft_hip_problem qs, qt;
@@ -518,30 +557,17 @@ Fastsum check_fastsum(const at::Tensor &sources, const at::Tensor &targets, cons
     TORCH_CHECK(x.is_cuda(), "torch_nfft.nfft_fastsum is currently only implemented for GPU tensors");
     TORCH_CHECK(coeffs.is_cuda(), "coeffs must be CUDA tensor");
     Fastsum f;
-    f.ps = check_points(sources, opt_source_batch, "(*out_batch)");
-    const bool same_tensor = sources.is_same(targets);
-    const bool same_batch = (!opt_source_batch.has_value() && !opt_target_batch.has_value()) ||
-                            (opt_source_batch.has_value() && opt_target_batch.has_value() &&
-                             opt_source_batch->is_same(*opt_target_batch));
-    f.shared = same_tensor && same_batch;  // core_cuda.cu:552-564
-    f.pt = f.shared ? f.ps : check_points(targets, opt_target_batch, "(*out_batch)");
-    CHECK_INPUT(f.pt.dim == f.ps.dim);
-    CHECK_INPUT(f.pt.B == f.ps.B);  // core_cuda.cu:566-568
+    static_cast<PointPair &>(f) = check_point_pair(sources, targets, opt_source_batch, opt_target_batch);
     CHECK_INPUT(coeffs.dim() == f.ps.dim);  // core_cuda.cu:585-590
     f.N = coeffs.size(0);
     for (int d = 1; d < f.ps.dim; ++d) CHECK_INPUT(coeffs.size(d) == f.N);
     f.real_coeffs = real_dtype(coeffs);
-    f.real_input = real_dtype(x);
-    CHECK_INPUT(x.dim() >= 1);
-    CHECK_INPUT(x.size(0) == f.ps.n);
+    const Coeffs cx = check_spatial(x, f.ps.n);
     CHECK_INPUT(x.device() == sources.device() && targets.device() == sources.device() &&
                 coeffs.device() == sources.device());
-    f.C = 1;
-    f.out_shape = {f.pt.n};
-    for (int64_t d = 1; d < x.dim(); ++d) {
-        f.C *= x.size(d);
-        f.out_shape.push_back(x.size(d));
-    }
+    f.real_input = cx.real_input;
+    f.C = cx.C;
+    f.out_shape = cx.shape({f.pt.n});
     f.qs = problem(f.ps, f.C, f.N, m, NFFT_HIP_POINTS_IN_QUARTER_BALL);
     f.qt = problem(f.pt, f.C, f.N, m, NFFT_HIP_POINTS_IN_QUARTER_BALL);
     return f;
@@ -563,9 +589,9 @@ at::Tensor fastsum_run(const at::Tensor &x, const at::Tensor &coeffs, const Fast
     void *bp = band ? band->data_ptr() : nullptr;
     c10::DeviceGuard guard(x.device());
     const bool planned = nfft_hip_plan_needed(&f.qs) != 0 || nfft_hip_plan_needed(&f.qt) != 0;
-    const int64_t ws_bytes = nfft_hip_fastsum_workspace_bytes(&f.qs, &f.qt, f.real_input ? 0 : 1, f.shared ? 1 : 0, planned ? 1 : 0);
-    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
-    at::Tensor ws = byte_buffer(ws_bytes, x);
+    at::Tensor ws = workspace_or_raise(
+        nfft_hip_fastsum_workspace_bytes(&f.qs, &f.qt, f.real_input ? 0 : 1, f.shared ? 1 : 0, planned ? 1 : 0), x);
+    const int64_t ws_bytes = ws.numel();
     const Points &ps = f.ps, &pt = f.pt;
     if (!planned) {  // two fused kernels on the caller's points (1-D, grid in LDS): no plans
         const float *spos = ps.pos.data_ptr<float>(), *tpos = pt.pos.data_ptr<float>();
@@ -649,9 +675,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> nfft_fastsum_backward(
     const at::Tensor cc = f.real_coeffs ? coeffs.contiguous() : coeffs.conj_physical().contiguous();
     const at::Tensor bc = want_band ? band->contiguous() : at::Tensor();
     c10::DeviceGuard guard(x.device());
-    const int64_t ws_bytes = nfft_hip_fastsum_grad_workspace_bytes(&f.qs, &f.qt, f.real_input ? 0 : 1);
-    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
-    at::Tensor ws = byte_buffer(ws_bytes, x);
+    at::Tensor ws = workspace_or_raise(nfft_hip_fastsum_grad_workspace_bytes(&f.qs, &f.qt, f.real_input ? 0 : 1), x);
     // (gradient gathers always run on plans: on the small-grid routes the forward pass made none and they are built here)
     const at::Tensor plan_s = get_plan(f.ps, f.qs);
     const at::Tensor plan_t = f.shared ? plan_s : get_plan(f.pt, f.qt);
@@ -659,7 +683,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> nfft_fastsum_backward(
                                                f.real_input ? 0 : 1, dyc.data_ptr(), cc.data_ptr(), f.real_coeffs ? 0 : 1,
                                                want_band ? bc.data_ptr() : nullptr, need_x ? dx.data_ptr() : nullptr,
                                                need_sources ? ds.data_ptr<float>() : nullptr,
-                                               need_targets ? dt.data_ptr<float>() : nullptr, ws.data_ptr(), ws_bytes,
+                                               need_targets ? dt.data_ptr<float>() : nullptr, ws.data_ptr(), ws.numel(),
                                                stream_of(x)));
     return {dx, ds, dt};
 }
@@ -693,10 +717,8 @@ at::Tensor nfft_toeplitz_kernel(at::Tensor t)
     at::Tensor K = at::empty(t.sizes(), t.options().dtype(at::kFloat));
     const nfft_hip_problem q = toeplitz_problem(dim, B, M / 2, 1);
     c10::DeviceGuard guard(t.device());
-    const int64_t ws_bytes = nfft_hip_toeplitz_kernel_workspace_bytes(&q);
-    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
-    at::Tensor ws = byte_buffer(ws_bytes, t);
-    check_rc(nfft_hip_toeplitz_kernel(&q, tc.data_ptr(), K.data_ptr<float>(), ws.data_ptr(), ws_bytes, stream_of(t)));
+    at::Tensor ws = workspace_or_raise(nfft_hip_toeplitz_kernel_workspace_bytes(&q), t);
+    check_rc(nfft_hip_toeplitz_kernel(&q, tc.data_ptr(), K.data_ptr<float>(), ws.data_ptr(), ws.numel(), stream_of(t)));
     return K;
 }
 
@@ -725,34 +747,71 @@ at::Tensor nfft_normal(at::Tensor kernel, at::Tensor x)
     if ((uintptr_t)kc.data_ptr() & 15u) kc = kc.clone();  // (a view at an odd offset: the multiply loads 16 bytes)
     const nfft_hip_problem q = toeplitz_problem(dim, B, N, C);
     c10::DeviceGuard guard(x.device());
-    const int64_t ws_bytes = nfft_hip_toeplitz_workspace_bytes(&q);
-    if (ws_bytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
-    at::Tensor ws = byte_buffer(ws_bytes, x);
+    at::Tensor ws = workspace_or_raise(nfft_hip_toeplitz_workspace_bytes(&q), x);
     check_rc(nfft_hip_toeplitz_apply(&q, kc.data_ptr<float>(), xc.data_ptr(), real_input ? 0 : 1, y.data_ptr(),
-                                     ws.data_ptr(), ws_bytes, stream_of(x)));
+                                     ws.data_ptr(), ws.numel(), stream_of(x)));
     return y;
 }
 
 // ---- near field of the fast summation for singular kernels (not in the reference) --------------
-// A point set ordered by (point set, cell) for nfft_hip_nearfield: the key of include/nfft_hip.h, one stable sort and the
+// A point set ordered by (point set, cell) for the pair kernels: the keys of include/nfft_hip.h, one stable sort and the
 // first point of every cell by a sorted search.  Device work on the current stream only: no read-back.
 struct CellOrder {
-    at::Tensor pos, order, start;  // [n, dim] float32 in cell order; [n] int64: the caller's row; [B G^dim + 1] int32
+    at::Tensor pos, order, start;  // [n, dim] float32 in cell order; [n] int64: the caller's row; [B prod G + 1] int32
 };
 
-CellOrder cell_order(const Points &p, int64_t G, int64_t cells_per_set)
+// Axis a has G[a] cells: cell = floor((pos[a] + shift) * scale[a]), clamped; the first axis is the fastest of the key.
+//   nfft_hip_nearfield:       the ball of radius 1/4, cells of edge 1 / (2 G):    shift 1/4, scale 2 G
+//   nfft_hip_ewald_near:      pos reduced to [-1/2, 1/2)^3, cells of edge 1 / G:   shift 1/2, scale G
+//   nfft_hip_ewald_near_box:  the same with a cell count per axis
+CellOrder cell_order(const at::Tensor &pos, const at::Tensor &batch, int64_t B, double shift, const int64_t *scale,
+                     const int64_t *G, int dim)
 {
-    const at::Tensor cell = ((p.pos + 0.25) * (double)(2 * G)).floor().clamp(0, G - 1).to(at::kLong);
-    at::Tensor key = cell.select(1, 0);
-    int64_t stride = G;
-    for (int a = 1; a < p.dim; ++a, stride *= G) key = key + cell.select(1, a) * stride;
-    if (p.batch.defined()) key = key + p.batch * cells_per_set;
+    at::Tensor key;
+    int64_t stride = 1;
+    for (int a = 0; a < dim; ++a) {
+        const at::Tensor cell = ((pos.select(1, a) + shift) * (double)scale[a]).floor().clamp(0, G[a] - 1).to(at::kLong);
+        key = a == 0 ? cell : key + cell * stride;
+        stride *= G[a];
+    }
+    if (batch.defined()) key = key + batch * stride;
     const auto sorted = at::sort(key, /*stable=*/true, /*dim=*/0, /*descending=*/false);
     CellOrder o;
     o.order = std::get<1>(sorted);
-    o.start = at::searchsorted(std::get<0>(sorted), at::arange(p.B * cells_per_set + 1, key.options()), /*out_int32=*/true);
-    o.pos = p.pos.index_select(0, o.order);
+    o.start = at::searchsorted(std::get<0>(sorted), at::arange(B * stride + 1, key.options()), /*out_int32=*/true);
+    o.pos = pos.index_select(0, o.order);
     return o;
+}
+
+CellOrder nearfield_cell_order(const Points &p, int64_t G)
+{
+    const int64_t Ga[3] = {G, G, G}, scale[3] = {2 * G, 2 * G, 2 * G};
+    return cell_order(p.pos, p.batch, p.B, 0.25, scale, Ga, p.dim);
+}
+
+// The near-field problem of `n_in` streamed and `n_out` output points with Cr real columns.  poly: the coefficients of T_I;
+// with gpoly those of T_I'(r) / r for the gradient kernels instead, copied to gpoly[8] (T_I itself is not read then).
+nfft_hip_nearfield_problem nearfield_problem(const Points &ps, int64_t n_in, int64_t n_out, int64_t Cr, int64_t kernel, double c,
+                                             double eps_I, at::ArrayRef<double> poly, double *gpoly = nullptr)
+{
+    nfft_hip_nearfield_problem q;
+    q.dim = ps.dim;
+    q.kernel = (int32_t)kernel;
+    q.poly_terms = (int32_t)poly.size() + (gpoly ? 1 : 0);
+    q.num_sources = n_in;
+    q.num_targets = n_out;
+    q.num_columns = Cr;
+    q.batch_size = ps.B;
+    q.c = c;
+    q.eps_I = eps_I;
+    for (size_t e = 0; e < 8; ++e) {
+        q.poly[e] = 0.0;
+        (gpoly ? gpoly : q.poly)[e] = e < poly.size() ? poly[e] : 0.0;
+    }
+    const int64_t G = nfft_hip_nearfield_cells(q.dim, eps_I, q.batch_size);
+    if (G < 0) check_rc(NFFT_HIP_EINVAL);
+    q.cells_per_axis = (int32_t)G;
+    return q;
 }
 
 // z[i] = sum_{j: same point set, |t_i - s_j| < eps_I} (K(r_ij) - T_I(r_ij)) x[j]; x's type and trailing shape
@@ -761,57 +820,27 @@ at::Tensor nfft_nearfield(at::Tensor sources, at::Tensor targets, at::Tensor x, 
                           at::ArrayRef<double> poly)
 {
     TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_nearfield is currently only implemented for GPU tensors");
-    const Points ps = check_points(sources, opt_source_batch, "(*out_batch)");
-    const bool same_batch = (!opt_source_batch.has_value() && !opt_target_batch.has_value()) ||
-                            (opt_source_batch.has_value() && opt_target_batch.has_value() &&
-                             opt_source_batch->is_same(*opt_target_batch));
-    const bool shared = sources.is_same(targets) && same_batch;
-    const Points pt = shared ? ps : check_points(targets, opt_target_batch, "(*out_batch)");
-    CHECK_INPUT(pt.dim == ps.dim);
-    CHECK_INPUT(pt.B == ps.B);
-    const bool real_input = real_dtype(x);
-    CHECK_INPUT(x.dim() >= 1);
-    CHECK_INPUT(x.size(0) == ps.n);
+    const PointPair pp = check_point_pair(sources, targets, opt_source_batch, opt_target_batch);
+    const Points &ps = pp.ps, &pt = pp.pt;
+    const Coeffs cx = check_spatial(x, ps.n);
     CHECK_INPUT(x.device() == sources.device() && targets.device() == sources.device());
     CHECK_INPUT(poly.size() >= 1 && poly.size() <= 8);
-    int64_t C = 1;
-    std::vector<int64_t> out_shape{pt.n};
-    for (int64_t d = 1; d < x.dim(); ++d) {
-        C *= x.size(d);
-        out_shape.push_back(x.size(d));
-    }
-    nfft_hip_nearfield_problem q;
-    q.dim = ps.dim;
-    q.kernel = (int32_t)kernel;
-    q.poly_terms = (int32_t)poly.size();
-    q.num_sources = ps.n;
-    q.num_targets = pt.n;
-    q.num_columns = real_input ? C : 2 * C;
-    q.batch_size = ps.B;
-    q.c = c;
-    q.eps_I = eps_I;
-    for (size_t e = 0; e < 8; ++e) q.poly[e] = e < poly.size() ? poly[e] : 0.0;
-    const int64_t G = nfft_hip_nearfield_cells(q.dim, eps_I, q.batch_size);
-    if (G < 0) check_rc(NFFT_HIP_EINVAL);
-    q.cells_per_axis = (int32_t)G;
+    const std::vector<int64_t> out_shape = cx.shape({pt.n});
+    const nfft_hip_nearfield_problem q = nearfield_problem(ps, ps.n, pt.n, cx.Cr(), kernel, c, eps_I, poly);
     const int64_t ws_bytes = nfft_hip_nearfield_workspace_bytes(&q);
     if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
-    if (ps.n == 0 || pt.n == 0 || C == 0) return at::zeros(out_shape, x.options());  // an empty sum: no launch
+    if (ps.n == 0 || pt.n == 0 || cx.C == 0) return at::zeros(out_shape, x.options());  // an empty sum: no launch
     c10::DeviceGuard guard(x.device());
-    int64_t cells_per_set = 1;
-    for (int a = 0; a < q.dim; ++a) cells_per_set *= G;
-    const CellOrder os = cell_order(ps, G, cells_per_set);
-    const CellOrder ot = shared ? os : cell_order(pt, G, cells_per_set);
-    const at::Tensor xc = x.contiguous();
-    const at::Tensor xr = (real_input ? xc : at::view_as_real(xc)).reshape({ps.n, q.num_columns}).index_select(0, os.order);
+    const CellOrder os = nearfield_cell_order(ps, q.cells_per_axis);
+    const CellOrder ot = pp.shared ? os : nearfield_cell_order(pt, q.cells_per_axis);
+    const at::Tensor xr = real_rows(x, cx.real_input, ps.n, q.num_columns, os.order);
     // (zeros: a target whose coordinates are not numbers has no cell and is not written)
     at::Tensor z = at::zeros({pt.n, q.num_columns}, x.options().dtype(at::kFloat));
     at::Tensor ws = byte_buffer(ws_bytes, x);
     check_rc(nfft_hip_nearfield(&q, os.pos.data_ptr<float>(), xr.data_ptr<float>(), os.start.data_ptr<int32_t>(),
                                 ot.pos.data_ptr<float>(), ot.order.data_ptr<int64_t>(), ot.start.data_ptr<int32_t>(),
                                 z.data_ptr<float>(), ws.data_ptr(), ws_bytes, stream_of(x)));
-    if (!real_input) z = at::view_as_complex(z.reshape({pt.n, C, 2}));
-    return z.reshape(out_shape);
+    return complex_back(z, cx.real_input, out_shape);
 }
 
 // The gradient of that sum at the targets and its transpose, g = (K' - T_I') / r:
@@ -824,57 +853,25 @@ at::Tensor nfft_nearfield_gradient(at::Tensor sources, at::Tensor targets, at::T
                                    int64_t kernel, double c, double eps_I, at::ArrayRef<double> poly, bool transpose)
 {
     TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_nearfield_gradient is currently only implemented for GPU tensors");
-    const Points ps = check_points(sources, opt_source_batch, "(*out_batch)");
-    const bool same_batch = (!opt_source_batch.has_value() && !opt_target_batch.has_value()) ||
-                            (opt_source_batch.has_value() && opt_target_batch.has_value() &&
-                             opt_source_batch->is_same(*opt_target_batch));
-    const bool shared = sources.is_same(targets) && same_batch;
-    const Points pt = shared ? ps : check_points(targets, opt_target_batch, "(*out_batch)");
-    CHECK_INPUT(pt.dim == ps.dim);
-    CHECK_INPUT(pt.B == ps.B);
+    const PointPair pp = check_point_pair(sources, targets, opt_source_batch, opt_target_batch);
+    const Points &ps = pp.ps, &pt = pp.pt;
     const Points &pin = transpose ? pt : ps, &pout = transpose ? ps : pt;  // streamed side, output side
     const int64_t dim = ps.dim;
-    const bool real_input = real_dtype(x);
-    const int64_t lead = transpose ? 2 : 1;
-    CHECK_INPUT(x.dim() >= lead);
-    CHECK_INPUT(x.size(0) == pin.n);
+    const Coeffs cx = check_spatial(x, pin.n, transpose ? 2 : 1);
     if (transpose) CHECK_INPUT(x.size(1) == dim);
     CHECK_INPUT(x.device() == sources.device() && targets.device() == sources.device());
     CHECK_INPUT(poly.size() >= 1 && poly.size() <= 7);
-    int64_t C = 1;
-    std::vector<int64_t> out_shape{pout.n};
-    if (!transpose) out_shape.push_back(dim);
-    for (int64_t d = lead; d < x.dim(); ++d) {
-        C *= x.size(d);
-        out_shape.push_back(x.size(d));
-    }
-    nfft_hip_nearfield_problem q;
-    q.dim = (int32_t)dim;
-    q.kernel = (int32_t)kernel;
-    q.poly_terms = (int32_t)poly.size() + 1;
-    q.num_sources = pin.n;
-    q.num_targets = pout.n;
-    q.num_columns = real_input ? C : 2 * C;
-    q.batch_size = ps.B;
-    q.c = c;
-    q.eps_I = eps_I;
-    for (size_t e = 0; e < 8; ++e) q.poly[e] = 0.0;  // (T_I itself is not read)
-    double gpoly[8] = {0.0};
-    for (size_t e = 0; e < poly.size(); ++e) gpoly[e] = poly[e];
-    const int64_t G = nfft_hip_nearfield_cells(q.dim, eps_I, q.batch_size);
-    if (G < 0) check_rc(NFFT_HIP_EINVAL);
-    q.cells_per_axis = (int32_t)G;
+    const std::vector<int64_t> out_shape = transpose ? cx.shape({pout.n}) : cx.shape({pout.n, dim});
+    double gpoly[8];
+    const nfft_hip_nearfield_problem q = nearfield_problem(ps, pin.n, pout.n, cx.Cr(), kernel, c, eps_I, poly, gpoly);
     const int64_t ws_bytes = nfft_hip_nearfield_gradient_workspace_bytes(&q);
     if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
-    if (ps.n == 0 || pt.n == 0 || C == 0) return at::zeros(out_shape, x.options());  // an empty sum: no launch
+    if (ps.n == 0 || pt.n == 0 || cx.C == 0) return at::zeros(out_shape, x.options());  // an empty sum: no launch
     c10::DeviceGuard guard(x.device());
-    int64_t cells_per_set = 1;
-    for (int a = 0; a < q.dim; ++a) cells_per_set *= G;
-    const CellOrder oin = cell_order(pin, G, cells_per_set);
-    const CellOrder oout = shared ? oin : cell_order(pout, G, cells_per_set);
+    const CellOrder oin = nearfield_cell_order(pin, q.cells_per_axis);
+    const CellOrder oout = pp.shared ? oin : nearfield_cell_order(pout, q.cells_per_axis);
     const int64_t in_row = (transpose ? dim : 1) * q.num_columns, out_row = (transpose ? 1 : dim) * q.num_columns;
-    const at::Tensor xc = x.contiguous();
-    const at::Tensor xr = (real_input ? xc : at::view_as_real(xc)).reshape({pin.n, in_row}).index_select(0, oin.order);
+    const at::Tensor xr = real_rows(x, cx.real_input, pin.n, in_row, oin.order);
     // (zeros: an output point whose coordinates are not numbers has no cell and is not written)
     at::Tensor z = at::zeros({pout.n, out_row}, x.options().dtype(at::kFloat));
     at::Tensor ws = byte_buffer(ws_bytes, x);
@@ -882,8 +879,7 @@ at::Tensor nfft_nearfield_gradient(at::Tensor sources, at::Tensor targets, at::T
                                          oin.start.data_ptr<int32_t>(), oout.pos.data_ptr<float>(),
                                          oout.order.data_ptr<int64_t>(), oout.start.data_ptr<int32_t>(), z.data_ptr<float>(),
                                          ws.data_ptr(), ws_bytes, stream_of(x)));
-    if (!real_input) z = at::view_as_complex(z.reshape({pout.n, out_row / 2, 2}));
-    return z.reshape(out_shape);
+    return complex_back(z, cx.real_input, out_shape);
 }
 
 // The gradient of that sum with respect to the points: for z = nfft_nearfield(x) and dy = dL/dz,
@@ -900,57 +896,31 @@ std::tuple<at::Tensor, at::Tensor> nfft_nearfield_point_gradient(at::Tensor sour
                                                                  bool need_sources, bool need_targets)
 {
     TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_nearfield_point_gradient is currently only implemented for GPU tensors");
-    const Points ps = check_points(sources, opt_source_batch, "(*out_batch)");
-    const bool same_batch = (!opt_source_batch.has_value() && !opt_target_batch.has_value()) ||
-                            (opt_source_batch.has_value() && opt_target_batch.has_value() &&
-                             opt_source_batch->is_same(*opt_target_batch));
-    const bool shared = sources.is_same(targets) && same_batch;
-    const Points pt = shared ? ps : check_points(targets, opt_target_batch, "(*out_batch)");
-    CHECK_INPUT(pt.dim == ps.dim);
-    CHECK_INPUT(pt.B == ps.B);
+    const PointPair pp = check_point_pair(sources, targets, opt_source_batch, opt_target_batch);
+    const Points &ps = pp.ps, &pt = pp.pt;
+    const bool shared = pp.shared;
     const int64_t dim = ps.dim;
-    const bool real_input = real_dtype(x);
+    const Coeffs cx = check_spatial(x, ps.n);
+    const bool real_input = cx.real_input;
     CHECK_INPUT(dy.scalar_type() == x.scalar_type());
-    CHECK_INPUT(x.dim() >= 1 && dy.dim() == x.dim());
-    CHECK_INPUT(x.size(0) == ps.n && dy.size(0) == pt.n);
+    CHECK_INPUT(dy.dim() == x.dim() && dy.size(0) == pt.n);
     CHECK_INPUT(x.device() == sources.device() && targets.device() == sources.device() && dy.device() == sources.device());
     CHECK_INPUT(poly.size() >= 1 && poly.size() <= 7);
-    int64_t C = 1;
-    for (int64_t d = 1; d < x.dim(); ++d) {
-        CHECK_INPUT(dy.size(d) == x.size(d));
-        C *= x.size(d);
-    }
-    nfft_hip_nearfield_problem q;
-    q.dim = (int32_t)dim;
-    q.kernel = (int32_t)kernel;
-    q.poly_terms = (int32_t)poly.size() + 1;
-    q.num_sources = ps.n;
-    q.num_targets = pt.n;
-    q.num_columns = real_input ? C : 2 * C;
-    q.batch_size = ps.B;
-    q.c = c;
-    q.eps_I = eps_I;
-    for (size_t e = 0; e < 8; ++e) q.poly[e] = 0.0;  // (T_I itself is not read)
-    double gpoly[8] = {0.0};
-    for (size_t e = 0; e < poly.size(); ++e) gpoly[e] = poly[e];
-    const int64_t G = nfft_hip_nearfield_cells(q.dim, eps_I, q.batch_size);
-    if (G < 0) check_rc(NFFT_HIP_EINVAL);
-    q.cells_per_axis = (int32_t)G;
+    for (int64_t d = 1; d < x.dim(); ++d) CHECK_INPUT(dy.size(d) == x.size(d));
+    double gpoly[8];
+    const nfft_hip_nearfield_problem q = nearfield_problem(ps, ps.n, pt.n, cx.Cr(), kernel, c, eps_I, poly, gpoly);
     if (nfft_hip_nearfield_point_gradient_workspace_bytes(&q) < 0) check_rc(NFFT_HIP_EINVAL);
     const at::TensorOptions opts = sources.options();
     const bool symmetric = shared && need_sources && need_targets;
     // (zeros: an output point whose coordinates are not numbers has no cell and is not written)
     at::Tensor ds = need_sources ? at::zeros({ps.n, dim}, opts) : at::empty({0, dim}, opts);
     at::Tensor dt = need_targets ? at::zeros({pt.n, dim}, opts) : at::empty({0, dim}, opts);
-    if (ps.n == 0 || pt.n == 0 || C == 0 || (!need_sources && !need_targets)) return {ds, dt};  // empty sums: no launch
+    if (ps.n == 0 || pt.n == 0 || cx.C == 0 || (!need_sources && !need_targets)) return {ds, dt};  // empty sums: no launch
     c10::DeviceGuard guard(x.device());
-    int64_t cells_per_set = 1;
-    for (int a = 0; a < q.dim; ++a) cells_per_set *= G;
-    const CellOrder os = cell_order(ps, G, cells_per_set);
-    const CellOrder ot = shared ? os : cell_order(pt, G, cells_per_set);
-    const at::Tensor xc = x.contiguous(), dyc = dy.contiguous();
-    const at::Tensor xr = (real_input ? xc : at::view_as_real(xc)).reshape({ps.n, q.num_columns}).index_select(0, os.order);
-    const at::Tensor dyr = (real_input ? dyc : at::view_as_real(dyc)).reshape({pt.n, q.num_columns}).index_select(0, ot.order);
+    const CellOrder os = nearfield_cell_order(ps, q.cells_per_axis);
+    const CellOrder ot = shared ? os : nearfield_cell_order(pt, q.cells_per_axis);
+    const at::Tensor xr = real_rows(x, real_input, ps.n, q.num_columns, os.order);
+    const at::Tensor dyr = real_rows(dy, real_input, pt.n, q.num_columns, ot.order);
     // one sweep: the streamed side (order, values) and the output side (order, values, result)
     auto sweep = [&](bool sym, const CellOrder &in, const at::Tensor &vin, const CellOrder &o, const at::Tensor &vout,
                      at::Tensor &out) {
@@ -976,19 +946,54 @@ std::tuple<at::Tensor, at::Tensor> nfft_nearfield_point_gradient(at::Tensor sour
 }
 
 // ---- near part of the Ewald sum for the periodic 1/r (not in the reference) --------------------
-// cell_order's sibling for nfft_hip_ewald_near: `pos` already reduced to [-1/2, 1/2)^3, G^3 cells of edge 1/G over the whole
-// torus, the key of include/nfft_hip.h.  Same sort and search; cell_order's own arithmetic is left as it is.
-CellOrder torus_cell_order(const at::Tensor &pos, const at::Tensor &batch, int64_t B, int64_t G)
+// p modulo 1 in [-1/2, 1/2): p - rint(p) is exact in float32 and equals p - floor(p + 1/2) wherever that sum is; what comes
+// out as +1/2 is the point -1/2
+at::Tensor torus_reduce(const at::Tensor &pos)
 {
-    const at::Tensor cell = ((pos + 0.5) * (double)G).floor().clamp(0, G - 1).to(at::kLong);
-    at::Tensor key = cell.select(1, 0) + cell.select(1, 1) * G + cell.select(1, 2) * (G * G);
-    if (batch.defined()) key = key + batch * (G * G * G);
-    const auto sorted = at::sort(key, /*stable=*/true, /*dim=*/0, /*descending=*/false);
-    CellOrder o;
-    o.order = std::get<1>(sorted);
-    o.start = at::searchsorted(std::get<0>(sorted), at::arange(B * G * G * G + 1, key.options()), /*out_int32=*/true);
-    o.pos = pos.index_select(0, o.order);
-    return o;
+    const at::Tensor red = pos - pos.round();
+    return at::where(red >= 0.5, red - 1.0, red);
+}
+
+// The cell order of points on the torus (nfft_hip_ewald_near_box's key; nfft_hip_ewald_near's with one count on every axis)
+CellOrder torus_cell_order(const Points &p, const int32_t *cells)
+{
+    const int64_t G[3] = {cells[0], cells[1], cells[2]};
+    return cell_order(torus_reduce(p.pos), p.batch, p.B, 0.5, G, G, 3);
+}
+
+// The charges x [n, *cols] of the Ewald operators, their pair-sum shapes and the (n, 3, *cols) field's
+struct EwaldInput { Points p; Coeffs cx; std::vector<int64_t> z_shape, f_shape; };
+EwaldInput check_ewald(const at::Tensor &pos, const at::Tensor &x, const c10::optional<at::Tensor> &opt_batch, bool with_field)
+{
+    EwaldInput in;
+    in.p = check_points(pos, opt_batch, "batch");
+    CHECK_INPUT(in.p.dim == 3);
+    in.cx = check_spatial(x, in.p.n);
+    CHECK_INPUT(x.device() == pos.device());
+    in.z_shape = in.cx.shape({in.p.n});
+    in.f_shape = with_field ? in.cx.shape({in.p.n, 3}) : std::vector<int64_t>{0};
+    return in;
+}
+
+nfft_hip_ewald_box_problem ewald_box_problem(const Points &p, int64_t Cr, bool with_field, const std::vector<double> &box,
+                                             double alpha, double r_cut)
+{
+    nfft_hip_ewald_box_problem q;
+    q.with_field = with_field ? 1 : 0;
+    q.num_points = p.n;
+    q.num_columns = Cr;
+    q.batch_size = p.B;
+    q.alpha = alpha;
+    q.r_cut = r_cut;
+    for (int e = 0; e < 6; ++e) q.box[e] = box[e];
+    if (nfft_hip_ewald_box_cells(q.box, r_cut, q.batch_size, q.cells) < 0) check_rc(NFFT_HIP_EINVAL);
+    return q;
+}
+
+// (z, f) [n, Cr] and [n, 3 Cr] float32 back in x's type and shapes
+std::tuple<at::Tensor, at::Tensor> ewald_result(const EwaldInput &in, const at::Tensor &z, const at::Tensor &f, bool with_field)
+{
+    return {complex_back(z, in.cx.real_input, in.z_shape), with_field ? complex_back(f, in.cx.real_input, in.f_shape) : f};
 }
 
 // (z, f): z[i] = sum_{j: same point set, 0 < r_ij < r_cut} erfc(alpha r_ij) / r_ij x[j] with r_ij the length of the minimum
@@ -999,24 +1004,12 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_near(at::Tensor pos, at::Tensor x,
                                                    double alpha, double r_cut, bool with_field)
 {
     TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_near is currently only implemented for GPU tensors");
-    const Points p = check_points(pos, opt_batch, "batch");
-    CHECK_INPUT(p.dim == 3);
-    const bool real_input = real_dtype(x);
-    CHECK_INPUT(x.dim() >= 1);
-    CHECK_INPUT(x.size(0) == p.n);
-    CHECK_INPUT(x.device() == pos.device());
-    int64_t C = 1;
-    std::vector<int64_t> z_shape{p.n}, f_shape{p.n, 3};
-    for (int64_t d = 1; d < x.dim(); ++d) {
-        C *= x.size(d);
-        z_shape.push_back(x.size(d));
-        f_shape.push_back(x.size(d));
-    }
-    if (!with_field) f_shape = {0};
+    const EwaldInput in = check_ewald(pos, x, opt_batch, with_field);
+    const Points &p = in.p;
     nfft_hip_ewald_problem q;
     q.with_field = with_field ? 1 : 0;
     q.num_points = p.n;
-    q.num_columns = real_input ? C : 2 * C;
+    q.num_columns = in.cx.Cr();
     q.batch_size = p.B;
     q.alpha = alpha;
     q.r_cut = r_cut;
@@ -1025,15 +1018,11 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_near(at::Tensor pos, at::Tensor x,
     q.cells_per_axis = (int32_t)G;
     const int64_t ws_bytes = nfft_hip_ewald_near_workspace_bytes(&q);
     if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
-    if (p.n == 0 || C == 0) return {at::zeros(z_shape, x.options()), at::zeros(f_shape, x.options())};  // no launch
+    if (p.n == 0 || in.cx.C == 0) return {at::zeros(in.z_shape, x.options()), at::zeros(in.f_shape, x.options())};  // no launch
     c10::DeviceGuard guard(x.device());
-    // p modulo 1 in [-1/2, 1/2): p - rint(p) is exact in float32 and equals p - floor(p + 1/2) wherever that sum is;
-    // what comes out as +1/2 is the point -1/2
-    at::Tensor red = p.pos - p.pos.round();
-    red = at::where(red >= 0.5, red - 1.0, red);
-    const CellOrder o = torus_cell_order(red, p.batch, p.B, G);
-    const at::Tensor xc = x.contiguous();
-    const at::Tensor xr = (real_input ? xc : at::view_as_real(xc)).reshape({p.n, q.num_columns}).index_select(0, o.order);
+    const int32_t cells[3] = {q.cells_per_axis, q.cells_per_axis, q.cells_per_axis};
+    const CellOrder o = torus_cell_order(p, cells);
+    const at::Tensor xr = real_rows(x, in.cx.real_input, p.n, q.num_columns, o.order);
     // (zeros: a point whose coordinates are not numbers has no cell and is not written)
     const at::TensorOptions opts = x.options().dtype(at::kFloat);
     at::Tensor z = at::zeros({p.n, q.num_columns}, opts);
@@ -1042,74 +1031,26 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_near(at::Tensor pos, at::Tensor x,
     check_rc(nfft_hip_ewald_near(&q, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
                                  o.order.data_ptr<int64_t>(), z.data_ptr<float>(), with_field ? f.data_ptr<float>() : nullptr,
                                  ws.data_ptr(), ws_bytes, stream_of(x)));
-    if (!real_input) {
-        z = at::view_as_complex(z.reshape({p.n, C, 2}));
-        if (with_field) f = at::view_as_complex(f.reshape({p.n, 3 * C, 2}));
-    }
-    return {z.reshape(z_shape), f.reshape(f_shape)};
+    return ewald_result(in, z, f, with_field);
 }
 
 // ---- the same pair sum in an orthorhombic or triclinic box (not in the reference) ---------------
-// torus_cell_order's sibling with a cell count per axis: `pos` fractional and already reduced to [-1/2, 1/2)^3, the key of
-// nfft_hip_ewald_near_box in include/nfft_hip.h
-CellOrder box_cell_order(const at::Tensor &pos, const at::Tensor &batch, int64_t B, const int32_t *G)
-{
-    at::Tensor key;
-    int64_t stride = 1;
-    for (int a = 0; a < 3; ++a) {
-        const at::Tensor cell = ((pos.select(1, a) + 0.5) * (double)G[a]).floor().clamp(0, G[a] - 1).to(at::kLong);
-        key = a == 0 ? cell : key + cell * stride;
-        stride *= G[a];
-    }
-    if (batch.defined()) key = key + batch * stride;
-    const auto sorted = at::sort(key, /*stable=*/true, /*dim=*/0, /*descending=*/false);
-    CellOrder o;
-    o.order = std::get<1>(sorted);
-    o.start = at::searchsorted(std::get<0>(sorted), at::arange(B * stride + 1, key.options()), /*out_int32=*/true);
-    o.pos = pos.index_select(0, o.order);
-    return o;
-}
-
 // (z, f) of nfft_ewald_near in the box A = box (A00, A10, A11, A20, A21, A22; rows = lattice vectors): pos holds FRACTIONAL
 // coordinates, taken modulo 1; r_ij is the length of d_ij = (ds - rint(ds)) A and f is Cartesian.
 std::tuple<at::Tensor, at::Tensor> nfft_ewald_near_box(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch,
                                                        std::vector<double> box, double alpha, double r_cut, bool with_field)
 {
     TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_near_box is currently only implemented for GPU tensors");
-    const Points p = check_points(pos, opt_batch, "batch");
-    CHECK_INPUT(p.dim == 3);
+    const EwaldInput in = check_ewald(pos, x, opt_batch, with_field);
+    const Points &p = in.p;
     CHECK_INPUT(box.size() == 6);
-    const bool real_input = real_dtype(x);
-    CHECK_INPUT(x.dim() >= 1);
-    CHECK_INPUT(x.size(0) == p.n);
-    CHECK_INPUT(x.device() == pos.device());
-    int64_t C = 1;
-    std::vector<int64_t> z_shape{p.n}, f_shape{p.n, 3};
-    for (int64_t d = 1; d < x.dim(); ++d) {
-        C *= x.size(d);
-        z_shape.push_back(x.size(d));
-        f_shape.push_back(x.size(d));
-    }
-    if (!with_field) f_shape = {0};
-    nfft_hip_ewald_box_problem q;
-    q.with_field = with_field ? 1 : 0;
-    q.num_points = p.n;
-    q.num_columns = real_input ? C : 2 * C;
-    q.batch_size = p.B;
-    q.alpha = alpha;
-    q.r_cut = r_cut;
-    for (int e = 0; e < 6; ++e) q.box[e] = box[e];
-    if (nfft_hip_ewald_box_cells(q.box, r_cut, q.batch_size, q.cells) < 0) check_rc(NFFT_HIP_EINVAL);
+    const nfft_hip_ewald_box_problem q = ewald_box_problem(p, in.cx.Cr(), with_field, box, alpha, r_cut);
     const int64_t ws_bytes = nfft_hip_ewald_near_box_workspace_bytes(&q);
     if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
-    if (p.n == 0 || C == 0) return {at::zeros(z_shape, x.options()), at::zeros(f_shape, x.options())};  // no launch
+    if (p.n == 0 || in.cx.C == 0) return {at::zeros(in.z_shape, x.options()), at::zeros(in.f_shape, x.options())};  // no launch
     c10::DeviceGuard guard(x.device());
-    // s modulo 1 in [-1/2, 1/2), as nfft_ewald_near does: what comes out as +1/2 is the point -1/2
-    at::Tensor red = p.pos - p.pos.round();
-    red = at::where(red >= 0.5, red - 1.0, red);
-    const CellOrder o = box_cell_order(red, p.batch, p.B, q.cells);
-    const at::Tensor xc = x.contiguous();
-    const at::Tensor xr = (real_input ? xc : at::view_as_real(xc)).reshape({p.n, q.num_columns}).index_select(0, o.order);
+    const CellOrder o = torus_cell_order(p, q.cells);
+    const at::Tensor xr = real_rows(x, in.cx.real_input, p.n, q.num_columns, o.order);
     // (zeros: a point whose coordinates are not numbers has no cell and is not written)
     const at::TensorOptions opts = x.options().dtype(at::kFloat);
     at::Tensor z = at::zeros({p.n, q.num_columns}, opts);
@@ -1118,11 +1059,7 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_near_box(at::Tensor pos, at::Tenso
     check_rc(nfft_hip_ewald_near_box(&q, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
                                      o.order.data_ptr<int64_t>(), z.data_ptr<float>(),
                                      with_field ? f.data_ptr<float>() : nullptr, ws.data_ptr(), ws_bytes, stream_of(x)));
-    if (!real_input) {
-        z = at::view_as_complex(z.reshape({p.n, C, 2}));
-        if (with_field) f = at::view_as_complex(f.reshape({p.n, 3 * C, 2}));
-    }
-    return {z.reshape(z_shape), f.reshape(f_shape)};
+    return ewald_result(in, z, f, with_field);
 }
 
 // ---- virial tensor of the Ewald sum (not in the reference) --------------------------------------
@@ -1133,38 +1070,20 @@ at::Tensor nfft_ewald_virial_near(at::Tensor pos, at::Tensor x, c10::optional<at
                                   double alpha, double r_cut)
 {
     TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_virial_near is currently only implemented for GPU tensors");
-    const Points p = check_points(pos, opt_batch, "batch");
-    CHECK_INPUT(p.dim == 3);
+    const EwaldInput in = check_ewald(pos, x, opt_batch, false);
+    const Points &p = in.p;
     CHECK_INPUT(box.size() == 6);
-    CHECK_INPUT(x.scalar_type() == at::kFloat);  // (the energy is bilinear: real charges only)
-    CHECK_INPUT(x.dim() >= 1);
-    CHECK_INPUT(x.size(0) == p.n);
-    CHECK_INPUT(x.device() == pos.device());
-    int64_t C = 1;
-    std::vector<int64_t> shape{p.B, 7};
-    for (int64_t d = 1; d < x.dim(); ++d) {
-        C *= x.size(d);
-        shape.push_back(x.size(d));
-    }
-    nfft_hip_ewald_box_problem q;
-    q.with_field = 0;
-    q.num_points = p.n;
-    q.num_columns = C;
-    q.batch_size = p.B;
-    q.alpha = alpha;
-    q.r_cut = r_cut;
-    for (int e = 0; e < 6; ++e) q.box[e] = box[e];
-    if (nfft_hip_ewald_box_cells(q.box, r_cut, q.batch_size, q.cells) < 0) check_rc(NFFT_HIP_EINVAL);
+    CHECK_INPUT(in.cx.real_input);  // (the energy is bilinear: real charges only)
+    const int64_t C = in.cx.C;
+    const std::vector<int64_t> shape = in.cx.shape({p.B, 7});
+    const nfft_hip_ewald_box_problem q = ewald_box_problem(p, C, false, box, alpha, r_cut);
     const int64_t ws_bytes = nfft_hip_ewald_virial_near_workspace_bytes(&q);
     if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
     const at::TensorOptions opts = x.options().dtype(at::kDouble);
     if (p.n == 0 || C == 0) return at::zeros(shape, opts);  // no launch
     c10::DeviceGuard guard(x.device());
-    // s modulo 1 in [-1/2, 1/2), as nfft_ewald_near does: what comes out as +1/2 is the point -1/2
-    at::Tensor red = p.pos - p.pos.round();
-    red = at::where(red >= 0.5, red - 1.0, red);
-    const CellOrder o = box_cell_order(red, p.batch, p.B, q.cells);
-    const at::Tensor xr = x.contiguous().reshape({p.n, C}).index_select(0, o.order);
+    const CellOrder o = torus_cell_order(p, q.cells);
+    const at::Tensor xr = real_rows(x, true, p.n, C, o.order);
     at::Tensor out = at::zeros({p.B, 7, C}, opts);
     at::Tensor ws = byte_buffer(ws_bytes, x);
     check_rc(nfft_hip_ewald_virial_near(&q, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
@@ -1227,8 +1146,7 @@ std::vector<int64_t> cube(int64_t N, int64_t dim)
 at::Tensor coeffs_workspace(int64_t N, int64_t dim, const at::Tensor &like, int64_t &nbytes)
 {
     nbytes = nfft_hip_coeffs_workspace_bytes(N, (int32_t)dim);
-    if (nbytes < 0) check_rc(std::string(nfft_hip_last_error()).rfind("Input mismatch", 0) == 0 ? NFFT_HIP_EINVAL : NFFT_HIP_EFFT);
-    return byte_buffer(nbytes, like);
+    return workspace_or_raise(nbytes, like);
 }
 
 at::Tensor gaussian_analytic_coeffs(double sigma, int64_t N, int64_t dim)
