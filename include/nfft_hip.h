@@ -448,6 +448,24 @@ int nfft_hip_ewald_near_box(const nfft_hip_ewald_box_problem *p, const float *po
                             const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
                             int64_t workspace_bytes, void *stream);
 
+/* ---- near part of the dispersion Ewald sum, the periodic 1/r^6 (no reference counterpart) ----
+ * The sum of c_j / r^6 over all images is split with a = alpha r: the smooth part is summed on the whole torus with
+ * nfft_hip_fastsum (coefficients pi^(3/2) alpha^3 f(b) / (3 V), b = pi |kappa| / alpha, f(b) = (1 - 2 b^2) exp(-b^2) +
+ * 2 sqrt(pi) b^3 erfc(b), k = 0 included, set up by the host side), and these two entry points add the short-ranged rest:
+ *     z[i, c]        = sum_{j in the point set of i, 0 < r_ij < r_cut} exp(-a^2) (1 + a^2 + a^4 / 2) / r_ij^6  xr[j, c]
+ *     field[i, a, c] = sum_j exp(-a^2) (6 + 6 a^2 + 3 a^4 + a^6) / r_ij^8  d_ij[a] xr[j, c]   (with_field = 1; minus the gradient)
+ * on the unit torus and in a box.  Problem structs, arguments, the order of the points, validation, error codes and
+ * determinism are EXACTLY those of nfft_hip_ewald_near and nfft_hip_ewald_near_box, and so is the workspace: there are no
+ * cell or workspace functions of their own, nfft_hip_ewald_near_cells / nfft_hip_ewald_near_workspace_bytes and
+ * nfft_hip_ewald_box_cells / nfft_hip_ewald_near_box_workspace_bytes serve both sweeps.  In float32 1 / r^8 overflows below
+ * r ~ 1.6e-5: closer pairs give inf. */
+int nfft_hip_ewald_dispersion_near(const nfft_hip_ewald_problem *p, const float *points, const float *xr,
+                                   const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
+                                   int64_t workspace_bytes, void *stream);
+int nfft_hip_ewald_dispersion_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                                       const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
+                                       int64_t workspace_bytes, void *stream);
+
 /* ---- virial tensor of the Ewald sum (no reference counterpart) ----
  * For the homogeneous strain A -> A (1 + eps) at fixed fractional coordinates the virial W_ab = -dU / d eps_ab of the
  * energy U = 1/2 sum_i q_i phi_i is a pair sum, a sum over the frequencies and a background term.  These two entry points

@@ -31,6 +31,15 @@ box (the identity box without --box) on the same charges: nfft_ewald_virial besi
 the virial kernel (nfft_hip_ewald_virial_near on restated plumbing, its second-level sum included) beside the field loop,
 in picoseconds per tested pair; and the far reduction (ops.nfft_ewald_virial_far) beside the torch composition
 ((band.abs() ** 2)[..., None] * coef7).sum(...) on the same band, with the bytes of band per second that each reaches.
+
+    python scripts/bench_ewald.py --dispersion [...]
+
+times the dispersion sum 1/r^6 in the unit cube instead: the same points and r_c, coefficients in
+[0.5, 1.5), alpha and N by DispersionSplitting.from_tolerance(tol, r_c); nfft_ewald_dispersion without and with the field, its
+far field, the near operator ops.nfft_ewald_dispersion_near and its pair loop on its own (nfft_hip_ewald_dispersion_near
+on restated plumbing), and beside it, in the same run on the same sorted points, cells and r_c, the Coulomb pair loop
+(nfft_hip_ewald_near with the alpha of EwaldSplitting.from_tolerance): the same pairs are tested and the same pass the cut,
+what differs is the pair weight.
 """
 import argparse
 import ctypes
@@ -313,6 +322,66 @@ def run(lib, n, args):
                       "value_over_one_over_r": round(ns / ns_y, 3), "field_over_one_over_r": round(ns_f / ns_y, 3)}))
 
 
+def run_dispersion(lib, n, args):
+    m = 4
+    r_c = min((3.0 * args.neighbours / (4.0 * math.pi * n)) ** (1.0 / 3.0), 1.0 / 3.0)
+    sp = tn.DispersionSplitting.from_tolerance(args.tol, r_c)
+    coulomb_alpha = math.sqrt(-math.log(args.tol)) / r_c  # (EwaldSplitting.from_tolerance's)
+    rng = np.random.default_rng(0)
+    v = (rng.random((n, 3)) - 0.5).astype(np.float32)
+    v[v >= 0.5] = -0.5  # (rounded up to the face: the same point)
+    pos = torch.from_numpy(v).cuda()
+    c = torch.from_numpy((rng.random(n) + 0.5).astype(np.float32)).cuda()
+    G = int(lib.nfft_hip_ewald_near_cells(r_c, 1))
+    wrapped, _ = pairs_tested(v, G)
+    whole = median_ms(lambda: tn.nfft_ewald_dispersion(c, pos, splitting=sp, cutoff=m), args.reps)
+    whole_f = median_ms(lambda: tn.nfft_ewald_dispersion(c, pos, splitting=sp, cutoff=m, field=True), args.reps)
+    far = median_ms(lambda: tn.nfft_fastsum(c, sp.coeffs, pos, cutoff=m), args.reps)
+    near = median_ms(lambda: tn.ops.nfft_ewald_dispersion_near(pos, c, None, sp.alpha, r_c, False), args.reps)
+    near_f = median_ms(lambda: tn.ops.nfft_ewald_dispersion_near(pos, c, None, sp.alpha, r_c, True), args.reps)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    spos, order, start = cell_order(pos, G, 0.5, G)
+    xs = c.index_select(0, order).reshape(n, 1).contiguous()
+    z, f = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+    zc, fc = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+    loops, coulomb = {}, {}
+    for with_field in (0, 1):
+        p = _lib.EwaldProblem(cells_per_axis=G, with_field=with_field, num_points=n, num_columns=1, batch_size=1,
+                              alpha=sp.alpha, r_cut=r_c)
+        pc = _lib.EwaldProblem(cells_per_axis=G, with_field=with_field, num_points=n, num_columns=1, batch_size=1,
+                               alpha=coulomb_alpha, r_cut=r_c)
+        nbytes = lib.nfft_hip_ewald_near_workspace_bytes(ctypes.byref(p))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+
+        def loop():
+            _lib.check(lib.nfft_hip_ewald_dispersion_near(ctypes.byref(p), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                                          order.data_ptr(), z.data_ptr(), f.data_ptr(), ws.data_ptr(), nbytes,
+                                                          stream))
+
+        def coulomb_loop():
+            _lib.check(lib.nfft_hip_ewald_near(ctypes.byref(pc), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                               order.data_ptr(), zc.data_ptr(), fc.data_ptr(), ws.data_ptr(), nbytes, stream))
+
+        loops[with_field] = median_ms(loop, args.reps)
+        coulomb[with_field] = median_ms(coulomb_loop, args.reps)
+    zo, fo = tn.ops.nfft_ewald_dispersion_near(pos, c, None, sp.alpha, r_c, True)
+    assert torch.equal(zo, z[:, 0]) and torch.equal(fo, f), "the restated plumbing must give the operator's bits"
+    tn.ops.check_status()
+    print(json.dumps({"bench": "ewald_dispersion", "points": n, "neighbours": args.neighbours, "tol": args.tol,
+                      "r_cut": round(r_c, 5), "alpha": round(sp.alpha, 3), "N": sp.bandwidth, "m": m, "cells_per_axis": G,
+                      "coulomb_alpha": round(coulomb_alpha, 3),
+                      "dispersion_ms": round(whole, 4), "dispersion_field_ms": round(whole_f, 4), "far_ms": round(far, 4),
+                      "near_ms": round(near, 4), "near_field_ms": round(near_f, 4),
+                      "pair_loop_ms": round(loops[0], 4), "pair_loop_field_ms": round(loops[1], 4),
+                      "coulomb_pair_loop_ms": round(coulomb[0], 4), "coulomb_pair_loop_field_ms": round(coulomb[1], 4),
+                      "pairs_tested": wrapped,
+                      "ps_per_pair": round(loops[0] * 1e9 / wrapped, 3), "ps_per_pair_field": round(loops[1] * 1e9 / wrapped, 3),
+                      "coulomb_ps_per_pair": round(coulomb[0] * 1e9 / wrapped, 3),
+                      "coulomb_ps_per_pair_field": round(coulomb[1] * 1e9 / wrapped, 3),
+                      "dispersion_over_coulomb": round(loops[0] / coulomb[0], 3),
+                      "dispersion_over_coulomb_field": round(loops[1] / coulomb[1], 3)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, nargs="+", default=[100000, 1000000])
@@ -322,12 +391,18 @@ def main():
     ap.add_argument("--box", type=lambda t: [float(e) for e in t.split(",")], default=None,
                     help="a,b,c (orthorhombic) or A00,A10,A11,A20,A21,A22 (lower triangular, rows = lattice vectors)")
     ap.add_argument("--virial", action="store_true", help="add a row for nfft_ewald_virial and its two reductions")
+    ap.add_argument("--dispersion", action="store_true", help="time the dispersion sum 1/r^6 (unit cube) instead")
     args = ap.parse_args()
     if args.box is not None and len(args.box) not in (3, 6):
         ap.error("--box takes three or six comma-separated numbers")
+    if args.dispersion and (args.box is not None or args.virial):
+        ap.error("--dispersion times the unit cube and goes with neither --box nor --virial")
     torch.cuda.set_device(0)
     lib = _lib.load()
     for n in args.points:
+        if args.dispersion:
+            run_dispersion(lib, n, args)
+            continue
         (run if args.box is None else run_box)(lib, n, args)
         if args.virial:
             run_virial(lib, n, args)

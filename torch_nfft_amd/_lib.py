@@ -63,6 +63,8 @@ SYMBOLS = (
     "nfft_hip_ewald_box_cells",
     "nfft_hip_ewald_near_box_workspace_bytes",
     "nfft_hip_ewald_near_box",
+    "nfft_hip_ewald_dispersion_near",
+    "nfft_hip_ewald_dispersion_near_box",
     "nfft_hip_ewald_virial_near_workspace_bytes",
     "nfft_hip_ewald_virial_near",
     "nfft_hip_ewald_virial_far_workspace_bytes",
@@ -253,6 +255,10 @@ def load():
     lib.nfft_hip_ewald_near_box_workspace_bytes.restype = i64
     lib.nfft_hip_ewald_near_box.argtypes = [ctypes.POINTER(EwaldBoxProblem), vp, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.nfft_hip_ewald_near_box.restype = ci
+    lib.nfft_hip_ewald_dispersion_near.argtypes = [ctypes.POINTER(EwaldProblem), vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.nfft_hip_ewald_dispersion_near.restype = ci
+    lib.nfft_hip_ewald_dispersion_near_box.argtypes = [ctypes.POINTER(EwaldBoxProblem), vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.nfft_hip_ewald_dispersion_near_box.restype = ci
     lib.nfft_hip_ewald_virial_near_workspace_bytes.argtypes = [ctypes.POINTER(EwaldBoxProblem)]
     lib.nfft_hip_ewald_virial_near_workspace_bytes.restype = i64
     lib.nfft_hip_ewald_virial_near.argtypes = [ctypes.POINTER(EwaldBoxProblem), vp, vp, vp, vp, vp, i64, vp]

@@ -1,5 +1,5 @@
 // C-ABI entry points of the pair kernels (include/nfft_hip.h): the near field of the fast summation for singular kernels,
-// the near part of the Ewald sum on the torus and in a box, the virial reductions.  They share only the error plumbing and
+// the near parts of the Ewald sums (1/r and 1/r^6) on the torus and in a box, the virial reductions.  They share only the error plumbing and
 // the workspace conventions (host_util.h) with the transforms of api.hip.
 #include "../../include/nfft_hip.h"
 
@@ -240,9 +240,12 @@ int64_t nfft_hip_ewald_near_workspace_bytes(const nfft_hip_ewald_problem *p)
     return ewald_near_need(p);
 }
 
-int nfft_hip_ewald_near(const nfft_hip_ewald_problem *p, const float *points, const float *xr, const int32_t *start,
-                        const int64_t *index, float *z, float *field, void *workspace, int64_t workspace_bytes,
-                        void *stream)
+// the checks of a wrapped pair sweep on the torus, then `launch` (the Coulomb sweep or the dispersion sweep of section 7j)
+typedef int (*ewald_launch)(const nfft_hip_ewald_problem *, const float *, const float *, const int *, const int64_t *, float *,
+                            float *, void *, hipStream_t);
+static int ewald_near_call(ewald_launch launch, const nfft_hip_ewald_problem *p, const float *points, const float *xr,
+                           const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
+                           int64_t workspace_bytes, void *stream)
 {
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate_ewald(p)) return rc;
@@ -252,7 +255,23 @@ int nfft_hip_ewald_near(const nfft_hip_ewald_problem *p, const float *points, co
     if (!points || !xr || !start || !index) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
     char *ws = workspace_base(workspace, workspace_bytes, ewald_near_need(p));
     if (!ws) return NFFT_HIP_EWORKSPACE;
-    return launch_ewald_near(p, points, xr, start, index, z, field, ws, (hipStream_t)stream);
+    return launch(p, points, xr, start, index, z, field, ws, (hipStream_t)stream);
+}
+
+int nfft_hip_ewald_near(const nfft_hip_ewald_problem *p, const float *points, const float *xr, const int32_t *start,
+                        const int64_t *index, float *z, float *field, void *workspace, int64_t workspace_bytes,
+                        void *stream)
+{
+    return ewald_near_call(launch_ewald_near, p, points, xr, start, index, z, field, workspace, workspace_bytes, stream);
+}
+
+// ---- near part of the dispersion Ewald sum, 1/r^6: the same problem, checks and workspace -------
+int nfft_hip_ewald_dispersion_near(const nfft_hip_ewald_problem *p, const float *points, const float *xr,
+                                   const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
+                                   int64_t workspace_bytes, void *stream)
+{
+    return ewald_near_call(launch_ewald_dispersion_near, p, points, xr, start, index, z, field, workspace, workspace_bytes,
+                           stream);
 }
 
 // ---- the same pair sum in an orthorhombic or triclinic box ------------------------------------
@@ -347,9 +366,11 @@ int64_t nfft_hip_ewald_near_box_workspace_bytes(const nfft_hip_ewald_box_problem
     return ewald_box_need(p);
 }
 
-int nfft_hip_ewald_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
-                            const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
-                            int64_t workspace_bytes, void *stream)
+typedef int (*ewald_box_launch)(const nfft_hip_ewald_box_problem *, const float *, const float *, const int *, const int64_t *,
+                                float *, float *, void *, hipStream_t);
+static int ewald_near_box_call(ewald_box_launch launch, const nfft_hip_ewald_box_problem *p, const float *points,
+                               const float *xr, const int32_t *start, const int64_t *index, float *z, float *field,
+                               void *workspace, int64_t workspace_bytes, void *stream)
 {
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate_ewald_box(p)) return rc;
@@ -359,7 +380,22 @@ int nfft_hip_ewald_near_box(const nfft_hip_ewald_box_problem *p, const float *po
     if (!points || !xr || !start || !index) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
     char *ws = workspace_base(workspace, workspace_bytes, ewald_box_need(p));
     if (!ws) return NFFT_HIP_EWORKSPACE;
-    return launch_ewald_near_box(p, points, xr, start, index, z, field, ws, (hipStream_t)stream);
+    return launch(p, points, xr, start, index, z, field, ws, (hipStream_t)stream);
+}
+
+int nfft_hip_ewald_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                            const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
+                            int64_t workspace_bytes, void *stream)
+{
+    return ewald_near_box_call(launch_ewald_near_box, p, points, xr, start, index, z, field, workspace, workspace_bytes, stream);
+}
+
+int nfft_hip_ewald_dispersion_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                                       const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
+                                       int64_t workspace_bytes, void *stream)
+{
+    return ewald_near_box_call(launch_ewald_dispersion_near_box, p, points, xr, start, index, z, field, workspace,
+                               workspace_bytes, stream);
 }
 
 // ---- virial tensor of the Ewald sum -----------------------------------------------------------

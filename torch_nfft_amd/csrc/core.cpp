@@ -1000,10 +1000,12 @@ std::tuple<at::Tensor, at::Tensor> ewald_result(const EwaldInput &in, const at::
 // image d_ij of pos_i - pos_j on the unit torus, x's type and shape; with_field: f[i, a] = -sum_j g(r_ij^2) d_ij[a] x[j],
 // [n, 3, *cols] (g = K'(r) / r of K = erfc(alpha r) / r), otherwise f is empty.  pos may hold any real values: they are
 // taken modulo 1.
-std::tuple<at::Tensor, at::Tensor> nfft_ewald_near(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch,
-                                                   double alpha, double r_cut, bool with_field)
+// (`sweep`: nfft_hip_ewald_near, or the dispersion sum's pair weights on the same problem, section 7j)
+using EwaldSweep = decltype(&nfft_hip_ewald_near);
+std::tuple<at::Tensor, at::Tensor> ewald_near_op(EwaldSweep sweep, const at::Tensor &pos, const at::Tensor &x,
+                                                 const c10::optional<at::Tensor> &opt_batch, double alpha, double r_cut,
+                                                 bool with_field)
 {
-    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_near is currently only implemented for GPU tensors");
     const EwaldInput in = check_ewald(pos, x, opt_batch, with_field);
     const Points &p = in.p;
     nfft_hip_ewald_problem q;
@@ -1028,19 +1030,26 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_near(at::Tensor pos, at::Tensor x,
     at::Tensor z = at::zeros({p.n, q.num_columns}, opts);
     at::Tensor f = with_field ? at::zeros({p.n, 3 * q.num_columns}, opts) : at::empty({0}, x.options());
     at::Tensor ws = byte_buffer(ws_bytes, x);
-    check_rc(nfft_hip_ewald_near(&q, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
-                                 o.order.data_ptr<int64_t>(), z.data_ptr<float>(), with_field ? f.data_ptr<float>() : nullptr,
-                                 ws.data_ptr(), ws_bytes, stream_of(x)));
+    check_rc(sweep(&q, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(), o.order.data_ptr<int64_t>(),
+                   z.data_ptr<float>(), with_field ? f.data_ptr<float>() : nullptr, ws.data_ptr(), ws_bytes, stream_of(x)));
     return ewald_result(in, z, f, with_field);
+}
+
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_near(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch,
+                                                   double alpha, double r_cut, bool with_field)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_near is currently only implemented for GPU tensors");
+    return ewald_near_op(nfft_hip_ewald_near, pos, x, opt_batch, alpha, r_cut, with_field);
 }
 
 // ---- the same pair sum in an orthorhombic or triclinic box (not in the reference) ---------------
 // (z, f) of nfft_ewald_near in the box A = box (A00, A10, A11, A20, A21, A22; rows = lattice vectors): pos holds FRACTIONAL
 // coordinates, taken modulo 1; r_ij is the length of d_ij = (ds - rint(ds)) A and f is Cartesian.
-std::tuple<at::Tensor, at::Tensor> nfft_ewald_near_box(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch,
-                                                       std::vector<double> box, double alpha, double r_cut, bool with_field)
+using EwaldBoxSweep = decltype(&nfft_hip_ewald_near_box);
+std::tuple<at::Tensor, at::Tensor> ewald_near_box_op(EwaldBoxSweep sweep, const at::Tensor &pos, const at::Tensor &x,
+                                                     const c10::optional<at::Tensor> &opt_batch, const std::vector<double> &box,
+                                                     double alpha, double r_cut, bool with_field)
 {
-    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_near_box is currently only implemented for GPU tensors");
     const EwaldInput in = check_ewald(pos, x, opt_batch, with_field);
     const Points &p = in.p;
     CHECK_INPUT(box.size() == 6);
@@ -1056,10 +1065,34 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_near_box(at::Tensor pos, at::Tenso
     at::Tensor z = at::zeros({p.n, q.num_columns}, opts);
     at::Tensor f = with_field ? at::zeros({p.n, 3 * q.num_columns}, opts) : at::empty({0}, x.options());
     at::Tensor ws = byte_buffer(ws_bytes, x);
-    check_rc(nfft_hip_ewald_near_box(&q, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
-                                     o.order.data_ptr<int64_t>(), z.data_ptr<float>(),
-                                     with_field ? f.data_ptr<float>() : nullptr, ws.data_ptr(), ws_bytes, stream_of(x)));
+    check_rc(sweep(&q, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(), o.order.data_ptr<int64_t>(),
+                   z.data_ptr<float>(), with_field ? f.data_ptr<float>() : nullptr, ws.data_ptr(), ws_bytes, stream_of(x)));
     return ewald_result(in, z, f, with_field);
+}
+
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_near_box(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch,
+                                                       std::vector<double> box, double alpha, double r_cut, bool with_field)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_near_box is currently only implemented for GPU tensors");
+    return ewald_near_box_op(nfft_hip_ewald_near_box, pos, x, opt_batch, box, alpha, r_cut, with_field);
+}
+
+// ---- near part of the dispersion Ewald sum, the periodic 1/r^6 (not in the reference) -----------
+// (z, f) as nfft_ewald_near and nfft_ewald_near_box with the pair weights w(r) = e^(-a^2) (1 + a^2 + a^4 / 2) / r^6, a = alpha r:
+// z[i] = sum_j w(r_ij) x[j], f[i, a] = sum_j (-w'(r_ij) / r_ij) d_ij[a] x[j] (minus the gradient)
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_dispersion_near(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch,
+                                                              double alpha, double r_cut, bool with_field)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_dispersion_near is currently only implemented for GPU tensors");
+    return ewald_near_op(nfft_hip_ewald_dispersion_near, pos, x, opt_batch, alpha, r_cut, with_field);
+}
+
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_dispersion_near_box(at::Tensor pos, at::Tensor x,
+                                                                  c10::optional<at::Tensor> opt_batch, std::vector<double> box,
+                                                                  double alpha, double r_cut, bool with_field)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_dispersion_near_box is currently only implemented for GPU tensors");
+    return ewald_near_box_op(nfft_hip_ewald_dispersion_near_box, pos, x, opt_batch, box, alpha, r_cut, with_field);
 }
 
 // ---- virial tensor of the Ewald sum (not in the reference) --------------------------------------
@@ -1255,6 +1288,11 @@ TORCH_LIBRARY(torch_nfft, m)
     // not in the reference: the same pair sum in an orthorhombic or triclinic box, on fractional positions
     m.def("_nfft_ewald_near_box(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut, bool with_field) "
           "-> (Tensor, Tensor)", &nfft_ewald_near_box);
+    // not in the reference: the wrapped pair sum of the dispersion Ewald sum 1/r^6 and its field (nfft_ewald_dispersion)
+    m.def("_nfft_ewald_dispersion_near(Tensor pos, Tensor x, Tensor? batch, float alpha, float r_cut, bool with_field) "
+          "-> (Tensor, Tensor)", &nfft_ewald_dispersion_near);
+    m.def("_nfft_ewald_dispersion_near_box(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut, "
+          "bool with_field) -> (Tensor, Tensor)", &nfft_ewald_dispersion_near_box);
     // not in the reference: the pair and the spectral reduction of the Ewald sum's virial tensor (nfft_ewald_virial)
     m.def("_nfft_ewald_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut) -> Tensor",
           &nfft_ewald_virial_near);

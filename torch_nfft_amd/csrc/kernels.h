@@ -185,6 +185,12 @@ int launch_ewald_near(const nfft_hip_ewald_problem *p, const float *pos, const f
 int64_t ewald_near_box_item_slots(const nfft_hip_ewald_box_problem *p);
 int launch_ewald_near_box(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xr, const int *start,
                           const int64_t *index, float *z, float *f, void *items, hipStream_t stream);
+// ewald_disp.hip (the wrapped pair sum of the dispersion Ewald sum, 1/r^6, and its field): arguments
+// and `items` as launch_ewald_near / launch_ewald_near_box (the same item slots)
+int launch_ewald_dispersion_near(const nfft_hip_ewald_problem *p, const float *pos, const float *xr, const int *start,
+                                 const int64_t *index, float *z, float *f, void *items, hipStream_t stream);
+int launch_ewald_dispersion_near_box(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xr, const int *start,
+                                     const int64_t *index, float *z, float *f, void *items, hipStream_t stream);
 // ewald_virial.hip (the virial tensor of the Ewald sum): the pair reduction, arguments as
 // nfft_hip_ewald_virial_near, `workspace`: ewald_virial_near_workspace(p) bytes, 256-byte aligned (the work items, then one
 // partial per item slot); and the spectral reduction, arguments as nfft_hip_ewald_virial_far, `workspace`:

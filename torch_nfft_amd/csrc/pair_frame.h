@@ -1,5 +1,5 @@
-// The frame of the pair kernels: nearfield.hip (the open grid of the fast summation), ewald_near.hip
-// and the pair kernel of ewald_virial.hip (the wrapped grid of the Ewald sum) stand on all of it, nearfield_pgrad.hip on all
+// The frame of the pair kernels: nearfield.hip (the open grid of the fast summation), ewald_near.hip,
+// ewald_disp.hip and the pair kernel of ewald_virial.hip (the wrapped grid of the Ewald sums) stand on all of it, nearfield_pgrad.hip on all
 // but the tile sweep, nearfield_grad.hip on the host dispatch only (section 7d says why).
 // Both point sets come ordered by (point set, cell) with a start table.  A workgroup owns one work item -- up to kNearBlock
 // output points of one cell -- and a lane one output point; a walk hands the contiguous ranges of streamed points of the
@@ -223,6 +223,22 @@ struct EwaldPairWeight {
         w = erfcf(q.alpha * (rr * ir)) * ir;
     }
     __device__ __forceinline__ float mg(const EwaldPairParams &q) const { return (w + q.slope * __expf(q.neg_alpha2 * rr)) * (ir * ir); }
+};
+
+// the pair weights of the dispersion sum from rr = r^2 > 0, a2 = alpha^2 r^2:
+// w = e^(-a2) (1 + a2 + a2^2 / 2) / r^6, and on request its negated slope mg = -w'(r) / r = e^(-a2) (6 + 6 a2 + 3 a2^2 + a2^3) / r^8.
+// One reciprocal, one exponential, two Horner forms; r^-8 leaves float32 below r ~ 1.6e-5.
+struct DispersionPairWeight {
+    float w, e, a2, ir2, ir6;
+    __device__ __forceinline__ DispersionPairWeight(float r2, const EwaldPairParams &q) : ir2(__builtin_amdgcn_rcpf(r2))
+    {
+        const float x = q.neg_alpha2 * r2;
+        a2 = -x;
+        e = __expf(x);
+        ir6 = ir2 * ir2 * ir2;
+        w = e * ((0.5f * a2 + 1.f) * a2 + 1.f) * ir6;
+    }
+    __device__ __forceinline__ float mg() const { return e * (((a2 + 3.f) * a2 + 6.f) * a2 + 6.f) * (ir6 * ir2); }
 };
 
 // ---- float64 sum over a workgroup -------------------------------------------------------------------------------------

@@ -48,27 +48,27 @@ from .nfft import nfft_adjoint, nfft_forward, nfft_fastsum
 MAX_R_CUT = 1.0 / 3.0  # the pair sweep needs 3 cells of edge >= r_cut per axis
 
 
-def _box_matrix(box):
+def _box_matrix(box, what="EwaldSplitting"):
     """``box`` (length 3: the edges of an orthorhombic cell; or ``[3, 3]`` lower triangular, rows = lattice vectors) as a
     float64 ``[3, 3]`` tensor on the host.  ValueError for another shape, entries that are not finite, entries above the
     diagonal that are not zero or a diagonal that is not positive; AssertionError for a tensor that requires grad."""
     if isinstance(box, torch.Tensor):
         if box.requires_grad:
-            raise AssertionError("EwaldSplitting is not differentiable w.r.t. the box, but box requires grad")
+            raise AssertionError("%s is not differentiable w.r.t. the box, but box requires grad" % what)
         A = box.detach().to(device="cpu", dtype=torch.float64)
     else:
         A = torch.as_tensor(box, dtype=torch.float64)
     if A.shape == (3,):
         A = torch.diag(A)
     if A.shape != (3, 3):
-        raise ValueError("EwaldSplitting: box must have length 3 (orthorhombic) or be [3, 3] lower triangular")
+        raise ValueError("%s: box must have length 3 (orthorhombic) or be [3, 3] lower triangular" % what)
     if not bool(torch.isfinite(A).all()):
-        raise ValueError("EwaldSplitting: the entries of box must be finite")
+        raise ValueError("%s: the entries of box must be finite" % what)
     if bool((torch.triu(A, 1) != 0).any()):
-        raise ValueError("EwaldSplitting: box must be lower triangular (rows = lattice vectors a_1 = (A00, 0, 0), "
-                         "a_2 = (A10, A11, 0), a_3); see the class docstring for a general cell")
+        raise ValueError("%s: box must be lower triangular (rows = lattice vectors a_1 = (A00, 0, 0), "
+                         "a_2 = (A10, A11, 0), a_3); see the class docstring of EwaldSplitting for a general cell" % what)
     if not bool((torch.diagonal(A) > 0).all()):
-        raise ValueError("EwaldSplitting: the diagonal of box must be positive")
+        raise ValueError("%s: the diagonal of box must be positive" % what)
     return A.contiguous()
 
 
@@ -87,7 +87,93 @@ def _box_widths(A):
     return tuple(1.0 / math.sqrt(float((inv[:, a] * inv[:, a]).sum())) for a in range(3))
 
 
-class EwaldSplitting:
+class _TorusSplitting:
+    """What ``EwaldSplitting`` and ``DispersionSplitting`` share: the checks of ``alpha``, ``r_cut``, ``bandwidth`` and
+    ``box``, the attributes ``alpha``, ``r_cut``, ``bandwidth``, ``box``, ``volume``, ``widths`` and ``cells``, and the box's
+    matrices.  A subclass turns ``|kappa|^2`` into its coefficients.  Messages carry the subclass's name."""
+
+    def _setup(self, alpha, r_cut, bandwidth, box):
+        """the checks and the attributes; returns ``|kappa|^2`` ``[N, N, N]`` float64 on the host (``|k|^2`` without a box)"""
+        what = type(self).__name__
+        alpha, r_cut, N = float(alpha), float(r_cut), int(bandwidth)
+        if N != bandwidth or N < 2 or N % 2:
+            raise ValueError("%s: bandwidth must be even and >= 2" % what)
+        if not (alpha > 0.0 and math.isfinite(alpha)):
+            raise ValueError("%s: alpha must be positive" % what)
+        self._field_coeffs = None
+        if box is None:
+            if not 0.0 < r_cut <= MAX_R_CUT:
+                raise ValueError("%s: r_cut must lie in (0, 1/3]" % what)
+            self.alpha, self.r_cut, self.bandwidth = alpha, r_cut, N
+            self.box, self.volume, self.widths = None, 1.0, (1.0, 1.0, 1.0)
+            self.cells = (int(_lib.load().nfft_hip_ewald_near_cells(r_cut, 1)),) * 3
+            k = torch.arange(-(N // 2), N // 2, dtype=torch.float64)
+            return (k * k).reshape(N, 1, 1) + (k * k).reshape(1, N, 1) + (k * k).reshape(1, 1, N)
+        A = _box_matrix(box, what)
+        widths = _box_widths(A)
+        if not 0.0 < r_cut <= min(widths) / 3.0:
+            raise ValueError("%s: r_cut must lie in (0, min w_a / 3] = (0, %.6g] for this box (perpendicular "
+                             "widths %.6g, %.6g, %.6g)" % ((what, min(widths) / 3.0) + widths))
+        self.alpha, self.r_cut, self.bandwidth = alpha, r_cut, N
+        self.box, self.widths = A, widths
+        self.volume = float(A[0, 0] * A[1, 1] * A[2, 2])
+        cells = (ctypes.c_int32 * 3)()
+        six = (ctypes.c_double * 6)(*self.box6)
+        if _lib.load().nfft_hip_ewald_box_cells(six, r_cut, 1, cells) < 0:
+            raise ValueError("%s: %s" % (what, _lib.last_error()))
+        self.cells = tuple(int(c) for c in cells)
+        self._on_device = {}
+        kappa = self._kappa()
+        return (kappa * kappa).sum(3)
+
+    @staticmethod
+    def _zero_unpaired(b):
+        """the planes ``k_a = -N/2`` have no partner ``+N/2``: zeroed, so that a real input gives a real sum"""
+        b[0, :, :] = 0.0
+        b[:, 0, :] = 0.0
+        b[:, :, 0] = 0.0
+        return b
+
+    @classmethod
+    def _tolerance_box(cls, tol, r_cut, box):
+        """the checks of ``from_tolerance``: (``tol``, ``r_cut``, the box matrix or ``None``, the longest lattice vector)"""
+        what = cls.__name__
+        tol, r_cut = float(tol), float(r_cut)
+        if not 0.0 < tol < 1.0:
+            raise ValueError("%s.from_tolerance: tol must lie in (0, 1)" % what)
+        if box is None:
+            if not 0.0 < r_cut <= MAX_R_CUT:
+                raise ValueError("%s: r_cut must lie in (0, 1/3]" % what)
+            return tol, r_cut, None, 1.0
+        A = _box_matrix(box, what)
+        if not 0.0 < r_cut <= min(_box_widths(A)) / 3.0:
+            raise ValueError("%s: r_cut must lie in (0, min w_a / 3] for this box" % what)
+        return tol, r_cut, A, max(math.sqrt(float((A[a] * A[a]).sum())) for a in range(3))
+
+    @property
+    def box6(self):
+        """``(A00, A10, A11, A20, A21, A22)``: the box as ``ops.nfft_ewald_near_box`` takes it"""
+        A = self.box
+        return tuple(float(A[i, j]) for i, j in ((0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2)))
+
+    def _kappa(self):
+        """``[N, N, N, 3]`` float64 on the host: the Cartesian wave vectors ``kappa_b = sum_a (A^-1)_ba k_a`` (without a
+        box: ``k`` itself)"""
+        N = self.bandwidth
+        inv = torch.eye(3, dtype=torch.float64) if self.box is None else _box_inverse(self.box)
+        k = torch.arange(-(N // 2), N // 2, dtype=torch.float64)
+        ks = (k.reshape(N, 1, 1), k.reshape(1, N, 1), k.reshape(1, 1, N))
+        return torch.stack([sum(float(inv[b, a]) * ks[a] for a in range(3)).expand(N, N, N) for b in range(3)], 3)
+
+    def _matrices(self, device):
+        """(``A`` float32, ``A^-1`` float64) on ``device``"""
+        key = str(device)
+        if key not in self._on_device:
+            self._on_device[key] = (self.box.to(torch.float32).to(device), _box_inverse(self.box).to(device))
+        return self._on_device[key]
+
+
+class EwaldSplitting(_TorusSplitting):
     """The three parameters of the split, the box and the far field's coefficients.
 
     ``alpha > 0`` is the splitting parameter, ``r_cut`` in ``(0, 1/3]`` the radius of the pair sum, ``bandwidth`` (even)
@@ -110,76 +196,18 @@ class EwaldSplitting:
 
     Attributes: ``box`` (``[3, 3]`` float64 on the host, or ``None``), ``volume``, ``widths`` and ``cells`` (the cell counts
     of the pair sweep for one point set)."""
+    _A_NAME = "an EwaldSplitting"
 
     def __init__(self, alpha, r_cut, bandwidth, box=None, device="cuda"):
-        alpha, r_cut, N = float(alpha), float(r_cut), int(bandwidth)
-        if N != bandwidth or N < 2 or N % 2:
-            raise ValueError("EwaldSplitting: bandwidth must be even and >= 2")
-        if not (alpha > 0.0 and math.isfinite(alpha)):
-            raise ValueError("EwaldSplitting: alpha must be positive")
-        if box is not None:
-            self._init_box(alpha, r_cut, N, _box_matrix(box), device)
-            return
-        if not 0.0 < r_cut <= MAX_R_CUT:
-            raise ValueError("EwaldSplitting: r_cut must lie in (0, 1/3]")
-        self.alpha, self.r_cut, self.bandwidth = alpha, r_cut, N
-        self.box, self.volume, self.widths = None, 1.0, (1.0, 1.0, 1.0)
-        self.cells = (int(_lib.load().nfft_hip_ewald_near_cells(r_cut, 1)),) * 3
-        k = torch.arange(-(N // 2), N // 2, dtype=torch.float64)
-        k2 = (k * k).reshape(N, 1, 1) + (k * k).reshape(1, N, 1) + (k * k).reshape(1, 1, N)
-        b = torch.exp(-(math.pi / alpha) ** 2 * k2) / (math.pi * k2.clamp(min=1.0))
-        b[N // 2, N // 2, N // 2] = 0.0
-        b[0, :, :] = 0.0
-        b[:, 0, :] = 0.0
-        b[:, :, 0] = 0.0
-        self.coeffs = b.to(torch.float32).to(torch.device(device)).contiguous()
-        self._field_coeffs = None
-
-    def _init_box(self, alpha, r_cut, N, A, device):
-        widths = _box_widths(A)
-        if not 0.0 < r_cut <= min(widths) / 3.0:
-            raise ValueError("EwaldSplitting: r_cut must lie in (0, min w_a / 3] = (0, %.6g] for this box (perpendicular "
-                             "widths %.6g, %.6g, %.6g)" % ((min(widths) / 3.0,) + widths))
-        self.alpha, self.r_cut, self.bandwidth = alpha, r_cut, N
-        self.box, self.widths = A, widths
-        self.volume = float(A[0, 0] * A[1, 1] * A[2, 2])
-        cells = (ctypes.c_int32 * 3)()
-        six = (ctypes.c_double * 6)(*self.box6)
-        if _lib.load().nfft_hip_ewald_box_cells(six, r_cut, 1, cells) < 0:
-            raise ValueError("EwaldSplitting: " + _lib.last_error())
-        self.cells = tuple(int(c) for c in cells)
-        kappa = self._kappa()
-        k2 = (kappa * kappa).sum(3)
-        b = torch.exp(-(math.pi / alpha) ** 2 * k2) / (math.pi * self.volume * torch.where(k2 > 0, k2, torch.ones_like(k2)))
-        b[N // 2, N // 2, N // 2] = 0.0
-        b[0, :, :] = 0.0
-        b[:, 0, :] = 0.0
-        b[:, :, 0] = 0.0
-        self._b64 = b
-        self.coeffs = b.to(torch.float32).to(torch.device(device)).contiguous()
-        self._field_coeffs = None
-        self._on_device = {}
-
-    @property
-    def box6(self):
-        """``(A00, A10, A11, A20, A21, A22)``: the box as ``ops.nfft_ewald_near_box`` takes it"""
-        A = self.box
-        return tuple(float(A[i, j]) for i, j in ((0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2)))
-
-    def _kappa(self):
-        """``[N, N, N, 3]`` float64 on the host: the Cartesian wave vectors ``kappa_b = sum_a (A^-1)_ba k_a``"""
+        k2 = self._setup(alpha, r_cut, bandwidth, box)
         N = self.bandwidth
-        inv = _box_inverse(self.box)
-        k = torch.arange(-(N // 2), N // 2, dtype=torch.float64)
-        ks = (k.reshape(N, 1, 1), k.reshape(1, N, 1), k.reshape(1, 1, N))
-        return torch.stack([sum(float(inv[b, a]) * ks[a] for a in range(3)).expand(N, N, N) for b in range(3)], 3)
-
-    def _matrices(self, device):
-        """(``A`` float32, ``A^-1`` float64) on ``device``"""
-        key = str(device)
-        if key not in self._on_device:
-            self._on_device[key] = (self.box.to(torch.float32).to(device), _box_inverse(self.box).to(device))
-        return self._on_device[key]
+        if box is not None:
+            b = torch.exp(-(math.pi / self.alpha) ** 2 * k2) / (math.pi * self.volume * torch.where(k2 > 0, k2, torch.ones_like(k2)))
+        else:
+            b = torch.exp(-(math.pi / self.alpha) ** 2 * k2) / (math.pi * k2.clamp(min=1.0))
+        b[N // 2, N // 2, N // 2] = 0.0
+        self._b64 = self._zero_unpaired(b)
+        self.coeffs = b.to(torch.float32).to(torch.device(device)).contiguous()
 
     @classmethod
     def from_tolerance(cls, tol, r_cut, box=None, device="cuda"):
@@ -191,23 +219,11 @@ class EwaldSplitting:
         With a ``box`` the plane ``k_a = N/2`` lies at the distance ``(N/2) / |a_a|`` from the origin of reciprocal space,
         so ``bandwidth`` is the next even integer ``>= 2 alpha sqrt(-ln tol) max_a |a_a| / pi``.  The grid is cubic in
         ``N``: the longest lattice vector sets ``N`` for all three axes."""
-        tol = float(tol)
-        if not 0.0 < tol < 1.0:
-            raise ValueError("EwaldSplitting.from_tolerance: tol must lie in (0, 1)")
+        tol, r_cut, A, longest = cls._tolerance_box(tol, r_cut, box)
         s = math.sqrt(-math.log(tol))
-        if box is not None:
-            A = _box_matrix(box)
-            if not 0.0 < float(r_cut) <= min(_box_widths(A)) / 3.0:
-                raise ValueError("EwaldSplitting: r_cut must lie in (0, min w_a / 3] for this box")
-            alpha = s / float(r_cut)
-            longest = max(math.sqrt(float((A[a] * A[a]).sum())) for a in range(3))
-            N = max(2, 2 * math.ceil(alpha * s * longest / math.pi))
-            return cls(alpha, r_cut, N, box=A, device=device)
-        if not 0.0 < float(r_cut) <= MAX_R_CUT:
-            raise ValueError("EwaldSplitting: r_cut must lie in (0, 1/3]")
-        alpha = s / float(r_cut)
-        N = max(2, 2 * math.ceil(alpha * s / math.pi))
-        return cls(alpha, r_cut, N, device=device)
+        alpha = s / r_cut
+        N = max(2, 2 * math.ceil(alpha * s * longest / math.pi))
+        return cls(alpha, r_cut, N, box=A, device=device)
 
     def field_coeffs(self):
         """``[N, N, N, 4]`` complex64: ``b_k`` and, for the three axes, ``(+2 pi i k_a) b_k`` -- the coefficients of
@@ -265,6 +281,27 @@ def _ewald(q, pos, batch, splitting, cutoff, field):
     return phi, (E + f if field else None)
 
 
+def _symmetric_backward(evaluate, ctx, g):
+    """The backward of a real symmetric operator ``q -> phi`` whose field ``E[q] = -grad phi`` comes with it
+    (``evaluate(q, pos, batch, splitting, cutoff, field) -> (phi, E)``): ``dq`` is the operator applied to ``g``,
+    ``dpos_i = -sum_c (g_ic E[q_c]_i + q_ic E[g_c]_i)``, times ``A^T`` with a box (``pos`` fractional, ``E`` Cartesian)."""
+    q, pos, batch = ctx.saved_tensors
+    need_q, need_pos = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    g = g.contiguous()
+    dq = dpos = None
+    if need_pos:
+        phi, E = evaluate(torch.stack([q, g], 1), pos, batch, ctx.splitting, ctx.cutoff, True)  # [n, (3,) 2, *cols]
+        dq = phi[:, 1]
+        w = g.unsqueeze(1).conj() * E[:, :, 0] + q.unsqueeze(1).conj() * E[:, :, 1]
+        w = w.real if w.is_complex() else w
+        dpos = -w.reshape(w.size(0), 3, math.prod(w.shape[2:])).sum(2)
+        if ctx.splitting.box is not None:
+            dpos = dpos @ ctx.splitting._matrices(dpos.device)[0].t()
+    elif need_q:
+        dq = evaluate(g, pos, batch, ctx.splitting, ctx.cutoff, False)[0]
+    return dq if need_q else None, dpos, None, None, None, None
+
+
 class NfftEwaldFunction(torch.autograd.Function):
     """``(phi, E)`` of ``nfft_ewald`` (``E`` empty without ``field``).  The operator ``q -> phi`` is real symmetric, so for
     ``g = dL/dphi`` the gradient in ``q`` is the operator applied to ``g``, and the gradient in the positions is
@@ -288,21 +325,7 @@ class NfftEwaldFunction(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g, _):
-        q, pos, batch = ctx.saved_tensors
-        need_q, need_pos = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        g = g.contiguous()
-        dq = dpos = None
-        if need_pos:
-            phi, E = _ewald(torch.stack([q, g], 1), pos, batch, ctx.splitting, ctx.cutoff, True)  # [n, (3,) 2, *cols]
-            dq = phi[:, 1]
-            w = g.unsqueeze(1).conj() * E[:, :, 0] + q.unsqueeze(1).conj() * E[:, :, 1]
-            w = w.real if w.is_complex() else w
-            dpos = -w.reshape(w.size(0), 3, math.prod(w.shape[2:])).sum(2)
-            if ctx.splitting.box is not None:
-                dpos = dpos @ ctx.splitting._matrices(dpos.device)[0].t()
-        elif need_q:
-            dq = _ewald(g, pos, batch, ctx.splitting, ctx.cutoff, False)[0]
-        return dq if need_q else None, dpos, None, None, None, None
+        return _symmetric_backward(_ewald, ctx, g)
 
 
 def _check(what, q, pos, batch, splitting, differentiable=True):
@@ -320,7 +343,7 @@ def _fractional(what, pos, splitting, fractional):
     """the positions as the Function takes them: as they are without a box, fractional with one"""
     if splitting.box is None:
         if fractional:
-            raise ValueError("%s: fractional=True needs an EwaldSplitting with a box" % what)
+            raise ValueError("%s: fractional=True needs %s with a box" % (what, splitting._A_NAME))
         return pos
     if fractional:
         return pos

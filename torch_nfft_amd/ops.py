@@ -194,6 +194,25 @@ def nfft_ewald_near_box(pos, x, batch, box, alpha, r_cut, with_field):
     return _ops._nfft_ewald_near_box(pos, x, batch, [float(a) for a in box], float(alpha), float(r_cut), bool(with_field))
 
 
+def nfft_ewald_dispersion_near(pos, x, batch, alpha, r_cut, with_field):
+    """torch_nfft::_nfft_ewald_dispersion_near(Tensor pos, Tensor x, Tensor? batch, float alpha, float r_cut,
+    bool with_field) -> (Tensor, Tensor) (not in the reference): the near part of the dispersion Ewald sum on the unit
+    torus, ``z_i = sum_{j: 0 < r_ij < r_cut} w(r_ij) x_j`` with ``w(r) = e^(-a^2) (1 + a^2 + a^4 / 2) / r^6``,
+    ``a = alpha r``, and with ``with_field`` ``f_i = sum_j mg(r_ij) d_ij x_j`` ``[n, 3, *cols]``,
+    ``mg = -w'(r) / r = e^(-a^2) (6 + 6 a^2 + 3 a^4 + a^6) / r^8`` (empty otherwise).  Points, point sets, shapes and
+    types as for ``nfft_ewald_near``.  One native call (``nfft_hip_ewald_dispersion_near``)."""
+    return _ops._nfft_ewald_dispersion_near(pos, x, batch, float(alpha), float(r_cut), bool(with_field))
+
+
+def nfft_ewald_dispersion_near_box(pos, x, batch, box, alpha, r_cut, with_field):
+    """torch_nfft::_nfft_ewald_dispersion_near_box(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha,
+    float r_cut, bool with_field) -> (Tensor, Tensor) (not in the reference): ``nfft_ewald_dispersion_near`` in the box
+    ``box = (A00, A10, A11, A20, A21, A22)`` on FRACTIONAL positions, as ``nfft_ewald_near_box``.  One native call
+    (``nfft_hip_ewald_dispersion_near_box``)."""
+    return _ops._nfft_ewald_dispersion_near_box(pos, x, batch, [float(a) for a in box], float(alpha), float(r_cut),
+                                                bool(with_field))
+
+
 def nfft_ewald_virial_near(pos, x, batch, box, alpha, r_cut):
     """torch_nfft::_nfft_ewald_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut) ->
     Tensor (not in the reference): the pair part of the Ewald energy and of the virial tensor ``W_ab = -dU / d eps_ab``,
