@@ -500,6 +500,30 @@ int nfft_hip_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns
                               const double *box_inverse, double pi2_over_alpha2, double *out, void *workspace,
                               int64_t workspace_bytes, void *stream);
 
+/* ---- virial tensor of the dispersion Ewald sum (no reference counterpart) ----
+ * The same two reductions for the periodic 1/r^6 of nfft_hip_ewald_dispersion_near_box: U = 1/2 sum_i c_i psi_i and
+ * W_ab = -dU / d eps_ab, seven float64 numbers per point set and column in the order above.  The self term
+ * -(alpha^6 / 12) sum_i c_i^2 (in U only) is the caller's; there is no background term.  tr W = 6 U for the converged sum.
+ * Arguments, checks, alignment and limits are those of the two entry points above, and so are the workspaces:
+ * nfft_hip_ewald_virial_near_workspace_bytes and nfft_hip_ewald_virial_far_workspace_bytes serve both.
+ *
+ * nfft_hip_ewald_dispersion_virial_near: with a = alpha r, w = exp(-a^2) (1 + a^2 + a^4 / 2) / r^6 and mg = -w'(r) / r,
+ *     out[b, 0, c] = 1/2 sum_{i in set b} xr[i, c] sum_{j: 0 < r_ij < r_cut} w(r_ij) xr[j, c]
+ *     out[b, e, c] = 1/2 sum_i xr[i, c] sum_j mg(r_ij) d_ij[a] d_ij[b] xr[j, c].
+ *
+ * nfft_hip_ewald_dispersion_virial_far: coeffs [N, N, N] float32 holds b_k (k = 0 included; cells with b_k = 0 are
+ * skipped) and strain_coeffs [N, N, N] float32 holds t_k = (d b_k / d |kappa|) / |kappa| = (2 pi^(7/2) alpha / V)
+ * (sqrt(pi) b erfc(b) - exp(-b^2)), b = pi |kappa| / alpha, which the caller evaluates in float64 (the two terms cancel
+ * at large b),
+ *     out[b, 0, c] = 1/2 sum_k b_k |band_k|^2
+ *     out[b, e, c] = 1/2 sum_k |band_k|^2 (b_k delta_ab + t_k kappa_a kappa_b). */
+int nfft_hip_ewald_dispersion_virial_near(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                                          const int32_t *start, double *out, void *workspace, int64_t workspace_bytes,
+                                          void *stream);
+int nfft_hip_ewald_dispersion_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, const void *band,
+                                         const float *coeffs, const float *strain_coeffs, const double *box_inverse, double *out,
+                                         void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.
  *   gaussian_analytic_coeffs      float32:  prod_d sqrt(pi) sigma exp(-sigma^2 pi^2 l_d^2)      (kernel_coeffs.cu:6-30)

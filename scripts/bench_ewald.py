@@ -40,6 +40,14 @@ far field, the near operator ops.nfft_ewald_dispersion_near and its pair loop on
 on restated plumbing), and beside it, in the same run on the same sorted points, cells and r_c, the Coulomb pair loop
 (nfft_hip_ewald_near with the alpha of EwaldSplitting.from_tolerance): the same pairs are tested and the same pass the cut,
 what differs is the pair weight.
+
+    python scripts/bench_ewald.py --dispersion --virial [...]
+
+adds the row of --virial for the dispersion sum's virial tensor after each of those, in the identity
+box on the same points and coefficients: nfft_ewald_dispersion_virial beside nfft_ewald_dispersion(field=True); the pair loop
+of nfft_hip_ewald_dispersion_virial_near beside the dispersion field loop (nfft_hip_ewald_dispersion_near_box), in
+picoseconds per tested pair; and the far reduction (ops.nfft_ewald_dispersion_virial_far) beside the torch composition on
+the same band, with its agreement with it.
 """
 import argparse
 import ctypes
@@ -382,6 +390,77 @@ def run_dispersion(lib, n, args):
                       "dispersion_over_coulomb_field": round(loops[1] / coulomb[1], 3)}))
 
 
+def run_dispersion_virial(lib, n, args):
+    """the row of run_virial for the dispersion sum, in the unit cube as the identity box"""
+    m = 4
+    box = [1.0, 0.0, 1.0, 0.0, 0.0, 1.0]
+    r_c = min((3.0 * args.neighbours / (4.0 * math.pi * n)) ** (1.0 / 3.0), 1.0 / 3.0)
+    sp = tn.DispersionSplitting.from_tolerance(args.tol, r_c, box=[1.0, 1.0, 1.0])
+    rng = np.random.default_rng(0)
+    v = (rng.random((n, 3)) - 0.5).astype(np.float32)
+    v[v >= 0.5] = -0.5  # (rounded up to the face: the same point)
+    pos = torch.from_numpy(v).cuda()
+    c = torch.from_numpy((rng.random(n) + 0.5).astype(np.float32)).cuda()
+    G, N = sp.cells, sp.bandwidth
+    tested = box_pairs_tested(v, G)
+    field = median_ms(lambda: tn.nfft_ewald_dispersion(c, pos, splitting=sp, cutoff=m, field=True, fractional=True), args.reps)
+    virial = median_ms(lambda: tn.nfft_ewald_dispersion_virial(c, pos, splitting=sp, cutoff=m, fractional=True), args.reps)
+    adjoint = median_ms(lambda: tn.nfft_adjoint(c, pos, bandwidth=N, cutoff=m), args.reps)
+    near_op = median_ms(lambda: tn.ops.nfft_ewald_dispersion_virial_near(pos, c, None, box, sp.alpha, r_c), args.reps)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    spos, order, start = box_cell_order(pos, G)
+    xs = c.index_select(0, order).reshape(n, 1).contiguous()
+    z, f = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+    p = _lib.EwaldBoxProblem(cells=(ctypes.c_int32 * 3)(*G), with_field=1, num_points=n, num_columns=1, batch_size=1,
+                             alpha=sp.alpha, r_cut=r_c, box=(ctypes.c_double * 6)(*box))
+    nbytes = lib.nfft_hip_ewald_near_box_workspace_bytes(ctypes.byref(p))
+    vbytes = lib.nfft_hip_ewald_virial_near_workspace_bytes(ctypes.byref(p))
+    assert nbytes > 0 and vbytes > 0, _lib.last_error()
+    ws, vws = torch.empty(nbytes, dtype=torch.uint8, device="cuda"), torch.empty(vbytes, dtype=torch.uint8, device="cuda")
+    seven = torch.zeros(1, 7, 1, dtype=torch.float64, device="cuda")
+
+    def field_loop():
+        _lib.check(lib.nfft_hip_ewald_dispersion_near_box(ctypes.byref(p), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                                          order.data_ptr(), z.data_ptr(), f.data_ptr(), ws.data_ptr(), nbytes,
+                                                          stream))
+
+    def virial_loop():
+        _lib.check(lib.nfft_hip_ewald_dispersion_virial_near(ctypes.byref(p), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                                             seven.data_ptr(), vws.data_ptr(), vbytes, stream))
+
+    loop_f, loop_v = median_ms(field_loop, args.reps), median_ms(virial_loop, args.reps)
+    assert torch.equal(tn.ops.nfft_ewald_dispersion_virial_near(pos, c, None, box, sp.alpha, r_c), seven[:, :, 0]), \
+        "the restated plumbing must give the operator's bits"
+    # the far reduction beside the torch composition on the same band
+    band = tn.nfft_adjoint(c, pos, bandwidth=N, cutoff=m)  # [1, N, N, N]
+    kappa = sp._kappa()
+    b64, t64 = sp._b64, sp.strain_coeffs().double().cpu()
+    coef7 = [b64] + [b64 + t64 * kappa[..., a] * kappa[..., a] for a in range(3)] + \
+            [t64 * kappa[..., a] * kappa[..., b] for a, b in ((1, 2), (0, 2), (0, 1))]
+    coef7 = (0.5 * torch.stack(coef7, 3)).to(torch.float32).cuda()  # [N, N, N, 7]
+    strain = sp.strain_coeffs()
+    far_v = median_ms(lambda: tn.ops.nfft_ewald_dispersion_virial_far(band, sp.coeffs, strain, box), args.reps)
+    far_t = median_ms(lambda: ((band.abs() ** 2)[..., None] * coef7).sum((1, 2, 3)), args.reps)
+    got = tn.ops.nfft_ewald_dispersion_virial_far(band, sp.coeffs, strain, box)
+    want = ((band.abs() ** 2)[..., None] * coef7).sum((1, 2, 3)).double()
+    tn.ops.check_status()
+    band_bytes = band.numel() * 8
+    print(json.dumps({"bench": "ewald_dispersion_virial", "box": box, "points": n, "neighbours": args.neighbours,
+                      "tol": args.tol, "r_cut": round(r_c, 5), "alpha": round(sp.alpha, 3), "N": N, "m": m, "cells": list(G),
+                      "dispersion_field_ms": round(field, 4), "dispersion_virial_ms": round(virial, 4),
+                      "virial_over_field": round(virial / field, 3), "adjoint_ms": round(adjoint, 4),
+                      "virial_near_ms": round(near_op, 4), "pair_loop_field_ms": round(loop_f, 4),
+                      "pair_loop_virial_ms": round(loop_v, 4), "pairs_tested": tested,
+                      "ps_per_pair_field": round(loop_f * 1e9 / tested, 3),
+                      "ps_per_pair_virial": round(loop_v * 1e9 / tested, 3),
+                      "virial_loop_over_field_loop": round(loop_v / loop_f, 3),
+                      "far_reduction_ms": round(far_v, 4), "far_torch_ms": round(far_t, 4),
+                      "torch_over_far_reduction": round(far_t / far_v, 2),
+                      "far_reduction_GBps": round(band_bytes / far_v * 1e-6, 1),
+                      "far_torch_GBps": round(band_bytes / far_t * 1e-6, 1),
+                      "far_rel_difference": float((got - want).norm() / want.norm())}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, nargs="+", default=[100000, 1000000])
@@ -395,13 +474,15 @@ def main():
     args = ap.parse_args()
     if args.box is not None and len(args.box) not in (3, 6):
         ap.error("--box takes three or six comma-separated numbers")
-    if args.dispersion and (args.box is not None or args.virial):
-        ap.error("--dispersion times the unit cube and goes with neither --box nor --virial")
+    if args.dispersion and args.box is not None:
+        ap.error("--dispersion times the unit cube and does not go with --box")
     torch.cuda.set_device(0)
     lib = _lib.load()
     for n in args.points:
         if args.dispersion:
             run_dispersion(lib, n, args)
+            if args.virial:
+                run_dispersion_virial(lib, n, args)
             continue
         (run if args.box is None else run_box)(lib, n, args)
         if args.virial:

@@ -411,6 +411,21 @@ static int validate_virial_far(int64_t N, int64_t batch_size, int64_t num_column
     return 0;
 }
 
+// the lower triangle of A^-1 as the far reductions take it
+static int validate_box_inverse(const double *box_inverse)
+{
+    if (!box_inverse) { set_error("Input mismatch: box_inverse is null"); return NFFT_HIP_EINVAL; }
+    if (!all_finite(box_inverse, 6, 1e300)) {
+        set_error("Input mismatch: the entries of box_inverse must be finite");
+        return NFFT_HIP_EINVAL;
+    }
+    if (!(box_inverse[0] > 0.0) || !(box_inverse[2] > 0.0) || !(box_inverse[5] > 0.0)) {
+        set_error("Input mismatch: the diagonal of box_inverse must be positive");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
 // the box problem's own checks, and the second level's launch: one workgroup per point set and column
 static int validate_virial_near(const nfft_hip_ewald_box_problem *p)
 {
@@ -431,8 +446,11 @@ int64_t nfft_hip_ewald_virial_near_workspace_bytes(const nfft_hip_ewald_box_prob
     return virial_near_need(p);
 }
 
-int nfft_hip_ewald_virial_near(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
-                               const int32_t *start, double *out, void *workspace, int64_t workspace_bytes, void *stream)
+// (`launch`: the pair reduction of the Coulomb sum, or that of the dispersion sum on the same problem, section 7k)
+typedef int (*virial_near_launch)(const nfft_hip_ewald_box_problem *, const float *, const float *, const int *, double *, void *,
+                                  hipStream_t);
+static int virial_near_call(virial_near_launch launch, const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                            const int32_t *start, double *out, void *workspace, int64_t workspace_bytes, void *stream)
 {
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate_virial_near(p)) return rc;
@@ -445,7 +463,13 @@ int nfft_hip_ewald_virial_near(const nfft_hip_ewald_box_problem *p, const float 
     if (!points || !xr || !start) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
     char *ws = workspace_base(workspace, workspace_bytes, virial_near_need(p));
     if (!ws) return NFFT_HIP_EWORKSPACE;
-    return launch_ewald_virial_near(p, points, xr, start, out, ws, (hipStream_t)stream);
+    return launch(p, points, xr, start, out, ws, (hipStream_t)stream);
+}
+
+int nfft_hip_ewald_virial_near(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                               const int32_t *start, double *out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return virial_near_call(launch_ewald_virial_near, p, points, xr, start, out, workspace, workspace_bytes, stream);
 }
 
 int64_t nfft_hip_ewald_virial_far_workspace_bytes(int64_t N, int64_t batch_size, int64_t num_columns)
@@ -460,15 +484,7 @@ int nfft_hip_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns
 {
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate_virial_far(N, batch_size, num_columns)) return rc;
-    if (!box_inverse) { set_error("Input mismatch: box_inverse is null"); return NFFT_HIP_EINVAL; }
-    if (!all_finite(box_inverse, 6, 1e300)) {
-        set_error("Input mismatch: the entries of box_inverse must be finite");
-        return NFFT_HIP_EINVAL;
-    }
-    if (!(box_inverse[0] > 0.0) || !(box_inverse[2] > 0.0) || !(box_inverse[5] > 0.0)) {
-        set_error("Input mismatch: the diagonal of box_inverse must be positive");
-        return NFFT_HIP_EINVAL;
-    }
+    if (int rc = validate_box_inverse(box_inverse)) return rc;
     if (!(pi2_over_alpha2 > 0.0) || !(pi2_over_alpha2 < 1e300)) {
         set_error("Input mismatch: pi2_over_alpha2 must be positive and finite");
         return NFFT_HIP_EINVAL;
@@ -479,6 +495,29 @@ int nfft_hip_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns
     if (!ws) return NFFT_HIP_EWORKSPACE;
     return launch_ewald_virial_far(N, batch_size, num_columns, band, coeffs, box_inverse, pi2_over_alpha2, out, ws,
                                    (hipStream_t)stream);
+}
+
+// ---- virial tensor of the dispersion Ewald sum: the checks and workspaces of section 7i -------
+int nfft_hip_ewald_dispersion_virial_near(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                                          const int32_t *start, double *out, void *workspace, int64_t workspace_bytes,
+                                          void *stream)
+{
+    return virial_near_call(launch_ewald_dispersion_virial_near, p, points, xr, start, out, workspace, workspace_bytes, stream);
+}
+
+int nfft_hip_ewald_dispersion_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, const void *band,
+                                         const float *coeffs, const float *strain_coeffs, const double *box_inverse, double *out,
+                                         void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_virial_far(N, batch_size, num_columns)) return rc;
+    if (int rc = validate_box_inverse(box_inverse)) return rc;
+    if (num_columns == 0) return 0;
+    if (!band || !coeffs || !strain_coeffs || !out) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    char *ws = workspace_base(workspace, workspace_bytes, virial_far_need(N, batch_size, num_columns));
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_ewald_dispersion_virial_far(N, batch_size, num_columns, band, coeffs, strain_coeffs, box_inverse, out, ws,
+                                              (hipStream_t)stream);
 }
 
 }  // extern "C"

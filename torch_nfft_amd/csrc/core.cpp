@@ -1099,10 +1099,11 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_dispersion_near_box(at::Tensor pos
 // [B, 7, *cols] float64: per point set and column the near part of the energy and of the virial W_ab = -dU / d eps_ab
 // (xx, yy, zz, yz, xz, xy) of the real charges x at the FRACTIONAL positions pos in the box A = box, taken modulo 1 and
 // ordered by cell exactly as nfft_ewald_near_box does
-at::Tensor nfft_ewald_virial_near(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch, std::vector<double> box,
-                                  double alpha, double r_cut)
+// (`reduce`: nfft_hip_ewald_virial_near, or the dispersion sum's pair weights on the same problem, section 7k)
+using VirialNearReduce = decltype(&nfft_hip_ewald_virial_near);
+at::Tensor virial_near_op(VirialNearReduce reduce, const at::Tensor &pos, const at::Tensor &x,
+                          const c10::optional<at::Tensor> &opt_batch, const std::vector<double> &box, double alpha, double r_cut)
 {
-    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_virial_near is currently only implemented for GPU tensors");
     const EwaldInput in = check_ewald(pos, x, opt_batch, false);
     const Points &p = in.p;
     CHECK_INPUT(box.size() == 6);
@@ -1119,16 +1120,25 @@ at::Tensor nfft_ewald_virial_near(at::Tensor pos, at::Tensor x, c10::optional<at
     const at::Tensor xr = real_rows(x, true, p.n, C, o.order);
     at::Tensor out = at::zeros({p.B, 7, C}, opts);
     at::Tensor ws = byte_buffer(ws_bytes, x);
-    check_rc(nfft_hip_ewald_virial_near(&q, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
-                                        out.data_ptr<double>(), ws.data_ptr(), ws_bytes, stream_of(x)));
+    check_rc(reduce(&q, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(), out.data_ptr<double>(),
+                    ws.data_ptr(), ws_bytes, stream_of(x)));
     return out.reshape(shape);
 }
 
-// [B, 7, *cols] float64: the far part of the same from band [B, N, N, N, *cols] complex64 (nfft_adjoint of the charges)
-// and the splitting's coeffs [N, N, N] float32; kappa = A^-1 k is formed in the kernel from box and the index
-at::Tensor nfft_ewald_virial_far(at::Tensor band, at::Tensor coeffs, std::vector<double> box, double alpha)
+at::Tensor nfft_ewald_virial_near(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch, std::vector<double> box,
+                                  double alpha, double r_cut)
 {
-    TORCH_CHECK(band.is_cuda(), "torch_nfft._nfft_ewald_virial_far is currently only implemented for GPU tensors");
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_virial_near is currently only implemented for GPU tensors");
+    return virial_near_op(nfft_hip_ewald_virial_near, pos, x, opt_batch, box, alpha, r_cut);
+}
+
+// [B, 7, *cols] float64: the far part of the same from band [B, N, N, N, *cols] complex64 (nfft_adjoint of the charges)
+// and the splitting's coeffs [N, N, N] float32; kappa = A^-1 k is formed in the kernel from box and the index.
+// (`reduce(N, B, C, band, coeffs, A^-1, out, workspace, bytes, stream)`: nfft_hip_ewald_virial_far with its alpha, or the
+// dispersion sum's reduction with its second grid, section 7k)
+template <class Reduce>
+at::Tensor virial_far_op(const at::Tensor &band, const at::Tensor &coeffs, const std::vector<double> &box, Reduce &&reduce)
+{
     CHECK_INPUT(band.scalar_type() == at::kComplexFloat);
     CHECK_INPUT(coeffs.scalar_type() == at::kFloat);
     CHECK_INPUT(coeffs.device() == band.device());
@@ -1136,7 +1146,6 @@ at::Tensor nfft_ewald_virial_far(at::Tensor band, at::Tensor coeffs, std::vector
     CHECK_INPUT(band.dim() >= 4 && coeffs.dim() == 3);
     const int64_t B = band.size(0), N = band.size(1);
     for (int64_t d = 0; d < 3; ++d) CHECK_INPUT(band.size(1 + d) == N && coeffs.size(d) == N);
-    CHECK_INPUT(alpha > 0.0);
     int64_t C = 1;
     std::vector<int64_t> shape{B, 7};
     for (int64_t d = 4; d < band.dim(); ++d) {
@@ -1156,10 +1165,45 @@ at::Tensor nfft_ewald_virial_far(at::Tensor band, at::Tensor coeffs, std::vector
     const at::Tensor bc = band.contiguous(), cc = coeffs.contiguous();
     at::Tensor out = at::zeros({B, 7, C}, opts);
     at::Tensor ws = byte_buffer(ws_bytes, band);
-    const double pi = 3.14159265358979323846;
-    check_rc(nfft_hip_ewald_virial_far(N, B, C, bc.data_ptr(), cc.data_ptr<float>(), inv, pi * pi / (alpha * alpha),
-                                       out.data_ptr<double>(), ws.data_ptr(), ws_bytes, stream_of(band)));
+    check_rc(reduce(N, B, C, bc.data_ptr(), cc.data_ptr<float>(), inv, out.data_ptr<double>(), ws.data_ptr(), ws_bytes,
+                    stream_of(band)));
     return out.reshape(shape);
+}
+
+at::Tensor nfft_ewald_virial_far(at::Tensor band, at::Tensor coeffs, std::vector<double> box, double alpha)
+{
+    TORCH_CHECK(band.is_cuda(), "torch_nfft._nfft_ewald_virial_far is currently only implemented for GPU tensors");
+    CHECK_INPUT(alpha > 0.0);
+    const double pi = 3.14159265358979323846;
+    return virial_far_op(band, coeffs, box, [&](int64_t N, int64_t B, int64_t C, const void *b, const float *c, const double *inv,
+                                                double *out, void *ws, int64_t ws_bytes, void *stream) {
+        return nfft_hip_ewald_virial_far(N, B, C, b, c, inv, pi * pi / (alpha * alpha), out, ws, ws_bytes, stream);
+    });
+}
+
+// ---- virial tensor of the dispersion Ewald sum (not in the reference) ---------------------------
+// [B, 7, *cols] float64 as the two operators above, for U = 1/2 sum_i c_i psi_i of the periodic 1/r^6: the pair part with the
+// weights of nfft_ewald_dispersion_near_box (w and mg = -w'(r) / r in place of erfc(alpha r) / r and -g) ...
+at::Tensor nfft_ewald_dispersion_virial_near(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch,
+                                             std::vector<double> box, double alpha, double r_cut)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_dispersion_virial_near is currently only implemented for GPU tensors");
+    return virial_near_op(nfft_hip_ewald_dispersion_virial_near, pos, x, opt_batch, box, alpha, r_cut);
+}
+
+// ... and the far part 1/2 sum_k |band_k|^2 (b_k, b_k delta_ab + t_k kappa_a kappa_b) from the splitting's coeffs (b_k) and
+// strain_coeffs (t_k), both [N, N, N] float32
+at::Tensor nfft_ewald_dispersion_virial_far(at::Tensor band, at::Tensor coeffs, at::Tensor strain_coeffs, std::vector<double> box)
+{
+    TORCH_CHECK(band.is_cuda(), "torch_nfft._nfft_ewald_dispersion_virial_far is currently only implemented for GPU tensors");
+    CHECK_INPUT(strain_coeffs.scalar_type() == at::kFloat);
+    CHECK_INPUT(strain_coeffs.device() == band.device());
+    CHECK_INPUT(strain_coeffs.sizes() == coeffs.sizes());
+    const at::Tensor tc = strain_coeffs.contiguous();
+    return virial_far_op(band, coeffs, box, [&](int64_t N, int64_t B, int64_t C, const void *b, const float *c, const double *inv,
+                                                double *out, void *ws, int64_t ws_bytes, void *stream) {
+        return nfft_hip_ewald_dispersion_virial_far(N, B, C, b, c, tc.data_ptr<float>(), inv, out, ws, ws_bytes, stream);
+    });
 }
 
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
@@ -1297,4 +1341,9 @@ TORCH_LIBRARY(torch_nfft, m)
     m.def("_nfft_ewald_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut) -> Tensor",
           &nfft_ewald_virial_near);
     m.def("_nfft_ewald_virial_far(Tensor band, Tensor coeffs, float[] box, float alpha) -> Tensor", &nfft_ewald_virial_far);
+    // not in the reference: the same two reductions for the dispersion Ewald sum 1/r^6 (nfft_ewald_dispersion_virial)
+    m.def("_nfft_ewald_dispersion_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut) "
+          "-> Tensor", &nfft_ewald_dispersion_virial_near);
+    m.def("_nfft_ewald_dispersion_virial_far(Tensor band, Tensor coeffs, Tensor strain_coeffs, float[] box) -> Tensor",
+          &nfft_ewald_dispersion_virial_far);
 }

@@ -22,6 +22,9 @@
 // virial_sum_kernel         second level of both: one workgroup per (point set, column) adds that set's partials, each
 //                           thread a fixed stride of them in order, then the workgroup sum.
 //
+// The second level, the workspaces and their layout also serve the dispersion sum's virial (ewald_disp_virial.hip, section
+// 7k) through launch_virial_sum, ewald_virial_near_item_slots / _partials and ewald_virial_far_blocks.
+//
 // No atomics anywhere and every order of addition is fixed by the launch geometry: two calls give the same bits.
 #include "pair_frame.h"
 
@@ -249,6 +252,18 @@ int64_t round256(int64_t bytes) { return (bytes + 255) & ~int64_t(255); }
 
 }  // namespace
 
+int ewald_virial_far_blocks(int64_t N) { return virial_far_blocks(N); }
+
+// the second level on `partial`: out [batch_size, 7, C]; the rows of a point set as virial_sum_kernel takes them
+int launch_virial_sum(const double *partial, int64_t batch_size, int64_t C, int rows_per_set, const void *items, const int *start,
+                      int cells_per_set, double *out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(virial_sum_kernel, dim3((unsigned)(batch_size * C)), dim3(kVirialBlock), 0, stream, partial, C,
+                       rows_per_set, (const int2 *)items, start, cells_per_set, out);
+    NFFT_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 int64_t ewald_virial_near_item_slots(const nfft_hip_ewald_box_problem *p)
 {
     return nearfield_item_slots(virial_cells(p), p->num_points);
@@ -260,13 +275,19 @@ int64_t ewald_virial_near_workspace(const nfft_hip_ewald_box_problem *p)
     return round256(slots * (int64_t)sizeof(int2)) + slots * kVirialTerms * p->num_columns * (int64_t)sizeof(double);
 }
 
+// the near workspace: the work items, then (256-byte aligned) one partial per item slot
+double *ewald_virial_near_partials(const nfft_hip_ewald_box_problem *p, void *workspace)
+{
+    return (double *)((char *)workspace + round256(ewald_virial_near_item_slots(p) * (int64_t)sizeof(int2)));
+}
+
 int launch_ewald_virial_near(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xr, const int *start,
                              double *out, void *workspace, hipStream_t stream)
 {
     const EwaldPairParams q = ewald_pair_params(p->cells[0], p->cells[1], p->cells[2], p->num_columns, p->alpha, p->r_cut, p->box);
     const int64_t slots = ewald_virial_near_item_slots(p);
     int2 *items = (int2 *)workspace;
-    double *partial = (double *)((char *)workspace + round256(slots * (int64_t)sizeof(int2)));
+    double *partial = ewald_virial_near_partials(p, workspace);
     if (int rc = launch_nearfield_items(virial_cells(p), p->num_points, start, items, stream)) return rc;
     const dim3 grid((unsigned)slots), block(kNearBlock);
     dispatch_columns(q.Cr, [&](auto CC) {
@@ -274,11 +295,8 @@ int launch_ewald_virial_near(const nfft_hip_ewald_box_problem *p, const float *p
                            partial);
     });
     NFFT_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(virial_sum_kernel, dim3((unsigned)(p->batch_size * q.Cr)), dim3(kVirialBlock), 0, stream,
-                       (const double *)partial, q.Cr, 0, (const int2 *)items, start,
-                       (int)(p->cells[0] * p->cells[1] * p->cells[2]), out);
-    NFFT_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_virial_sum(partial, p->batch_size, q.Cr, 0, items, start, (int)(p->cells[0] * p->cells[1] * p->cells[2]), out,
+                             stream);
 }
 
 int64_t ewald_virial_far_workspace(int64_t N, int64_t batch_size, int64_t num_columns)
@@ -308,10 +326,7 @@ int launch_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, 
         hipLaunchKernelGGL((ewald_virial_far_kernel<CC()>), grid, block, 0, stream, q, (const float2 *)band, coeffs, partial);
     });
     NFFT_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(virial_sum_kernel, dim3((unsigned)(batch_size * q.C)), dim3(kVirialBlock), 0, stream,
-                       (const double *)partial, q.C, q.blocks, (const int2 *)nullptr, (const int *)nullptr, 0, out);
-    NFFT_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_virial_sum(partial, batch_size, q.C, q.blocks, nullptr, nullptr, 0, out, stream);
 }
 
 }  // namespace nfft

@@ -202,6 +202,21 @@ int64_t ewald_virial_far_workspace(int64_t N, int64_t batch_size, int64_t num_co
 int launch_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
                             const double *box_inverse, double pi2_over_alpha2, double *out, void *workspace,
                             hipStream_t stream);
+// ... and what the dispersion sum's virial shares with it: the item slots and the partials of the near workspace, the
+// workgroups per point set of the far reduction, and the second level (out [batch_size, 7, C] from `partial`: with `items`
+// the item slots of each set's cells, without them rows_per_set rows per set)
+int64_t ewald_virial_near_item_slots(const nfft_hip_ewald_box_problem *p);
+double *ewald_virial_near_partials(const nfft_hip_ewald_box_problem *p, void *workspace);
+int ewald_virial_far_blocks(int64_t N);
+int launch_virial_sum(const double *partial, int64_t batch_size, int64_t C, int rows_per_set, const void *items, const int *start,
+                      int cells_per_set, double *out, hipStream_t stream);
+// ewald_disp_virial.hip (the virial tensor of the dispersion Ewald sum): arguments as
+// nfft_hip_ewald_dispersion_virial_near / _far, the workspaces those of ewald_virial.hip
+int launch_ewald_dispersion_virial_near(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xr, const int *start,
+                                        double *out, void *workspace, hipStream_t stream);
+int launch_ewald_dispersion_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
+                                       const float *strain_coeffs, const double *box_inverse, double *out, void *workspace,
+                                       hipStream_t stream);
 
 // smallgrid.hip: transforms whose oversampled grid (<= 4096 cells) fits one workgroup's LDS -- one kernel per direction,
 // no point plan

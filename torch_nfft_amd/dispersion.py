@@ -23,7 +23,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import ops
-from .ewald import _TorusSplitting, _fractional, _set_sums, _symmetric_backward
+from .ewald import _IDENTITY6, _TorusSplitting, _fractional, _set_sums, _symmetric_backward, _voigt_to_matrix
 from .nfft import nfft_adjoint, nfft_forward, nfft_fastsum
 
 
@@ -41,6 +41,12 @@ def _far_factor(b):
     return f.clamp(min=0.0)
 
 
+def _strain_factor(b):
+    """``f'(b) / (6 b) = sqrt(pi) b erfc(b) - e^(-b^2)`` of a float64 tensor, clamped at 0 from above: ``-1`` at ``b = 0``,
+    increasing, ``~ -e^(-b^2) / (2 b^2)`` for large ``b``"""
+    return (math.sqrt(math.pi) * b * torch.special.erfc(b) - torch.exp(-b * b)).clamp(max=0.0)
+
+
 class DispersionSplitting(_TorusSplitting):
     """The three parameters of the dispersion split, the box and the far field's coefficients: the counterpart of
     ``EwaldSplitting`` for ``1 / r^6``, with the same arguments, checks, box conventions and attributes (``alpha``,
@@ -55,6 +61,7 @@ class DispersionSplitting(_TorusSplitting):
         b = (math.pi ** 1.5 * self.alpha ** 3 / (3.0 * self.volume)) * _far_factor((math.pi / self.alpha) * torch.sqrt(k2))
         self._b64 = self._zero_unpaired(b)
         self.coeffs = b.to(torch.float32).to(torch.device(device)).contiguous()
+        self._strain_coeffs = None
 
     @classmethod
     def from_tolerance(cls, tol, r_cut, box=None, device="cuda"):
@@ -91,6 +98,20 @@ class DispersionSplitting(_TorusSplitting):
                 cols.append(torch.complex(torch.zeros_like(b), 2.0 * math.pi * kappa[..., a] * b))
             self._field_coeffs = torch.stack(cols, 3).to(torch.complex64).to(self.coeffs.device).contiguous()
         return self._field_coeffs
+
+    def strain_coeffs(self):
+        """``[N, N, N]`` float32 on the device of ``coeffs``: ``t_k = (d b_k / d |kappa|) / |kappa| = (2 pi^(7/2) alpha / V)
+        (sqrt(pi) b erfc(b) - e^(-b^2))``, ``b = pi |kappa| / alpha`` -- what the strain ``A -> A (1 + eps)`` does to ``b_k``,
+        ``d b_k / d eps_ab = -t_k kappa_a kappa_b`` beside the volume's ``-b_k delta_ab`` (``nfft_ewald_dispersion_virial``).
+        Evaluated in float64 on the host (the two terms cancel to ``-e^(-b^2) / (2 b^2)`` at large ``b``), clamped at ``<= 0``,
+        finite at ``k = 0`` and zero wherever ``coeffs`` is zero (the unpaired planes ``k_a = -N/2``, and cells whose ``b_k`` is
+        below float32: the native reduction skips them); built on first use."""
+        if self._strain_coeffs is None:
+            b = (math.pi / self.alpha) * torch.sqrt((self._kappa() ** 2).sum(3))
+            t = (2.0 * math.pi ** 3.5 * self.alpha / self.volume) * _strain_factor(b)
+            t[self.coeffs.cpu() == 0] = 0.0
+            self._strain_coeffs = t.to(torch.float32).to(self.coeffs.device).contiguous()
+        return self._strain_coeffs
 
 
 def _dispersion(c, pos, batch, splitting, cutoff, field):
@@ -138,13 +159,15 @@ class NfftEwaldDispersionFunction(torch.autograd.Function):
         return _symmetric_backward(_dispersion, ctx, g)
 
 
-def _check(what, c, pos, batch, splitting):
+def _check(what, c, pos, batch, splitting, differentiable=True):
     if not isinstance(splitting, DispersionSplitting):
         raise TypeError("%s: splitting must be a DispersionSplitting" % what)
     if pos.dim() != 2 or pos.size(1) != 3:
         raise ValueError("%s: the periodic 1/r^6 sum is three-dimensional, pos must be [n, 3]" % what)
     if batch is not None and batch.requires_grad:
-        raise AssertionError("%s is differentiable w.r.t. c and pos only, but batch requires grad" % what)
+        if differentiable:
+            raise AssertionError("%s is differentiable w.r.t. c and pos only, but batch requires grad" % what)
+        raise AssertionError("%s: batch holds point-set indices and must not require grad" % what)
 
 
 def nfft_ewald_dispersion(c, pos, batch=None, /, splitting=None, cutoff=4, field=False, fractional=False):
@@ -180,3 +203,41 @@ def nfft_ewald_dispersion_energy(c, pos, batch=None, /, splitting=None, cutoff=4
         raise ValueError("nfft_ewald_dispersion_energy: fractional=True needs a DispersionSplitting with a box")
     psi = nfft_ewald_dispersion(c, pos, batch, splitting=splitting, cutoff=cutoff, fractional=fractional)
     return 0.5 * _set_sums(c * psi, batch)[0]
+
+
+def nfft_ewald_dispersion_virial(c, pos, batch=None, /, splitting=None, cutoff=4, fractional=False):
+    """``(U, W)``: ``U_b = 1/2 sum_{i in point set b} c_i psi_i`` ``[B, *cols]`` of ``nfft_ewald_dispersion_energy`` and the
+    virial tensor ``W_ab = -dU / d eps_ab`` ``[B, 3, 3, *cols]`` for the homogeneous strain ``A -> A (1 + eps)`` of the box at
+    fixed fractional coordinates, per point set and column, both with the dtype of ``c``: the counterpart of
+    ``nfft_ewald_virial`` for ``1 / r^6`` (DESIGN.md section 7k).  ``W`` is symmetric and in the box's units (energy);
+    ``psi`` is homogeneous of degree -6 in the box, so ``tr W = 6 U`` up to the truncation of the sum (``tr W = U`` for
+    ``1/r``).  The signs are those of ``nfft_ewald_dispersion_energy``: the physical dispersion energy and virial of the pair
+    coefficients ``C6_ij = c_i c_j`` are the NEGATIVES ``-U`` and ``-W``, ``-W / splitting.volume`` is the dispersion part of
+    the pressure tensor, and ``virial_to_box_gradient(W, splitting.box)`` is the gradient of ``U`` in the box's entries.
+
+    ``c`` ``[n, *cols]`` must be real (float32): the energy is bilinear and for complex coefficients the far part is not
+    ``|S_k|^2`` (ValueError).  ``pos``, ``batch``, ``cutoff`` and ``fractional`` are those of ``nfft_ewald_dispersion``,
+    ``splitting`` a ``DispersionSplitting`` (TypeError otherwise); without a box the cell is the unit cube.
+
+    One adjoint transform, then two native reductions in float64 and without atomics -- over the frequencies of its output,
+    ``1/2 sum_k |S_k|^2 (b_k, b_k delta_ab + t_k kappa_a kappa_b)`` with ``t = splitting.strain_coeffs()``, and over the pairs
+    within ``r_cut``, ``1/2 sum_ij c_i c_j (w, mg d_a d_b)`` -- and the self term ``-(alpha^6 / 12) sum c_i^2`` (in ``U`` only: it
+    has no strain in it) added in float64 before the cast.  The ``k = 0`` term is part of both sums: no background.
+
+    Runs under ``torch.no_grad()``: ``U`` and ``W`` are constants to autograd.  Inputs that require grad are accepted and
+    get no gradient from here (use ``nfft_ewald_dispersion_energy`` for forces); ``batch`` must not require grad
+    (AssertionError)."""
+    _check("nfft_ewald_dispersion_virial", c, pos, batch, splitting, differentiable=False)
+    if c.is_complex():
+        raise ValueError("nfft_ewald_dispersion_virial: the coefficients must be real (the energy is bilinear in c)")
+    with torch.no_grad():
+        c, pos = c.detach(), pos.detach()
+        pos = _fractional("nfft_ewald_dispersion_virial", pos, splitting, fractional)
+        alpha, N = splitting.alpha, splitting.bandwidth
+        box6 = _IDENTITY6 if splitting.box is None else splitting.box6
+        band = nfft_adjoint(c, pos, batch, bandwidth=N, cutoff=int(cutoff))  # [B, N, N, N, *cols]
+        seven = ops.nfft_ewald_dispersion_virial_far(band, splitting.coeffs, splitting.strain_coeffs(), box6)
+        seven = seven + ops.nfft_ewald_dispersion_virial_near(pos, c, batch, box6, alpha, splitting.r_cut)  # [B, 7, *cols] float64
+        c64 = c.double()
+        U = seven[:, 0] - (alpha ** 6 / 12.0) * _set_sums(c64 * c64, batch)[0]
+        return U.to(c.dtype), _voigt_to_matrix(seven[:, 1:]).to(c.dtype)

@@ -392,6 +392,15 @@ _IDENTITY6 = (1.0, 0.0, 1.0, 0.0, 0.0, 1.0)
 _VOIGT = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))  # the order of the two native reductions after the energy
 
 
+def _voigt_to_matrix(six):
+    """``[B, 6, *cols]`` in that order as the symmetric ``[B, 3, 3, *cols]``"""
+    W = six.new_zeros((six.size(0), 3, 3) + tuple(six.shape[2:]))
+    for e, (a, b) in enumerate(_VOIGT):
+        W[:, a, b] = six[:, e]
+        W[:, b, a] = six[:, e]
+    return W
+
+
 def nfft_ewald_virial(q, pos, batch=None, /, splitting=None, cutoff=4, fractional=False):
     """``(U, W)``: the energy ``U_b = 1/2 sum_{i in point set b} q_i phi_i`` ``[B, *cols]`` of ``nfft_ewald_energy`` and
     the virial tensor ``W_ab = -dU / d eps_ab`` ``[B, 3, 3, *cols]`` for the homogeneous strain ``A -> A (1 + eps)`` of the
@@ -426,10 +435,7 @@ def nfft_ewald_virial(q, pos, batch=None, /, splitting=None, cutoff=4, fractiona
         total = _set_sums(q64, batch)[0]
         background = (math.pi / (2.0 * alpha * alpha * splitting.volume)) * total * total
         U = seven[:, 0] - (alpha / math.sqrt(math.pi)) * _set_sums(q64 * q64, batch)[0] - background
-        W = seven.new_zeros((seven.size(0), 3, 3) + tuple(seven.shape[2:]))
-        for e, (a, b) in enumerate(_VOIGT):
-            W[:, a, b] = seven[:, 1 + e]
-            W[:, b, a] = seven[:, 1 + e]
+        W = _voigt_to_matrix(seven[:, 1:])
         for a in range(3):
             W[:, a, a] -= background
         return U.to(q.dtype), W.to(q.dtype)
@@ -439,7 +445,10 @@ def virial_to_box_gradient(W, box):
     """``dU/dA`` at fixed fractional coordinates from the virial ``W`` ``[B, 3, 3, *cols]`` of ``nfft_ewald_virial``:
     ``tril(-A^-T W)`` ``[B, 3, 3, *cols]``, the six free entries of the lower-triangular box ``A`` (zeros above the
     diagonal).  ``box`` as ``EwaldSplitting`` takes it (three edges or ``[3, 3]`` lower triangular); ``None`` is the unit
-    cube.  Pure torch, on the device and in the dtype of ``W``."""
+    cube.  Pure torch, on the device and in the dtype of ``W``.
+
+    The identity holds for any energy and its strain derivative, so the ``W`` of ``nfft_ewald_dispersion_virial`` goes
+    through unchanged and gives the gradient of that function's ``U`` (the physical dispersion energy is ``-U``: negate)."""
     if W.dim() < 3 or W.size(1) != 3 or W.size(2) != 3:
         raise ValueError("virial_to_box_gradient: W must be [B, 3, 3, *cols]")
     inv = torch.eye(3, dtype=torch.float64) if box is None else _box_inverse(_box_matrix(box))

@@ -239,6 +239,32 @@ def nfft_ewald_virial_far(band, coeffs, box, alpha):
     return _ops._nfft_ewald_virial_far(band, coeffs, [float(a) for a in box], float(alpha))
 
 
+def nfft_ewald_dispersion_virial_near(pos, x, batch, box, alpha, r_cut):
+    """torch_nfft::_nfft_ewald_dispersion_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha,
+    float r_cut) -> Tensor (not in the reference): ``nfft_ewald_virial_near`` for the dispersion sum, ``[B, 7, *cols]``
+    float64 in the same order, with the pair weights of ``nfft_ewald_dispersion_near``::
+
+        out[b, 0] = 1/2 sum_{i in set b} x_i sum_{j: 0 < r_ij < r_cut} w(r_ij) x_j
+        out[b, e] = 1/2 sum_i x_i sum_j mg(r_ij) d_ij[a] d_ij[b] x_j
+
+    Arguments as there.  One native call (``nfft_hip_ewald_dispersion_virial_near``), no atomics:
+    two calls give the same bits."""
+    return _ops._nfft_ewald_dispersion_virial_near(pos, x, batch, [float(a) for a in box], float(alpha), float(r_cut))
+
+
+def nfft_ewald_dispersion_virial_far(band, coeffs, strain_coeffs, box):
+    """torch_nfft::_nfft_ewald_dispersion_virial_far(Tensor band, Tensor coeffs, Tensor strain_coeffs, float[] box) ->
+    Tensor (not in the reference): the spectral part of the same, ``[B, 7, *cols]`` float64, from ``band``
+    ``[B, N, N, N, *cols]`` complex64 and a ``DispersionSplitting``'s ``coeffs`` (``b_k``) and ``strain_coeffs()`` (``t_k``),
+    both ``[N, N, N]`` float32::
+
+        out[b, 0] = 1/2 sum_k b_k |band_k|^2
+        out[b, e] = 1/2 sum_k |band_k|^2 (b_k delta_ab + t_k kappa_a kappa_b),  kappa = A^-1 k
+
+    One native call (``nfft_hip_ewald_dispersion_virial_far``), one pass over ``band``, no atomics."""
+    return _ops._nfft_ewald_dispersion_virial_far(band, coeffs, strain_coeffs, [float(a) for a in box])
+
+
 class _on_device:
     """The coefficient operators create their output on the current device (like the reference, which has no
     device argument); ``device=`` selects it for the duration of the call."""
