@@ -524,6 +524,38 @@ int nfft_hip_ewald_dispersion_virial_far(int64_t N, int64_t batch_size, int64_t 
                                          const float *coeffs, const float *strain_coeffs, const double *box_inverse, double *out,
                                          void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- Ewald sum of point charges and point dipoles (no reference counterpart) ----
+ * Source j carries a charge q_j and a Cartesian dipole mu_j, packed as xs [points, 4, num_columns] = (q, mu_x, mu_y, mu_z).
+ * With d = d_ij, r = |d|, m = mu_j . d and the Smith functions B_0 = erfc(alpha r) / r,
+ * B_l = ((2l - 1) B_(l-1) + (2 alpha^2)^l / (alpha sqrt(pi)) exp(-alpha^2 r^2)) / r^2, the two near entry points give, over the
+ * pairs 0 < r_ij < r_cut of one point set,
+ *     phi[i]     = sum_j q_j B_0 + m B_1
+ *     E[i, a]    = sum_j (q_j B_1 + m B_2) d_a - mu_j,a B_1                                        (E = -grad phi)
+ *     T[i, a, b] = sum_j q_j (delta_ab B_1 - d_a d_b B_2) + (mu_j,a d_b + mu_j,b d_a + m delta_ab) B_2 - m d_a d_b B_3
+ * (T_ab = d E_a / d x_b) as out [points, 4, num_columns] = (phi, E_x, E_y, E_z) for order = 1 and out [points, 10,
+ * num_columns] for order = 2, T following in the order xx, yy, zz, yz, xz, xy; rows in the caller's order through index.
+ * Problem structs (num_columns counts the columns of four values; with_field must be 0 or 1 and is otherwise not read),
+ * the order of the points, validation, error codes, determinism and workspace are those of nfft_hip_ewald_near and
+ * nfft_hip_ewald_near_box: nfft_hip_ewald_near_workspace_bytes and nfft_hip_ewald_near_box_workspace_bytes serve these
+ * sweeps too.  order must be 1 or 2 ("Input mismatch").
+ *
+ * nfft_hip_ewald_dipole_spectral: band [batch_size, N, N, N, 4, num_columns] complex64 (the adjoint transform of xs, index
+ * k + N/2), coeffs [N, N, N] float32 (b_k), box_inverse[6] = the lower triangle I00, I10, I11, I20, I21, I22 of A^-1
+ * (kappa = A^-1 k; the unit cube: 1, 0, 1, 0, 0, 1).  With rho_k = band_q + 2 pi i kappa . band_mu and R = b_k rho_k it writes
+ * out [batch_size, N, N, N, 4 or 10, num_columns] complex64,
+ *     out[.., 0] = R,   out[.., 1 + a] = 2 pi i kappa_a R,   out[.., 4 + e] = 4 pi^2 kappa_a kappa_b R   (order = 2),
+ * whose forward transform is the far part of (phi, E, T): the signs are those of the transforms (the adjoint sums
+ * exp(+2 pi i k.s), the forward exp(-2 pi i k.s)).  2 pi kappa is formed in float32 from the float64 box_inverse.  One
+ * pass, no workspace.  N even, 2 <= N <= 2048, 1 <= batch_size < 2^14, 0 <= num_columns < 2^21, N^3 num_columns < 2^31. */
+int nfft_hip_ewald_dipole_near(const nfft_hip_ewald_problem *p, const float *points, const float *xs, const int32_t *start,
+                               const int64_t *index, int32_t order, float *out, void *workspace, int64_t workspace_bytes,
+                               void *stream);
+int nfft_hip_ewald_dipole_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xs,
+                                   const int32_t *start, const int64_t *index, int32_t order, float *out, void *workspace,
+                                   int64_t workspace_bytes, void *stream);
+int nfft_hip_ewald_dipole_spectral(int64_t N, int64_t batch_size, int64_t num_columns, int32_t order, const void *band,
+                                   const float *coeffs, const double *box_inverse, void *out, void *stream);
+
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.
  *   gaussian_analytic_coeffs      float32:  prod_d sqrt(pi) sigma exp(-sigma^2 pi^2 l_d^2)      (kernel_coeffs.cu:6-30)

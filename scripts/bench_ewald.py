@@ -48,6 +48,14 @@ box on the same points and coefficients: nfft_ewald_dispersion_virial beside nff
 of nfft_hip_ewald_dispersion_virial_near beside the dispersion field loop (nfft_hip_ewald_dispersion_near_box), in
 picoseconds per tested pair; and the far reduction (ops.nfft_ewald_dispersion_virial_far) beside the torch composition on
 the same band, with its agreement with it.
+
+    python scripts/bench_ewald.py --dipole [...]
+
+times the sum of charges and point dipoles in the unit cube on the same points, r_c, alpha and N:
+nfft_ewald_dipole of order 1 and 2 beside nfft_ewald with its field; the near operator; the spectral kernel beside the
+torch composition on the same band; and the dipole pair loops of order 1 and 2 (nfft_hip_ewald_dipole_near on restated
+plumbing) beside the Coulomb pair loop with its field (nfft_hip_ewald_near) on the same sorted points and cells.  The calls
+of a group are timed in turn (a, b, c, a, b, c, ...), median, minimum and maximum of `reps` each.
 """
 import argparse
 import ctypes
@@ -461,6 +469,94 @@ def run_dispersion_virial(lib, n, args):
                       "far_rel_difference": float((got - want).norm() / want.norm())}))
 
 
+def alternating_ms(fns, reps):
+    """{name: (median, min, max) ms} of the calls `fns` {name: fn}, timed with device events in turn -- a, b, c, a, b, c, ... --
+    after two warm-up calls each, so that what else the machine does falls on all of them alike"""
+    for fn in fns.values():
+        fn()
+        fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in fns}
+    for _ in range(reps):
+        for name, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[name].append(a.elapsed_time(b))
+    return {name: (float(np.median(t)), float(min(t)), float(max(t))) for name, t in times.items()}
+
+
+def run_dipole(lib, n, args):
+    """the sum of charges and point dipoles in the unit cube: the same points, r_c, alpha and N as `run`"""
+    m = 4
+    r_c = min((3.0 * args.neighbours / (4.0 * math.pi * n)) ** (1.0 / 3.0), 1.0 / 3.0)
+    sp = tn.EwaldSplitting.from_tolerance(args.tol, r_c)
+    rng = np.random.default_rng(0)
+    v = (rng.random((n, 3)) - 0.5).astype(np.float32)
+    v[v >= 0.5] = -0.5  # (rounded up to the face: the same point)
+    pos = torch.from_numpy(v).cuda()
+    q = torch.from_numpy(rng.standard_normal(n).astype(np.float32)).cuda()
+    mu = torch.from_numpy(rng.standard_normal((n, 3)).astype(np.float32)).cuda()
+    packed = torch.cat([q.unsqueeze(1), mu], 1).contiguous()  # [n, 4]
+    G, N = int(lib.nfft_hip_ewald_near_cells(r_c, 1)), sp.bandwidth
+    wrapped, _ = pairs_tested(v, G)
+    whole = alternating_ms({
+        "coulomb_field": lambda: tn.nfft_ewald(q, pos, splitting=sp, cutoff=m, field=True),
+        "order1": lambda: tn.nfft_ewald_dipole(q, mu, pos, splitting=sp, cutoff=m),
+        "order2": lambda: tn.nfft_ewald_dipole(q, mu, pos, splitting=sp, cutoff=m, gradient=True),
+        "near_op1": lambda: tn.ops.nfft_ewald_dipole_near(pos, packed, None, (), sp.alpha, r_c, 1),
+        "near_op2": lambda: tn.ops.nfft_ewald_dipole_near(pos, packed, None, (), sp.alpha, r_c, 2)}, args.reps)
+    # the spectral step beside the torch composition on the same band
+    band = tn.nfft_adjoint(packed, pos, bandwidth=N, cutoff=m)  # [1, N, N, N, 4]
+    tau = 2.0 * math.pi * sp._kappa()
+    row0 = sp._b64.unsqueeze(3) * torch.cat([torch.ones(N, N, N, 1, dtype=torch.complex128), 1j * tau], 3)
+    rows = [row0] + [1j * tau[..., a, None] * row0 for a in range(3)] + \
+           [(tau[..., a] * tau[..., b]).unsqueeze(3) * row0 for a, b in ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))]
+    table = torch.stack(rows, 3).to(torch.complex64).cuda()  # [N, N, N, 10, 4]
+    spectral = alternating_ms({
+        "kernel": lambda: tn.ops.nfft_ewald_dipole_spectral(band, sp.coeffs, (), 2),
+        "torch": lambda: torch.einsum("xyzsr,bxyzr->bxyzs", table, band)}, args.reps)
+    got, want = tn.ops.nfft_ewald_dipole_spectral(band, sp.coeffs, (), 2), torch.einsum("xyzsr,bxyzr->bxyzs", table, band)
+    # the pair loops on their own, on the same sorted points and cells: the Coulomb loop with its field, the dipole loops
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    spos, order, start = cell_order(pos, G, 0.5, G)
+    xq = q.index_select(0, order).reshape(n, 1).contiguous()
+    xp = packed.index_select(0, order).contiguous()
+    z, f = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+    outs = {1: torch.zeros(n, 4, device="cuda"), 2: torch.zeros(n, 10, device="cuda")}
+    p = _lib.EwaldProblem(cells_per_axis=G, with_field=1, num_points=n, num_columns=1, batch_size=1, alpha=sp.alpha, r_cut=r_c)
+    nbytes = lib.nfft_hip_ewald_near_workspace_bytes(ctypes.byref(p))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+
+    def coulomb_loop():
+        _lib.check(lib.nfft_hip_ewald_near(ctypes.byref(p), spos.data_ptr(), xq.data_ptr(), start.data_ptr(), order.data_ptr(),
+                                           z.data_ptr(), f.data_ptr(), ws.data_ptr(), nbytes, stream))
+
+    def dipole_loop(o):
+        _lib.check(lib.nfft_hip_ewald_dipole_near(ctypes.byref(p), spos.data_ptr(), xp.data_ptr(), start.data_ptr(),
+                                                  order.data_ptr(), o, outs[o].data_ptr(), ws.data_ptr(), nbytes, stream))
+
+    loops = alternating_ms({"coulomb": coulomb_loop, "order1": lambda: dipole_loop(1), "order2": lambda: dipole_loop(2)}, args.reps)
+    assert torch.equal(tn.ops.nfft_ewald_dipole_near(pos, packed, None, (), sp.alpha, r_c, 2), outs[2]), \
+        "the restated plumbing must give the operator's bits"
+    tn.ops.check_status()
+    ms = lambda t: [round(e, 4) for e in t]  # noqa: E731
+    print(json.dumps({"bench": "ewald_dipole", "points": n, "neighbours": args.neighbours, "tol": args.tol, "r_cut": round(r_c, 5),
+                      "alpha": round(sp.alpha, 3), "N": N, "m": m, "cells_per_axis": G, "reps": args.reps,
+                      "median_min_max_ms": {"whole": {k: ms(t) for k, t in whole.items()},
+                                            "spectral": {k: ms(t) for k, t in spectral.items()},
+                                            "pair_loop": {k: ms(t) for k, t in loops.items()}},
+                      "pairs_tested": wrapped,
+                      "ps_per_pair": {k: round(t[0] * 1e9 / wrapped, 3) for k, t in loops.items()},
+                      "order1_over_coulomb_field_loop": round(loops["order1"][0] / loops["coulomb"][0], 3),
+                      "order2_over_coulomb_field_loop": round(loops["order2"][0] / loops["coulomb"][0], 3),
+                      "torch_over_spectral_kernel": round(spectral["torch"][0] / spectral["kernel"][0], 2),
+                      "spectral_GBps": round((band.numel() + got.numel()) * 8 / spectral["kernel"][0] * 1e-6, 1),
+                      "spectral_rel_difference": float((got - want).norm() / want.norm())}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, nargs="+", default=[100000, 1000000])
@@ -471,14 +567,20 @@ def main():
                     help="a,b,c (orthorhombic) or A00,A10,A11,A20,A21,A22 (lower triangular, rows = lattice vectors)")
     ap.add_argument("--virial", action="store_true", help="add a row for nfft_ewald_virial and its two reductions")
     ap.add_argument("--dispersion", action="store_true", help="time the dispersion sum 1/r^6 (unit cube) instead")
+    ap.add_argument("--dipole", action="store_true", help="time the sum of charges and point dipoles (unit cube) instead")
     args = ap.parse_args()
     if args.box is not None and len(args.box) not in (3, 6):
         ap.error("--box takes three or six comma-separated numbers")
     if args.dispersion and args.box is not None:
         ap.error("--dispersion times the unit cube and does not go with --box")
+    if args.dipole and (args.box is not None or args.dispersion or args.virial):
+        ap.error("--dipole times the unit cube on its own")
     torch.cuda.set_device(0)
     lib = _lib.load()
     for n in args.points:
+        if args.dipole:
+            run_dipole(lib, n, args)
+            continue
         if args.dispersion:
             run_dispersion(lib, n, args)
             if args.virial:

@@ -1,5 +1,5 @@
 // C-ABI entry points of the pair kernels (include/nfft_hip.h): the near field of the fast summation for singular kernels,
-// the near parts of the Ewald sums (1/r and 1/r^6) on the torus and in a box, the virial reductions.  They share only the error plumbing and
+// the near parts of the Ewald sums (1/r, 1/r^6 and dipoles) on the torus and in a box, the virial reductions.  They share only the error plumbing and
 // the workspace conventions (host_util.h) with the transforms of api.hip.
 #include "../../include/nfft_hip.h"
 
@@ -240,7 +240,8 @@ int64_t nfft_hip_ewald_near_workspace_bytes(const nfft_hip_ewald_problem *p)
     return ewald_near_need(p);
 }
 
-// the checks of a wrapped pair sweep on the torus, then `launch` (the Coulomb sweep or the dispersion sweep of section 7j)
+// the checks of a wrapped pair sweep on the torus, then `launch` (the Coulomb sweep, the dispersion sweep of section 7j or
+// the dipole sweep of section 7l)
 typedef int (*ewald_launch)(const nfft_hip_ewald_problem *, const float *, const float *, const int *, const int64_t *, float *,
                             float *, void *, hipStream_t);
 static int ewald_near_call(ewald_launch launch, const nfft_hip_ewald_problem *p, const float *points, const float *xr,
@@ -398,6 +399,57 @@ int nfft_hip_ewald_dispersion_near_box(const nfft_hip_ewald_box_problem *p, cons
                                workspace_bytes, stream);
 }
 
+// ---- Ewald sum of charges and point dipoles: the same problems, checks and workspaces ------------
+static int check_dipole_order(int32_t order)
+{
+    if (order != 1 && order != 2) { set_error("Input mismatch: order must be 1 or 2"); return NFFT_HIP_EINVAL; }
+    return 0;
+}
+
+// the dipole sweeps of order 1 and 2 as the shared calls launch them (one output: the field pointer is not used)
+static int dipole_near_1(const nfft_hip_ewald_problem *p, const float *pos, const float *xs, const int *start, const int64_t *index,
+                         float *out, float *, void *items, hipStream_t s)
+{
+    return launch_ewald_dipole_near(p, 1, pos, xs, start, index, out, items, s);
+}
+
+static int dipole_near_2(const nfft_hip_ewald_problem *p, const float *pos, const float *xs, const int *start, const int64_t *index,
+                         float *out, float *, void *items, hipStream_t s)
+{
+    return launch_ewald_dipole_near(p, 2, pos, xs, start, index, out, items, s);
+}
+
+static int dipole_near_box_1(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xs, const int *start,
+                             const int64_t *index, float *out, float *, void *items, hipStream_t s)
+{
+    return launch_ewald_dipole_near_box(p, 1, pos, xs, start, index, out, items, s);
+}
+
+static int dipole_near_box_2(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xs, const int *start,
+                             const int64_t *index, float *out, float *, void *items, hipStream_t s)
+{
+    return launch_ewald_dipole_near_box(p, 2, pos, xs, start, index, out, items, s);
+}
+
+// (out stands for z and for field in the shared checks)
+int nfft_hip_ewald_dipole_near(const nfft_hip_ewald_problem *p, const float *points, const float *xs, const int32_t *start,
+                               const int64_t *index, int32_t order, float *out, void *workspace, int64_t workspace_bytes,
+                               void *stream)
+{
+    if (int rc = check_dipole_order(order)) return rc;
+    return ewald_near_call(order == 2 ? dipole_near_2 : dipole_near_1, p, points, xs, start, index, out, out, workspace,
+                           workspace_bytes, stream);
+}
+
+int nfft_hip_ewald_dipole_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xs,
+                                   const int32_t *start, const int64_t *index, int32_t order, float *out, void *workspace,
+                                   int64_t workspace_bytes, void *stream)
+{
+    if (int rc = check_dipole_order(order)) return rc;
+    return ewald_near_box_call(order == 2 ? dipole_near_box_2 : dipole_near_box_1, p, points, xs, start, index, out, out,
+                               workspace, workspace_bytes, stream);
+}
+
 // ---- virial tensor of the Ewald sum -----------------------------------------------------------
 static int validate_virial_far(int64_t N, int64_t batch_size, int64_t num_columns)
 {
@@ -495,6 +547,23 @@ int nfft_hip_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns
     if (!ws) return NFFT_HIP_EWORKSPACE;
     return launch_ewald_virial_far(N, batch_size, num_columns, band, coeffs, box_inverse, pi2_over_alpha2, out, ws,
                                    (hipStream_t)stream);
+}
+
+// ---- the spectral step of the dipole sum -------------------------------------------------------
+int nfft_hip_ewald_dipole_spectral(int64_t N, int64_t batch_size, int64_t num_columns, int32_t order, const void *band,
+                                   const float *coeffs, const double *box_inverse, void *out, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = check_dipole_order(order)) return rc;
+    if (int rc = validate_virial_far(N, batch_size, num_columns)) return rc;
+    if (N * N * N * num_columns >= (int64_t(1) << 31)) {
+        set_error("Input mismatch: N^3 num_columns < 2^31 is required");
+        return NFFT_HIP_EINVAL;
+    }
+    if (int rc = validate_box_inverse(box_inverse)) return rc;
+    if (num_columns == 0) return 0;
+    if (!band || !coeffs || !out) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    return launch_ewald_dipole_spectral(N, batch_size, num_columns, order, band, coeffs, box_inverse, out, (hipStream_t)stream);
 }
 
 // ---- virial tensor of the dispersion Ewald sum: the checks and workspaces of section 7i -------

@@ -1206,6 +1206,101 @@ at::Tensor nfft_ewald_dispersion_virial_far(at::Tensor band, at::Tensor coeffs, 
     });
 }
 
+// ---- Ewald sum of charges and point dipoles (not in the reference) ------------------------------
+// [n, 4 or 10, *cols] float32: the pair sums (phi, E) and, at order 2, the six entries xx, yy, zz, yz, xz, xy of T = grad E of
+// the packed sources xs [n, 4, *cols] = (q, mu) over the pairs within r_cut, with the Smith functions of alpha.  An empty box:
+// the unit torus, pos taken modulo 1; six numbers: the box A of nfft_ewald_near_box, pos FRACTIONAL, mu, E and T Cartesian.
+at::Tensor nfft_ewald_dipole_near(at::Tensor pos, at::Tensor xs, c10::optional<at::Tensor> opt_batch, std::vector<double> box,
+                                  double alpha, double r_cut, int64_t order)
+{
+    TORCH_CHECK(xs.is_cuda(), "torch_nfft._nfft_ewald_dipole_near is currently only implemented for GPU tensors");
+    const Points p = check_points(pos, opt_batch, "batch");
+    CHECK_INPUT(p.dim == 3);
+    CHECK_INPUT(xs.scalar_type() == at::kFloat);
+    const Coeffs cx = check_spatial(xs, p.n, 2);
+    CHECK_INPUT(xs.size(1) == 4);
+    CHECK_INPUT(xs.device() == pos.device());
+    CHECK_INPUT(box.empty() || box.size() == 6);
+    CHECK_INPUT(order == 1 || order == 2);
+    const int64_t sums = order == 2 ? 10 : 4, C = cx.C;
+    const std::vector<int64_t> shape = cx.shape({p.n, sums});
+    nfft_hip_ewald_problem qc;
+    nfft_hip_ewald_box_problem qb;
+    int32_t cells[3];
+    int64_t ws_bytes;
+    if (box.empty()) {
+        qc.with_field = 1;
+        qc.num_points = p.n;
+        qc.num_columns = C;
+        qc.batch_size = p.B;
+        qc.alpha = alpha;
+        qc.r_cut = r_cut;
+        const int64_t G = nfft_hip_ewald_near_cells(r_cut, qc.batch_size);
+        if (G < 0) check_rc(NFFT_HIP_EINVAL);
+        qc.cells_per_axis = cells[0] = cells[1] = cells[2] = (int32_t)G;
+        ws_bytes = nfft_hip_ewald_near_workspace_bytes(&qc);
+    } else {
+        qb = ewald_box_problem(p, C, true, box, alpha, r_cut);
+        for (int a = 0; a < 3; ++a) cells[a] = qb.cells[a];
+        ws_bytes = nfft_hip_ewald_near_box_workspace_bytes(&qb);
+    }
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    if (p.n == 0 || C == 0) return at::zeros(shape, xs.options());  // no launch
+    c10::DeviceGuard guard(xs.device());
+    const CellOrder o = torus_cell_order(p, cells);
+    const at::Tensor xr = real_rows(xs, true, p.n, 4 * C, o.order);
+    // (zeros: a point whose coordinates are not numbers has no cell and is not written)
+    at::Tensor out = at::zeros({p.n, sums * C}, xs.options());
+    at::Tensor ws = byte_buffer(ws_bytes, xs);
+    if (box.empty())
+        check_rc(nfft_hip_ewald_dipole_near(&qc, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
+                                            o.order.data_ptr<int64_t>(), (int32_t)order, out.data_ptr<float>(), ws.data_ptr(),
+                                            ws_bytes, stream_of(xs)));
+    else
+        check_rc(nfft_hip_ewald_dipole_near_box(&qb, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
+                                                o.order.data_ptr<int64_t>(), (int32_t)order, out.data_ptr<float>(), ws.data_ptr(),
+                                                ws_bytes, stream_of(xs)));
+    return out.reshape(shape);
+}
+
+// [B, N, N, N, 4 or 10, *cols] complex64: the spectra of the far part of (phi, E, T) from band [B, N, N, N, 4, *cols] complex64
+// (nfft_adjoint of the packed sources) and the splitting's coeffs [N, N, N] float32; kappa = A^-1 k is formed in the kernel
+// from box (empty: the unit cube) and the index
+at::Tensor nfft_ewald_dipole_spectral(at::Tensor band, at::Tensor coeffs, std::vector<double> box, int64_t order)
+{
+    TORCH_CHECK(band.is_cuda(), "torch_nfft._nfft_ewald_dipole_spectral is currently only implemented for GPU tensors");
+    CHECK_INPUT(band.scalar_type() == at::kComplexFloat);
+    CHECK_INPUT(coeffs.scalar_type() == at::kFloat);
+    CHECK_INPUT(coeffs.device() == band.device());
+    CHECK_INPUT(box.empty() || box.size() == 6);
+    CHECK_INPUT(order == 1 || order == 2);
+    CHECK_INPUT(band.dim() >= 5 && coeffs.dim() == 3);
+    const int64_t B = band.size(0), N = band.size(1);
+    for (int64_t d = 0; d < 3; ++d) CHECK_INPUT(band.size(1 + d) == N && coeffs.size(d) == N);
+    CHECK_INPUT(band.size(4) == 4);
+    int64_t C = 1;
+    std::vector<int64_t> shape{B, N, N, N, order == 2 ? 10 : 4};
+    for (int64_t d = 5; d < band.dim(); ++d) {
+        C *= band.size(d);
+        shape.push_back(band.size(d));
+    }
+    double inv[6] = {1.0, 0.0, 1.0, 0.0, 0.0, 1.0};
+    if (!box.empty()) {
+        const double a00 = box[0], a10 = box[1], a11 = box[2], a20 = box[3], a21 = box[4], a22 = box[5];
+        CHECK_INPUT(a00 > 0.0 && a11 > 0.0 && a22 > 0.0);
+        const double i00 = 1.0 / a00, i11 = 1.0 / a11, i22 = 1.0 / a22;
+        const double lower[6] = {i00, -a10 * i00 * i11, i11, (a10 * a21 - a11 * a20) * i00 * i11 * i22, -a21 * i11 * i22, i22};
+        for (int e = 0; e < 6; ++e) inv[e] = lower[e];
+    }
+    if (B == 0 || C == 0) return at::zeros(shape, band.options());  // no launch
+    c10::DeviceGuard guard(band.device());
+    const at::Tensor bc = band.contiguous(), cc = coeffs.contiguous();
+    at::Tensor out = at::empty(shape, band.options());
+    check_rc(nfft_hip_ewald_dipole_spectral(N, B, C, (int32_t)order, bc.data_ptr(), cc.data_ptr<float>(), inv, out.data_ptr(),
+                                            stream_of(band)));
+    return out;
+}
+
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
 at::TensorOptions current_device_options(at::ScalarType dtype)
 {
@@ -1346,4 +1441,9 @@ TORCH_LIBRARY(torch_nfft, m)
           "-> Tensor", &nfft_ewald_dispersion_virial_near);
     m.def("_nfft_ewald_dispersion_virial_far(Tensor band, Tensor coeffs, Tensor strain_coeffs, float[] box) -> Tensor",
           &nfft_ewald_dispersion_virial_far);
+    // not in the reference: the pair sweep and the spectral step of the Ewald sum of charges and dipoles (nfft_ewald_dipole)
+    m.def("_nfft_ewald_dipole_near(Tensor pos, Tensor xs, Tensor? batch, float[] box, float alpha, float r_cut, int order) "
+          "-> Tensor", &nfft_ewald_dipole_near);
+    m.def("_nfft_ewald_dipole_spectral(Tensor band, Tensor coeffs, float[] box, int order) -> Tensor",
+          &nfft_ewald_dipole_spectral);
 }

@@ -1,5 +1,5 @@
 // The frame of the pair kernels: nearfield.hip (the open grid of the fast summation), ewald_near.hip,
-// ewald_disp.hip and the pair kernels of ewald_virial.hip and ewald_disp_virial.hip (the wrapped grid of the Ewald sums) stand on all of it, nearfield_pgrad.hip on all
+// ewald_disp.hip, ewald_dipole.hip and the pair kernels of ewald_virial.hip and ewald_disp_virial.hip (the wrapped grid of the Ewald sums) stand on all of it, nearfield_pgrad.hip on all
 // but the tile sweep, nearfield_grad.hip on the host dispatch only (section 7d says why).
 // Both point sets come ordered by (point set, cell) with a start table.  A workgroup owns one work item -- up to kNearBlock
 // output points of one cell -- and a lane one output point; a walk hands the contiguous ranges of streamed points of the
@@ -223,6 +223,26 @@ struct EwaldPairWeight {
         w = erfcf(q.alpha * (rr * ir)) * ir;
     }
     __device__ __forceinline__ float mg(const EwaldPairParams &q) const { return (w + q.slope * __expf(q.neg_alpha2 * rr)) * (ir * ir); }
+};
+
+// the pair weights of the dipole sum from rr = r^2 > 0: the Smith functions B_0 = erfc(alpha r) / r and
+// B_l = ((2l - 1) B_(l-1) + (2 alpha^2)^l / (alpha sqrt(pi)) e^(-alpha^2 r^2)) / r^2 up to l = TOP (B_1 is EwaldPairWeight::mg).
+// One erfcf, one __expf, one rsqrtf; every term of the recurrence is positive: no cancellation.
+template <int TOP>
+struct DipolePairWeight {
+    float B[TOP + 1];
+    __device__ __forceinline__ DipolePairWeight(float rr, const EwaldPairParams &q)
+    {
+        const float ir = rsqrtf(rr), ir2 = ir * ir;
+        const float two_alpha2 = -2.f * q.neg_alpha2;
+        float g = q.slope * __expf(q.neg_alpha2 * rr);  // (2 alpha^2)^l / (alpha sqrt(pi)) e^(-alpha^2 r^2) at l = 1
+        B[0] = erfcf(q.alpha * (rr * ir)) * ir;
+#pragma unroll
+        for (int l = 1; l <= TOP; ++l) {
+            B[l] = fmaf((float)(2 * l - 1), B[l - 1], g) * ir2;
+            g *= two_alpha2;
+        }
+    }
 };
 
 // the pair weights of the dispersion sum from rr = r^2 > 0, a2 = alpha^2 r^2:

@@ -265,6 +265,34 @@ def nfft_ewald_dispersion_virial_far(band, coeffs, strain_coeffs, box):
     return _ops._nfft_ewald_dispersion_virial_far(band, coeffs, strain_coeffs, [float(a) for a in box])
 
 
+def nfft_ewald_dipole_near(pos, xs, batch, box, alpha, r_cut, order):
+    """torch_nfft::_nfft_ewald_dipole_near(Tensor pos, Tensor xs, Tensor? batch, float[] box, float alpha, float r_cut,
+    int order) -> Tensor (not in the reference): the near part of the Ewald sum of charges and point dipoles.  ``xs``
+    ``[n, 4, *cols]`` float32 packs ``(q, mu_x, mu_y, mu_z)``; with ``d = d_ij``, ``m = mu_j . d`` and the Smith functions
+    ``B_0 = erfc(alpha r) / r``, ``B_l = ((2l - 1) B_(l-1) + (2 alpha^2)^l / (alpha sqrt(pi)) e^(-alpha^2 r^2)) / r^2`` the result
+    ``[n, 4, *cols]`` (``order = 1``) holds, over the pairs ``0 < r_ij < r_cut`` of i's point set::
+
+        phi_i  = sum_j q_j B_0 + m B_1
+        E_i,a  = sum_j (q_j B_1 + m B_2) d_a - mu_j,a B_1
+
+    and ``[n, 10, *cols]`` (``order = 2``) also ``T_i,ab = sum_j q_j (delta_ab B_1 - d_a d_b B_2) + (mu_j,a d_b + mu_j,b d_a +
+    m delta_ab) B_2 - m d_a d_b B_3`` in the order xx, yy, zz, yz, xz, xy.  An empty ``box`` is the unit torus (``pos`` modulo
+    1); six numbers are the box of ``nfft_ewald_near_box``: ``pos`` FRACTIONAL, ``mu``, ``E`` and ``T`` Cartesian.  One native
+    call (``nfft_hip_ewald_dipole_near`` / ``_near_box``), no atomics: two calls give the same bits."""
+    return _ops._nfft_ewald_dipole_near(pos, xs, batch, [float(a) for a in box], float(alpha), float(r_cut), int(order))
+
+
+def nfft_ewald_dipole_spectral(band, coeffs, box, order):
+    """torch_nfft::_nfft_ewald_dipole_spectral(Tensor band, Tensor coeffs, float[] box, int order) -> Tensor (not in the
+    reference): from ``band`` ``[B, N, N, N, 4, *cols]`` complex64 (``nfft_adjoint`` of the packed sources) and an
+    ``EwaldSplitting``'s ``coeffs`` ``[N, N, N]`` float32 the spectra ``[B, N, N, N, 4 or 10, *cols]`` complex64 whose
+    ``nfft_forward`` is the far part of ``(phi, E)`` and, at ``order = 2``, of the six entries of ``T``: with
+    ``R = b_k (band_q + 2 pi i kappa . band_mu)``, ``kappa = A^-1 k`` (an empty ``box``: ``kappa = k``), the rows are ``R``,
+    ``2 pi i kappa_a R`` and ``4 pi^2 kappa_a kappa_b R``.  One native call (``nfft_hip_ewald_dipole_spectral``; DESIGN.md
+    section 7l), one read and one write."""
+    return _ops._nfft_ewald_dipole_spectral(band, coeffs, [float(a) for a in box], int(order))
+
+
 class _on_device:
     """The coefficient operators create their output on the current device (like the reference, which has no
     device argument); ``device=`` selects it for the duration of the call."""
