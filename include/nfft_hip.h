@@ -556,6 +556,36 @@ int nfft_hip_ewald_dipole_near_box(const nfft_hip_ewald_box_problem *p, const fl
 int nfft_hip_ewald_dipole_spectral(int64_t N, int64_t batch_size, int64_t num_columns, int32_t order, const void *band,
                                    const float *coeffs, const double *box_inverse, void *out, void *stream);
 
+/* ---- Periodic Stokeslet sum, Hasimoto's Ewald sum (no reference counterpart) ----
+ * Source j carries a Cartesian force f_j, xs [points, 3, num_columns].  With d = d_ij, r = |d|, m = d . f_j, the Smith functions
+ * B_0, B_1, B_2 of the dipole sum above and g = (2 alpha / sqrt(pi)) exp(-alpha^2 r^2), the two near entry points give, over the
+ * pairs 0 < r_ij < r_cut of one point set,
+ *     u[i, a]    = sum_j (B_0 - g) f_j,a + B_1 m d_a
+ *     G[i, a, b] = sum_j (2 alpha^2 g - B_1) f_j,a d_b + B_1 (d_a f_j,b + m delta_ab) - B_2 m d_a d_b        (G_ab = d u_a / d x_b)
+ * as out [points, 3, num_columns] for order = 1 and out [points, 12, num_columns] for order = 2, G following row-major in ab
+ * (it is not symmetric; its trace is zero); rows in the caller's order through index.  Problem structs (num_columns counts
+ * the columns of three values; with_field must be 0 or 1 and is otherwise not read), the order of the points, validation,
+ * error codes, determinism and workspace are those of nfft_hip_ewald_near and nfft_hip_ewald_near_box:
+ * nfft_hip_ewald_near_workspace_bytes and nfft_hip_ewald_near_box_workspace_bytes serve these sweeps too.  order must be 1 or
+ * 2 ("Input mismatch").
+ *
+ * nfft_hip_ewald_stokeslet_spectral: band [batch_size, N, N, N, 3, num_columns] complex64 (the adjoint transform of xs, index
+ * k + N/2), coeffs [N, N, N] float32 (c_k = 2 b_k (1 + pi^2 |kappa|^2 / alpha^2)), box_inverse[6] = the lower triangle of A^-1 as
+ * for nfft_hip_ewald_dipole_spectral.  With tau = 2 pi kappa and rho the three rows of band it writes
+ * out [batch_size, N, N, N, 3 or 12, num_columns] complex64,
+ *     U = c_k (rho - tau (tau . rho) / |tau|^2),   out[.., a] = U_a,   out[.., 3 + 3 a + b] = -i tau_b U_a   (order = 2),
+ * the quotient taken as 0 where |tau|^2 = 0, whose forward transform is the far part of (u, G): the signs are those of the
+ * transforms (the adjoint sums exp(+2 pi i k.s), the forward exp(-2 pi i k.s), whose derivative along x_b is -i tau_b).
+ * tau is formed in float32 from the float64 box_inverse.  One pass, no workspace.  Limits as for the dipole sum's. */
+int nfft_hip_ewald_stokeslet_near(const nfft_hip_ewald_problem *p, const float *points, const float *xs, const int32_t *start,
+                                  const int64_t *index, int32_t order, float *out, void *workspace, int64_t workspace_bytes,
+                                  void *stream);
+int nfft_hip_ewald_stokeslet_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xs,
+                                      const int32_t *start, const int64_t *index, int32_t order, float *out, void *workspace,
+                                      int64_t workspace_bytes, void *stream);
+int nfft_hip_ewald_stokeslet_spectral(int64_t N, int64_t batch_size, int64_t num_columns, int32_t order, const void *band,
+                                      const float *coeffs, const double *box_inverse, void *out, void *stream);
+
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.
  *   gaussian_analytic_coeffs      float32:  prod_d sqrt(pi) sigma exp(-sigma^2 pi^2 l_d^2)      (kernel_coeffs.cu:6-30)

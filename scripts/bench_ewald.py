@@ -56,6 +56,13 @@ nfft_ewald_dipole of order 1 and 2 beside nfft_ewald with its field; the near op
 torch composition on the same band; and the dipole pair loops of order 1 and 2 (nfft_hip_ewald_dipole_near on restated
 plumbing) beside the Coulomb pair loop with its field (nfft_hip_ewald_near) on the same sorted points and cells.  The calls
 of a group are timed in turn (a, b, c, a, b, c, ...), median, minimum and maximum of `reps` each.
+
+    python scripts/bench_ewald.py --stokeslet [...]
+
+times the periodic Stokeslet sum in the unit cube on the same points, r_c, alpha and N, in the same way:
+nfft_ewald_stokeslet for u and for (u, G) beside nfft_ewald with its field; the near operator; the spectral kernel beside the
+torch composition on the same band; and the Stokeslet pair loops of order 1 and 2 (nfft_hip_ewald_stokeslet_near on restated
+plumbing) beside the Coulomb pair loop with its field on the same sorted points and cells.
 """
 import argparse
 import ctypes
@@ -557,6 +564,76 @@ def run_dipole(lib, n, args):
                       "spectral_rel_difference": float((got - want).norm() / want.norm())}))
 
 
+def run_stokeslet(lib, n, args):
+    """the periodic Stokeslet sum in the unit cube: the same points, r_c, alpha and N as `run`"""
+    m = 4
+    r_c = min((3.0 * args.neighbours / (4.0 * math.pi * n)) ** (1.0 / 3.0), 1.0 / 3.0)
+    sp = tn.EwaldSplitting.from_tolerance(args.tol, r_c)
+    rng = np.random.default_rng(0)
+    v = (rng.random((n, 3)) - 0.5).astype(np.float32)
+    v[v >= 0.5] = -0.5  # (rounded up to the face: the same point)
+    pos = torch.from_numpy(v).cuda()
+    q = torch.from_numpy(rng.standard_normal(n).astype(np.float32)).cuda()
+    f = torch.from_numpy(rng.standard_normal((n, 3)).astype(np.float32)).cuda()
+    G, N = int(lib.nfft_hip_ewald_near_cells(r_c, 1)), sp.bandwidth
+    wrapped, _ = pairs_tested(v, G)
+    whole = alternating_ms({
+        "coulomb_field": lambda: tn.nfft_ewald(q, pos, splitting=sp, cutoff=m, field=True),
+        "u": lambda: tn.nfft_ewald_stokeslet(f, pos, splitting=sp, cutoff=m),
+        "u_G": lambda: tn.nfft_ewald_stokeslet(f, pos, splitting=sp, cutoff=m, gradient=True),
+        "near_op1": lambda: tn.ops.nfft_ewald_stokeslet_near(pos, f, None, (), sp.alpha, r_c, 1),
+        "near_op2": lambda: tn.ops.nfft_ewald_stokeslet_near(pos, f, None, (), sp.alpha, r_c, 2)}, args.reps)
+    # the spectral step beside the torch composition on the same band
+    band = tn.nfft_adjoint(f, pos, bandwidth=N, cutoff=m)  # [1, N, N, N, 3]
+    tau = 2.0 * math.pi * sp._kappa()
+    t2 = (tau * tau).sum(3)
+    P = torch.eye(3, dtype=torch.float64) - tau.unsqueeze(4) * tau.unsqueeze(3) / torch.where(t2 > 0, t2, torch.ones_like(t2))[..., None, None]
+    P = (sp.stokeslet_coeffs.double().cpu()[..., None, None] * P).to(torch.complex128)  # [N, N, N, 3, 3]
+    table = torch.cat([P, (-1j * P.unsqueeze(4) * tau[..., None, :, None]).reshape(N, N, N, 9, 3)], 3).to(torch.complex64).cuda()
+    coeffs = sp.stokeslet_coeffs
+    spectral = alternating_ms({
+        "kernel": lambda: tn.ops.nfft_ewald_stokeslet_spectral(band, coeffs, (), 2),
+        "torch": lambda: torch.einsum("xyzsr,bxyzr->bxyzs", table, band)}, args.reps)
+    got, want = tn.ops.nfft_ewald_stokeslet_spectral(band, coeffs, (), 2), torch.einsum("xyzsr,bxyzr->bxyzs", table, band)
+    # the pair loops on their own, on the same sorted points and cells: the Coulomb loop with its field, the Stokeslet loops
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    spos, order, start = cell_order(pos, G, 0.5, G)
+    xq = q.index_select(0, order).reshape(n, 1).contiguous()
+    xf = f.index_select(0, order).contiguous()
+    z, e = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+    outs = {1: torch.zeros(n, 3, device="cuda"), 2: torch.zeros(n, 12, device="cuda")}
+    p = _lib.EwaldProblem(cells_per_axis=G, with_field=1, num_points=n, num_columns=1, batch_size=1, alpha=sp.alpha, r_cut=r_c)
+    nbytes = lib.nfft_hip_ewald_near_workspace_bytes(ctypes.byref(p))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+
+    def coulomb_loop():
+        _lib.check(lib.nfft_hip_ewald_near(ctypes.byref(p), spos.data_ptr(), xq.data_ptr(), start.data_ptr(), order.data_ptr(),
+                                           z.data_ptr(), e.data_ptr(), ws.data_ptr(), nbytes, stream))
+
+    def stokeslet_loop(o):
+        _lib.check(lib.nfft_hip_ewald_stokeslet_near(ctypes.byref(p), spos.data_ptr(), xf.data_ptr(), start.data_ptr(),
+                                                     order.data_ptr(), o, outs[o].data_ptr(), ws.data_ptr(), nbytes, stream))
+
+    loops = alternating_ms({"coulomb": coulomb_loop, "order1": lambda: stokeslet_loop(1), "order2": lambda: stokeslet_loop(2)},
+                           args.reps)
+    assert torch.equal(tn.ops.nfft_ewald_stokeslet_near(pos, f, None, (), sp.alpha, r_c, 2), outs[2]), \
+        "the restated plumbing must give the operator's bits"
+    tn.ops.check_status()
+    ms = lambda t: [round(e, 4) for e in t]  # noqa: E731
+    print(json.dumps({"bench": "ewald_stokeslet", "points": n, "neighbours": args.neighbours, "tol": args.tol, "r_cut": round(r_c, 5),
+                      "alpha": round(sp.alpha, 3), "N": N, "m": m, "cells_per_axis": G, "reps": args.reps,
+                      "median_min_max_ms": {"whole": {k: ms(t) for k, t in whole.items()},
+                                            "spectral": {k: ms(t) for k, t in spectral.items()},
+                                            "pair_loop": {k: ms(t) for k, t in loops.items()}},
+                      "pairs_tested": wrapped,
+                      "ps_per_pair": {k: round(t[0] * 1e9 / wrapped, 3) for k, t in loops.items()},
+                      "order1_over_coulomb_field_loop": round(loops["order1"][0] / loops["coulomb"][0], 3),
+                      "order2_over_coulomb_field_loop": round(loops["order2"][0] / loops["coulomb"][0], 3),
+                      "torch_over_spectral_kernel": round(spectral["torch"][0] / spectral["kernel"][0], 2),
+                      "spectral_GBps": round((band.numel() + got.numel()) * 8 / spectral["kernel"][0] * 1e-6, 1),
+                      "spectral_rel_difference": float((got - want).norm() / want.norm())}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, nargs="+", default=[100000, 1000000])
@@ -568,6 +645,7 @@ def main():
     ap.add_argument("--virial", action="store_true", help="add a row for nfft_ewald_virial and its two reductions")
     ap.add_argument("--dispersion", action="store_true", help="time the dispersion sum 1/r^6 (unit cube) instead")
     ap.add_argument("--dipole", action="store_true", help="time the sum of charges and point dipoles (unit cube) instead")
+    ap.add_argument("--stokeslet", action="store_true", help="time the periodic Stokeslet sum (unit cube) instead")
     args = ap.parse_args()
     if args.box is not None and len(args.box) not in (3, 6):
         ap.error("--box takes three or six comma-separated numbers")
@@ -575,9 +653,14 @@ def main():
         ap.error("--dispersion times the unit cube and does not go with --box")
     if args.dipole and (args.box is not None or args.dispersion or args.virial):
         ap.error("--dipole times the unit cube on its own")
+    if args.stokeslet and (args.box is not None or args.dispersion or args.virial or args.dipole):
+        ap.error("--stokeslet times the unit cube on its own")
     torch.cuda.set_device(0)
     lib = _lib.load()
     for n in args.points:
+        if args.stokeslet:
+            run_stokeslet(lib, n, args)
+            continue
         if args.dipole:
             run_dipole(lib, n, args)
             continue

@@ -1,5 +1,5 @@
 // C-ABI entry points of the pair kernels (include/nfft_hip.h): the near field of the fast summation for singular kernels,
-// the near parts of the Ewald sums (1/r, 1/r^6 and dipoles) on the torus and in a box, the virial reductions.  They share only the error plumbing and
+// the near parts of the Ewald sums (1/r, 1/r^6, dipoles and Stokeslets) on the torus and in a box, the virial reductions.  They share only the error plumbing and
 // the workspace conventions (host_util.h) with the transforms of api.hip.
 #include "../../include/nfft_hip.h"
 
@@ -241,7 +241,7 @@ int64_t nfft_hip_ewald_near_workspace_bytes(const nfft_hip_ewald_problem *p)
 }
 
 // the checks of a wrapped pair sweep on the torus, then `launch` (the Coulomb sweep, the dispersion sweep of section 7j or
-// the dipole sweep of section 7l)
+// the dipole sweep of section 7l or the Stokeslet sweep of section 7m)
 typedef int (*ewald_launch)(const nfft_hip_ewald_problem *, const float *, const float *, const int *, const int64_t *, float *,
                             float *, void *, hipStream_t);
 static int ewald_near_call(ewald_launch launch, const nfft_hip_ewald_problem *p, const float *points, const float *xr,
@@ -450,6 +450,51 @@ int nfft_hip_ewald_dipole_near_box(const nfft_hip_ewald_box_problem *p, const fl
                                workspace, workspace_bytes, stream);
 }
 
+// ---- periodic Stokeslet sum: the same problems, checks and workspaces ---------------------------
+// the Stokeslet sweeps of order 1 and 2 as the shared calls launch them (one output: the field pointer is not used)
+static int stokeslet_near_1(const nfft_hip_ewald_problem *p, const float *pos, const float *xs, const int *start,
+                            const int64_t *index, float *out, float *, void *items, hipStream_t s)
+{
+    return launch_ewald_stokeslet_near(p, 1, pos, xs, start, index, out, items, s);
+}
+
+static int stokeslet_near_2(const nfft_hip_ewald_problem *p, const float *pos, const float *xs, const int *start,
+                            const int64_t *index, float *out, float *, void *items, hipStream_t s)
+{
+    return launch_ewald_stokeslet_near(p, 2, pos, xs, start, index, out, items, s);
+}
+
+static int stokeslet_near_box_1(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xs, const int *start,
+                                const int64_t *index, float *out, float *, void *items, hipStream_t s)
+{
+    return launch_ewald_stokeslet_near_box(p, 1, pos, xs, start, index, out, items, s);
+}
+
+static int stokeslet_near_box_2(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xs, const int *start,
+                                const int64_t *index, float *out, float *, void *items, hipStream_t s)
+{
+    return launch_ewald_stokeslet_near_box(p, 2, pos, xs, start, index, out, items, s);
+}
+
+// (out stands for z and for field in the shared checks; the order is checked as for the dipole sweep)
+int nfft_hip_ewald_stokeslet_near(const nfft_hip_ewald_problem *p, const float *points, const float *xs, const int32_t *start,
+                                  const int64_t *index, int32_t order, float *out, void *workspace, int64_t workspace_bytes,
+                                  void *stream)
+{
+    if (int rc = check_dipole_order(order)) return rc;
+    return ewald_near_call(order == 2 ? stokeslet_near_2 : stokeslet_near_1, p, points, xs, start, index, out, out, workspace,
+                           workspace_bytes, stream);
+}
+
+int nfft_hip_ewald_stokeslet_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xs,
+                                      const int32_t *start, const int64_t *index, int32_t order, float *out, void *workspace,
+                                      int64_t workspace_bytes, void *stream)
+{
+    if (int rc = check_dipole_order(order)) return rc;
+    return ewald_near_box_call(order == 2 ? stokeslet_near_box_2 : stokeslet_near_box_1, p, points, xs, start, index, out, out,
+                               workspace, workspace_bytes, stream);
+}
+
 // ---- virial tensor of the Ewald sum -----------------------------------------------------------
 static int validate_virial_far(int64_t N, int64_t batch_size, int64_t num_columns)
 {
@@ -564,6 +609,23 @@ int nfft_hip_ewald_dipole_spectral(int64_t N, int64_t batch_size, int64_t num_co
     if (num_columns == 0) return 0;
     if (!band || !coeffs || !out) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
     return launch_ewald_dipole_spectral(N, batch_size, num_columns, order, band, coeffs, box_inverse, out, (hipStream_t)stream);
+}
+
+// ---- the spectral step of the Stokeslet sum: the checks of the dipole sum's ---------------------
+int nfft_hip_ewald_stokeslet_spectral(int64_t N, int64_t batch_size, int64_t num_columns, int32_t order, const void *band,
+                                      const float *coeffs, const double *box_inverse, void *out, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = check_dipole_order(order)) return rc;
+    if (int rc = validate_virial_far(N, batch_size, num_columns)) return rc;
+    if (N * N * N * num_columns >= (int64_t(1) << 31)) {
+        set_error("Input mismatch: N^3 num_columns < 2^31 is required");
+        return NFFT_HIP_EINVAL;
+    }
+    if (int rc = validate_box_inverse(box_inverse)) return rc;
+    if (num_columns == 0) return 0;
+    if (!band || !coeffs || !out) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    return launch_ewald_stokeslet_spectral(N, batch_size, num_columns, order, band, coeffs, box_inverse, out, (hipStream_t)stream);
 }
 
 // ---- virial tensor of the dispersion Ewald sum: the checks and workspaces of section 7i -------

@@ -1206,23 +1206,38 @@ at::Tensor nfft_ewald_dispersion_virial_far(at::Tensor band, at::Tensor coeffs, 
     });
 }
 
-// ---- Ewald sum of charges and point dipoles (not in the reference) ------------------------------
-// [n, 4 or 10, *cols] float32: the pair sums (phi, E) and, at order 2, the six entries xx, yy, zz, yz, xz, xy of T = grad E of
-// the packed sources xs [n, 4, *cols] = (q, mu) over the pairs within r_cut, with the Smith functions of alpha.  An empty box:
-// the unit torus, pos taken modulo 1; six numbers: the box A of nfft_ewald_near_box, pos FRACTIONAL, mu, E and T Cartesian.
-at::Tensor nfft_ewald_dipole_near(at::Tensor pos, at::Tensor xs, c10::optional<at::Tensor> opt_batch, std::vector<double> box,
-                                  double alpha, double r_cut, int64_t order)
+// ---- Ewald sums of packed sources: charges with point dipoles (section 7l) and Stokeslets (section 7m) ------------------
+// What tells the two apart: the operators' names, the rows of a packed source, the sums per column at order 1 and 2 and the
+// three entry points (their signatures are the same).
+struct PackedSum {
+    const char *near_name, *spectral_name;
+    int64_t rows, sums[2];
+    decltype(&nfft_hip_ewald_dipole_near) near;
+    decltype(&nfft_hip_ewald_dipole_near_box) near_box;
+    decltype(&nfft_hip_ewald_dipole_spectral) spectral;
+};
+
+const PackedSum kDipoleSum = {"_nfft_ewald_dipole_near", "_nfft_ewald_dipole_spectral", 4, {4, 10},
+                              nfft_hip_ewald_dipole_near, nfft_hip_ewald_dipole_near_box, nfft_hip_ewald_dipole_spectral};
+const PackedSum kStokesletSum = {"_nfft_ewald_stokeslet_near", "_nfft_ewald_stokeslet_spectral", 3, {3, 12},
+                                 nfft_hip_ewald_stokeslet_near, nfft_hip_ewald_stokeslet_near_box,
+                                 nfft_hip_ewald_stokeslet_spectral};
+
+// [n, sums, *cols] float32: the pair sums of the packed sources xs [n, rows, *cols] over the pairs within r_cut.  An empty box:
+// the unit torus, pos taken modulo 1; six numbers: the box A of nfft_ewald_near_box, pos FRACTIONAL, vectors Cartesian.
+at::Tensor packed_near(const PackedSum &k, at::Tensor pos, at::Tensor xs, c10::optional<at::Tensor> opt_batch,
+                       std::vector<double> box, double alpha, double r_cut, int64_t order)
 {
-    TORCH_CHECK(xs.is_cuda(), "torch_nfft._nfft_ewald_dipole_near is currently only implemented for GPU tensors");
+    TORCH_CHECK(xs.is_cuda(), "torch_nfft.", k.near_name, " is currently only implemented for GPU tensors");
     const Points p = check_points(pos, opt_batch, "batch");
     CHECK_INPUT(p.dim == 3);
     CHECK_INPUT(xs.scalar_type() == at::kFloat);
     const Coeffs cx = check_spatial(xs, p.n, 2);
-    CHECK_INPUT(xs.size(1) == 4);
+    CHECK_INPUT(xs.size(1) == k.rows);
     CHECK_INPUT(xs.device() == pos.device());
     CHECK_INPUT(box.empty() || box.size() == 6);
     CHECK_INPUT(order == 1 || order == 2);
-    const int64_t sums = order == 2 ? 10 : 4, C = cx.C;
+    const int64_t sums = k.sums[order - 1], C = cx.C;
     const std::vector<int64_t> shape = cx.shape({p.n, sums});
     nfft_hip_ewald_problem qc;
     nfft_hip_ewald_box_problem qb;
@@ -1248,27 +1263,26 @@ at::Tensor nfft_ewald_dipole_near(at::Tensor pos, at::Tensor xs, c10::optional<a
     if (p.n == 0 || C == 0) return at::zeros(shape, xs.options());  // no launch
     c10::DeviceGuard guard(xs.device());
     const CellOrder o = torus_cell_order(p, cells);
-    const at::Tensor xr = real_rows(xs, true, p.n, 4 * C, o.order);
+    const at::Tensor xr = real_rows(xs, true, p.n, k.rows * C, o.order);
     // (zeros: a point whose coordinates are not numbers has no cell and is not written)
     at::Tensor out = at::zeros({p.n, sums * C}, xs.options());
     at::Tensor ws = byte_buffer(ws_bytes, xs);
     if (box.empty())
-        check_rc(nfft_hip_ewald_dipole_near(&qc, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
-                                            o.order.data_ptr<int64_t>(), (int32_t)order, out.data_ptr<float>(), ws.data_ptr(),
-                                            ws_bytes, stream_of(xs)));
+        check_rc(k.near(&qc, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(), o.order.data_ptr<int64_t>(),
+                        (int32_t)order, out.data_ptr<float>(), ws.data_ptr(), ws_bytes, stream_of(xs)));
     else
-        check_rc(nfft_hip_ewald_dipole_near_box(&qb, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
-                                                o.order.data_ptr<int64_t>(), (int32_t)order, out.data_ptr<float>(), ws.data_ptr(),
-                                                ws_bytes, stream_of(xs)));
+        check_rc(k.near_box(&qb, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
+                            o.order.data_ptr<int64_t>(), (int32_t)order, out.data_ptr<float>(), ws.data_ptr(), ws_bytes,
+                            stream_of(xs)));
     return out.reshape(shape);
 }
 
-// [B, N, N, N, 4 or 10, *cols] complex64: the spectra of the far part of (phi, E, T) from band [B, N, N, N, 4, *cols] complex64
-// (nfft_adjoint of the packed sources) and the splitting's coeffs [N, N, N] float32; kappa = A^-1 k is formed in the kernel
-// from box (empty: the unit cube) and the index
-at::Tensor nfft_ewald_dipole_spectral(at::Tensor band, at::Tensor coeffs, std::vector<double> box, int64_t order)
+// [B, N, N, N, sums, *cols] complex64: the spectra of the far part from band [B, N, N, N, rows, *cols] complex64 (nfft_adjoint of
+// the packed sources) and a coefficient grid [N, N, N] float32; kappa = A^-1 k is formed in the kernel from box (empty: the
+// unit cube) and the index
+at::Tensor packed_spectral(const PackedSum &k, at::Tensor band, at::Tensor coeffs, std::vector<double> box, int64_t order)
 {
-    TORCH_CHECK(band.is_cuda(), "torch_nfft._nfft_ewald_dipole_spectral is currently only implemented for GPU tensors");
+    TORCH_CHECK(band.is_cuda(), "torch_nfft.", k.spectral_name, " is currently only implemented for GPU tensors");
     CHECK_INPUT(band.scalar_type() == at::kComplexFloat);
     CHECK_INPUT(coeffs.scalar_type() == at::kFloat);
     CHECK_INPUT(coeffs.device() == band.device());
@@ -1277,9 +1291,9 @@ at::Tensor nfft_ewald_dipole_spectral(at::Tensor band, at::Tensor coeffs, std::v
     CHECK_INPUT(band.dim() >= 5 && coeffs.dim() == 3);
     const int64_t B = band.size(0), N = band.size(1);
     for (int64_t d = 0; d < 3; ++d) CHECK_INPUT(band.size(1 + d) == N && coeffs.size(d) == N);
-    CHECK_INPUT(band.size(4) == 4);
+    CHECK_INPUT(band.size(4) == k.rows);
     int64_t C = 1;
-    std::vector<int64_t> shape{B, N, N, N, order == 2 ? 10 : 4};
+    std::vector<int64_t> shape{B, N, N, N, k.sums[order - 1]};
     for (int64_t d = 5; d < band.dim(); ++d) {
         C *= band.size(d);
         shape.push_back(band.size(d));
@@ -1296,9 +1310,34 @@ at::Tensor nfft_ewald_dipole_spectral(at::Tensor band, at::Tensor coeffs, std::v
     c10::DeviceGuard guard(band.device());
     const at::Tensor bc = band.contiguous(), cc = coeffs.contiguous();
     at::Tensor out = at::empty(shape, band.options());
-    check_rc(nfft_hip_ewald_dipole_spectral(N, B, C, (int32_t)order, bc.data_ptr(), cc.data_ptr<float>(), inv, out.data_ptr(),
-                                            stream_of(band)));
+    check_rc(k.spectral(N, B, C, (int32_t)order, bc.data_ptr(), cc.data_ptr<float>(), inv, out.data_ptr(), stream_of(band)));
     return out;
+}
+
+// the Ewald sum of charges and point dipoles (not in the reference): xs [n, 4, *cols] = (q, mu); the sums
+// are (phi, E) and, at order 2, the six entries xx, yy, zz, yz, xz, xy of T = grad E, with the Smith functions of alpha
+at::Tensor nfft_ewald_dipole_near(at::Tensor pos, at::Tensor xs, c10::optional<at::Tensor> batch, std::vector<double> box,
+                                  double alpha, double r_cut, int64_t order)
+{
+    return packed_near(kDipoleSum, pos, xs, batch, box, alpha, r_cut, order);
+}
+
+at::Tensor nfft_ewald_dipole_spectral(at::Tensor band, at::Tensor coeffs, std::vector<double> box, int64_t order)
+{
+    return packed_spectral(kDipoleSum, band, coeffs, box, order);
+}
+
+// the periodic Stokeslet sum (not in the reference): f [n, 3, *cols] Cartesian forces; the sums are u and,
+// at order 2, the nine entries of G = grad u, row-major (G_ab = d u_a / d x_b)
+at::Tensor nfft_ewald_stokeslet_near(at::Tensor pos, at::Tensor f, c10::optional<at::Tensor> batch, std::vector<double> box,
+                                     double alpha, double r_cut, int64_t order)
+{
+    return packed_near(kStokesletSum, pos, f, batch, box, alpha, r_cut, order);
+}
+
+at::Tensor nfft_ewald_stokeslet_spectral(at::Tensor band, at::Tensor coeffs, std::vector<double> box, int64_t order)
+{
+    return packed_spectral(kStokesletSum, band, coeffs, box, order);
 }
 
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
@@ -1446,4 +1485,9 @@ TORCH_LIBRARY(torch_nfft, m)
           "-> Tensor", &nfft_ewald_dipole_near);
     m.def("_nfft_ewald_dipole_spectral(Tensor band, Tensor coeffs, float[] box, int order) -> Tensor",
           &nfft_ewald_dipole_spectral);
+    // not in the reference: the pair sweep and the spectral step of the periodic Stokeslet sum (nfft_ewald_stokeslet)
+    m.def("_nfft_ewald_stokeslet_near(Tensor pos, Tensor f, Tensor? batch, float[] box, float alpha, float r_cut, int order) "
+          "-> Tensor", &nfft_ewald_stokeslet_near);
+    m.def("_nfft_ewald_stokeslet_spectral(Tensor band, Tensor coeffs, float[] box, int order) -> Tensor",
+          &nfft_ewald_stokeslet_spectral);
 }

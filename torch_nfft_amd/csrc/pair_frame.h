@@ -1,5 +1,5 @@
 // The frame of the pair kernels: nearfield.hip (the open grid of the fast summation), ewald_near.hip,
-// ewald_disp.hip, ewald_dipole.hip and the pair kernels of ewald_virial.hip and ewald_disp_virial.hip (the wrapped grid of the Ewald sums) stand on all of it, nearfield_pgrad.hip on all
+// ewald_disp.hip, ewald_dipole.hip, ewald_stokeslet.hip and the pair kernels of ewald_virial.hip and ewald_disp_virial.hip (the wrapped grid of the Ewald sums) stand on all of it, nearfield_pgrad.hip on all
 // but the tile sweep, nearfield_grad.hip on the host dispatch only (section 7d says why).
 // Both point sets come ordered by (point set, cell) with a start table.  A workgroup owns one work item -- up to kNearBlock
 // output points of one cell -- and a lane one output point; a walk hands the contiguous ranges of streamed points of the
@@ -241,6 +241,31 @@ struct DipolePairWeight {
         for (int l = 1; l <= TOP; ++l) {
             B[l] = fmaf((float)(2 * l - 1), B[l - 1], g) * ir2;
             g *= two_alpha2;
+        }
+    }
+};
+
+// the pair weights of the Stokeslet sum from rr = r^2 > 0, with the Smith functions B_0, B_1, B_2 above and
+// their l = 1 inhomogeneity g = (2 alpha / sqrt(pi)) e^(-alpha^2 r^2): a = B_0 - g weighs f, B1 weighs (d . f) d, and for the
+// velocity gradient (ORDER = 2) c = 2 alpha^2 g - B_1 = (d/dr)(B_0 - g) / r and B2 = (3 B_1 + 2 alpha^2 g) / r^2 = -(d/dr) B_1 / r.
+// One erfcf, one __expf, one rsqrtf.  a changes sign near alpha r = 0.56: the difference loses digits there relative to
+// itself, not relative to the sum, whose other term B_1 m d is of the size of B_0.
+template <int ORDER>
+struct StokesletPairWeight {
+    float a, B1, c, B2;
+    __device__ __forceinline__ StokesletPairWeight(float rr, const EwaldPairParams &q)
+    {
+        const float ir = rsqrtf(rr), ir2 = ir * ir;
+        const float g = q.slope * __expf(q.neg_alpha2 * rr);
+        const float B0 = erfcf(q.alpha * (rr * ir)) * ir;
+        a = B0 - g;
+        B1 = (B0 + g) * ir2;
+        if (ORDER == 2) {
+            const float g2 = -2.f * q.neg_alpha2 * g;  // 2 alpha^2 g
+            c = g2 - B1;
+            B2 = fmaf(3.f, B1, g2) * ir2;
+        } else {
+            c = B2 = 0.f;
         }
     }
 };

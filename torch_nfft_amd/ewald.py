@@ -225,6 +225,18 @@ class EwaldSplitting(_TorusSplitting):
         N = max(2, 2 * math.ceil(alpha * s * longest / math.pi))
         return cls(alpha, r_cut, N, box=A, device=device)
 
+    @property
+    def stokeslet_coeffs(self):
+        """``[N, N, N]`` float32 on the device of ``coeffs``: ``c_k = 2 b_k (1 + pi^2 |kappa|^2 / alpha^2)``, the far field's
+        coefficients of the periodic Stokeslet sum (``stokeslet.py``), from the float64 values on the host; zero at ``k = 0``
+        and on the unpaired planes, as ``b_k`` is (built on first use)"""
+        c = self.__dict__.get("_stokeslet_coeffs")
+        if c is None:
+            kappa = self._kappa()
+            c = 2.0 * self._b64 * (1.0 + (math.pi / self.alpha) ** 2 * (kappa * kappa).sum(3))
+            c = self._stokeslet_coeffs = c.to(torch.float32).to(self.coeffs.device).contiguous()
+        return c
+
     def field_coeffs(self):
         """``[N, N, N, 4]`` complex64: ``b_k`` and, for the three axes, ``(+2 pi i k_a) b_k`` -- the coefficients of
         ``phi`` and of ``E = -grad phi`` as four columns of one forward transform (built on first use).  With a box the

@@ -293,6 +293,33 @@ def nfft_ewald_dipole_spectral(band, coeffs, box, order):
     return _ops._nfft_ewald_dipole_spectral(band, coeffs, [float(a) for a in box], int(order))
 
 
+def nfft_ewald_stokeslet_near(pos, f, batch, box, alpha, r_cut, order):
+    """torch_nfft::_nfft_ewald_stokeslet_near(Tensor pos, Tensor f, Tensor? batch, float[] box, float alpha, float r_cut,
+    int order) -> Tensor (not in the reference): the near part of the periodic Stokeslet sum.  ``f`` ``[n, 3, *cols]`` float32
+    holds Cartesian forces; with ``d = d_ij``, ``m = d . f_j``, the Smith functions ``B_0, B_1, B_2`` of
+    ``nfft_ewald_dipole_near`` and ``g = (2 alpha / sqrt(pi)) e^(-alpha^2 r^2)`` the result ``[n, 3, *cols]`` (``order = 1``) holds,
+    over the pairs ``0 < r_ij < r_cut`` of i's point set::
+
+        u_i,a  = sum_j (B_0 - g) f_j,a + B_1 m d_a
+
+    and ``[n, 12, *cols]`` (``order = 2``) also ``G_i,ab = sum_j (2 alpha^2 g - B_1) f_j,a d_b + B_1 (d_a f_j,b + m delta_ab) -
+    B_2 m d_a d_b = d u_a / d x_b`` as rows ``3 + 3 a + b``.  An empty ``box`` is the unit torus (``pos`` modulo 1); six numbers
+    are the box of ``nfft_ewald_near_box``: ``pos`` FRACTIONAL, ``f``, ``u`` and ``G`` Cartesian.  One native call
+    (``nfft_hip_ewald_stokeslet_near`` / ``_near_box``), no atomics: two calls give the same bits."""
+    return _ops._nfft_ewald_stokeslet_near(pos, f, batch, [float(a) for a in box], float(alpha), float(r_cut), int(order))
+
+
+def nfft_ewald_stokeslet_spectral(band, coeffs, box, order):
+    """torch_nfft::_nfft_ewald_stokeslet_spectral(Tensor band, Tensor coeffs, float[] box, int order) -> Tensor (not in the
+    reference): from ``band`` ``[B, N, N, N, 3, *cols]`` complex64 (``nfft_adjoint`` of the forces) and
+    ``EwaldSplitting.stokeslet_coeffs`` ``[N, N, N]`` float32 the spectra ``[B, N, N, N, 3 or 12, *cols]`` complex64 whose
+    ``nfft_forward`` is the far part of ``u`` and, at ``order = 2``, of the nine entries of ``G``: with ``tau = 2 pi kappa``,
+    ``kappa = A^-1 k`` (an empty ``box``: ``kappa = k``), ``U = c_k (band - tau (tau . band) / |tau|^2)``, the rows are ``U_a`` and
+    ``-i tau_b U_a`` at ``3 + 3 a + b``.  One native call (``nfft_hip_ewald_stokeslet_spectral``), one
+    read and one write."""
+    return _ops._nfft_ewald_stokeslet_spectral(band, coeffs, [float(a) for a in box], int(order))
+
+
 class _on_device:
     """The coefficient operators create their output on the current device (like the reference, which has no
     device argument); ``device=`` selects it for the duration of the call."""
