@@ -586,6 +586,27 @@ int nfft_hip_ewald_stokeslet_near_box(const nfft_hip_ewald_box_problem *p, const
 int nfft_hip_ewald_stokeslet_spectral(int64_t N, int64_t batch_size, int64_t num_columns, int32_t order, const void *band,
                                       const float *coeffs, const double *box_inverse, void *out, void *stream);
 
+/* ---- Periodic Rotne-Prager-Yamakawa sum, Beenakker's Ewald sum (no reference counterpart) ----
+ * Source j is a sphere of the radius `radius` (one per call) with a Cartesian force f_j, xs [points, 3, num_columns].  The
+ * tensor is (1 + (a^2 / 3) lap) S(d) of the Stokeslet S above for r >= 2 a and (4 / (3 a)) ((1 - 9 r / (32 a)) I + 3 d d^T / (32 a r))
+ * for overlapping spheres.  With q = a^2 / 3 and B_l, g as above the two entry points give, over the pairs 0 < r_ij < r_cut of
+ * one point set,
+ *     u[i, a]    = sum_j W1 f_j,a + W2 m d_a
+ *     G[i, a, b] = sum_j D1 f_j,a d_b + D2 m d_a d_b + W2 (m delta_ab + d_a f_j,b)                          (G_ab = d u_a / d x_b)
+ *     W1 = (B_0 - g) + q (2 B_1 + (8 alpha^2 - 4 alpha^4 r^2) g)                    W2 = B_1 + q (4 alpha^4 g - 2 B_2)
+ *     D1 = (2 alpha^2 g - B_1) + q (-2 B_2 + (8 alpha^6 r^2 - 24 alpha^4) g)            D2 = -B_2 + q (2 B_3 - 8 alpha^6 g)
+ * and for r < 2 a these plus the difference of the overlap form and the unscreened tensor.  Coincident points (r = 0) do
+ * not see each other; the sphere's own mobility 4 / (3 a) is the caller's self term.  Output, problem structs, the order of
+ * the points, validation, error codes, determinism and workspace are those of nfft_hip_ewald_stokeslet_near and
+ * nfft_hip_ewald_stokeslet_near_box; in addition radius must be finite and positive with 2 radius <= r_cut ("Input mismatch").
+ * The far part is nfft_hip_ewald_stokeslet_spectral with the coefficients c_k (1 - (a^2 / 3) |tau|^2). */
+int nfft_hip_ewald_rpy_near(const nfft_hip_ewald_problem *p, const float *points, const float *xs, const int32_t *start,
+                            const int64_t *index, int32_t order, double radius, float *out, void *workspace,
+                            int64_t workspace_bytes, void *stream);
+int nfft_hip_ewald_rpy_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xs, const int32_t *start,
+                                const int64_t *index, int32_t order, double radius, float *out, void *workspace,
+                                int64_t workspace_bytes, void *stream);
+
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.
  *   gaussian_analytic_coeffs      float32:  prod_d sqrt(pi) sigma exp(-sigma^2 pi^2 l_d^2)      (kernel_coeffs.cu:6-30)

@@ -63,6 +63,15 @@ times the periodic Stokeslet sum in the unit cube on the 
 nfft_ewald_stokeslet for u and for (u, G) beside nfft_ewald with its field; the near operator; the spectral kernel beside the
 torch composition on the same band; and the Stokeslet pair loops of order 1 and 2 (nfft_hip_ewald_stokeslet_near on restated
 plumbing) beside the Coulomb pair loop with its field on the same sorted points and cells.
+
+    python scripts/bench_ewald.py --rpy [--phi 0.1] [...]
+
+times the periodic Rotne-Prager-Yamakawa sum in the same way on the same points, r_c, alpha and N, for
+spheres of the volume fraction phi, n (4/3) pi a^3 = phi (the points are uniform, not a hard-sphere configuration: the share
+(2 a / r_c)^3 of the pairs inside the cut overlap and take the second branch; that expected share is reported, not counted): nfft_ewald_rpy for
+u and for (u, G) beside nfft_ewald with its field and nfft_ewald_stokeslet; the near operator; and the pair loops of order
+1 and 2 (nfft_hip_ewald_rpy_near on restated plumbing) beside the Stokeslet loops and the Coulomb loop with its field.  The
+far part is the Stokeslet sum's with another table and is not timed again.
 """
 import argparse
 import ctypes
@@ -634,6 +643,73 @@ def run_stokeslet(lib, n, args):
                       "spectral_rel_difference": float((got - want).norm() / want.norm())}))
 
 
+def run_rpy(lib, n, args):
+    """the periodic Rotne-Prager-Yamakawa sum in the unit cube: the same points, r_c, alpha and N as `run`"""
+    m = 4
+    r_c = min((3.0 * args.neighbours / (4.0 * math.pi * n)) ** (1.0 / 3.0), 1.0 / 3.0)
+    a = min((3.0 * args.phi / (4.0 * math.pi * n)) ** (1.0 / 3.0), 0.5 * r_c)
+    sp = tn.EwaldSplitting.from_tolerance(args.tol, r_c)
+    rng = np.random.default_rng(0)
+    v = (rng.random((n, 3)) - 0.5).astype(np.float32)
+    v[v >= 0.5] = -0.5  # (rounded up to the face: the same point)
+    pos = torch.from_numpy(v).cuda()
+    q = torch.from_numpy(rng.standard_normal(n).astype(np.float32)).cuda()
+    f = torch.from_numpy(rng.standard_normal((n, 3)).astype(np.float32)).cuda()
+    G, N = int(lib.nfft_hip_ewald_near_cells(r_c, 1)), sp.bandwidth
+    wrapped, _ = pairs_tested(v, G)
+    tn.rpy_coeffs(sp, a)  # (built once, outside the timing)
+    whole = alternating_ms({
+        "coulomb_field": lambda: tn.nfft_ewald(q, pos, splitting=sp, cutoff=m, field=True),
+        "stokeslet_u": lambda: tn.nfft_ewald_stokeslet(f, pos, splitting=sp, cutoff=m),
+        "u": lambda: tn.nfft_ewald_rpy(f, pos, splitting=sp, radius=a, cutoff=m),
+        "u_G": lambda: tn.nfft_ewald_rpy(f, pos, splitting=sp, radius=a, cutoff=m, gradient=True),
+        "near_op1": lambda: tn.ops.nfft_ewald_rpy_near(pos, f, None, (), sp.alpha, r_c, a, 1),
+        "near_op2": lambda: tn.ops.nfft_ewald_rpy_near(pos, f, None, (), sp.alpha, r_c, a, 2)}, args.reps)
+    # the pair loops on their own, on the same sorted points and cells: the Coulomb loop with its field, the Stokeslet loops, these
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    spos, order, start = cell_order(pos, G, 0.5, G)
+    xq = q.index_select(0, order).reshape(n, 1).contiguous()
+    xf = f.index_select(0, order).contiguous()
+    z, e = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+    outs = {1: torch.zeros(n, 3, device="cuda"), 2: torch.zeros(n, 12, device="cuda")}
+    souts = {1: torch.zeros(n, 3, device="cuda"), 2: torch.zeros(n, 12, device="cuda")}
+    p = _lib.EwaldProblem(cells_per_axis=G, with_field=1, num_points=n, num_columns=1, batch_size=1, alpha=sp.alpha, r_cut=r_c)
+    nbytes = lib.nfft_hip_ewald_near_workspace_bytes(ctypes.byref(p))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+
+    def coulomb_loop():
+        _lib.check(lib.nfft_hip_ewald_near(ctypes.byref(p), spos.data_ptr(), xq.data_ptr(), start.data_ptr(), order.data_ptr(),
+                                           z.data_ptr(), e.data_ptr(), ws.data_ptr(), nbytes, stream))
+
+    def stokeslet_loop(o):
+        _lib.check(lib.nfft_hip_ewald_stokeslet_near(ctypes.byref(p), spos.data_ptr(), xf.data_ptr(), start.data_ptr(),
+                                                     order.data_ptr(), o, souts[o].data_ptr(), ws.data_ptr(), nbytes, stream))
+
+    def rpy_loop(o):
+        _lib.check(lib.nfft_hip_ewald_rpy_near(ctypes.byref(p), spos.data_ptr(), xf.data_ptr(), start.data_ptr(), order.data_ptr(),
+                                               o, a, outs[o].data_ptr(), ws.data_ptr(), nbytes, stream))
+
+    loops = alternating_ms({"coulomb": coulomb_loop, "stokeslet1": lambda: stokeslet_loop(1), "stokeslet2": lambda: stokeslet_loop(2),
+                            "order1": lambda: rpy_loop(1), "order2": lambda: rpy_loop(2)}, args.reps)
+    assert torch.equal(tn.ops.nfft_ewald_rpy_near(pos, f, None, (), sp.alpha, r_c, a, 2), outs[2]), \
+        "the restated plumbing must give the operator's bits"
+    tn.ops.check_status()
+    ms = lambda t: [round(e, 4) for e in t]  # noqa: E731
+    print(json.dumps({"bench": "ewald_rpy", "points": n, "neighbours": args.neighbours, "tol": args.tol, "r_cut": round(r_c, 5),
+                      "radius": round(a, 6), "phi": args.phi, "overlapping_share_of_pairs_in_cut": round((2.0 * a / r_c) ** 3, 5),
+                      "alpha": round(sp.alpha, 3), "N": N, "m": m, "cells_per_axis": G, "reps": args.reps,
+                      "median_min_max_ms": {"whole": {k: ms(t) for k, t in whole.items()},
+                                            "pair_loop": {k: ms(t) for k, t in loops.items()}},
+                      "pairs_tested": wrapped,
+                      "ps_per_pair": {k: round(t[0] * 1e9 / wrapped, 3) for k, t in loops.items()},
+                      "order1_over_coulomb_field_loop": round(loops["order1"][0] / loops["coulomb"][0], 3),
+                      "order2_over_coulomb_field_loop": round(loops["order2"][0] / loops["coulomb"][0], 3),
+                      "order1_over_stokeslet_loop": round(loops["order1"][0] / loops["stokeslet1"][0], 3),
+                      "order2_over_stokeslet_loop": round(loops["order2"][0] / loops["stokeslet2"][0], 3),
+                      "u_over_coulomb_field": round(whole["u"][0] / whole["coulomb_field"][0], 3),
+                      "u_G_over_coulomb_field": round(whole["u_G"][0] / whole["coulomb_field"][0], 3)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, nargs="+", default=[100000, 1000000])
@@ -646,6 +722,8 @@ def main():
     ap.add_argument("--dispersion", action="store_true", help="time the dispersion sum 1/r^6 (unit cube) instead")
     ap.add_argument("--dipole", action="store_true", help="time the sum of charges and point dipoles (unit cube) instead")
     ap.add_argument("--stokeslet", action="store_true", help="time the periodic Stokeslet sum (unit cube) instead")
+    ap.add_argument("--rpy", action="store_true", help="time the periodic Rotne-Prager-Yamakawa sum (unit cube) instead")
+    ap.add_argument("--phi", type=float, default=0.1, help="--rpy: the volume fraction of the spheres, n (4/3) pi a^3")
     args = ap.parse_args()
     if args.box is not None and len(args.box) not in (3, 6):
         ap.error("--box takes three or six comma-separated numbers")
@@ -655,9 +733,14 @@ def main():
         ap.error("--dipole times the unit cube on its own")
     if args.stokeslet and (args.box is not None or args.dispersion or args.virial or args.dipole):
         ap.error("--stokeslet times the unit cube on its own")
+    if args.rpy and (args.box is not None or args.dispersion or args.virial or args.dipole or args.stokeslet):
+        ap.error("--rpy times the unit cube on its own")
     torch.cuda.set_device(0)
     lib = _lib.load()
     for n in args.points:
+        if args.rpy:
+            run_rpy(lib, n, args)
+            continue
         if args.stokeslet:
             run_stokeslet(lib, n, args)
             continue

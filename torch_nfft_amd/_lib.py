@@ -77,6 +77,8 @@ SYMBOLS = (
     "nfft_hip_ewald_stokeslet_near",
     "nfft_hip_ewald_stokeslet_near_box",
     "nfft_hip_ewald_stokeslet_spectral",
+    "nfft_hip_ewald_rpy_near",
+    "nfft_hip_ewald_rpy_near_box",
     "nfft_hip_gaussian_analytic_coeffs",
     "nfft_hip_interpolation_grid",
     "nfft_hip_coeffs_workspace_bytes",
@@ -293,6 +295,10 @@ def load():
     lib.nfft_hip_ewald_stokeslet_near_box.restype = ci
     lib.nfft_hip_ewald_stokeslet_spectral.argtypes = [i64, i64, i64, ctypes.c_int32, vp, vp, ctypes.POINTER(ctypes.c_double), vp, vp]
     lib.nfft_hip_ewald_stokeslet_spectral.restype = ci
+    lib.nfft_hip_ewald_rpy_near.argtypes = [ctypes.POINTER(EwaldProblem), vp, vp, vp, vp, ctypes.c_int32, ctypes.c_double, vp, vp, i64, vp]
+    lib.nfft_hip_ewald_rpy_near.restype = ci
+    lib.nfft_hip_ewald_rpy_near_box.argtypes = [ctypes.POINTER(EwaldBoxProblem), vp, vp, vp, vp, ctypes.c_int32, ctypes.c_double, vp, vp, i64, vp]
+    lib.nfft_hip_ewald_rpy_near_box.restype = ci
     lib.nfft_hip_gaussian_analytic_coeffs.argtypes = [ctypes.c_double, i64, ctypes.c_int32, vp, vp]
     lib.nfft_hip_gaussian_analytic_coeffs.restype = ci
     lib.nfft_hip_interpolation_grid.argtypes = [i64, ctypes.c_int32, ci, vp, vp]

@@ -240,6 +240,21 @@ int64_t nfft_hip_ewald_near_workspace_bytes(const nfft_hip_ewald_problem *p)
     return ewald_near_need(p);
 }
 
+// the checks of a wrapped pair sweep on the torus, in their order; *ws: the aligned workspace, or null where there is nothing to launch
+static int ewald_near_checks(const nfft_hip_ewald_problem *p, const float *points, const float *xr, const int32_t *start,
+                             const int64_t *index, float *z, float *field, void *workspace, int64_t workspace_bytes, char **ws)
+{
+    *ws = nullptr;
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_ewald(p)) return rc;
+    if (p->num_points == 0 || p->num_columns == 0) return 0;
+    if (!z) { set_error("Input mismatch: z is null"); return NFFT_HIP_EINVAL; }
+    if (p->with_field && !field) { set_error("Input mismatch: field is null"); return NFFT_HIP_EINVAL; }
+    if (!points || !xr || !start || !index) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    *ws = workspace_base(workspace, workspace_bytes, ewald_near_need(p));
+    return *ws ? 0 : NFFT_HIP_EWORKSPACE;
+}
+
 // the checks of a wrapped pair sweep on the torus, then `launch` (the Coulomb sweep, the dispersion sweep of section 7j or
 // the dipole sweep of section 7l or the Stokeslet sweep of section 7m)
 typedef int (*ewald_launch)(const nfft_hip_ewald_problem *, const float *, const float *, const int *, const int64_t *, float *,
@@ -248,14 +263,9 @@ static int ewald_near_call(ewald_launch launch, const nfft_hip_ewald_problem *p,
                            const int32_t *start, const int64_t *index, float *z, float *field, void *workspace,
                            int64_t workspace_bytes, void *stream)
 {
-    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
-    if (int rc = validate_ewald(p)) return rc;
-    if (p->num_points == 0 || p->num_columns == 0) return 0;
-    if (!z) { set_error("Input mismatch: z is null"); return NFFT_HIP_EINVAL; }
-    if (p->with_field && !field) { set_error("Input mismatch: field is null"); return NFFT_HIP_EINVAL; }
-    if (!points || !xr || !start || !index) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    char *ws = workspace_base(workspace, workspace_bytes, ewald_near_need(p));
-    if (!ws) return NFFT_HIP_EWORKSPACE;
+    char *ws;
+    if (int rc = ewald_near_checks(p, points, xr, start, index, z, field, workspace, workspace_bytes, &ws)) return rc;
+    if (!ws) return 0;
     return launch(p, points, xr, start, index, z, field, ws, (hipStream_t)stream);
 }
 
@@ -367,20 +377,31 @@ int64_t nfft_hip_ewald_near_box_workspace_bytes(const nfft_hip_ewald_box_problem
     return ewald_box_need(p);
 }
 
-typedef int (*ewald_box_launch)(const nfft_hip_ewald_box_problem *, const float *, const float *, const int *, const int64_t *,
-                                float *, float *, void *, hipStream_t);
-static int ewald_near_box_call(ewald_box_launch launch, const nfft_hip_ewald_box_problem *p, const float *points,
-                               const float *xr, const int32_t *start, const int64_t *index, float *z, float *field,
-                               void *workspace, int64_t workspace_bytes, void *stream)
+// (as ewald_near_checks)
+static int ewald_near_box_checks(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr, const int32_t *start,
+                                 const int64_t *index, float *z, float *field, void *workspace, int64_t workspace_bytes,
+                                 char **ws)
 {
+    *ws = nullptr;
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate_ewald_box(p)) return rc;
     if (p->num_points == 0 || p->num_columns == 0) return 0;
     if (!z) { set_error("Input mismatch: z is null"); return NFFT_HIP_EINVAL; }
     if (p->with_field && !field) { set_error("Input mismatch: field is null"); return NFFT_HIP_EINVAL; }
     if (!points || !xr || !start || !index) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    char *ws = workspace_base(workspace, workspace_bytes, ewald_box_need(p));
-    if (!ws) return NFFT_HIP_EWORKSPACE;
+    *ws = workspace_base(workspace, workspace_bytes, ewald_box_need(p));
+    return *ws ? 0 : NFFT_HIP_EWORKSPACE;
+}
+
+typedef int (*ewald_box_launch)(const nfft_hip_ewald_box_problem *, const float *, const float *, const int *, const int64_t *,
+                                float *, float *, void *, hipStream_t);
+static int ewald_near_box_call(ewald_box_launch launch, const nfft_hip_ewald_box_problem *p, const float *points,
+                               const float *xr, const int32_t *start, const int64_t *index, float *z, float *field,
+                               void *workspace, int64_t workspace_bytes, void *stream)
+{
+    char *ws;
+    if (int rc = ewald_near_box_checks(p, points, xr, start, index, z, field, workspace, workspace_bytes, &ws)) return rc;
+    if (!ws) return 0;
     return launch(p, points, xr, start, index, z, field, ws, (hipStream_t)stream);
 }
 
@@ -493,6 +514,41 @@ int nfft_hip_ewald_stokeslet_near_box(const nfft_hip_ewald_box_problem *p, const
     if (int rc = check_dipole_order(order)) return rc;
     return ewald_near_box_call(order == 2 ? stokeslet_near_box_2 : stokeslet_near_box_1, p, points, xs, start, index, out, out,
                                workspace, workspace_bytes, stream);
+}
+
+// ---- periodic Rotne-Prager-Yamakawa sum: the same problems, checks and workspaces ---------------
+// the sphere radius: finite, positive, and two spheres in contact inside the pair sum's reach (the overlap branch r < 2 a
+// belongs to the pair sum alone)
+static int check_rpy_radius(double radius, const double *r_cut)
+{
+    if (!(radius > 0.0) || !(radius < 1e300)) { set_error("Input mismatch: radius must be positive and finite"); return NFFT_HIP_EINVAL; }
+    if (r_cut && 2.0 * radius > *r_cut) { set_error("Input mismatch: 2 radius <= r_cut is required"); return NFFT_HIP_EINVAL; }
+    return 0;
+}
+
+// (out stands for z and for field in the shared checks; the order is checked as for the dipole sweep)
+int nfft_hip_ewald_rpy_near(const nfft_hip_ewald_problem *p, const float *points, const float *xs, const int32_t *start,
+                            const int64_t *index, int32_t order, double radius, float *out, void *workspace,
+                            int64_t workspace_bytes, void *stream)
+{
+    if (int rc = check_dipole_order(order)) return rc;
+    if (int rc = check_rpy_radius(radius, p ? &p->r_cut : nullptr)) return rc;
+    char *ws;
+    if (int rc = ewald_near_checks(p, points, xs, start, index, out, out, workspace, workspace_bytes, &ws)) return rc;
+    if (!ws) return 0;
+    return launch_ewald_rpy_near(p, order, radius, points, xs, start, index, out, ws, (hipStream_t)stream);
+}
+
+int nfft_hip_ewald_rpy_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xs, const int32_t *start,
+                                const int64_t *index, int32_t order, double radius, float *out, void *workspace,
+                                int64_t workspace_bytes, void *stream)
+{
+    if (int rc = check_dipole_order(order)) return rc;
+    if (int rc = check_rpy_radius(radius, p ? &p->r_cut : nullptr)) return rc;
+    char *ws;
+    if (int rc = ewald_near_box_checks(p, points, xs, start, index, out, out, workspace, workspace_bytes, &ws)) return rc;
+    if (!ws) return 0;
+    return launch_ewald_rpy_near_box(p, order, radius, points, xs, start, index, out, ws, (hipStream_t)stream);
 }
 
 // ---- virial tensor of the Ewald sum -----------------------------------------------------------

@@ -1206,29 +1206,27 @@ at::Tensor nfft_ewald_dispersion_virial_far(at::Tensor band, at::Tensor coeffs, 
     });
 }
 
-// ---- Ewald sums of packed sources: charges with point dipoles (section 7l) and Stokeslets (section 7m) ------------------
-// What tells the two apart: the operators' names, the rows of a packed source, the sums per column at order 1 and 2 and the
-// three entry points (their signatures are the same).
+// ---- Ewald sums of packed sources: charges with point dipoles (section 7l), Stokeslets (section 7m), spheres (section 7n) --
+// What tells them apart: the stem of the operators' names, the rows of a packed source, the sums per column at order 1 and 2
+// and the entry points, which the operators pass beside it (the near ones share a signature and so do the spectral ones; the
+// sum over spheres has a radius more and binds it in a closure).
 struct PackedSum {
-    const char *near_name, *spectral_name;
+    const char *stem;  // the operators are stem + "_near" and stem + "_spectral"
     int64_t rows, sums[2];
-    decltype(&nfft_hip_ewald_dipole_near) near;
-    decltype(&nfft_hip_ewald_dipole_near_box) near_box;
-    decltype(&nfft_hip_ewald_dipole_spectral) spectral;
 };
 
-const PackedSum kDipoleSum = {"_nfft_ewald_dipole_near", "_nfft_ewald_dipole_spectral", 4, {4, 10},
-                              nfft_hip_ewald_dipole_near, nfft_hip_ewald_dipole_near_box, nfft_hip_ewald_dipole_spectral};
-const PackedSum kStokesletSum = {"_nfft_ewald_stokeslet_near", "_nfft_ewald_stokeslet_spectral", 3, {3, 12},
-                                 nfft_hip_ewald_stokeslet_near, nfft_hip_ewald_stokeslet_near_box,
-                                 nfft_hip_ewald_stokeslet_spectral};
+const PackedSum kDipoleSum = {"_nfft_ewald_dipole", 4, {4, 10}};
+const PackedSum kStokesletSum = {"_nfft_ewald_stokeslet", 3, {3, 12}};
+const PackedSum kRpySum = {"_nfft_ewald_rpy", 3, {3, 12}};
 
 // [n, sums, *cols] float32: the pair sums of the packed sources xs [n, rows, *cols] over the pairs within r_cut.  An empty box:
 // the unit torus, pos taken modulo 1; six numbers: the box A of nfft_ewald_near_box, pos FRACTIONAL, vectors Cartesian.
-at::Tensor packed_near(const PackedSum &k, at::Tensor pos, at::Tensor xs, c10::optional<at::Tensor> opt_batch,
-                       std::vector<double> box, double alpha, double r_cut, int64_t order)
+// near and near_box: the two entry points, called with the arguments of nfft_hip_ewald_dipole_near / _near_box.
+template <typename Near, typename NearBox>
+at::Tensor packed_near(const PackedSum &k, Near near, NearBox near_box, at::Tensor pos, at::Tensor xs,
+                       c10::optional<at::Tensor> opt_batch, std::vector<double> box, double alpha, double r_cut, int64_t order)
 {
-    TORCH_CHECK(xs.is_cuda(), "torch_nfft.", k.near_name, " is currently only implemented for GPU tensors");
+    TORCH_CHECK(xs.is_cuda(), "torch_nfft.", k.stem, "_near is currently only implemented for GPU tensors");
     const Points p = check_points(pos, opt_batch, "batch");
     CHECK_INPUT(p.dim == 3);
     CHECK_INPUT(xs.scalar_type() == at::kFloat);
@@ -1268,21 +1266,22 @@ at::Tensor packed_near(const PackedSum &k, at::Tensor pos, at::Tensor xs, c10::o
     at::Tensor out = at::zeros({p.n, sums * C}, xs.options());
     at::Tensor ws = byte_buffer(ws_bytes, xs);
     if (box.empty())
-        check_rc(k.near(&qc, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(), o.order.data_ptr<int64_t>(),
-                        (int32_t)order, out.data_ptr<float>(), ws.data_ptr(), ws_bytes, stream_of(xs)));
+        check_rc(near(&qc, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(), o.order.data_ptr<int64_t>(),
+                      (int32_t)order, out.data_ptr<float>(), ws.data_ptr(), ws_bytes, stream_of(xs)));
     else
-        check_rc(k.near_box(&qb, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
-                            o.order.data_ptr<int64_t>(), (int32_t)order, out.data_ptr<float>(), ws.data_ptr(), ws_bytes,
-                            stream_of(xs)));
+        check_rc(near_box(&qb, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
+                          o.order.data_ptr<int64_t>(), (int32_t)order, out.data_ptr<float>(), ws.data_ptr(), ws_bytes,
+                          stream_of(xs)));
     return out.reshape(shape);
 }
 
 // [B, N, N, N, sums, *cols] complex64: the spectra of the far part from band [B, N, N, N, rows, *cols] complex64 (nfft_adjoint of
 // the packed sources) and a coefficient grid [N, N, N] float32; kappa = A^-1 k is formed in the kernel from box (empty: the
-// unit cube) and the index
-at::Tensor packed_spectral(const PackedSum &k, at::Tensor band, at::Tensor coeffs, std::vector<double> box, int64_t order)
+// unit cube) and the index; spectral: the entry point
+at::Tensor packed_spectral(const PackedSum &k, decltype(&nfft_hip_ewald_dipole_spectral) spectral, at::Tensor band,
+                           at::Tensor coeffs, std::vector<double> box, int64_t order)
 {
-    TORCH_CHECK(band.is_cuda(), "torch_nfft.", k.spectral_name, " is currently only implemented for GPU tensors");
+    TORCH_CHECK(band.is_cuda(), "torch_nfft.", k.stem, "_spectral is currently only implemented for GPU tensors");
     CHECK_INPUT(band.scalar_type() == at::kComplexFloat);
     CHECK_INPUT(coeffs.scalar_type() == at::kFloat);
     CHECK_INPUT(coeffs.device() == band.device());
@@ -1310,7 +1309,7 @@ at::Tensor packed_spectral(const PackedSum &k, at::Tensor band, at::Tensor coeff
     c10::DeviceGuard guard(band.device());
     const at::Tensor bc = band.contiguous(), cc = coeffs.contiguous();
     at::Tensor out = at::empty(shape, band.options());
-    check_rc(k.spectral(N, B, C, (int32_t)order, bc.data_ptr(), cc.data_ptr<float>(), inv, out.data_ptr(), stream_of(band)));
+    check_rc(spectral(N, B, C, (int32_t)order, bc.data_ptr(), cc.data_ptr<float>(), inv, out.data_ptr(), stream_of(band)));
     return out;
 }
 
@@ -1319,12 +1318,13 @@ at::Tensor packed_spectral(const PackedSum &k, at::Tensor band, at::Tensor coeff
 at::Tensor nfft_ewald_dipole_near(at::Tensor pos, at::Tensor xs, c10::optional<at::Tensor> batch, std::vector<double> box,
                                   double alpha, double r_cut, int64_t order)
 {
-    return packed_near(kDipoleSum, pos, xs, batch, box, alpha, r_cut, order);
+    return packed_near(kDipoleSum, nfft_hip_ewald_dipole_near, nfft_hip_ewald_dipole_near_box, pos, xs, batch, box, alpha, r_cut,
+                       order);
 }
 
 at::Tensor nfft_ewald_dipole_spectral(at::Tensor band, at::Tensor coeffs, std::vector<double> box, int64_t order)
 {
-    return packed_spectral(kDipoleSum, band, coeffs, box, order);
+    return packed_spectral(kDipoleSum, nfft_hip_ewald_dipole_spectral, band, coeffs, box, order);
 }
 
 // the periodic Stokeslet sum (not in the reference): f [n, 3, *cols] Cartesian forces; the sums are u and,
@@ -1332,12 +1332,29 @@ at::Tensor nfft_ewald_dipole_spectral(at::Tensor band, at::Tensor coeffs, std::v
 at::Tensor nfft_ewald_stokeslet_near(at::Tensor pos, at::Tensor f, c10::optional<at::Tensor> batch, std::vector<double> box,
                                      double alpha, double r_cut, int64_t order)
 {
-    return packed_near(kStokesletSum, pos, f, batch, box, alpha, r_cut, order);
+    return packed_near(kStokesletSum, nfft_hip_ewald_stokeslet_near, nfft_hip_ewald_stokeslet_near_box, pos, f, batch, box, alpha,
+                       r_cut, order);
 }
 
 at::Tensor nfft_ewald_stokeslet_spectral(at::Tensor band, at::Tensor coeffs, std::vector<double> box, int64_t order)
 {
-    return packed_spectral(kStokesletSum, band, coeffs, box, order);
+    return packed_spectral(kStokesletSum, nfft_hip_ewald_stokeslet_spectral, band, coeffs, box, order);
+}
+
+// the periodic Rotne-Prager-Yamakawa sum (not in the reference): f [n, 3, *cols] Cartesian forces on spheres
+// of one radius; the sums are those of the Stokeslet sweep.  The far part is nfft_ewald_stokeslet_spectral with another table.
+at::Tensor nfft_ewald_rpy_near(at::Tensor pos, at::Tensor f, c10::optional<at::Tensor> batch, std::vector<double> box, double alpha,
+                               double r_cut, double radius, int64_t order)
+{
+    const auto near = [radius](const nfft_hip_ewald_problem *p, const float *points, const float *xs, const int32_t *start,
+                               const int64_t *index, int32_t o, float *out, void *ws, int64_t ws_bytes, void *stream) {
+        return nfft_hip_ewald_rpy_near(p, points, xs, start, index, o, radius, out, ws, ws_bytes, stream);
+    };
+    const auto near_box = [radius](const nfft_hip_ewald_box_problem *p, const float *points, const float *xs, const int32_t *start,
+                                   const int64_t *index, int32_t o, float *out, void *ws, int64_t ws_bytes, void *stream) {
+        return nfft_hip_ewald_rpy_near_box(p, points, xs, start, index, o, radius, out, ws, ws_bytes, stream);
+    };
+    return packed_near(kRpySum, near, near_box, pos, f, batch, box, alpha, r_cut, order);
 }
 
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
@@ -1490,4 +1507,7 @@ TORCH_LIBRARY(torch_nfft, m)
           "-> Tensor", &nfft_ewald_stokeslet_near);
     m.def("_nfft_ewald_stokeslet_spectral(Tensor band, Tensor coeffs, float[] box, int order) -> Tensor",
           &nfft_ewald_stokeslet_spectral);
+    // not in the reference: the pair sweep of the periodic Rotne-Prager-Yamakawa sum (nfft_ewald_rpy)
+    m.def("_nfft_ewald_rpy_near(Tensor pos, Tensor f, Tensor? batch, float[] box, float alpha, float r_cut, float radius, "
+          "int order) -> Tensor", &nfft_ewald_rpy_near);
 }

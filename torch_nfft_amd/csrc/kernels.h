@@ -209,6 +209,12 @@ int launch_ewald_stokeslet_near_box(const nfft_hip_ewald_box_problem *p, int ord
                                     const int *start, const int64_t *index, float *out, void *items, hipStream_t stream);
 int launch_ewald_stokeslet_spectral(int64_t N, int64_t batch_size, int64_t num_columns, int order, const void *band,
                                     const float *coeffs, const double *box_inverse, void *out, hipStream_t stream);
+// ewald_rpy.hip (the periodic Rotne-Prager-Yamakawa sum): the wrapped pair sum of u and, at order 2, of
+// G = grad u for spheres of one radius, arguments as nfft_hip_ewald_rpy_near / _near_box, `items` as launch_ewald_stokeslet_near
+int launch_ewald_rpy_near(const nfft_hip_ewald_problem *p, int order, double radius, const float *pos, const float *xs,
+                          const int *start, const int64_t *index, float *out, void *items, hipStream_t stream);
+int launch_ewald_rpy_near_box(const nfft_hip_ewald_box_problem *p, int order, double radius, const float *pos, const float *xs,
+                              const int *start, const int64_t *index, float *out, void *items, hipStream_t stream);
 // ewald_virial.hip (the virial tensor of the Ewald sum): the pair reduction, arguments as
 // nfft_hip_ewald_virial_near, `workspace`: ewald_virial_near_workspace(p) bytes, 256-byte aligned (the work items, then one
 // partial per item slot); and the spectral reduction, arguments as nfft_hip_ewald_virial_far, `workspace`:

@@ -320,6 +320,24 @@ def nfft_ewald_stokeslet_spectral(band, coeffs, box, order):
     return _ops._nfft_ewald_stokeslet_spectral(band, coeffs, [float(a) for a in box], int(order))
 
 
+def nfft_ewald_rpy_near(pos, f, batch, box, alpha, r_cut, radius, order):
+    """torch_nfft::_nfft_ewald_rpy_near(Tensor pos, Tensor f, Tensor? batch, float[] box, float alpha, float r_cut, float radius,
+    int order) -> Tensor (not in the reference): the near part of the periodic Rotne-Prager-Yamakawa sum for spheres of the
+    radius ``a = radius``.  Arguments, shapes and rows are those of ``nfft_ewald_stokeslet_near``; with ``q = a^2 / 3`` and
+    ``B_3 = (5 B_2 + 4 alpha^4 g) / r^2`` the sums over the pairs ``0 < r_ij < r_cut`` are::
+
+        u_i,a  = sum_j W1 f_j,a + W2 m d_a
+        G_i,ab = sum_j D1 f_j,a d_b + D2 m d_a d_b + W2 (m delta_ab + d_a f_j,b)
+        W1 = (B_0 - g) + q (2 B_1 + (8 alpha^2 - 4 alpha^4 r^2) g)             W2 = B_1 + q (4 alpha^4 g - 2 B_2)
+        D1 = (2 alpha^2 g - B_1) + q (-2 B_2 + (8 alpha^6 r^2 - 24 alpha^4) g)     D2 = -B_2 + q (2 B_3 - 8 alpha^6 g)
+
+    and for overlapping spheres, ``r < 2 a``, these plus the difference of the overlap form ``(4 / (3 a)) ((1 - 9 r / (32 a)) I +
+    3 d d^T / (32 a r))`` and the unscreened tensor.  ``radius`` must be positive with ``2 radius <= r_cut`` ("Input mismatch").
+    Coincident points do not see each other.  One native call (``nfft_hip_ewald_rpy_near`` / ``_near_box``; DESIGN.md section
+    7n), no atomics: two calls give the same bits."""
+    return _ops._nfft_ewald_rpy_near(pos, f, batch, [float(a) for a in box], float(alpha), float(r_cut), float(radius), int(order))
+
+
 class _on_device:
     """The coefficient operators create their output on the current device (like the reference, which has no
     device argument); ``device=`` selects it for the duration of the call."""

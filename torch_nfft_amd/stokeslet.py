@@ -51,6 +51,24 @@ def _matrix(nine):
     return nine.reshape((nine.size(0), 3, 3) + tuple(nine.shape[2:]))
 
 
+def _symmetric_backward(evaluate, f, g, splitting, need_f, need_pos):
+    """``(df, dpos)`` of ``sum g . u[f]`` for a real symmetric operator ``evaluate(forces, order) -> [n, 3 or 12, *cols]``: see
+    ``NfftEwaldStokesletFunction``"""
+    g = g.contiguous()
+    df = dpos = None
+    if need_pos:
+        out = evaluate(torch.stack([f, g], 2), 2)  # [n, 12, 2, *cols]
+        df = out[:, :3, 1]
+        Gf, Gg = _matrix(out[:, 3:, 0]), _matrix(out[:, 3:, 1])  # [n, 3 (a), 3 (b), *cols]
+        w = (g.unsqueeze(2) * Gf + f.unsqueeze(2) * Gg).sum(1)  # [n, 3 (b), *cols]
+        dpos = w.reshape(w.size(0), 3, math.prod(w.shape[2:])).sum(2)
+        if splitting.box is not None:
+            dpos = dpos @ splitting._matrices(dpos.device)[0].t()
+    elif need_f:
+        df = evaluate(g, 1)
+    return df if need_f else None, dpos
+
+
 class NfftEwaldStokesletFunction(torch.autograd.Function):
     """``(u, G)`` of ``nfft_ewald_stokeslet`` (``G`` empty without ``gradient``).  The operator ``f -> u`` is real symmetric, so
     for ``g = dL/du`` the gradient in the forces is that operator applied to ``g``, ``df = u[g]``, and the gradient in the
@@ -74,27 +92,16 @@ class NfftEwaldStokesletFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g, _):
         f, pos, batch = ctx.saved_tensors
-        need_f, need_pos = ctx.needs_input_grad[:2]
-        g = g.contiguous()
-        df = dpos = None
-        if need_pos:
-            out = _stokeslet(torch.stack([f, g], 2), pos, batch, ctx.splitting, ctx.cutoff, 2)  # [n, 12, 2, *cols]
-            df = out[:, :3, 1]
-            Gf, Gg = _matrix(out[:, 3:, 0]), _matrix(out[:, 3:, 1])  # [n, 3 (a), 3 (b), *cols]
-            w = (g.unsqueeze(2) * Gf + f.unsqueeze(2) * Gg).sum(1)  # [n, 3 (b), *cols]
-            dpos = w.reshape(w.size(0), 3, math.prod(w.shape[2:])).sum(2)
-            if ctx.splitting.box is not None:
-                dpos = dpos @ ctx.splitting._matrices(dpos.device)[0].t()
-        elif need_f:
-            df = _stokeslet(g, pos, batch, ctx.splitting, ctx.cutoff, 1)
-        return df if need_f else None, dpos, None, None, None, None
+        df, dpos = _symmetric_backward(lambda x, order: _stokeslet(x, pos, batch, ctx.splitting, ctx.cutoff, order), f, g,
+                                       ctx.splitting, *ctx.needs_input_grad[:2])
+        return df, dpos, None, None, None, None
 
 
-def _check(what, f, pos, batch, splitting):
+def _check(what, f, pos, batch, splitting, name="Stokeslet"):
     if not isinstance(splitting, EwaldSplitting):
         raise TypeError("%s: splitting must be an EwaldSplitting" % what)
     if pos.dim() != 2 or pos.size(1) != 3:
-        raise ValueError("%s: the periodic Stokeslet sum is three-dimensional, pos must be [n, 3]" % what)
+        raise ValueError("%s: the periodic %s sum is three-dimensional, pos must be [n, 3]" % (what, name))
     if f.is_complex():
         raise ValueError("%s: f must be real (float32), not complex" % what)
     if f.dtype != torch.float32:
