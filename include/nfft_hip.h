@@ -607,6 +607,54 @@ int nfft_hip_ewald_rpy_near_box(const nfft_hip_ewald_box_problem *p, const float
                                 const int64_t *index, int32_t order, double radius, float *out, void *workspace,
                                 int64_t workspace_bytes, void *stream);
 
+/* ---- Bonded-pair exclusions of the Coulomb and dispersion Ewald sums (no reference counterpart) ----
+ * What a list of unordered pairs {i, j} of one point set takes back out of nfft_hip_ewald_near (kind 0) or
+ * nfft_hip_ewald_dispersion_near (kind 1) plus their far fields.  The list is symmetric and sorted, in CSR form over the
+ * points IN THE CALLER'S ORDER (no cell order, no index array):
+ *   points    [n, 3] float32, reduced to [-1/2, 1/2)^3 exactly as for the sweeps (fractional for the box entry point)
+ *   xr        [n, Cr] float32 real columns
+ *   row_start int32 [n + 1], col int32 [num_entries], weight float32 [num_entries] = 1 - scale of the pair
+ *     z[i, c]        = sum_{k in row i} weight[k] K0(r) xr[col[k], c]           K0 = 1 / r (kind 0), 1 / r^6 (kind 1)
+ *     field[i, a, c] = sum_{k in row i} weight[k] K1(r) d[a] xr[col[k], c]      K1 = 1 / r^3,        6 / r^8
+ * with d the minimum image of points_i - points_col[k], formed by the very routine of the sweeps (the same bits), r = |d|.
+ * An entry at r = 0 gives K0 = 2 alpha / sqrt(pi) (kind 0) or alpha^6 / 6 (kind 1), the limit of the smooth part, and no
+ * field.  The caller SUBTRACTS z and field from the sums.  field [n, 3, Cr] is written with with_field = 1 only.  Entries
+ * whose column lies outside [0, n) are skipped.  No atomics, a row is added in its order: two calls give the same bits.
+ * No workspace.  Validation ("Input mismatch...") before any device access: null pointers, negative counts,
+ * num_points and num_entries < 2^31, kind 0 or 1, with_field 0 or 1, alpha finite and positive, batch_size >= 1, and for the
+ * box entry points a finite box with a positive diagonal (nfft_hip_ewald_excl does not read box).
+ *
+ * nfft_hip_ewald_excl_virial: the listed pairs' share of the energy and the virial of nfft_hip_ewald_virial_near /
+ * nfft_hip_ewald_dispersion_virial_near, each pair once, in their order (energy, xx, yy, zz, yz, xz, xy), float64
+ * [batch_size, 7, Cr]:
+ *     out[b, 0, c] = sum_{pairs of set b} weight K0(r) xr[i, c] xr[j, c]
+ *     out[b, e, c] = sum_{pairs of set b} weight K1(r) d[a] d[b] xr[i, c] xr[j, c]          (r = 0: the energy only)
+ * in the box `box` (the unit cube is 1, 0, 1, 0, 0, 1).  set_start int32 [batch_size + 1]: the first point of every point
+ * set (the points are sorted by point set); null with batch_size = 1.  Two levels in float64 without atomics, as
+ * nfft_hip_ewald_virial_near; num_columns < 2^21 and batch_size * num_columns < 2^21 are required.  With no points or no
+ * entries the output is set to zero; with no columns nothing is done. */
+#define NFFT_HIP_EXCL_COULOMB 0
+#define NFFT_HIP_EXCL_DISPERSION 1
+typedef struct nfft_hip_ewald_excl_problem {
+    int32_t kind;        /* NFFT_HIP_EXCL_* */
+    int32_t with_field;  /* 0: z only; 1: z and field (not used by the virial) */
+    int64_t num_points;
+    int64_t num_columns; /* real columns Cr */
+    int64_t num_entries; /* entries of col and weight: twice the number of pairs */
+    int64_t batch_size;  /* point sets (the virial's output rows) */
+    double alpha;        /* splitting parameter, > 0 */
+    double box[6];       /* A00, A10, A11, A20, A21, A22 */
+} nfft_hip_ewald_excl_problem;
+int nfft_hip_ewald_excl(const nfft_hip_ewald_excl_problem *p, const float *points, const float *xr, const int32_t *row_start,
+                        const int32_t *col, const float *weight, float *z, float *field, void *stream);
+int nfft_hip_ewald_excl_box(const nfft_hip_ewald_excl_problem *p, const float *points, const float *xr,
+                            const int32_t *row_start, const int32_t *col, const float *weight, float *z, float *field,
+                            void *stream);
+int64_t nfft_hip_ewald_excl_virial_workspace_bytes(const nfft_hip_ewald_excl_problem *p);
+int nfft_hip_ewald_excl_virial(const nfft_hip_ewald_excl_problem *p, const float *points, const float *xr,
+                               const int32_t *row_start, const int32_t *col, const float *weight, const int32_t *set_start,
+                               double *out, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.
  *   gaussian_analytic_coeffs      float32:  prod_d sqrt(pi) sigma exp(-sigma^2 pi^2 l_d^2)      (kernel_coeffs.cu:6-30)

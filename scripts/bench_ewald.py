@@ -72,6 +72,14 @@ spheres of the volume fraction phi, n (4/3) pi a^3 = phi (the points are uniform
 u and for (u, G) beside nfft_ewald with its field and nfft_ewald_stokeslet; the near operator; and the pair loops of order
 1 and 2 (nfft_hip_ewald_rpy_near on restated plumbing) beside the Stokeslet loops and the Coulomb loop with its field.  The
 far part is the Stokeslet sum's with another table and is not timed again.
+
+    python scripts/bench_ewald.py --exclusions [--box ...] [...]
+
+times the bonded-pair correction of the Coulomb sum on rigid triples with three listed pairs each (a
+water model) in the unit cube or in the box: the list kernel alone (nfft_hip_ewald_excl / _box on restated plumbing) and the
+operator around it beside the pair sweep with its field and beside the whole nfft_ewald(field=True) with and without the
+list, and the bytes the list kernel must move (row_start, col, weights, the gathered positions and values, the outputs) as a
+share of the HBM's specified rate.
 """
 import argparse
 import ctypes
@@ -710,6 +718,91 @@ def run_rpy(lib, n, args):
                       "u_G_over_coulomb_field": round(whole["u_G"][0] / whole["coulomb_field"][0], 3)}))
 
 
+HBM_PEAK_GBPS = 8000.0  # the MI355X's HBM3E, as specified
+
+
+def run_exclusions(lib, n, args):
+    """bonded-pair exclusions: n / 3 rigid triples (a water model: charges -0.834, 0.417, 0.417, the
+    bond 0.3 of the molecules' mean spacing, 104.5 degrees) with their three listed pairs each, in the unit cube or in --box.
+    The correction alone (the operator, and the list kernel on restated plumbing) beside the pair sweep with its field and
+    beside the whole nfft_ewald(field=True) with and without the list"""
+    m = 4
+    n -= n % 3
+    mol = n // 3
+    box = args.box
+    if box is not None and len(box) == 3:
+        box = [box[0], 0.0, box[1], 0.0, 0.0, box[2]]
+    A = np.eye(3) if box is None else np.array([[box[0], 0, 0], [box[1], box[2], 0], [box[3], box[4], box[5]]])
+    V = float(np.linalg.det(A))
+    r_c = (3.0 * args.neighbours * V / (4.0 * math.pi * n)) ** (1.0 / 3.0)
+    if box is None:
+        r_c = min(r_c, 1.0 / 3.0)
+    sp = tn.EwaldSplitting.from_tolerance(args.tol, r_c, box=None if box is None else torch.from_numpy(A))
+    rng = np.random.default_rng(0)
+    bond = 0.3 * (V / mol) ** (1.0 / 3.0)
+    centre = (rng.random((mol, 3)) - 0.5) @ A
+    # a random orthonormal pair (u, v) per molecule: the two hydrogens at bond (cos, +-sin)(104.5 / 2)
+    u = rng.standard_normal((mol, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    v = np.cross(u, rng.standard_normal((mol, 3)))
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    half = math.radians(104.5 / 2)
+    x = np.stack([centre, centre + bond * (math.cos(half) * u + math.sin(half) * v),
+                  centre + bond * (math.cos(half) * u - math.sin(half) * v)], 1).reshape(n, 3)
+    s = (x @ np.linalg.inv(A)).astype(np.float32)
+    q = np.tile(np.array([-0.834, 0.417, 0.417], dtype=np.float32), mol)
+    o = 3 * np.arange(mol)
+    pairs = np.concatenate([np.stack([o, o + 1], 1), np.stack([o, o + 2], 1), np.stack([o + 1, o + 2], 1)])
+    ex = tn.ExclusionList(pairs, n)
+    pos, qd = torch.from_numpy(s).cuda(), torch.from_numpy(q).cuda()
+    frac = {} if box is None else {"fractional": True}
+    box6 = () if box is None else sp.box6
+    near = ((lambda: tn.ops.nfft_ewald_near(pos, qd, None, sp.alpha, r_c, True)) if box is None else
+            (lambda: tn.ops.nfft_ewald_near_box(pos, qd, None, box6, sp.alpha, r_c, True)))
+    # the list kernel alone, on restated plumbing: reduced positions, one real column
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    red = pos - pos.round()
+    red = torch.where(red >= 0.5, red - 1.0, red).contiguous()
+    xr = qd.reshape(n, 1).contiguous()
+    z, e = torch.empty(n, 1, device="cuda"), torch.empty(n, 3, device="cuda")
+    p = _lib.EwaldExclProblem(kind=_lib.EXCL_COULOMB, with_field=1, num_points=n, num_columns=1, num_entries=ex.col.numel(),
+                              batch_size=1, alpha=sp.alpha,
+                              box=(ctypes.c_double * 6)(*(box if box is not None else (1.0, 0.0, 1.0, 0.0, 0.0, 1.0))))
+    entry = lib.nfft_hip_ewald_excl if box is None else lib.nfft_hip_ewald_excl_box
+
+    def kernel():
+        _lib.check(entry(ctypes.byref(p), red.data_ptr(), xr.data_ptr(), ex.row_start.data_ptr(), ex.col.data_ptr(),
+                         ex.coulomb_weight.data_ptr(), z.data_ptr(), e.data_ptr(), stream))
+
+    def operator():
+        return tn.ops.nfft_ewald_excl(pos, qd, None, ex.row_start, ex.col, ex.coulomb_weight, box6, sp.alpha, 0, True)
+
+    t = alternating_ms({
+        "list_kernel": kernel,
+        "correction_op": operator,
+        "pair_sweep_field": near,
+        "whole_field": lambda: tn.nfft_ewald(qd, pos, splitting=sp, cutoff=m, field=True, **frac),
+        "whole_field_with_list": lambda: tn.nfft_ewald(qd, pos, splitting=sp, cutoff=m, field=True, exclusions=ex, **frac)}, args.reps)
+    zo, fo = operator()
+    assert torch.equal(zo, z.reshape(n)) and torch.equal(fo, e), "the restated plumbing must give the operator's bits"
+    tn.ops.check_status()
+    entries = ex.col.numel()
+    # what the list kernel must move: the CSR arrays, each lane's own position, one gathered position and one gathered value per
+    # entry, the value and the three field components out
+    nbytes = 4 * (n + 1) + 8 * entries + 12 * n + 12 * entries + 4 * entries + 16 * n
+    ms = lambda v: [round(a, 4) for a in v]  # noqa: E731
+    gbps = nbytes / t["list_kernel"][0] * 1e-6
+    print(json.dumps({"bench": "ewald_exclusions", "points": n, "molecules": mol, "listed_pairs": int(pairs.shape[0]),
+                      "box": box, "bond": round(bond, 6), "neighbours": args.neighbours, "tol": args.tol, "r_cut": round(r_c, 5),
+                      "alpha": round(sp.alpha, 3), "N": sp.bandwidth, "m": m, "reps": args.reps,
+                      "median_min_max_ms": {k: ms(v) for k, v in t.items()},
+                      "list_kernel_bytes": nbytes, "list_kernel_GBps": round(gbps, 1),
+                      "fraction_of_hbm_peak": round(gbps / HBM_PEAK_GBPS, 4),
+                      "list_kernel_over_pair_sweep": round(t["list_kernel"][0] / t["pair_sweep_field"][0], 4),
+                      "correction_op_over_whole": round(t["correction_op"][0] / t["whole_field"][0], 4),
+                      "with_list_over_without": round(t["whole_field_with_list"][0] / t["whole_field"][0], 4)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, nargs="+", default=[100000, 1000000])
@@ -724,9 +817,13 @@ def main():
     ap.add_argument("--stokeslet", action="store_true", help="time the periodic Stokeslet sum (unit cube) instead")
     ap.add_argument("--rpy", action="store_true", help="time the periodic Rotne-Prager-Yamakawa sum (unit cube) instead")
     ap.add_argument("--phi", type=float, default=0.1, help="--rpy: the volume fraction of the spheres, n (4/3) pi a^3")
+    ap.add_argument("--exclusions", action="store_true",
+                    help="time the bonded-pair correction on rigid triples (the unit cube, or --box) instead")
     args = ap.parse_args()
     if args.box is not None and len(args.box) not in (3, 6):
         ap.error("--box takes three or six comma-separated numbers")
+    if args.exclusions and (args.dispersion or args.virial or args.dipole or args.stokeslet or args.rpy):
+        ap.error("--exclusions times the Coulomb sum's correction on its own (with or without --box)")
     if args.dispersion and args.box is not None:
         ap.error("--dispersion times the unit cube and does not go with --box")
     if args.dipole and (args.box is not None or args.dispersion or args.virial):
@@ -738,6 +835,9 @@ def main():
     torch.cuda.set_device(0)
     lib = _lib.load()
     for n in args.points:
+        if args.exclusions:
+            run_exclusions(lib, n, args)
+            continue
         if args.rpy:
             run_rpy(lib, n, args)
             continue

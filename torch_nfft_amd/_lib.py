@@ -79,6 +79,10 @@ SYMBOLS = (
     "nfft_hip_ewald_stokeslet_spectral",
     "nfft_hip_ewald_rpy_near",
     "nfft_hip_ewald_rpy_near_box",
+    "nfft_hip_ewald_excl",
+    "nfft_hip_ewald_excl_box",
+    "nfft_hip_ewald_excl_virial_workspace_bytes",
+    "nfft_hip_ewald_excl_virial",
     "nfft_hip_gaussian_analytic_coeffs",
     "nfft_hip_interpolation_grid",
     "nfft_hip_coeffs_workspace_bytes",
@@ -151,6 +155,23 @@ class EwaldBoxProblem(ctypes.Structure):
         ("batch_size", ctypes.c_int64),
         ("alpha", ctypes.c_double),
         ("r_cut", ctypes.c_double),
+        ("box", ctypes.c_double * 6),
+    ]
+
+
+EXCL_COULOMB, EXCL_DISPERSION = 0, 1
+
+
+class EwaldExclProblem(ctypes.Structure):
+    """``nfft_hip_ewald_excl_problem`` of include/nfft_hip.h."""
+    _fields_ = [
+        ("kind", ctypes.c_int32),
+        ("with_field", ctypes.c_int32),
+        ("num_points", ctypes.c_int64),
+        ("num_columns", ctypes.c_int64),
+        ("num_entries", ctypes.c_int64),
+        ("batch_size", ctypes.c_int64),
+        ("alpha", ctypes.c_double),
         ("box", ctypes.c_double * 6),
     ]
 
@@ -299,6 +320,13 @@ def load():
     lib.nfft_hip_ewald_rpy_near.restype = ci
     lib.nfft_hip_ewald_rpy_near_box.argtypes = [ctypes.POINTER(EwaldBoxProblem), vp, vp, vp, vp, ctypes.c_int32, ctypes.c_double, vp, vp, i64, vp]
     lib.nfft_hip_ewald_rpy_near_box.restype = ci
+    for f in (lib.nfft_hip_ewald_excl, lib.nfft_hip_ewald_excl_box):
+        f.argtypes = [ctypes.POINTER(EwaldExclProblem), vp, vp, vp, vp, vp, vp, vp, vp]
+        f.restype = ci
+    lib.nfft_hip_ewald_excl_virial_workspace_bytes.argtypes = [ctypes.POINTER(EwaldExclProblem)]
+    lib.nfft_hip_ewald_excl_virial_workspace_bytes.restype = i64
+    lib.nfft_hip_ewald_excl_virial.argtypes = [ctypes.POINTER(EwaldExclProblem), vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.nfft_hip_ewald_excl_virial.restype = ci
     lib.nfft_hip_gaussian_analytic_coeffs.argtypes = [ctypes.c_double, i64, ctypes.c_int32, vp, vp]
     lib.nfft_hip_gaussian_analytic_coeffs.restype = ci
     lib.nfft_hip_interpolation_grid.argtypes = [i64, ctypes.c_int32, ci, vp, vp]

@@ -1,5 +1,6 @@
 // C-ABI entry points of the pair kernels (include/nfft_hip.h): the near field of the fast summation for singular kernels,
-// the near parts of the Ewald sums (1/r, 1/r^6, dipoles and Stokeslets) on the torus and in a box, the virial reductions.  They share only the error plumbing and
+// the near parts of the Ewald sums (1/r, 1/r^6, dipoles and Stokeslets) on the torus and in a box, the virial reductions, the bonded-pair
+// exclusions.  They share only the error plumbing and
 // the workspace conventions (host_util.h) with the transforms of api.hip.
 #include "../../include/nfft_hip.h"
 
@@ -705,6 +706,103 @@ int nfft_hip_ewald_dispersion_virial_far(int64_t N, int64_t batch_size, int64_t 
     if (!ws) return NFFT_HIP_EWORKSPACE;
     return launch_ewald_dispersion_virial_far(N, batch_size, num_columns, band, coeffs, strain_coeffs, box_inverse, out, ws,
                                               (hipStream_t)stream);
+}
+
+// ---- bonded-pair exclusions of the Coulomb and dispersion Ewald sums ----------------------------
+static int validate_excl(const nfft_hip_ewald_excl_problem *p, bool with_box)
+{
+    if (!p) { set_error("Input mismatch: null problem"); return NFFT_HIP_EINVAL; }
+    if (p->kind != NFFT_HIP_EXCL_COULOMB && p->kind != NFFT_HIP_EXCL_DISPERSION) {
+        set_error("Input mismatch: kind must be 0 (Coulomb) or 1 (dispersion)");
+        return NFFT_HIP_EINVAL;
+    }
+    if (p->with_field != 0 && p->with_field != 1) { set_error("Input mismatch: with_field must be 0 or 1"); return NFFT_HIP_EINVAL; }
+    if (p->num_points < 0 || p->num_columns < 0 || p->num_entries < 0 || p->batch_size < 1) {
+        set_error("Input mismatch: negative size");
+        return NFFT_HIP_EINVAL;
+    }
+    if (p->num_points >= (int64_t(1) << 31) || p->num_entries >= (int64_t(1) << 31)) {
+        set_error("Input mismatch: too many points or entries");
+        return NFFT_HIP_EINVAL;
+    }
+    if (!(p->alpha > 0.0) || !(p->alpha < 1e18)) { set_error("Input mismatch: alpha must be positive and finite"); return NFFT_HIP_EINVAL; }
+    double w[3];
+    if (with_box && !ewald_box_widths(p->box, w)) {
+        set_error("Input mismatch: the box must be finite with a positive diagonal");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+typedef int (*excl_launch)(const nfft_hip_ewald_excl_problem *, const float *, const float *, const int *, const int *,
+                           const float *, float *, float *, hipStream_t);
+static int excl_call(excl_launch launch, bool with_box, const nfft_hip_ewald_excl_problem *p, const float *points, const float *xr,
+                     const int32_t *row_start, const int32_t *col, const float *weight, float *z, float *field, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_excl(p, with_box)) return rc;
+    if (p->num_points == 0 || p->num_columns == 0) return 0;
+    if (!z) { set_error("Input mismatch: z is null"); return NFFT_HIP_EINVAL; }
+    if (p->with_field && !field) { set_error("Input mismatch: field is null"); return NFFT_HIP_EINVAL; }
+    if (!points || !xr || !row_start || (p->num_entries > 0 && (!col || !weight))) {
+        set_error("Input mismatch: null input");
+        return NFFT_HIP_EINVAL;
+    }
+    return launch(p, points, xr, row_start, col, weight, z, field, (hipStream_t)stream);
+}
+
+int nfft_hip_ewald_excl(const nfft_hip_ewald_excl_problem *p, const float *points, const float *xr, const int32_t *row_start,
+                        const int32_t *col, const float *weight, float *z, float *field, void *stream)
+{
+    return excl_call(launch_ewald_excl, false, p, points, xr, row_start, col, weight, z, field, stream);
+}
+
+int nfft_hip_ewald_excl_box(const nfft_hip_ewald_excl_problem *p, const float *points, const float *xr,
+                            const int32_t *row_start, const int32_t *col, const float *weight, float *z, float *field,
+                            void *stream)
+{
+    return excl_call(launch_ewald_excl_box, true, p, points, xr, row_start, col, weight, z, field, stream);
+}
+
+// the list's own checks, and the second level's launch: one workgroup per point set and column
+static int validate_excl_virial(const nfft_hip_ewald_excl_problem *p)
+{
+    if (int rc = validate_excl(p, true)) return rc;
+    if (p->num_columns >= (int64_t(1) << 21) || p->batch_size >= (int64_t(1) << 21) ||
+        p->batch_size * p->num_columns >= (int64_t(1) << 21)) {
+        set_error("Input mismatch: num_columns < 2^21 and batch_size * num_columns < 2^21 are required");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+static int64_t excl_virial_need(const nfft_hip_ewald_excl_problem *p) { return ewald_excl_virial_workspace(p) + 256; }
+
+int64_t nfft_hip_ewald_excl_virial_workspace_bytes(const nfft_hip_ewald_excl_problem *p)
+{
+    if (validate_excl_virial(p)) return -1;
+    return excl_virial_need(p);
+}
+
+int nfft_hip_ewald_excl_virial(const nfft_hip_ewald_excl_problem *p, const float *points, const float *xr,
+                               const int32_t *row_start, const int32_t *col, const float *weight, const int32_t *set_start,
+                               double *out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_excl_virial(p)) return rc;
+    if (p->num_columns == 0) return 0;
+    if (!out) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
+    if (p->num_points == 0 || p->num_entries == 0) {
+        NFFT_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(p->batch_size * 7 * p->num_columns) * sizeof(double), (hipStream_t)stream));
+        return 0;
+    }
+    if (!points || !xr || !row_start || !col || !weight || (p->batch_size > 1 && !set_start)) {
+        set_error("Input mismatch: null input");
+        return NFFT_HIP_EINVAL;
+    }
+    char *ws = workspace_base(workspace, workspace_bytes, excl_virial_need(p));
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_ewald_excl_virial(p, points, xr, row_start, col, weight, set_start, out, ws, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1357,6 +1357,103 @@ at::Tensor nfft_ewald_rpy_near(at::Tensor pos, at::Tensor f, c10::optional<at::T
     return packed_near(kRpySum, near, near_box, pos, f, batch, box, alpha, r_cut, order);
 }
 
+// ---- bonded-pair exclusions of the Coulomb and dispersion Ewald sums (not in the reference) ------
+// The list's CSR arrays as the native calls take them, checked against the points
+struct ExclInput { at::Tensor row_start, col, weight; };
+ExclInput check_excl(const at::Tensor &row_start, const at::Tensor &col, const at::Tensor &weight, const at::Tensor &pos, int64_t n)
+{
+    CHECK_INPUT(row_start.scalar_type() == at::kInt && col.scalar_type() == at::kInt && weight.scalar_type() == at::kFloat);
+    CHECK_INPUT(row_start.dim() == 1 && col.dim() == 1 && weight.dim() == 1);
+    CHECK_INPUT(row_start.numel() == n + 1 && weight.numel() == col.numel());
+    CHECK_INPUT(row_start.device() == pos.device() && col.device() == pos.device() && weight.device() == pos.device());
+    return {row_start.contiguous(), col.contiguous(), weight.contiguous()};
+}
+
+nfft_hip_ewald_excl_problem excl_problem(const Points &p, int64_t Cr, int64_t entries, const std::vector<double> &box, double alpha,
+                                         int64_t kind, bool with_field)
+{
+    CHECK_INPUT(box.empty() || box.size() == 6);
+    CHECK_INPUT(kind == NFFT_HIP_EXCL_COULOMB || kind == NFFT_HIP_EXCL_DISPERSION);
+    static const double unit[6] = {1.0, 0.0, 1.0, 0.0, 0.0, 1.0};
+    nfft_hip_ewald_excl_problem q;
+    q.kind = (int32_t)kind;
+    q.with_field = with_field ? 1 : 0;
+    q.num_points = p.n;
+    q.num_columns = Cr;
+    q.num_entries = entries;
+    q.batch_size = p.B;
+    q.alpha = alpha;
+    for (int e = 0; e < 6; ++e) q.box[e] = box.empty() ? unit[e] : box[e];
+    return q;
+}
+
+// x's rows [n, row] float32 in the caller's order (complex values: real and imaginary parts as columns)
+at::Tensor real_rows_in_place(const at::Tensor &x, bool real_input, int64_t n, int64_t row)
+{
+    const at::Tensor xc = x.contiguous();
+    return (real_input ? xc : at::view_as_real(xc)).reshape({n, row}).contiguous();
+}
+
+// (z, f): what the listed pairs take out of (phi, E) of the Coulomb sum (kind 0) or (psi, G) of the dispersion sum (kind 1),
+// z[i] = sum_{k in row i} weight[k] K0(r) x[col[k]] and f[i, a] = sum_k weight[k] K1(r) d[a] x[col[k]], x's type and shapes
+// as for nfft_ewald_near.  box: no numbers for the unit torus, six for the box of nfft_ewald_near_box (pos FRACTIONAL).  The
+// positions are reduced with torus_reduce, as the sweeps' cell order reduces them: the image carries the same bits.
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_excl(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch,
+                                                   at::Tensor row_start, at::Tensor col, at::Tensor weight,
+                                                   std::vector<double> box, double alpha, int64_t kind, bool with_field)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_excl is currently only implemented for GPU tensors");
+    const EwaldInput in = check_ewald(pos, x, opt_batch, with_field);
+    const Points &p = in.p;
+    const ExclInput ex = check_excl(row_start, col, weight, pos, p.n);
+    const nfft_hip_ewald_excl_problem q = excl_problem(p, in.cx.Cr(), ex.col.numel(), box, alpha, kind, with_field);
+    if (p.n == 0 || in.cx.C == 0 || q.num_entries == 0)
+        return {at::zeros(in.z_shape, x.options()), at::zeros(in.f_shape, x.options())};  // no launch
+    c10::DeviceGuard guard(x.device());
+    const at::Tensor red = torus_reduce(p.pos).contiguous();
+    const at::Tensor xr = real_rows_in_place(x, in.cx.real_input, p.n, q.num_columns);
+    const at::TensorOptions opts = x.options().dtype(at::kFloat);
+    at::Tensor z = at::empty({p.n, q.num_columns}, opts);
+    at::Tensor f = with_field ? at::empty({p.n, 3 * q.num_columns}, opts) : at::empty({0}, x.options());
+    check_rc((box.empty() ? nfft_hip_ewald_excl : nfft_hip_ewald_excl_box)(
+        &q, red.data_ptr<float>(), xr.data_ptr<float>(), ex.row_start.data_ptr<int32_t>(), ex.col.data_ptr<int32_t>(),
+        ex.weight.data_ptr<float>(), z.data_ptr<float>(), with_field ? f.data_ptr<float>() : nullptr, stream_of(x)));
+    return ewald_result(in, z, f, with_field);
+}
+
+// [B, 7, *cols] float64: the listed pairs' share of nfft_ewald_virial_near (kind 0) or nfft_ewald_dispersion_virial_near
+// (kind 1), each pair once, in their order; real x only; box: six numbers (the unit cube: 1, 0, 1, 0, 0, 1), pos FRACTIONAL
+at::Tensor nfft_ewald_excl_virial(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch, at::Tensor row_start,
+                                  at::Tensor col, at::Tensor weight, std::vector<double> box, double alpha, int64_t kind)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_excl_virial is currently only implemented for GPU tensors");
+    const EwaldInput in = check_ewald(pos, x, opt_batch, false);
+    const Points &p = in.p;
+    CHECK_INPUT(box.size() == 6);
+    CHECK_INPUT(in.cx.real_input);  // (the energy is bilinear: real values only)
+    const ExclInput ex = check_excl(row_start, col, weight, pos, p.n);
+    const int64_t C = in.cx.C;
+    const std::vector<int64_t> shape = in.cx.shape({p.B, 7});
+    const nfft_hip_ewald_excl_problem q = excl_problem(p, C, ex.col.numel(), box, alpha, kind, false);
+    const int64_t ws_bytes = nfft_hip_ewald_excl_virial_workspace_bytes(&q);
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    const at::TensorOptions opts = x.options().dtype(at::kDouble);
+    if (p.n == 0 || C == 0 || q.num_entries == 0) return at::zeros(shape, opts);  // no launch
+    c10::DeviceGuard guard(x.device());
+    const at::Tensor red = torus_reduce(p.pos).contiguous();
+    const at::Tensor xr = real_rows_in_place(x, true, p.n, C);
+    at::Tensor set_start;
+    if (p.batch.defined())
+        set_start = at::searchsorted(p.batch, at::arange(p.B + 1, p.batch.options()), /*out_int32=*/true).contiguous();
+    at::Tensor out = at::empty({p.B, 7, C}, opts);
+    at::Tensor ws = byte_buffer(ws_bytes, x);
+    check_rc(nfft_hip_ewald_excl_virial(&q, red.data_ptr<float>(), xr.data_ptr<float>(), ex.row_start.data_ptr<int32_t>(),
+                                        ex.col.data_ptr<int32_t>(), ex.weight.data_ptr<float>(),
+                                        set_start.defined() ? set_start.data_ptr<int32_t>() : nullptr, out.data_ptr<double>(),
+                                        ws.data_ptr(), ws_bytes, stream_of(x)));
+    return out.reshape(shape);
+}
+
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
 at::TensorOptions current_device_options(at::ScalarType dtype)
 {
@@ -1510,4 +1607,9 @@ TORCH_LIBRARY(torch_nfft, m)
     // not in the reference: the pair sweep of the periodic Rotne-Prager-Yamakawa sum (nfft_ewald_rpy)
     m.def("_nfft_ewald_rpy_near(Tensor pos, Tensor f, Tensor? batch, float[] box, float alpha, float r_cut, float radius, "
           "int order) -> Tensor", &nfft_ewald_rpy_near);
+    // not in the reference: what a list of bonded pairs takes out of the Coulomb and dispersion Ewald sums and their virials
+    m.def("_nfft_ewald_excl(Tensor pos, Tensor x, Tensor? batch, Tensor row_start, Tensor col, Tensor weight, float[] box, "
+          "float alpha, int kind, bool with_field) -> (Tensor, Tensor)", &nfft_ewald_excl);
+    m.def("_nfft_ewald_excl_virial(Tensor pos, Tensor x, Tensor? batch, Tensor row_start, Tensor col, Tensor weight, "
+          "float[] box, float alpha, int kind) -> Tensor", &nfft_ewald_excl_virial);
 }

@@ -241,6 +241,18 @@ int launch_ewald_dispersion_virial_near(const nfft_hip_ewald_box_problem *p, con
 int launch_ewald_dispersion_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
                                        const float *strain_coeffs, const double *box_inverse, double *out, void *workspace,
                                        hipStream_t stream);
+// ewald_excl.hip (bonded-pair exclusions of the Coulomb and dispersion Ewald sums): the list kernel on
+// the unit torus and in a box, arguments as nfft_hip_ewald_excl / _box; and the listed pairs' share of the virial, arguments
+// as nfft_hip_ewald_excl_virial, `workspace`: ewald_excl_virial_workspace(p) bytes, 8-byte aligned (one partial per workgroup;
+// the second level is launch_virial_sum)
+int launch_ewald_excl(const nfft_hip_ewald_excl_problem *p, const float *pos, const float *xr, const int *row_start,
+                      const int *col, const float *weight, float *z, float *f, hipStream_t stream);
+int launch_ewald_excl_box(const nfft_hip_ewald_excl_problem *p, const float *pos, const float *xr, const int *row_start,
+                          const int *col, const float *weight, float *z, float *f, hipStream_t stream);
+int64_t ewald_excl_virial_workspace(const nfft_hip_ewald_excl_problem *p);
+int launch_ewald_excl_virial(const nfft_hip_ewald_excl_problem *p, const float *pos, const float *xr, const int *row_start,
+                             const int *col, const float *weight, const int *set_start, double *out, void *workspace,
+                             hipStream_t stream);
 
 // smallgrid.hip: transforms whose oversampled grid (<= 4096 cells) fits one workgroup's LDS -- one kernel per direction,
 // no point plan

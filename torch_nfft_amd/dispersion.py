@@ -23,6 +23,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import ops
+from . import exclusions as _exclusions
 from .ewald import _IDENTITY6, _TorusSplitting, _fractional, _set_sums, _symmetric_backward, _voigt_to_matrix
 from .nfft import nfft_adjoint, nfft_forward, nfft_fastsum
 
@@ -114,9 +115,10 @@ class DispersionSplitting(_TorusSplitting):
         return self._strain_coeffs
 
 
-def _dispersion(c, pos, batch, splitting, cutoff, field):
+def _dispersion(c, pos, batch, splitting, cutoff, field, exclusions=None):
     """(psi, G or None) without autograd: far field, pair sweep, self term (with a box: ``pos`` fractional, ``G``
-    Cartesian)"""
+    Cartesian).  The listed pairs of ``exclusions`` are taken out of the pair sweep's sums before anything else is added to
+    them, as in ``ewald._ewald``."""
     N = splitting.bandwidth
     if field:
         cols = [1] * (c.dim() - 1)
@@ -131,6 +133,9 @@ def _dispersion(c, pos, batch, splitting, cutoff, field):
         z, f = ops.nfft_ewald_dispersion_near_box(pos, c, batch, splitting.box6, alpha, splitting.r_cut, field)
     else:
         z, f = ops.nfft_ewald_dispersion_near(pos, c, batch, alpha, splitting.r_cut, field)
+    if exclusions is not None:
+        zx, fx = _exclusions.correction(_exclusions.DISPERSION, c, pos, batch, splitting, exclusions, field)
+        z, f = z - zx, (f - fx if field else f)
     psi = psi + z - (alpha ** 6 / 6.0) * c
     return psi, (G + f if field else None)
 
@@ -142,12 +147,12 @@ class NfftEwaldDispersionFunction(torch.autograd.Function):
     order only (``once_differentiable``); ``G`` is not differentiable."""
 
     @staticmethod
-    def forward(ctx, c, pos, batch, splitting, cutoff, field):
+    def forward(ctx, c, pos, batch, splitting, cutoff, field, exclusions=None):
         if batch is not None and batch.requires_grad:
             raise AssertionError("nfft_ewald_dispersion is differentiable w.r.t. c and pos only, but batch requires grad")
-        ctx.splitting, ctx.cutoff = splitting, cutoff
+        ctx.splitting, ctx.cutoff, ctx.exclusions = splitting, cutoff, exclusions
         ctx.save_for_backward(c, pos, batch)
-        psi, G = _dispersion(c, pos, batch, splitting, cutoff, field)
+        psi, G = _dispersion(c, pos, batch, splitting, cutoff, field, exclusions)
         if G is None:
             G = c.new_empty(0)
         ctx.mark_non_differentiable(G)
@@ -156,7 +161,7 @@ class NfftEwaldDispersionFunction(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g, _):
-        return _symmetric_backward(_dispersion, ctx, g)
+        return _symmetric_backward(_dispersion, ctx, g) + (None,)
 
 
 def _check(what, c, pos, batch, splitting, differentiable=True):
@@ -170,7 +175,7 @@ def _check(what, c, pos, batch, splitting, differentiable=True):
         raise AssertionError("%s: batch holds point-set indices and must not require grad" % what)
 
 
-def nfft_ewald_dispersion(c, pos, batch=None, /, splitting=None, cutoff=4, field=False, fractional=False):
+def nfft_ewald_dispersion(c, pos, batch=None, /, splitting=None, cutoff=4, field=False, fractional=False, exclusions=None):
     """The periodic dispersion sum ``psi_i = sum'_{j, n} c_j / |x_i - x_j + n|^6`` of the coefficients ``c`` ``[n, *cols]``
     (float32 or complex64) at ``pos`` ``[n, 3]``, over the points of i's point set (``batch``: sorted point-set indices) and
     all their periodic images; only the self pair is left out.  The sum converges absolutely: no background, no
@@ -186,26 +191,37 @@ def nfft_ewald_dispersion(c, pos, batch=None, /, splitting=None, cutoff=4, field
 
     Differentiable once in ``c`` and ``pos``; ``G`` itself is not differentiable, a second derivative raises a
     RuntimeError, and ``batch`` must not require grad (AssertionError).  The gradient comes back in the coordinates that
-    were passed."""
+    were passed.
+
+    ``exclusions`` is ``None`` or an ``ExclusionList`` over the ``n`` points (TypeError, ValueError as for ``nfft_ewald``):
+    every listed pair ``{i, j}`` loses ``(1 - s^D_ij) c_j / r^6`` in ``psi_i`` and ``6 (1 - s^D_ij) c_j d_ij / r^8`` in ``G_i``
+    for the one image that the sweep sees (a pair at ``r = 0``: ``(1 - s^D_ij) c_j alpha^6 / 6`` and no field), by one more
+    native call; the gradients are those of the corrected sum.  The sweep has added the pair before the correction
+    removes it: an excluded pair leaves a rounding of about ``2^-24 |c_j| / r^6`` in ``psi_i`` (``exclusions.py``)."""
     _check("nfft_ewald_dispersion", c, pos, batch, splitting)
+    exclusions = _exclusions.check_exclusions("nfft_ewald_dispersion", exclusions, pos)
     pos = _fractional("nfft_ewald_dispersion", pos, splitting, fractional)
-    psi, G = NfftEwaldDispersionFunction.apply(c, pos, batch, splitting, int(cutoff), bool(field))
+    if exclusions is None:
+        psi, G = NfftEwaldDispersionFunction.apply(c, pos, batch, splitting, int(cutoff), bool(field))
+    else:
+        psi, G = NfftEwaldDispersionFunction.apply(c, pos, batch, splitting, int(cutoff), bool(field), exclusions)
     return (psi, G) if field else psi
 
 
-def nfft_ewald_dispersion_energy(c, pos, batch=None, /, splitting=None, cutoff=4, fractional=False):
+def nfft_ewald_dispersion_energy(c, pos, batch=None, /, splitting=None, cutoff=4, fractional=False, exclusions=None):
     """``U_b = 1/2 sum_{i in point set b} c_i psi_i`` with ``psi = nfft_ewald_dispersion(c, pos, batch, ...)``:
     ``[B, *cols]``, one value per point set and column (bilinear in ``c``).  The physical dispersion energy of the pair
     coefficients ``C6_ij = c_i c_j`` (geometric mixing) is its NEGATIVE, ``-U``: the attraction is ``-C6 / r^6``.
-    ``dU/dpos_i = -c_i G_i`` summed over the columns."""
+    ``dU/dpos_i = -c_i G_i`` summed over the columns.  ``exclusions`` as for ``nfft_ewald_dispersion``: every listed pair loses
+    ``(1 - s^D_ij) c_i c_j / r^6``."""
     _check("nfft_ewald_dispersion_energy", c, pos, batch, splitting)
     if splitting.box is None and fractional:
         raise ValueError("nfft_ewald_dispersion_energy: fractional=True needs a DispersionSplitting with a box")
-    psi = nfft_ewald_dispersion(c, pos, batch, splitting=splitting, cutoff=cutoff, fractional=fractional)
+    psi = nfft_ewald_dispersion(c, pos, batch, splitting=splitting, cutoff=cutoff, fractional=fractional, exclusions=exclusions)
     return 0.5 * _set_sums(c * psi, batch)[0]
 
 
-def nfft_ewald_dispersion_virial(c, pos, batch=None, /, splitting=None, cutoff=4, fractional=False):
+def nfft_ewald_dispersion_virial(c, pos, batch=None, /, splitting=None, cutoff=4, fractional=False, exclusions=None):
     """``(U, W)``: ``U_b = 1/2 sum_{i in point set b} c_i psi_i`` ``[B, *cols]`` of ``nfft_ewald_dispersion_energy`` and the
     virial tensor ``W_ab = -dU / d eps_ab`` ``[B, 3, 3, *cols]`` for the homogeneous strain ``A -> A (1 + eps)`` of the box at
     fixed fractional coordinates, per point set and column, both with the dtype of ``c``: the counterpart of
@@ -222,7 +238,10 @@ def nfft_ewald_dispersion_virial(c, pos, batch=None, /, splitting=None, cutoff=4
     One adjoint transform, then two native reductions in float64 and without atomics -- over the frequencies of its output,
     ``1/2 sum_k |S_k|^2 (b_k, b_k delta_ab + t_k kappa_a kappa_b)`` with ``t = splitting.strain_coeffs()``, and over the pairs
     within ``r_cut``, ``1/2 sum_ij c_i c_j (w, mg d_a d_b)`` -- and the self term ``-(alpha^6 / 12) sum c_i^2`` (in ``U`` only: it
-    has no strain in it) added in float64 before the cast.  The ``k = 0`` term is part of both sums: no background.
+    has no strain in it) added in float64 before the cast.  The ``k = 0`` term is part of both sums: no background.  With
+    ``exclusions`` (as for ``nfft_ewald_dispersion``) a third native reduction takes ``(1 - s^D_ij) c_i c_j / r^6`` out of ``U`` and
+    ``6 (1 - s^D_ij) c_i c_j d_a d_b / r^8`` out of ``W`` for every listed pair (``tr W = 6 U`` stays; a pair at ``r = 0``:
+    ``(1 - s^D_ij) c_i c_j alpha^6 / 6`` in ``U`` only).
 
     Runs under ``torch.no_grad()``: ``U`` and ``W`` are constants to autograd.  Inputs that require grad are accepted and
     get no gradient from here (use ``nfft_ewald_dispersion_energy`` for forces); ``batch`` must not require grad
@@ -230,6 +249,7 @@ def nfft_ewald_dispersion_virial(c, pos, batch=None, /, splitting=None, cutoff=4
     _check("nfft_ewald_dispersion_virial", c, pos, batch, splitting, differentiable=False)
     if c.is_complex():
         raise ValueError("nfft_ewald_dispersion_virial: the coefficients must be real (the energy is bilinear in c)")
+    exclusions = _exclusions.check_exclusions("nfft_ewald_dispersion_virial", exclusions, pos)
     with torch.no_grad():
         c, pos = c.detach(), pos.detach()
         pos = _fractional("nfft_ewald_dispersion_virial", pos, splitting, fractional)
@@ -238,6 +258,8 @@ def nfft_ewald_dispersion_virial(c, pos, batch=None, /, splitting=None, cutoff=4
         band = nfft_adjoint(c, pos, batch, bandwidth=N, cutoff=int(cutoff))  # [B, N, N, N, *cols]
         seven = ops.nfft_ewald_dispersion_virial_far(band, splitting.coeffs, splitting.strain_coeffs(), box6)
         seven = seven + ops.nfft_ewald_dispersion_virial_near(pos, c, batch, box6, alpha, splitting.r_cut)  # [B, 7, *cols] float64
+        if exclusions is not None:
+            seven = seven - _exclusions.virial_correction(_exclusions.DISPERSION, c, pos, batch, splitting, exclusions)
         c64 = c.double()
         U = seven[:, 0] - (alpha ** 6 / 12.0) * _set_sums(c64 * c64, batch)[0]
         return U.to(c.dtype), _voigt_to_matrix(seven[:, 1:]).to(c.dtype)

@@ -43,6 +43,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
+from . import exclusions as _exclusions
 from .nfft import nfft_adjoint, nfft_forward, nfft_fastsum
 
 MAX_R_CUT = 1.0 / 3.0  # the pair sweep needs 3 cells of edge >= r_cut per axis
@@ -270,9 +271,11 @@ def _set_sums(q, batch):
     return total, total.index_select(0, batch)
 
 
-def _ewald(q, pos, batch, splitting, cutoff, field):
+def _ewald(q, pos, batch, splitting, cutoff, field, exclusions=None):
     """(phi, E or None) without autograd: far field, pair sweep, self and background terms (with a box: ``pos`` fractional,
-    ``E`` Cartesian)"""
+    ``E`` Cartesian).  The listed pairs of ``exclusions`` are taken out of the pair sweep's sums before anything else is added
+    to them: where a listed pair's 1 / r dominates a point's sum the two are within a factor of two of each other and that
+    difference is exact, and the far field, the self and the background term are not rounded at the size of 1 / r."""
     N = splitting.bandwidth
     if field:
         cols = [1] * (q.dim() - 1)
@@ -285,11 +288,13 @@ def _ewald(q, pos, batch, splitting, cutoff, field):
     alpha = splitting.alpha
     if splitting.box is not None:
         z, f = ops.nfft_ewald_near_box(pos, q, batch, splitting.box6, alpha, splitting.r_cut, field)
-        background = math.pi / (alpha * alpha * splitting.volume)
-        phi = phi + z - (2.0 * alpha / math.sqrt(math.pi)) * q - background * _set_sums(q, batch)[1]
-        return phi, (E + f if field else None)
-    z, f = ops.nfft_ewald_near(pos, q, batch, splitting.alpha, splitting.r_cut, field)
-    phi = phi + z - (2.0 * alpha / math.sqrt(math.pi)) * q - (math.pi / (alpha * alpha)) * _set_sums(q, batch)[1]
+    else:
+        z, f = ops.nfft_ewald_near(pos, q, batch, splitting.alpha, splitting.r_cut, field)
+    if exclusions is not None:
+        zx, fx = _exclusions.correction(_exclusions.COULOMB, q, pos, batch, splitting, exclusions, field)
+        z, f = z - zx, (f - fx if field else f)
+    background = math.pi / (alpha * alpha * splitting.volume)
+    phi = phi + z - (2.0 * alpha / math.sqrt(math.pi)) * q - background * _set_sums(q, batch)[1]
     return phi, (E + f if field else None)
 
 
@@ -301,6 +306,9 @@ def _symmetric_backward(evaluate, ctx, g):
     need_q, need_pos = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
     g = g.contiguous()
     dq = dpos = None
+    if getattr(ctx, "exclusions", None) is not None:  # (symmetric weights: the corrected operator is symmetric too)
+        all_pairs, exclusions = evaluate, ctx.exclusions
+        evaluate = lambda *args: all_pairs(*args, exclusions)  # noqa: E731
     if need_pos:
         phi, E = evaluate(torch.stack([q, g], 1), pos, batch, ctx.splitting, ctx.cutoff, True)  # [n, (3,) 2, *cols]
         dq = phi[:, 1]
@@ -323,12 +331,12 @@ class NfftEwaldFunction(torch.autograd.Function):
     ``dL/ds = (dL/dx) A^T``."""
 
     @staticmethod
-    def forward(ctx, q, pos, batch, splitting, cutoff, field):
+    def forward(ctx, q, pos, batch, splitting, cutoff, field, exclusions=None):
         if batch is not None and batch.requires_grad:
             raise AssertionError("nfft_ewald is differentiable w.r.t. q and pos only, but batch requires grad")
-        ctx.splitting, ctx.cutoff = splitting, cutoff
+        ctx.splitting, ctx.cutoff, ctx.exclusions = splitting, cutoff, exclusions
         ctx.save_for_backward(q, pos, batch)
-        phi, E = _ewald(q, pos, batch, splitting, cutoff, field)
+        phi, E = _ewald(q, pos, batch, splitting, cutoff, field, exclusions)
         if E is None:
             E = q.new_empty(0)
         ctx.mark_non_differentiable(E)
@@ -337,7 +345,7 @@ class NfftEwaldFunction(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g, _):
-        return _symmetric_backward(_ewald, ctx, g)
+        return _symmetric_backward(_ewald, ctx, g) + (None,)
 
 
 def _check(what, q, pos, batch, splitting, differentiable=True):
@@ -362,7 +370,7 @@ def _fractional(what, pos, splitting, fractional):
     return (pos.double() @ splitting._matrices(pos.device)[1]).float()
 
 
-def nfft_ewald(q, pos, batch=None, /, splitting=None, cutoff=4, field=False, fractional=False):
+def nfft_ewald(q, pos, batch=None, /, splitting=None, cutoff=4, field=False, fractional=False, exclusions=None):
     """The periodic Coulomb potential ``phi_i = sum'_{j, n} q_j / |x_i - x_j + n|`` of the charges ``q`` ``[n, *cols]``
     (float32 or complex64) at ``pos`` ``[n, 3]`` in the unit box, over the charges of i's point set (``batch``: sorted
     point-set indices, as everywhere) and all their periodic images, in the Ewald sense: the self pair is left out, and
@@ -381,22 +389,33 @@ def nfft_ewald(q, pos, batch=None, /, splitting=None, cutoff=4, field=False, fra
     (converted in float64, ``s = pos A^-1``, and rounded to float32), or with ``fractional=True`` the fractional
     coordinates ``s`` themselves, taken modulo 1.  ``phi`` and ``E`` are in the box's units and ``E`` is always Cartesian;
     the gradient comes back in the coordinates that were passed (``dL/ds = (dL/dx) A^T``).  Without a box ``fractional``
-    must stay False (ValueError)."""
+    must stay False (ValueError).
+
+    ``exclusions`` is ``None`` or an ``ExclusionList`` over the ``n`` points (TypeError for anything else, ValueError for
+    another point count): every listed pair ``{i, j}`` loses ``(1 - s^C_ij) q_j / r`` in ``phi_i`` and
+    ``(1 - s^C_ij) q_j d_ij / r^3`` in ``E_i`` for the one image ``d_ij`` that the sweep sees (a pair at ``r = 0``:
+    ``(1 - s^C_ij) q_j 2 alpha / sqrt(pi)`` and no field), by one more native call; the operator stays symmetric and the
+    gradients are those of the corrected sum.  The sweep has added the pair before the correction removes it: an
+    excluded pair at the separation ``r`` leaves a rounding of about ``2^-24 |q_j| / r`` in ``phi_i`` (``exclusions.py``)."""
     _check("nfft_ewald", q, pos, batch, splitting)
+    exclusions = _exclusions.check_exclusions("nfft_ewald", exclusions, pos)
     pos = _fractional("nfft_ewald", pos, splitting, fractional)
-    phi, E = NfftEwaldFunction.apply(q, pos, batch, splitting, int(cutoff), bool(field))
+    if exclusions is None:
+        phi, E = NfftEwaldFunction.apply(q, pos, batch, splitting, int(cutoff), bool(field))
+    else:
+        phi, E = NfftEwaldFunction.apply(q, pos, batch, splitting, int(cutoff), bool(field), exclusions)
     return (phi, E) if field else phi
 
 
-def nfft_ewald_energy(q, pos, batch=None, /, splitting=None, cutoff=4, fractional=False):
+def nfft_ewald_energy(q, pos, batch=None, /, splitting=None, cutoff=4, fractional=False, exclusions=None):
     """``U_b = 1/2 sum_{i in point set b} q_i phi_i`` with ``phi = nfft_ewald(q, pos, batch, ...)``: ``[B, *cols]``, one
     energy per point set and column (bilinear in ``q``: no conjugate for complex charges).  Its gradient in ``pos`` is
     minus the force, ``dU/dpos_i = -q_i E_i`` summed over the columns (Cartesian ``pos`` in a box; ``fractional`` as for
-    ``nfft_ewald``)."""
+    ``nfft_ewald``); ``exclusions`` as there: every listed pair loses ``(1 - s^C_ij) q_i q_j / r``."""
     _check("nfft_ewald_energy", q, pos, batch, splitting)
     if splitting.box is None and fractional:
         raise ValueError("nfft_ewald_energy: fractional=True needs an EwaldSplitting with a box")
-    phi = nfft_ewald(q, pos, batch, splitting=splitting, cutoff=cutoff, fractional=fractional)
+    phi = nfft_ewald(q, pos, batch, splitting=splitting, cutoff=cutoff, fractional=fractional, exclusions=exclusions)
     return 0.5 * _set_sums(q * phi, batch)[0]
 
 
@@ -413,7 +432,7 @@ def _voigt_to_matrix(six):
     return W
 
 
-def nfft_ewald_virial(q, pos, batch=None, /, splitting=None, cutoff=4, fractional=False):
+def nfft_ewald_virial(q, pos, batch=None, /, splitting=None, cutoff=4, fractional=False, exclusions=None):
     """``(U, W)``: the energy ``U_b = 1/2 sum_{i in point set b} q_i phi_i`` ``[B, *cols]`` of ``nfft_ewald_energy`` and
     the virial tensor ``W_ab = -dU / d eps_ab`` ``[B, 3, 3, *cols]`` for the homogeneous strain ``A -> A (1 + eps)`` of the
     box at fixed fractional coordinates, per point set and column, both with the dtype of ``q``.  ``W`` is symmetric and
@@ -428,13 +447,16 @@ def nfft_ewald_virial(q, pos, batch=None, /, splitting=None, cutoff=4, fractiona
     ``r_cut`` -- in float64 and without atomics (they give the same bits on every call; the transform before them spreads
     with float atomics, so the whole does not); the self term ``-(alpha / sqrt(pi))
     sum q_i^2`` (in ``U`` only: it has no strain in it) and the background ``-pi Q^2 / (2 alpha^2 V)`` (in ``U`` and on the
-    diagonal of ``W``) are added in float64 before the cast.
+    diagonal of ``W``) are added in float64 before the cast.  With ``exclusions`` (as for ``nfft_ewald``) a third native
+    reduction of the same kind takes ``(1 - s^C_ij) q_i q_j / r`` out of ``U`` and ``(1 - s^C_ij) q_i q_j d_a d_b / r^3`` out of
+    ``W`` for every listed pair (``tr W = U`` stays; a pair at ``r = 0``: ``(1 - s^C_ij) q_i q_j 2 alpha / sqrt(pi)`` in ``U`` only).
 
     Runs under ``torch.no_grad()``: ``U`` and ``W`` are constants to autograd.  Inputs that require grad are accepted and
     get no gradient from here (use ``nfft_ewald_energy`` for forces); ``batch`` must not require grad (AssertionError)."""
     _check("nfft_ewald_virial", q, pos, batch, splitting, differentiable=False)
     if q.is_complex():
         raise ValueError("nfft_ewald_virial: the charges must be real (the energy is bilinear in q)")
+    exclusions = _exclusions.check_exclusions("nfft_ewald_virial", exclusions, pos)
     with torch.no_grad():
         q, pos = q.detach(), pos.detach()
         pos = _fractional("nfft_ewald_virial", pos, splitting, fractional)
@@ -443,6 +465,8 @@ def nfft_ewald_virial(q, pos, batch=None, /, splitting=None, cutoff=4, fractiona
         band = nfft_adjoint(q, pos, batch, bandwidth=N, cutoff=int(cutoff))  # [B, N, N, N, *cols]
         seven = ops.nfft_ewald_virial_far(band, splitting.coeffs, box6, alpha)
         seven = seven + ops.nfft_ewald_virial_near(pos, q, batch, box6, alpha, splitting.r_cut)  # [B, 7, *cols] float64
+        if exclusions is not None:
+            seven = seven - _exclusions.virial_correction(_exclusions.COULOMB, q, pos, batch, splitting, exclusions)
         q64 = q.double()
         total = _set_sums(q64, batch)[0]
         background = (math.pi / (2.0 * alpha * alpha * splitting.volume)) * total * total

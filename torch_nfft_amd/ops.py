@@ -338,6 +338,33 @@ def nfft_ewald_rpy_near(pos, f, batch, box, alpha, r_cut, radius, order):
     return _ops._nfft_ewald_rpy_near(pos, f, batch, [float(a) for a in box], float(alpha), float(r_cut), float(radius), int(order))
 
 
+def nfft_ewald_excl(pos, x, batch, row_start, col, weight, box, alpha, kind, with_field):
+    """torch_nfft::_nfft_ewald_excl(Tensor pos, Tensor x, Tensor? batch, Tensor row_start, Tensor col, Tensor weight,
+    float[] box, float alpha, int kind, bool with_field) -> (Tensor, Tensor) (not in the reference): what the listed pairs of an
+    ``ExclusionList`` -- its CSR arrays ``row_start`` ``[n + 1]`` int32, ``col`` ``[2 m]`` int32, ``weight`` ``[2 m]`` float32 -- take
+    out of the Coulomb sum (``kind = 0``) or the dispersion sum (``kind = 1``)::
+
+        z_i   = sum_{k in row i} weight_k K0(r) x[col_k]          K0 = 1 / r,   1 / r^6
+        f_i,a = sum_{k in row i} weight_k K1(r) d_a x[col_k]      K1 = 1 / r^3, 6 / r^8
+
+    with ``d`` the minimum image of ``pos_i - pos_col`` as the pair sweeps form it (the same bits) and, at ``r = 0``,
+    ``K0 = 2 alpha / sqrt(pi)`` or ``alpha^6 / 6`` and no field.  ``x``, ``z`` and ``f`` as for ``nfft_ewald_near``; ``box`` is
+    ``()`` for the unit torus or the six numbers of ``nfft_ewald_near_box`` (``pos`` FRACTIONAL).  The caller subtracts.  One
+    native call (``nfft_hip_ewald_excl`` / ``_box``), no atomics: two calls give the same bits."""
+    return _ops._nfft_ewald_excl(pos, x, batch, row_start, col, weight, [float(a) for a in box], float(alpha), int(kind),
+                                 bool(with_field))
+
+
+def nfft_ewald_excl_virial(pos, x, batch, row_start, col, weight, box, alpha, kind):
+    """torch_nfft::_nfft_ewald_excl_virial(Tensor pos, Tensor x, Tensor? batch, Tensor row_start, Tensor col, Tensor weight,
+    float[] box, float alpha, int kind) -> Tensor (not in the reference): ``[B, 7, *cols]`` float64, the listed pairs' share of
+    ``nfft_ewald_virial_near`` (``kind = 0``) or ``nfft_ewald_dispersion_virial_near`` (``kind = 1``) in their order, each pair
+    once: ``sum weight K0(r) x_i x_j`` and ``sum weight K1(r) d_a d_b x_i x_j`` (at ``r = 0`` the energy only).  Real ``x``;
+    ``box`` six numbers, ``pos`` FRACTIONAL.  One native call (``nfft_hip_ewald_excl_virial``), no
+    atomics: two calls give the same bits."""
+    return _ops._nfft_ewald_excl_virial(pos, x, batch, row_start, col, weight, [float(a) for a in box], float(alpha), int(kind))
+
+
 class _on_device:
     """The coefficient operators create their output on the current device (like the reference, which has no
     device argument); ``device=`` selects it for the duration of the call."""
