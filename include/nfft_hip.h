@@ -655,6 +655,35 @@ int nfft_hip_ewald_excl_virial(const nfft_hip_ewald_excl_problem *p, const float
                                const int32_t *row_start, const int32_t *col, const float *weight, const int32_t *set_start,
                                double *out, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- Ewald sum of the screened Coulomb (Yukawa) potential exp(-lambda r) / r (no reference counterpart) ----
+ * The sum of q_j exp(-lambda r) / r over all images is split with beta = lambda / (2 alpha): the smooth part is summed on the
+ * whole torus with nfft_hip_fastsum (coefficients 4 pi exp(-K / (4 alpha^2)) / (V K), K = 4 pi^2 |kappa|^2 + lambda^2, k = 0
+ * included unless the caller wants the one-component-plasma background; set up by the host side), and the first two entry
+ * points add the short-ranged rest:
+ *     z[i, c]        = sum_{j in the point set of i, 0 < r_ij < r_cut} w(r_ij) xr[j, c]
+ *     field[i, a, c] = sum_j mg(r_ij) d_ij[a] xr[j, c]                    (with_field = 1; minus the gradient)
+ *     w  = (P + M) / (2 r),   P = exp(lambda r) erfc(alpha r + beta),   M = exp(-lambda r) erfc(alpha r - beta)
+ *     mg = -w'(r) / r = (w + lambda (M - P) / 2 + (2 alpha / sqrt(pi)) exp(-alpha^2 r^2 - beta^2)) / r^2
+ * on the unit torus and in a box.  The third is the pair part of the virial of U = 1/2 sum_i q_i phi_i at fixed lambda,
+ *     out[b, 0, c] = 1/2 sum_{i in set b} xr[i, c] sum_{j: 0 < r_ij < r_cut} w(r_ij) xr[j, c]
+ *     out[b, e, c] = 1/2 sum_i xr[i, c] sum_j mg(r_ij) d_ij[a] d_ij[b] xr[j, c]        (xx, yy, zz, yz, xz, xy)
+ * in float64 [batch_size, 7, columns]; the spectral part is nfft_hip_ewald_dispersion_virial_far with the grids b_k and
+ * t_k = -8 pi^2 b_k (1 / (4 alpha^2) + 1 / K), and the self and background terms are the caller's.
+ * Problem structs, arguments, the order of the points, validation, error codes, determinism and workspaces are EXACTLY those
+ * of nfft_hip_ewald_near, nfft_hip_ewald_near_box and nfft_hip_ewald_virial_near, whose cell and workspace functions serve
+ * these too.  In addition screening = lambda must be finite, >= 0 and at most 50 / r_cut ("Input mismatch: ... screening ...",
+ * checked before anything else, also for an empty problem): past it exp(-lambda r_cut) / r_cut is below exp(-50) / r_cut and
+ * float32 exponentials of lambda r run out of range at 88.  screening = 0 gives the Coulomb weights erfc(alpha r) / r. */
+int nfft_hip_ewald_yukawa_near(const nfft_hip_ewald_problem *p, const float *points, const float *xr, const int32_t *start,
+                               const int64_t *index, double screening, float *z, float *field, void *workspace,
+                               int64_t workspace_bytes, void *stream);
+int nfft_hip_ewald_yukawa_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                                   const int32_t *start, const int64_t *index, double screening, float *z, float *field,
+                                   void *workspace, int64_t workspace_bytes, void *stream);
+int nfft_hip_ewald_yukawa_virial_near(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                                      const int32_t *start, double screening, double *out, void *workspace,
+                                      int64_t workspace_bytes, void *stream);
+
 /* Coefficient set-up (csrc/cuda/kernel_coeffs.cu, drivers core_cuda.cu:855-1064).  Outputs are [N]^dim
  * arrays, index l + N/2 on every axis.
  *   gaussian_analytic_coeffs      float32:  prod_d sqrt(pi) sigma exp(-sigma^2 pi^2 l_d^2)      (kernel_coeffs.cu:6-30)

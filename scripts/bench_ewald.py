@@ -80,6 +80,14 @@ water model) in the unit cube or in the box: the list kernel alone (nfft_hip_ewa
 operator around it beside the pair sweep with its field and beside the whole nfft_ewald(field=True) with and without the
 list, and the bytes the list kernel must move (row_start, col, weights, the gathered positions and values, the outputs) as a
 share of the HBM's specified rate.
+
+    python scripts/bench_ewald.py --yukawa [--virial] [--screening 1.0] [...]
+
+times the screened Coulomb sum e^(-lambda r) / r in the unit cube on the same points, r_c, alpha and N,
+lambda = screening / r_c: nfft_ewald_yukawa without and with the field beside nfft_ewald; the near operator; and the pair
+loops (nfft_hip_ewald_yukawa_near on restated plumbing) beside the Coulomb pair loops on the same sorted points and cells,
+timed in turn.  With --virial a second row in the identity box: nfft_ewald_yukawa_virial beside nfft_ewald_yukawa(field=True),
+and the pair loop of nfft_hip_ewald_yukawa_virial_near beside the field loop and beside the Coulomb virial loop.
 """
 import argparse
 import ctypes
@@ -803,6 +811,111 @@ def run_exclusions(lib, n, args):
                       "with_list_over_without": round(t["whole_field_with_list"][0] / t["whole_field"][0], 4)}))
 
 
+def run_yukawa(lib, n, args):
+    """the screened Coulomb sum in the unit cube: the same points, r_c, alpha and N as `run`, lambda =
+    args.screening / r_c; with --virial its virial tensor in the identity box as well"""
+    m = 4
+    r_c = min((3.0 * args.neighbours / (4.0 * math.pi * n)) ** (1.0 / 3.0), 1.0 / 3.0)
+    lam = args.screening / r_c
+    sp = tn.YukawaSplitting.from_tolerance(args.tol, r_c, lam)
+    ew = tn.EwaldSplitting.from_tolerance(args.tol, r_c)
+    rng = np.random.default_rng(0)
+    v = (rng.random((n, 3)) - 0.5).astype(np.float32)
+    v[v >= 0.5] = -0.5  # (rounded up to the face: the same point)
+    pos = torch.from_numpy(v).cuda()
+    q = torch.from_numpy(rng.standard_normal(n).astype(np.float32)).cuda()
+    G, N = int(lib.nfft_hip_ewald_near_cells(r_c, 1)), sp.bandwidth
+    wrapped, _ = pairs_tested(v, G)
+    whole = alternating_ms({
+        "coulomb": lambda: tn.nfft_ewald(q, pos, splitting=ew, cutoff=m),
+        "coulomb_field": lambda: tn.nfft_ewald(q, pos, splitting=ew, cutoff=m, field=True),
+        "yukawa": lambda: tn.nfft_ewald_yukawa(q, pos, splitting=sp, cutoff=m),
+        "yukawa_field": lambda: tn.nfft_ewald_yukawa(q, pos, splitting=sp, cutoff=m, field=True),
+        "near_op": lambda: tn.ops.nfft_ewald_yukawa_near(pos, q, None, (), sp.alpha, r_c, lam, False),
+        "near_op_field": lambda: tn.ops.nfft_ewald_yukawa_near(pos, q, None, (), sp.alpha, r_c, lam, True)}, args.reps)
+    # the pair loops on their own, on the same sorted points and cells: the same pairs are tested and the same pass the cut
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    spos, order, start = cell_order(pos, G, 0.5, G)
+    xs = q.index_select(0, order).reshape(n, 1).contiguous()
+    z, f = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+    zc, fc = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+    ps = {w: _lib.EwaldProblem(cells_per_axis=G, with_field=w, num_points=n, num_columns=1, batch_size=1, alpha=sp.alpha, r_cut=r_c)
+          for w in (0, 1)}
+    nbytes = lib.nfft_hip_ewald_near_workspace_bytes(ctypes.byref(ps[1]))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+
+    def yukawa_loop(w):
+        _lib.check(lib.nfft_hip_ewald_yukawa_near(ctypes.byref(ps[w]), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                                  order.data_ptr(), lam, z.data_ptr(), f.data_ptr(), ws.data_ptr(), nbytes, stream))
+
+    def coulomb_loop(w):
+        _lib.check(lib.nfft_hip_ewald_near(ctypes.byref(ps[w]), spos.data_ptr(), xs.data_ptr(), start.data_ptr(), order.data_ptr(),
+                                           zc.data_ptr(), fc.data_ptr(), ws.data_ptr(), nbytes, stream))
+
+    loops = alternating_ms({"coulomb": lambda: coulomb_loop(0), "coulomb_field": lambda: coulomb_loop(1),
+                            "yukawa": lambda: yukawa_loop(0), "yukawa_field": lambda: yukawa_loop(1)}, args.reps)
+    zo, fo = tn.ops.nfft_ewald_yukawa_near(pos, q, None, (), sp.alpha, r_c, lam, True)
+    assert torch.equal(zo, z[:, 0]) and torch.equal(fo, f), "the restated plumbing must give the operator's bits"
+    tn.ops.check_status()
+    ms = lambda t: [round(e, 4) for e in t]  # noqa: E731
+    print(json.dumps({"bench": "ewald_yukawa", "points": n, "neighbours": args.neighbours, "tol": args.tol, "r_cut": round(r_c, 5),
+                      "alpha": round(sp.alpha, 3), "N": N, "m": m, "cells_per_axis": G, "screening": round(lam, 4),
+                      "screening_r_cut": args.screening, "reps": args.reps,
+                      "median_min_max_ms": {"whole": {k: ms(t) for k, t in whole.items()},
+                                            "pair_loop": {k: ms(t) for k, t in loops.items()}},
+                      "pairs_tested": wrapped,
+                      "ps_per_pair": {k: round(t[0] * 1e9 / wrapped, 3) for k, t in loops.items()},
+                      "yukawa_over_coulomb_loop": round(loops["yukawa"][0] / loops["coulomb"][0], 3),
+                      "yukawa_over_coulomb_field_loop": round(loops["yukawa_field"][0] / loops["coulomb_field"][0], 3),
+                      "yukawa_over_coulomb_whole": round(whole["yukawa"][0] / whole["coulomb"][0], 3),
+                      "yukawa_over_coulomb_whole_field": round(whole["yukawa_field"][0] / whole["coulomb_field"][0], 3)}))
+    if not args.virial:
+        return
+    box = [1.0, 0.0, 1.0, 0.0, 0.0, 1.0]
+    spb = tn.YukawaSplitting.from_tolerance(args.tol, r_c, lam, box=[1.0, 1.0, 1.0])
+    Gb = spb.cells
+    spos, order, start = box_cell_order(pos, Gb)
+    xs = q.index_select(0, order).reshape(n, 1).contiguous()
+    pb = _lib.EwaldBoxProblem(cells=(ctypes.c_int32 * 3)(*Gb), with_field=1, num_points=n, num_columns=1, batch_size=1,
+                              alpha=spb.alpha, r_cut=r_c, box=(ctypes.c_double * 6)(*box))
+    nbytes = lib.nfft_hip_ewald_near_box_workspace_bytes(ctypes.byref(pb))
+    vbytes = lib.nfft_hip_ewald_virial_near_workspace_bytes(ctypes.byref(pb))
+    assert nbytes > 0 and vbytes > 0, _lib.last_error()
+    ws, vws = torch.empty(nbytes, dtype=torch.uint8, device="cuda"), torch.empty(vbytes, dtype=torch.uint8, device="cuda")
+    seven = torch.zeros(1, 7, 1, dtype=torch.float64, device="cuda")
+
+    def field_loop():
+        _lib.check(lib.nfft_hip_ewald_yukawa_near_box(ctypes.byref(pb), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                                      order.data_ptr(), lam, z.data_ptr(), f.data_ptr(), ws.data_ptr(), nbytes,
+                                                      stream))
+
+    def virial_loop():
+        _lib.check(lib.nfft_hip_ewald_yukawa_virial_near(ctypes.byref(pb), spos.data_ptr(), xs.data_ptr(), start.data_ptr(), lam,
+                                                         seven.data_ptr(), vws.data_ptr(), vbytes, stream))
+
+    def coulomb_virial_loop():
+        _lib.check(lib.nfft_hip_ewald_virial_near(ctypes.byref(pb), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                                  seven.data_ptr(), vws.data_ptr(), vbytes, stream))
+
+    t = alternating_ms({
+        "yukawa_field": lambda: tn.nfft_ewald_yukawa(q, pos, splitting=spb, cutoff=m, field=True, fractional=True),
+        "yukawa_virial": lambda: tn.nfft_ewald_yukawa_virial(q, pos, splitting=spb, cutoff=m, fractional=True),
+        "field_loop": field_loop, "coulomb_virial_loop": coulomb_virial_loop, "virial_loop": virial_loop}, args.reps)
+    assert torch.equal(tn.ops.nfft_ewald_yukawa_virial_near(pos, q, None, box, spb.alpha, r_c, lam), seven[:, :, 0]), \
+        "the restated plumbing must give the operator's bits"
+    tn.ops.check_status()
+    tested = box_pairs_tested(v, Gb)
+    print(json.dumps({"bench": "ewald_yukawa_virial", "box": box, "points": n, "neighbours": args.neighbours, "tol": args.tol,
+                      "r_cut": round(r_c, 5), "alpha": round(spb.alpha, 3), "N": spb.bandwidth, "m": m, "cells": list(Gb),
+                      "screening": round(lam, 4), "reps": args.reps,
+                      "median_min_max_ms": {k: ms(e) for k, e in t.items()}, "pairs_tested": tested,
+                      "ps_per_pair_field": round(t["field_loop"][0] * 1e9 / tested, 3),
+                      "ps_per_pair_virial": round(t["virial_loop"][0] * 1e9 / tested, 3),
+                      "virial_over_field": round(t["yukawa_virial"][0] / t["yukawa_field"][0], 3),
+                      "virial_loop_over_field_loop": round(t["virial_loop"][0] / t["field_loop"][0], 3),
+                      "virial_loop_over_coulomb_virial_loop": round(t["virial_loop"][0] / t["coulomb_virial_loop"][0], 3)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, nargs="+", default=[100000, 1000000])
@@ -819,9 +932,15 @@ def main():
     ap.add_argument("--phi", type=float, default=0.1, help="--rpy: the volume fraction of the spheres, n (4/3) pi a^3")
     ap.add_argument("--exclusions", action="store_true",
                     help="time the bonded-pair correction on rigid triples (the unit cube, or --box) instead")
+    ap.add_argument("--yukawa", action="store_true", help="time the screened Coulomb sum (unit cube) instead; with --virial its virial too")
+    ap.add_argument("--screening", type=float, default=1.0, help="--yukawa: lambda r_c, the screening parameter times r_c")
     args = ap.parse_args()
     if args.box is not None and len(args.box) not in (3, 6):
         ap.error("--box takes three or six comma-separated numbers")
+    if args.yukawa and (args.box is not None or args.dispersion or args.dipole or args.stokeslet or args.rpy or args.exclusions):
+        ap.error("--yukawa times the unit cube on its own (with or without --virial)")
+    if args.yukawa and not 0.0 < args.screening <= 50.0:
+        ap.error("--screening is lambda r_c and must lie in (0, 50]")
     if args.exclusions and (args.dispersion or args.virial or args.dipole or args.stokeslet or args.rpy):
         ap.error("--exclusions times the Coulomb sum's correction on its own (with or without --box)")
     if args.dispersion and args.box is not None:
@@ -835,6 +954,9 @@ def main():
     torch.cuda.set_device(0)
     lib = _lib.load()
     for n in args.points:
+        if args.yukawa:
+            run_yukawa(lib, n, args)
+            continue
         if args.exclusions:
             run_exclusions(lib, n, args)
             continue

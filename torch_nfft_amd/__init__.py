@@ -28,6 +28,8 @@ from .stokeslet import (nfft_ewald_stokeslet, nfft_ewald_stokeslet_power, stokes
                         NfftEwaldStokesletFunction)
 from .rpy import nfft_ewald_rpy, nfft_ewald_rpy_power, rpy_coeffs, rpy_splitting, NfftEwaldRpyFunction  # noqa: E402
 from .exclusions import ExclusionList  # noqa: E402
+from .yukawa import (YukawaSplitting, nfft_ewald_yukawa, nfft_ewald_yukawa_energy, NfftEwaldYukawaFunction,  # noqa: E402
+                     nfft_ewald_yukawa_virial)
 from .matrices import GramMatrix, AdjacencyMatrix  # noqa: E402
 from .kernel import GaussianKernel  # noqa: E402
 from . import utils  # noqa: E402
@@ -42,6 +44,8 @@ __all__ = ["nfft_adjoint", "nfft_forward", "nfft_fastsum", "nfft_toeplitz_kernel
            "nfft_ewald_dispersion_virial", "nfft_ewald_dipole", "nfft_ewald_dipole_energy", "NfftEwaldDipoleFunction",
            "nfft_ewald_stokeslet", "nfft_ewald_stokeslet_power", "stokeslet_splitting", "NfftEwaldStokesletFunction",
            "nfft_ewald_rpy", "nfft_ewald_rpy_power", "rpy_coeffs", "rpy_splitting", "NfftEwaldRpyFunction", "ExclusionList",
+           "YukawaSplitting", "nfft_ewald_yukawa", "nfft_ewald_yukawa_energy", "NfftEwaldYukawaFunction",
+           "nfft_ewald_yukawa_virial",
            "ndft_forward", "ndft_adjoint", "ndft_fastsum",
            "exact_trigonometric_matrix", "exact_gaussian_matrix", "NfftAdjointFunction", "NfftForwardFunction",
            "NfftFastsumFunction", "gaussian_analytic_coeffs", "gaussian_interpolated_coeffs", "interpolation_grid",

@@ -83,6 +83,9 @@ SYMBOLS = (
     "nfft_hip_ewald_excl_box",
     "nfft_hip_ewald_excl_virial_workspace_bytes",
     "nfft_hip_ewald_excl_virial",
+    "nfft_hip_ewald_yukawa_near",
+    "nfft_hip_ewald_yukawa_near_box",
+    "nfft_hip_ewald_yukawa_virial_near",
     "nfft_hip_gaussian_analytic_coeffs",
     "nfft_hip_interpolation_grid",
     "nfft_hip_coeffs_workspace_bytes",
@@ -327,6 +330,12 @@ def load():
     lib.nfft_hip_ewald_excl_virial_workspace_bytes.restype = i64
     lib.nfft_hip_ewald_excl_virial.argtypes = [ctypes.POINTER(EwaldExclProblem), vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.nfft_hip_ewald_excl_virial.restype = ci
+    lib.nfft_hip_ewald_yukawa_near.argtypes = [ctypes.POINTER(EwaldProblem), vp, vp, vp, vp, ctypes.c_double, vp, vp, vp, i64, vp]
+    lib.nfft_hip_ewald_yukawa_near.restype = ci
+    lib.nfft_hip_ewald_yukawa_near_box.argtypes = [ctypes.POINTER(EwaldBoxProblem), vp, vp, vp, vp, ctypes.c_double, vp, vp, vp, i64, vp]
+    lib.nfft_hip_ewald_yukawa_near_box.restype = ci
+    lib.nfft_hip_ewald_yukawa_virial_near.argtypes = [ctypes.POINTER(EwaldBoxProblem), vp, vp, vp, ctypes.c_double, vp, vp, i64, vp]
+    lib.nfft_hip_ewald_yukawa_virial_near.restype = ci
     lib.nfft_hip_gaussian_analytic_coeffs.argtypes = [ctypes.c_double, i64, ctypes.c_int32, vp, vp]
     lib.nfft_hip_gaussian_analytic_coeffs.restype = ci
     lib.nfft_hip_interpolation_grid.argtypes = [i64, ctypes.c_int32, ci, vp, vp]

@@ -603,9 +603,11 @@ int64_t nfft_hip_ewald_virial_near_workspace_bytes(const nfft_hip_ewald_box_prob
 // (`launch`: the pair reduction of the Coulomb sum, or that of the dispersion sum on the same problem, section 7k)
 typedef int (*virial_near_launch)(const nfft_hip_ewald_box_problem *, const float *, const float *, const int *, double *, void *,
                                   hipStream_t);
-static int virial_near_call(virial_near_launch launch, const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
-                            const int32_t *start, double *out, void *workspace, int64_t workspace_bytes, void *stream)
+// the checks of a pair reduction, in their order; *ws: the aligned workspace, or null where there is nothing to launch
+static int virial_near_checks(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr, const int32_t *start,
+                              double *out, void *workspace, int64_t workspace_bytes, void *stream, char **ws)
 {
+    *ws = nullptr;
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate_virial_near(p)) return rc;
     if (p->num_columns == 0) return 0;
@@ -615,8 +617,16 @@ static int virial_near_call(virial_near_launch launch, const nfft_hip_ewald_box_
         return 0;
     }
     if (!points || !xr || !start) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    char *ws = workspace_base(workspace, workspace_bytes, virial_near_need(p));
-    if (!ws) return NFFT_HIP_EWORKSPACE;
+    *ws = workspace_base(workspace, workspace_bytes, virial_near_need(p));
+    return *ws ? 0 : NFFT_HIP_EWORKSPACE;
+}
+
+static int virial_near_call(virial_near_launch launch, const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                            const int32_t *start, double *out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    char *ws;
+    if (int rc = virial_near_checks(p, points, xr, start, out, workspace, workspace_bytes, stream, &ws)) return rc;
+    if (!ws) return 0;
     return launch(p, points, xr, start, out, ws, (hipStream_t)stream);
 }
 
@@ -706,6 +716,67 @@ int nfft_hip_ewald_dispersion_virial_far(int64_t N, int64_t batch_size, int64_t 
     if (!ws) return NFFT_HIP_EWORKSPACE;
     return launch_ewald_dispersion_virial_far(N, batch_size, num_columns, band, coeffs, strain_coeffs, box_inverse, out, ws,
                                               (hipStream_t)stream);
+}
+
+// ---- Ewald sum of the screened Coulomb potential: the same problems, checks and workspaces --------
+// the screening parameter: finite, not negative, and lambda r_cut <= 50 (float32 exponentials of lambda r leave their range at 88,
+// and at 50 the pair weight at the cut is below e^-50 / r_cut); the product is checked once the problem's own r_cut has been (r_cut == nullptr: not yet)
+static int check_screening(double screening, const double *r_cut)
+{
+    if (!(screening >= 0.0) || !(screening < 1e300)) {
+        set_error("Input mismatch: screening must be finite and >= 0");
+        return NFFT_HIP_EINVAL;
+    }
+    if (r_cut && !(screening * *r_cut <= 50.0)) {
+        set_error("Input mismatch: screening * r_cut <= 50 is required");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+// (In the three entry points below take_pending_fault and the problem's validation run here, so that the screening is judged
+// before the shared checks return early on an empty problem, and once more inside those checks.  The repetition is
+// deliberate: the first non-zero return leaves, a taken fault is not reported twice, and the validation only reads.)
+int nfft_hip_ewald_yukawa_near(const nfft_hip_ewald_problem *p, const float *points, const float *xr, const int32_t *start,
+                               const int64_t *index, double screening, float *z, float *field, void *workspace,
+                               int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = check_screening(screening, nullptr)) return rc;
+    if (int rc = validate_ewald(p)) return rc;
+    if (int rc = check_screening(screening, &p->r_cut)) return rc;
+    char *ws;
+    if (int rc = ewald_near_checks(p, points, xr, start, index, z, field, workspace, workspace_bytes, &ws)) return rc;
+    if (!ws) return 0;
+    return launch_ewald_yukawa_near(p, screening, points, xr, start, index, z, field, ws, (hipStream_t)stream);
+}
+
+int nfft_hip_ewald_yukawa_near_box(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                                   const int32_t *start, const int64_t *index, double screening, float *z, float *field,
+                                   void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = check_screening(screening, nullptr)) return rc;
+    if (int rc = validate_ewald_box(p)) return rc;
+    if (int rc = check_screening(screening, &p->r_cut)) return rc;
+    char *ws;
+    if (int rc = ewald_near_box_checks(p, points, xr, start, index, z, field, workspace, workspace_bytes, &ws)) return rc;
+    if (!ws) return 0;
+    return launch_ewald_yukawa_near_box(p, screening, points, xr, start, index, z, field, ws, (hipStream_t)stream);
+}
+
+int nfft_hip_ewald_yukawa_virial_near(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr,
+                                      const int32_t *start, double screening, double *out, void *workspace,
+                                      int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = check_screening(screening, nullptr)) return rc;
+    if (int rc = validate_virial_near(p)) return rc;
+    if (int rc = check_screening(screening, &p->r_cut)) return rc;
+    char *ws;
+    if (int rc = virial_near_checks(p, points, xr, start, out, workspace, workspace_bytes, stream, &ws)) return rc;
+    if (!ws) return 0;
+    return launch_ewald_yukawa_virial_near(p, screening, points, xr, start, out, ws, (hipStream_t)stream);
 }
 
 // ---- bonded-pair exclusions of the Coulomb and dispersion Ewald sums ----------------------------

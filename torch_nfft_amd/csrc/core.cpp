@@ -1000,8 +1000,9 @@ std::tuple<at::Tensor, at::Tensor> ewald_result(const EwaldInput &in, const at::
 // image d_ij of pos_i - pos_j on the unit torus, x's type and shape; with_field: f[i, a] = -sum_j g(r_ij^2) d_ij[a] x[j],
 // [n, 3, *cols] (g = K'(r) / r of K = erfc(alpha r) / r), otherwise f is empty.  pos may hold any real values: they are
 // taken modulo 1.
-// (`sweep`: nfft_hip_ewald_near, or the dispersion sum's pair weights on the same problem, section 7j)
-using EwaldSweep = decltype(&nfft_hip_ewald_near);
+// (`sweep`: nfft_hip_ewald_near, or the dispersion sum's pair weights on the same problem, section 7j, or a closure with
+// these arguments that binds the screening of section 7p)
+template <class EwaldSweep>
 std::tuple<at::Tensor, at::Tensor> ewald_near_op(EwaldSweep sweep, const at::Tensor &pos, const at::Tensor &x,
                                                  const c10::optional<at::Tensor> &opt_batch, double alpha, double r_cut,
                                                  bool with_field)
@@ -1045,7 +1046,7 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_near(at::Tensor pos, at::Tensor x,
 // ---- the same pair sum in an orthorhombic or triclinic box (not in the reference) ---------------
 // (z, f) of nfft_ewald_near in the box A = box (A00, A10, A11, A20, A21, A22; rows = lattice vectors): pos holds FRACTIONAL
 // coordinates, taken modulo 1; r_ij is the length of d_ij = (ds - rint(ds)) A and f is Cartesian.
-using EwaldBoxSweep = decltype(&nfft_hip_ewald_near_box);
+template <class EwaldBoxSweep>
 std::tuple<at::Tensor, at::Tensor> ewald_near_box_op(EwaldBoxSweep sweep, const at::Tensor &pos, const at::Tensor &x,
                                                      const c10::optional<at::Tensor> &opt_batch, const std::vector<double> &box,
                                                      double alpha, double r_cut, bool with_field)
@@ -1099,8 +1100,9 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_dispersion_near_box(at::Tensor pos
 // [B, 7, *cols] float64: per point set and column the near part of the energy and of the virial W_ab = -dU / d eps_ab
 // (xx, yy, zz, yz, xz, xy) of the real charges x at the FRACTIONAL positions pos in the box A = box, taken modulo 1 and
 // ordered by cell exactly as nfft_ewald_near_box does
-// (`reduce`: nfft_hip_ewald_virial_near, or the dispersion sum's pair weights on the same problem, section 7k)
-using VirialNearReduce = decltype(&nfft_hip_ewald_virial_near);
+// (`reduce`: nfft_hip_ewald_virial_near, or the dispersion sum's pair weights on the same problem, section 7k, or a closure
+// with these arguments that binds the screening of section 7p)
+template <class VirialNearReduce>
 at::Tensor virial_near_op(VirialNearReduce reduce, const at::Tensor &pos, const at::Tensor &x,
                           const c10::optional<at::Tensor> &opt_batch, const std::vector<double> &box, double alpha, double r_cut)
 {
@@ -1357,6 +1359,42 @@ at::Tensor nfft_ewald_rpy_near(at::Tensor pos, at::Tensor f, c10::optional<at::T
     return packed_near(kRpySum, near, near_box, pos, f, batch, box, alpha, r_cut, order);
 }
 
+// ---- Ewald sum of the screened Coulomb potential e^(-lambda r) / r (not in the reference) -------------
+// (z, f) as nfft_ewald_near (an empty box: the unit torus) and nfft_ewald_near_box (six numbers) with the pair weights of
+// nfft_hip_ewald_yukawa_near, lambda = screening: z[i] = sum_j w(r_ij) x[j], f[i, a] = sum_j (-w'(r_ij) / r_ij) d_ij[a] x[j]
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_yukawa_near(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch,
+                                                          std::vector<double> box, double alpha, double r_cut, double screening,
+                                                          bool with_field)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_yukawa_near is currently only implemented for GPU tensors");
+    CHECK_INPUT(box.empty() || box.size() == 6);
+    if (box.empty()) {
+        const auto sweep = [screening](const nfft_hip_ewald_problem *p, const float *points, const float *xr, const int32_t *start,
+                                       const int64_t *index, float *z, float *f, void *ws, int64_t ws_bytes, void *stream) {
+            return nfft_hip_ewald_yukawa_near(p, points, xr, start, index, screening, z, f, ws, ws_bytes, stream);
+        };
+        return ewald_near_op(sweep, pos, x, opt_batch, alpha, r_cut, with_field);
+    }
+    const auto sweep = [screening](const nfft_hip_ewald_box_problem *p, const float *points, const float *xr, const int32_t *start,
+                                   const int64_t *index, float *z, float *f, void *ws, int64_t ws_bytes, void *stream) {
+        return nfft_hip_ewald_yukawa_near_box(p, points, xr, start, index, screening, z, f, ws, ws_bytes, stream);
+    };
+    return ewald_near_box_op(sweep, pos, x, opt_batch, box, alpha, r_cut, with_field);
+}
+
+// [B, 7, *cols] float64 as nfft_ewald_virial_near with the same pair weights (w and mg = -w'(r) / r); the far part is
+// nfft_ewald_dispersion_virial_far with the splitting's two grids
+at::Tensor nfft_ewald_yukawa_virial_near(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch, std::vector<double> box,
+                                         double alpha, double r_cut, double screening)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_yukawa_virial_near is currently only implemented for GPU tensors");
+    const auto reduce = [screening](const nfft_hip_ewald_box_problem *p, const float *points, const float *xr, const int32_t *start,
+                                    double *out, void *ws, int64_t ws_bytes, void *stream) {
+        return nfft_hip_ewald_yukawa_virial_near(p, points, xr, start, screening, out, ws, ws_bytes, stream);
+    };
+    return virial_near_op(reduce, pos, x, opt_batch, box, alpha, r_cut);
+}
+
 // ---- bonded-pair exclusions of the Coulomb and dispersion Ewald sums (not in the reference) ------
 // The list's CSR arrays as the native calls take them, checked against the points
 struct ExclInput { at::Tensor row_start, col, weight; };
@@ -1607,6 +1645,11 @@ TORCH_LIBRARY(torch_nfft, m)
     // not in the reference: the pair sweep of the periodic Rotne-Prager-Yamakawa sum (nfft_ewald_rpy)
     m.def("_nfft_ewald_rpy_near(Tensor pos, Tensor f, Tensor? batch, float[] box, float alpha, float r_cut, float radius, "
           "int order) -> Tensor", &nfft_ewald_rpy_near);
+    // not in the reference: the pair sweep and the pair reduction of the screened Coulomb (Yukawa) Ewald sum (nfft_ewald_yukawa)
+    m.def("_nfft_ewald_yukawa_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut, float screening, "
+          "bool with_field) -> (Tensor, Tensor)", &nfft_ewald_yukawa_near);
+    m.def("_nfft_ewald_yukawa_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut, "
+          "float screening) -> Tensor", &nfft_ewald_yukawa_virial_near);
     // not in the reference: what a list of bonded pairs takes out of the Coulomb and dispersion Ewald sums and their virials
     m.def("_nfft_ewald_excl(Tensor pos, Tensor x, Tensor? batch, Tensor row_start, Tensor col, Tensor weight, float[] box, "
           "float alpha, int kind, bool with_field) -> (Tensor, Tensor)", &nfft_ewald_excl);

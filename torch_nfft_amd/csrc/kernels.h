@@ -241,6 +241,15 @@ int launch_ewald_dispersion_virial_near(const nfft_hip_ewald_box_problem *p, con
 int launch_ewald_dispersion_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
                                        const float *strain_coeffs, const double *box_inverse, double *out, void *workspace,
                                        hipStream_t stream);
+// ewald_yukawa.hip (the Ewald sum of the screened Coulomb potential e^(-lambda r) / r): the wrapped pair
+// sum and its field, arguments and `items` as launch_ewald_near / launch_ewald_near_box (the same item slots), and the pair
+// part of its virial, arguments and `workspace` as launch_ewald_virial_near; `screening` is lambda
+int launch_ewald_yukawa_near(const nfft_hip_ewald_problem *p, double screening, const float *pos, const float *xr, const int *start,
+                             const int64_t *index, float *z, float *f, void *items, hipStream_t stream);
+int launch_ewald_yukawa_near_box(const nfft_hip_ewald_box_problem *p, double screening, const float *pos, const float *xr,
+                                 const int *start, const int64_t *index, float *z, float *f, void *items, hipStream_t stream);
+int launch_ewald_yukawa_virial_near(const nfft_hip_ewald_box_problem *p, double screening, const float *pos, const float *xr,
+                                    const int *start, double *out, void *workspace, hipStream_t stream);
 // ewald_excl.hip (bonded-pair exclusions of the Coulomb and dispersion Ewald sums): the list kernel on
 // the unit torus and in a box, arguments as nfft_hip_ewald_excl / _box; and the listed pairs' share of the virial, arguments
 // as nfft_hip_ewald_excl_virial, `workspace`: ewald_excl_virial_workspace(p) bytes, 8-byte aligned (one partial per workgroup;

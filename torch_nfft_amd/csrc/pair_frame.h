@@ -1,5 +1,5 @@
 // The frame of the pair kernels: nearfield.hip (the open grid of the fast summation), ewald_near.hip,
-// ewald_disp.hip, ewald_dipole.hip, ewald_stokeslet.hip and the pair kernels of ewald_virial.hip and ewald_disp_virial.hip (the wrapped grid of the Ewald sums) stand on all of it, nearfield_pgrad.hip on all
+// ewald_disp.hip, ewald_dipole.hip, ewald_stokeslet.hip, ewald_yukawa.hip and the pair kernels of ewald_virial.hip and ewald_disp_virial.hip (the wrapped grid of the Ewald sums) stand on all of it, nearfield_pgrad.hip on all
 // but the tile sweep, nearfield_grad.hip on the host dispatch only (section 7d says why).
 // Both point sets come ordered by (point set, cell) with a start table.  A workgroup owns one work item -- up to kNearBlock
 // output points of one cell -- and a lane one output point; a walk hands the contiguous ranges of streamed points of the
@@ -284,6 +284,48 @@ struct DispersionPairWeight {
         w = e * ((0.5f * a2 + 1.f) * a2 + 1.f) * ir6;
     }
     __device__ __forceinline__ float mg() const { return e * (((a2 + 3.f) * a2 + 6.f) * a2 + 6.f) * (ir6 * ir2); }
+};
+
+// the constants of the Yukawa pair weight beside EwaldPairParams: the screening parameter lambda,
+// beta = lambda / (2 alpha), e^(-beta^2) and (2 alpha / sqrt(pi)) e^(-beta^2)
+struct YukawaPairParams {
+    float lambda, beta, ebeta, gslope;
+};
+
+inline YukawaPairParams yukawa_pair_params(double alpha, double screening)
+{
+    const double beta = screening / (2.0 * alpha);
+    YukawaPairParams y;
+    y.lambda = (float)screening;
+    y.beta = (float)beta;
+    y.ebeta = (float)std::exp(-beta * beta);
+    y.gslope = (float)(2.0 * alpha / 1.7724538509055160273 * std::exp(-beta * beta));
+    return y;
+}
+
+// the pair weights of the screened Coulomb sum e^(-lambda r) / r from rr = r^2 > 0, with
+// P = e^(lambda r) erfc(alpha r + beta) and M = e^(-lambda r) erfc(alpha r - beta): w = (P + M) / (2 r), and on request its
+// negated slope mg = -w'(r) / r = (w + lambda (M - P) / 2 + g) / r^2, g = (2 alpha / sqrt(pi)) e^(-alpha^2 r^2 - beta^2); M >= P, so the
+// three terms are positive and nothing cancels.  At lambda = 0 these are EwaldPairWeight's.
+// A mixed form: M as written (erfcf takes a negative argument as it is), but P = e^(-alpha^2 r^2 - beta^2) erfcx(alpha r + beta),
+// which is the same number since (alpha r + beta)^2 = alpha^2 r^2 + beta^2 + lambda r.  The plain product loses P where
+// erfc(alpha r + beta) leaves float32 (alpha r + beta > 9.2, e.g. alpha r = beta = 4.6, lambda r = 42) although P is still 6 % of M
+// there, and overflows past lambda r = 88; this one does neither, its erfcx argument is positive (the all-erfcx form would need
+// erfcx at alpha r - beta < 0, a growing exponential again), and the exponential that it needs is the one g needs.  Cost: one
+// erfcf, one erfcxf, one rsqrtf, one expf (e^(-lambda r): its argument reaches 50, where the fast exponential's rounding of
+// lambda r log2(e) alone is 3e-6) and one __expf.  Section 7p has what a comparison with the plain form showed.
+struct YukawaPairWeight {
+    float w, ir, hd, e;  // hd = (M - P) / 2, e = e^(-alpha^2 r^2)
+    __device__ __forceinline__ YukawaPairWeight(float rr, const EwaldPairParams &q, const YukawaPairParams &y) : ir(rsqrtf(rr))
+    {
+        const float r = rr * ir, ar = q.alpha * r;
+        e = __expf(q.neg_alpha2 * rr);
+        const float P = y.ebeta * e * erfcxf(ar + y.beta);
+        const float M = expf(-y.lambda * r) * erfcf(ar - y.beta);
+        w = 0.5f * (P + M) * ir;
+        hd = 0.5f * (M - P);
+    }
+    __device__ __forceinline__ float mg(const YukawaPairParams &y) const { return (w + y.lambda * hd + y.gslope * e) * (ir * ir); }
 };
 
 // ---- float64 sum over a workgroup -------------------------------------------------------------------------------------

@@ -365,6 +365,38 @@ def nfft_ewald_excl_virial(pos, x, batch, row_start, col, weight, box, alpha, ki
     return _ops._nfft_ewald_excl_virial(pos, x, batch, row_start, col, weight, [float(a) for a in box], float(alpha), int(kind))
 
 
+def nfft_ewald_yukawa_near(pos, x, batch, box, alpha, r_cut, screening, with_field):
+    """torch_nfft::_nfft_ewald_yukawa_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut,
+    float screening, bool with_field) -> (Tensor, Tensor) (not in the reference): the near part of the Ewald sum of the screened
+    Coulomb potential ``e^(-lambda r) / r``, ``lambda = screening``, ``beta = lambda / (2 alpha)``::
+
+        z[i]    = sum_{j: 0 < r_ij < r_cut} w(r_ij) x[j]                 w  = (P + M) / (2 r)
+        f[i, a] = sum_{j: 0 < r_ij < r_cut} mg(r_ij) d_ij[a] x[j]        mg = -w'(r) / r = (w + lambda (M - P) / 2 + g) / r^2
+        P = e^(lambda r) erfc(alpha r + beta),  M = e^(-lambda r) erfc(alpha r - beta),  g = (2 alpha / sqrt(pi)) e^(-alpha^2 r^2 - beta^2)
+
+    ``f`` is minus the gradient, ``[n, 3, *cols]``, and empty unless ``with_field``.  ``box`` is ``()`` for the unit torus
+    (``nfft_ewald_near``'s arguments and positions) or the six numbers of ``nfft_ewald_near_box`` (``pos`` FRACTIONAL).
+    ``screening`` must be finite, ``>= 0`` and at most ``50 / r_cut`` ("Input mismatch"); at 0 the weights are the Coulomb
+    ones.  One native call (``nfft_hip_ewald_yukawa_near`` / ``_near_box``), no atomics: two calls give
+    the same bits."""
+    return _ops._nfft_ewald_yukawa_near(pos, x, batch, [float(a) for a in box], float(alpha), float(r_cut), float(screening),
+                                        bool(with_field))
+
+
+def nfft_ewald_yukawa_virial_near(pos, x, batch, box, alpha, r_cut, screening):
+    """torch_nfft::_nfft_ewald_yukawa_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut,
+    float screening) -> Tensor (not in the reference): ``nfft_ewald_virial_near`` for the screened Coulomb sum, ``[B, 7, *cols]``
+    float64 in the same order, with the pair weights of ``nfft_ewald_yukawa_near``::
+
+        out[b, 0] = 1/2 sum_{i in set b} x_i sum_{j: 0 < r_ij < r_cut} w(r_ij) x_j
+        out[b, e] = 1/2 sum_i x_i sum_j mg(r_ij) d_ij[a] d_ij[b] x_j               (xx, yy, zz, yz, xz, xy)
+
+    Arguments as there (``box`` always six numbers), ``screening`` as above.  One native call
+    (``nfft_hip_ewald_yukawa_virial_near``), no atomics: two calls give the same bits."""
+    return _ops._nfft_ewald_yukawa_virial_near(pos, x, batch, [float(a) for a in box], float(alpha), float(r_cut),
+                                               float(screening))
+
+
 class _on_device:
     """The coefficient operators create their output on the current device (like the reference, which has no
     device argument); ``device=`` selects it for the duration of the call."""
