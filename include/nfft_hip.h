@@ -524,6 +524,42 @@ int nfft_hip_ewald_dispersion_virial_far(int64_t N, int64_t batch_size, int64_t 
                                          const float *coeffs, const float *strain_coeffs, const double *box_inverse, double *out,
                                          void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- potential, field, energy and virial of the Ewald sum in one pass (no reference counterpart) ----
+ * What one constant-pressure step needs from the sum, without doing the walk over the pairs and the pass over the
+ * spectrum twice: nfft_hip_ewald_near_box with with_field = 1 and nfft_hip_ewald_virial_near in one pair kernel, and the
+ * coefficient product of the field's far part and nfft_hip_ewald_virial_far in one spectral kernel.  The sums, the order
+ * energy, xx, yy, zz, yz, xz, xy of the seven numbers, the checks, limits, error codes and workspaces are those of the
+ * Coulomb sum's entry points above (section 7i): nfft_hip_ewald_step_near_workspace_bytes returns what
+ * nfft_hip_ewald_virial_near_workspace_bytes does and nfft_hip_ewald_step_spectral_workspace_bytes what
+ * nfft_hip_ewald_virial_far_workspace_bytes does.  Real data only.
+ *
+ * nfft_hip_ewald_step_near: points, xr, start and index as for nfft_hip_ewald_near_box (with_field is not used and must be
+ * 0 or 1; the unit cube is the box 1, 0, 1, 0, 0, 1),
+ *     z[index[i], c]    = sum_{j: 0 < r_ij < r_cut} erfc(alpha r_ij) / r_ij  xr[j, c]              float32 [points, columns]
+ *     f[index[i], a, c] = sum_j (-g(r_ij^2)) d_ij[a] xr[j, c]                                       float32 [points, 3, columns]
+ *     out7[b, 0, c]     = 1/2 sum_{i in set b} xr[i, c] (the sum of z)                             float64 [batch_size, 7, columns]
+ *     out7[b, e, c]     = 1/2 sum_i xr[i, c] sum_j (-g(r_ij^2)) d_ij[a] d_ij[b] xr[j, c],
+ * the ten sums of a point and column kept side by side in float32 over one walk.  With no points out7 is set to zero;
+ * with no columns nothing is done.
+ *
+ * nfft_hip_ewald_step_spectral: band, coeffs, box_inverse and pi2_over_alpha2 as for nfft_hip_ewald_virial_far; it
+ * writes spectra [batch_size, N, N, N, 4, num_columns] complex64,
+ *     spectra[.., 0, c] = b_k band[.., c],   spectra[.., 1 + a, c] = 2 pi i kappa_a b_k band[.., c]
+ * (zeros where b_k = 0; 2 pi kappa is formed in float32 from the float64 box_inverse), whose forward transform is the far
+ * part of (phi, E) with the signs of the transforms, and out7 as nfft_hip_ewald_virial_far from the same read of band.
+ * band and spectra need the 8-byte alignment of complex64 only; when both are 16-byte aligned, cells of one, two or four
+ * columns move in 16-byte pieces.
+ *
+ * Two levels, float64 and no atomics as above: two calls give the same bits. */
+int64_t nfft_hip_ewald_step_near_workspace_bytes(const nfft_hip_ewald_box_problem *p);
+int nfft_hip_ewald_step_near(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr, const int32_t *start,
+                             const int64_t *index, float *z, float *f, double *out7, void *workspace, int64_t workspace_bytes,
+                             void *stream);
+int64_t nfft_hip_ewald_step_spectral_workspace_bytes(int64_t N, int64_t batch_size, int64_t num_columns);
+int nfft_hip_ewald_step_spectral(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
+                                 const double *box_inverse, double pi2_over_alpha2, void *spectra, double *out7, void *workspace,
+                                 int64_t workspace_bytes, void *stream);
+
 /* ---- Ewald sum of point charges and point dipoles (no reference counterpart) ----
  * Source j carries a charge q_j and a Cartesian dipole mu_j, packed as xs [points, 4, num_columns] = (q, mu_x, mu_y, mu_z).
  * With d = d_ij, r = |d|, m = mu_j . d and the Smith functions B_0 = erfc(alpha r) / r,

@@ -81,6 +81,15 @@ operator around it beside the pair sweep with its field and beside the whole nff
 list, and the bytes the list kernel must move (row_start, col, weights, the gathered positions and values, the outputs) as a
 share of the HBM's specified rate.
 
+    python scripts/bench_ewald.py --step [--box ...] [--exclusions] [...]
+
+times the fused step in the box (the identity box without --box) on uniform charges, one row per point
+count: nfft_ewald(field=True), nfft_ewald_virial, their sum and nfft_ewald_step; the two pair loops and the fused one on their
+own (nfft_hip_ewald_near_box, nfft_hip_ewald_virial_near and nfft_hip_ewald_step_near on restated plumbing, in picoseconds per
+tested pair); and the torch product with field_coeffs() plus ops.nfft_ewald_virial_far beside ops.nfft_ewald_step_spectral on
+the same band.  All are timed in turn, median, minimum and maximum of `reps` each.  With --exclusions the three public calls
+carry a list of the n / 2 pairs (2 i, 2 i + 1).
+
     python scripts/bench_ewald.py --yukawa [--virial] [--screening 1.0] [...]
 
 times the screened Coulomb sum e^(-lambda r) / r in the unit cube on the same points, r_c, alpha and N,
@@ -916,6 +925,94 @@ def run_yukawa(lib, n, args):
                       "virial_loop_over_coulomb_virial_loop": round(t["virial_loop"][0] / t["coulomb_virial_loop"][0], 3)}))
 
 
+def run_step(lib, n, args):
+    """the fused step beside the two calls, the two pair loops and the two spectral passes that it replaces"""
+    m = 4
+    box = [1.0, 0.0, 1.0, 0.0, 0.0, 1.0] if args.box is None else \
+        (args.box if len(args.box) == 6 else [args.box[0], 0.0, args.box[1], 0.0, 0.0, args.box[2]])
+    A = [[box[0], 0.0, 0.0], [box[1], box[2], 0.0], [box[3], box[4], box[5]]]
+    probe = tn.EwaldSplitting(1.0, 1e-3 * min(box[0], box[2], box[5]), 2, box=A, device="cpu")  # (volume and widths)
+    r_c = min((3.0 * args.neighbours * probe.volume / (4.0 * math.pi * n)) ** (1.0 / 3.0), min(probe.widths) / 3.0)
+    sp = tn.EwaldSplitting.from_tolerance(args.tol, r_c, box=A)
+    rng = np.random.default_rng(0)
+    v = (rng.random((n, 3)) - 0.5).astype(np.float32)
+    v[v >= 0.5] = -0.5  # (rounded up to the face: the same point)
+    pos = torch.from_numpy(v).cuda()
+    q = torch.from_numpy(rng.standard_normal(n).astype(np.float32)).cuda()
+    G, N = sp.cells, sp.bandwidth
+    tested = box_pairs_tested(v, G)
+    kw = {"splitting": sp, "cutoff": m, "fractional": True}
+    if args.exclusions:
+        even = 2 * np.arange(n // 2)
+        kw["exclusions"] = tn.ExclusionList(np.stack([even, even + 1], 1), n)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    spos, order, start = box_cell_order(pos, G)
+    xs = q.index_select(0, order).reshape(n, 1).contiguous()
+    z, f = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+    zs, fs = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda")
+    p = _lib.EwaldBoxProblem(cells=(ctypes.c_int32 * 3)(*G), with_field=1, num_points=n, num_columns=1, batch_size=1,
+                             alpha=sp.alpha, r_cut=r_c, box=(ctypes.c_double * 6)(*box))
+    nbytes = lib.nfft_hip_ewald_near_box_workspace_bytes(ctypes.byref(p))
+    vbytes = lib.nfft_hip_ewald_virial_near_workspace_bytes(ctypes.byref(p))
+    sbytes = lib.nfft_hip_ewald_step_near_workspace_bytes(ctypes.byref(p))
+    assert nbytes > 0 and vbytes > 0 and sbytes > 0, _lib.last_error()
+    ws, vws, sws = (torch.empty(b, dtype=torch.uint8, device="cuda") for b in (nbytes, vbytes, sbytes))
+    seven, seven_s = (torch.zeros(1, 7, 1, dtype=torch.float64, device="cuda") for _ in range(2))
+
+    def field_loop():
+        _lib.check(lib.nfft_hip_ewald_near_box(ctypes.byref(p), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                               order.data_ptr(), z.data_ptr(), f.data_ptr(), ws.data_ptr(), nbytes, stream))
+
+    def virial_loop():
+        _lib.check(lib.nfft_hip_ewald_virial_near(ctypes.byref(p), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                                  seven.data_ptr(), vws.data_ptr(), vbytes, stream))
+
+    def step_loop():
+        _lib.check(lib.nfft_hip_ewald_step_near(ctypes.byref(p), spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                                order.data_ptr(), zs.data_ptr(), fs.data_ptr(), seven_s.data_ptr(),
+                                                sws.data_ptr(), sbytes, stream))
+
+    band = tn.nfft_adjoint(q, pos, bandwidth=N, cutoff=m)  # [1, N, N, N]
+    fc = sp.field_coeffs().reshape(1, N, N, N, 4)
+    t = alternating_ms({
+        "ewald_field": lambda: tn.nfft_ewald(q, pos, field=True, **kw),
+        "ewald_virial": lambda: tn.nfft_ewald_virial(q, pos, **kw),
+        "ewald_step": lambda: tn.nfft_ewald_step(q, pos, **kw),
+        "pair_loop_field": field_loop, "pair_loop_virial": virial_loop, "pair_loop_step": step_loop,
+        "spectral_product": lambda: band.unsqueeze(4) * fc,
+        "spectral_virial_far": lambda: tn.ops.nfft_ewald_virial_far(band, sp.coeffs, box, sp.alpha),
+        "spectral_step": lambda: tn.ops.nfft_ewald_step_spectral(band, sp.coeffs, box, sp.alpha)}, args.reps)
+    zo, fo, so = tn.ops.nfft_ewald_step_near(pos, q, None, box, sp.alpha, r_c)
+    assert torch.equal(zo, zs[:, 0]) and torch.equal(fo, fs) and torch.equal(so, seven_s[:, :, 0]), \
+        "the restated plumbing must give the operator's bits"
+    spectra, far7 = tn.ops.nfft_ewald_step_spectral(band, sp.coeffs, box, sp.alpha)
+    want = band.unsqueeze(4) * fc
+    tn.ops.check_status()
+    ms = lambda v: [round(a, 4) for a in v]  # noqa: E731
+    med = {k: v[0] for k, v in t.items()}
+    two_calls = med["ewald_field"] + med["ewald_virial"]
+    two_loops = med["pair_loop_field"] + med["pair_loop_virial"]
+    two_passes = med["spectral_product"] + med["spectral_virial_far"]
+    print(json.dumps({"bench": "ewald_step", "box": box, "points": n, "neighbours": args.neighbours, "tol": args.tol,
+                      "r_cut": round(r_c, 5), "alpha": round(sp.alpha, 3), "N": N, "m": m, "cells": list(G), "reps": args.reps,
+                      "exclusions": bool(args.exclusions), "median_min_max_ms": {k: ms(v) for k, v in t.items()},
+                      "field_plus_virial_ms": round(two_calls, 4), "step_over_field_plus_virial": round(med["ewald_step"] / two_calls, 3),
+                      "step_over_field": round(med["ewald_step"] / med["ewald_field"], 3),
+                      # (the two calls at their slowest against the step at its fastest, and the other way round)
+                      "ratio_range": [round(t["ewald_step"][1] / (t["ewald_field"][2] + t["ewald_virial"][2]), 3),
+                                      round(t["ewald_step"][2] / (t["ewald_field"][1] + t["ewald_virial"][1]), 3)],
+                      "pairs_tested": tested,
+                      "ps_per_pair": {k[10:]: round(med[k] * 1e9 / tested, 3) for k in med if k.startswith("pair_loop_")},
+                      "two_pair_loops_ms": round(two_loops, 4), "step_loop_over_two_loops": round(med["pair_loop_step"] / two_loops, 3),
+                      "step_loop_over_field_loop": round(med["pair_loop_step"] / med["pair_loop_field"], 3),
+                      "two_spectral_passes_ms": round(two_passes, 4),
+                      "step_spectral_over_two_passes": round(med["spectral_step"] / two_passes, 3),
+                      "step_spectral_GBps": round(band.numel() * 8 * 5 / med["spectral_step"] * 1e-6, 1),  # (one read, four writes)
+                      "same_bits_as_the_two_loops": bool(torch.equal(zs, z) and torch.equal(fs, f) and torch.equal(seven_s, seven)),
+                      "same_bits_as_virial_far": bool(torch.equal(far7, tn.ops.nfft_ewald_virial_far(band, sp.coeffs, box, sp.alpha))),
+                      "spectra_rel_difference": float((spectra - want).norm() / want.norm())}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, nargs="+", default=[100000, 1000000])
@@ -933,10 +1030,14 @@ def main():
     ap.add_argument("--exclusions", action="store_true",
                     help="time the bonded-pair correction on rigid triples (the unit cube, or --box) instead")
     ap.add_argument("--yukawa", action="store_true", help="time the screened Coulomb sum (unit cube) instead; with --virial its virial too")
+    ap.add_argument("--step", action="store_true",
+                    help="time nfft_ewald_step beside the calls, pair loops and spectral passes it replaces (with --box, --exclusions)")
     ap.add_argument("--screening", type=float, default=1.0, help="--yukawa: lambda r_c, the screening parameter times r_c")
     args = ap.parse_args()
     if args.box is not None and len(args.box) not in (3, 6):
         ap.error("--box takes three or six comma-separated numbers")
+    if args.step and (args.virial or args.dispersion or args.dipole or args.stokeslet or args.rpy or args.yukawa):
+        ap.error("--step times the Coulomb sum's fused step on its own (with or without --box and --exclusions)")
     if args.yukawa and (args.box is not None or args.dispersion or args.dipole or args.stokeslet or args.rpy or args.exclusions):
         ap.error("--yukawa times the unit cube on its own (with or without --virial)")
     if args.yukawa and not 0.0 < args.screening <= 50.0:
@@ -954,6 +1055,9 @@ def main():
     torch.cuda.set_device(0)
     lib = _lib.load()
     for n in args.points:
+        if args.step:
+            run_step(lib, n, args)
+            continue
         if args.yukawa:
             run_yukawa(lib, n, args)
             continue

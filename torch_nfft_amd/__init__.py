@@ -20,7 +20,7 @@ from .nearfield import (RegularizedKernel, nfft_nearfield, nfft_fastsum_nearfiel
                         nfft_nearfield_gradient, nfft_fastsum_nearfield_gradient, NfftNearfieldGradientFunction,
                         NfftNearfieldPointsFunction)
 from .ewald import (EwaldSplitting, nfft_ewald, nfft_ewald_energy, NfftEwaldFunction, nfft_ewald_virial,  # noqa: E402
-                    virial_to_box_gradient)
+                    nfft_ewald_step, virial_to_box_gradient)
 from .dispersion import (DispersionSplitting, nfft_ewald_dispersion, nfft_ewald_dispersion_energy,  # noqa: E402
                          NfftEwaldDispersionFunction, nfft_ewald_dispersion_virial)
 from .dipole import nfft_ewald_dipole, nfft_ewald_dipole_energy, NfftEwaldDipoleFunction  # noqa: E402
@@ -39,7 +39,8 @@ __all__ = ["nfft_adjoint", "nfft_forward", "nfft_fastsum", "nfft_toeplitz_kernel
            "NfftNormalFunction", "RegularizedKernel", "nfft_nearfield", "nfft_fastsum_nearfield",
            "NfftNearfieldFunction", "nfft_nearfield_gradient", "nfft_fastsum_nearfield_gradient",
            "NfftNearfieldGradientFunction", "NfftNearfieldPointsFunction", "EwaldSplitting", "nfft_ewald",
-           "nfft_ewald_energy", "NfftEwaldFunction", "nfft_ewald_virial", "virial_to_box_gradient", "DispersionSplitting",
+           "nfft_ewald_energy", "NfftEwaldFunction", "nfft_ewald_virial", "nfft_ewald_step", "virial_to_box_gradient",
+           "DispersionSplitting",
            "nfft_ewald_dispersion", "nfft_ewald_dispersion_energy", "NfftEwaldDispersionFunction",
            "nfft_ewald_dispersion_virial", "nfft_ewald_dipole", "nfft_ewald_dipole_energy", "NfftEwaldDipoleFunction",
            "nfft_ewald_stokeslet", "nfft_ewald_stokeslet_power", "stokeslet_splitting", "NfftEwaldStokesletFunction",

@@ -661,6 +661,47 @@ int nfft_hip_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns
                                    (hipStream_t)stream);
 }
 
+// ---- potential, field, energy and virial in one pass: the checks and workspaces of section 7i ----
+int64_t nfft_hip_ewald_step_near_workspace_bytes(const nfft_hip_ewald_box_problem *p)
+{
+    return nfft_hip_ewald_virial_near_workspace_bytes(p);
+}
+
+int nfft_hip_ewald_step_near(const nfft_hip_ewald_box_problem *p, const float *points, const float *xr, const int32_t *start,
+                             const int64_t *index, float *z, float *f, double *out7, void *workspace, int64_t workspace_bytes,
+                             void *stream)
+{
+    char *ws;
+    if (int rc = virial_near_checks(p, points, xr, start, out7, workspace, workspace_bytes, stream, &ws)) return rc;
+    if (!ws) return 0;  // (no columns, or no points: out7 has been zeroed and there is no row of z or f)
+    if (!index || !z || !f) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    return launch_ewald_step_near(p, points, xr, start, index, z, f, out7, ws, (hipStream_t)stream);
+}
+
+int64_t nfft_hip_ewald_step_spectral_workspace_bytes(int64_t N, int64_t batch_size, int64_t num_columns)
+{
+    return nfft_hip_ewald_virial_far_workspace_bytes(N, batch_size, num_columns);
+}
+
+int nfft_hip_ewald_step_spectral(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
+                                 const double *box_inverse, double pi2_over_alpha2, void *spectra, double *out7, void *workspace,
+                                 int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_virial_far(N, batch_size, num_columns)) return rc;
+    if (int rc = validate_box_inverse(box_inverse)) return rc;
+    if (!(pi2_over_alpha2 > 0.0) || !(pi2_over_alpha2 < 1e300)) {
+        set_error("Input mismatch: pi2_over_alpha2 must be positive and finite");
+        return NFFT_HIP_EINVAL;
+    }
+    if (num_columns == 0) return 0;
+    if (!band || !coeffs || !spectra || !out7) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    char *ws = workspace_base(workspace, workspace_bytes, virial_far_need(N, batch_size, num_columns));
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_ewald_step_spectral(N, batch_size, num_columns, band, coeffs, box_inverse, pi2_over_alpha2, spectra, out7, ws,
+                                      (hipStream_t)stream);
+}
+
 // ---- the spectral step of the dipole sum -------------------------------------------------------
 int nfft_hip_ewald_dipole_spectral(int64_t N, int64_t batch_size, int64_t num_columns, int32_t order, const void *band,
                                    const float *coeffs, const double *box_inverse, void *out, void *stream)

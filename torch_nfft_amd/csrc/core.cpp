@@ -1138,8 +1138,10 @@ at::Tensor nfft_ewald_virial_near(at::Tensor pos, at::Tensor x, c10::optional<at
 // and the splitting's coeffs [N, N, N] float32; kappa = A^-1 k is formed in the kernel from box and the index.
 // (`reduce(N, B, C, band, coeffs, A^-1, out, workspace, bytes, stream)`: nfft_hip_ewald_virial_far with its alpha, or the
 // dispersion sum's reduction with its second grid, section 7k)
+// (`workspace_bytes`: the size query that goes with `reduce`)
 template <class Reduce>
-at::Tensor virial_far_op(const at::Tensor &band, const at::Tensor &coeffs, const std::vector<double> &box, Reduce &&reduce)
+at::Tensor virial_far_op(const at::Tensor &band, const at::Tensor &coeffs, const std::vector<double> &box, Reduce &&reduce,
+                         int64_t (*workspace_bytes)(int64_t, int64_t, int64_t) = nfft_hip_ewald_virial_far_workspace_bytes)
 {
     CHECK_INPUT(band.scalar_type() == at::kComplexFloat);
     CHECK_INPUT(coeffs.scalar_type() == at::kFloat);
@@ -1160,7 +1162,7 @@ at::Tensor virial_far_op(const at::Tensor &band, const at::Tensor &coeffs, const
     CHECK_INPUT(a00 > 0.0 && a11 > 0.0 && a22 > 0.0);
     const double i00 = 1.0 / a00, i11 = 1.0 / a11, i22 = 1.0 / a22;
     const double inv[6] = {i00, -a10 * i00 * i11, i11, (a10 * a21 - a11 * a20) * i00 * i11 * i22, -a21 * i11 * i22, i22};
-    const int64_t ws_bytes = nfft_hip_ewald_virial_far_workspace_bytes(N, B, C);
+    const int64_t ws_bytes = workspace_bytes(N, B, C);
     if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
     if (C == 0) return at::zeros(shape, opts);  // no launch
     c10::DeviceGuard guard(band.device());
@@ -1181,6 +1183,60 @@ at::Tensor nfft_ewald_virial_far(at::Tensor band, at::Tensor coeffs, std::vector
                                                 double *out, void *ws, int64_t ws_bytes, void *stream) {
         return nfft_hip_ewald_virial_far(N, B, C, b, c, inv, pi * pi / (alpha * alpha), out, ws, ws_bytes, stream);
     });
+}
+
+// ---- potential, field, energy and virial of the Ewald sum in one pass (not in the reference) ----
+// (z, f, seven): z and f of nfft_ewald_near_box with the field and seven of nfft_ewald_virial_near from one walk over the
+// pairs: the same checks, reduction of pos, cell order and index as those two, real charges only
+std::tuple<at::Tensor, at::Tensor, at::Tensor> nfft_ewald_step_near(at::Tensor pos, at::Tensor x, c10::optional<at::Tensor> opt_batch,
+                                                                    std::vector<double> box, double alpha, double r_cut)
+{
+    TORCH_CHECK(x.is_cuda(), "torch_nfft._nfft_ewald_step_near is currently only implemented for GPU tensors");
+    const EwaldInput in = check_ewald(pos, x, opt_batch, true);
+    const Points &p = in.p;
+    CHECK_INPUT(box.size() == 6);
+    CHECK_INPUT(in.cx.real_input);  // (the energy is bilinear: real charges only)
+    const int64_t C = in.cx.C;
+    const std::vector<int64_t> seven_shape = in.cx.shape({p.B, 7});
+    const nfft_hip_ewald_box_problem q = ewald_box_problem(p, C, true, box, alpha, r_cut);
+    const int64_t ws_bytes = nfft_hip_ewald_step_near_workspace_bytes(&q);
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    const at::TensorOptions opts = x.options().dtype(at::kFloat), opts64 = x.options().dtype(at::kDouble);
+    if (p.n == 0 || C == 0)  // no launch
+        return {at::zeros(in.z_shape, x.options()), at::zeros(in.f_shape, x.options()), at::zeros(seven_shape, opts64)};
+    c10::DeviceGuard guard(x.device());
+    const CellOrder o = torus_cell_order(p, q.cells);
+    const at::Tensor xr = real_rows(x, true, p.n, C, o.order);
+    // (zeros: a point whose coordinates are not numbers has no cell and is not written)
+    at::Tensor z = at::zeros({p.n, C}, opts);
+    at::Tensor f = at::zeros({p.n, 3 * C}, opts);
+    at::Tensor out = at::zeros({p.B, 7, C}, opts64);
+    at::Tensor ws = byte_buffer(ws_bytes, x);
+    check_rc(nfft_hip_ewald_step_near(&q, o.pos.data_ptr<float>(), xr.data_ptr<float>(), o.start.data_ptr<int32_t>(),
+                                      o.order.data_ptr<int64_t>(), z.data_ptr<float>(), f.data_ptr<float>(),
+                                      out.data_ptr<double>(), ws.data_ptr(), ws_bytes, stream_of(x)));
+    const auto zf = ewald_result(in, z, f, true);
+    return {std::get<0>(zf), std::get<1>(zf), out.reshape(seven_shape)};
+}
+
+// (spectra, seven): spectra [B, N, N, N, 4, *cols] complex64 = band times (b_k, 2 pi i kappa_a b_k), the four spectra whose
+// forward transform is the far part of (phi, E), and seven of nfft_ewald_virial_far, from one read of band
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_step_spectral(at::Tensor band, at::Tensor coeffs, std::vector<double> box, double alpha)
+{
+    TORCH_CHECK(band.is_cuda(), "torch_nfft._nfft_ewald_step_spectral is currently only implemented for GPU tensors");
+    CHECK_INPUT(alpha > 0.0);
+    CHECK_INPUT(band.dim() >= 4);
+    const double pi = 3.14159265358979323846;
+    std::vector<int64_t> shape = band.sizes().vec();
+    shape.insert(shape.begin() + 4, 4);
+    at::Tensor spectra;
+    at::Tensor seven = virial_far_op(band, coeffs, box, [&](int64_t N, int64_t B, int64_t C, const void *b, const float *c,
+                                                            const double *inv, double *out, void *ws, int64_t ws_bytes, void *stream) {
+        spectra = at::empty(shape, band.options());  // (every entry is written)
+        return nfft_hip_ewald_step_spectral(N, B, C, b, c, inv, pi * pi / (alpha * alpha), spectra.data_ptr(), out, ws, ws_bytes, stream);
+    }, nfft_hip_ewald_step_spectral_workspace_bytes);
+    if (!spectra.defined()) spectra = at::zeros(shape, band.options());  // (no point sets or no columns: no launch)
+    return {spectra, seven};
 }
 
 // ---- virial tensor of the dispersion Ewald sum (not in the reference) ---------------------------
@@ -1627,6 +1683,11 @@ TORCH_LIBRARY(torch_nfft, m)
     m.def("_nfft_ewald_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut) -> Tensor",
           &nfft_ewald_virial_near);
     m.def("_nfft_ewald_virial_far(Tensor band, Tensor coeffs, float[] box, float alpha) -> Tensor", &nfft_ewald_virial_far);
+    // not in the reference: the field sweep and the two reductions above in one pair walk and one spectral pass (nfft_ewald_step)
+    m.def("_nfft_ewald_step_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut) "
+          "-> (Tensor, Tensor, Tensor)", &nfft_ewald_step_near);
+    m.def("_nfft_ewald_step_spectral(Tensor band, Tensor coeffs, float[] box, float alpha) -> (Tensor, Tensor)",
+          &nfft_ewald_step_spectral);
     // not in the reference: the same two reductions for the dispersion Ewald sum 1/r^6 (nfft_ewald_dispersion_virial)
     m.def("_nfft_ewald_dispersion_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut) "
           "-> Tensor", &nfft_ewald_dispersion_virial_near);

@@ -234,6 +234,14 @@ double *ewald_virial_near_partials(const nfft_hip_ewald_box_problem *p, void *wo
 int ewald_virial_far_blocks(int64_t N);
 int launch_virial_sum(const double *partial, int64_t batch_size, int64_t C, int rows_per_set, const void *items, const int *start,
                       int cells_per_set, double *out, hipStream_t stream);
+// ewald_step.hip (potential, field, energy and virial of the Ewald sum in one pair walk and one spectral pass, DESIGN.md
+// section 7q): arguments as nfft_hip_ewald_step_near / _spectral, the workspaces those of ewald_virial.hip
+// (ewald_virial_near_workspace, ewald_virial_far_workspace), the second level its launch_virial_sum
+int launch_ewald_step_near(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xr, const int *start,
+                           const int64_t *index, float *z, float *f, double *out, void *workspace, hipStream_t stream);
+int launch_ewald_step_spectral(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
+                               const double *box_inverse, double pi2_over_alpha2, void *spectra, double *out, void *workspace,
+                               hipStream_t stream);
 // ewald_disp_virial.hip (the virial tensor of the dispersion Ewald sum): arguments as
 // nfft_hip_ewald_dispersion_virial_near / _far, the workspaces those of ewald_virial.hip
 int launch_ewald_dispersion_virial_near(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xr, const int *start,

@@ -35,6 +35,9 @@ The virial tensor: for the homogeneous strain ``A -> A (1
 
 ``W`` is symmetric, ``tr W = U`` for the converged sum, ``W / V`` is the Coulomb part of the pressure tensor and
 ``dU/dA = -A^-T W`` at fixed ``s`` (``nfft_ewald_virial``, ``virial_to_box_gradient``).
+
+``nfft_ewald_step`` returns ``(phi, E, U, W)`` of one configuration from one adjoint transform, one spectral pass, one
+forward transform and one walk over the pairs, where the two calls above repeat the first and the last.
 """
 import ctypes
 import math
@@ -475,6 +478,56 @@ def nfft_ewald_virial(q, pos, batch=None, /, splitting=None, cutoff=4, fractiona
         for a in range(3):
             W[:, a, a] -= background
         return U.to(q.dtype), W.to(q.dtype)
+
+
+def nfft_ewald_step(q, pos, batch=None, /, splitting=None, cutoff=4, fractional=False, exclusions=None):
+    """``(phi, E, U, W)``: what one constant-pressure or cell-relaxation step needs from the Coulomb sum, in one pass
+    (DESIGN.md section 7q).  ``phi`` ``[n, *cols]`` and ``E = -grad phi`` ``[n, 3, *cols]`` (Cartesian, in the box's units)
+    are those of ``nfft_ewald(q, pos, batch, field=True)``, ``U`` ``[B, *cols]`` and ``W`` ``[B, 3, 3, *cols]`` those of
+    ``nfft_ewald_virial(q, pos, batch)``, all with the dtype of ``q``: the same definitions, self and background terms and
+    float64 assembly of ``U`` and ``W`` before the cast.  The forces are ``q_i E_i``.
+
+    ``q`` ``[n, *cols]`` must be real (float32; ValueError).  ``pos``, ``batch``, ``splitting``, ``cutoff``, ``fractional`` and
+    ``exclusions`` are those of ``nfft_ewald``; without a box the cell is the unit cube.
+
+    One adjoint transform, one native spectral pass (the four spectra of ``(phi, E)`` and the frequencies' share of ``U`` and
+    ``W`` from one read), one forward transform of the four spectra, one native walk over the pairs within ``r_cut`` (ten sums
+    per point and column, of which seven are reduced in float64), then the terms -- where the two separate calls do the
+    adjoint transform and the walk twice.  With ``exclusions`` the listed pairs' shares are subtracted from the walk's sums
+    before anything else is added to them, as in ``nfft_ewald``.  The two native steps use no atomics and give the same bits
+    on every call; the transforms around them spread with float atomics, so the whole does not.
+
+    Runs under ``torch.no_grad()``: all four outputs are constants to autograd.  Inputs that require grad are accepted and
+    get no gradient from here; ``batch`` must not require grad (AssertionError)."""
+    _check("nfft_ewald_step", q, pos, batch, splitting, differentiable=False)
+    if q.is_complex():
+        raise ValueError("nfft_ewald_step: the charges must be real (the energy is bilinear in q)")
+    exclusions = _exclusions.check_exclusions("nfft_ewald_step", exclusions, pos)
+    with torch.no_grad():
+        q, pos = q.detach(), pos.detach()
+        pos = _fractional("nfft_ewald_step", pos, splitting, fractional)
+        alpha, N = splitting.alpha, splitting.bandwidth
+        box6 = _IDENTITY6 if splitting.box is None else splitting.box6
+        band = nfft_adjoint(q, pos, batch, bandwidth=N, cutoff=int(cutoff))  # [B, N, N, N, *cols]
+        spectra, far7 = ops.nfft_ewald_step_spectral(band, splitting.coeffs, box6, alpha)
+        far = nfft_forward(spectra, pos, batch, cutoff=int(cutoff), real_output=True)  # [n, 4, *cols]
+        z, f, near7 = ops.nfft_ewald_step_near(pos, q, batch, box6, alpha, splitting.r_cut)
+        if exclusions is not None:
+            zx, fx = _exclusions.correction(_exclusions.COULOMB, q, pos, batch, splitting, exclusions, True)
+            z, f = z - zx, f - fx
+            near7 = near7 - _exclusions.virial_correction(_exclusions.COULOMB, q, pos, batch, splitting, exclusions)
+        seven = far7 + near7
+        background = math.pi / (alpha * alpha * splitting.volume)
+        phi = far[:, 0] + z - (2.0 * alpha / math.sqrt(math.pi)) * q - background * _set_sums(q, batch)[1]
+        E = far[:, 1:] + f
+        q64 = q.double()
+        total = _set_sums(q64, batch)[0]
+        background = (0.5 * background) * total * total
+        U = seven[:, 0] - (alpha / math.sqrt(math.pi)) * _set_sums(q64 * q64, batch)[0] - background
+        W = _voigt_to_matrix(seven[:, 1:])
+        for a in range(3):
+            W[:, a, a] -= background
+        return phi, E, U.to(q.dtype), W.to(q.dtype)
 
 
 def virial_to_box_gradient(W, box):

@@ -239,6 +239,27 @@ def nfft_ewald_virial_far(band, coeffs, box, alpha):
     return _ops._nfft_ewald_virial_far(band, coeffs, [float(a) for a in box], float(alpha))
 
 
+def nfft_ewald_step_near(pos, x, batch, box, alpha, r_cut):
+    """torch_nfft::_nfft_ewald_step_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut) ->
+    (Tensor, Tensor, Tensor) (not in the reference): ``(z, f, seven)`` -- ``z`` ``[n, *cols]`` and ``f`` ``[n, 3, *cols]``
+    float32 of ``nfft_ewald_near_box(..., with_field=True)`` and ``seven`` ``[B, 7, *cols]`` float64 of
+    ``nfft_ewald_virial_near`` -- from one walk over the pairs that keeps the ten sums of a point and column side by side.
+    ``pos`` fractional (any real values, taken modulo 1), ``x`` float32 (real charges only), ``box`` six numbers (the unit
+    cube: ``1, 0, 1, 0, 0, 1``).  One native call (``nfft_hip_ewald_step_near``), no atomics: two
+    calls give the same bits."""
+    return _ops._nfft_ewald_step_near(pos, x, batch, [float(a) for a in box], float(alpha), float(r_cut))
+
+
+def nfft_ewald_step_spectral(band, coeffs, box, alpha):
+    """torch_nfft::_nfft_ewald_step_spectral(Tensor band, Tensor coeffs, float[] box, float alpha) -> (Tensor, Tensor) (not
+    in the reference): ``(spectra, seven)`` from one pass over ``band`` ``[B, N, N, N, *cols]`` complex64 -- ``spectra``
+    ``[B, N, N, N, 4, *cols]`` complex64, ``band`` times ``b_k`` and ``(2 pi i kappa_a) b_k`` (what the product with
+    ``EwaldSplitting.field_coeffs()`` gives; ``2 pi kappa`` formed in float32 from ``box``), whose forward transform is the far
+    part of ``(phi, E)``, and ``seven`` ``[B, 7, *cols]`` float64 of ``nfft_ewald_virial_far``.  One native call
+    (``nfft_hip_ewald_step_spectral``), no atomics."""
+    return _ops._nfft_ewald_step_spectral(band, coeffs, [float(a) for a in box], float(alpha))
+
+
 def nfft_ewald_dispersion_virial_near(pos, x, batch, box, alpha, r_cut):
     """torch_nfft::_nfft_ewald_dispersion_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha,
     float r_cut) -> Tensor (not in the reference): ``nfft_ewald_virial_near`` for the dispersion sum, ``[B, 7, *cols]``
