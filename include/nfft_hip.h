@@ -560,6 +560,45 @@ int nfft_hip_ewald_step_spectral(int64_t N, int64_t batch_size, int64_t num_colu
                                  const double *box_inverse, double pi2_over_alpha2, void *spectra, double *out7, void *workspace,
                                  int64_t workspace_bytes, void *stream);
 
+/* ---- forces, energies and virial of a Lennard-Jones + Coulomb model in one pass (no reference counterpart) ----
+ * Point j carries a charge q_j, a dispersion coefficient c_j and a repulsion coefficient a_j, packed as xs [points, 3];
+ * geometric mixing, C6_ij = c_i c_j and C12_ij = a_i a_j.  The energy is U = U_C + U_LJ with U_C the Coulomb Ewald sum
+ * (alpha = p->alpha) and U_LJ = 1/2 sum_ij a_i a_j / r_ij^12 [r_ij < r_cut] minus the dispersion Ewald sum of c
+ * (alpha = alpha_dispersion); both sums share r_cut, the box and the cells.  Real data, one column (p->num_columns must be 1).
+ *
+ * nfft_hip_ewald_lj_step_near: the nfft_hip_ewald_box_problem, the cell-ordered fractional points, start and index of
+ * nfft_hip_ewald_step_near (with_field is not used and must be 0 or 1; the unit cube is the box 1, 0, 1, 0, 0, 1).  Over the
+ * pairs 0 < r_ij < r_cut, with w_C, mg_C the Coulomb pair weights, w_D, mg_D the dispersion pair weights and
+ * s_ij = q_i q_j mg_C - c_i c_j mg_D + 12 a_i a_j / r^14:
+ *     f[index[i], a] = sum_j s_ij d_ij[a]                                                      float32 [points, 3]
+ *     out8[b, 0]     = 1/2 sum_ij q_i q_j w_C                                                  float64 [batch_size, 8]
+ *     out8[b, 1]     = 1/2 sum_ij (a_i a_j / r^12 - c_i c_j w_D)
+ *     out8[b, 2 + e] = 1/2 sum_ij s_ij d_ij[a] d_ij[b],   e = 0 .. 5: ab = xx, yy, zz, yz, xz, xy
+ * (f is the near part of the force itself: the lane's own coefficients are inside).  With no points out8 is set to zero.
+ * Separations below 1.6e-5, or at which 12 a_i a_j / r^14 leaves float32, give values that are not numbers.
+ *
+ * nfft_hip_ewald_lj_step_spectral: band [batch_size, N, N, N, 2] complex64, the adjoint transform of the columns (q, c);
+ * the float32 grids [N, N, N] coeffs_coulomb (b^C_k), coeffs_dispersion (b^D_k) and strain_dispersion (t^D_k, as for
+ * nfft_hip_ewald_dispersion_virial_far); box_inverse and pi2_over_alpha2 (of the Coulomb alpha) as for
+ * nfft_hip_ewald_virial_far.  It writes spectra [batch_size, N, N, N, 6] complex64,
+ *     spectra[.., a] = 2 pi i kappa_a b^C_k band[.., 0],   spectra[.., 3 + a] = 2 pi i kappa_a b^D_k band[.., 1]
+ * (zeros where the table is zero; 2 pi kappa in float32), whose forward transform is the far part of (E, G), and
+ *     out8[b, 0] = 1/2 sum_k b^C_k |S^q_k|^2,   out8[b, 1] = -1/2 sum_k b^D_k |S^c_k|^2,
+ *     out8[b, 2 + e] = the terms of nfft_hip_ewald_virial_far minus those of nfft_hip_ewald_dispersion_virial_far.
+ * band and spectra need the 8-byte alignment of complex64 only; when both are 16-byte aligned a cell moves in 16-byte pieces.
+ *
+ * Checks, limits and error codes are those of the Coulomb step's entry points; the *_workspace_bytes functions return -1 for
+ * a problem that would be refused.  Two levels, float64 and no atomics: two calls give the same bits. */
+int64_t nfft_hip_ewald_lj_step_near_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion);
+int nfft_hip_ewald_lj_step_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, const float *points, const float *xs,
+                                const int32_t *start, const int64_t *index, float *f, double *out8, void *workspace,
+                                int64_t workspace_bytes, void *stream);
+int64_t nfft_hip_ewald_lj_step_spectral_workspace_bytes(int64_t N, int64_t batch_size);
+int nfft_hip_ewald_lj_step_spectral(int64_t N, int64_t batch_size, const void *band, const float *coeffs_coulomb,
+                                    const float *coeffs_dispersion, const float *strain_dispersion, const double *box_inverse,
+                                    double pi2_over_alpha2, void *spectra, double *out8, void *workspace, int64_t workspace_bytes,
+                                    void *stream);
+
 /* ---- Ewald sum of point charges and point dipoles (no reference counterpart) ----
  * Source j carries a charge q_j and a Cartesian dipole mu_j, packed as xs [points, 4, num_columns] = (q, mu_x, mu_y, mu_z).
  * With d = d_ij, r = |d|, m = mu_j . d and the Smith functions B_0 = erfc(alpha r) / r,

@@ -90,6 +90,15 @@ tested pair); and the torch product with field_coeffs() plus ops.nfft_ewald_viri
 the same band.  All are timed in turn, median, minimum and maximum of `reps` each.  With --exclusions the three public calls
 carry a list of the n / 2 pairs (2 i, 2 i + 1).
 
+    python scripts/bench_ewald.py --lj-step [--box ...] [...]
+
+times the Lennard-Jones + Coulomb step on a jittered lattice with sigma = 0.8 x its spacing, one row per
+point count: nfft_ewald_step, nfft_ewald_dispersion(field=True) and nfft_ewald_dispersion_virial (each with the splitting that
+from_tolerance gives it, the bandwidth raised to the next size with prime factors <= 7 unless --bandwidth-as-is), their sum and
+nfft_ewald_lj_step (one bandwidth for both sums, the larger of the two); the three pair
+loops and the new one on restated plumbing; the three spectral passes and the new one on the same band.  All are timed in turn,
+median, minimum and maximum of `reps` each.
+
     python scripts/bench_ewald.py --yukawa [--virial] [--screening 1.0] [...]
 
 times the screened Coulomb sum e^(-lambda r) / r in the unit cube on the same points, r_c, alpha and N,
@@ -1013,6 +1022,131 @@ def run_step(lib, n, args):
                       "spectra_rel_difference": float((spectra - want).norm() / want.norm())}))
 
 
+def fft_friendly(N):
+    """the first even size >= N whose prime factors are 2, 3, 5 and 7"""
+    N += N % 2
+    while True:
+        m = N
+        for p in (2, 3, 5, 7):
+            while m % p == 0:
+                m //= p
+        if m == 1:
+            return N
+        N += 2
+
+
+def run_lj_step(lib, n, args):
+    """the Lennard-Jones + Coulomb step beside the three calls, the three pair loops and the three
+    spectral passes that it replaces, on a jittered lattice (r^-12 forbids uniform points).  The three calls get the
+    splittings that from_tolerance gives each sum; the step needs one bandwidth for both and takes the larger.  Every
+    bandwidth is raised to the next size with small prime factors (from_tolerance may return one like 278 = 2 x 139, at which
+    the FFT of every call runs many times slower); --bandwidth-as-is keeps what from_tolerance returns."""
+    m = 4
+    box = [1.0, 0.0, 1.0, 0.0, 0.0, 1.0] if args.box is None else \
+        (args.box if len(args.box) == 6 else [args.box[0], 0.0, args.box[1], 0.0, 0.0, args.box[2]])
+    A = [[box[0], 0.0, 0.0], [box[1], box[2], 0.0], [box[3], box[4], box[5]]]
+    probe = tn.EwaldSplitting(1.0, 1e-3 * min(box[0], box[2], box[5]), 2, box=A, device="cpu")  # (volume and widths)
+    r_c = min((3.0 * args.neighbours * probe.volume / (4.0 * math.pi * n)) ** (1.0 / 3.0), min(probe.widths) / 3.0)
+    own_c = tn.EwaldSplitting.from_tolerance(args.tol, r_c, box=A)
+    own_d = tn.DispersionSplitting.from_tolerance(args.tol, r_c, box=A)
+    if not args.bandwidth_as_is:
+        own_c = tn.EwaldSplitting(own_c.alpha, r_c, fft_friendly(own_c.bandwidth), box=A)
+        own_d = tn.DispersionSplitting(own_d.alpha, r_c, fft_friendly(own_d.bandwidth), box=A)
+    N = max(own_c.bandwidth, own_d.bandwidth)
+    spc = tn.EwaldSplitting(own_c.alpha, r_c, N, box=A)
+    spd = tn.DispersionSplitting(own_d.alpha, r_c, N, box=A)
+    rng = np.random.default_rng(0)
+    side = int(math.ceil(n ** (1.0 / 3.0)))
+    g = (np.arange(side) + 0.5) / side - 0.5
+    v = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    v = (v + (rng.random(v.shape) - 0.5) * (0.4 / side))[rng.permutation(side ** 3)[:n]].astype(np.float32)
+    v[v >= 0.5] = -0.5  # (rounded up to the face: the same point)
+    pos = torch.from_numpy(v).cuda()
+    sigma = 0.8 * probe.volume ** (1.0 / 3.0) / side * (0.95 + 0.1 * rng.random(n))
+    cc, aa = tn.lj_coefficients(torch.from_numpy(sigma), torch.from_numpy(0.5 + rng.random(n)))
+    q = torch.from_numpy(rng.standard_normal(n).astype(np.float32)).cuda()
+    c, a = cc.float().cuda(), aa.float().cuda()
+    G = spc.cells
+    assert spd.cells == G
+    tested = box_pairs_tested(v, G)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    spos, order, start = box_cell_order(pos, G)
+    qs, cs = (t.index_select(0, order).reshape(n, 1).contiguous() for t in (q, c))
+    xs = torch.stack([q, c, a], 1).index_select(0, order).contiguous()
+    z, f, fl = torch.zeros(n, 1, device="cuda"), torch.zeros(n, 3, device="cuda"), torch.zeros(n, 3, device="cuda")
+    pc, pd = (_lib.EwaldBoxProblem(cells=(ctypes.c_int32 * 3)(*G), with_field=1, num_points=n, num_columns=1, batch_size=1,
+                                   alpha=alpha, r_cut=r_c, box=(ctypes.c_double * 6)(*box)) for alpha in (spc.alpha, spd.alpha))
+    sizes = [lib.nfft_hip_ewald_step_near_workspace_bytes(ctypes.byref(pc)), lib.nfft_hip_ewald_near_box_workspace_bytes(ctypes.byref(pd)),
+             lib.nfft_hip_ewald_virial_near_workspace_bytes(ctypes.byref(pd)),
+             lib.nfft_hip_ewald_lj_step_near_workspace_bytes(ctypes.byref(pc), spd.alpha)]
+    assert min(sizes) > 0, _lib.last_error()
+    wss = [torch.empty(b, dtype=torch.uint8, device="cuda") for b in sizes]
+    seven_c, seven_d = (torch.zeros(1, 7, 1, dtype=torch.float64, device="cuda") for _ in range(2))
+    eight = torch.zeros(1, 8, dtype=torch.float64, device="cuda")
+
+    def coulomb_step_loop():
+        _lib.check(lib.nfft_hip_ewald_step_near(ctypes.byref(pc), spos.data_ptr(), qs.data_ptr(), start.data_ptr(), order.data_ptr(),
+                                                z.data_ptr(), f.data_ptr(), seven_c.data_ptr(), wss[0].data_ptr(), sizes[0], stream))
+
+    def dispersion_field_loop():
+        _lib.check(lib.nfft_hip_ewald_dispersion_near_box(ctypes.byref(pd), spos.data_ptr(), cs.data_ptr(), start.data_ptr(),
+                                                          order.data_ptr(), z.data_ptr(), f.data_ptr(), wss[1].data_ptr(), sizes[1], stream))
+
+    def dispersion_virial_loop():
+        _lib.check(lib.nfft_hip_ewald_dispersion_virial_near(ctypes.byref(pd), spos.data_ptr(), cs.data_ptr(), start.data_ptr(),
+                                                             seven_d.data_ptr(), wss[2].data_ptr(), sizes[2], stream))
+
+    def lj_loop():
+        _lib.check(lib.nfft_hip_ewald_lj_step_near(ctypes.byref(pc), spd.alpha, spos.data_ptr(), xs.data_ptr(), start.data_ptr(),
+                                                   order.data_ptr(), fl.data_ptr(), eight.data_ptr(), wss[3].data_ptr(), sizes[3], stream))
+
+    band = tn.nfft_adjoint(torch.stack([q, c], 1), pos, bandwidth=N, cutoff=m)  # [1, N, N, N, 2]
+    bq, bc = band[..., 0].contiguous(), band[..., 1].contiguous()
+    fd = spd.field_coeffs().reshape(1, N, N, N, 4)
+    kc, kd = ({"splitting": sp, "cutoff": m, "fractional": True} for sp in (own_c, own_d))
+    kl = {"coulomb": spc, "dispersion": spd, "cutoff": m, "fractional": True}
+    t = alternating_ms({
+        "ewald_step": lambda: tn.nfft_ewald_step(q, pos, **kc),
+        "dispersion_field": lambda: tn.nfft_ewald_dispersion(c, pos, field=True, **kd),
+        "dispersion_virial": lambda: tn.nfft_ewald_dispersion_virial(c, pos, **kd),
+        "lj_step": lambda: tn.nfft_ewald_lj_step(q, c, a, pos, **kl),
+        "pair_loop_coulomb_step": coulomb_step_loop, "pair_loop_dispersion_field": dispersion_field_loop,
+        "pair_loop_dispersion_virial": dispersion_virial_loop, "pair_loop_lj_step": lj_loop,
+        "spectral_coulomb_step": lambda: tn.ops.nfft_ewald_step_spectral(bq, spc.coeffs, box, spc.alpha),
+        "spectral_dispersion_product": lambda: bc.unsqueeze(4) * fd,
+        "spectral_dispersion_virial_far": lambda: tn.ops.nfft_ewald_dispersion_virial_far(bc, spd.coeffs, spd.strain_coeffs(), box),
+        "spectral_lj_step": lambda: tn.ops.nfft_ewald_lj_step_spectral(band, spc.coeffs, spd.coeffs, spd.strain_coeffs(), box, spc.alpha)},
+        args.reps)
+    fo, eo = tn.ops.nfft_ewald_lj_step_near(pos, torch.stack([q, c, a], 1), None, box, spc.alpha, spd.alpha, r_c)
+    assert torch.equal(fo, fl) and torch.equal(eo, eight), "the restated plumbing must give the operator's bits"
+    tn.ops.check_status()
+    ms = lambda v: [round(e, 4) for e in v]  # noqa: E731
+    med = {k: v[0] for k, v in t.items()}
+    old = ("ewald_step", "dispersion_field", "dispersion_virial")
+    loops = ("pair_loop_coulomb_step", "pair_loop_dispersion_field", "pair_loop_dispersion_virial")
+    passes = ("spectral_coulomb_step", "spectral_dispersion_product", "spectral_dispersion_virial_far")
+    three = sum(med[k] for k in old)
+    print(json.dumps({"bench": "ewald_lj_step", "box": box, "points": n, "neighbours": args.neighbours, "tol": args.tol,
+                      "r_cut": round(r_c, 5), "alpha_coulomb": round(spc.alpha, 3), "alpha_dispersion": round(spd.alpha, 3), "N": N,
+                      "N_of_the_three_calls": [own_c.bandwidth, own_d.bandwidth], "m": m, "cells": list(G), "reps": args.reps,
+                      "median_min_max_ms": {k: ms(v) for k, v in t.items()},
+                      "three_calls_ms": round(three, 4), "lj_step_over_three_calls": round(med["lj_step"] / three, 3),
+                      # (the three calls at their slowest against the step at its fastest, and the other way round)
+                      "ratio_range": [round(t["lj_step"][1] / sum(t[k][2] for k in old), 3),
+                                      round(t["lj_step"][2] / sum(t[k][1] for k in old), 3)],
+                      "pairs_tested": tested,
+                      "ps_per_pair": {k[10:]: round(med[k] * 1e9 / tested, 3) for k in med if k.startswith("pair_loop_")},
+                      "three_pair_loops_ms": round(sum(med[k] for k in loops), 4),
+                      "lj_loop_over_three_loops": round(med["pair_loop_lj_step"] / sum(med[k] for k in loops), 3),
+                      "lj_loop_ratio_range": [round(t["pair_loop_lj_step"][1] / sum(t[k][2] for k in loops), 3),
+                                              round(t["pair_loop_lj_step"][2] / sum(t[k][1] for k in loops), 3)],
+                      "three_spectral_passes_ms": round(sum(med[k] for k in passes), 4),
+                      "lj_spectral_over_three_passes": round(med["spectral_lj_step"] / sum(med[k] for k in passes), 3),
+                      "lj_spectral_ratio_range": [round(t["spectral_lj_step"][1] / sum(t[k][2] for k in passes), 3),
+                                                  round(t["spectral_lj_step"][2] / sum(t[k][1] for k in passes), 3)],
+                      "lj_spectral_GBps": round(N ** 3 * (16 + 48 + 12) / med["spectral_lj_step"] * 1e-6, 1)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, nargs="+", default=[100000, 1000000])
@@ -1032,12 +1166,19 @@ def main():
     ap.add_argument("--yukawa", action="store_true", help="time the screened Coulomb sum (unit cube) instead; with --virial its virial too")
     ap.add_argument("--step", action="store_true",
                     help="time nfft_ewald_step beside the calls, pair loops and spectral passes it replaces (with --box, --exclusions)")
+    ap.add_argument("--lj-step", action="store_true",
+                    help="time nfft_ewald_lj_step beside the three calls, pair loops and spectral passes it replaces (with --box)")
+    ap.add_argument("--bandwidth-as-is", action="store_true",
+                    help="--lj-step: keep the bandwidths of from_tolerance instead of the next sizes with prime factors <= 7")
     ap.add_argument("--screening", type=float, default=1.0, help="--yukawa: lambda r_c, the screening parameter times r_c")
     args = ap.parse_args()
     if args.box is not None and len(args.box) not in (3, 6):
         ap.error("--box takes three or six comma-separated numbers")
     if args.step and (args.virial or args.dispersion or args.dipole or args.stokeslet or args.rpy or args.yukawa):
         ap.error("--step times the Coulomb sum's fused step on its own (with or without --box and --exclusions)")
+    if args.lj_step and (args.step or args.virial or args.dispersion or args.dipole or args.stokeslet or args.rpy or args.yukawa
+                         or args.exclusions):
+        ap.error("--lj-step times the Lennard-Jones + Coulomb step on its own (with or without --box)")
     if args.yukawa and (args.box is not None or args.dispersion or args.dipole or args.stokeslet or args.rpy or args.exclusions):
         ap.error("--yukawa times the unit cube on its own (with or without --virial)")
     if args.yukawa and not 0.0 < args.screening <= 50.0:
@@ -1055,6 +1196,9 @@ def main():
     torch.cuda.set_device(0)
     lib = _lib.load()
     for n in args.points:
+        if args.lj_step:
+            run_lj_step(lib, n, args)
+            continue
         if args.step:
             run_step(lib, n, args)
             continue

@@ -702,6 +702,73 @@ int nfft_hip_ewald_step_spectral(int64_t N, int64_t batch_size, int64_t num_colu
                                       (hipStream_t)stream);
 }
 
+// ---- Lennard-Jones + Coulomb step: the box problem's checks, eight sums per point set ----------
+// the problem of the pair walk: the box problem with one column (the three values of a point are not columns) and the
+// second splitting parameter
+static int validate_lj_step_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion)
+{
+    if (int rc = validate_ewald_box(p)) return rc;
+    if (p->num_columns != 1) { set_error("Input mismatch: num_columns must be 1"); return NFFT_HIP_EINVAL; }
+    if (!(alpha_dispersion > 0.0) || !(alpha_dispersion < 1e18)) {
+        set_error("Input mismatch: alpha_dispersion must be positive and finite");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+static int validate_lj_step_spectral(int64_t N, int64_t batch_size) { return validate_virial_far(N, batch_size, 1); }
+
+int64_t nfft_hip_ewald_lj_step_near_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion)
+{
+    if (validate_lj_step_near(p, alpha_dispersion)) return -1;
+    return ewald_lj_step_near_workspace(p) + 256;
+}
+
+int nfft_hip_ewald_lj_step_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, const float *points, const float *xs,
+                                const int32_t *start, const int64_t *index, float *f, double *out8, void *workspace,
+                                int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_lj_step_near(p, alpha_dispersion)) return rc;
+    if (!out8) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
+    if (p->num_points == 0) {  // (no row of f)
+        NFFT_HIP_CHECK(hipMemsetAsync(out8, 0, (size_t)(p->batch_size * 8) * sizeof(double), (hipStream_t)stream));
+        return 0;
+    }
+    if (!points || !xs || !start || !index || !f) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    char *ws = workspace_base(workspace, workspace_bytes, ewald_lj_step_near_workspace(p) + 256);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_ewald_lj_step_near(p, alpha_dispersion, points, xs, start, index, f, out8, ws, (hipStream_t)stream);
+}
+
+int64_t nfft_hip_ewald_lj_step_spectral_workspace_bytes(int64_t N, int64_t batch_size)
+{
+    if (validate_lj_step_spectral(N, batch_size)) return -1;
+    return ewald_lj_step_spectral_workspace(N, batch_size) + 256;
+}
+
+int nfft_hip_ewald_lj_step_spectral(int64_t N, int64_t batch_size, const void *band, const float *coeffs_coulomb,
+                                    const float *coeffs_dispersion, const float *strain_dispersion, const double *box_inverse,
+                                    double pi2_over_alpha2, void *spectra, double *out8, void *workspace, int64_t workspace_bytes,
+                                    void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_lj_step_spectral(N, batch_size)) return rc;
+    if (int rc = validate_box_inverse(box_inverse)) return rc;
+    if (!(pi2_over_alpha2 > 0.0) || !(pi2_over_alpha2 < 1e300)) {
+        set_error("Input mismatch: pi2_over_alpha2 must be positive and finite");
+        return NFFT_HIP_EINVAL;
+    }
+    if (!band || !coeffs_coulomb || !coeffs_dispersion || !strain_dispersion || !spectra || !out8) {
+        set_error("Input mismatch: null input");
+        return NFFT_HIP_EINVAL;
+    }
+    char *ws = workspace_base(workspace, workspace_bytes, ewald_lj_step_spectral_workspace(N, batch_size) + 256);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_ewald_lj_step_spectral(N, batch_size, band, coeffs_coulomb, coeffs_dispersion, strain_dispersion, box_inverse,
+                                         pi2_over_alpha2, spectra, out8, ws, (hipStream_t)stream);
+}
+
 // ---- the spectral step of the dipole sum -------------------------------------------------------
 int nfft_hip_ewald_dipole_spectral(int64_t N, int64_t batch_size, int64_t num_columns, int32_t order, const void *band,
                                    const float *coeffs, const double *box_inverse, void *out, void *stream)

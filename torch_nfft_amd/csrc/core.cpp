@@ -1239,6 +1239,77 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_step_spectral(at::Tensor band, at:
     return {spectra, seven};
 }
 
+// ---- forces, energies and virial of a Lennard-Jones + Coulomb model in one pass (not in the reference; section 7r) ----
+// (f, eight): f [n, 3] float32, the pair part of the force on every point, and eight [B, 8] float64 (U_C, U_LJ, then xx, yy,
+// zz, yz, xz, xy of the virial), from one walk over the pairs within r_cut.  xs [n, 3] float32 = (q, c, a) per point; pos
+// fractional, reduced and ordered by cell as nfft_ewald_step_near does
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_lj_step_near(at::Tensor pos, at::Tensor xs, c10::optional<at::Tensor> opt_batch,
+                                                           std::vector<double> box, double alpha_coulomb, double alpha_dispersion,
+                                                           double r_cut)
+{
+    TORCH_CHECK(xs.is_cuda(), "torch_nfft._nfft_ewald_lj_step_near is currently only implemented for GPU tensors");
+    const Points p = check_points(pos, opt_batch, "batch");
+    CHECK_INPUT(p.dim == 3);
+    CHECK_INPUT(xs.scalar_type() == at::kFloat && xs.dim() == 2 && xs.size(0) == p.n && xs.size(1) == 3);
+    CHECK_INPUT(xs.device() == pos.device());
+    CHECK_INPUT(box.size() == 6);
+    const nfft_hip_ewald_box_problem q = ewald_box_problem(p, 1, true, box, alpha_coulomb, r_cut);
+    const int64_t ws_bytes = nfft_hip_ewald_lj_step_near_workspace_bytes(&q, alpha_dispersion);
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    const at::TensorOptions opts64 = xs.options().dtype(at::kDouble);
+    // (zeros: a point whose coordinates are not numbers has no cell and is not written)
+    at::Tensor f = at::zeros({p.n, 3}, xs.options());
+    at::Tensor out = at::zeros({p.B, 8}, opts64);
+    if (p.n == 0) return {f, out};  // no launch
+    c10::DeviceGuard guard(xs.device());
+    const CellOrder o = torus_cell_order(p, q.cells);
+    const at::Tensor xr = real_rows(xs, true, p.n, 3, o.order);
+    at::Tensor ws = byte_buffer(ws_bytes, xs);
+    check_rc(nfft_hip_ewald_lj_step_near(&q, alpha_dispersion, o.pos.data_ptr<float>(), xr.data_ptr<float>(),
+                                         o.start.data_ptr<int32_t>(), o.order.data_ptr<int64_t>(), f.data_ptr<float>(),
+                                         out.data_ptr<double>(), ws.data_ptr(), ws_bytes, stream_of(xs)));
+    return {f, out};
+}
+
+// (spectra, eight): spectra [B, N, N, N, 6] complex64 = 2 pi i kappa_a times (b^C band[.., 0], b^D band[.., 1]), whose forward
+// transform is the far part of (E, G), and eight [B, 8] float64 as above from the same read of band [B, N, N, N, 2], the
+// adjoint transform of (q, c).  A band that is not contiguous is copied; a contiguous view keeps its alignment.
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_lj_step_spectral(at::Tensor band, at::Tensor coeffs_coulomb,
+                                                               at::Tensor coeffs_dispersion, at::Tensor strain_dispersion,
+                                                               std::vector<double> box, double alpha_coulomb)
+{
+    TORCH_CHECK(band.is_cuda(), "torch_nfft._nfft_ewald_lj_step_spectral is currently only implemented for GPU tensors");
+    CHECK_INPUT(alpha_coulomb > 0.0);
+    CHECK_INPUT(band.scalar_type() == at::kComplexFloat && band.dim() == 5 && band.size(4) == 2);
+    CHECK_INPUT(box.size() == 6);
+    const int64_t B = band.size(0), N = band.size(1);
+    CHECK_INPUT(band.size(2) == N && band.size(3) == N);
+    at::Tensor tables[3] = {coeffs_coulomb, coeffs_dispersion, strain_dispersion};
+    for (at::Tensor &t : tables) {
+        CHECK_INPUT(t.scalar_type() == at::kFloat && t.device() == band.device() && t.dim() == 3);
+        for (int64_t d = 0; d < 3; ++d) CHECK_INPUT(t.size(d) == N);
+        t = t.contiguous();
+    }
+    const at::TensorOptions opts64 = band.options().dtype(at::kDouble);
+    at::Tensor out = at::zeros({B, 8}, opts64);
+    if (B == 0) return {at::zeros({B, N, N, N, 6}, band.options()), out};
+    const double a00 = box[0], a10 = box[1], a11 = box[2], a20 = box[3], a21 = box[4], a22 = box[5];
+    CHECK_INPUT(a00 > 0.0 && a11 > 0.0 && a22 > 0.0);
+    const double i00 = 1.0 / a00, i11 = 1.0 / a11, i22 = 1.0 / a22;
+    const double inv[6] = {i00, -a10 * i00 * i11, i11, (a10 * a21 - a11 * a20) * i00 * i11 * i22, -a21 * i11 * i22, i22};
+    const double pi = 3.14159265358979323846;
+    const int64_t ws_bytes = nfft_hip_ewald_lj_step_spectral_workspace_bytes(N, B);
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    c10::DeviceGuard guard(band.device());
+    const at::Tensor bc = band.contiguous();
+    at::Tensor spectra = at::empty({B, N, N, N, 6}, band.options());  // (every entry is written)
+    at::Tensor ws = byte_buffer(ws_bytes, band);
+    check_rc(nfft_hip_ewald_lj_step_spectral(N, B, bc.data_ptr(), tables[0].data_ptr<float>(), tables[1].data_ptr<float>(),
+                                             tables[2].data_ptr<float>(), inv, pi * pi / (alpha_coulomb * alpha_coulomb),
+                                             spectra.data_ptr(), out.data_ptr<double>(), ws.data_ptr(), ws_bytes, stream_of(band)));
+    return {spectra, out};
+}
+
 // ---- virial tensor of the dispersion Ewald sum (not in the reference) ---------------------------
 // [B, 7, *cols] float64 as the two operators above, for U = 1/2 sum_i c_i psi_i of the periodic 1/r^6: the pair part with the
 // weights of nfft_ewald_dispersion_near_box (w and mg = -w'(r) / r in place of erfc(alpha r) / r and -g) ...
@@ -1688,6 +1759,11 @@ TORCH_LIBRARY(torch_nfft, m)
           "-> (Tensor, Tensor, Tensor)", &nfft_ewald_step_near);
     m.def("_nfft_ewald_step_spectral(Tensor band, Tensor coeffs, float[] box, float alpha) -> (Tensor, Tensor)",
           &nfft_ewald_step_spectral);
+    // not in the reference: Coulomb, dispersion and r^-12 repulsion in one pair walk and one spectral pass (nfft_ewald_lj_step)
+    m.def("_nfft_ewald_lj_step_near(Tensor pos, Tensor xs, Tensor? batch, float[] box, float alpha_coulomb, "
+          "float alpha_dispersion, float r_cut) -> (Tensor, Tensor)", &nfft_ewald_lj_step_near);
+    m.def("_nfft_ewald_lj_step_spectral(Tensor band, Tensor coeffs_coulomb, Tensor coeffs_dispersion, Tensor strain_dispersion, "
+          "float[] box, float alpha_coulomb) -> (Tensor, Tensor)", &nfft_ewald_lj_step_spectral);
     // not in the reference: the same two reductions for the dispersion Ewald sum 1/r^6 (nfft_ewald_dispersion_virial)
     m.def("_nfft_ewald_dispersion_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut) "
           "-> Tensor", &nfft_ewald_dispersion_virial_near);

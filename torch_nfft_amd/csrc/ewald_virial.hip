@@ -200,12 +200,12 @@ __global__ void __launch_bounds__(kVirialBlock) ewald_virial_far_kernel(VirialFa
 }
 
 // out[b, e, c] = sum of partial[row, e, c] over the rows of point set b, column c (one workgroup each,
-// blockIdx.x = b C + c).
+// blockIdx.x = b C + c), e < terms: seven here and in the sums that share this level, eight in ewald_lj_step.hip (section 7r).
 // items == nullptr: the rows are b * rows_per_set ... (b + 1) * rows_per_set.  Otherwise the rows are the item slots of the
 // set's cells: slot = first point / kNearBlock + cell + piece grows with the cell, so they are the slots from that of the
 // set's first cell up to that of the next set's first cell.  The last slot of a cell lies before the first slot of the next
 // cell, so that range holds items of set b (item.x / cells_per_set == b) and empty slots (item.x < 0, skipped), no others.
-__global__ void __launch_bounds__(kVirialBlock) virial_sum_kernel(const double *__restrict__ partial, int64_t C,
+__global__ void __launch_bounds__(kVirialBlock) virial_sum_kernel(const double *__restrict__ partial, int terms, int64_t C,
                                                                   int rows_per_set, const int2 *__restrict__ items,
                                                                   const int *__restrict__ start, int cells_per_set,
                                                                   double *__restrict__ out)
@@ -222,18 +222,18 @@ __global__ void __launch_bounds__(kVirialBlock) virial_sum_kernel(const double *
         lo = b * rows_per_set;
         hi = lo + rows_per_set;
     }
-    for (int e = 0; e < kVirialTerms; ++e) {
+    for (int e = 0; e < terms; ++e) {
         double v = 0.0;
         for (int64_t row = lo + tid; row < hi; row += kVirialBlock) {
             if (items) {
                 const int cell = items[row].x;
                 if (cell < 0) continue;
             }
-            v += partial[(row * kVirialTerms + e) * C + c];
+            v += partial[(row * terms + e) * C + c];
         }
         const double sum[1] = {v};
         const double r = block_sum_f64(sum, s_red);
-        if (tid == 0) out[(b * kVirialTerms + e) * C + c] = r;
+        if (tid == 0) out[(b * terms + e) * C + c] = r;
     }
 }
 
@@ -254,14 +254,22 @@ int64_t round256(int64_t bytes) { return (bytes + 255) & ~int64_t(255); }
 
 int ewald_virial_far_blocks(int64_t N) { return virial_far_blocks(N); }
 
-// the second level on `partial`: out [batch_size, 7, C]; the rows of a point set as virial_sum_kernel takes them
-int launch_virial_sum(const double *partial, int64_t batch_size, int64_t C, int rows_per_set, const void *items, const int *start,
-                      int cells_per_set, double *out, hipStream_t stream)
+// the second level on `partial` [rows, terms, C]: out [batch_size, terms, C]; the rows of a point set as virial_sum_kernel
+// takes them
+int launch_virial_sum_terms(const double *partial, int terms, int64_t batch_size, int64_t C, int rows_per_set, const void *items,
+                            const int *start, int cells_per_set, double *out, hipStream_t stream)
 {
-    hipLaunchKernelGGL(virial_sum_kernel, dim3((unsigned)(batch_size * C)), dim3(kVirialBlock), 0, stream, partial, C,
+    hipLaunchKernelGGL(virial_sum_kernel, dim3((unsigned)(batch_size * C)), dim3(kVirialBlock), 0, stream, partial, terms, C,
                        rows_per_set, (const int2 *)items, start, cells_per_set, out);
     NFFT_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+// ... with the seven terms of a virial
+int launch_virial_sum(const double *partial, int64_t batch_size, int64_t C, int rows_per_set, const void *items, const int *start,
+                      int cells_per_set, double *out, hipStream_t stream)
+{
+    return launch_virial_sum_terms(partial, kVirialTerms, batch_size, C, rows_per_set, items, start, cells_per_set, out, stream);
 }
 
 int64_t ewald_virial_near_item_slots(const nfft_hip_ewald_box_problem *p)

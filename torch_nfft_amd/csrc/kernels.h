@@ -234,6 +234,20 @@ double *ewald_virial_near_partials(const nfft_hip_ewald_box_problem *p, void *wo
 int ewald_virial_far_blocks(int64_t N);
 int launch_virial_sum(const double *partial, int64_t batch_size, int64_t C, int rows_per_set, const void *items, const int *start,
                       int cells_per_set, double *out, hipStream_t stream);
+// (the same level over `partial` [rows, terms, C] for any number of terms: out [batch_size, terms, C])
+int launch_virial_sum_terms(const double *partial, int terms, int64_t batch_size, int64_t C, int rows_per_set, const void *items,
+                            const int *start, int cells_per_set, double *out, hipStream_t stream);
+// ewald_lj_step.hip (forces, energies and virial of a Lennard-Jones + Coulomb model in one pair walk and one spectral pass,
+// DESIGN.md section 7r): arguments as nfft_hip_ewald_lj_step_near / _spectral; `workspace`: ewald_lj_step_near_workspace(p)
+// bytes, 256-byte aligned (the work items, then one partial [8] per item slot), and ewald_lj_step_spectral_workspace(N, B)
+// bytes, 8-byte aligned
+int64_t ewald_lj_step_near_workspace(const nfft_hip_ewald_box_problem *p);
+int64_t ewald_lj_step_spectral_workspace(int64_t N, int64_t batch_size);
+int launch_ewald_lj_step_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, const float *pos, const float *xs,
+                              const int *start, const int64_t *index, float *f, double *out, void *workspace, hipStream_t stream);
+int launch_ewald_lj_step_spectral(int64_t N, int64_t batch_size, const void *band, const float *coeffs_coulomb,
+                                  const float *coeffs_dispersion, const float *strain_dispersion, const double *box_inverse,
+                                  double pi2_over_alpha2, void *spectra, double *out, void *workspace, hipStream_t stream);
 // ewald_step.hip (potential, field, energy and virial of the Ewald sum in one pair walk and one spectral pass, DESIGN.md
 // section 7q): arguments as nfft_hip_ewald_step_near / _spectral, the workspaces those of ewald_virial.hip
 // (ewald_virial_near_workspace, ewald_virial_far_workspace), the second level its launch_virial_sum

@@ -1,0 +1,139 @@
+"""Nonbonded step of a Lennard-Jones + Coulomb model in a periodic box: forces, energies and the virial tensor from one pass
+(no reference counterpart).
+
+Every point carries a charge ``q_i``, a dispersion coefficient ``c_i`` and a repulsion coefficient ``a_i``, with geometric
+mixing for both powers, ``C6_ij = c_i c_j`` and ``C12_ij = a_i a_j``.  With ``lj_coefficients(sigma, epsilon)`` these are
+``4 eps_ij sigma_ij^6`` and ``4 eps_ij sigma_ij^12`` for ``eps_ij = sqrt(eps_i eps_j)``, ``sigma_ij = sqrt(sigma_i sigma_j)`` (the
+OPLS rule).  The energy of a point set is ``U = U_coulomb + U_lj``::
+
+    U_coulomb = 1/2 sum_i q_i phi_i                               phi: the Ewald sum of ewald.py (tin-foil, self and background terms)
+    U_lj      = 1/2 sum_i a_i rho_i - 1/2 sum_i c_i psi_i         psi: the dispersion Ewald sum of dispersion.py (LJ-PME, all images)
+    rho_i     = sum_{j: 0 < r_ij < r_cut} a_j / r_ij^12           minimum images, plainly truncated: no shift, no tail correction
+
+The attraction is summed over the whole lattice, the repulsion over the pairs within ``r_cut`` only: what the truncation
+leaves out of a pair just beyond the cut is ``a_i a_j / r_cut^12``.
+"""
+import math
+
+import torch
+
+from . import ops
+from .dispersion import DispersionSplitting
+from .ewald import EwaldSplitting, _IDENTITY6, _fractional, _set_sums, _voigt_to_matrix
+from .nfft import nfft_adjoint, nfft_forward
+
+
+def lj_coefficients(sigma, epsilon):
+    """``(c, a)`` with ``c = 2 sqrt(epsilon) sigma^3`` and ``a = 2 sqrt(epsilon) sigma^6``, elementwise: the per-point
+    coefficients whose products are the Lennard-Jones pair coefficients under geometric mixing, ``c_i c_j = 4 eps_ij
+    sigma_ij^6`` and ``a_i a_j = 4 eps_ij sigma_ij^12`` with ``eps_ij = sqrt(eps_i eps_j)`` and ``sigma_ij = sqrt(sigma_i
+    sigma_j)``.  Pure torch, differentiable, any dtype and device."""
+    sigma, epsilon = torch.as_tensor(sigma), torch.as_tensor(epsilon)
+    root = 2.0 * torch.sqrt(epsilon)
+    s3 = sigma * sigma * sigma
+    return root * s3, root * s3 * s3
+
+
+def _check_splittings(what, coulomb, dispersion):
+    if not isinstance(coulomb, EwaldSplitting):
+        raise TypeError("%s: coulomb must be an EwaldSplitting" % what)
+    if not isinstance(dispersion, DispersionSplitting):
+        raise TypeError("%s: dispersion must be a DispersionSplitting" % what)
+    if coulomb.r_cut != dispersion.r_cut:
+        raise ValueError("%s: the two splittings must have the same r_cut (%r and %r): one walk serves both sums"
+                         % (what, coulomb.r_cut, dispersion.r_cut))
+    if coulomb.bandwidth != dispersion.bandwidth:
+        raise ValueError("%s: the two splittings must have the same bandwidth (%d and %d): one transform serves both sums"
+                         % (what, coulomb.bandwidth, dispersion.bandwidth))
+    if (coulomb.box is None) != (dispersion.box is None) or (coulomb.box is not None and not torch.equal(coulomb.box, dispersion.box)):
+        raise ValueError("%s: the two splittings must have the same box" % what)
+
+
+def _check_values(what, values, pos):
+    """``(q, c, a)`` as three float32 ``[n]`` tensors, ``None`` as zeros"""
+    n, out = pos.size(0), []
+    for name, v in zip("qca", values):
+        if v is None:
+            out.append(torch.zeros(n, dtype=torch.float32, device=pos.device))
+            continue
+        if v.is_complex():
+            raise ValueError("%s: %s must be real (the energy is bilinear in it)" % (what, name))
+        if v.dim() != 1:
+            raise ValueError("%s: %s must be [n]: columns are not supported" % (what, name))
+        if v.size(0) != n:
+            raise ValueError("%s: %s must hold one value per point" % (what, name))
+        if v.dtype != torch.float32:
+            raise ValueError("%s: %s must be float32" % (what, name))
+        out.append(v.detach())
+    return out
+
+
+def nfft_ewald_lj_step(q, c, a, pos, batch=None, /, coulomb=None, dispersion=None, cutoff=4, fractional=False):
+    """``(F, U_coulomb, U_lj, W)``: what one molecular-dynamics step needs from the nonbonded part of a Lennard-Jones +
+    Coulomb model, in one pass.
+
+    ``q``, ``c``, ``a`` are real float32 ``[n]`` -- charges, dispersion and repulsion coefficients with ``C6_ij = c_i c_j`` and
+    ``C12_ij = a_i a_j`` (``lj_coefficients``) -- and any of them may be ``None``, meaning zeros.  A trailing dimension
+    (columns) or complex values raise ValueError.  ``pos`` ``[n, 3]``, ``batch``, ``cutoff`` and ``fractional`` are those of
+    ``nfft_ewald_step``.  ``coulomb`` is an ``EwaldSplitting`` and ``dispersion`` a ``DispersionSplitting`` (TypeError otherwise)
+    with the same ``r_cut``, ``bandwidth`` and ``box`` (ValueError naming the field otherwise); their ``alpha`` may differ.
+
+    The energy of a point set is ``U = U_coulomb + U_lj``.  ``U_coulomb`` is the ``U`` of ``nfft_ewald_virial`` (tin-foil, self
+    and background terms).  ``U_lj = 1/2 sum_i a_i rho_i - 1/2 sum_i c_i psi_i`` with ``psi`` the full lattice sum of
+    ``nfft_ewald_dispersion`` (self term included) and ``rho_i = sum_{j: 0 < r_ij < r_cut} a_j / r_ij^12`` over minimum images,
+    plainly truncated at ``r_cut`` with no shift and no tail correction: the pair term that the truncation drops just beyond
+    the cut is ``a_i a_j / r_cut^12``.
+
+    Returns
+
+    * ``F`` ``[n, 3]`` float32, the physical force ``-dU/dx_i = q_i E_i - c_i G_i + a_i H_i``, Cartesian and in the box's units:
+      ``E`` and ``G`` are the fields of ``nfft_ewald`` and ``nfft_ewald_dispersion`` and ``H_i = sum_j 12 a_j d_ij / r_ij^14``;
+    * ``U_coulomb``, ``U_lj`` ``[B]`` float32;
+    * ``W`` ``[B, 3, 3]`` float32, ``W_ab = -dU / d eps_ab`` of the total for the strain ``A -> A (1 + eps)`` at fixed fractional
+      coordinates: ``W = W_C - W_D + W_R`` with ``W_C`` of ``nfft_ewald_virial``, ``W_D`` of ``nfft_ewald_dispersion_virial`` and
+      ``W_R = 1/2 sum_ij a_i a_j 12 d_a d_b / r^14``, hence ``tr W = U_C - 6 U_D + 12 U_R`` for the converged sums.
+      ``virial_to_box_gradient`` applies unchanged.
+
+    One adjoint transform of the two columns ``(q, c)``, one native spectral pass (the six spectra of ``(E, G)`` and the
+    frequencies' share of the energies and of ``W`` from one read), one forward transform of the six spectra, one native walk
+    over the pairs within ``r_cut`` (eleven sums per point, eight of them reduced in float64), then the self and background
+    terms in float64 before the cast -- where ``nfft_ewald_step``, ``nfft_ewald_dispersion(field=True)`` and
+    ``nfft_ewald_dispersion_virial`` together do three adjoint transforms and three walks.  The two native steps use no atomics
+    and give the same bits on every call; the transforms around them spread with float atomics, so the whole does not.
+
+    Coincident points do not see each other.  The pair walk works in float32: separations below ``1.6e-5``, or so small that
+    ``12 a_i a_j / r^14`` exceeds ``3.4e38``, give values that are not numbers.
+
+    Exclusions are out of scope and there is no ``exclusions=`` keyword.  The subtract-afterwards correction that serves
+    ``1/r`` would leave a rounding of ``2^-24 a_i a_j / r^12`` per bonded pair, which at bonded distances is not small; bonded
+    pairs need masking inside the pair loop.
+
+    Runs under ``torch.no_grad()``: all four outputs are constants to autograd.  Inputs that require grad are accepted and get
+    no gradient from here; ``batch`` must not require grad (AssertionError)."""
+    what = "nfft_ewald_lj_step"
+    _check_splittings(what, coulomb, dispersion)
+    if pos.dim() != 2 or pos.size(1) != 3:
+        raise ValueError("%s: the periodic sums are three-dimensional, pos must be [n, 3]" % what)
+    if batch is not None and batch.requires_grad:
+        raise AssertionError("%s: batch holds point-set indices and must not require grad" % what)
+    q, c, a = _check_values(what, (q, c, a), pos)
+    with torch.no_grad():
+        pos = _fractional(what, pos.detach(), coulomb, fractional)
+        alpha_c, alpha_d, N = coulomb.alpha, dispersion.alpha, coulomb.bandwidth
+        box6 = _IDENTITY6 if coulomb.box is None else coulomb.box6
+        band = nfft_adjoint(torch.stack([q, c], 1), pos, batch, bandwidth=N, cutoff=int(cutoff))  # [B, N, N, N, 2]
+        spectra, far8 = ops.nfft_ewald_lj_step_spectral(band, coulomb.coeffs, dispersion.coeffs, dispersion.strain_coeffs(), box6,
+                                                        alpha_c)
+        far = nfft_forward(spectra, pos, batch, cutoff=int(cutoff), real_output=True)  # [n, 6]: E, then G
+        f, near8 = ops.nfft_ewald_lj_step_near(pos, torch.stack([q, c, a], 1), batch, box6, alpha_c, alpha_d, coulomb.r_cut)
+        F = f + q.unsqueeze(1) * far[:, :3] - c.unsqueeze(1) * far[:, 3:]
+        eight = far8 + near8  # [B, 8] float64
+        q64, c64 = q.double(), c.double()
+        total = _set_sums(q64, batch)[0]
+        background = (math.pi / (2.0 * alpha_c * alpha_c * coulomb.volume)) * total * total
+        U_coulomb = eight[:, 0] - (alpha_c / math.sqrt(math.pi)) * _set_sums(q64 * q64, batch)[0] - background
+        U_lj = eight[:, 1] + (alpha_d ** 6 / 12.0) * _set_sums(c64 * c64, batch)[0]
+        W = _voigt_to_matrix(eight[:, 2:])
+        for e in range(3):
+            W[:, e, e] -= background
+        return F, U_coulomb.float(), U_lj.float(), W.float()

@@ -260,6 +260,33 @@ def nfft_ewald_step_spectral(band, coeffs, box, alpha):
     return _ops._nfft_ewald_step_spectral(band, coeffs, [float(a) for a in box], float(alpha))
 
 
+def nfft_ewald_lj_step_near(pos, xs, batch, box, alpha_coulomb, alpha_dispersion, r_cut):
+    """torch_nfft::_nfft_ewald_lj_step_near(Tensor pos, Tensor xs, Tensor? batch, float[] box, float alpha_coulomb,
+    float alpha_dispersion, float r_cut) -> (Tensor, Tensor) (not in the reference): ``(f, eight)`` of a Lennard-Jones +
+    Coulomb model from one walk over the pairs ``0 < r_ij < r_cut``.  ``xs`` ``[n, 3]`` float32 holds ``(q, c, a)`` per point
+    (``C6_ij = c_i c_j``, ``C12_ij = a_i a_j``).  ``f`` ``[n, 3]`` float32 is the pair part of the force,
+    ``sum_j (q_i q_j mg_C - c_i c_j mg_D + 12 a_i a_j / r^14) d_ij``; ``eight`` ``[B, 8]`` float64 is ``1/2 sum q_i q_j w_C``,
+    ``1/2 sum (a_i a_j / r^12 - c_i c_j w_D)`` and the six virial terms ``xx, yy, zz, yz, xz, xy`` of the same pair sum.
+    ``pos`` fractional (any real values, taken modulo 1), ``box`` six numbers (the unit cube: ``1, 0, 1, 0, 0, 1``).  One native
+    call (``nfft_hip_ewald_lj_step_near``), no atomics: two calls give the same bits."""
+    return _ops._nfft_ewald_lj_step_near(pos, xs, batch, [float(a) for a in box], float(alpha_coulomb), float(alpha_dispersion),
+                                         float(r_cut))
+
+
+def nfft_ewald_lj_step_spectral(band, coeffs_coulomb, coeffs_dispersion, strain_dispersion, box, alpha_coulomb):
+    """torch_nfft::_nfft_ewald_lj_step_spectral(Tensor band, Tensor coeffs_coulomb, Tensor coeffs_dispersion,
+    Tensor strain_dispersion, float[] box, float alpha_coulomb) -> (Tensor, Tensor) (not in the reference): ``(spectra,
+    eight)`` from one pass over ``band`` ``[B, N, N, N, 2]`` complex64, the adjoint transform of the columns ``(q, c)`` --
+    ``spectra`` ``[B, N, N, N, 6]`` complex64, ``(2 pi i kappa_a) b^C_k band[.., 0]`` and ``(2 pi i kappa_a) b^D_k band[.., 1]``
+    (zeros where the table is zero), whose forward transform is the far part of ``(E, G)``, and ``eight`` ``[B, 8]`` float64:
+    ``1/2 sum b^C |S^q|^2``, ``-1/2 sum b^D |S^c|^2`` and the six virial terms of ``nfft_ewald_virial_far`` minus those of
+    ``nfft_ewald_dispersion_virial_far``.  The three tables are ``EwaldSplitting.coeffs``, ``DispersionSplitting.coeffs`` and
+    ``DispersionSplitting.strain_coeffs()``.  One native call (``nfft_hip_ewald_lj_step_spectral``), no
+    atomics."""
+    return _ops._nfft_ewald_lj_step_spectral(band, coeffs_coulomb, coeffs_dispersion, strain_dispersion, [float(a) for a in box],
+                                             float(alpha_coulomb))
+
+
 def nfft_ewald_dispersion_virial_near(pos, x, batch, box, alpha, r_cut):
     """torch_nfft::_nfft_ewald_dispersion_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha,
     float r_cut) -> Tensor (not in the reference): ``nfft_ewald_virial_near`` for the dispersion sum, ``[B, 7, *cols]``
