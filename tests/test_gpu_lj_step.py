@@ -75,10 +75,12 @@ def _relative(got, want):
     return float(np.abs(np.asarray(got, dtype=np.float64) - want).max() / np.abs(want).max())
 
 
-def _coefficients(rng, n, A):
+def _coefficients(rng, n, A, spacing=None):
     """(q, c, a) float32: standard normal charges, sigma = 0.8 x the lattice spacing along the box's shortest stretch
-    (+- 5 %: at most 1.3 d_min, whatever the box), epsilon in [0.5, 1.5)"""
-    spacing = lj.LJ_SPACING * np.linalg.svd(A, compute_uv=False).min()
+    (+- 5 %: at most 1.3 d_min, whatever the box), epsilon in [0.5, 1.5).  spacing: the Cartesian spacing of another lattice
+    than lj_points'"""
+    if spacing is None:
+        spacing = lj.LJ_SPACING * np.linalg.svd(A, compute_uv=False).min()
     sigma, eps = 0.8 * spacing * (0.95 + 0.1 * rng.random(n)), 0.5 + rng.random(n)
     c, a = lj.lj_coefficients(sigma, eps)
     return rng.standard_normal(n).astype(np.float32), c.astype(np.float32), a.astype(np.float32)

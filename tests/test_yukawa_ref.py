@@ -130,6 +130,86 @@ def test_near_sum_is_sensitive_to_mistakes():
         assert max(ez, ef) >= 1e-2
 
 
+def _virial_before_the_factoring(q, s, A, batch, alpha, lam, r_c, N, background):
+    """yukawa_ref.virial as it stood before near_virial was factored out of it: the pair part inline, W by one einsum"""
+    qc = dr._columns(np.asarray(q))
+    s = np.asarray(s, dtype=np.float64)
+    Am = dr._box(A)
+    V = abs(np.linalg.det(Am))
+    b, t = yr.coeffs(A, alpha, lam, N, background).reshape(-1), yr.strain_coeffs(A, alpha, lam, N, background).reshape(-1)
+    K, kap = dr.kappa(A, N)
+    K, kap, t, b = K.reshape(-1, 3)[b != 0], kap.reshape(-1, 3)[b != 0], t[b != 0], b[b != 0]
+    sets = dr._sets(batch, s.shape[0])
+    U, W = np.zeros((len(sets), qc.shape[1])), np.zeros((len(sets), 3, 3, qc.shape[1]))
+    for n, sel in enumerate(sets):
+        if sel.size == 0:
+            continue
+        qs = qc[sel]
+        ds = s[sel][:, None, :] - s[sel][None, :, :]
+        d = (ds - np.rint(ds)) @ Am
+        w, mg = yr.pair_weights(d, alpha, lam, r_c)
+        U[n] = 0.5 * np.einsum("ic,ij,jc->c", qs, w, qs)
+        W[n] = 0.5 * np.einsum("ic,ij,ija,ijb,jc->abc", qs, mg, d, d, qs)
+        S = np.exp(-2j * math.pi * K @ s[sel].T) @ qs
+        p = (S * np.conj(S)).real
+        U[n] += 0.5 * (b[:, None] * p).sum(0)
+        W[n] += 0.5 * (np.einsum("k,kc->c", b, p)[None, None] * np.eye(3)[:, :, None] + np.einsum("k,ka,kb,kc->abc", t, kap, kap, p))
+        U[n] -= 0.5 * yr.self_term(alpha, lam) * (qs * qs).sum(0)
+        if background:
+            bg = 0.5 * yr.background_term(alpha, lam, V) * qs.sum(0) ** 2
+            U[n] += bg
+            W[n] += bg[None, None] * np.eye(3)[:, :, None]
+    return U, W
+
+
+@pytest.mark.parametrize("box,background", [("cube", False), ("T", True), ("O", False)])
+def test_factored_pair_part_leaves_the_virial_unchanged(box, background):
+    """virial() with its pair part taken from near_virial against the function as it stood, to float64 rounding, three point
+    sets with an empty one and two columns; and near_virial is that pair part in the order energy, xx, yy, zz, yz, xz, xy"""
+    A = BOXES[box]
+    rng = np.random.default_rng(17)
+    n = 90
+    s = rng.random((n, 3)) - 0.5
+    q = rng.standard_normal((n, 2)) + 0.2
+    batch = np.concatenate([np.zeros(40, np.int64), np.full(50, 2, np.int64)])
+    alpha, r_c, N, lam = 6.0, 0.25, 8, 10.0
+    U, W = yr.virial(q, s, A, batch, alpha, lam, r_c, N, background=background)
+    U0, W0 = _virial_before_the_factoring(q, s, A, batch, alpha, lam, r_c, N, background)
+    assert U.shape == (3, 2) and W.shape == (3, 3, 3, 2) and not U[1].any() and not W[1].any()
+    eu, ew = np.abs(U - U0).max() / np.abs(U0).max(), np.abs(W - W0).max() / np.abs(W0).max()
+    print("yukawa virial in %s, factored against before: U %.3e, W %.3e" % (box, eu, ew))
+    assert eu <= 1e-14 and ew <= 1e-14
+    seven = yr.near_virial(q, s, A, batch, alpha, lam, r_c)
+    assert seven.shape == (3, 7, 2) and not seven[1].any() and seven[0].all() and seven[2].all()
+    for sel, b in ((np.arange(40), 0), (np.arange(40, 90), 2)):
+        ds = s[sel][:, None, :] - s[sel][None, :, :]
+        d = (ds - np.rint(ds)) @ dr._box(A)
+        w, mg = yr.pair_weights(d, alpha, lam, r_c)
+        want = [0.5 * np.einsum("ic,ij,jc->c", q[sel], w, q[sel])]
+        want += [0.5 * np.einsum("ic,ij,jc->c", q[sel], mg * d[..., i] * d[..., j], q[sel]) for i, j in
+                 ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))]
+        assert np.abs(seven[b] - np.array(want)).max() <= 1e-13 * np.abs(seven[b]).max()
+    assert yr.near_virial(q[:, 0], s, A, None, alpha, lam, r_c).shape == (1, 7)
+
+
+def test_near_virial_is_sensitive_to_the_pair_weight_mutants():
+    """on the counted 3^3 layout in T (tests/pair_frame_ref.py) at lambda = 10, (5, 0.3), every mutant of the pair weight
+    moves the pair part of the virial by at least ten times the gate that tests/test_gpu_pair_frame_edges.py holds the
+    native pair reduction to (seen: beta's sign 1.5e1, the e^(lambda r) term dropped 6.6e-2, e^(-beta^2) missing in g 4.8e-1,
+    the Coulomb weights 4.5e-1)"""
+    import pair_frame_ref as pf
+    from ewald_virial_ref import rel_fro
+    from test_gpu_pair_frame_edges import GATES
+    gate = GATES[("yukawa_virial_near", "seven")]
+    L = pf.layout("grid3")
+    q = np.random.default_rng(1).standard_normal(L.n).astype(np.float32)
+    ref = yr.near_virial(q, L.points, T, None, 5.0, 10.0, 0.3)
+    for m in yr.MUTANTS:
+        moved = rel_fro(yr.near_virial(q, L.points, T, None, 5.0, 10.0, 0.3, mutant=m), ref)
+        print("near_virial on the counted layout, mutant %s: moves by %.3e (gate %.1e)" % (m, moved, gate))
+        assert moved >= 10 * gate
+
+
 def test_weights_at_zero_screening_are_the_coulomb_weights():
     d = np.random.default_rng(4).random((50, 3)) * 0.2
     for a, b in zip(yr.pair_weights(d, 6.0, 0.0), yr.pair_weights(d, 6.0, 0.0, mutant="coulomb")):

@@ -17,7 +17,8 @@ the positions are FRACTIONAL, ``x = s A``, ``kappa = A^-1 k``, ``V = det A``; ``
 ``coeffs`` / ``strain_coeffs``  ``b_k = 4 pi e^(-K / (4 alpha^2)) / (V K)`` and ``t_k = -8 pi^2 b_k (1 / (4 alpha^2) + 1 / K)`` on
                            ``[-N/2, N/2)^3``, the unpaired planes ``k_a = -N/2`` zeroed, ``b_0`` zeroed with ``background``
 ``yukawa``                 near + far - self (+ background): the algorithm in exact arithmetic, per point set
-``virial``                 ``(U, W)`` of the same: pairs, frequencies, self and background terms
+``near_virial``            the pair part of the next alone, ``[B, 7, *cols]`` in the order of the native pair reduction
+``virial``                 ``(U, W)`` of the same: pairs (``near_virial``), frequencies, self and background terms
 ``near_points``            the 512 points of the GPU near-sweep tests
 """
 import itertools
@@ -205,6 +206,30 @@ def yukawa(q, s, A, batch, alpha, lam, r_c, N, background=False):
     return phi, f + ff
 
 
+def near_virial(q, s, A, batch, alpha, lam, r_c, mutant=None):
+    """the pair part of ``virial`` alone, in the layout of the native pair reduction: [B, 7, *cols] -- energy, xx, yy, zz, yz, xz,
+    xy of 1/2 sum_ij q_i q_j (w, mg d_a d_b) over the wrapped minimum images with 0 < r < r_c, real q; an empty point set
+    gives zeros.  ``mutant``: one mistake of ``pair_weights``"""
+    q0 = np.asarray(q)
+    s = np.asarray(s, dtype=np.float64)
+    Am = _box(A)
+    qc = _columns(q0)
+    assert not np.iscomplexobj(qc)
+    sets = _sets(batch, s.shape[0])
+    out = np.zeros((len(sets), 7, qc.shape[1]))
+    for n, sel in enumerate(sets):
+        if sel.size == 0:
+            continue
+        qs = qc[sel]
+        ds = s[sel][:, None, :] - s[sel][None, :, :]
+        d = (ds - np.rint(ds)) @ Am
+        w, mg = pair_weights(d, alpha, lam, r_c, mutant)
+        out[n, 0] = 0.5 * np.einsum("ic,ij,jc->c", qs, w, qs)
+        for e, (a, b) in enumerate(((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))):
+            out[n, 1 + e] = 0.5 * np.einsum("ic,ij,jc->c", qs, mg * d[..., a] * d[..., b], qs)
+    return out.reshape((len(sets), 7) + q0.shape[1:])
+
+
 def virial(q, s, A, batch, alpha, lam, r_c, N, background=False):
     """(U [B, *cols], W [B, 3, 3, *cols]) of the split sum in exact arithmetic, real q: W_ab = -dU / d eps_ab for
     A -> A (1 + eps) at fixed s and fixed lam"""
@@ -218,17 +243,15 @@ def virial(q, s, A, batch, alpha, lam, r_c, N, background=False):
     K, kap = dr.kappa(A, N)
     K, kap, t, b = K.reshape(-1, 3)[b != 0], kap.reshape(-1, 3)[b != 0], t[b != 0], b[b != 0]
     sets = _sets(batch, s.shape[0])
-    U = np.zeros((len(sets), qc.shape[1]))
+    pairs = near_virial(qc, s, A, batch, alpha, lam, r_c)  # [B, 7, C]
+    U = pairs[:, 0].copy()
     W = np.zeros((len(sets), 3, 3, qc.shape[1]))
+    for e, (i, j) in enumerate(((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))):
+        W[:, i, j] = W[:, j, i] = pairs[:, 1 + e]
     for n, sel in enumerate(sets):
         if sel.size == 0:
             continue
         qs = qc[sel]
-        ds = s[sel][:, None, :] - s[sel][None, :, :]
-        d = (ds - np.rint(ds)) @ Am
-        w, mg = pair_weights(d, alpha, lam, r_c)
-        U[n] = 0.5 * np.einsum("ic,ij,jc->c", qs, w, qs)
-        W[n] = 0.5 * np.einsum("ic,ij,ija,ijb,jc->abc", qs, mg, d, d, qs)
         for c0 in range(0, K.shape[0], 4096):
             Kc, kc, bc, tc = K[c0:c0 + 4096], kap[c0:c0 + 4096], b[c0:c0 + 4096], t[c0:c0 + 4096]
             S = np.exp(-2j * math.pi * Kc @ s[sel].T) @ qs  # [nk, C]
