@@ -599,6 +599,38 @@ int nfft_hip_ewald_lj_step_spectral(int64_t N, int64_t batch_size, const void *b
                                     double pi2_over_alpha2, void *spectra, double *out8, void *workspace, int64_t workspace_bytes,
                                     void *stream);
 
+/* ---- the same step with bonded-pair exclusions (no reference counterpart) ----
+ * The list is the CSR matrix of nfft_hip_ewald_excl over the points in the CALLER's order: row_start int32 [points + 1], col
+ * int32 [num_entries] ascending within a row, weight_coulomb and weight_lj float32 [num_entries] holding w = 1 - s for the
+ * Coulomb scale s^C and the Lennard-Jones scale s^L (both powers) of the pair.  Each listed pair {i, j} stands in both rows.
+ *
+ * nfft_hip_ewald_lj_excl_near: nfft_hip_ewald_lj_step_near with the terms of a listed pair SCALED before they are added:
+ * q_i q_j by s^C, c_i c_j and a_i a_j by s^L (a pair with both scales zero adds nothing).  index must hold each point's
+ * position in the caller's order, below 2^31.  With num_entries = 0, f and out8 have the bits of nfft_hip_ewald_lj_step_near.
+ *
+ * nfft_hip_ewald_lj_excl_list: points [points, 3] fractional, reduced to [-1/2, 1/2)^3 as the cell order reduces them, and xs
+ * [points, 3], both in the CALLER's order; set_start int32 [batch_size + 1], the first point of every point set (may be null
+ * for one point set).  With d the image of s_i - s_col[k] as the pair walk forms it, r = |d| and, for r < r_cut (r = 0
+ * included), the smooth parts S_C = erf(alpha r) / r, T_C = -S_C' / r at p->alpha and S_D = 1 / r^6 - w_D, T_D = -S_D' / r at
+ * alpha_dispersion -- for r >= r_cut the full 1 / r, 1 / r^3, 1 / r^6, 6 / r^8 -- and g = w^L c_i c_j T_D - w^C q_i q_j T_C:
+ *     f[i, a]        = sum_{k in row i} g d[a]                                                  float32 [points, 3]
+ *     out8[b, 0]     = -sum_{pairs} w^C q_i q_j S_C,   out8[b, 1] = sum_{pairs} w^L c_i c_j S_D     float64 [batch_size, 8]
+ *     out8[b, 2 + e] = sum_{pairs} g d[a] d[b],   e = 0 .. 5: ab = xx, yy, zz, yz, xz, xy         (each pair once, col > row)
+ * which are to be ADDED to the results of the walk.  Entries whose column lies outside [0, points) are skipped.
+ *
+ * Both take the checks of nfft_hip_ewald_lj_step_near and in addition refuse null list pointers (row_start always, the others
+ * when num_entries > 0), a negative num_entries and one of 2^31 or more.  No atomics: two calls give the same bits. */
+int64_t nfft_hip_ewald_lj_excl_near_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion);
+int nfft_hip_ewald_lj_excl_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_entries,
+                                const float *points, const float *xs, const int32_t *start, const int64_t *index,
+                                const int32_t *row_start, const int32_t *col, const float *weight_coulomb, const float *weight_lj,
+                                float *f, double *out8, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t nfft_hip_ewald_lj_excl_list_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion);
+int nfft_hip_ewald_lj_excl_list(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_entries,
+                                const float *points, const float *xs, const int32_t *row_start, const int32_t *col,
+                                const float *weight_coulomb, const float *weight_lj, const int32_t *set_start, float *f,
+                                double *out8, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- Ewald sum of point charges and point dipoles (no reference counterpart) ----
  * Source j carries a charge q_j and a Cartesian dipole mu_j, packed as xs [points, 4, num_columns] = (q, mu_x, mu_y, mu_z).
  * With d = d_ij, r = |d|, m = mu_j . d and the Smith functions B_0 = erfc(alpha r) / r,

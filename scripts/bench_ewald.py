@@ -99,6 +99,15 @@ nfft_ewald_lj_step (one bandwidth for both sums, the larger of the two); the thr
 loops and the new one on restated plumbing; the three spectral passes and the new one on the same band.  All are timed in turn,
 median, minimum and maximum of `reps` each.
 
+    python scripts/bench_ewald.py --lj-step --exclusions [--box ...] [...]
+
+times the step with bonded-pair exclusions on n / 3 rigid triples (the water model of --exclusions:
+charges -0.834, 0.417, 0.417, the bond 0.3 of the molecules' spacing, 104.5 degrees, Lennard-Jones on the first atom of each)
+on a jittered lattice with their three listed pairs each at scale 0, one row per point count: nfft_ewald_lj_excl_step beside
+nfft_ewald_lj_step on the same points (what the masking costs) and beside nfft_ewald_step, nfft_ewald_dispersion(field=True)
+and nfft_ewald_dispersion_virial with exclusions= (the yardstick of section 7r); and the masked walk, the unmasked walk and
+the list kernel as operators.  All are timed in turn, median, minimum and maximum of `reps` each.
+
     python scripts/bench_ewald.py --yukawa [--virial] [--screening 1.0] [...]
 
 times the screened Coulomb sum e^(-lambda r) / r in the unit cube on the same points, r_c, alpha and N,
@@ -1147,6 +1156,82 @@ def run_lj_step(lib, n, args):
                       "lj_spectral_GBps": round(N ** 3 * (16 + 48 + 12) / med["spectral_lj_step"] * 1e-6, 1)}))
 
 
+def run_lj_excl_step(lib, n, args):
+    """the Lennard-Jones + Coulomb step with bonded-pair exclusions on rigid triples: the water model
+    of run_exclusions on the jittered lattice of run_lj_step (one molecule per site), its three pairs per molecule listed at
+    scale 0.  Splittings and bandwidths as run_lj_step chooses them."""
+    m = 4
+    n -= n % 3
+    mol = n // 3
+    box = [1.0, 0.0, 1.0, 0.0, 0.0, 1.0] if args.box is None else \
+        (args.box if len(args.box) == 6 else [args.box[0], 0.0, args.box[1], 0.0, 0.0, args.box[2]])
+    A = np.array([[box[0], 0.0, 0.0], [box[1], box[2], 0.0], [box[3], box[4], box[5]]])
+    probe = tn.EwaldSplitting(1.0, 1e-3 * min(box[0], box[2], box[5]), 2, box=A, device="cpu")  # (volume and widths)
+    r_c = min((3.0 * args.neighbours * probe.volume / (4.0 * math.pi * n)) ** (1.0 / 3.0), min(probe.widths) / 3.0)
+    own_c = tn.EwaldSplitting.from_tolerance(args.tol, r_c, box=A)
+    own_d = tn.DispersionSplitting.from_tolerance(args.tol, r_c, box=A)
+    if not args.bandwidth_as_is:
+        own_c = tn.EwaldSplitting(own_c.alpha, r_c, fft_friendly(own_c.bandwidth), box=A)
+        own_d = tn.DispersionSplitting(own_d.alpha, r_c, fft_friendly(own_d.bandwidth), box=A)
+    N = max(own_c.bandwidth, own_d.bandwidth)
+    spc = tn.EwaldSplitting(own_c.alpha, r_c, N, box=A)
+    spd = tn.DispersionSplitting(own_d.alpha, r_c, N, box=A)
+    rng = np.random.default_rng(0)
+    side = int(math.ceil(mol ** (1.0 / 3.0)))
+    g = (np.arange(side) + 0.5) / side - 0.5
+    centre = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    centre = (centre + (rng.random(centre.shape) - 0.5) * (0.2 / side))[rng.permutation(side ** 3)[:mol]] @ A
+    spacing = probe.volume ** (1.0 / 3.0) / side
+    bond = 0.3 * spacing
+    u = rng.standard_normal((mol, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    v = np.cross(u, rng.standard_normal((mol, 3)))
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    half = math.radians(104.5 / 2)
+    x = np.stack([centre, centre + bond * (math.cos(half) * u + math.sin(half) * v),
+                  centre + bond * (math.cos(half) * u - math.sin(half) * v)], 1).reshape(n, 3)
+    pos = torch.from_numpy((x @ np.linalg.inv(A)).astype(np.float32)).cuda()
+    q = torch.from_numpy(np.tile(np.array([-0.834, 0.417, 0.417], dtype=np.float32), mol)).cuda()
+    sigma = np.zeros(n)
+    sigma[0::3] = 0.8 * spacing  # (the hydrogens carry no Lennard-Jones term, as in TIP3P)
+    cc, aa = tn.lj_coefficients(torch.from_numpy(sigma), torch.ones(n, dtype=torch.float64))
+    c, a = cc.float().cuda(), aa.float().cuda()
+    o = 3 * np.arange(mol)
+    ex = tn.ExclusionList(np.concatenate([np.stack([o, o + 1], 1), np.stack([o, o + 2], 1), np.stack([o + 1, o + 2], 1)]), n)
+    lists = (ex.row_start, ex.col, ex.coulomb_weight, ex.dispersion_weight)
+    xs = torch.stack([q, c, a], 1)
+    kc, kd = ({"splitting": sp, "cutoff": m, "fractional": True, "exclusions": ex} for sp in (own_c, own_d))
+    kl = {"coulomb": spc, "dispersion": spd, "cutoff": m, "fractional": True}
+    walk = (box, spc.alpha, spd.alpha, r_c)
+    t = alternating_ms({
+        "lj_excl_step": lambda: tn.nfft_ewald_lj_excl_step(q, c, a, pos, exclusions=ex, **kl),
+        "lj_step": lambda: tn.nfft_ewald_lj_step(q, c, a, pos, **kl),
+        "ewald_step": lambda: tn.nfft_ewald_step(q, pos, **kc),
+        "dispersion_field": lambda: tn.nfft_ewald_dispersion(c, pos, field=True, **kd),
+        "dispersion_virial": lambda: tn.nfft_ewald_dispersion_virial(c, pos, **kd),
+        "masked_walk_op": lambda: tn.ops.nfft_ewald_lj_excl_near(pos, xs, None, *lists, *walk),
+        "unmasked_walk_op": lambda: tn.ops.nfft_ewald_lj_step_near(pos, xs, None, *walk),
+        "list_kernel_op": lambda: tn.ops.nfft_ewald_lj_excl_list(pos, xs, None, *lists, *walk)},
+        args.reps)
+    tn.ops.check_status()
+    ms = lambda v_: [round(e, 4) for e in v_]  # noqa: E731
+    med = {k: v_[0] for k, v_ in t.items()}
+    old = ("ewald_step", "dispersion_field", "dispersion_virial")
+    three = sum(med[k] for k in old)
+    print(json.dumps({"bench": "ewald_lj_excl_step", "box": box, "points": n, "listed_pairs": len(ex), "neighbours": args.neighbours,
+                      "tol": args.tol, "r_cut": round(r_c, 5), "alpha_coulomb": round(spc.alpha, 3),
+                      "alpha_dispersion": round(spd.alpha, 3), "N": N, "N_of_the_three_calls": [own_c.bandwidth, own_d.bandwidth],
+                      "m": m, "cells": list(spc.cells), "reps": args.reps, "median_min_max_ms": {k: ms(v_) for k, v_ in t.items()},
+                      "lj_excl_step_over_lj_step": round(med["lj_excl_step"] / med["lj_step"], 3),
+                      "lj_excl_step_over_lj_step_range": [round(t["lj_excl_step"][1] / t["lj_step"][2], 3),
+                                                          round(t["lj_excl_step"][2] / t["lj_step"][1], 3)],
+                      "three_calls_with_exclusions_ms": round(three, 4),
+                      "lj_excl_step_over_three_calls": round(med["lj_excl_step"] / three, 3),
+                      "ratio_range": [round(t["lj_excl_step"][1] / sum(t[k][2] for k in old), 3),
+                                      round(t["lj_excl_step"][2] / sum(t[k][1] for k in old), 3)],
+                      "masked_over_unmasked_walk_op": round(med["masked_walk_op"] / med["unmasked_walk_op"], 3)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, nargs="+", default=[100000, 1000000])
@@ -1167,7 +1252,8 @@ def main():
     ap.add_argument("--step", action="store_true",
                     help="time nfft_ewald_step beside the calls, pair loops and spectral passes it replaces (with --box, --exclusions)")
     ap.add_argument("--lj-step", action="store_true",
-                    help="time nfft_ewald_lj_step beside the three calls, pair loops and spectral passes it replaces (with --box)")
+                    help="time nfft_ewald_lj_step beside the three calls, pair loops and spectral passes it replaces (with --box); "
+                         "with --exclusions nfft_ewald_lj_excl_step on rigid triples beside it and beside the three calls")
     ap.add_argument("--bandwidth-as-is", action="store_true",
                     help="--lj-step: keep the bandwidths of from_tolerance instead of the next sizes with prime factors <= 7")
     ap.add_argument("--screening", type=float, default=1.0, help="--yukawa: lambda r_c, the screening parameter times r_c")
@@ -1176,9 +1262,8 @@ def main():
         ap.error("--box takes three or six comma-separated numbers")
     if args.step and (args.virial or args.dispersion or args.dipole or args.stokeslet or args.rpy or args.yukawa):
         ap.error("--step times the Coulomb sum's fused step on its own (with or without --box and --exclusions)")
-    if args.lj_step and (args.step or args.virial or args.dispersion or args.dipole or args.stokeslet or args.rpy or args.yukawa
-                         or args.exclusions):
-        ap.error("--lj-step times the Lennard-Jones + Coulomb step on its own (with or without --box)")
+    if args.lj_step and (args.step or args.virial or args.dispersion or args.dipole or args.stokeslet or args.rpy or args.yukawa):
+        ap.error("--lj-step times the Lennard-Jones + Coulomb step on its own (with or without --box and --exclusions)")
     if args.yukawa and (args.box is not None or args.dispersion or args.dipole or args.stokeslet or args.rpy or args.exclusions):
         ap.error("--yukawa times the unit cube on its own (with or without --virial)")
     if args.yukawa and not 0.0 < args.screening <= 50.0:
@@ -1197,7 +1282,7 @@ def main():
     lib = _lib.load()
     for n in args.points:
         if args.lj_step:
-            run_lj_step(lib, n, args)
+            (run_lj_excl_step if args.exclusions else run_lj_step)(lib, n, args)
             continue
         if args.step:
             run_step(lib, n, args)

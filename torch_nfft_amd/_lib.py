@@ -79,6 +79,10 @@ SYMBOLS = (
     "nfft_hip_ewald_lj_step_near",
     "nfft_hip_ewald_lj_step_spectral_workspace_bytes",
     "nfft_hip_ewald_lj_step_spectral",
+    "nfft_hip_ewald_lj_excl_near_workspace_bytes",
+    "nfft_hip_ewald_lj_excl_near",
+    "nfft_hip_ewald_lj_excl_list_workspace_bytes",
+    "nfft_hip_ewald_lj_excl_list",
     "nfft_hip_ewald_dipole_near",
     "nfft_hip_ewald_dipole_near_box",
     "nfft_hip_ewald_dipole_spectral",
@@ -333,6 +337,15 @@ def load():
     lib.nfft_hip_ewald_lj_step_spectral.argtypes = [i64, i64, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_double, vp,
                                                     vp, vp, i64, vp]
     lib.nfft_hip_ewald_lj_step_spectral.restype = ci
+    for f in (lib.nfft_hip_ewald_lj_excl_near_workspace_bytes, lib.nfft_hip_ewald_lj_excl_list_workspace_bytes):
+        f.argtypes = [ctypes.POINTER(EwaldBoxProblem), ctypes.c_double]
+        f.restype = i64
+    lib.nfft_hip_ewald_lj_excl_near.argtypes = [ctypes.POINTER(EwaldBoxProblem), ctypes.c_double, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                vp, vp, vp, i64, vp]
+    lib.nfft_hip_ewald_lj_excl_near.restype = ci
+    lib.nfft_hip_ewald_lj_excl_list.argtypes = [ctypes.POINTER(EwaldBoxProblem), ctypes.c_double, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                vp, vp, i64, vp]
+    lib.nfft_hip_ewald_lj_excl_list.restype = ci
     lib.nfft_hip_ewald_dipole_near.argtypes = [ctypes.POINTER(EwaldProblem), vp, vp, vp, vp, ctypes.c_int32, vp, vp, i64, vp]
     lib.nfft_hip_ewald_dipole_near.restype = ci
     lib.nfft_hip_ewald_dipole_near_box.argtypes = [ctypes.POINTER(EwaldBoxProblem), vp, vp, vp, vp, ctypes.c_int32, vp, vp, i64, vp]

@@ -769,6 +769,73 @@ int nfft_hip_ewald_lj_step_spectral(int64_t N, int64_t batch_size, const void *b
                                          pi2_over_alpha2, spectra, out8, ws, (hipStream_t)stream);
 }
 
+// ---- the same step with bonded-pair exclusions: the checks above, and the list's -------------
+static int validate_lj_excl(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_entries, const void *row_start,
+                            const void *col, const void *weight_coulomb, const void *weight_lj)
+{
+    if (int rc = validate_lj_step_near(p, alpha_dispersion)) return rc;
+    if (num_entries < 0) { set_error("Input mismatch: negative num_entries"); return NFFT_HIP_EINVAL; }
+    if (p->num_points >= (int64_t(1) << 31) || num_entries >= (int64_t(1) << 31)) {
+        set_error("Input mismatch: too many points or entries");
+        return NFFT_HIP_EINVAL;
+    }
+    if (p->num_points > 0 && (!row_start || (num_entries > 0 && (!col || !weight_coulomb || !weight_lj)))) {
+        set_error("Input mismatch: null list");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+int64_t nfft_hip_ewald_lj_excl_near_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion)
+{
+    if (validate_lj_step_near(p, alpha_dispersion)) return -1;
+    return ewald_lj_excl_near_workspace(p) + 256;
+}
+
+int nfft_hip_ewald_lj_excl_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_entries,
+                                const float *points, const float *xs, const int32_t *start, const int64_t *index,
+                                const int32_t *row_start, const int32_t *col, const float *weight_coulomb, const float *weight_lj,
+                                float *f, double *out8, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_lj_excl(p, alpha_dispersion, num_entries, row_start, col, weight_coulomb, weight_lj)) return rc;
+    if (!out8) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
+    if (p->num_points == 0) {  // (no row of f)
+        NFFT_HIP_CHECK(hipMemsetAsync(out8, 0, (size_t)(p->batch_size * 8) * sizeof(double), (hipStream_t)stream));
+        return 0;
+    }
+    if (!points || !xs || !start || !index || !f) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    char *ws = workspace_base(workspace, workspace_bytes, ewald_lj_excl_near_workspace(p) + 256);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_ewald_lj_excl_near(p, alpha_dispersion, num_entries, points, xs, start, index, row_start, col, weight_coulomb,
+                                     weight_lj, f, out8, ws, (hipStream_t)stream);
+}
+
+int64_t nfft_hip_ewald_lj_excl_list_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion)
+{
+    if (validate_lj_step_near(p, alpha_dispersion)) return -1;
+    return ewald_lj_excl_list_workspace(p) + 256;
+}
+
+int nfft_hip_ewald_lj_excl_list(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_entries,
+                                const float *points, const float *xs, const int32_t *row_start, const int32_t *col,
+                                const float *weight_coulomb, const float *weight_lj, const int32_t *set_start, float *f,
+                                double *out8, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_lj_excl(p, alpha_dispersion, num_entries, row_start, col, weight_coulomb, weight_lj)) return rc;
+    if (!out8) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
+    if (p->num_points == 0) {  // (no row of f)
+        NFFT_HIP_CHECK(hipMemsetAsync(out8, 0, (size_t)(p->batch_size * 8) * sizeof(double), (hipStream_t)stream));
+        return 0;
+    }
+    if (!points || !xs || !f || (p->batch_size > 1 && !set_start)) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    char *ws = workspace_base(workspace, workspace_bytes, ewald_lj_excl_list_workspace(p) + 256);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_ewald_lj_excl_list(p, alpha_dispersion, num_entries, points, xs, row_start, col, weight_coulomb, weight_lj,
+                                     set_start, f, out8, ws, (hipStream_t)stream);
+}
+
 // ---- the spectral step of the dipole sum -------------------------------------------------------
 int nfft_hip_ewald_dipole_spectral(int64_t N, int64_t batch_size, int64_t num_columns, int32_t order, const void *band,
                                    const float *coeffs, const double *box_inverse, void *out, void *stream)

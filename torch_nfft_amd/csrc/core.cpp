@@ -1619,6 +1619,87 @@ at::Tensor nfft_ewald_excl_virial(at::Tensor pos, at::Tensor x, c10::optional<at
     return out.reshape(shape);
 }
 
+// ---- bonded-pair exclusions of the Lennard-Jones + Coulomb step (not in the reference) ----------
+struct LjExclInput {
+    Points p;
+    ExclInput ex;
+    at::Tensor wl;
+    nfft_hip_ewald_box_problem q;
+};
+LjExclInput check_lj_excl(const at::Tensor &pos, const at::Tensor &xs, const c10::optional<at::Tensor> &opt_batch,
+                          const at::Tensor &row_start, const at::Tensor &col, const at::Tensor &weight_coulomb,
+                          const at::Tensor &weight_lj, const std::vector<double> &box, double alpha_coulomb, double r_cut)
+{
+    const Points p = check_points(pos, opt_batch, "batch");
+    CHECK_INPUT(p.dim == 3);
+    CHECK_INPUT(xs.scalar_type() == at::kFloat && xs.dim() == 2 && xs.size(0) == p.n && xs.size(1) == 3);
+    CHECK_INPUT(xs.device() == pos.device());
+    CHECK_INPUT(box.size() == 6);
+    const ExclInput ex = check_excl(row_start, col, weight_coulomb, pos, p.n);
+    CHECK_INPUT(weight_lj.scalar_type() == at::kFloat && weight_lj.dim() == 1 && weight_lj.numel() == ex.col.numel());
+    CHECK_INPUT(weight_lj.device() == pos.device());
+    return {p, ex, weight_lj.contiguous(), ewald_box_problem(p, 1, true, box, alpha_coulomb, r_cut)};
+}
+
+// (f, eight) of nfft_ewald_lj_step_near with the terms of the listed pairs scaled by 1 - weight before they are added: the
+// list is ExclusionList's CSR matrix over the points in the caller's order with the two weights 1 - s^C and 1 - s^L
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_lj_excl_near(at::Tensor pos, at::Tensor xs, c10::optional<at::Tensor> opt_batch,
+                                                           at::Tensor row_start, at::Tensor col, at::Tensor weight_coulomb,
+                                                           at::Tensor weight_lj, std::vector<double> box, double alpha_coulomb,
+                                                           double alpha_dispersion, double r_cut)
+{
+    TORCH_CHECK(xs.is_cuda(), "torch_nfft._nfft_ewald_lj_excl_near is currently only implemented for GPU tensors");
+    const LjExclInput in = check_lj_excl(pos, xs, opt_batch, row_start, col, weight_coulomb, weight_lj, box, alpha_coulomb, r_cut);
+    const Points &p = in.p;
+    const int64_t ws_bytes = nfft_hip_ewald_lj_excl_near_workspace_bytes(&in.q, alpha_dispersion);
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    // (zeros: a point whose coordinates are not numbers has no cell and is not written)
+    at::Tensor f = at::zeros({p.n, 3}, xs.options());
+    at::Tensor out = at::zeros({p.B, 8}, xs.options().dtype(at::kDouble));
+    if (p.n == 0) return {f, out};  // no launch
+    c10::DeviceGuard guard(xs.device());
+    const CellOrder o = torus_cell_order(p, in.q.cells);
+    const at::Tensor xr = real_rows(xs, true, p.n, 3, o.order);
+    at::Tensor ws = byte_buffer(ws_bytes, xs);
+    const bool any = in.ex.col.numel() > 0;
+    check_rc(nfft_hip_ewald_lj_excl_near(&in.q, alpha_dispersion, in.ex.col.numel(), o.pos.data_ptr<float>(), xr.data_ptr<float>(),
+                                         o.start.data_ptr<int32_t>(), o.order.data_ptr<int64_t>(),
+                                         in.ex.row_start.data_ptr<int32_t>(), any ? in.ex.col.data_ptr<int32_t>() : nullptr,
+                                         any ? in.ex.weight.data_ptr<float>() : nullptr, any ? in.wl.data_ptr<float>() : nullptr,
+                                         f.data_ptr<float>(), out.data_ptr<double>(), ws.data_ptr(), ws_bytes, stream_of(xs)));
+    return {f, out};
+}
+
+// (f, eight) to ADD to those of nfft_ewald_lj_excl_near: minus the listed pairs' smooth share (r < r_cut) or their whole
+// Coulomb and dispersion terms (r >= r_cut), on the positions reduced with torus_reduce as the walk's cell order reduces them
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_lj_excl_list(at::Tensor pos, at::Tensor xs, c10::optional<at::Tensor> opt_batch,
+                                                           at::Tensor row_start, at::Tensor col, at::Tensor weight_coulomb,
+                                                           at::Tensor weight_lj, std::vector<double> box, double alpha_coulomb,
+                                                           double alpha_dispersion, double r_cut)
+{
+    TORCH_CHECK(xs.is_cuda(), "torch_nfft._nfft_ewald_lj_excl_list is currently only implemented for GPU tensors");
+    const LjExclInput in = check_lj_excl(pos, xs, opt_batch, row_start, col, weight_coulomb, weight_lj, box, alpha_coulomb, r_cut);
+    const Points &p = in.p;
+    const int64_t ws_bytes = nfft_hip_ewald_lj_excl_list_workspace_bytes(&in.q, alpha_dispersion);
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    at::Tensor f = at::zeros({p.n, 3}, xs.options());
+    at::Tensor out = at::zeros({p.B, 8}, xs.options().dtype(at::kDouble));
+    if (p.n == 0 || in.ex.col.numel() == 0) return {f, out};  // no launch
+    c10::DeviceGuard guard(xs.device());
+    const at::Tensor red = torus_reduce(p.pos).contiguous();
+    const at::Tensor xr = xs.contiguous();
+    at::Tensor set_start;
+    if (p.batch.defined())
+        set_start = at::searchsorted(p.batch, at::arange(p.B + 1, p.batch.options()), /*out_int32=*/true).contiguous();
+    at::Tensor ws = byte_buffer(ws_bytes, xs);
+    check_rc(nfft_hip_ewald_lj_excl_list(&in.q, alpha_dispersion, in.ex.col.numel(), red.data_ptr<float>(), xr.data_ptr<float>(),
+                                         in.ex.row_start.data_ptr<int32_t>(), in.ex.col.data_ptr<int32_t>(),
+                                         in.ex.weight.data_ptr<float>(), in.wl.data_ptr<float>(),
+                                         set_start.defined() ? set_start.data_ptr<int32_t>() : nullptr, f.data_ptr<float>(),
+                                         out.data_ptr<double>(), ws.data_ptr(), ws_bytes, stream_of(xs)));
+    return {f, out};
+}
+
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
 at::TensorOptions current_device_options(at::ScalarType dtype)
 {
@@ -1788,6 +1869,13 @@ TORCH_LIBRARY(torch_nfft, m)
     m.def("_nfft_ewald_yukawa_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha, float r_cut, "
           "float screening) -> Tensor", &nfft_ewald_yukawa_virial_near);
     // not in the reference: what a list of bonded pairs takes out of the Coulomb and dispersion Ewald sums and their virials
+    // not in the reference: the Lennard-Jones + Coulomb step with bonded-pair exclusions (nfft_ewald_lj_excl_step)
+    m.def("_nfft_ewald_lj_excl_near(Tensor pos, Tensor xs, Tensor? batch, Tensor row_start, Tensor col, Tensor weight_coulomb, "
+          "Tensor weight_lj, float[] box, float alpha_coulomb, float alpha_dispersion, float r_cut) -> (Tensor, Tensor)",
+          &nfft_ewald_lj_excl_near);
+    m.def("_nfft_ewald_lj_excl_list(Tensor pos, Tensor xs, Tensor? batch, Tensor row_start, Tensor col, Tensor weight_coulomb, "
+          "Tensor weight_lj, float[] box, float alpha_coulomb, float alpha_dispersion, float r_cut) -> (Tensor, Tensor)",
+          &nfft_ewald_lj_excl_list);
     m.def("_nfft_ewald_excl(Tensor pos, Tensor x, Tensor? batch, Tensor row_start, Tensor col, Tensor weight, float[] box, "
           "float alpha, int kind, bool with_field) -> (Tensor, Tensor)", &nfft_ewald_excl);
     m.def("_nfft_ewald_excl_virial(Tensor pos, Tensor x, Tensor? batch, Tensor row_start, Tensor col, Tensor weight, "

@@ -248,6 +248,19 @@ int launch_ewald_lj_step_near(const nfft_hip_ewald_box_problem *p, double alpha_
 int launch_ewald_lj_step_spectral(int64_t N, int64_t batch_size, const void *band, const float *coeffs_coulomb,
                                   const float *coeffs_dispersion, const float *strain_dispersion, const double *box_inverse,
                                   double pi2_over_alpha2, void *spectra, double *out, void *workspace, hipStream_t stream);
+// ewald_lj_excl.hip (bonded-pair exclusions of the Lennard-Jones + Coulomb step): the masked pair walk
+// and the list kernel, arguments as nfft_hip_ewald_lj_excl_near / _list; `workspace`: ewald_lj_excl_near_workspace(p) bytes,
+// 256-byte aligned (as ewald_lj_step_near_workspace), and ewald_lj_excl_list_workspace(p) bytes, 8-byte aligned
+int64_t ewald_lj_excl_near_workspace(const nfft_hip_ewald_box_problem *p);
+int64_t ewald_lj_excl_list_workspace(const nfft_hip_ewald_box_problem *p);
+int launch_ewald_lj_excl_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_entries, const float *pos,
+                              const float *xs, const int *start, const int64_t *index, const int *row_start, const int *col,
+                              const float *weight_coulomb, const float *weight_lj, float *f, double *out, void *workspace,
+                              hipStream_t stream);
+int launch_ewald_lj_excl_list(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_entries, const float *pos,
+                              const float *xs, const int *row_start, const int *col, const float *weight_coulomb,
+                              const float *weight_lj, const int *set_start, float *f, double *out, void *workspace,
+                              hipStream_t stream);
 // ewald_step.hip (potential, field, energy and virial of the Ewald sum in one pair walk and one spectral pass, DESIGN.md
 // section 7q): arguments as nfft_hip_ewald_step_near / _spectral, the workspaces those of ewald_virial.hip
 // (ewald_virial_near_workspace, ewald_virial_far_workspace), the second level its launch_virial_sum

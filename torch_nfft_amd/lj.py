@@ -19,6 +19,7 @@ import torch
 
 from . import ops
 from .dispersion import DispersionSplitting
+from .exclusions import check_exclusions
 from .ewald import EwaldSplitting, _IDENTITY6, _fractional, _set_sums, _voigt_to_matrix
 from .nfft import nfft_adjoint, nfft_forward
 
@@ -104,19 +105,53 @@ def nfft_ewald_lj_step(q, c, a, pos, batch=None, /, coulomb=None, dispersion=Non
     Coincident points do not see each other.  The pair walk works in float32: separations below ``1.6e-5``, or so small that
     ``12 a_i a_j / r^14`` exceeds ``3.4e38``, give values that are not numbers.
 
-    Exclusions are out of scope and there is no ``exclusions=`` keyword.  The subtract-afterwards correction that serves
-    ``1/r`` would leave a rounding of ``2^-24 a_i a_j / r^12`` per bonded pair, which at bonded distances is not small; bonded
-    pairs need masking inside the pair loop.
+    Exclusions are not handled here and there is no ``exclusions=`` keyword: ``nfft_ewald_lj_excl_step`` is this call with an
+    ``ExclusionList``.  It scales the terms of bonded pairs inside the pair loop, since the subtract-afterwards correction
+    that serves ``1/r`` would leave a rounding of ``2^-24 a_i a_j / r^12`` per bonded pair, which at bonded distances is not small.
 
     Runs under ``torch.no_grad()``: all four outputs are constants to autograd.  Inputs that require grad are accepted and get
     no gradient from here; ``batch`` must not require grad (AssertionError)."""
-    what = "nfft_ewald_lj_step"
+    return _lj_step("nfft_ewald_lj_step", q, c, a, pos, batch, coulomb, dispersion, None, cutoff, fractional)
+
+
+def nfft_ewald_lj_excl_step(q, c, a, pos, batch=None, /, coulomb=None, dispersion=None, exclusions=None, cutoff=4, fractional=False):
+    """``(F, U_coulomb, U_lj, W)`` of ``nfft_ewald_lj_step`` with bonded-pair exclusions: the same
+    inputs, outputs, checks and ``no_grad`` behaviour, and ``exclusions``, an ``ExclusionList`` over the points of ``pos`` or
+    ``None`` (TypeError, ValueError as for ``nfft_ewald(exclusions=)``).  With ``None`` it returns exactly what
+    ``nfft_ewald_lj_step`` returns, by that code path.
+
+    The Coulomb scale ``s^C`` of a listed pair is the list's ``coulomb_scale``; the Lennard-Jones scale ``s^L`` is its
+    ``dispersion_scale`` and applies to BOTH powers, ``r^-6`` and ``r^-12`` (AMBER and OPLS scale the whole 1-4 Lennard-Jones
+    term; a force field with separate 1-4 parameters is not covered).  With ``w = 1 - s``, ``d`` the minimum image of
+    ``x_i - x_j`` as the pair sweeps form it and ``r = |d|``, each listed pair once, the ONE image that the bond refers to loses::
+
+        U_C  -= w^C q_i q_j / r                F_i -= w^C q_i q_j d / r^3               W -= w^C q_i q_j d d^T / r^3
+        U_LJ -= w^L (a_i a_j / r^12 [r < r_cut] - c_i c_j / r^6)
+        F_i  -= w^L (12 a_i a_j / r^14 [r < r_cut] - 6 c_i c_j / r^8) d                  (F_j the opposite; W likewise with d d^T)
+
+    and ``tr W = U_C - 6 U_D + 12 U_R`` holds for the corrected converged sums.  A listed pair at ``r = 0`` (a virtual site on
+    its atom) takes ``U_C -= w^C q_i q_j 2 alpha_C / sqrt(pi)`` and ``U_LJ += w^L c_i c_j alpha_D^6 / 6``, no force, no virial
+    term and no repulsion, which makes the sums continuous in ``r -> 0`` for a fully excluded pair; with ``s > 0`` a coincident
+    pair is the caller's error.
+
+    Nothing is subtracted afterwards from a large number: the pair walk looks every passing pair up in the list (a binary
+    search of the lane's row, for the pairs whose index falls between the row's ends only) and scales its terms by ``s`` before
+    they reach an accumulator -- a fully excluded pair adds nothing at all -- and a second native step over the list removes
+    the smooth share of the listed pairs that the far field holds, ``erf(alpha_C r) / r`` and ``1 / r^6`` minus the dispersion
+    pair weight, which are bounded by their values at ``r = 0``.  Both steps use no atomics and give the same bits on every
+    call; the transforms and the spectral step are those of ``nfft_ewald_lj_step``."""
+    return _lj_step("nfft_ewald_lj_excl_step", q, c, a, pos, batch, coulomb, dispersion, exclusions, cutoff, fractional)
+
+
+def _lj_step(what, q, c, a, pos, batch, coulomb, dispersion, exclusions, cutoff, fractional):
+    """the body of both calls; exclusions=None is nfft_ewald_lj_step"""
     _check_splittings(what, coulomb, dispersion)
     if pos.dim() != 2 or pos.size(1) != 3:
         raise ValueError("%s: the periodic sums are three-dimensional, pos must be [n, 3]" % what)
     if batch is not None and batch.requires_grad:
         raise AssertionError("%s: batch holds point-set indices and must not require grad" % what)
     q, c, a = _check_values(what, (q, c, a), pos)
+    ex = check_exclusions(what, exclusions, pos)
     with torch.no_grad():
         pos = _fractional(what, pos.detach(), coulomb, fractional)
         alpha_c, alpha_d, N = coulomb.alpha, dispersion.alpha, coulomb.bandwidth
@@ -125,8 +160,17 @@ def nfft_ewald_lj_step(q, c, a, pos, batch=None, /, coulomb=None, dispersion=Non
         spectra, far8 = ops.nfft_ewald_lj_step_spectral(band, coulomb.coeffs, dispersion.coeffs, dispersion.strain_coeffs(), box6,
                                                         alpha_c)
         far = nfft_forward(spectra, pos, batch, cutoff=int(cutoff), real_output=True)  # [n, 6]: E, then G
-        f, near8 = ops.nfft_ewald_lj_step_near(pos, torch.stack([q, c, a], 1), batch, box6, alpha_c, alpha_d, coulomb.r_cut)
-        F = f + q.unsqueeze(1) * far[:, :3] - c.unsqueeze(1) * far[:, 3:]
+        xs = torch.stack([q, c, a], 1)
+        if ex is None:
+            f, near8 = ops.nfft_ewald_lj_step_near(pos, xs, batch, box6, alpha_c, alpha_d, coulomb.r_cut)
+            F = f + q.unsqueeze(1) * far[:, :3] - c.unsqueeze(1) * far[:, 3:]
+        else:
+            # the listed pairs come scaled out of the walk; the list step takes their smooth share back out of the far field
+            lists = (ex.row_start, ex.col, ex.coulomb_weight, ex.dispersion_weight)
+            f, near8 = ops.nfft_ewald_lj_excl_near(pos, xs, batch, *lists, box6, alpha_c, alpha_d, coulomb.r_cut)
+            lf, list8 = ops.nfft_ewald_lj_excl_list(pos, xs, batch, *lists, box6, alpha_c, alpha_d, coulomb.r_cut)
+            F = (f.double() + lf.double() + (q.unsqueeze(1) * far[:, :3] - c.unsqueeze(1) * far[:, 3:]).double()).float()
+            near8 = near8 + list8
         eight = far8 + near8  # [B, 8] float64
         q64, c64 = q.double(), c.double()
         total = _set_sums(q64, batch)[0]

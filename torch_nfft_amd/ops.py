@@ -287,6 +287,30 @@ def nfft_ewald_lj_step_spectral(band, coeffs_coulomb, coeffs_dispersion, strain_
                                              float(alpha_coulomb))
 
 
+def nfft_ewald_lj_excl_near(pos, xs, batch, row_start, col, weight_coulomb, weight_lj, box, alpha_coulomb, alpha_dispersion, r_cut):
+    """torch_nfft::_nfft_ewald_lj_excl_near(Tensor pos, Tensor xs, Tensor? batch, Tensor row_start, Tensor col,
+    Tensor weight_coulomb, Tensor weight_lj, float[] box, float alpha_coulomb, float alpha_dispersion, float r_cut) ->
+    (Tensor, Tensor) (not in the reference): ``(f, eight)`` of ``nfft_ewald_lj_step_near`` with the terms of the listed pairs
+    scaled BEFORE they are added -- ``q_i q_j`` by ``s^C = 1 - weight_coulomb``, ``c_i c_j`` and ``a_i a_j`` by
+    ``s^L = 1 - weight_lj``; a pair with both scales zero adds nothing.  ``row_start`` ``[n + 1]`` int32, ``col`` ``[2 m]`` int32
+    and the weights ``[2 m]`` float32 are an ``ExclusionList``'s.  With an empty list the bits of ``nfft_ewald_lj_step_near``.
+    One native call (``nfft_hip_ewald_lj_excl_near``), no atomics: two calls give the same bits."""
+    return _ops._nfft_ewald_lj_excl_near(pos, xs, batch, row_start, col, weight_coulomb, weight_lj, [float(a) for a in box],
+                                         float(alpha_coulomb), float(alpha_dispersion), float(r_cut))
+
+
+def nfft_ewald_lj_excl_list(pos, xs, batch, row_start, col, weight_coulomb, weight_lj, box, alpha_coulomb, alpha_dispersion, r_cut):
+    """torch_nfft::_nfft_ewald_lj_excl_list(Tensor pos, Tensor xs, Tensor? batch, Tensor row_start, Tensor col,
+    Tensor weight_coulomb, Tensor weight_lj, float[] box, float alpha_coulomb, float alpha_dispersion, float r_cut) ->
+    (Tensor, Tensor) (not in the reference): ``(f, eight)`` to ADD to those of ``nfft_ewald_lj_excl_near`` -- minus the share of
+    the listed pairs that the far field holds (``r < r_cut``, ``r = 0`` included: ``w^C q_i q_j erf(alpha_C r) / r`` and
+    ``-w^L c_i c_j (1 / r^6 - w_D)``, with their slopes) or, beyond the cut, their whole ``1 / r`` and ``1 / r^6`` terms.
+    ``f`` ``[n, 3]`` float32 in row order, ``eight`` ``[B, 8]`` float64 with each pair once.  Bounded values only.  One native
+    call (``nfft_hip_ewald_lj_excl_list``), no atomics: two calls give the same bits."""
+    return _ops._nfft_ewald_lj_excl_list(pos, xs, batch, row_start, col, weight_coulomb, weight_lj, [float(a) for a in box],
+                                         float(alpha_coulomb), float(alpha_dispersion), float(r_cut))
+
+
 def nfft_ewald_dispersion_virial_near(pos, x, batch, box, alpha, r_cut):
     """torch_nfft::_nfft_ewald_dispersion_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha,
     float r_cut) -> Tensor (not in the reference): ``nfft_ewald_virial_near`` for the dispersion sum, ``[B, 7, *cols]``
