@@ -631,6 +631,34 @@ int nfft_hip_ewald_lj_excl_list(const nfft_hip_ewald_box_problem *p, double alph
                                 const float *weight_coulomb, const float *weight_lj, const int32_t *set_start, float *f,
                                 double *out8, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- the same walk with per-type-pair Lennard-Jones parameters (no reference counterpart) ----
+ * For force fields whose C6_ij and C12_ij are not products of per-point numbers (Lorentz-Berthelot mixing, fitted cross
+ * terms).  Point j carries a charge q_j and the coefficient c_j that the GRID sees, packed as xs [points, 2], and a type
+ * types[j] in [0, num_types), int32 [points]; xs and types in the cell order of `points`.  table is float32
+ * [num_types, num_types, 2] = (C12(t, t'), dC6(t, t')), symmetric in (t, t'), where dC6 is what the pair's C6 has above the
+ * product c_i c_j that the far field carries.  A type outside [0, num_types) is clamped into it: nothing is read outside
+ * the table.  With w_C, mg_C, w_D, mg_D as for nfft_hip_ewald_lj_step_near, over the pairs 0 < r_ij < r_cut and
+ * s_ij = q_i q_j mg_C - c_i c_j mg_D + 12 C12 / r^14 - 6 dC6 / r^8:
+ *     f[index[i], a] = sum_j s_ij d_ij[a]                                                      float32 [points, 3]
+ *     out8[b, 0]     = 1/2 sum_ij q_i q_j w_C                                                  float64 [batch_size, 8]
+ *     out8[b, 1]     = 1/2 sum_ij (C12 / r^12 - dC6 / r^6 - c_i c_j w_D)
+ *     out8[b, 2 + e] = 1/2 sum_ij s_ij d_ij[a] d_ij[b],   e = 0 .. 5: ab = xx, yy, zz, yz, xz, xy
+ * The list (row_start, col, weight_coulomb, weight_lj, num_entries) is that of nfft_hip_ewald_lj_excl_near: a listed pair's
+ * q_i q_j is scaled by s^C and its c_i c_j, C12 and dC6 by s^L before they are added, and nfft_hip_ewald_lj_excl_list on
+ * (q, c, 0) removes the far field's share.  All four list pointers null and num_entries = 0: no list, and a kernel that
+ * holds no list code; with a list of no entries the bits are the same.  Separations below 1.6e-5, or at which
+ * 12 C12 / r^14 or 6 dC6 / r^8 leaves float32, give values that are not numbers.
+ *
+ * Checks, limits, error codes and the workspace are those of nfft_hip_ewald_lj_excl_near; in addition num_types outside
+ * [1, 32], a null table, a table that is not 8-byte aligned (an entry moves as one load) and list pointers without row_start
+ * are refused ("Input mismatch").  With no points out8 is set to zero.  No atomics: two calls give the same bits. */
+int64_t nfft_hip_ewald_lj_table_near_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion);
+int nfft_hip_ewald_lj_table_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_types, int64_t num_entries,
+                                 const float *points, const float *xs, const int32_t *types, const float *table,
+                                 const int32_t *start, const int64_t *index, const int32_t *row_start, const int32_t *col,
+                                 const float *weight_coulomb, const float *weight_lj, float *f, double *out8, void *workspace,
+                                 int64_t workspace_bytes, void *stream);
+
 /* ---- Ewald sum of point charges and point dipoles (no reference counterpart) ----
  * Source j carries a charge q_j and a Cartesian dipole mu_j, packed as xs [points, 4, num_columns] = (q, mu_x, mu_y, mu_z).
  * With d = d_ij, r = |d|, m = mu_j . d and the Smith functions B_0 = erfc(alpha r) / r,

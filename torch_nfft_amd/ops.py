@@ -311,6 +311,23 @@ def nfft_ewald_lj_excl_list(pos, xs, batch, row_start, col, weight_coulomb, weig
                                          float(alpha_coulomb), float(alpha_dispersion), float(r_cut))
 
 
+def nfft_ewald_lj_table_near(pos, xs, types, table, batch, row_start, col, weight_coulomb, weight_lj, box, alpha_coulomb,
+                             alpha_dispersion, r_cut):
+    """torch_nfft::_nfft_ewald_lj_table_near(Tensor pos, Tensor xs, Tensor types, Tensor table, Tensor? batch,
+    Tensor? row_start, Tensor? col, Tensor? weight_coulomb, Tensor? weight_lj, float[] box, float alpha_coulomb,
+    float alpha_dispersion, float r_cut) -> (Tensor, Tensor) (not in the reference): ``(f, eight)`` of
+    ``nfft_ewald_lj_step_near`` with per-type-pair parameters.  ``xs`` ``[n, 2]`` float32 holds ``(q, c)`` with ``c`` the
+    coefficient that the grid sees, ``types`` ``[n]`` int32 the points' types and ``table`` ``[T, T, 2]`` float32
+    ``(C12, dC6)`` per pair of types, ``1 <= T <= 32``, with ``dC6 = C6 - c_i c_j``: the pair slope is ``q_i q_j mg_C -
+    c_i c_j mg_D + 12 C12 / r^14 - 6 dC6 / r^8`` and the second energy ``1/2 sum (C12 / r^12 - dC6 / r^6 - c_i c_j w_D)``.  A type
+    outside ``[0, T)`` is clamped.  The four list tensors are an ``ExclusionList``'s, all of them or all ``None``; with them
+    ``q_i q_j`` of a listed pair is scaled by ``s^C`` and ``c_i c_j``, ``C12``, ``dC6`` by ``s^L`` before they are added, and an
+    empty list gives the bits of the call without one.  One native call (``nfft_hip_ewald_lj_table_near``; DESIGN.md section
+    7t), no atomics: two calls give the same bits."""
+    return _ops._nfft_ewald_lj_table_near(pos, xs, types, table, batch, row_start, col, weight_coulomb, weight_lj,
+                                          [float(a) for a in box], float(alpha_coulomb), float(alpha_dispersion), float(r_cut))
+
+
 def nfft_ewald_dispersion_virial_near(pos, x, batch, box, alpha, r_cut):
     """torch_nfft::_nfft_ewald_dispersion_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha,
     float r_cut) -> Tensor (not in the reference): ``nfft_ewald_virial_near`` for the dispersion sum, ``[B, 7, *cols]``
