@@ -13,6 +13,8 @@ built from the counts:
                      live lanes) and, per item, the lengths of the ranges that it sweeps
 ``point_groups``     per point, which edge of the frame computes it: the second wave of an item, the last and partly idle item
                      of a cut cell
+``pair_streams``     per pair of points and per direction: the item that computes one end, the range of its walk that holds the
+                     other, and the LDS tile in which that one is staged (tests/pair_frame_lists_ref.py)
 ``LAYOUTS``          the three layouts of tests/test_gpu_pair_frame_edges.py, whose coverage tests/test_pair_frame_ref.py asserts
 
 What the walk does on a G0 = 3 grid: the items of the cells c0 = 0 and c0 = 2 sweep every row in two ranges (one cell, then
@@ -162,8 +164,9 @@ def _sorted(points, batch, cells):
     return key, order, start
 
 
-def _walk(k, start, G0, G1, G2):
-    """WrappedWalk of the cell k (counted over all point sets): the lengths of the ranges [first, last) that it hands on"""
+def _walk(k, start, G0, G1, G2, bounds=False):
+    """WrappedWalk of the cell k (counted over all point sets): the lengths of the ranges [first, last) that it hands on;
+    with `bounds` the ranges themselves, [m, 2] int64 of (first, last) in the cell order"""
     c0, c1, c2 = k % G0, (k // G0) % G1, (k // (G0 * G1)) % G2
     set0 = k - (c2 * G1 + c1) * G0 - c0  # first cell of the point set
     split = c0 == 0 or c0 == G0 - 1
@@ -176,10 +179,11 @@ def _walk(k, start, G0, G1, G2):
         for d1 in (-1, 0, 1):
             w1 = G1 - 1 if c1 + d1 < 0 else (0 if c1 + d1 >= G1 else c1 + d1)
             row = set0 + (w2 * G1 + w1) * G0
-            swept.append(int(start[row + hi0] - start[row + lo0]))
+            swept.append((int(start[row + lo0]), int(start[row + hi0])))
             if split:
-                swept.append(int(start[row + hi1] - start[row + lo1]))
-    return np.array(swept, dtype=np.int64)
+                swept.append((int(start[row + lo1]), int(start[row + hi1])))
+    swept = np.array(swept, dtype=np.int64)
+    return swept if bounds else swept[:, 1] - swept[:, 0]
 
 
 def frame_geometry(points, batch, cells):
@@ -214,6 +218,44 @@ def point_groups(points, batch, cells):
     second[order] = rank % NEAR_BLOCK >= WAVE
     last[order] = (size > NEAR_BLOCK) & (size % NEAR_BLOCK != 0) & (rank >= (size // NEAR_BLOCK) * NEAR_BLOCK)
     return second, last
+
+
+def pair_streams(points, batch, cells, pairs):
+    """Where the walk of one end of a pair meets the other end.  `pairs` [m, 2] holds caller-order indices (i, j) of two points
+    of one point set; direction 0 is "i is computed, j is streamed", direction 1 the reverse.  Returns a dict of int64 [m, 2]
+    arrays, one column per direction:
+      ``item``    the work item that computes the output point, an index into frame_geometry's items
+      ``range``   which of that item's ranges (in the walk's order) holds the streamed point
+      ``first``, ``last``  that range in the cell order
+      ``offset``  the streamed point's place in it; ``tile`` = offset // kNearTile, the LDS tile it is staged in
+    The 27 cells of a walk are distinct (every G_a >= 3), so at most one range holds the streamed point (asserted); where the
+    two cells are no neighbours, or the ends lie in two point sets, the walk never meets it: -1 in every array but ``item``."""
+    G0, G1, G2 = (int(g) for g in cells)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    _, order, start = _sorted(points, batch, cells)
+    n = order.shape[0]
+    place = np.empty(n, np.int64)
+    place[order] = np.arange(n)  # the caller's index -> the place in the cell order
+    cell = np.searchsorted(start, np.arange(n), side="right") - 1  # of the sorted points
+    items_before = np.concatenate([[0], np.cumsum(-(-(start[1:] - start[:-1]) // NEAR_BLOCK))])  # items of the cells before
+    out = {k: np.full(pairs.shape, -1, np.int64) for k in ("item", "range", "first", "last", "offset", "tile")}
+    walks = {}
+    for direction in (0, 1):
+        pi, pj = place[pairs[:, direction]], place[pairs[:, 1 - direction]]
+        ki = cell[pi]
+        out["item"][:, direction] = items_before[ki] + (pi - start[ki]) // NEAR_BLOCK
+        for k in np.unique(ki):
+            if k not in walks:
+                walks[k] = _walk(int(k), start, G0, G1, G2, bounds=True)
+            rows = np.flatnonzero(ki == k)
+            inside = (pj[rows, None] >= walks[k][None, :, 0]) & (pj[rows, None] < walks[k][None, :, 1])
+            assert (inside.sum(1) <= 1).all()
+            rows, r = rows[inside.any(1)], inside.argmax(1)[inside.any(1)]
+            out["range"][rows, direction] = r
+            out["first"][rows, direction], out["last"][rows, direction] = walks[k][r, 0], walks[k][r, 1]
+    out["offset"] = np.where(out["first"] >= 0, np.stack([place[pairs[:, 1]], place[pairs[:, 0]]], 1) - out["first"], -1)
+    out["tile"] = out["offset"] // NEAR_TILE
+    return out
 
 
 # ---- the three layouts -------------------------------------------------------------------------------------------------

@@ -11,6 +11,9 @@ takes the moved float32 values, and the separations are asserted again on them.
 
 Tolerances.  Each gate is 4 x the largest relative error of the first device run against the float64 restatement, written
 beside it, and none may exceed 1e-4 (the condition of section 7r); rel_l2 for F, rel_fro for W, the relative error for U.
+
+The edges of the pair kernels' frame -- counted cells, listed partners in a second and third LDS tile, every row shape of the
+search, the list kernel's second loop trip and its weights in r -- are in tests/test_gpu_pair_frame_lists.py.
 """
 import math
 

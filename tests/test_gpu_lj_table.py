@@ -10,6 +10,9 @@ moved by (+3, -2, +1) lattice vectors, which rounds it to float32 once more; the
 
 Tolerances.  Each gate is 4 x the largest relative error of the first device run against the float64 restatement, written
 beside it, and none may exceed 1e-4 (the condition of section 7r); rel_l2 for F, rel_fro for W, the relative error for U.
+
+The edges of the pair kernels' frame -- counted cells with 32 types mixed within a half wave, with and without a list -- are
+in tests/test_gpu_pair_frame_lists.py.
 """
 import math
 
