@@ -1,5 +1,7 @@
 """Point plans at the level of their tables: nfft_hip_plan_points against a torch reimplementation of the binning.
 
+Geometry and table offsets come from the layout entry nfft_dbg_plan_layout, and every plan is also compared exactly with the
+numpy reference of tests/plan_ref.py (tests/test_gpu_plan_edges.py has the small cases that stand on the sort's boundaries).
 The plan's order inside a plan bin has never been fixed (LDS atomics hand out the slots), so nothing here depends on it:
 every point appears once, every entry lies inside the offsets range of the plan bin its coordinates give, the last
 offset is the entry count, and -- for plans in column-group order -- the groups inside every slab come in order 0, 1, 2.
@@ -12,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import plan_ref
 from conftest import rel_l2
 from oracle import nfft_ref
 
@@ -26,21 +29,6 @@ def lib():
     return _lib.load()
 
 
-def _align(v, a=256):
-    return (v + a - 1) // a * a
-
-
-def _tiling(d, N, m):
-    """(tile extents of the internal axes 1, 2, plan bins per pencil along axis 0) of the plans these tests
-    build: the matrix-core tiling for 3-D (scatter variant, one bin per slab), 32 x 32 tiles for 2-D, 256 cells for 1-D."""
-    W = 2 * m + 2
-    if d == 3:
-        return 33 - W, 65 - W, 2 * N
-    if d == 2:
-        return 32, 32, 1
-    return 1, 256, 1
-
-
 def _plan(lib, d, N, m, pos, batch, B):
     from torch_nfft_amd import _lib
     n = pos.shape[0]
@@ -52,41 +40,37 @@ def _plan(lib, d, N, m, pos, batch, B):
     _lib.check(lib.nfft_hip_plan_points(ctypes.byref(prob), p(pos), p(batch), p(plan), nbytes, s))
     torch.cuda.synchronize()
     _lib.check_status()
-    return plan
+    return plan, _lib.plan_layout(prob, 0)[0]
 
 
 def _check_plan(lib, d, N, m, pos, batch=None, B=1, groups=False):
-    """Builds the plan of (pos, batch) and checks its tables against the binning recomputed here."""
+    """Builds the plan of (pos, batch) and checks its tables: against the binning recomputed here with torch, and exactly
+    against the reference of tests/plan_ref.py.  Geometry and table offsets come from the layout entry."""
     n = pos.shape[0]
     M = 2 * N
-    T1, T2, np0 = _tiling(d, N, m)
-    nt1 = -(-M // T1) if d >= 2 else 1
-    nt2 = -(-M // T2)
-    tiles_per_batch = np0 * nt1 * nt2
-    ntiles = tiles_per_batch * B
-    plan = _plan(lib, d, N, m, pos, batch, B)
-    # layout (binning.hip plan_layout): offsets | cursors | seal block (256 B) | perm (1-D / 2-D) | tile-ordered points
-    off_cursor = _align((ntiles + 1) * 4)
-    off_seal = off_cursor + _align((ntiles + 1) * 4)
-    off_perm = off_seal + 256
-    off_spos = _align(off_perm + (0 if d == 3 else n * 4))
-    offsets = plan[: (ntiles + 1) * 4].view(torch.int32).long()
+    plan, L = _plan(lib, d, N, m, pos, batch, B)
+    assert (L.dim, L.M, L.cap, L.grouped) == (d, M, n, groups)
+    T1, T2, np0, nt2 = L.Ta1, L.Ta2, L.np0, L.nta2
+    tiles_per_batch, ntiles = L.tiles_per_batch, L.ntiles
+    offsets = plan[L.off_offsets: L.off_offsets + (ntiles + 1) * 4].view(torch.int32).long()
     assert int(offsets[0]) == 0
     assert int(offsets[-1]) == n  # the last offset is the entry count
     assert bool((offsets[1:] >= offsets[:-1]).all())
     if d == 3:
-        rec = plan[off_spos: off_spos + n * 16].view(torch.float32).view(n, 4)
+        rec = plan[L.off_spos: L.off_spos + n * 16].view(torch.float32).view(n, 4)
         idx = rec[:, 3].contiguous().view(torch.int32).long()
         coords = rec[:, :3]
     else:
-        idx = plan[off_perm: off_perm + n * 4].view(torch.int32).long()
-        coords = plan[off_spos: off_spos + n * d * 4].view(torch.float32).view(n, d)
+        idx = plan[L.off_perm: L.off_perm + n * 4].view(torch.int32).long()
+        coords = plan[L.off_spos: L.off_spos + n * d * 4].view(torch.float32).view(n, d)
     # every point appears once, with its own coordinates
     assert bool(((idx >= 0) & (idx < n)).all())
     assert int(torch.bincount(idx, minlength=n).max()) == 1
     assert torch.equal(coords, pos[idx])
+    # (a float64 floor: split_cell's cell for all but coordinates a hair below zero, which these inputs do not have --
+    # tests/plan_ref.py cells() is the exact statement, and check_plan below uses it)
     cell = torch.remainder(torch.floor(coords.double() * M).long(), M)
-    c0 = cell[:, 0] if d == 3 else torch.zeros_like(idx)
+    c0 = cell[:, 0] // L.bin0 if d == 3 else torch.zeros_like(idx)
     c1 = cell[:, d - 2] if d >= 2 else torch.zeros_like(idx)
     c2 = cell[:, d - 1]
     b = batch[idx] if batch is not None else torch.zeros_like(idx)
@@ -102,6 +86,9 @@ def _check_plan(lib, d, N, m, pos, batch=None, B=1, groups=False):
         grp = torch.where(col + W <= 32, 0, torch.where(col >= 32, 2, 1))
         same = tile[1:] == tile[:-1]
         assert bool((grp[1:][same] >= grp[:-1][same]).all())
+    # ... and exactly: offsets, the points of every bin, bit-equal records, the group words
+    plan_ref.check_plan(L, plan_ref.cut_tables(L, plan.cpu().numpy()), pos.cpu().numpy(),
+                        batch.cpu().numpy() if batch is not None else None)
     return plan
 
 

@@ -407,6 +407,9 @@ def load():
     if hasattr(lib, "nfft_dbg_route"):
         lib.nfft_dbg_route.argtypes = [P, i64, vp]
         lib.nfft_dbg_route.restype = ci
+    if hasattr(lib, "nfft_dbg_plan_layout"):
+        lib.nfft_dbg_plan_layout.argtypes = [P, i64, vp, vp]
+        lib.nfft_dbg_plan_layout.restype = ci
     if hasattr(lib, "nfft_dbg_work_list"):
         lib.nfft_dbg_work_list.argtypes = [P, vp, ci, vp, vp, vp, i64, vp]
         lib.nfft_dbg_work_list.restype = ci
@@ -488,6 +491,35 @@ def route(problem, real_columns):
     check(load().nfft_dbg_route(ctypes.byref(problem), real_columns, out))
     return Route(bool(out[0]), bool(out[1]), bool(out[2]), SPREAD_MODES[out[3]], bool(out[4]), GATHER_KERNELS[out[5]],
                  int(out[6]), bool(out[7]))
+
+
+PLAN_SCANS = ("none", "small4", "small16", "hipcub")  # csrc/kernels.h PlanDecisions::scan_kind
+PlanLayout = collections.namedtuple(
+    "PlanLayout",
+    "dim m M W Ta1 Ta2 nta1 nta2 np0 bin0 SB sb2 CG wide owned pair pstride tiles_per_batch "
+    "ntiles cap l1bins l1seg npencils block_points nblocks two_level grouped "
+    "off_offsets off_cursor off_seal off_perm off_spos off_groups off_own "
+    "one_level local_scan fuse scan_items scan")
+_PLAN_LAYOUT_FLAGS = ("wide", "owned", "pair", "two_level", "grouped", "one_level", "local_scan", "fuse")
+
+
+def plan_layout(problem, real_columns=0):
+    """Test entry ``nfft_dbg_plan_layout``: (main, owned) -- geometry, layout and host decisions of the point plan that
+    csrc/api.hip plan_route gives ``problem`` for calls with ``real_columns`` real planes per point set, and of the owned
+    plan behind it (None when the route has none).  The ``off_*`` table offsets count from the plan's own start, which
+    is ``off_own`` bytes into the plan buffer (0 for the main plan); ``scan`` names the scan between the two first-level
+    passes ("none": the scatter pass scans the counts itself).  Host code only; the process's NFFT_HIP_* switches apply."""
+    nf = len(PlanLayout._fields) + 1
+    main, own = (ctypes.c_int64 * nf)(), (ctypes.c_int64 * nf)()
+    check(load().nfft_dbg_plan_layout(ctypes.byref(problem), real_columns, main, own))
+
+    def record(a):
+        v = dict(zip(PlanLayout._fields, (int(a[i]) for i in range(nf - 1))))
+        for k in _PLAN_LAYOUT_FLAGS:
+            v[k] = bool(v[k])
+        v["scan"] = PLAN_SCANS[v["scan"]]
+        return PlanLayout(**v)
+    return record(main), (record(own) if main[nf - 1] else None)
 
 
 FFT_ROUTES = ("full", "roc_rows", "own_planar", "own_ci")  # csrc/api.hip FftRoute

@@ -772,6 +772,38 @@ int nfft_dbg_route(const nfft_hip_problem *p, int64_t real_columns, int32_t *out
     return 0;
 }
 
+// Test entry (tests/test_plan_ref.py, tests/test_gpu_plan_edges.py; not part of the C ABI either): geometry, layout and
+// host decisions of the point plans plan_route gives a problem.  main[kPlanLayoutFields]: the plan at the start of the
+// buffer; own[kPlanLayoutFields]: the owned plan behind it, filled when the route has one (main[39] = own[39] = 1).
+// Fields: {dim, m, M, W, Ta[1], Ta[2], nta[1], nta[2], np0, bin0, SB, sb2, CG, wide, owned, pair, pstride,
+// tiles_per_batch | ntiles, cap, l1bins, l1seg, npencils, block_points, nblocks, two_level, grouped, off_offsets,
+// off_cursor, off_seal, off_perm, off_spos, off_groups (byte offsets from the plan's own start), off_own (start of this
+// plan in the buffer) | one_level, local_scan, fuse, scan items, scan kind (kernels.h PlanDecisions) | has an owned plan}.
+// Host code only: no launch, no device memory.
+constexpr int kPlanLayoutFields = 40;
+static void fill_plan_layout(const Geom &g, const PlanLayout &L, int64_t base, bool has_own, int64_t *o)
+{
+    const PlanDecisions d = plan_decisions(g, L);
+    const int64_t v[kPlanLayoutFields] = {
+        g.dim, g.m, g.M, g.W, g.Ta[1], g.Ta[2], g.nta[1], g.nta[2], g.np0, g.bin0, g.SB, g.sb2, g.CG, g.wide, g.owned, g.pair,
+        g.pstride, g.tiles_per_batch,
+        L.ntiles, L.cap, L.l1bins, L.l1seg, L.npencils, L.block_points, L.nblocks, L.two_level ? 1 : 0, L.grouped ? 1 : 0,
+        L.off_offsets, L.off_cursor, L.off_seal, L.off_perm, L.off_spos, L.off_groups, base,
+        d.one_level ? 1 : 0, d.local_scan ? 1 : 0, d.fuse ? 1 : 0, d.scan_items, d.scan_kind,
+        has_own ? 1 : 0};
+    for (int i = 0; i < kPlanLayoutFields; ++i) o[i] = v[i];
+}
+int nfft_dbg_plan_layout(const nfft_hip_problem *p, int64_t real_columns, int64_t *main, int64_t *own)
+{
+    if (int rc = validate(p)) return rc;
+    if (!main || !own || real_columns < 0) { set_error("Input mismatch: no plan layout"); return NFFT_HIP_EINVAL; }
+    const Route r = plan_route(p, real_columns);
+    fill_plan_layout(r.g, r.L, 0, r.owned, main);
+    for (int i = 0; i < kPlanLayoutFields; ++i) own[i] = 0;
+    if (r.owned) fill_plan_layout(r.go, r.Lo, r.off_own, true, own);
+    return 0;
+}
+
 // make_route as adjoint_impl / forward_impl call it (planes per column: of x for an adjoint, of y for a forward transform)
 static int stage_route(const nfft_hip_problem *p, int adjoint, int x_is_complex, int real_output, Route &r, bool size_fft_work)
 {

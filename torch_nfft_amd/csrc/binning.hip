@@ -1023,10 +1023,14 @@ __global__ void __launch_bounds__(1024) small_scan_kernel(const int *__restrict_
     }
 }
 
+// which scan exclusive_scan takes for `items` counters: 1 small_scan_kernel<4>, 2 small_scan_kernel<16>, 3 hipcub
+static inline int scan_kind_of(int64_t items) { return items <= 4096 ? 1 : items <= kSmallScanItems ? 2 : 3; }
+
 static int exclusive_scan(const int *in, int *out, int64_t items, void *scratch, int64_t scratch_bytes, hipStream_t stream)
 {
-    if (items <= kSmallScanItems) {
-        if (items <= 4096) hipLaunchKernelGGL(small_scan_kernel<4>, dim3(1), dim3(1024), 0, stream, in, out, (int)items);
+    const int kind = scan_kind_of(items);
+    if (kind < 3) {
+        if (kind == 1) hipLaunchKernelGGL(small_scan_kernel<4>, dim3(1), dim3(1024), 0, stream, in, out, (int)items);
         else hipLaunchKernelGGL(small_scan_kernel<16>, dim3(1), dim3(1024), 0, stream, in, out, (int)items);
         NFFT_HIP_CHECK(hipGetLastError());
         return 0;
@@ -1036,6 +1040,30 @@ static int exclusive_scan(const int *in, int *out, int64_t items, void *scratch,
     if ((int64_t)scan_bytes > scratch_bytes) { set_error("scan scratch too small"); return 2; }
     NFFT_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(scratch, scan_bytes, in, out, (int)items, stream));
     return 0;
+}
+
+// The host decisions of launch_plan_points, in one place: the launch below and the test entry nfft_dbg_plan_layout
+// (api.hip) both read them here.
+PlanDecisions plan_decisions(const Geom &g, const PlanLayout &L)
+{
+    PlanDecisions d{};
+    if (!L.two_level) {
+        // single-level sort (bin_count_kernel / bin_fill_kernel): one scan of the plan bins' counts
+        d.scan_items = L.ntiles + 1;
+        d.scan_kind = scan_kind_of(d.scan_items);
+        return d;
+    }
+    d.scan_items = L.npencils * L.nblocks + 1;
+    const int64_t fine_keys = (int64_t)L.l1bins * g.SB * g.CG;
+    // (1-D / 2-D: the first level is the whole sort; a small table of counts is scanned inside the scatter pass)
+    d.one_level = g.dim < 3 && L.l1seg == 1 && fine_keys == 1 && L.ntiles == L.npencils;
+    // (local_scan: two LDS ints per bin + the static 128 bytes of the seal sum must stay within the 64 KB a launch gets
+    // without raising the kernel's limit -- not so for 8 177 .. 8 192 bins)
+    d.local_scan = d.one_level && d.scan_items <= 16384 && 2 * L.npencils * 4 + 16 * 8 <= 65536;
+    d.scan_kind = d.local_scan ? 0 : scan_kind_of(d.scan_items);
+    // second level: in one pass when every bin fits it (3-D: 16-byte records), else by eight parts per bin
+    d.fuse = !d.one_level && g.dim == 3 && fine_keys <= kFuseMaxKeys;
+    return d;
 }
 
 int launch_plan_points(const Geom &g_in, const PlanLayout &L, const float *pos, const int64_t *batch, int64_t n, int64_t B,
@@ -1056,18 +1084,15 @@ int launch_plan_points(const Geom &g_in, const PlanLayout &L, const float *pos, 
         int *hscan = (int *)(base + L.off_hscan);
         float4 *tmp = (float4 *)(base + L.off_tmp);
         const int npencils = (int)L.npencils, nblocks = (int)L.nblocks;
-        const int64_t items = L.npencils * L.nblocks + 1;
+        const PlanDecisions dec = plan_decisions(g, L);
+        const int64_t items = dec.scan_items;
         const size_t lds1 = (size_t)npencils * 4;
         unsigned short *key1 = (unsigned short *)(base + L.off_key1), *key2 = (unsigned short *)(base + L.off_key2);
         const bool common = g.dim == 3 && !g.owned;
         hipLaunchKernelGGL(common ? sort1_count_kernel<true> : sort1_count_kernel<false>, dim3(nblocks), dim3(kSortThreads), lds1, stream, g, pos, batch, n, B,
                            npencils, nblocks, (int)L.block_points, hist, key1, seal ? (unsigned long long *)(base + L.off_sealpart) : nullptr,
                            device_status_block());
-        // (1-D / 2-D: the first level is the whole sort; a small table of counts is scanned inside the scatter pass)
-        const bool one_level = g.dim < 3 && g.l1seg == 1 && (int64_t)g.l1bins * g.SB * g.CG == 1 && L.ntiles == L.npencils;
-        // (local_scan: two LDS ints per bin + the static 128 bytes of the seal sum must stay within the 64 KB a launch gets
-        // without raising the kernel's limit -- not so for 8 177 .. 8 192 bins)
-        const bool local_scan = one_level && items <= 16384 && 2 * lds1 + 16 * 8 <= 65536;
+        const bool one_level = dec.one_level, local_scan = dec.local_scan;
         if (!local_scan)
             if (int rc = exclusive_scan(hist, hscan, items, base + L.off_scan, L.scan_bytes, stream)) return rc;
         hipLaunchKernelGGL(common ? sort1_scatter_kernel<true> : sort1_scatter_kernel<false>, dim3(nblocks), dim3(kSortThreads),
@@ -1082,7 +1107,7 @@ int launch_plan_points(const Geom &g_in, const PlanLayout &L, const float *pos, 
         const size_t lds2 = (size_t)g.l1bins * g.SB * g.CG * 4;
         // second level: in one pass when every bin fits it (3-D: 16-byte records), else by eight parts per bin; the route
         // is taken on the device (sort2_route_kernel), and the launches that do not have it return at once
-        const bool fuse = g.dim == 3 && (int64_t)g.l1bins * g.SB * g.CG <= kFuseMaxKeys;
+        const bool fuse = dec.fuse;
         int *const route = fuse ? cursor : nullptr;  // (the cursors serve the single-level sort only)
         if (fuse) {
             hipLaunchKernelGGL(sort2_route_kernel, dim3(1), dim3(1024), 0, stream, npencils, nblocks, hscan, route);

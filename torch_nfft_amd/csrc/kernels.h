@@ -8,6 +8,16 @@ namespace nfft {
 // binning.hip
 int launch_plan_points(const Geom &g, const PlanLayout &L, const float *pos, const int64_t *batch, int64_t n, int64_t B,
                        void *plan, hipStream_t stream);
+// What launch_plan_points decides on the host for a plan of layout L: `one_level` (1-D / 2-D: the first level is the whole
+// sort), `local_scan` (its scatter pass scans the table of counts itself), `fuse` (the second level may take the one-pass
+// kernel; the device decides, sort2_route_kernel), the item count of the scan between the passes and which scan runs
+// (0 none, 1 small_scan_kernel<4>, 2 small_scan_kernel<16>, 3 hipcub).
+struct PlanDecisions {
+    bool one_level, local_scan, fuse;
+    int64_t scan_items;
+    int scan_kind;
+};
+PlanDecisions plan_decisions(const Geom &g, const PlanLayout &L);
 // Seal of a point plan: a 64-bit checksum of the points (and the batch vector) it was built from, left in the plan's seal
 // block (common.h: PlanLayout::off_seal) by the pass that counts the points -- no pass of its own.  verify: recompute the
 // checksum from the arrays as they are now into accumulator `slot` and raise kFaultStalePlan in the device's status
