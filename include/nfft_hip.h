@@ -659,6 +659,31 @@ int nfft_hip_ewald_lj_table_near(const nfft_hip_ewald_box_problem *p, double alp
                                  const float *weight_coulomb, const float *weight_lj, float *f, double *out8, void *workspace,
                                  int64_t workspace_bytes, void *stream);
 
+/* ---- the same walk for Buckingham / Born-Mayer-Huggins pair potentials (no reference counterpart) ----
+ * For force fields whose repulsion is an exponential (Tosi-Fumi alkali halides, BKS silica, ionic ceramics).  The argument
+ * list, xs [points, 2] = (q, c), types, the list and every output are those of nfft_hip_ewald_lj_table_near; table is float32
+ * [num_types, num_types, 4] = (A(t, t'), B(t, t'), dC6(t, t'), C8(t, t')), symmetric in (t, t'), for the pair energy
+ * A e^(-B r) - C6 / r^6 - C8 / r^8 (B = 1 / rho; attractions enter with positive C6, C8) with dC6 what the pair's C6 has above
+ * the product c_i c_j that the far field carries.  Over the pairs 0 < r_ij < r_cut, plainly truncated, and with
+ * s_ij = q_i q_j mg_C - c_i c_j mg_D + A B e^(-B r) / r - 6 dC6 / r^8 - 8 C8 / r^10:
+ *     f[index[i], a] = sum_j s_ij d_ij[a]                                                      float32 [points, 3]
+ *     out8[b, 0]     = 1/2 sum_ij q_i q_j w_C                                                  float64 [batch_size, 8]
+ *     out8[b, 1]     = 1/2 sum_ij (A e^(-B r) - dC6 / r^6 - C8 / r^8 - c_i c_j w_D)
+ *     out8[b, 2 + e] = 1/2 sum_ij s_ij d_ij[a] d_ij[b],   e = 0 .. 5: ab = xx, yy, zz, yz, xz, xy
+ * A listed pair's q_i q_j is scaled by s^C and its c_i c_j, A, dC6 and C8 by s^L before they are added.  With c = 0 (no
+ * dispersion on the grid) the terms in c_i c_j are exact zeros and alpha_dispersion only has to be valid.  A type outside
+ * [0, num_types) is clamped.  Separations below 1.6e-5, or at which 6 dC6 / r^8 or 8 C8 / r^10 leaves float32, give values that
+ * are not numbers; the exponential term is finite everywhere.
+ *
+ * Checks, limits, error codes and the workspace are those of nfft_hip_ewald_lj_table_near, except that table must be
+ * 16-byte aligned (an entry moves as one load).  No atomics: two calls give the same bits. */
+int64_t nfft_hip_ewald_bmh_table_near_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion);
+int nfft_hip_ewald_bmh_table_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_types, int64_t num_entries,
+                                  const float *points, const float *xs, const int32_t *types, const float *table,
+                                  const int32_t *start, const int64_t *index, const int32_t *row_start, const int32_t *col,
+                                  const float *weight_coulomb, const float *weight_lj, float *f, double *out8, void *workspace,
+                                  int64_t workspace_bytes, void *stream);
+
 /* ---- Ewald sum of point charges and point dipoles (no reference counterpart) ----
  * Source j carries a charge q_j and a Cartesian dipole mu_j, packed as xs [points, 4, num_columns] = (q, mu_x, mu_y, mu_z).
  * With d = d_ij, r = |d|, m = mu_j . d and the Smith functions B_0 = erfc(alpha r) / r,

@@ -117,6 +117,15 @@ tables with sigma between 0.5 and 0.8 of the spacing: the new pair operator besi
 beside nfft_ewald_lj_step / nfft_ewald_lj_excl_step.  The yardsticks take geometric (c, a) of the same sigma and epsilon: other
 numbers, the same work.  All are timed in turn, median, minimum and maximum of `reps` each.
 
+    python scripts/bench_ewald.py --lj-step --bmh [--exclusions] [--types 2 32] [--box ...] [...]
+
+times the Buckingham / Born-Mayer-Huggins + Coulomb step, one row per point count and type count T,
+exp-6 tables with r_m between 0.7 and 1.0 of the spacing and a C8 term: the new pair operator beside the untouched
+_nfft_ewald_lj_table_near and nfft_ewald_bmh_table_step beside the untouched nfft_ewald_lj_table_step, on the same points, types
+and list in the same process (the points of --lj-step --table; the yardsticks take a Lorentz-Berthelot table of the same sizes:
+other numbers, the same frame), and nfft_ewald_bmh_table_step(dispersion=None) with nothing on the grid.  All are timed in turn,
+median, minimum and maximum of `reps` each.
+
     python scripts/bench_ewald.py --yukawa [--virial] [--screening 1.0] [...]
 
 times the screened Coulomb sum e^(-lambda r) / r in the unit cube on the same points, r_c, alpha and N,
@@ -1326,6 +1335,102 @@ def run_lj_table_step(lib, n, args):
                           "step_over_yardstick": ratio("table_step", "yardstick_step")}))
 
 
+def run_bmh_table_step(lib, n, args):
+    """the Buckingham / Born-Mayer-Huggins + Coulomb step beside the step of section 7t on the same points,
+    types and list: the points, splittings and bandwidths of run_lj_table_step, restated."""
+    m = 4
+    triples = args.exclusions
+    if triples:
+        n -= n % 3
+    sites = n // 3 if triples else n
+    box = [1.0, 0.0, 1.0, 0.0, 0.0, 1.0] if args.box is None else \
+        (args.box if len(args.box) == 6 else [args.box[0], 0.0, args.box[1], 0.0, 0.0, args.box[2]])
+    A = np.array([[box[0], 0.0, 0.0], [box[1], box[2], 0.0], [box[3], box[4], box[5]]])
+    probe = tn.EwaldSplitting(1.0, 1e-3 * min(box[0], box[2], box[5]), 2, box=A, device="cpu")  # (volume and widths)
+    r_c = min((3.0 * args.neighbours * probe.volume / (4.0 * math.pi * n)) ** (1.0 / 3.0), min(probe.widths) / 3.0)
+    own_c = tn.EwaldSplitting.from_tolerance(args.tol, r_c, box=A)
+    own_d = tn.DispersionSplitting.from_tolerance(args.tol, r_c, box=A)
+    N = max(own_c.bandwidth, own_d.bandwidth)
+    if not args.bandwidth_as_is:
+        N = max(fft_friendly(own_c.bandwidth), fft_friendly(own_d.bandwidth))
+    spc = tn.EwaldSplitting(own_c.alpha, r_c, N, box=A)
+    spd = tn.DispersionSplitting(own_d.alpha, r_c, N, box=A)
+    rng = np.random.default_rng(0)
+    side = int(math.ceil(sites ** (1.0 / 3.0)))
+    g = (np.arange(side) + 0.5) / side - 0.5
+    v = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    spacing = probe.volume ** (1.0 / 3.0) / side
+    if triples:
+        centre = (v + (rng.random(v.shape) - 0.5) * (0.2 / side))[rng.permutation(side ** 3)[:sites]] @ A
+        bond = 0.3 * spacing
+        u = rng.standard_normal((sites, 3))
+        u /= np.linalg.norm(u, axis=1, keepdims=True)
+        w = np.cross(u, rng.standard_normal((sites, 3)))
+        w /= np.linalg.norm(w, axis=1, keepdims=True)
+        half = math.radians(104.5 / 2)
+        x = np.stack([centre, centre + bond * (math.cos(half) * u + math.sin(half) * w),
+                      centre + bond * (math.cos(half) * u - math.sin(half) * w)], 1).reshape(n, 3)
+        v = (x @ np.linalg.inv(A)).astype(np.float32)
+        q = torch.from_numpy(np.tile(np.array([-0.834, 0.417, 0.417], dtype=np.float32), sites)).cuda()
+        o = 3 * np.arange(sites)
+        ex = tn.ExclusionList(np.concatenate([np.stack([o, o + 1], 1), np.stack([o, o + 2], 1), np.stack([o + 1, o + 2], 1)]), n)
+        lists = (ex.row_start, ex.col, ex.coulomb_weight, ex.dispersion_weight)
+    else:
+        v = (v + (rng.random(v.shape) - 0.5) * (0.4 / side))[rng.permutation(side ** 3)[:n]].astype(np.float32)
+        v[v >= 0.5] = -0.5  # (rounded up to the face: the same point)
+        q = torch.from_numpy(rng.standard_normal(n).astype(np.float32)).cuda()
+        ex, lists = None, (None,) * 4
+    pos = torch.from_numpy(v).cuda()
+    kl = {"coulomb": spc, "dispersion": spd, "cutoff": m, "fractional": True}
+    walk = (box, spc.alpha, spd.alpha, r_c)
+    for T in args.types:
+        heavy = max(T // 2, 1) if triples else T  # (the types that carry a short-range term)
+        size, eps = np.zeros(T), np.zeros(T)
+        size[:heavy], eps[:heavy] = spacing * (0.7 + 0.3 * rng.random(heavy)), 0.5 + rng.random(heavy)
+        types = rng.integers(0, heavy, n)
+        if triples:
+            light = rng.integers(heavy, T, n) if T > heavy else np.zeros(n, dtype=np.int64)
+            types = np.where(np.arange(n) % 3 == 0, types, light)
+            if T == heavy:  # (one type: every atom is an oxygen)
+                types[:] = 0
+        tt = torch.from_numpy(types).cuda()
+        # exp-6: r_m and the steepness (12 .. 14) mixed arithmetically, eps geometrically; light types keep B and lose A, C6, C8
+        rm = 0.5 * (size[:, None] + size[None, :])
+        rm[rm == 0.0] = spacing
+        st = 12.0 + 2.0 * rng.random(T)
+        st = 0.5 * (st[:, None] + st[None, :])
+        e = np.sqrt(eps[:, None] * eps[None, :])
+        C6 = e * st * rm ** 6 / (st - 6.0)
+        tabs = [torch.from_numpy(v) for v in (6.0 * e * np.exp(st) / (st - 6.0), st / rm, C6, 0.3 * C6 * rm ** 2)]
+        table = tn.BMHPairTable(*tabs, tt)
+        bare = tn.BMHPairTable(*tabs, tt, grid_c=torch.zeros(T))
+        yard = tn.LJPairTable.lorentz_berthelot(torch.from_numpy(0.7 * size), torch.from_numpy(eps), tt)
+        xs, xs0, xsy = torch.stack([q, table.c], 1), torch.stack([q, bare.c], 1), torch.stack([q, yard.c], 1)
+        walk0 = (box, spc.alpha, spc.alpha, r_c)
+        kl0 = {"coulomb": spc, "dispersion": None, "cutoff": m, "fractional": True}
+        fns = {"bmh_walk_op": lambda: tn.ops.nfft_ewald_bmh_table_near(pos, xs, table.types, table.table, None, *lists, *walk),
+               "bmh_walk_op_no_grid": lambda: tn.ops.nfft_ewald_bmh_table_near(pos, xs0, bare.types, bare.table, None, *lists, *walk0),
+               "yardstick_walk_op": lambda: tn.ops.nfft_ewald_lj_table_near(pos, xsy, yard.types, yard.table, None, *lists, *walk),
+               "bmh_step": lambda: tn.nfft_ewald_bmh_table_step(q, table, pos, exclusions=ex, **kl),
+               "bmh_step_no_grid": lambda: tn.nfft_ewald_bmh_table_step(q, bare, pos, exclusions=ex, **kl0),
+               "yardstick_step": lambda: tn.nfft_ewald_lj_table_step(q, yard, pos, exclusions=ex, **kl)}
+        t = alternating_ms(fns, args.reps)
+        tn.ops.check_status()
+        med = {k: v_[0] for k, v_ in t.items()}
+        ratio = lambda new, old: [round(med[new] / med[old], 3), round(t[new][1] / t[old][2], 3), round(t[new][2] / t[old][1], 3)]  # noqa: E731
+        print(json.dumps({"bench": "ewald_bmh_table_step", "yardstick": "lj_table", "exclusions": bool(triples), "box": box, "points": n,
+                          "types": T, "table_lds_bytes": 16 * T * (T | 1), "yardstick_lds_bytes": 8 * T * (T | 1),
+                          "neighbours": args.neighbours, "tol": args.tol, "r_cut": round(r_c, 5),
+                          "alpha_coulomb": round(spc.alpha, 3), "alpha_dispersion": round(spd.alpha, 3),
+                          "N": N, "m": m, "cells": list(spc.cells), "reps": args.reps,
+                          "median_min_max_ms": {k: [round(e_, 4) for e_ in v_] for k, v_ in t.items()},
+                          # (median over median; then the new at its fastest over the old at its slowest, and the other way round)
+                          "walk_op_over_yardstick": ratio("bmh_walk_op", "yardstick_walk_op"),
+                          "walk_op_no_grid_over_yardstick": ratio("bmh_walk_op_no_grid", "yardstick_walk_op"),
+                          "step_over_yardstick": ratio("bmh_step", "yardstick_step"),
+                          "step_no_grid_over_yardstick": ratio("bmh_step_no_grid", "yardstick_step")}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, nargs="+", default=[100000, 1000000])
@@ -1351,7 +1456,10 @@ def main():
     ap.add_argument("--table", action="store_true",
                     help="--lj-step: time nfft_ewald_lj_table_step and its pair operator beside nfft_ewald_lj_step, with --exclusions "
                          "beside nfft_ewald_lj_excl_step, for every type count of --types")
-    ap.add_argument("--types", type=int, nargs="+", default=[2, 32], help="--table: the type counts T, each in [1, 32]")
+    ap.add_argument("--bmh", action="store_true",
+                    help="--lj-step: time nfft_ewald_bmh_table_step (also with dispersion=None) and its pair operator beside "
+                         "nfft_ewald_lj_table_step and its pair operator, with or without --exclusions, for every type count of --types")
+    ap.add_argument("--types", type=int, nargs="+", default=[2, 32], help="--table, --bmh: the type counts T, each in [1, 32]")
     ap.add_argument("--bandwidth-as-is", action="store_true",
                     help="--lj-step: keep the bandwidths of from_tolerance instead of the next sizes with prime factors <= 7")
     ap.add_argument("--screening", type=float, default=1.0, help="--yukawa: lambda r_c, the screening parameter times r_c")
@@ -1364,6 +1472,8 @@ def main():
         ap.error("--lj-step times the Lennard-Jones + Coulomb step on its own (with or without --box and --exclusions)")
     if args.table and not args.lj_step:
         ap.error("--table goes with --lj-step")
+    if args.bmh and (not args.lj_step or args.table):
+        ap.error("--bmh goes with --lj-step and not with --table")
     if args.yukawa and (args.box is not None or args.dispersion or args.dipole or args.stokeslet or args.rpy or args.exclusions):
         ap.error("--yukawa times the unit cube on its own (with or without --virial)")
     if args.yukawa and not 0.0 < args.screening <= 50.0:
@@ -1383,6 +1493,9 @@ def main():
     for n in args.points:
         if args.lj_step and args.table:
             run_lj_table_step(lib, n, args)
+            continue
+        if args.lj_step and args.bmh:
+            run_bmh_table_step(lib, n, args)
             continue
         if args.lj_step:
             (run_lj_excl_step if args.exclusions else run_lj_step)(lib, n, args)

@@ -31,6 +31,7 @@ from .exclusions import ExclusionList  # noqa: E402
 from .yukawa import (YukawaSplitting, nfft_ewald_yukawa, nfft_ewald_yukawa_energy, NfftEwaldYukawaFunction,  # noqa: E402
                      nfft_ewald_yukawa_virial)
 from .lj import LJPairTable, lj_coefficients, nfft_ewald_lj_step, nfft_ewald_lj_excl_step, nfft_ewald_lj_table_step  # noqa: E402
+from .bmh import BMHPairTable, nfft_ewald_bmh_table_step  # noqa: E402
 from .matrices import GramMatrix, AdjacencyMatrix  # noqa: E402
 from .kernel import GaussianKernel  # noqa: E402
 from . import utils  # noqa: E402
@@ -49,6 +50,7 @@ __all__ = ["nfft_adjoint", "nfft_forward", "nfft_fastsum", "nfft_toeplitz_kernel
            "YukawaSplitting", "nfft_ewald_yukawa", "nfft_ewald_yukawa_energy", "NfftEwaldYukawaFunction",
            "nfft_ewald_yukawa_virial", "lj_coefficients", "nfft_ewald_lj_step",
            "nfft_ewald_lj_excl_step", "LJPairTable", "nfft_ewald_lj_table_step",
+           "BMHPairTable", "nfft_ewald_bmh_table_step",
            "ndft_forward", "ndft_adjoint", "ndft_fastsum",
            "exact_trigonometric_matrix", "exact_gaussian_matrix", "NfftAdjointFunction", "NfftForwardFunction",
            "NfftFastsumFunction", "gaussian_analytic_coeffs", "gaussian_interpolated_coeffs", "interpolation_grid",

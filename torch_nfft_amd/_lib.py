@@ -85,6 +85,8 @@ SYMBOLS = (
     "nfft_hip_ewald_lj_excl_list",
     "nfft_hip_ewald_lj_table_near_workspace_bytes",
     "nfft_hip_ewald_lj_table_near",
+    "nfft_hip_ewald_bmh_table_near_workspace_bytes",
+    "nfft_hip_ewald_bmh_table_near",
     "nfft_hip_ewald_dipole_near",
     "nfft_hip_ewald_dipole_near_box",
     "nfft_hip_ewald_dipole_spectral",
@@ -353,6 +355,11 @@ def load():
     lib.nfft_hip_ewald_lj_table_near.argtypes = [ctypes.POINTER(EwaldBoxProblem), ctypes.c_double, i64, i64, vp, vp, vp, vp, vp, vp,
                                                  vp, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.nfft_hip_ewald_lj_table_near.restype = ci
+    lib.nfft_hip_ewald_bmh_table_near_workspace_bytes.argtypes = [ctypes.POINTER(EwaldBoxProblem), ctypes.c_double]
+    lib.nfft_hip_ewald_bmh_table_near_workspace_bytes.restype = i64
+    lib.nfft_hip_ewald_bmh_table_near.argtypes = [ctypes.POINTER(EwaldBoxProblem), ctypes.c_double, i64, i64, vp, vp, vp, vp, vp, vp,
+                                                  vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.nfft_hip_ewald_bmh_table_near.restype = ci
     lib.nfft_hip_ewald_dipole_near.argtypes = [ctypes.POINTER(EwaldProblem), vp, vp, vp, vp, ctypes.c_int32, vp, vp, i64, vp]
     lib.nfft_hip_ewald_dipole_near.restype = ci
     lib.nfft_hip_ewald_dipole_near_box.argtypes = [ctypes.POINTER(EwaldBoxProblem), vp, vp, vp, vp, ctypes.c_int32, vp, vp, i64, vp]

@@ -22,7 +22,7 @@ CORE = os.path.join(HERE, "core.so")
 CORE_SRC = os.path.join(CSRC, "core.cpp")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
-SOURCES = ["api.hip", "api_pair.hip", "binning.hip", "spread.hip", "spread_reg.hip", "spread_mfma.hip", "interp.hip", "interp_grad.hip", "hvp_spectral.hip", "interp_mfma.hip", "interp_cols.hip", "interp_stream.hip", "smallgrid.hip", "spectral.hip", "colfft.hip", "coeffs.hip", "toeplitz.hip", "nearfield.hip", "nearfield_grad.hip", "nearfield_pgrad.hip", "ewald_near.hip", "ewald_disp.hip", "ewald_virial.hip", "ewald_step.hip", "ewald_lj_step.hip", "ewald_lj_excl.hip", "ewald_lj_table.hip", "ewald_disp_virial.hip", "ewald_dipole.hip", "ewald_stokeslet.hip", "ewald_rpy.hip", "ewald_excl.hip", "ewald_yukawa.hip", "selftest.hip", "fft.cpp"]
+SOURCES = ["api.hip", "api_pair.hip", "binning.hip", "spread.hip", "spread_reg.hip", "spread_mfma.hip", "interp.hip", "interp_grad.hip", "hvp_spectral.hip", "interp_mfma.hip", "interp_cols.hip", "interp_stream.hip", "smallgrid.hip", "spectral.hip", "colfft.hip", "coeffs.hip", "toeplitz.hip", "nearfield.hip", "nearfield_grad.hip", "nearfield_pgrad.hip", "ewald_near.hip", "ewald_disp.hip", "ewald_virial.hip", "ewald_step.hip", "ewald_lj_step.hip", "ewald_lj_excl.hip", "ewald_lj_table.hip", "ewald_bmh_table.hip", "ewald_disp_virial.hip", "ewald_dipole.hip", "ewald_stokeslet.hip", "ewald_rpy.hip", "ewald_excl.hip", "ewald_yukawa.hip", "selftest.hip", "fft.cpp"]
 # -ffp-contract=on: multiply-adds are fused only where one expression says so.  Until round 4 the library was built with
 # =fast (fusion across statements), which silently broke an error-free transformation twice (the f16 split in round 2,
 # split_cell in round 3: DESIGN.md section 5); the transformations are inline asm now and pinned bit for bit by

@@ -883,6 +883,54 @@ int nfft_hip_ewald_lj_table_near(const nfft_hip_ewald_box_problem *p, double alp
                                       col, weight_coulomb, weight_lj, f, out8, ws, (hipStream_t)stream);
 }
 
+// ---- the walk of the Buckingham / Born-Mayer-Huggins step: the checks of the table walk above, with
+// an entry of 16 bytes that moves as one load ---
+static int validate_bmh_table(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_types, const void *table,
+                              int64_t num_entries, const void *row_start, const void *col, const void *weight_coulomb,
+                              const void *weight_lj)
+{
+    if (int rc = validate_lj_step_near(p, alpha_dispersion)) return rc;
+    if (num_types < 1 || num_types > 32) { set_error("Input mismatch: num_types must lie in [1, 32]"); return NFFT_HIP_EINVAL; }
+    if (!table) { set_error("Input mismatch: table is null"); return NFFT_HIP_EINVAL; }
+    if ((uintptr_t)table & 15) { set_error("Input mismatch: table must be 16-byte aligned"); return NFFT_HIP_EINVAL; }
+    if (p->num_points >= (int64_t(1) << 31)) { set_error("Input mismatch: too many points or entries"); return NFFT_HIP_EINVAL; }
+    if (!row_start) {  // no list: the unmasked walk
+        if (col || weight_coulomb || weight_lj || num_entries != 0) {
+            set_error("Input mismatch: a list without row_start");
+            return NFFT_HIP_EINVAL;
+        }
+        return 0;
+    }
+    return validate_lj_excl(p, alpha_dispersion, num_entries, row_start, col, weight_coulomb, weight_lj);
+}
+
+int64_t nfft_hip_ewald_bmh_table_near_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion)
+{
+    if (validate_lj_step_near(p, alpha_dispersion)) return -1;
+    return ewald_bmh_table_near_workspace(p) + 256;
+}
+
+int nfft_hip_ewald_bmh_table_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_types, int64_t num_entries,
+                                  const float *points, const float *xs, const int32_t *types, const float *table,
+                                  const int32_t *start, const int64_t *index, const int32_t *row_start, const int32_t *col,
+                                  const float *weight_coulomb, const float *weight_lj, float *f, double *out8, void *workspace,
+                                  int64_t workspace_bytes, void *stream)
+{
+    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
+    if (int rc = validate_bmh_table(p, alpha_dispersion, num_types, table, num_entries, row_start, col, weight_coulomb, weight_lj))
+        return rc;
+    if (!out8) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
+    if (p->num_points == 0) {  // (no row of f)
+        NFFT_HIP_CHECK(hipMemsetAsync(out8, 0, (size_t)(p->batch_size * 8) * sizeof(double), (hipStream_t)stream));
+        return 0;
+    }
+    if (!points || !xs || !types || !start || !index || !f) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    char *ws = workspace_base(workspace, workspace_bytes, ewald_bmh_table_near_workspace(p) + 256);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch_ewald_bmh_table_near(p, alpha_dispersion, num_types, num_entries, points, xs, types, table, start, index, row_start,
+                                       col, weight_coulomb, weight_lj, f, out8, ws, (hipStream_t)stream);
+}
+
 // ---- the spectral step of the dipole sum -------------------------------------------------------
 int nfft_hip_ewald_dipole_spectral(int64_t N, int64_t batch_size, int64_t num_columns, int32_t order, const void *band,
                                    const float *coeffs, const double *box_inverse, void *out, void *stream)

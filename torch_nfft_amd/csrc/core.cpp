@@ -1754,6 +1754,60 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_lj_table_near(at::Tensor pos, at::
     return {f, out};
 }
 
+// ---- the pair walk of the Buckingham / Born-Mayer-Huggins + Coulomb step (not in the reference) ------
+// (f, eight) of nfft_ewald_lj_table_near for table [T, T, 4] float32 = (A, B, dC6, C8): the pair energy of two types within
+// r_cut is A e^(-B r) - dC6 / r^6 - C8 / r^8 beside the Ewald weights of (q, c).  Everything else as there
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_bmh_table_near(at::Tensor pos, at::Tensor xs, at::Tensor types, at::Tensor table,
+                                                             c10::optional<at::Tensor> opt_batch,
+                                                             c10::optional<at::Tensor> row_start, c10::optional<at::Tensor> col,
+                                                             c10::optional<at::Tensor> weight_coulomb,
+                                                             c10::optional<at::Tensor> weight_lj, std::vector<double> box,
+                                                             double alpha_coulomb, double alpha_dispersion, double r_cut)
+{
+    TORCH_CHECK(xs.is_cuda(), "torch_nfft._nfft_ewald_bmh_table_near is currently only implemented for GPU tensors");
+    const Points p = check_points(pos, opt_batch, "batch");
+    CHECK_INPUT(p.dim == 3);
+    CHECK_INPUT(xs.scalar_type() == at::kFloat && xs.dim() == 2 && xs.size(0) == p.n && xs.size(1) == 2);
+    CHECK_INPUT(types.scalar_type() == at::kInt && types.dim() == 1 && types.size(0) == p.n);
+    CHECK_INPUT(table.scalar_type() == at::kFloat && table.dim() == 3 && table.size(0) == table.size(1) && table.size(2) == 4);
+    CHECK_INPUT(table.size(0) >= 1 && table.size(0) <= 32);
+    CHECK_INPUT(xs.device() == pos.device() && types.device() == pos.device() && table.device() == pos.device());
+    CHECK_INPUT(box.size() == 6);
+    const bool masked = row_start.has_value();
+    CHECK_INPUT(col.has_value() == masked && weight_coulomb.has_value() == masked && weight_lj.has_value() == masked);
+    ExclInput ex;
+    at::Tensor wl;
+    if (masked) {
+        ex = check_excl(*row_start, *col, *weight_coulomb, pos, p.n);
+        CHECK_INPUT(weight_lj->scalar_type() == at::kFloat && weight_lj->dim() == 1 && weight_lj->numel() == ex.col.numel());
+        CHECK_INPUT(weight_lj->device() == pos.device());
+        wl = weight_lj->contiguous();
+    }
+    const nfft_hip_ewald_box_problem q = ewald_box_problem(p, 1, true, box, alpha_coulomb, r_cut);
+    const int64_t ws_bytes = nfft_hip_ewald_bmh_table_near_workspace_bytes(&q, alpha_dispersion);
+    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
+    // (zeros: a point whose coordinates are not numbers has no cell and is not written)
+    at::Tensor f = at::zeros({p.n, 3}, xs.options());
+    at::Tensor out = at::zeros({p.B, 8}, xs.options().dtype(at::kDouble));
+    if (p.n == 0) return {f, out};  // no launch
+    c10::DeviceGuard guard(xs.device());
+    const CellOrder o = torus_cell_order(p, q.cells);
+    const at::Tensor xr = real_rows(xs, true, p.n, 2, o.order);
+    const at::Tensor tr = types.index_select(0, o.order);
+    at::Tensor tab = table.contiguous();
+    if ((uintptr_t)tab.data_ptr() & 15) tab = tab.clone();  // (a view into a larger tensor: an entry moves as one 16-byte load)
+    at::Tensor ws = byte_buffer(ws_bytes, xs);
+    const int64_t entries = masked ? ex.col.numel() : 0;
+    const bool any = entries > 0;
+    check_rc(nfft_hip_ewald_bmh_table_near(&q, alpha_dispersion, tab.size(0), entries, o.pos.data_ptr<float>(), xr.data_ptr<float>(),
+                                           tr.data_ptr<int32_t>(), tab.data_ptr<float>(), o.start.data_ptr<int32_t>(),
+                                           o.order.data_ptr<int64_t>(), masked ? ex.row_start.data_ptr<int32_t>() : nullptr,
+                                           any ? ex.col.data_ptr<int32_t>() : nullptr, any ? ex.weight.data_ptr<float>() : nullptr,
+                                           any ? wl.data_ptr<float>() : nullptr, f.data_ptr<float>(), out.data_ptr<double>(),
+                                           ws.data_ptr(), ws_bytes, stream_of(xs)));
+    return {f, out};
+}
+
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device
 at::TensorOptions current_device_options(at::ScalarType dtype)
 {
@@ -1934,6 +1988,10 @@ TORCH_LIBRARY(torch_nfft, m)
     m.def("_nfft_ewald_lj_table_near(Tensor pos, Tensor xs, Tensor types, Tensor table, Tensor? batch, Tensor? row_start, "
           "Tensor? col, Tensor? weight_coulomb, Tensor? weight_lj, float[] box, float alpha_coulomb, float alpha_dispersion, "
           "float r_cut) -> (Tensor, Tensor)", &nfft_ewald_lj_table_near);
+    // not in the reference: the pair walk of the Buckingham / Born-Mayer-Huggins step (nfft_ewald_bmh_table_step)
+    m.def("_nfft_ewald_bmh_table_near(Tensor pos, Tensor xs, Tensor types, Tensor table, Tensor? batch, Tensor? row_start, "
+          "Tensor? col, Tensor? weight_coulomb, Tensor? weight_lj, float[] box, float alpha_coulomb, float alpha_dispersion, "
+          "float r_cut) -> (Tensor, Tensor)", &nfft_ewald_bmh_table_near);
     m.def("_nfft_ewald_excl(Tensor pos, Tensor x, Tensor? batch, Tensor row_start, Tensor col, Tensor weight, float[] box, "
           "float alpha, int kind, bool with_field) -> (Tensor, Tensor)", &nfft_ewald_excl);
     m.def("_nfft_ewald_excl_virial(Tensor pos, Tensor x, Tensor? batch, Tensor row_start, Tensor col, Tensor weight, "

@@ -279,6 +279,14 @@ int launch_ewald_lj_table_near(const nfft_hip_ewald_box_problem *p, double alpha
                                const float *pos, const float *xs, const int *types, const float *table, const int *start,
                                const int64_t *index, const int *row_start, const int *col, const float *weight_coulomb,
                                const float *weight_lj, float *f, double *out, void *workspace, hipStream_t stream);
+// ewald_bmh_table.hip (the pair walk of the Buckingham / Born-Mayer-Huggins + Coulomb step with a type-pair table, DESIGN.md
+// section 7u): arguments as nfft_hip_ewald_bmh_table_near, row_start == nullptr for the unmasked walk; `workspace`:
+// ewald_bmh_table_near_workspace(p) bytes, 256-byte aligned (as ewald_lj_step_near_workspace)
+int64_t ewald_bmh_table_near_workspace(const nfft_hip_ewald_box_problem *p);
+int launch_ewald_bmh_table_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_types, int64_t num_entries,
+                                const float *pos, const float *xs, const int *types, const float *table, const int *start,
+                                const int64_t *index, const int *row_start, const int *col, const float *weight_coulomb,
+                                const float *weight_lj, float *f, double *out, void *workspace, hipStream_t stream);
 // ewald_step.hip (potential, field, energy and virial of the Ewald sum in one pair walk and one spectral pass, DESIGN.md
 // section 7q): arguments as nfft_hip_ewald_step_near / _spectral, the workspaces those of ewald_virial.hip
 // (ewald_virial_near_workspace, ewald_virial_far_workspace), the second level its launch_virial_sum

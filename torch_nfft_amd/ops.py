@@ -328,6 +328,22 @@ def nfft_ewald_lj_table_near(pos, xs, types, table, batch, row_start, col, weigh
                                           [float(a) for a in box], float(alpha_coulomb), float(alpha_dispersion), float(r_cut))
 
 
+def nfft_ewald_bmh_table_near(pos, xs, types, table, batch, row_start, col, weight_coulomb, weight_lj, box, alpha_coulomb,
+                              alpha_dispersion, r_cut):
+    """torch_nfft::_nfft_ewald_bmh_table_near(Tensor pos, Tensor xs, Tensor types, Tensor table, Tensor? batch,
+    Tensor? row_start, Tensor? col, Tensor? weight_coulomb, Tensor? weight_lj, float[] box, float alpha_coulomb,
+    float alpha_dispersion, float r_cut) -> (Tensor, Tensor) (not in the reference): ``(f, eight)`` of
+    ``nfft_ewald_lj_table_near`` for Buckingham / Born-Mayer-Huggins pair potentials.  Every argument is that operator's but
+    ``table``, ``[T, T, 4]`` float32 ``(A, B, dC6, C8)`` per pair of types, ``1 <= T <= 32``, with ``dC6 = C6 - c_i c_j``: the pair
+    slope is ``q_i q_j mg_C - c_i c_j mg_D + A B e^(-B r) / r - 6 dC6 / r^8 - 8 C8 / r^10`` and the second energy ``1/2 sum
+    (A e^(-B r) - dC6 / r^6 - C8 / r^8 - c_i c_j w_D)`` over the pairs within ``r_cut``.  With a list ``q_i q_j`` of a listed pair
+    is scaled by ``s^C`` and ``c_i c_j``, ``A``, ``dC6``, ``C8`` by ``s^L`` before they are added; an empty list gives the bits of
+    the call without one.  One native call (``nfft_hip_ewald_bmh_table_near``), no atomics: two calls
+    give the same bits."""
+    return _ops._nfft_ewald_bmh_table_near(pos, xs, types, table, batch, row_start, col, weight_coulomb, weight_lj,
+                                           [float(a) for a in box], float(alpha_coulomb), float(alpha_dispersion), float(r_cut))
+
+
 def nfft_ewald_dispersion_virial_near(pos, x, batch, box, alpha, r_cut):
     """torch_nfft::_nfft_ewald_dispersion_virial_near(Tensor pos, Tensor x, Tensor? batch, float[] box, float alpha,
     float r_cut) -> Tensor (not in the reference): ``nfft_ewald_virial_near`` for the dispersion sum, ``[B, 7, *cols]``
