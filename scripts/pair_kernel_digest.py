@@ -11,7 +11,10 @@ Cases (profiles/r16_pair_frame.md): real columns 1, 2, 3 (the tail predicate of 
 point sets of 1 500 and 40 points (cells of the small one are empty) and 400 points crowded into one cell of the first
 (several work items per cell, a second LDS tile per range); near field in dim 1, 2, 3, all eight kernels at dim 3, Horner
 forms of up to 4 and of more terms, shared and separate targets; Ewald with r_c = 1/3 (G = 3: two of three cells of a row on
-the split path) and 0.2, with and without the field, an orthorhombic box of 3 x 4 x 6 cells and a triclinic one."""
+the split path) and 0.2, with and without the field, an orthorhombic box of 3 x 4 x 6 cells and a triclinic one.
+The step walks (step_frame.h; profiles/r20_step_frame.md) run on the same layout of points in the unit box at r_c = 1/3 and
+in the two other boxes: the product law without a list, with an empty one and with one (bonded_list), the two table laws
+in all three ways at T = 1, 2 and 32, the Buckingham table with and without a coefficient on the grid, and the list kernel."""
 import hashlib
 import os
 import sys
@@ -120,9 +123,97 @@ def ewald_cases():
     ops.check_status()
 
 
+def bonded_list(pos, batch, G):
+    """pairs of `pos` (set 0 apart from its crowd, and the crowd) with their two scales: chains of three near neighbours
+    (the triples), one pair across a border of the G^3 cells, one across the torus seam, four pairs inside the crowd's cell
+    that share a point (a row of several entries) and one pair beyond every r_c used here.  The scales cycle through
+    (0, 0), (0, 0.5), (1, 1), (0.5, 0): the first is the walk's early return"""
+    first = int(np.flatnonzero(batch == 0)[-1]) + 1 - 1500  # set 0 after its crowd
+    s = pos[first:first + 1500].astype(np.float64)
+    raw = s[:, None, :] - s[None, :, :]
+    r = np.linalg.norm(raw - np.rint(raw), axis=2)
+    np.fill_diagonal(r, 9.0)
+    cell = np.floor((s + 0.5) * G).astype(np.int64).clip(0, G - 1)
+    seam = (np.abs(raw) > 0.5).any(2)
+    border = (cell[:, None, :] != cell[None, :, :]).any(2) & ~seam
+    pairs, used = [], set()
+
+    def add(i, j):
+        key = (min(i, j), max(i, j))
+        if i != j and key not in used:
+            used.add(key)
+            pairs.append((first + key[0], first + key[1]))
+
+    for mask in (seam, border):
+        i, j = np.unravel_index(np.argmin(np.where(mask, r, 9.0)), r.shape)
+        assert r[i, j] < 0.2, "no short pair across the seam or a border"
+        add(int(i), int(j))
+    for i in range(0, 1500, 50):  # triples: i, its nearest neighbour, and that one's
+        j = int(np.argmin(r[i]))
+        k = int(np.argsort(r[j])[1]) if int(np.argmin(r[j])) == i else int(np.argmin(r[j]))
+        add(i, j), add(j, k), add(i, k)
+    i, j = np.unravel_index(np.argmax(np.where(r < 9.0, r, 0.0)), r.shape)
+    add(int(i), int(j))  # (beyond the cut: only the list kernel sees it)
+    pairs += [(7, k) for k in (3, 11, 200, 399)]  # (the crowd comes first)
+    scales = np.array([(0.0, 0.0), (0.0, 0.5), (1.0, 1.0), (0.5, 0.0)])[np.arange(len(pairs)) % 4]
+    return np.array(pairs), scales[:, 0], scales[:, 1]
+
+
+def step_cases():
+    """the walks of the nonbonded steps (step_frame.h) and, as a control that shares nothing with them, the list kernel"""
+    boxes = (("unit", [1.0, 0.0, 1.0, 0.0, 0.0, 1.0], 1.0 / 3.0), ("ortho", [1.0, 0.0, 1.4, 0.0, 0.0, 2.0], 0.3),
+             ("tilted", [1.0, 0.2, 1.1, 0.1, -0.3, 1.3], 0.3))
+    rng = np.random.default_rng(11)
+    pos, batch = torus_sets(rng, (1500, 40), 400)
+    n = len(pos)
+    pd, bd = cuda(pos), cuda(batch)
+    pairs, sc, sl = bonded_list(pos, batch, 3)
+    lists = {"list": tn.ExclusionList(pairs, n, coulomb_scale=sc, dispersion_scale=sl, batch=batch),
+             "empty": tn.ExclusionList(np.zeros((0, 2), np.int64), n, batch=batch)}
+    csr = {k: (ex.row_start, ex.col, ex.coulomb_weight, ex.dispersion_weight) for k, ex in lists.items()}
+    csr["none"] = (None, None, None, None)
+    # sigma between 0.02 and 0.03 and epsilon between 0.5 and 1.5, as the steps' tests have them: the closest pair of the crowd
+    # (7e-4) stays far inside float32
+    q = rng.standard_normal(n).astype(np.float32)
+    alpha_c, alpha_d = 10.0, 11.5
+    sigma, eps = 0.02 + 0.01 * rng.random(n), 0.5 + rng.random(n)
+    c, a = (t.float().cuda() for t in tn.lj_coefficients(torch.from_numpy(sigma), torch.from_numpy(eps)))
+    xs3 = torch.stack([cuda(q), c, a], 1)
+    for name, box, r_c in boxes:
+        walk = (box, alpha_c, alpha_d, r_c)
+        report("lj_step_near %s" % name, *ops.nfft_ewald_lj_step_near(pd, xs3, bd, *walk))
+        for k in ("empty", "list"):
+            report("lj_excl_near %s %s" % (name, k), *ops.nfft_ewald_lj_excl_near(pd, xs3, bd, *csr[k], *walk))
+        report("lj_excl_list %s" % name, *ops.nfft_ewald_lj_excl_list(pd, xs3, bd, *csr["list"], *walk))
+    for T in (1, 2, 32):
+        types = (np.arange(n) % T).astype(np.int32)  # (all types present)
+        rng.shuffle(types)
+        ts, te = 0.02 + 0.01 * rng.random(T), 0.5 + rng.random(T)
+        lj = tn.LJPairTable.lorentz_berthelot(ts, te, cuda(types))
+        # exp-6: the minimum at r_m = sigma_ij with depth eps_ij, steepness 12 to 14, and a C8 of a tenth of C6 r_m^2
+        rm = 0.5 * (ts[:, None] + ts[None, :])
+        e = np.sqrt(te[:, None] * te[None, :])
+        steep = 12.0 + 2.0 * rng.random((T, T))
+        steep = 0.5 * (steep + steep.T)
+        A, B, c6 = e * 6.0 / (steep - 6.0) * np.exp(steep), steep / rm, e * steep / (steep - 6.0) * rm ** 6
+        bmh = {"grid": tn.BMHPairTable(A, B, c6, 0.1 * c6 * rm * rm, cuda(types)),
+               "nogrid": tn.BMHPairTable(A, B, c6, 0.1 * c6 * rm * rm, cuda(types), grid_c=torch.zeros(T))}
+        for name, box, r_c in boxes:
+            walk = (box, alpha_c, alpha_d, r_c)
+            for k in ("none", "empty", "list"):
+                label = "T %d %s %s" % (T, name, k)
+                report("lj_table_near " + label,
+                       *ops.nfft_ewald_lj_table_near(pd, torch.stack([cuda(q), lj.c], 1), lj.types, lj.table, bd, *csr[k], *walk))
+                for grid, tab in bmh.items():
+                    report("bmh_table_near %s " % grid + label,
+                           *ops.nfft_ewald_bmh_table_near(pd, torch.stack([cuda(q), tab.c], 1), tab.types, tab.table, bd, *csr[k], *walk))
+    ops.check_status()
+
+
 if __name__ == "__main__":
     print("library:", os.environ.get("NFFT_HIP_LIB", "the package's own"), file=sys.stderr)
     with open("/proc/self/maps") as maps:  # (what the process really runs: one libnfft_hip, under the one core.so)
         print("mapped:", sorted({line.split()[-1] for line in maps if "libnfft_hip" in line}), file=sys.stderr, flush=True)
     near_field_cases()
     ewald_cases()
+    step_cases()

@@ -426,19 +426,19 @@ def test_c_abi_validation_without_gpu():
 
 
 def test_kernel_resource_usage():
-    """both instantiations of bmh_table_near_kernel: no scratch and no spills, the 8320 bytes of static LDS of the walks of 7r,
+    """both instantiations of step_near_kernel with BmhTableLaw: no scratch and no spills, the 8320 bytes of static LDS of the walks of 7r,
     7s and 7t (the table's 16 T (T | 1) bytes are dynamic), and no name that the resource gates of those sections would take
     for their kernels (the VGPR and SGPR figures are recorded in DESIGN.md section 7u, not gated)"""
     from resource_usage import resource_usage
     usage = resource_usage("ewald_bmh_table.hip")
     seen = set()
     for name, u in sorted(usage.items()):
-        assert not re.search(r"lj_step_near_kernel|lj_excl_masked_kernel|lj_excl_list_kernel|lj_table_near_kernel", name)
-        m = re.search(r"bmh_table_near_kernelILb(\d)E", name)
+        assert not re.search(r"LjProductLaw|LjTableLaw|lj_excl_list_kernel", name)
+        m = re.search(r"step_near_kernelI\w*?BmhTableLawELb(\d)E", name)
         if not m:
             continue
         seen.add(int(m.group(1)))
-        print("bmh_table_near_kernel<%s>" % m.group(1), "VGPRs %d SGPRs %d occupancy %d LDS %d" % (u["VGPRs"], u["TotalSGPRs"], u["Occupancy"], u["LDS Size"]))
+        print("step_near_kernel<BmhTableLaw, %s>" % m.group(1), "VGPRs %d SGPRs %d occupancy %d LDS %d" % (u["VGPRs"], u["TotalSGPRs"], u["Occupancy"], u["LDS Size"]))
         assert u["ScratchSize"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (name, u)
         assert u["LDS Size"] == 8320
     assert seen == {0, 1}

@@ -1,5 +1,5 @@
-"""GPU tests of the Lennard-Jones + Coulomb step with bonded-pair exclusions: the masked pair walk and
-the list kernel of csrc/ewald_lj_excl.hip on their own, then nfft_ewald_lj_excl_step as a whole, against the float64
+"""GPU tests of the Lennard-Jones + Coulomb step with bonded-pair exclusions: the masked pair walk
+(csrc/ewald_lj_step.hip) and the list kernel of csrc/ewald_lj_excl.hip on their own, then nfft_ewald_lj_excl_step as a whole, against the float64
 restatement (tests/lj_excl_ref.py) on the same float32 positions.
 
 Points.  lj_excl_ref.bonded_points: water-like molecules with bonds of sigma / 3, four-atom chains with scaled 1-4 pairs, a

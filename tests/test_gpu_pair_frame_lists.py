@@ -1,5 +1,5 @@
 """GPU tests of the exclusion and type-table pair walks at the edges of the pair kernels' frame (csrc/pair_frame.h, DESIGN.md
-sections 7d, 7s and 7t): lj_excl_masked_kernel, lj_excl_list_kernel and both instantiations of lj_table_near_kernel on the
+sections 7d, 7s, 7t and 7v): the masked product walk, lj_excl_list_kernel and both table walks of step_near_kernel on the
 counted layouts of tests/pair_frame_ref.py -- cells of exactly 0, 1, 63, 64, 65, 127, 128, 129, 255, 256, 257 and 300 points,
 the same behind an empty point set -- with an exclusion list laid over them by tests/pair_frame_lists_ref.py, whose classes
 put a listed pair where the list's own state can go wrong: the partner staged in the second or third LDS tile (its caller

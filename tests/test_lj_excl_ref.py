@@ -335,20 +335,22 @@ def test_c_abi_validation_without_gpu():
 
 
 def test_kernel_resource_usage():
-    """both kernels of csrc/ewald_lj_excl.hip: no scratch and no spills, the masked walk with the unmasked one's 8320 bytes of
-    LDS; and no name that the resource gate of tests/test_lj_step_ref.py would take for the unmasked kernel (the VGPR and SGPR
-    figures are recorded in DESIGN.md section 7s, not gated)"""
+    """both kernels of section 7s -- the list kernel of csrc/ewald_lj_excl.hip and the masked walk, step_near_kernel<LjProductLaw,
+    true> of csrc/ewald_lj_step.hip: no scratch and no spills, the masked walk with the unmasked one's 8320 bytes of LDS; and
+    in the list kernel's file no walk that the resource gate of tests/test_lj_step_ref.py would take for its own (the VGPR and
+    SGPR figures are recorded in DESIGN.md sections 7s and 7v, not gated)"""
     from resource_usage import resource_usage
-    usage = resource_usage("ewald_lj_excl.hip")
     seen = set()
-    for name, u in sorted(usage.items()):
-        assert not re.search(r"lj_step_near_kernel", name)
-        m = re.search(r"lj_excl_masked_kernel|lj_excl_list_kernel", name)
-        if not m:
-            continue
-        seen.add(m.group(0))
-        print(m.group(0), "VGPRs %d SGPRs %d occupancy %d LDS %d" % (u["VGPRs"], u["TotalSGPRs"], u["Occupancy"], u["LDS Size"]))
-        assert u["ScratchSize"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (name, u)
-        if m.group(0) == "lj_excl_masked_kernel":
-            assert u["LDS Size"] == 8320
-    assert seen == {"lj_excl_masked_kernel", "lj_excl_list_kernel"}
+    for source in ("ewald_lj_excl.hip", "ewald_lj_step.hip"):
+        for name, u in sorted(resource_usage(source).items()):
+            assert source == "ewald_lj_step.hip" or not re.search(r"step_near_kernel", name)
+            m = re.search(r"step_near_kernelI\w*?LjProductLawELb1E|lj_excl_list_kernel", name)
+            if not m:
+                continue
+            key = "lj_excl_list_kernel" if m.group(0) == "lj_excl_list_kernel" else "masked walk"
+            seen.add((source, key))
+            print(key, "VGPRs %d SGPRs %d occupancy %d LDS %d" % (u["VGPRs"], u["TotalSGPRs"], u["Occupancy"], u["LDS Size"]))
+            assert u["ScratchSize"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (name, u)
+            if key == "masked walk":
+                assert u["LDS Size"] == 8320
+    assert seen == {("ewald_lj_step.hip", "masked walk"), ("ewald_lj_excl.hip", "lj_excl_list_kernel")}

@@ -16,21 +16,21 @@ from ewald_virial_ref import rel_fro
 
 
 def test_kernel_resource_usage():
-    """both kernels: no scratch and no spills (the library's own flags; the VGPR, SGPR and LDS figures are recorded in
-    DESIGN.md section 7r, not gated)"""
+    """the spectral kernel and both instantiations of step_near_kernel with the product law, the unmasked walk and the masked
+    one of section 7s: no scratch and no spills (the library's own flags; the VGPR, SGPR and LDS figures are recorded in
+    DESIGN.md sections 7r and 7v, not gated)"""
     from resource_usage import resource_usage
     usage = resource_usage("ewald_lj_step.hip")
     seen = set()
     for name, u in sorted(usage.items()):
-        m = re.search(r"(lj_step_near_kernel)ILb(\d)E|(lj_step_spectral_kernel)", name)
+        m = re.search(r"step_near_kernelI\w*?(LjProductLaw)ELb(\d)E|(lj_step_spectral_kernel)", name)
         if not m:
             continue
         key = (m.group(1), int(m.group(2))) if m.group(1) else (m.group(3),)
         seen.add(key)
         print(key, "VGPRs %d SGPRs %d occupancy %d LDS %d" % (u["VGPRs"], u["TotalSGPRs"], u["Occupancy"], u["LDS Size"]))
         assert u["ScratchSize"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (key, u)
-    # (the unit cube runs as the identity box: BOX = true only)
-    assert seen == {("lj_step_near_kernel", 1), ("lj_step_spectral_kernel",)}
+    assert seen == {("LjProductLaw", 0), ("LjProductLaw", 1), ("lj_step_spectral_kernel",)}
 
 
 def test_lj_coefficients():

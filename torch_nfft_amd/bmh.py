@@ -15,15 +15,13 @@ The exponential is finite at ``r = 0`` and the attractions are not: below the ma
 inside the first neighbour shell for published tables) the model attracts without bound.  Nothing here guards that inner
 wall; a configuration that crosses it is the caller's to prevent.
 """
-import math
-
 import torch
 
 from . import ops
 from .dispersion import DispersionSplitting
 from .exclusions import check_exclusions
-from .ewald import EwaldSplitting, _IDENTITY6, _fractional, _set_sums, _voigt_to_matrix
-from .lj import MAX_TYPES, _check_splittings, _check_values
+from .ewald import EwaldSplitting, _IDENTITY6, _fractional
+from .lj import MAX_TYPES, _check_splittings, _check_values, _step_tail
 from .nfft import nfft_adjoint, nfft_forward
 
 _FLOAT32_MAX = 3.4028234663852886e38
@@ -214,24 +212,11 @@ def nfft_ewald_bmh_table_step(q, table, pos, batch=None, /, coulomb=None, disper
             far_force = q.unsqueeze(1) * far[:, :3] - c.unsqueeze(1) * far[:, 3:]
         xs = torch.stack([q, c], 1)
         walk = (box6, alpha_c, alpha_d, coulomb.r_cut)
-        if ex is None:
-            f, near8 = ops.nfft_ewald_bmh_table_near(pos, xs, table.types, table.table, batch, None, None, None, None, *walk)
-            F = f + far_force
-        else:
+        lists, listed = (None, None, None, None), None
+        if ex is not None:
             # the listed pairs come scaled out of the walk; the list step of 7s takes the smooth share of q_i q_j and c_i c_j
             # back out of the far field, which holds nothing of A, dC6 and C8
             lists = (ex.row_start, ex.col, ex.coulomb_weight, ex.dispersion_weight)
-            f, near8 = ops.nfft_ewald_bmh_table_near(pos, xs, table.types, table.table, batch, *lists, *walk)
-            lf, list8 = ops.nfft_ewald_lj_excl_list(pos, torch.stack([q, c, torch.zeros_like(q)], 1), batch, *lists, *walk)
-            F = (f.double() + lf.double() + far_force.double()).float()
-            near8 = near8 + list8
-        eight = far8 + near8  # [B, 8] float64
-        q64, c64 = q.double(), c.double()
-        total = _set_sums(q64, batch)[0]
-        background = (math.pi / (2.0 * alpha_c * alpha_c * coulomb.volume)) * total * total
-        U_coulomb = eight[:, 0] - (alpha_c / math.sqrt(math.pi)) * _set_sums(q64 * q64, batch)[0] - background
-        U_sr = eight[:, 1] + (alpha_d ** 6 / 12.0) * _set_sums(c64 * c64, batch)[0]
-        W = _voigt_to_matrix(eight[:, 2:])
-        for e in range(3):
-            W[:, e, e] -= background
-        return F, U_coulomb.float(), U_sr.float(), W.float()
+            listed = ops.nfft_ewald_lj_excl_list(pos, torch.stack([q, c, torch.zeros_like(q)], 1), batch, *lists, *walk)
+        f, near8 = ops.nfft_ewald_bmh_table_near(pos, xs, table.types, table.table, batch, *lists, *walk)
+        return _step_tail(far_force, far8, f, near8, listed, q, c, alpha_c, alpha_d, coulomb, batch)

@@ -718,27 +718,42 @@ static int validate_lj_step_near(const nfft_hip_ewald_box_problem *p, double alp
 
 static int validate_lj_step_spectral(int64_t N, int64_t batch_size) { return validate_virial_far(N, batch_size, 1); }
 
+// the four walks of these steps (step_frame.h) have one workspace ...
 int64_t nfft_hip_ewald_lj_step_near_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion)
 {
     if (validate_lj_step_near(p, alpha_dispersion)) return -1;
-    return ewald_lj_step_near_workspace(p) + 256;
+    return ewald_step8_near_workspace(p) + 256;
+}
+
+// ... and, after the pending fault and their own checks (`rc`: the first of them that failed), one call: out8, the empty
+// problem, the null checks (a walk with a table reads types), the workspace and the launch
+static int step_near_call(step_near_launch *launch, int rc, const nfft_hip_ewald_box_problem *p, double alpha_dispersion,
+                          int64_t num_types, int64_t num_entries, const float *points, const float *xs, const int32_t *types,
+                          const float *table, const int32_t *start, const int64_t *index, const int32_t *row_start,
+                          const int32_t *col, const float *weight_coulomb, const float *weight_lj, float *f, double *out8,
+                          void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (rc) return rc;
+    if (!out8) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
+    if (p->num_points == 0) {  // (no row of f)
+        NFFT_HIP_CHECK(hipMemsetAsync(out8, 0, (size_t)(p->batch_size * 8) * sizeof(double), (hipStream_t)stream));
+        return 0;
+    }
+    if (!points || !xs || (table && !types) || !start || !index || !f) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
+    char *ws = workspace_base(workspace, workspace_bytes, ewald_step8_near_workspace(p) + 256);
+    if (!ws) return NFFT_HIP_EWORKSPACE;
+    return launch(p, alpha_dispersion, num_types, num_entries, points, xs, types, table, start, index, row_start, col, weight_coulomb,
+                  weight_lj, f, out8, ws, (hipStream_t)stream);
 }
 
 int nfft_hip_ewald_lj_step_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, const float *points, const float *xs,
                                 const int32_t *start, const int64_t *index, float *f, double *out8, void *workspace,
                                 int64_t workspace_bytes, void *stream)
 {
-    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
-    if (int rc = validate_lj_step_near(p, alpha_dispersion)) return rc;
-    if (!out8) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
-    if (p->num_points == 0) {  // (no row of f)
-        NFFT_HIP_CHECK(hipMemsetAsync(out8, 0, (size_t)(p->batch_size * 8) * sizeof(double), (hipStream_t)stream));
-        return 0;
-    }
-    if (!points || !xs || !start || !index || !f) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    char *ws = workspace_base(workspace, workspace_bytes, ewald_lj_step_near_workspace(p) + 256);
-    if (!ws) return NFFT_HIP_EWORKSPACE;
-    return launch_ewald_lj_step_near(p, alpha_dispersion, points, xs, start, index, f, out8, ws, (hipStream_t)stream);
+    const int fault = take_pending_fault();  // a kernel of an earlier call gave up: say so
+    return step_near_call(launch_ewald_lj_step_near, fault ? fault : validate_lj_step_near(p, alpha_dispersion), p, alpha_dispersion,
+                          0, 0, points, xs, nullptr, nullptr, start, index, nullptr, nullptr, nullptr, nullptr, f, out8, workspace,
+                          workspace_bytes, stream);
 }
 
 int64_t nfft_hip_ewald_lj_step_spectral_workspace_bytes(int64_t N, int64_t batch_size)
@@ -788,8 +803,7 @@ static int validate_lj_excl(const nfft_hip_ewald_box_problem *p, double alpha_di
 
 int64_t nfft_hip_ewald_lj_excl_near_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion)
 {
-    if (validate_lj_step_near(p, alpha_dispersion)) return -1;
-    return ewald_lj_excl_near_workspace(p) + 256;
+    return nfft_hip_ewald_lj_step_near_workspace_bytes(p, alpha_dispersion);
 }
 
 int nfft_hip_ewald_lj_excl_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_entries,
@@ -797,18 +811,12 @@ int nfft_hip_ewald_lj_excl_near(const nfft_hip_ewald_box_problem *p, double alph
                                 const int32_t *row_start, const int32_t *col, const float *weight_coulomb, const float *weight_lj,
                                 float *f, double *out8, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
-    if (int rc = validate_lj_excl(p, alpha_dispersion, num_entries, row_start, col, weight_coulomb, weight_lj)) return rc;
-    if (!out8) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
-    if (p->num_points == 0) {  // (no row of f)
-        NFFT_HIP_CHECK(hipMemsetAsync(out8, 0, (size_t)(p->batch_size * 8) * sizeof(double), (hipStream_t)stream));
-        return 0;
-    }
-    if (!points || !xs || !start || !index || !f) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    char *ws = workspace_base(workspace, workspace_bytes, ewald_lj_excl_near_workspace(p) + 256);
-    if (!ws) return NFFT_HIP_EWORKSPACE;
-    return launch_ewald_lj_excl_near(p, alpha_dispersion, num_entries, points, xs, start, index, row_start, col, weight_coulomb,
-                                     weight_lj, f, out8, ws, (hipStream_t)stream);
+    const int fault = take_pending_fault();  // a kernel of an earlier call gave up: say so
+    return step_near_call(
+        launch_ewald_lj_step_near,
+        fault ? fault : validate_lj_excl(p, alpha_dispersion, num_entries, row_start, col, weight_coulomb, weight_lj), p,
+        alpha_dispersion, 0, num_entries, points, xs, nullptr, nullptr, start, index, row_start, col, weight_coulomb, weight_lj, f,
+        out8, workspace, workspace_bytes, stream);
 }
 
 int64_t nfft_hip_ewald_lj_excl_list_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion)
@@ -836,15 +844,19 @@ int nfft_hip_ewald_lj_excl_list(const nfft_hip_ewald_box_problem *p, double alph
                                      set_start, f, out8, ws, (hipStream_t)stream);
 }
 
-// ---- the same walk with a type-pair table: the checks above, the table's, and the list's if any ---
-static int validate_lj_table(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_types, const void *table,
-                             int64_t num_entries, const void *row_start, const void *col, const void *weight_coulomb,
-                             const void *weight_lj)
+// ---- the same walk with a type-pair table (DESIGN.md sections 7t and 7u): the checks above, the table's, and the list's if
+// any.  An entry of entry_bytes bytes (8: (C12, dC6); 16: (A, B, dC6, C8)) moves as one load ---
+static int validate_step_table(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_types, const void *table,
+                               int entry_bytes, int64_t num_entries, const void *row_start, const void *col,
+                               const void *weight_coulomb, const void *weight_lj)
 {
     if (int rc = validate_lj_step_near(p, alpha_dispersion)) return rc;
     if (num_types < 1 || num_types > 32) { set_error("Input mismatch: num_types must lie in [1, 32]"); return NFFT_HIP_EINVAL; }
     if (!table) { set_error("Input mismatch: table is null"); return NFFT_HIP_EINVAL; }
-    if ((uintptr_t)table & 7) { set_error("Input mismatch: table must be 8-byte aligned"); return NFFT_HIP_EINVAL; }
+    if ((uintptr_t)table & (uintptr_t)(entry_bytes - 1)) {
+        set_error(entry_bytes == 8 ? "Input mismatch: table must be 8-byte aligned" : "Input mismatch: table must be 16-byte aligned");
+        return NFFT_HIP_EINVAL;
+    }
     if (p->num_points >= (int64_t(1) << 31)) { set_error("Input mismatch: too many points or entries"); return NFFT_HIP_EINVAL; }
     if (!row_start) {  // no list: the unmasked walk
         if (col || weight_coulomb || weight_lj || num_entries != 0) {
@@ -858,8 +870,7 @@ static int validate_lj_table(const nfft_hip_ewald_box_problem *p, double alpha_d
 
 int64_t nfft_hip_ewald_lj_table_near_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion)
 {
-    if (validate_lj_step_near(p, alpha_dispersion)) return -1;
-    return ewald_lj_table_near_workspace(p) + 256;
+    return nfft_hip_ewald_lj_step_near_workspace_bytes(p, alpha_dispersion);
 }
 
 int nfft_hip_ewald_lj_table_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_types, int64_t num_entries,
@@ -868,46 +879,18 @@ int nfft_hip_ewald_lj_table_near(const nfft_hip_ewald_box_problem *p, double alp
                                  const float *weight_coulomb, const float *weight_lj, float *f, double *out8, void *workspace,
                                  int64_t workspace_bytes, void *stream)
 {
-    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
-    if (int rc = validate_lj_table(p, alpha_dispersion, num_types, table, num_entries, row_start, col, weight_coulomb, weight_lj))
-        return rc;
-    if (!out8) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
-    if (p->num_points == 0) {  // (no row of f)
-        NFFT_HIP_CHECK(hipMemsetAsync(out8, 0, (size_t)(p->batch_size * 8) * sizeof(double), (hipStream_t)stream));
-        return 0;
-    }
-    if (!points || !xs || !types || !start || !index || !f) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    char *ws = workspace_base(workspace, workspace_bytes, ewald_lj_table_near_workspace(p) + 256);
-    if (!ws) return NFFT_HIP_EWORKSPACE;
-    return launch_ewald_lj_table_near(p, alpha_dispersion, num_types, num_entries, points, xs, types, table, start, index, row_start,
-                                      col, weight_coulomb, weight_lj, f, out8, ws, (hipStream_t)stream);
+    const int fault = take_pending_fault();  // a kernel of an earlier call gave up: say so
+    return step_near_call(
+        launch_ewald_lj_table_near,
+        fault ? fault : validate_step_table(p, alpha_dispersion, num_types, table, 8, num_entries, row_start, col, weight_coulomb, weight_lj),
+        p, alpha_dispersion, num_types, num_entries, points, xs, types, table, start, index, row_start, col, weight_coulomb, weight_lj,
+        f, out8, workspace, workspace_bytes, stream);
 }
 
-// ---- the walk of the Buckingham / Born-Mayer-Huggins step: the checks of the table walk above, with
-// an entry of 16 bytes that moves as one load ---
-static int validate_bmh_table(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_types, const void *table,
-                              int64_t num_entries, const void *row_start, const void *col, const void *weight_coulomb,
-                              const void *weight_lj)
-{
-    if (int rc = validate_lj_step_near(p, alpha_dispersion)) return rc;
-    if (num_types < 1 || num_types > 32) { set_error("Input mismatch: num_types must lie in [1, 32]"); return NFFT_HIP_EINVAL; }
-    if (!table) { set_error("Input mismatch: table is null"); return NFFT_HIP_EINVAL; }
-    if ((uintptr_t)table & 15) { set_error("Input mismatch: table must be 16-byte aligned"); return NFFT_HIP_EINVAL; }
-    if (p->num_points >= (int64_t(1) << 31)) { set_error("Input mismatch: too many points or entries"); return NFFT_HIP_EINVAL; }
-    if (!row_start) {  // no list: the unmasked walk
-        if (col || weight_coulomb || weight_lj || num_entries != 0) {
-            set_error("Input mismatch: a list without row_start");
-            return NFFT_HIP_EINVAL;
-        }
-        return 0;
-    }
-    return validate_lj_excl(p, alpha_dispersion, num_entries, row_start, col, weight_coulomb, weight_lj);
-}
-
+// ---- the walk of the Buckingham / Born-Mayer-Huggins step ---
 int64_t nfft_hip_ewald_bmh_table_near_workspace_bytes(const nfft_hip_ewald_box_problem *p, double alpha_dispersion)
 {
-    if (validate_lj_step_near(p, alpha_dispersion)) return -1;
-    return ewald_bmh_table_near_workspace(p) + 256;
+    return nfft_hip_ewald_lj_step_near_workspace_bytes(p, alpha_dispersion);
 }
 
 int nfft_hip_ewald_bmh_table_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_types, int64_t num_entries,
@@ -916,19 +899,12 @@ int nfft_hip_ewald_bmh_table_near(const nfft_hip_ewald_box_problem *p, double al
                                   const float *weight_coulomb, const float *weight_lj, float *f, double *out8, void *workspace,
                                   int64_t workspace_bytes, void *stream)
 {
-    if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
-    if (int rc = validate_bmh_table(p, alpha_dispersion, num_types, table, num_entries, row_start, col, weight_coulomb, weight_lj))
-        return rc;
-    if (!out8) { set_error("Input mismatch: out is null"); return NFFT_HIP_EINVAL; }
-    if (p->num_points == 0) {  // (no row of f)
-        NFFT_HIP_CHECK(hipMemsetAsync(out8, 0, (size_t)(p->batch_size * 8) * sizeof(double), (hipStream_t)stream));
-        return 0;
-    }
-    if (!points || !xs || !types || !start || !index || !f) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
-    char *ws = workspace_base(workspace, workspace_bytes, ewald_bmh_table_near_workspace(p) + 256);
-    if (!ws) return NFFT_HIP_EWORKSPACE;
-    return launch_ewald_bmh_table_near(p, alpha_dispersion, num_types, num_entries, points, xs, types, table, start, index, row_start,
-                                       col, weight_coulomb, weight_lj, f, out8, ws, (hipStream_t)stream);
+    const int fault = take_pending_fault();  // a kernel of an earlier call gave up: say so
+    return step_near_call(
+        launch_ewald_bmh_table_near,
+        fault ? fault : validate_step_table(p, alpha_dispersion, num_types, table, 16, num_entries, row_start, col, weight_coulomb, weight_lj),
+        p, alpha_dispersion, num_types, num_entries, points, xs, types, table, start, index, row_start, col, weight_coulomb, weight_lj,
+        f, out8, workspace, workspace_bytes, stream);
 }
 
 // ---- the spectral step of the dipole sum -------------------------------------------------------

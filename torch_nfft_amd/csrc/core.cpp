@@ -1700,76 +1700,28 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_lj_excl_list(at::Tensor pos, at::T
     return {f, out};
 }
 
-// ---- the pair walk of the Lennard-Jones + Coulomb step with a type-pair table (not in the reference) --
-// (f, eight) of nfft_ewald_lj_step_near for xs [n, 2] = (q, c), types [n] int32 and table [T, T, 2] float32 = (C12, dC6):
-// the pair's repulsion and what its C6 has above c_i c_j come from the table entry of the two types.  The four list tensors
-// are ExclusionList's, all given or none: with them the listed pairs' terms are scaled as by nfft_ewald_lj_excl_near
-std::tuple<at::Tensor, at::Tensor> nfft_ewald_lj_table_near(at::Tensor pos, at::Tensor xs, at::Tensor types, at::Tensor table,
-                                                            c10::optional<at::Tensor> opt_batch,
-                                                            c10::optional<at::Tensor> row_start, c10::optional<at::Tensor> col,
-                                                            c10::optional<at::Tensor> weight_coulomb,
-                                                            c10::optional<at::Tensor> weight_lj, std::vector<double> box,
-                                                            double alpha_coulomb, double alpha_dispersion, double r_cut)
-{
-    TORCH_CHECK(xs.is_cuda(), "torch_nfft._nfft_ewald_lj_table_near is currently only implemented for GPU tensors");
-    const Points p = check_points(pos, opt_batch, "batch");
-    CHECK_INPUT(p.dim == 3);
-    CHECK_INPUT(xs.scalar_type() == at::kFloat && xs.dim() == 2 && xs.size(0) == p.n && xs.size(1) == 2);
-    CHECK_INPUT(types.scalar_type() == at::kInt && types.dim() == 1 && types.size(0) == p.n);
-    CHECK_INPUT(table.scalar_type() == at::kFloat && table.dim() == 3 && table.size(0) == table.size(1) && table.size(2) == 2);
-    CHECK_INPUT(table.size(0) >= 1 && table.size(0) <= 32);
-    CHECK_INPUT(xs.device() == pos.device() && types.device() == pos.device() && table.device() == pos.device());
-    CHECK_INPUT(box.size() == 6);
-    const bool masked = row_start.has_value();
-    CHECK_INPUT(col.has_value() == masked && weight_coulomb.has_value() == masked && weight_lj.has_value() == masked);
-    ExclInput ex;
-    at::Tensor wl;
-    if (masked) {
-        ex = check_excl(*row_start, *col, *weight_coulomb, pos, p.n);
-        CHECK_INPUT(weight_lj->scalar_type() == at::kFloat && weight_lj->dim() == 1 && weight_lj->numel() == ex.col.numel());
-        CHECK_INPUT(weight_lj->device() == pos.device());
-        wl = weight_lj->contiguous();
-    }
-    const nfft_hip_ewald_box_problem q = ewald_box_problem(p, 1, true, box, alpha_coulomb, r_cut);
-    const int64_t ws_bytes = nfft_hip_ewald_lj_table_near_workspace_bytes(&q, alpha_dispersion);
-    if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
-    // (zeros: a point whose coordinates are not numbers has no cell and is not written)
-    at::Tensor f = at::zeros({p.n, 3}, xs.options());
-    at::Tensor out = at::zeros({p.B, 8}, xs.options().dtype(at::kDouble));
-    if (p.n == 0) return {f, out};  // no launch
-    c10::DeviceGuard guard(xs.device());
-    const CellOrder o = torus_cell_order(p, q.cells);
-    const at::Tensor xr = real_rows(xs, true, p.n, 2, o.order);
-    const at::Tensor tr = types.index_select(0, o.order);
-    const at::Tensor tab = table.contiguous();
-    at::Tensor ws = byte_buffer(ws_bytes, xs);
-    const int64_t entries = masked ? ex.col.numel() : 0;
-    const bool any = entries > 0;
-    check_rc(nfft_hip_ewald_lj_table_near(&q, alpha_dispersion, tab.size(0), entries, o.pos.data_ptr<float>(), xr.data_ptr<float>(),
-                                          tr.data_ptr<int32_t>(), tab.data_ptr<float>(), o.start.data_ptr<int32_t>(),
-                                          o.order.data_ptr<int64_t>(), masked ? ex.row_start.data_ptr<int32_t>() : nullptr,
-                                          any ? ex.col.data_ptr<int32_t>() : nullptr, any ? ex.weight.data_ptr<float>() : nullptr,
-                                          any ? wl.data_ptr<float>() : nullptr, f.data_ptr<float>(), out.data_ptr<double>(),
-                                          ws.data_ptr(), ws_bytes, stream_of(xs)));
-    return {f, out};
-}
+// ---- the pair walks with a type-pair table (not in the reference; DESIGN.md sections 7t and 7u) ---------------------------
+typedef int table_near_entry(const nfft_hip_ewald_box_problem *, double, int64_t, int64_t, const float *, const float *,
+                             const int32_t *, const float *, const int32_t *, const int64_t *, const int32_t *, const int32_t *,
+                             const float *, const float *, float *, double *, void *, int64_t, void *);
 
-// ---- the pair walk of the Buckingham / Born-Mayer-Huggins + Coulomb step (not in the reference) ------
-// (f, eight) of nfft_ewald_lj_table_near for table [T, T, 4] float32 = (A, B, dC6, C8): the pair energy of two types within
-// r_cut is A e^(-B r) - dC6 / r^6 - C8 / r^8 beside the Ewald weights of (q, c).  Everything else as there
-std::tuple<at::Tensor, at::Tensor> nfft_ewald_bmh_table_near(at::Tensor pos, at::Tensor xs, at::Tensor types, at::Tensor table,
-                                                             c10::optional<at::Tensor> opt_batch,
-                                                             c10::optional<at::Tensor> row_start, c10::optional<at::Tensor> col,
-                                                             c10::optional<at::Tensor> weight_coulomb,
-                                                             c10::optional<at::Tensor> weight_lj, std::vector<double> box,
-                                                             double alpha_coulomb, double alpha_dispersion, double r_cut)
+// (f, eight) of `entry` for xs [n, 2] = (q, c), types [n] int32 and table [T, T, width] float32.  The four list tensors are
+// ExclusionList's, all given or none: with them the listed pairs' terms are scaled as by nfft_ewald_lj_excl_near.  realign:
+// the bytes to which a table that is a view into a larger tensor is cloned (1: taken as it comes)
+std::tuple<at::Tensor, at::Tensor> ewald_table_near(const char *name, int64_t width, uintptr_t realign, table_near_entry *entry,
+                                                    const at::Tensor &pos, const at::Tensor &xs, const at::Tensor &types,
+                                                    const at::Tensor &table, const c10::optional<at::Tensor> &opt_batch,
+                                                    const c10::optional<at::Tensor> &row_start, const c10::optional<at::Tensor> &col,
+                                                    const c10::optional<at::Tensor> &weight_coulomb,
+                                                    const c10::optional<at::Tensor> &weight_lj, const std::vector<double> &box,
+                                                    double alpha_coulomb, double alpha_dispersion, double r_cut)
 {
-    TORCH_CHECK(xs.is_cuda(), "torch_nfft._nfft_ewald_bmh_table_near is currently only implemented for GPU tensors");
+    TORCH_CHECK(xs.is_cuda(), "torch_nfft.", name, " is currently only implemented for GPU tensors");
     const Points p = check_points(pos, opt_batch, "batch");
     CHECK_INPUT(p.dim == 3);
     CHECK_INPUT(xs.scalar_type() == at::kFloat && xs.dim() == 2 && xs.size(0) == p.n && xs.size(1) == 2);
     CHECK_INPUT(types.scalar_type() == at::kInt && types.dim() == 1 && types.size(0) == p.n);
-    CHECK_INPUT(table.scalar_type() == at::kFloat && table.dim() == 3 && table.size(0) == table.size(1) && table.size(2) == 4);
+    CHECK_INPUT(table.scalar_type() == at::kFloat && table.dim() == 3 && table.size(0) == table.size(1) && table.size(2) == width);
     CHECK_INPUT(table.size(0) >= 1 && table.size(0) <= 32);
     CHECK_INPUT(xs.device() == pos.device() && types.device() == pos.device() && table.device() == pos.device());
     CHECK_INPUT(box.size() == 6);
@@ -1784,7 +1736,7 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_bmh_table_near(at::Tensor pos, at:
         wl = weight_lj->contiguous();
     }
     const nfft_hip_ewald_box_problem q = ewald_box_problem(p, 1, true, box, alpha_coulomb, r_cut);
-    const int64_t ws_bytes = nfft_hip_ewald_bmh_table_near_workspace_bytes(&q, alpha_dispersion);
+    const int64_t ws_bytes = nfft_hip_ewald_lj_table_near_workspace_bytes(&q, alpha_dispersion);  // (one for every step walk)
     if (ws_bytes < 0) check_rc(NFFT_HIP_EINVAL);
     // (zeros: a point whose coordinates are not numbers has no cell and is not written)
     at::Tensor f = at::zeros({p.n, 3}, xs.options());
@@ -1795,17 +1747,41 @@ std::tuple<at::Tensor, at::Tensor> nfft_ewald_bmh_table_near(at::Tensor pos, at:
     const at::Tensor xr = real_rows(xs, true, p.n, 2, o.order);
     const at::Tensor tr = types.index_select(0, o.order);
     at::Tensor tab = table.contiguous();
-    if ((uintptr_t)tab.data_ptr() & 15) tab = tab.clone();  // (a view into a larger tensor: an entry moves as one 16-byte load)
+    if ((uintptr_t)tab.data_ptr() & (realign - 1)) tab = tab.clone();  // (an entry moves as one load)
     at::Tensor ws = byte_buffer(ws_bytes, xs);
     const int64_t entries = masked ? ex.col.numel() : 0;
     const bool any = entries > 0;
-    check_rc(nfft_hip_ewald_bmh_table_near(&q, alpha_dispersion, tab.size(0), entries, o.pos.data_ptr<float>(), xr.data_ptr<float>(),
-                                           tr.data_ptr<int32_t>(), tab.data_ptr<float>(), o.start.data_ptr<int32_t>(),
-                                           o.order.data_ptr<int64_t>(), masked ? ex.row_start.data_ptr<int32_t>() : nullptr,
-                                           any ? ex.col.data_ptr<int32_t>() : nullptr, any ? ex.weight.data_ptr<float>() : nullptr,
-                                           any ? wl.data_ptr<float>() : nullptr, f.data_ptr<float>(), out.data_ptr<double>(),
-                                           ws.data_ptr(), ws_bytes, stream_of(xs)));
+    check_rc(entry(&q, alpha_dispersion, tab.size(0), entries, o.pos.data_ptr<float>(), xr.data_ptr<float>(), tr.data_ptr<int32_t>(),
+                   tab.data_ptr<float>(), o.start.data_ptr<int32_t>(), o.order.data_ptr<int64_t>(),
+                   masked ? ex.row_start.data_ptr<int32_t>() : nullptr, any ? ex.col.data_ptr<int32_t>() : nullptr,
+                   any ? ex.weight.data_ptr<float>() : nullptr, any ? wl.data_ptr<float>() : nullptr, f.data_ptr<float>(),
+                   out.data_ptr<double>(), ws.data_ptr(), ws_bytes, stream_of(xs)));
     return {f, out};
+}
+
+// table = (C12, dC6): the pair's repulsion and what its C6 has above c_i c_j come from the table entry of the two types
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_lj_table_near(at::Tensor pos, at::Tensor xs, at::Tensor types, at::Tensor table,
+                                                            c10::optional<at::Tensor> opt_batch,
+                                                            c10::optional<at::Tensor> row_start, c10::optional<at::Tensor> col,
+                                                            c10::optional<at::Tensor> weight_coulomb,
+                                                            c10::optional<at::Tensor> weight_lj, std::vector<double> box,
+                                                            double alpha_coulomb, double alpha_dispersion, double r_cut)
+{
+    return ewald_table_near("_nfft_ewald_lj_table_near", 2, 1, nfft_hip_ewald_lj_table_near, pos, xs, types, table, opt_batch,
+                            row_start, col, weight_coulomb, weight_lj, box, alpha_coulomb, alpha_dispersion, r_cut);
+}
+
+// table = (A, B, dC6, C8): the pair energy of two types within r_cut is A e^(-B r) - dC6 / r^6 - C8 / r^8 beside the Ewald
+// weights of (q, c); an entry moves as one 16-byte load
+std::tuple<at::Tensor, at::Tensor> nfft_ewald_bmh_table_near(at::Tensor pos, at::Tensor xs, at::Tensor types, at::Tensor table,
+                                                             c10::optional<at::Tensor> opt_batch,
+                                                             c10::optional<at::Tensor> row_start, c10::optional<at::Tensor> col,
+                                                             c10::optional<at::Tensor> weight_coulomb,
+                                                             c10::optional<at::Tensor> weight_lj, std::vector<double> box,
+                                                             double alpha_coulomb, double alpha_dispersion, double r_cut)
+{
+    return ewald_table_near("_nfft_ewald_bmh_table_near", 4, 16, nfft_hip_ewald_bmh_table_near, pos, xs, types, table, opt_batch,
+                            row_start, col, weight_coulomb, weight_lj, box, alpha_coulomb, alpha_dispersion, r_cut);
 }
 
 // coefficient operators (csrc/core.cpp:124-171; drivers core_cuda.cu:855-1064): outputs live on the current device

@@ -4,14 +4,8 @@
 // SCALED by s before they reach an accumulator; the bounded smooth share that the far field has added is taken out by the
 // list kernel.  Nothing of the size of 1/r, 1/r^6 or 1/r^12 of a bonded pair is formed and cancelled.
 //
-// lj_excl_masked_kernel  lj_step_near_kernel<true>'s items, lanes, walk, tiles, image, test 0 < rr < rc2 and epilogue.  The
-//                        staging policy StageLjIndexed puts (q_j, c_j, a_j) and, as integer bits, the streamed point's
-//                        caller-order index into one float4: one 16-byte LDS read per pair, 8320 bytes of LDS as before.
-//                        A lane reads its own caller index and its row bounds once and keeps lo = col[first], hi =
-//                        col[last - 1] (an empty row: an empty interval).  A passing pair whose index lies outside [lo, hi]
-//                        takes the expressions of the unmasked body; inside, a binary search of the lane's row decides.  On
-//                        a hit q_i q_j is scaled by s^C, c_i c_j and p = a_i a_j / r^12 by s^L, and the same expressions
-//                        follow; a pair with both scales zero returns before its weights are formed and adds nothing.
+// The masked pair walk is step_near_kernel<LjProductLaw, true> (step_frame.h, ewald_lj_step.hip).  Here:
+//
 // lj_excl_list_kernel    ewald_excl_kernel's lane per point in the caller's order on the positions reduced by torus_reduce
 //                        (the image carries the sweep's bits, so both kernels agree on which side of r_c a pair lies), in
 //                        row order, three float32 force sums per lane; and ewald_excl_virial_kernel's pair-once (col > row)
@@ -27,148 +21,20 @@
 //                        It writes what to ADD: lf_i = -sum_k (w^C q_i q_j T_C - w^L c_i c_j T_D) d and the eight sums
 //                        (-w^C qq S_C, +w^L cc S_D, -g d_a d_b).
 //
-// Entries whose column lies outside [0, n) and row bounds outside [0, entries] are skipped, not trusted.  The second level of
-// both is launch_virial_sum_terms of ewald_virial.hip with eight terms.  No atomics anywhere: two calls give the same bits.
-#include "pair_frame.h"
+// Entries whose column lies outside [0, n) and row bounds outside [0, entries] are skipped, not trusted.  The second level
+// is launch_virial_sum_terms of ewald_virial.hip with eight terms.  No atomics anywhere: two calls give the same bits.
+#include "step_frame.h"
 
 namespace nfft {
 
 namespace {
 
-constexpr int kLjTerms = 8;   // U_C, U_LJ, xx, yy, zz, yz, xz, xy
-constexpr int kLjSums = 11;   // s d_x, d_y, d_z; s d_a d_b in the order of the virial's terms; the two energies
+constexpr int kLjTerms = kStepTerms;
 constexpr int kLjValues = 3;  // q, c, a
 constexpr int kListBlock = 256;
 constexpr int kListBlocks = 1024;          // workgroups per point set of the list kernel, at most
 constexpr double kSeriesSwitch = 0.125;    // u = alpha^2 r^2 below which the series run
 constexpr int kSeriesTerms = 8;
-
-// the CSR list on the device
-struct ExclList {
-    const int *__restrict__ row_start;
-    const int *__restrict__ col;
-    const float *__restrict__ wc;
-    const float *__restrict__ wl;
-    int n, entries;
-};
-
-// staging policy: (q_j, c_j, a_j) of xs [n, 3] and the caller-order index of the streamed point as integer bits
-struct StageLjIndexed {
-    float *s_x;
-    const float *__restrict__ xs;
-    const int64_t *__restrict__ index;
-    __device__ __forceinline__ void point(int j, int64_t i) const
-    {
-        const float *xp = xs + i * kLjValues;
-        s_x[j * 4 + 0] = xp[0];
-        s_x[j * 4 + 1] = xp[1];
-        s_x[j * 4 + 2] = xp[2];
-        s_x[j * 4 + 3] = __int_as_float((int)index[i]);
-    }
-};
-
-// the entry of the ascending row [first, last) whose column is j, or -1
-__device__ __forceinline__ int find_in_row(const int *__restrict__ col, int first, int last, int j)
-{
-    while (first < last) {
-        const int mid = first + ((last - first) >> 1);
-        const int c = col[mid];
-        if (c == j) return mid;
-        if (c < j) first = mid + 1;
-        else last = mid;
-    }
-    return -1;
-}
-
-__global__ void __launch_bounds__(kNearBlock) lj_excl_masked_kernel(EwaldPairParams qc, EwaldPairParams qd, ExclList ex,
-                                                                    const int2 *__restrict__ items, const float *__restrict__ pos,
-                                                                    const float *__restrict__ xs, const int *__restrict__ start,
-                                                                    const int64_t *__restrict__ index, float *__restrict__ f,
-                                                                    double *__restrict__ partial)
-{
-    __shared__ float4 s_pos[kNearTile];
-    __shared__ __attribute__((aligned(16))) float s_x[kNearTile * 4];
-    __shared__ double s_red[kNearBlock / 64][kLjTerms];
-    const int2 item = items[blockIdx.x];
-    if (item.x < 0) return;  // (uniform: an empty slot; the second level skips it)
-    const PairLane lane = pair_lane(item, start);
-    const WrappedWalk walk(lane.cell, qc.G0, qc.G1, qc.G2);
-    // (a lane without a target sums pairs of the origin with zero parameters; it stores nothing)
-    const float4 t = lane_position(lane, pos, 3, 0.f);
-    float qi = 0.f, ci = 0.f, ai = 0.f;
-    int64_t gi = 0;
-    int row0 = 0, row1 = 0, lo = 1, hi = 0;  // (no row: an empty interval)
-    if (lane.active) {
-        const float *xp = xs + (int64_t)lane.ti * kLjValues;
-        qi = xp[0];
-        ci = xp[1];
-        ai = xp[2];
-        gi = index[lane.ti];
-        if (gi >= 0 && gi < ex.n) {
-            row0 = max(ex.row_start[gi], 0);
-            row1 = min(ex.row_start[gi + 1], ex.entries);
-            if (row0 < row1) {
-                lo = ex.col[row0];
-                hi = ex.col[row1 - 1];
-            }
-        }
-    }
-    float acc[kLjSums];
-#pragma unroll
-    for (int e = 0; e < kLjSums; ++e) acc[e] = 0.f;
-    const StageLjIndexed stage = {s_x, xs, index};
-    walk(start, [&](int first, int last) {
-        sweep_range<2>(first, last, lane, s_pos, pos, 3, stage, [&](int j) {
-            const PairSep d = ewald_image<true>(t, s_pos[j], qc);
-            // the lanes that fail the test sit the expansion out
-            if (!(d.rr > 0.f && d.rr < qc.rc2)) return;
-            const float4 v = *reinterpret_cast<const float4 *>(s_x + j * 4);  // (q_j, c_j, a_j, the index's bits)
-            float qq = qi * v.x, cc = ci * v.y, aj = v.z;
-            const int jg = __float_as_int(v.w);
-            if (jg >= lo && jg <= hi) {
-                const int k = find_in_row(ex.col, row0, row1, jg);
-                if (k >= 0) {
-                    const float sc = 1.f - ex.wc[k], sl = 1.f - ex.wl[k];
-                    if (sc == 0.f && sl == 0.f) return;  // fully excluded: nothing is formed
-                    qq *= sc;
-                    cc *= sl;
-                    aj *= sl;
-                }
-            }
-            const EwaldPairWeight e(d.rr, qc);
-            const DispersionPairWeight w6(d.rr, qd);
-            const float p = (ai * w6.ir6) * (aj * w6.ir6);  // (s^L) a_i a_j / r^12
-            const float s = fmaf(qq, e.mg(qc), fmaf(-cc, w6.mg(), 12.f * p * w6.ir2));
-            const float gx = s * d.dx, gy = s * d.dy, gz = s * d.dz;
-            acc[0] += gx;
-            acc[1] += gy;
-            acc[2] += gz;
-            acc[3] += gx * d.dx;
-            acc[4] += gy * d.dy;
-            acc[5] += gz * d.dz;
-            acc[6] += gy * d.dz;
-            acc[7] += gx * d.dz;
-            acc[8] += gx * d.dy;
-            acc[9] += qq * e.w;
-            acc[10] += fmaf(-cc, w6.w, p);
-        });
-    });
-    if (lane.active) {
-        float *fp = f + gi * 3;
-        fp[0] = acc[0];
-        fp[1] = acc[1];
-        fp[2] = acc[2];
-    }
-    // every pair is seen from both ends: halved, float64 from here on; a lane without a target adds exactly zero
-    double red[kLjTerms];
-    red[0] = lane.active ? 0.5 * (double)acc[9] : 0.0;
-    red[1] = lane.active ? 0.5 * (double)acc[10] : 0.0;
-#pragma unroll
-    for (int e = 0; e < 6; ++e) red[2 + e] = lane.active ? 0.5 * (double)acc[3 + e] : 0.0;
-    const double v = block_sum_f64(red, s_red);
-    const int tid = threadIdx.x;
-    if (tid < kLjTerms) partial[(int64_t)blockIdx.x * kLjTerms + tid] = v;
-}
 
 struct ListParams {
     int blocks;            // workgroups per point set
@@ -288,8 +154,6 @@ __global__ void __launch_bounds__(kListBlock) lj_excl_list_kernel(EwaldPairParam
     if (tid < kLjTerms) partial[(int64_t)blockIdx.x * kLjTerms + tid] = v;
 }
 
-int64_t round256(int64_t bytes) { return (bytes + 255) & ~int64_t(255); }
-
 ExclList excl_list(const nfft_hip_ewald_box_problem *p, int64_t entries, const int *row_start, const int *col, const float *wc,
                    const float *wl)
 {
@@ -305,35 +169,9 @@ int list_blocks(const nfft_hip_ewald_box_problem *p)
 
 }  // namespace
 
-// the masked sweep's workspace is the unmasked one's: the work items, then one partial [8] per item slot
-int64_t ewald_lj_excl_near_workspace(const nfft_hip_ewald_box_problem *p)
-{
-    const int64_t slots = ewald_virial_near_item_slots(p);
-    return round256(slots * (int64_t)sizeof(int2)) + slots * kLjTerms * (int64_t)sizeof(double);
-}
-
 int64_t ewald_lj_excl_list_workspace(const nfft_hip_ewald_box_problem *p)
 {
     return p->batch_size * list_blocks(p) * kLjTerms * (int64_t)sizeof(double);
-}
-
-int launch_ewald_lj_excl_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_entries, const float *pos,
-                              const float *xs, const int *start, const int64_t *index, const int *row_start, const int *col,
-                              const float *weight_coulomb, const float *weight_lj, float *f, double *out, void *workspace,
-                              hipStream_t stream)
-{
-    const EwaldPairParams qc = ewald_pair_params(p->cells[0], p->cells[1], p->cells[2], kLjValues, p->alpha, p->r_cut, p->box);
-    const EwaldPairParams qd = ewald_pair_params(p->cells[0], p->cells[1], p->cells[2], kLjValues, alpha_dispersion, p->r_cut, p->box);
-    const ExclList ex = excl_list(p, num_entries, row_start, col, weight_coulomb, weight_lj);
-    const int64_t cells_per_set = (int64_t)p->cells[0] * p->cells[1] * p->cells[2];
-    const int64_t slots = ewald_virial_near_item_slots(p);
-    int2 *items = (int2 *)workspace;
-    double *partial = ewald_virial_near_partials(p, workspace);
-    if (int rc = launch_nearfield_items(p->batch_size * cells_per_set, p->num_points, start, items, stream)) return rc;
-    hipLaunchKernelGGL(lj_excl_masked_kernel, dim3((unsigned)slots), dim3(kNearBlock), 0, stream, qc, qd, ex, (const int2 *)items, pos,
-                       xs, start, index, f, partial);
-    NFFT_HIP_CHECK(hipGetLastError());
-    return launch_virial_sum_terms(partial, kLjTerms, p->batch_size, 1, 0, items, start, (int)cells_per_set, out, stream);
 }
 
 int launch_ewald_lj_excl_list(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_entries, const float *pos,

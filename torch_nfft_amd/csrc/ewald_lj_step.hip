@@ -7,14 +7,12 @@
 // spectrum, where the Coulomb step, the dispersion sweep and the dispersion virial walk the pairs three times and read the
 // spectrum twice.  The repulsion is plainly truncated at r_c and has no spectral part.
 //
-// lj_step_near_kernel      ewald_step_near_kernel's items, lanes, LDS tiles, 27-cell walk, image and test 0 < rr < rc2; the
-//                          streamed values of a point are (q_j, c_j, a_j) packed as xs [n, 3] and staged by StageColumns<4>
-//                          with its zero pad.  Per passing pair: EwaldPairWeight at alpha_C, DispersionPairWeight at alpha_D
-//                          and, from the reciprocal that the latter forms, p = (a_i r^-6) (a_j r^-6) = a_i a_j / r^12; then
-//                          s = q_i q_j mg_C - c_i c_j mg_D + 12 p / r^2 and eleven float32 sums: s d_a (the force), s d_a d_b
-//                          (xx, yy, zz, yz, xz, xy), q_i q_j w_C and p - c_i c_j w_D.  A lane with a target stores its force
-//                          through `index`; the other eight sums are halved and summed in float64 over the workgroup: one
-//                          partial [8] per item slot, in the order U_C, U_LJ, xx, yy, zz, yz, xz, xy.
+// The pair walk is step_near_kernel of step_frame.h with the PRODUCT LAW below, u = a_i a_j / r^12: the streamed values of a
+// point are (q_j, c_j, a_j) packed as xs [n, 3].  Without a list they are staged by StageColumns<4> with its zero pad and no
+// index is read per staged point; with one (the list kernel is in ewald_lj_excl.hip) StageLjIndexed puts
+// the streamed point's caller-order index, as integer bits, in the pad's place.  From the reciprocal that the dispersion
+// weight forms, p = (a_i r^-6) (a_j r^-6) = a_i a_j / r^12 and the slope is 12 p / r^2; s^L scales a_j.
+//
 // lj_step_spectral_kernel  ewald_step_spectral_kernel's thread-to-cell mapping and carried index digits on band [B, N, N, N, 2]
 //                          = the adjoint transform of (q, c): writes the six spectra i tau_a b^C S^q and i tau_a b^D S^c
 //                          (zeros where the table is zero) and sums, in float64, 1/2 b^C |S^q|^2, -1/2 b^D |S^c|^2 and the
@@ -27,86 +25,55 @@
 //
 // The second level of both is launch_virial_sum_terms of ewald_virial.hip with eight terms.  No atomics anywhere and every
 // order of addition is fixed by the launch geometry: two calls give the same bits.
-#include "pair_frame.h"
+#include "step_frame.h"
 
 namespace nfft {
 
 namespace {
 
-constexpr int kLjTerms = 8;        // U_C, U_LJ, xx, yy, zz, yz, xz, xy
-constexpr int kLjSums = 11;        // s d_x, d_y, d_z; s d_a d_b in the order of the virial's terms; the two energies
-constexpr int kLjValues = 3;       // q, c, a
+constexpr int kLjTerms = kStepTerms;
 constexpr int kVirialBlock = 256;  // lanes of the spectral kernel (and of the second level in ewald_virial.hip)
 
-// qc: the block of the Coulomb weights (alpha_C) and of the walk and the image; qd: that of the dispersion weights (alpha_D)
-template <bool BOX>
-__global__ void __launch_bounds__(kNearBlock) lj_step_near_kernel(EwaldPairParams qc, EwaldPairParams qd,
-                                                                  const int2 *__restrict__ items, const float *__restrict__ pos,
-                                                                  const float *__restrict__ xs, const int *__restrict__ start,
-                                                                  const int64_t *__restrict__ index, float *__restrict__ f,
-                                                                  double *__restrict__ partial)
-{
-    __shared__ float4 s_pos[kNearTile];
-    __shared__ __attribute__((aligned(16))) float s_x[kNearTile * 4];
-    __shared__ double s_red[kNearBlock / 64][kLjTerms];
-    const int2 item = items[blockIdx.x];
-    if (item.x < 0) return;  // (uniform: an empty slot; the second level skips it)
-    const PairLane lane = pair_lane(item, start);
-    const WrappedWalk walk(lane.cell, qc.G0, BOX ? qc.G1 : qc.G0, BOX ? qc.G2 : qc.G0);
-    // (a lane without a target sums pairs of the origin with zero parameters; it stores nothing)
-    const float4 t = lane_position(lane, pos, 3, 0.f);
-    float qi = 0.f, ci = 0.f, ai = 0.f;
-    if (lane.active) {
-        const float *xp = xs + (int64_t)lane.ti * kLjValues;
-        qi = xp[0];
-        ci = xp[1];
-        ai = xp[2];
+// staging policy: (q_j, c_j, a_j) of xs [n, 3] and the caller-order index of the streamed point as integer bits
+struct StageLjIndexed {
+    float *s_x;
+    const float *__restrict__ xs;
+    const int64_t *__restrict__ index;
+    __device__ __forceinline__ void point(int j, int64_t i) const
+    {
+        const float *xp = xs + i * 3;
+        s_x[j * 4 + 0] = xp[0];
+        s_x[j * 4 + 1] = xp[1];
+        s_x[j * 4 + 2] = xp[2];
+        s_x[j * 4 + 3] = __int_as_float((int)index[i]);
     }
-    float acc[kLjSums];
-#pragma unroll
-    for (int e = 0; e < kLjSums; ++e) acc[e] = 0.f;
-    const StageColumns<4> stage = {s_x, xs, kLjValues, 0};
-    walk(start, [&](int first, int last) {
-        sweep_range<2>(first, last, lane, s_pos, pos, 3, stage, [&](int j) {
-            const PairSep d = ewald_image<BOX>(t, s_pos[j], qc);
-            // the lanes that fail the test sit the expansion out
-            if (!(d.rr > 0.f && d.rr < qc.rc2)) return;
-            const float4 v = *reinterpret_cast<const float4 *>(s_x + j * 4);  // (q_j, c_j, a_j, 0)
-            const EwaldPairWeight e(d.rr, qc);
-            const DispersionPairWeight w6(d.rr, qd);
-            const float qq = qi * v.x, cc = ci * v.y;
-            const float p = (ai * w6.ir6) * (v.z * w6.ir6);  // a_i a_j / r^12
-            const float s = fmaf(qq, e.mg(qc), fmaf(-cc, w6.mg(), 12.f * p * w6.ir2));
-            const float gx = s * d.dx, gy = s * d.dy, gz = s * d.dz;
-            acc[0] += gx;
-            acc[1] += gy;
-            acc[2] += gz;
-            acc[3] += gx * d.dx;
-            acc[4] += gy * d.dy;
-            acc[5] += gz * d.dz;
-            acc[6] += gy * d.dz;
-            acc[7] += gx * d.dz;
-            acc[8] += gx * d.dy;
-            acc[9] += qq * e.w;
-            acc[10] += fmaf(-cc, w6.w, p);
-        });
-    });
-    if (lane.active) {
-        float *fp = f + index[lane.ti] * 3;
-        fp[0] = acc[0];
-        fp[1] = acc[1];
-        fp[2] = acc[2];
+};
+
+// the product law (step_frame.h has what a law is): C12_ij = a_i a_j, no table and no block
+struct LjProductLaw {
+    static constexpr int kValues = 3;  // q, c, a
+    struct Params {};
+    typedef float Own;  // a_i
+    struct Coef {
+        float ai, aj;
+        __device__ __forceinline__ void scale(float sl) { aj *= sl; }
+        __device__ __forceinline__ void terms(const EwaldPairWeight &, const DispersionPairWeight &w6, float &slope, float &u) const
+        {
+            const float p = (ai * w6.ir6) * (aj * w6.ir6);  // (s^L) a_i a_j / r^12
+            slope = 12.f * p * w6.ir2;
+            u = p;
+        }
+    };
+    __device__ __forceinline__ LjProductLaw(const Params &) {}
+    template <bool MASKED>
+    __device__ __forceinline__ auto stage(float *s_x, const float *xs, const int64_t *index) const
+    {
+        if constexpr (MASKED) return StageLjIndexed{s_x, xs, index};
+        else return StageColumns<4>{s_x, xs, kValues, 0};
     }
-    // every pair is seen from both ends: halved, float64 from here on; a lane without a target adds exactly zero
-    double red[kLjTerms];
-    red[0] = lane.active ? 0.5 * (double)acc[9] : 0.0;
-    red[1] = lane.active ? 0.5 * (double)acc[10] : 0.0;
-#pragma unroll
-    for (int e = 0; e < 6; ++e) red[2 + e] = lane.active ? 0.5 * (double)acc[3 + e] : 0.0;
-    const double v = block_sum_f64(red, s_red);
-    const int tid = threadIdx.x;
-    if (tid < kLjTerms) partial[(int64_t)blockIdx.x * kLjTerms + tid] = v;
-}
+    __device__ __forceinline__ Own own(const float *xp, int) const { return xp[2]; }
+    __device__ __forceinline__ Coef coef(Own ai, const float4 &v) const { return {ai, v.z}; }
+};
 
 struct LjSpectralParams {
     int N, blocks;  // frequencies per axis; workgroups per point set
@@ -225,16 +192,14 @@ __global__ void __launch_bounds__(kVirialBlock) lj_step_spectral_kernel(LjSpectr
     if (tid < kLjTerms) partial[(int64_t)blockIdx.x * kLjTerms + tid] = 0.5 * v;
 }
 
-int64_t round256(int64_t bytes) { return (bytes + 255) & ~int64_t(255); }
-
 }  // namespace
 
-// the near workspace: the work items, then (256-byte aligned, where ewald_virial_near_partials points) one partial [8] per
-// item slot
-int64_t ewald_lj_step_near_workspace(const nfft_hip_ewald_box_problem *p)
+// the workspace of every step walk: the work items, then (256-byte aligned, where ewald_virial_near_partials points) one
+// partial [8] per item slot
+int64_t ewald_step8_near_workspace(const nfft_hip_ewald_box_problem *p)
 {
     const int64_t slots = ewald_virial_near_item_slots(p);
-    return round256(slots * (int64_t)sizeof(int2)) + slots * kLjTerms * (int64_t)sizeof(double);
+    return round256(slots * (int64_t)sizeof(int2)) + slots * kStepTerms * (int64_t)sizeof(double);
 }
 
 int64_t ewald_lj_step_spectral_workspace(int64_t N, int64_t batch_size)
@@ -242,21 +207,14 @@ int64_t ewald_lj_step_spectral_workspace(int64_t N, int64_t batch_size)
     return batch_size * ewald_virial_far_blocks(N) * kLjTerms * (int64_t)sizeof(double);
 }
 
-// (the unit cube runs as the identity box, as the Coulomb step does: one instantiation)
-int launch_ewald_lj_step_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, const float *pos, const float *xs,
-                              const int *start, const int64_t *index, float *f, double *out, void *workspace, hipStream_t stream)
+// (the unit cube runs as the identity box, as the Coulomb step does; no types and no table)
+int launch_ewald_lj_step_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t, int64_t num_entries,
+                              const float *pos, const float *xs, const int *, const float *, const int *start, const int64_t *index,
+                              const int *row_start, const int *col, const float *weight_coulomb, const float *weight_lj, float *f,
+                              double *out, void *workspace, hipStream_t stream)
 {
-    const EwaldPairParams qc = ewald_pair_params(p->cells[0], p->cells[1], p->cells[2], kLjValues, p->alpha, p->r_cut, p->box);
-    const EwaldPairParams qd = ewald_pair_params(p->cells[0], p->cells[1], p->cells[2], kLjValues, alpha_dispersion, p->r_cut, p->box);
-    const int64_t cells_per_set = (int64_t)p->cells[0] * p->cells[1] * p->cells[2];
-    const int64_t slots = ewald_virial_near_item_slots(p);
-    int2 *items = (int2 *)workspace;
-    double *partial = ewald_virial_near_partials(p, workspace);
-    if (int rc = launch_nearfield_items(p->batch_size * cells_per_set, p->num_points, start, items, stream)) return rc;
-    hipLaunchKernelGGL((lj_step_near_kernel<true>), dim3((unsigned)slots), dim3(kNearBlock), 0, stream, qc, qd, (const int2 *)items,
-                       pos, xs, start, index, f, partial);
-    NFFT_HIP_CHECK(hipGetLastError());
-    return launch_virial_sum_terms(partial, kLjTerms, p->batch_size, 1, 0, items, start, (int)cells_per_set, out, stream);
+    return launch_step_near<LjProductLaw>(p, alpha_dispersion, {}, 0, num_entries, pos, xs, start, index, row_start, col,
+                                          weight_coulomb, weight_lj, f, out, workspace, stream);
 }
 
 int launch_ewald_lj_step_spectral(int64_t N, int64_t batch_size, const void *band, const float *coeffs_coulomb,

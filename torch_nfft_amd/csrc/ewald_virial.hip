@@ -26,6 +26,7 @@
 // 7k) through launch_virial_sum, ewald_virial_near_item_slots / _partials and ewald_virial_far_blocks.
 //
 // No atomics anywhere and every order of addition is fixed by the launch geometry: two calls give the same bits.
+#include "host_util.h"
 #include "pair_frame.h"
 
 namespace nfft {
@@ -247,8 +248,6 @@ int virial_far_blocks(int64_t N)
     const int64_t cells = N * N * N;
     return (int)std::min<int64_t>((cells + kVirialBlock - 1) / kVirialBlock, kVirialFarBlocks);
 }
-
-int64_t round256(int64_t bytes) { return (bytes + 255) & ~int64_t(255); }
 
 }  // namespace
 

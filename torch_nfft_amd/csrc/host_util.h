@@ -4,6 +4,9 @@
 
 namespace nfft {
 
+// where a workspace's next block begins: blocks inside an aligned workspace sit on 256-byte boundaries
+inline int64_t round256(int64_t bytes) { return (bytes + 255) & ~int64_t(255); }
+
 // Offsets of a workspace's blocks, each on a 256-byte boundary.  The entry points align the caller's pointer up to 256
 // themselves (workspace_base), which may skip up to 255 bytes: total() is the aligned end + 256 bytes of slack for that.
 // Carve(end) continues an earlier carve from its end().

@@ -247,46 +247,30 @@ int launch_virial_sum(const double *partial, int64_t batch_size, int64_t C, int 
 // (the same level over `partial` [rows, terms, C] for any number of terms: out [batch_size, terms, C])
 int launch_virial_sum_terms(const double *partial, int terms, int64_t batch_size, int64_t C, int rows_per_set, const void *items,
                             const int *start, int cells_per_set, double *out, hipStream_t stream);
-// ewald_lj_step.hip (forces, energies and virial of a Lennard-Jones + Coulomb model in one pair walk and one spectral pass,
-// DESIGN.md section 7r): arguments as nfft_hip_ewald_lj_step_near / _spectral; `workspace`: ewald_lj_step_near_workspace(p)
-// bytes, 256-byte aligned (the work items, then one partial [8] per item slot), and ewald_lj_step_spectral_workspace(N, B)
-// bytes, 8-byte aligned
-int64_t ewald_lj_step_near_workspace(const nfft_hip_ewald_box_problem *p);
+// The step walks (step_frame.h): one pair walk per pair law, all with one argument list -- that of
+// nfft_hip_ewald_lj_table_near, row_start == nullptr for the unmasked walk; the product law reads no types and no table --
+// and one workspace: ewald_step8_near_workspace(p) bytes, 256-byte aligned (the work items, then one partial [8] per item
+// slot).  ewald_lj_step.hip: the product law a_i a_j / r^12 (sections 7r, 7s); ewald_lj_table.hip: the (C12, dC6) table
+// (section 7t); ewald_bmh_table.hip: the (A, B, dC6, C8) table of Buckingham / Born-Mayer-Huggins (section 7u)
+typedef int step_near_launch(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_types, int64_t num_entries,
+                             const float *pos, const float *xs, const int *types, const float *table, const int *start,
+                             const int64_t *index, const int *row_start, const int *col, const float *weight_coulomb,
+                             const float *weight_lj, float *f, double *out, void *workspace, hipStream_t stream);
+int64_t ewald_step8_near_workspace(const nfft_hip_ewald_box_problem *p);
+step_near_launch launch_ewald_lj_step_near, launch_ewald_lj_table_near, launch_ewald_bmh_table_near;
+// ewald_lj_step.hip also has the spectral pass of these steps, arguments as nfft_hip_ewald_lj_step_spectral; `workspace`:
+// ewald_lj_step_spectral_workspace(N, B) bytes, 8-byte aligned
 int64_t ewald_lj_step_spectral_workspace(int64_t N, int64_t batch_size);
-int launch_ewald_lj_step_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, const float *pos, const float *xs,
-                              const int *start, const int64_t *index, float *f, double *out, void *workspace, hipStream_t stream);
 int launch_ewald_lj_step_spectral(int64_t N, int64_t batch_size, const void *band, const float *coeffs_coulomb,
                                   const float *coeffs_dispersion, const float *strain_dispersion, const double *box_inverse,
                                   double pi2_over_alpha2, void *spectra, double *out, void *workspace, hipStream_t stream);
-// ewald_lj_excl.hip (bonded-pair exclusions of the Lennard-Jones + Coulomb step): the masked pair walk
-// and the list kernel, arguments as nfft_hip_ewald_lj_excl_near / _list; `workspace`: ewald_lj_excl_near_workspace(p) bytes,
-// 256-byte aligned (as ewald_lj_step_near_workspace), and ewald_lj_excl_list_workspace(p) bytes, 8-byte aligned
-int64_t ewald_lj_excl_near_workspace(const nfft_hip_ewald_box_problem *p);
+// ewald_lj_excl.hip (bonded-pair exclusions of these steps): the list kernel, arguments as
+// nfft_hip_ewald_lj_excl_list; `workspace`: ewald_lj_excl_list_workspace(p) bytes, 8-byte aligned
 int64_t ewald_lj_excl_list_workspace(const nfft_hip_ewald_box_problem *p);
-int launch_ewald_lj_excl_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_entries, const float *pos,
-                              const float *xs, const int *start, const int64_t *index, const int *row_start, const int *col,
-                              const float *weight_coulomb, const float *weight_lj, float *f, double *out, void *workspace,
-                              hipStream_t stream);
 int launch_ewald_lj_excl_list(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_entries, const float *pos,
                               const float *xs, const int *row_start, const int *col, const float *weight_coulomb,
                               const float *weight_lj, const int *set_start, float *f, double *out, void *workspace,
                               hipStream_t stream);
-// ewald_lj_table.hip (the pair walk of the Lennard-Jones + Coulomb step with a type-pair table):
-// arguments as nfft_hip_ewald_lj_table_near, row_start == nullptr for the unmasked walk; `workspace`:
-// ewald_lj_table_near_workspace(p) bytes, 256-byte aligned (as ewald_lj_step_near_workspace)
-int64_t ewald_lj_table_near_workspace(const nfft_hip_ewald_box_problem *p);
-int launch_ewald_lj_table_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_types, int64_t num_entries,
-                               const float *pos, const float *xs, const int *types, const float *table, const int *start,
-                               const int64_t *index, const int *row_start, const int *col, const float *weight_coulomb,
-                               const float *weight_lj, float *f, double *out, void *workspace, hipStream_t stream);
-// ewald_bmh_table.hip (the pair walk of the Buckingham / Born-Mayer-Huggins + Coulomb step with a type-pair table, DESIGN.md
-// section 7u): arguments as nfft_hip_ewald_bmh_table_near, row_start == nullptr for the unmasked walk; `workspace`:
-// ewald_bmh_table_near_workspace(p) bytes, 256-byte aligned (as ewald_lj_step_near_workspace)
-int64_t ewald_bmh_table_near_workspace(const nfft_hip_ewald_box_problem *p);
-int launch_ewald_bmh_table_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, int64_t num_types, int64_t num_entries,
-                                const float *pos, const float *xs, const int *types, const float *table, const int *start,
-                                const int64_t *index, const int *row_start, const int *col, const float *weight_coulomb,
-                                const float *weight_lj, float *f, double *out, void *workspace, hipStream_t stream);
 // ewald_step.hip (potential, field, energy and virial of the Ewald sum in one pair walk and one spectral pass, DESIGN.md
 // section 7q): arguments as nfft_hip_ewald_step_near / _spectral, the workspaces those of ewald_virial.hip
 // (ewald_virial_near_workspace, ewald_virial_far_workspace), the second level its launch_virial_sum

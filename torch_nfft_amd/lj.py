@@ -73,6 +73,26 @@ def _check_values(what, values, pos):
     return out
 
 
+def _step_tail(far_force, far8, f, near8, listed, q, c, alpha_c, alpha_d, coulomb, batch):
+    """``(F, U_coulomb, U_sr, W)`` of a step from its parts: the far field's force and eight sums, the pair walk's ``(f, near8)``,
+    the list step's ``(lf, list8)`` (``None`` without exclusions), then the self and background terms in float64"""
+    if listed is None:
+        F = f + far_force
+    else:
+        F = (f.double() + listed[0].double() + far_force.double()).float()
+        near8 = near8 + listed[1]
+    eight = far8 + near8  # [B, 8] float64
+    q64, c64 = q.double(), c.double()
+    total = _set_sums(q64, batch)[0]
+    background = (math.pi / (2.0 * alpha_c * alpha_c * coulomb.volume)) * total * total
+    U_coulomb = eight[:, 0] - (alpha_c / math.sqrt(math.pi)) * _set_sums(q64 * q64, batch)[0] - background
+    U_sr = eight[:, 1] + (alpha_d ** 6 / 12.0) * _set_sums(c64 * c64, batch)[0]
+    W = _voigt_to_matrix(eight[:, 2:])
+    for e in range(3):
+        W[:, e, e] -= background
+    return F, U_coulomb.float(), U_sr.float(), W.float()
+
+
 def nfft_ewald_lj_step(q, c, a, pos, batch=None, /, coulomb=None, dispersion=None, cutoff=4, fractional=False):
     """``(F, U_coulomb, U_lj, W)``: what one molecular-dynamics step needs from the nonbonded part of a Lennard-Jones +
     Coulomb model, in one pass.
@@ -304,29 +324,17 @@ def nfft_ewald_lj_table_step(q, table, pos, batch=None, /, coulomb=None, dispers
         spectra, far8 = ops.nfft_ewald_lj_step_spectral(band, coulomb.coeffs, dispersion.coeffs, dispersion.strain_coeffs(), box6,
                                                         alpha_c)
         far = nfft_forward(spectra, pos, batch, cutoff=int(cutoff), real_output=True)  # [n, 6]: E, then G
+        far_force = q.unsqueeze(1) * far[:, :3] - c.unsqueeze(1) * far[:, 3:]
         xs = torch.stack([q, c], 1)
         walk = (box6, alpha_c, alpha_d, coulomb.r_cut)
-        if ex is None:
-            f, near8 = ops.nfft_ewald_lj_table_near(pos, xs, table.types, table.table, batch, None, None, None, None, *walk)
-            F = f + q.unsqueeze(1) * far[:, :3] - c.unsqueeze(1) * far[:, 3:]
-        else:
+        lists, listed = (None, None, None, None), None
+        if ex is not None:
             # the listed pairs come scaled out of the walk; the list step of 7s takes the smooth share of q_i q_j and c_i c_j
             # back out of the far field, which holds nothing of C12 and dC6
             lists = (ex.row_start, ex.col, ex.coulomb_weight, ex.dispersion_weight)
-            f, near8 = ops.nfft_ewald_lj_table_near(pos, xs, table.types, table.table, batch, *lists, *walk)
-            lf, list8 = ops.nfft_ewald_lj_excl_list(pos, torch.stack([q, c, torch.zeros_like(q)], 1), batch, *lists, *walk)
-            F = (f.double() + lf.double() + (q.unsqueeze(1) * far[:, :3] - c.unsqueeze(1) * far[:, 3:]).double()).float()
-            near8 = near8 + list8
-        eight = far8 + near8  # [B, 8] float64
-        q64, c64 = q.double(), c.double()
-        total = _set_sums(q64, batch)[0]
-        background = (math.pi / (2.0 * alpha_c * alpha_c * coulomb.volume)) * total * total
-        U_coulomb = eight[:, 0] - (alpha_c / math.sqrt(math.pi)) * _set_sums(q64 * q64, batch)[0] - background
-        U_lj = eight[:, 1] + (alpha_d ** 6 / 12.0) * _set_sums(c64 * c64, batch)[0]
-        W = _voigt_to_matrix(eight[:, 2:])
-        for e in range(3):
-            W[:, e, e] -= background
-        return F, U_coulomb.float(), U_lj.float(), W.float()
+            listed = ops.nfft_ewald_lj_excl_list(pos, torch.stack([q, c, torch.zeros_like(q)], 1), batch, *lists, *walk)
+        f, near8 = ops.nfft_ewald_lj_table_near(pos, xs, table.types, table.table, batch, *lists, *walk)
+        return _step_tail(far_force, far8, f, near8, listed, q, c, alpha_c, alpha_d, coulomb, batch)
 
 
 def _lj_step(what, q, c, a, pos, batch, coulomb, dispersion, exclusions, cutoff, fractional):
@@ -346,24 +354,15 @@ def _lj_step(what, q, c, a, pos, batch, coulomb, dispersion, exclusions, cutoff,
         spectra, far8 = ops.nfft_ewald_lj_step_spectral(band, coulomb.coeffs, dispersion.coeffs, dispersion.strain_coeffs(), box6,
                                                         alpha_c)
         far = nfft_forward(spectra, pos, batch, cutoff=int(cutoff), real_output=True)  # [n, 6]: E, then G
+        far_force = q.unsqueeze(1) * far[:, :3] - c.unsqueeze(1) * far[:, 3:]
         xs = torch.stack([q, c, a], 1)
+        walk = (box6, alpha_c, alpha_d, coulomb.r_cut)
         if ex is None:
-            f, near8 = ops.nfft_ewald_lj_step_near(pos, xs, batch, box6, alpha_c, alpha_d, coulomb.r_cut)
-            F = f + q.unsqueeze(1) * far[:, :3] - c.unsqueeze(1) * far[:, 3:]
+            f, near8 = ops.nfft_ewald_lj_step_near(pos, xs, batch, *walk)
+            listed = None
         else:
             # the listed pairs come scaled out of the walk; the list step takes their smooth share back out of the far field
             lists = (ex.row_start, ex.col, ex.coulomb_weight, ex.dispersion_weight)
-            f, near8 = ops.nfft_ewald_lj_excl_near(pos, xs, batch, *lists, box6, alpha_c, alpha_d, coulomb.r_cut)
-            lf, list8 = ops.nfft_ewald_lj_excl_list(pos, xs, batch, *lists, box6, alpha_c, alpha_d, coulomb.r_cut)
-            F = (f.double() + lf.double() + (q.unsqueeze(1) * far[:, :3] - c.unsqueeze(1) * far[:, 3:]).double()).float()
-            near8 = near8 + list8
-        eight = far8 + near8  # [B, 8] float64
-        q64, c64 = q.double(), c.double()
-        total = _set_sums(q64, batch)[0]
-        background = (math.pi / (2.0 * alpha_c * alpha_c * coulomb.volume)) * total * total
-        U_coulomb = eight[:, 0] - (alpha_c / math.sqrt(math.pi)) * _set_sums(q64 * q64, batch)[0] - background
-        U_lj = eight[:, 1] + (alpha_d ** 6 / 12.0) * _set_sums(c64 * c64, batch)[0]
-        W = _voigt_to_matrix(eight[:, 2:])
-        for e in range(3):
-            W[:, e, e] -= background
-        return F, U_coulomb.float(), U_lj.float(), W.float()
+            f, near8 = ops.nfft_ewald_lj_excl_near(pos, xs, batch, *lists, *walk)
+            listed = ops.nfft_ewald_lj_excl_list(pos, xs, batch, *lists, *walk)
+        return _step_tail(far_force, far8, f, near8, listed, q, c, alpha_c, alpha_d, coulomb, batch)
