@@ -41,7 +41,7 @@ def report(label, *tensors):
     for t in tensors:
         a = t.detach().cpu().contiguous().numpy()
         h.update(a.tobytes())
-        mass += float(np.abs(a.astype(np.float64)).sum())
+        mass += float(np.abs(a).astype(np.float64).sum())  # (a complex entry by its modulus)
     assert np.isfinite(mass) and mass > 0.0, label  # (a sum of nothing would compare equal too)
     print("%-58s %s  |sum| %.6e" % (label, h.hexdigest(), mass), flush=True)
 
@@ -210,6 +210,62 @@ def step_cases():
     ops.check_status()
 
 
+def band_at(rng, shape, offset):
+    """a seeded complex64 band of `shape` that starts `offset` (0 or 8) bytes past a 16-byte boundary of its storage"""
+    flat = rng.standard_normal((int(np.prod(shape)) + 1, 2)).astype(np.float32)
+    band = torch.view_as_complex(cuda(flat))[offset // 8:][:int(np.prod(shape))].view(shape)
+    assert band.is_contiguous() and band.data_ptr() % 16 == offset
+    return band
+
+
+def reduction_cases():
+    """the reductions on virial_frame.h and the spectral kernels on spectral_frame.h (DESIGN.md section 7w;
+    profiles/r21_reduction_frames.md): the pair reductions on the layout of ewald_cases() at every CC, its tail and a second
+    column pass; the strided sweeps at one cell per thread at most (N = 12) and at several with both carries (N = 72), the
+    one-thread-per-element kernels at N = 12 and 16; bands on and 8 bytes off a 16-byte boundary"""
+    boxes = (("ortho", [1.0, 0.0, 1.4, 0.0, 0.0, 2.0], 0.3), ("tilted", [1.0, 0.2, 1.1, 0.1, -0.3, 1.3], 0.3),
+             ("unit", [1.0, 0.0, 1.0, 0.0, 0.0, 1.0], 1.0 / 3.0))
+    rng = np.random.default_rng(7)
+    pos, batch = torus_sets(rng, (1500, 40), 400)
+    pd, bd = cuda(pos), cuda(batch)
+    charges = {cols: cuda(rng.standard_normal((len(pos), cols)).astype(np.float32)) for cols in (1, 2, 3, 5)}
+    alpha = 10.0
+    for name, box, r_c in boxes:
+        for cols in (1, 2, 3, 5):
+            label = "%s r_c %.3f Cr %d" % (name, r_c, cols)
+            walk = (pd, charges[cols], bd, box, alpha, r_c)
+            report("disp virial near " + label, ops.nfft_ewald_dispersion_virial_near(*walk))
+            report("yukawa virial near " + label, ops.nfft_ewald_yukawa_virial_near(*walk, 1.0 / r_c))
+            report("step near " + label, *ops.nfft_ewald_step_near(*walk))
+    ops.check_status()
+    tilted3 = np.array([[1.0, 0.0, 0.0], [0.2, 1.1, 0.0], [0.1, -0.3, 1.3]])
+    for N in (12, 72):
+        sc = tn.EwaldSplitting(alpha, 0.3, N, box=tilted3)
+        sd = tn.DispersionSplitting(11.5, 0.3, N, box=tilted3)
+        strain = sd.strain_coeffs()
+        for cols, offset in ((1, 0), (2, 0), (4, 0), (3, 0), (5, 0), (1, 8), (2, 8), (4, 8)):
+            band = band_at(rng, (2, N, N, N, cols), offset)
+            label = "N %d C %d band +%d" % (N, cols, offset)
+            if offset:  # (ewald_cases() has the aligned bands of this one)
+                report("virial far " + label, ops.nfft_ewald_virial_far(band, sc.coeffs, sc.box6, alpha))
+            report("disp virial far " + label, ops.nfft_ewald_dispersion_virial_far(band, sd.coeffs, strain, sd.box6))
+            report("step spectral " + label, *ops.nfft_ewald_step_spectral(band, sc.coeffs, sc.box6, alpha))
+        for offset in (0, 8):
+            band = band_at(rng, (2, N, N, N, 2), offset)
+            report("lj step spectral N %d band +%d" % (N, offset),
+                   *ops.nfft_ewald_lj_step_spectral(band, sc.coeffs, sd.coeffs, strain, sc.box6, alpha))
+    for N in (12, 16):
+        sc = tn.EwaldSplitting(alpha, 0.3, N, box=tilted3)
+        for order in (1, 2):
+            for cols in (1, 2, 4, 3):
+                label = "N %d C %d order %d" % (N, cols, order)
+                report("dipole spectral " + label,
+                       ops.nfft_ewald_dipole_spectral(band_at(rng, (2, N, N, N, 4, cols), 0), sc.coeffs, sc.box6, order))
+                report("stokeslet spectral " + label,
+                       ops.nfft_ewald_stokeslet_spectral(band_at(rng, (2, N, N, N, 3, cols), 0), sc.stokeslet_coeffs, sc.box6, order))
+    ops.check_status()
+
+
 if __name__ == "__main__":
     print("library:", os.environ.get("NFFT_HIP_LIB", "the package's own"), file=sys.stderr)
     with open("/proc/self/maps") as maps:  # (what the process really runs: one libnfft_hip, under the one core.so)
@@ -217,3 +273,4 @@ if __name__ == "__main__":
     near_field_cases()
     ewald_cases()
     step_cases()
+    reduction_cases()

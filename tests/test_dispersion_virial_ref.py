@@ -282,11 +282,12 @@ def test_kernel_resource_usage():
     usage = resource_usage("ewald_disp_virial.hip")
     seen = set()
     for name, u in sorted(usage.items()):
-        m = re.search(r"(ewald_disp_virial_near_kernel|ewald_disp_virial_far_kernel)ILi(\d)EE", name)
+        # (the frames' kernels with this file's policies)
+        m = re.search(r"(virial_near_kernel)ILi(\d)E\w*?DispersionVirialWeightE|(virial_far_kernel)ILi(\d)E\w*?TableStrainE", name)
         assert m, name  # (nothing else in that file)
-        key = (m.group(1), int(m.group(2)))
+        key = (m.group(1) or m.group(3), int(m.group(2) or m.group(4)))
         seen.add(key)
         print(key, "VGPRs %d AGPRs %d occupancy %d LDS %d" % (u["VGPRs"], u.get("AGPRs", 0), u["Occupancy"], u["LDS Size"]))
         assert u["ScratchSize"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (key, u)
-    assert seen == {(k, cc) for k in ("ewald_disp_virial_near_kernel", "ewald_disp_virial_far_kernel") for cc in (1, 2, 4)}
+    assert seen == {(k, cc) for k in ("virial_near_kernel", "virial_far_kernel") for cc in (1, 2, 4)}
     assert len(usage) == 6

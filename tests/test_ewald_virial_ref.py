@@ -315,11 +315,12 @@ def test_kernel_resource_usage():
     usage = resource_usage("ewald_virial.hip")
     seen = set()
     for name, u in sorted(usage.items()):
-        m = re.search(r"(ewald_virial_near_kernel|ewald_virial_far_kernel)ILi(\d)E|(virial_sum_kernel)", name)
+        # (the frames' kernels with this file's policies)
+        m = re.search(r"(virial_near_kernel)ILi(\d)E\w*?CoulombVirialWeightE|(virial_far_kernel)ILi(\d)E\w*?CoulombStrainE|(virial_sum_kernel)", name)
         if not m:
             continue
-        key = (m.group(1) or m.group(3), int(m.group(2) or 0))
+        key = (m.group(1) or m.group(3) or m.group(5), int(m.group(2) or m.group(4) or 0))
         seen.add(key)
         print(key, "VGPRs %d AGPRs %d occupancy %d LDS %d" % (u["VGPRs"], u.get("AGPRs", 0), u["Occupancy"], u["LDS Size"]))
         assert u["ScratchSize"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (key, u)
-    assert seen == {(k, cc) for k in ("ewald_virial_near_kernel", "ewald_virial_far_kernel") for cc in (1, 2, 4)} | {("virial_sum_kernel", 0)}
+    assert seen == {(k, cc) for k in ("virial_near_kernel", "virial_far_kernel") for cc in (1, 2, 4)} | {("virial_sum_kernel", 0)}

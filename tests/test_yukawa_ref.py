@@ -417,7 +417,7 @@ def test_pair_kernel_resource_usage():
     sweep, red = {}, {}
     for name, u in usage.items():
         m = re.search(r"ewald_yukawa_near_kernelILi(\d)ELb(\d)ELb(\d)EE", name)
-        v = re.search(r"ewald_yukawa_virial_near_kernelILi(\d)EE", name)
+        v = re.search(r"virial_near_kernelILi(\d)E\w*?YukawaVirialWeightE", name)  # (virial_frame.h)
         assert m or v, name  # (nothing else in that file)
         if m:
             sweep[(int(m.group(1)), int(m.group(2)), int(m.group(3)))] = u
@@ -430,7 +430,7 @@ def test_pair_kernel_resource_usage():
         m = re.search(r"ewald_disp_near_kernelILi(\d)ELb(\d)ELb(\d)EE", name)
         twin_sweep[(int(m.group(1)), int(m.group(2)), int(m.group(3)))] = u
     for name, u in resource_usage("ewald_disp_virial.hip").items():
-        v = re.search(r"ewald_disp_virial_near_kernelILi(\d)EE", name)
+        v = re.search(r"virial_near_kernelILi(\d)E\w*?DispersionVirialWeightE", name)
         if v:
             twin_red[int(v.group(1))] = u
     for kind, by, twin in (("sweep", sweep, twin_sweep), ("virial", red, twin_red)):

@@ -636,6 +636,26 @@ int nfft_hip_ewald_virial_near(const nfft_hip_ewald_box_problem *p, const float 
     return virial_near_call(launch_ewald_virial_near, p, points, xr, start, out, workspace, workspace_bytes, stream);
 }
 
+// pi^2 / alpha^2 of the Coulomb sum's spectral reductions
+static int check_pi2_over_alpha2(double pi2_over_alpha2)
+{
+    if (!(pi2_over_alpha2 > 0.0) || !(pi2_over_alpha2 < 1e300)) {
+        set_error("Input mismatch: pi2_over_alpha2 must be positive and finite");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
+// the kernels with one thread per (frequency, column) count them in 32 bits
+static int check_spectral_elements(int64_t N, int64_t num_columns)
+{
+    if (N * N * N * num_columns >= (int64_t(1) << 31)) {
+        set_error("Input mismatch: N^3 num_columns < 2^31 is required");
+        return NFFT_HIP_EINVAL;
+    }
+    return 0;
+}
+
 int64_t nfft_hip_ewald_virial_far_workspace_bytes(int64_t N, int64_t batch_size, int64_t num_columns)
 {
     if (validate_virial_far(N, batch_size, num_columns)) return -1;
@@ -649,10 +669,7 @@ int nfft_hip_ewald_virial_far(int64_t N, int64_t batch_size, int64_t num_columns
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate_virial_far(N, batch_size, num_columns)) return rc;
     if (int rc = validate_box_inverse(box_inverse)) return rc;
-    if (!(pi2_over_alpha2 > 0.0) || !(pi2_over_alpha2 < 1e300)) {
-        set_error("Input mismatch: pi2_over_alpha2 must be positive and finite");
-        return NFFT_HIP_EINVAL;
-    }
+    if (int rc = check_pi2_over_alpha2(pi2_over_alpha2)) return rc;
     if (num_columns == 0) return 0;
     if (!band || !coeffs || !out) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
     char *ws = workspace_base(workspace, workspace_bytes, virial_far_need(N, batch_size, num_columns));
@@ -690,10 +707,7 @@ int nfft_hip_ewald_step_spectral(int64_t N, int64_t batch_size, int64_t num_colu
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate_virial_far(N, batch_size, num_columns)) return rc;
     if (int rc = validate_box_inverse(box_inverse)) return rc;
-    if (!(pi2_over_alpha2 > 0.0) || !(pi2_over_alpha2 < 1e300)) {
-        set_error("Input mismatch: pi2_over_alpha2 must be positive and finite");
-        return NFFT_HIP_EINVAL;
-    }
+    if (int rc = check_pi2_over_alpha2(pi2_over_alpha2)) return rc;
     if (num_columns == 0) return 0;
     if (!band || !coeffs || !spectra || !out7) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
     char *ws = workspace_base(workspace, workspace_bytes, virial_far_need(N, batch_size, num_columns));
@@ -770,10 +784,7 @@ int nfft_hip_ewald_lj_step_spectral(int64_t N, int64_t batch_size, const void *b
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = validate_lj_step_spectral(N, batch_size)) return rc;
     if (int rc = validate_box_inverse(box_inverse)) return rc;
-    if (!(pi2_over_alpha2 > 0.0) || !(pi2_over_alpha2 < 1e300)) {
-        set_error("Input mismatch: pi2_over_alpha2 must be positive and finite");
-        return NFFT_HIP_EINVAL;
-    }
+    if (int rc = check_pi2_over_alpha2(pi2_over_alpha2)) return rc;
     if (!band || !coeffs_coulomb || !coeffs_dispersion || !strain_dispersion || !spectra || !out8) {
         set_error("Input mismatch: null input");
         return NFFT_HIP_EINVAL;
@@ -914,10 +925,7 @@ int nfft_hip_ewald_dipole_spectral(int64_t N, int64_t batch_size, int64_t num_co
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = check_dipole_order(order)) return rc;
     if (int rc = validate_virial_far(N, batch_size, num_columns)) return rc;
-    if (N * N * N * num_columns >= (int64_t(1) << 31)) {
-        set_error("Input mismatch: N^3 num_columns < 2^31 is required");
-        return NFFT_HIP_EINVAL;
-    }
+    if (int rc = check_spectral_elements(N, num_columns)) return rc;
     if (int rc = validate_box_inverse(box_inverse)) return rc;
     if (num_columns == 0) return 0;
     if (!band || !coeffs || !out) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }
@@ -931,10 +939,7 @@ int nfft_hip_ewald_stokeslet_spectral(int64_t N, int64_t batch_size, int64_t num
     if (int rc = take_pending_fault()) return rc;  // a kernel of an earlier call gave up: say so
     if (int rc = check_dipole_order(order)) return rc;
     if (int rc = validate_virial_far(N, batch_size, num_columns)) return rc;
-    if (N * N * N * num_columns >= (int64_t(1) << 31)) {
-        set_error("Input mismatch: N^3 num_columns < 2^31 is required");
-        return NFFT_HIP_EINVAL;
-    }
+    if (int rc = check_spectral_elements(N, num_columns)) return rc;
     if (int rc = validate_box_inverse(box_inverse)) return rc;
     if (num_columns == 0) return 0;
     if (!band || !coeffs || !out) { set_error("Input mismatch: null input"); return NFFT_HIP_EINVAL; }

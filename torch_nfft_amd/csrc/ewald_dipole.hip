@@ -18,7 +18,7 @@
 //
 // The spectral step turns the adjoint transform of the packed sources, band [B, N, N, N, 4, C], into the 4 or 10 spectra
 // whose forward transform is the far part of (phi, E, T): one read and one write of every frequency.
-#include "pair_frame.h"
+#include "spectral_frame.h"
 
 namespace nfft {
 
@@ -122,43 +122,30 @@ int launch_pairs(const EwaldPairParams &q, int64_t cells, int64_t slots, int64_t
 
 // ---- the spectral step ------------------------------------------------------------------------------------------------
 
-constexpr int kSpectralBlock = 256;
-
-struct DipoleSpectralParams {
-    unsigned N, C, count;                // frequencies per axis; columns; N^3 C
-    float t00, t10, t11, t20, t21, t22;  // 2 pi times the lower triangle of A^-1
-};
-
-// One thread per (frequency, column) of the point set blockIdx.y: rho = band_q + 2 pi i kappa . band_mu (the transforms' sign
-// convention: the adjoint sums e^(+2 pi i k.s), EwaldSplitting.field_coeffs), R = b_k rho, and with tau = 2 pi kappa
+// One thread per (frequency, column) of the point set blockIdx.y (spectral_element of spectral_frame.h): rho = band_q +
+// 2 pi i kappa . band_mu (the transforms' sign convention: the adjoint sums e^(+2 pi i k.s), EwaldSplitting.field_coeffs),
+// R = b_k rho, and with tau = 2 pi kappa
 //     out[0] = R,   out[1 + a] = i tau_a R,   out[4 + e] = tau_a tau_b R  (e: xx, yy, zz, yz, xz, xy).
 template <int ORDER>
-__global__ void __launch_bounds__(kSpectralBlock) ewald_dipole_spectral_kernel(DipoleSpectralParams q, const float2 *__restrict__ band,
+__global__ void __launch_bounds__(kSpectralBlock) ewald_dipole_spectral_kernel(SpectralElementParams q, const float2 *__restrict__ band,
                                                                                 const float *__restrict__ coeffs,
                                                                                 float2 *__restrict__ out)
 {
     constexpr int SUMS = ORDER == 2 ? 10 : 4;
-    const unsigned e = blockIdx.x * kSpectralBlock + threadIdx.x;
-    if (e >= q.count) return;
-    const unsigned N = q.N, C = q.C;
-    const unsigned k = e / C, c = e - k * C;
-    const unsigned i2 = k % N, i01 = k / N, i1 = i01 % N, i0 = i01 / N;
-    const int half = (int)(N / 2);
-    const float k0 = (float)((int)i0 - half), k1 = (float)((int)i1 - half), k2 = (float)((int)i2 - half);
-    const float bk = coeffs[k];
-    const float tx = q.t00 * k0;
-    const float ty = fmaf(q.t11, k1, q.t10 * k0);
-    const float tz = fmaf(q.t22, k2, fmaf(q.t21, k1, q.t20 * k0));
-    const int64_t cell = (int64_t)blockIdx.y * (q.count / C) + k;  // (with the point set)
-    const float2 *bp = band + cell * 4 * C + c;
+    SpectralElement el;
+    if (!spectral_element(q, el)) return;
+    const unsigned C = q.C, c = el.c;
+    const float bk = coeffs[el.k];
+    const float tx = el.tau.x, ty = el.tau.y, tz = el.tau.z;
+    const float2 *bp = band + el.cell * 4 * C + c;
     const float2 vq = bp[0], vx = bp[C], vy = bp[2 * C], vz = bp[3 * C];
     const float mre = fmaf(tz, vz.x, fmaf(ty, vy.x, tx * vx.x)), mim = fmaf(tz, vz.y, fmaf(ty, vy.y, tx * vx.y));
     const float2 R = make_float2(bk * (vq.x - mim), bk * (vq.y + mre));
-    float2 *op = out + cell * SUMS * C + c;
+    float2 *op = out + el.cell * SUMS * C + c;
     op[0] = R;
-    op[C] = make_float2(-tx * R.y, tx * R.x);
-    op[2 * C] = make_float2(-ty * R.y, ty * R.x);
-    op[3 * C] = make_float2(-tz * R.y, tz * R.x);
+    op[C] = times_i(tx, R);
+    op[2 * C] = times_i(ty, R);
+    op[3 * C] = times_i(tz, R);
     if constexpr (ORDER == 2) {
         const float w[6] = {tx * tx, ty * ty, tz * tz, ty * tz, tx * tz, tx * ty};
 #pragma unroll
@@ -189,24 +176,8 @@ int launch_ewald_dipole_near_box(const nfft_hip_ewald_box_problem *p, int order,
 int launch_ewald_dipole_spectral(int64_t N, int64_t batch_size, int64_t num_columns, int order, const void *band,
                                  const float *coeffs, const double *box_inverse, void *out, hipStream_t stream)
 {
-    const double two_pi = 6.28318530717958647692;
-    DipoleSpectralParams q;
-    q.N = (unsigned)N;
-    q.C = (unsigned)num_columns;
-    q.count = (unsigned)(N * N * N * num_columns);  // (< 2^31: the entry point's check)
-    q.t00 = (float)(two_pi * box_inverse[0]);
-    q.t10 = (float)(two_pi * box_inverse[1]);
-    q.t11 = (float)(two_pi * box_inverse[2]);
-    q.t20 = (float)(two_pi * box_inverse[3]);
-    q.t21 = (float)(two_pi * box_inverse[4]);
-    q.t22 = (float)(two_pi * box_inverse[5]);
-    const dim3 grid((q.count + kSpectralBlock - 1) / kSpectralBlock, (unsigned)batch_size), block(kSpectralBlock);
-    if (order == 2)
-        hipLaunchKernelGGL(ewald_dipole_spectral_kernel<2>, grid, block, 0, stream, q, (const float2 *)band, coeffs, (float2 *)out);
-    else
-        hipLaunchKernelGGL(ewald_dipole_spectral_kernel<1>, grid, block, 0, stream, q, (const float2 *)band, coeffs, (float2 *)out);
-    NFFT_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_spectral_elements(order == 2 ? ewald_dipole_spectral_kernel<2> : ewald_dipole_spectral_kernel<1>, N, batch_size,
+                                    num_columns, band, coeffs, box_inverse, out, stream);
 }
 
 }  // namespace nfft

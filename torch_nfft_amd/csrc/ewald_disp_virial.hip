@@ -12,229 +12,41 @@
 // t_k = (d b_k / d |kappa|) / |kappa| <= 0 read from a grid of its own that the host side evaluated in float64 (its two
 // terms cancel at large |kappa|; finite at k = 0, where it multiplies kappa kappa = 0).  The k = 0 term of b_k is kept.
 //
-// ewald_disp_virial_near_kernel  ewald_virial_near_kernel with the dispersion pair weights: the frame of pair_frame.h, box
-//                                form, seven float32 sums per column, then x_i / 2 of the lane's own target in float64 and
-//                                the workgroup's sum.  One partial [7, Cr] float64 per item slot.
-// ewald_disp_virial_far_kernel   ewald_virial_far_kernel with one more 4-byte load per cell (t_k) in place of its closed
-//                                form.  One partial [7, C] per workgroup.  Cells with b_k = 0 are skipped.
-// The second level, the workspaces and their layout are those of ewald_virial.hip (launch_virial_sum).
-//
-// No atomics anywhere and every order of addition is fixed by the launch geometry: two calls give the same bits.
-#include "pair_frame.h"
+// Both reductions are the frames' (DESIGN.md section 7w), and nothing but the policies is left here:
+// virial_near_kernel<CC, DispersionVirialWeight>  of virial_frame.h (until 7w: ewald_disp_virial_near_kernel<CC>).
+// virial_far_kernel<CC, TableStrain>              of spectral_frame.h: one more 4-byte load per cell (t_k) in place of the
+//                                                 Coulomb sum's closed form (until 7w: ewald_disp_virial_far_kernel<CC>).
+// The second level, the workspaces and their layout are those of ewald_virial.hip.
+#include "spectral_frame.h"
 
 namespace nfft {
 
 namespace {
 
-constexpr int kVirialTerms = 7;    // energy, xx, yy, zz, yz, xz, xy
-constexpr int kVirialBlock = 256;  // lanes of the far kernel (and of the second level in ewald_virial.hip)
-
-template <int CC>
-__global__ void __launch_bounds__(kNearBlock) ewald_disp_virial_near_kernel(EwaldPairParams q, const int2 *__restrict__ items,
-                                                                            const float *__restrict__ pos,
-                                                                            const float *__restrict__ xr,
-                                                                            const int *__restrict__ start,
-                                                                            double *__restrict__ partial)
-{
-    __shared__ float4 s_pos[kNearTile];
-    __shared__ __attribute__((aligned(16))) float s_x[kNearTile * CC];
-    __shared__ double s_red[kNearBlock / 64][kVirialTerms * CC];
-    const int2 item = items[blockIdx.x];
-    if (item.x < 0) return;  // (uniform: an empty slot; the second level skips it)
-    const PairLane lane = pair_lane(item, start);
-    const WrappedWalk walk(lane.cell, q.G0, q.G1, q.G2);
-    // (a lane without a target sums pairs of the origin; its sums are replaced by zero before the reduction)
-    const float4 t = lane_position(lane, pos, 3, 0.f);
-    for (int64_t col0 = 0; col0 < q.Cr; col0 += CC) {
-        float acc[kVirialTerms][CC];
-#pragma unroll
-        for (int e = 0; e < kVirialTerms; ++e)
-#pragma unroll
-            for (int c = 0; c < CC; ++c) acc[e][c] = 0.f;
-        const StageColumns<CC> stage = {s_x, xr, q.Cr, col0};
-        walk(start, [&](int first, int last) {
-            sweep_range<2>(first, last, lane, s_pos, pos, 3, stage, [&](int j) {
-                const PairSep d = ewald_image<true>(t, s_pos[j], q);
-                if (!(d.rr > 0.f && d.rr < q.rc2)) return;
-                const DispersionPairWeight e(d.rr, q);
-                const float w = e.w, mg = e.mg();
-                const float gx = mg * d.dx, gy = mg * d.dy, gz = mg * d.dz;
-                const float pxx = gx * d.dx, pyy = gy * d.dy, pzz = gz * d.dz;
-                const float pyz = gy * d.dz, pxz = gx * d.dz, pxy = gx * d.dy;
-#pragma unroll
-                for (int c = 0; c < CC; ++c) {
-                    const float v = s_x[j * CC + c];
-                    acc[0][c] += w * v;
-                    acc[1][c] += pxx * v;
-                    acc[2][c] += pyy * v;
-                    acc[3][c] += pzz * v;
-                    acc[4][c] += pyz * v;
-                    acc[5][c] += pxz * v;
-                    acc[6][c] += pxy * v;
-                }
-            });
-        });
-        // x_i / 2 of the lane's own target, float64 from here on; a lane without a target adds exactly zero
-        double red[kVirialTerms * CC];
-#pragma unroll
-        for (int c = 0; c < CC; ++c) {
-            const bool live = lane.active && col0 + c < q.Cr;
-            const double h = live ? 0.5 * (double)xr[(int64_t)lane.ti * q.Cr + col0 + c] : 0.0;
-#pragma unroll
-            for (int e = 0; e < kVirialTerms; ++e) red[e * CC + c] = live ? h * (double)acc[e][c] : 0.0;
-        }
-        const double v = block_sum_f64(red, s_red);
-        const int tid = threadIdx.x;
-        if (tid < kVirialTerms * CC) {
-            const int e = tid / CC, c = tid % CC;
-            if (col0 + c < q.Cr) partial[((int64_t)blockIdx.x * kVirialTerms + e) * q.Cr + col0 + c] = v;
-        }
+// the pair weight of the dispersion sum (virial_frame.h has what a weight is): DispersionPairWeight, no block of its own
+struct DispersionVirialWeight {
+    struct Params {};
+    static __device__ __forceinline__ void weights(float rr, const EwaldPairParams &q, const Params &, float &w, float &mg)
+    {
+        const DispersionPairWeight e(rr, q);
+        w = e.w;
+        mg = e.mg();
     }
-}
-
-struct DispVirialFarParams {
-    int N, blocks;  // frequencies per axis; workgroups per point set
-    int wide;       // band is 16-byte aligned: a cell of two or four columns is read with 16-byte loads
-    int64_t C;
-    double i00, i10, i11, i20, i21, i22;  // the lower triangle of A^-1
 };
-
-template <int CC>
-__global__ void __launch_bounds__(kVirialBlock) ewald_disp_virial_far_kernel(DispVirialFarParams q,
-                                                                             const float2 *__restrict__ band,
-                                                                             const float *__restrict__ coeffs,
-                                                                             const float *__restrict__ strain,
-                                                                             double *__restrict__ partial)
-{
-    __shared__ double s_red[kVirialBlock / 64][kVirialTerms * CC];
-    const int tid = threadIdx.x;
-    const int N = q.N, half = q.N / 2;
-    const int64_t cells = (int64_t)N * N * N;
-    const int set = blockIdx.x / q.blocks, blk = blockIdx.x % q.blocks;  // (point set, workgroup within it)
-    const float2 *bb = band + (int64_t)set * cells * q.C;
-    for (int64_t col0 = 0; col0 < q.C; col0 += CC) {
-        double acc[kVirialTerms * CC];
-#pragma unroll
-        for (int n = 0; n < kVirialTerms * CC; ++n) acc[n] = 0.0;
-        // the cells blk * 256 + tid, + stride, + 2 stride, ...: their index (i0, i1, i2) is kept beside them and advanced
-        // by the stride's own digits with carries, so that no division runs per cell
-        const int stride = q.blocks * kVirialBlock;
-        const unsigned first = (unsigned)blk * kVirialBlock + tid;
-        int i2 = (int)(first % (unsigned)N), i1 = (int)((first / (unsigned)N) % (unsigned)N), i0 = (int)(first / ((unsigned)N * N));
-        const int s2 = stride % N, s1 = (stride / N) % N, s0 = stride / (N * N);
-        for (int64_t cell = first; cell < cells; cell += stride) {
-            const float bk = coeffs[cell];
-            const int k0 = i0 - half, k1 = i1 - half, k2 = i2 - half;
-            i2 += s2;
-            if (i2 >= N) {
-                i2 -= N;
-                ++i1;
-            }
-            i1 += s1;
-            if (i1 >= N) {
-                i1 -= N;
-                ++i0;
-            }
-            i0 += s0;
-            if (bk == 0.f) continue;  // the zeroed planes k_a = -N/2 (and coefficients below float32); k = 0 stays
-            // kappa = A^-1 k, A^-1 lower triangular
-            const double kx = q.i00 * k0;
-            const double ky = q.i10 * k0 + q.i11 * k1;
-            const double kz = q.i20 * k0 + q.i21 * k1 + q.i22 * k2;
-            const double b = (double)bk;
-            const double t = (double)strain[cell];
-            double wgt[kVirialTerms];
-            wgt[0] = b;
-            wgt[1] = b + t * kx * kx;
-            wgt[2] = b + t * ky * ky;
-            wgt[3] = b + t * kz * kz;
-            wgt[4] = t * ky * kz;
-            wgt[5] = t * kx * kz;
-            wgt[6] = t * kx * ky;
-            float2 v[CC];
-            const float2 *bp = bb + cell * q.C + col0;
-            bool loaded = false;
-            if constexpr (CC == 2) {
-                if (q.C == 2 && q.wide) {  // (16 bytes per cell, aligned: one load)
-                    const float4 u = *reinterpret_cast<const float4 *>(bp);
-                    v[0] = make_float2(u.x, u.y);
-                    v[1] = make_float2(u.z, u.w);
-                    loaded = true;
-                }
-            }
-            if constexpr (CC == 4) {
-                if (q.C == 4 && q.wide) {  // (32 bytes per cell, aligned: two loads)
-                    const float4 u0 = reinterpret_cast<const float4 *>(bp)[0], u1 = reinterpret_cast<const float4 *>(bp)[1];
-                    v[0] = make_float2(u0.x, u0.y);
-                    v[1] = make_float2(u0.z, u0.w);
-                    v[2] = make_float2(u1.x, u1.y);
-                    v[3] = make_float2(u1.z, u1.w);
-                    loaded = true;
-                }
-            }
-            if (!loaded) {
-#pragma unroll
-                for (int c = 0; c < CC; ++c) v[c] = col0 + c < q.C ? bp[c] : make_float2(0.f, 0.f);
-            }
-#pragma unroll
-            for (int c = 0; c < CC; ++c) {
-                const double p = (double)v[c].x * (double)v[c].x + (double)v[c].y * (double)v[c].y;
-#pragma unroll
-                for (int e = 0; e < kVirialTerms; ++e) acc[e * CC + c] += wgt[e] * p;
-            }
-        }
-        const double v = block_sum_f64(acc, s_red);
-        if (tid < kVirialTerms * CC) {
-            const int e = tid / CC, c = tid % CC;
-            if (col0 + c < q.C) partial[((int64_t)blockIdx.x * kVirialTerms + e) * q.C + col0 + c] = 0.5 * v;
-        }
-    }
-}
 
 }  // namespace
 
 int launch_ewald_dispersion_virial_near(const nfft_hip_ewald_box_problem *p, const float *pos, const float *xr, const int *start,
                                         double *out, void *workspace, hipStream_t stream)
 {
-    const EwaldPairParams q = ewald_pair_params(p->cells[0], p->cells[1], p->cells[2], p->num_columns, p->alpha, p->r_cut, p->box);
-    const int64_t cells = p->batch_size * p->cells[0] * p->cells[1] * p->cells[2];
-    const int64_t slots = ewald_virial_near_item_slots(p);
-    int2 *items = (int2 *)workspace;
-    double *partial = ewald_virial_near_partials(p, workspace);
-    if (int rc = launch_nearfield_items(cells, p->num_points, start, items, stream)) return rc;
-    const dim3 grid((unsigned)slots), block(kNearBlock);
-    dispatch_columns(q.Cr, [&](auto CC) {
-        hipLaunchKernelGGL((ewald_disp_virial_near_kernel<CC()>), grid, block, 0, stream, q, (const int2 *)items, pos, xr, start,
-                           partial);
-    });
-    NFFT_HIP_CHECK(hipGetLastError());
-    return launch_virial_sum(partial, p->batch_size, q.Cr, 0, items, start, (int)(p->cells[0] * p->cells[1] * p->cells[2]), out,
-                             stream);
+    return launch_virial_near<DispersionVirialWeight>(p, {}, pos, xr, start, out, workspace, stream);
 }
 
 int launch_ewald_dispersion_virial_far(int64_t N, int64_t batch_size, int64_t num_columns, const void *band, const float *coeffs,
                                        const float *strain_coeffs, const double *box_inverse, double *out, void *workspace,
                                        hipStream_t stream)
 {
-    DispVirialFarParams q;
-    q.N = (int)N;
-    q.blocks = ewald_virial_far_blocks(N);
-    q.C = num_columns;
-    q.wide = ((uintptr_t)band & 15) == 0 ? 1 : 0;  // (otherwise 8-byte loads, which complex64 data always allows)
-    q.i00 = box_inverse[0];
-    q.i10 = box_inverse[1];
-    q.i11 = box_inverse[2];
-    q.i20 = box_inverse[3];
-    q.i21 = box_inverse[4];
-    q.i22 = box_inverse[5];
-    double *partial = (double *)workspace;
-    const dim3 grid((unsigned)(q.blocks * batch_size)), block(kVirialBlock);
-    dispatch_columns(q.C, [&](auto CC) {
-        hipLaunchKernelGGL((ewald_disp_virial_far_kernel<CC()>), grid, block, 0, stream, q, (const float2 *)band, coeffs,
-                           strain_coeffs, partial);
-    });
-    NFFT_HIP_CHECK(hipGetLastError());
-    return launch_virial_sum(partial, batch_size, q.C, q.blocks, nullptr, nullptr, 0, out, stream);
+    return launch_virial_far(N, batch_size, num_columns, band, coeffs, box_inverse, TableStrain{strain_coeffs}, out, workspace, stream);
 }
 
 }  // namespace nfft

@@ -13,9 +13,9 @@
 // the streamed point's caller-order index, as integer bits, in the pad's place.  From the reciprocal that the dispersion
 // weight forms, p = (a_i r^-6) (a_j r^-6) = a_i a_j / r^12 and the slope is 12 p / r^2; s^L scales a_j.
 //
-// lj_step_spectral_kernel  ewald_step_spectral_kernel's thread-to-cell mapping and carried index digits on band [B, N, N, N, 2]
-//                          = the adjoint transform of (q, c): writes the six spectra i tau_a b^C S^q and i tau_a b^D S^c
-//                          (zeros where the table is zero) and sums, in float64, 1/2 b^C |S^q|^2, -1/2 b^D |S^c|^2 and the
+// lj_step_spectral_kernel  written from the pieces of spectral_frame.h: ewald_step_spectral_kernel's
+//                          sweep, load and tau on band [B, N, N, N, 2] = the adjoint transform of (q, c): writes the six
+//                          spectra i tau_a b^C S^q and i tau_a b^D S^c (zeros where the table is zero) and sums, in float64, 1/2 b^C |S^q|^2, -1/2 b^D |S^c|^2 and the
 //                          six virial terms -- the Coulomb weights of section 7i minus the dispersion weights of section 7k.
 //                          One partial [8] per workgroup.
 //
@@ -25,6 +25,7 @@
 //
 // The second level of both is launch_virial_sum_terms of ewald_virial.hip with eight terms.  No atomics anywhere and every
 // order of addition is fixed by the launch geometry: two calls give the same bits.
+#include "spectral_frame.h"
 #include "step_frame.h"
 
 namespace nfft {
@@ -32,7 +33,6 @@ namespace nfft {
 namespace {
 
 constexpr int kLjTerms = kStepTerms;
-constexpr int kVirialBlock = 256;  // lanes of the spectral kernel (and of the second level in ewald_virial.hip)
 
 // staging policy: (q_j, c_j, a_j) of xs [n, 3] and the caller-order index of the streamed point as integer bits
 struct StageLjIndexed {
@@ -75,76 +75,39 @@ struct LjProductLaw {
     __device__ __forceinline__ Coef coef(Own ai, const float4 &v) const { return {ai, v.z}; }
 };
 
-struct LjSpectralParams {
-    int N, blocks;  // frequencies per axis; workgroups per point set
-    int wide;       // band and spectra are 16-byte aligned: a cell moves as one 16-byte load and three 16-byte stores
-    double i00, i10, i11, i20, i21, i22;  // the lower triangle of A^-1
-    double p2a2;                          // pi^2 / alpha_C^2
-    float t00, t10, t11, t20, t21, t22;   // 2 pi times the lower triangle of A^-1
-};
-
-// (x + i y) times the imaginary i t
-__device__ __forceinline__ float2 times_i(float t, float2 r) { return make_float2(-t * r.y, t * r.x); }
-
-__global__ void __launch_bounds__(kVirialBlock) lj_step_spectral_kernel(LjSpectralParams q, const float2 *__restrict__ band,
+__global__ void __launch_bounds__(kVirialBlock) lj_step_spectral_kernel(SpectralHead h, BoxInverse inv, CoulombStrain strain_c,
+                                                                        TwoPiInverse tpi, const float2 *__restrict__ band,
                                                                         const float *__restrict__ coeffs_c,
                                                                         const float *__restrict__ coeffs_d,
                                                                         const float *__restrict__ strain_d,
                                                                         float2 *__restrict__ spectra, double *__restrict__ partial)
 {
     __shared__ double s_red[kVirialBlock / 64][kLjTerms];
-    const int tid = threadIdx.x;
-    const int N = q.N, half = q.N / 2;
-    const int64_t cells = (int64_t)N * N * N;
-    const int set = blockIdx.x / q.blocks, blk = blockIdx.x % q.blocks;  // (point set, workgroup within it)
+    const int64_t cells = (int64_t)h.N * h.N * h.N;
+    const int set = blockIdx.x / h.blocks;  // (the workgroup's point set)
     const float2 *bb = band + (int64_t)set * cells * 2;
     float2 *ss = spectra + (int64_t)set * cells * 6;
     double acc[kLjTerms];
 #pragma unroll
     for (int n = 0; n < kLjTerms; ++n) acc[n] = 0.0;
-    // the cells blk * 256 + tid, + stride, + 2 stride, ...: their index (i0, i1, i2) is kept beside them and advanced
-    // by the stride's own digits with carries, so that no division runs per cell
-    const int stride = q.blocks * kVirialBlock;
-    const unsigned first = (unsigned)blk * kVirialBlock + tid;
-    int i2 = (int)(first % (unsigned)N), i1 = (int)((first / (unsigned)N) % (unsigned)N), i0 = (int)(first / ((unsigned)N * N));
-    const int s2 = stride % N, s1 = (stride / N) % N, s0 = stride / (N * N);
-    for (int64_t cell = first; cell < cells; cell += stride) {
+    for (CellSweep sweep(h.N, h.blocks); sweep.more(); sweep.advance()) {
+        const int64_t cell = sweep.cell;
         const float bc = coeffs_c[cell], bd = coeffs_d[cell];
-        const int k0 = i0 - half, k1 = i1 - half, k2 = i2 - half;
-        i2 += s2;
-        if (i2 >= N) {
-            i2 -= N;
-            ++i1;
-        }
-        i1 += s1;
-        if (i1 >= N) {
-            i1 -= N;
-            ++i0;
-        }
-        i0 += s0;
-        const float2 *bp = bb + cell * 2;
+        int k0, k1, k2;
+        sweep.frequency(k0, k1, k2);
         float2 *sp = ss + cell * 6;
-        float2 sq, sc;  // S^q_k, S^c_k
-        if (q.wide) {   // (16 bytes per cell, aligned: one load)
-            const float4 u = *reinterpret_cast<const float4 *>(bp);
-            sq = make_float2(u.x, u.y);
-            sc = make_float2(u.z, u.w);
-        } else {
-            sq = bp[0];
-            sc = bp[1];
-        }
+        float2 s[2];  // S^q_k, S^c_k (16 bytes per cell: one load where aligned)
+        load_cell<2>(bb + cell * 2, 2, 0, h.wide, s);
+        const float2 sq = s[0], sc = s[1];
         // the six spectra: i tau_a R with R = b_k S_k and tau = 2 pi kappa in float32.  A zero in a table (k = 0 for the
         // Coulomb one, the zeroed planes k_a = -N/2 for both) gives zeros, whatever band holds there
-        const float kf0 = (float)k0, kf1 = (float)k1, kf2 = (float)k2;
-        const float tx = q.t00 * kf0;
-        const float ty = fmaf(q.t11, kf1, q.t10 * kf0);
-        const float tz = fmaf(q.t22, kf2, fmaf(q.t21, kf1, q.t20 * kf0));
+        const float3 tau = tpi.tau((float)k0, (float)k1, (float)k2);
         const float2 zero = make_float2(0.f, 0.f);
         const float2 Rq = bc == 0.f ? zero : make_float2(bc * sq.x, bc * sq.y);
         const float2 Rc = bd == 0.f ? zero : make_float2(bd * sc.x, bd * sc.y);
-        const float2 o0 = times_i(tx, Rq), o1 = times_i(ty, Rq), o2 = times_i(tz, Rq);
-        const float2 o3 = times_i(tx, Rc), o4 = times_i(ty, Rc), o5 = times_i(tz, Rc);
-        if (q.wide) {  // (48 bytes per cell, aligned: three stores)
+        const float2 o0 = times_i(tau.x, Rq), o1 = times_i(tau.y, Rq), o2 = times_i(tau.z, Rq);
+        const float2 o3 = times_i(tau.x, Rc), o4 = times_i(tau.y, Rc), o5 = times_i(tau.z, Rc);
+        if (h.wide) {  // (48 bytes per cell, aligned: three stores)
             float4 *sp4 = reinterpret_cast<float4 *>(sp);
             sp4[0] = make_float4(o0.x, o0.y, o1.x, o1.y);
             sp4[1] = make_float4(o2.x, o2.y, o3.x, o3.y);
@@ -158,14 +121,13 @@ __global__ void __launch_bounds__(kVirialBlock) lj_step_spectral_kernel(LjSpectr
             sp[5] = o5;
         }
         if (bc == 0.f && bd == 0.f) continue;
-        // kappa = A^-1 k, A^-1 lower triangular
-        const double kx = q.i00 * k0;
-        const double ky = q.i10 * k0 + q.i11 * k1;
-        const double kz = q.i20 * k0 + q.i21 * k1 + q.i22 * k2;
+        // (the seven weights of strain_weights, each multiplied in where it is formed: kept in an array of their own first,
+        // as the other reductions have them, they cost this kernel two VGPRs)
+        const double3 kap = inv.kappa(k0, k1, k2);
+        const double kx = kap.x, ky = kap.y, kz = kap.z;
         if (bc != 0.f) {  // (not k = 0: kappa^2 > 0)
-            const double kk = kx * kx + ky * ky + kz * kz;
             const double b = (double)bc;
-            const double t = -2.0 * (1.0 / kk + q.p2a2) * b;
+            const double t = strain_c(cell, b, kx, ky, kz);
             const double p = (double)sq.x * (double)sq.x + (double)sq.y * (double)sq.y;
             acc[0] += b * p;
             acc[2] += (b + t * kx * kx) * p;
@@ -188,8 +150,7 @@ __global__ void __launch_bounds__(kVirialBlock) lj_step_spectral_kernel(LjSpectr
             acc[7] -= (t * kx * ky) * p;
         }
     }
-    const double v = block_sum_f64(acc, s_red);
-    if (tid < kLjTerms) partial[(int64_t)blockIdx.x * kLjTerms + tid] = 0.5 * v;
+    block_sums_to_partial<kLjTerms, 1>(acc, s_red, 0.5, 1, 0, partial);
 }
 
 }  // namespace
@@ -221,29 +182,14 @@ int launch_ewald_lj_step_spectral(int64_t N, int64_t batch_size, const void *ban
                                   const float *coeffs_dispersion, const float *strain_dispersion, const double *box_inverse,
                                   double pi2_over_alpha2, void *spectra, double *out, void *workspace, hipStream_t stream)
 {
-    const double two_pi = 6.28318530717958647692;
-    LjSpectralParams q;
-    q.N = (int)N;
-    q.blocks = ewald_virial_far_blocks(N);
-    q.wide = (((uintptr_t)band | (uintptr_t)spectra) & 15) == 0 ? 1 : 0;  // (otherwise 8-byte pieces, which complex64 allows)
-    q.i00 = box_inverse[0];
-    q.i10 = box_inverse[1];
-    q.i11 = box_inverse[2];
-    q.i20 = box_inverse[3];
-    q.i21 = box_inverse[4];
-    q.i22 = box_inverse[5];
-    q.p2a2 = pi2_over_alpha2;
-    q.t00 = (float)(two_pi * box_inverse[0]);
-    q.t10 = (float)(two_pi * box_inverse[1]);
-    q.t11 = (float)(two_pi * box_inverse[2]);
-    q.t20 = (float)(two_pi * box_inverse[3]);
-    q.t21 = (float)(two_pi * box_inverse[4]);
-    q.t22 = (float)(two_pi * box_inverse[5]);
-    double *partial = (double *)workspace;
-    hipLaunchKernelGGL(lj_step_spectral_kernel, dim3((unsigned)(q.blocks * batch_size)), dim3(kVirialBlock), 0, stream, q,
-                       (const float2 *)band, coeffs_coulomb, coeffs_dispersion, strain_dispersion, (float2 *)spectra, partial);
-    NFFT_HIP_CHECK(hipGetLastError());
-    return launch_virial_sum_terms(partial, kLjTerms, batch_size, 1, q.blocks, nullptr, nullptr, 0, out, stream);
+    // (one column of eight sums)
+    return launch_spectral_reduction(
+        N, batch_size, 1, (uintptr_t)band | (uintptr_t)spectra, kLjTerms, out, workspace, stream,
+        [&](dim3 grid, const SpectralHead &h, double *partial) {
+            hipLaunchKernelGGL(lj_step_spectral_kernel, grid, dim3(kVirialBlock), 0, stream, h, BoxInverse(box_inverse),
+                               CoulombStrain{pi2_over_alpha2}, TwoPiInverse(box_inverse), (const float2 *)band, coeffs_coulomb,
+                               coeffs_dispersion, strain_dispersion, (float2 *)spectra, partial);
+        });
 }
 
 }  // namespace nfft

@@ -18,7 +18,7 @@
 // The spectral step turns the adjoint transform of the forces, band [B, N, N, N, 3, C], into the 3 or 12 spectra whose
 // forward transform is the far part of (u, G): the projection onto the plane across the wave vector, one read and one
 // write of every frequency.
-#include "pair_frame.h"
+#include "spectral_frame.h"
 
 namespace nfft {
 
@@ -126,45 +126,31 @@ int launch_pairs(const EwaldPairParams &q, int64_t cells, int64_t slots, int64_t
 
 // ---- the spectral step ------------------------------------------------------------------------------------------------
 
-constexpr int kSpectralBlock = 256;
-
-struct StokesletSpectralParams {
-    unsigned N, C, count;                // frequencies per axis; columns; N^3 C
-    float t00, t10, t11, t20, t21, t22;  // 2 pi times the lower triangle of A^-1
-};
-
-// One thread per (frequency, column) of the point set blockIdx.y.  With tau = 2 pi kappa and rho the three rows of band,
+// One thread per (frequency, column) of the point set blockIdx.y (spectral_element of spectral_frame.h).  With
+// tau = 2 pi kappa and rho the three rows of band,
 //     U = c_k (rho - tau (tau . rho) / |tau|^2)          (the quotient is 0 where |tau|^2 = 0)
 //     out[a] = U_a,   out[3 + 3 a + b] = -i tau_b U_a
 // in the transforms' sign convention: the adjoint sums e^(+2 pi i k.s) and the forward e^(-2 pi i k.s), whose derivative
 // along x_b is the factor -i tau_b (EwaldSplitting.field_coeffs carries the same flip for E = -grad phi).
 template <int ORDER>
-__global__ void __launch_bounds__(kSpectralBlock) ewald_stokeslet_spectral_kernel(StokesletSpectralParams q,
+__global__ void __launch_bounds__(kSpectralBlock) ewald_stokeslet_spectral_kernel(SpectralElementParams q,
                                                                                    const float2 *__restrict__ band,
                                                                                    const float *__restrict__ coeffs,
                                                                                    float2 *__restrict__ out)
 {
     constexpr int SUMS = ORDER == 2 ? 12 : 3;
-    const unsigned e = blockIdx.x * kSpectralBlock + threadIdx.x;
-    if (e >= q.count) return;
-    const unsigned N = q.N, C = q.C;
-    const unsigned k = e / C, c = e - k * C;
-    const unsigned i2 = k % N, i01 = k / N, i1 = i01 % N, i0 = i01 / N;
-    const int half = (int)(N / 2);
-    const float k0 = (float)((int)i0 - half), k1 = (float)((int)i1 - half), k2 = (float)((int)i2 - half);
-    const float ck = coeffs[k];
-    float tau[3];
-    tau[0] = q.t00 * k0;
-    tau[1] = fmaf(q.t11, k1, q.t10 * k0);
-    tau[2] = fmaf(q.t22, k2, fmaf(q.t21, k1, q.t20 * k0));
+    SpectralElement el;
+    if (!spectral_element(q, el)) return;
+    const unsigned C = q.C, c = el.c;
+    const float ck = coeffs[el.k];
+    const float tau[3] = {el.tau.x, el.tau.y, el.tau.z};
     const float t2 = fmaf(tau[2], tau[2], fmaf(tau[1], tau[1], tau[0] * tau[0]));
     const float it2 = t2 > 0.f ? 1.f / t2 : 0.f;
-    const int64_t cell = (int64_t)blockIdx.y * (q.count / C) + k;  // (with the point set)
-    const float2 *bp = band + cell * 3 * C + c;
+    const float2 *bp = band + el.cell * 3 * C + c;
     const float2 v[3] = {bp[0], bp[C], bp[2 * C]};
     const float pre = fmaf(tau[2], v[2].x, fmaf(tau[1], v[1].x, tau[0] * v[0].x)) * it2;
     const float pim = fmaf(tau[2], v[2].y, fmaf(tau[1], v[1].y, tau[0] * v[0].y)) * it2;
-    float2 *op = out + cell * SUMS * C + c;
+    float2 *op = out + el.cell * SUMS * C + c;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const float2 U = make_float2(ck * fmaf(-tau[a], pre, v[a].x), ck * fmaf(-tau[a], pim, v[a].y));
@@ -199,26 +185,8 @@ int launch_ewald_stokeslet_near_box(const nfft_hip_ewald_box_problem *p, int ord
 int launch_ewald_stokeslet_spectral(int64_t N, int64_t batch_size, int64_t num_columns, int order, const void *band,
                                     const float *coeffs, const double *box_inverse, void *out, hipStream_t stream)
 {
-    const double two_pi = 6.28318530717958647692;
-    StokesletSpectralParams q;
-    q.N = (unsigned)N;
-    q.C = (unsigned)num_columns;
-    q.count = (unsigned)(N * N * N * num_columns);  // (< 2^31: the entry point's check)
-    q.t00 = (float)(two_pi * box_inverse[0]);
-    q.t10 = (float)(two_pi * box_inverse[1]);
-    q.t11 = (float)(two_pi * box_inverse[2]);
-    q.t20 = (float)(two_pi * box_inverse[3]);
-    q.t21 = (float)(two_pi * box_inverse[4]);
-    q.t22 = (float)(two_pi * box_inverse[5]);
-    const dim3 grid((q.count + kSpectralBlock - 1) / kSpectralBlock, (unsigned)batch_size), block(kSpectralBlock);
-    if (order == 2)
-        hipLaunchKernelGGL(ewald_stokeslet_spectral_kernel<2>, grid, block, 0, stream, q, (const float2 *)band, coeffs,
-                           (float2 *)out);
-    else
-        hipLaunchKernelGGL(ewald_stokeslet_spectral_kernel<1>, grid, block, 0, stream, q, (const float2 *)band, coeffs,
-                           (float2 *)out);
-    NFFT_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_spectral_elements(order == 2 ? ewald_stokeslet_spectral_kernel<2> : ewald_stokeslet_spectral_kernel<1>, N,
+                                    batch_size, num_columns, band, coeffs, box_inverse, out, stream);
 }
 
 }  // namespace nfft

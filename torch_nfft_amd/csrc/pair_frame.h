@@ -1,5 +1,6 @@
 // The frame of the pair kernels: nearfield.hip (the open grid of the fast summation), ewald_near.hip,
-// ewald_disp.hip, ewald_dipole.hip, ewald_stokeslet.hip, ewald_yukawa.hip and the pair kernels of ewald_virial.hip, ewald_step.hip, ewald_lj_step.hip and ewald_disp_virial.hip (the wrapped grid of the Ewald sums) stand on all of it, nearfield_pgrad.hip on all
+// ewald_disp.hip, ewald_dipole.hip, ewald_stokeslet.hip, ewald_yukawa.hip, ewald_step.hip and the pair reductions and step
+// walks of virial_frame.h and step_frame.h (the wrapped grid of the Ewald sums) stand on all of it, nearfield_pgrad.hip on all
 // but the tile sweep, nearfield_grad.hip on the host dispatch only (section 7d says why).
 // Both point sets come ordered by (point set, cell) with a start table.  A workgroup owns one work item -- up to kNearBlock
 // output points of one cell -- and a lane one output point; a walk hands the contiguous ranges of streamed points of the

@@ -32,8 +32,7 @@
 //     Coef::terms(e, w6, slope, u)    the short-range slope -u'(r) / r and energy u from the two weights
 // -ffp-contract=on fuses within one expression only: a law's expressions live whole inside terms().
 #pragma once
-#include "host_util.h"
-#include "pair_frame.h"
+#include "virial_frame.h"
 
 namespace nfft {
 
@@ -213,13 +212,11 @@ __global__ void __launch_bounds__(kNearBlock) step_near_kernel(EwaldPairParams q
     red[1] = lane.active ? 0.5 * (double)acc[10] : 0.0;
 #pragma unroll
     for (int e = 0; e < 6; ++e) red[2 + e] = lane.active ? 0.5 * (double)acc[3 + e] : 0.0;
-    const double v = block_sum_f64(red, s_red);
-    const int tid = threadIdx.x;
-    if (tid < kStepTerms) partial[(int64_t)blockIdx.x * kStepTerms + tid] = v;
+    block_sums_to_partial<kStepTerms, 1>(red, s_red, 1.0, 1, 0, partial);
 }
 
-// The launch of a step walk: the work items, the walk (row_start == nullptr: no list, the unmasked instantiation) with
-// `lds` bytes of dynamic LDS, the second level.  `workspace`: ewald_step8_near_workspace(p) bytes, 256-byte aligned
+// The launch of a step walk: the launch sequence of virial_frame.h around the walk (row_start == nullptr: no list, the
+// unmasked instantiation) with `lds` bytes of dynamic LDS.  `workspace`: ewald_step8_near_workspace(p) bytes, 256-byte aligned
 template <class Law>
 int launch_step_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersion, const typename Law::Params &lp, size_t lds,
                      int64_t num_entries, const float *pos, const float *xs, const int *start, const int64_t *index,
@@ -229,17 +226,12 @@ int launch_step_near(const nfft_hip_ewald_box_problem *p, double alpha_dispersio
     const EwaldPairParams qc = ewald_pair_params(p->cells[0], p->cells[1], p->cells[2], Law::kValues, p->alpha, p->r_cut, p->box);
     const EwaldPairParams qd = ewald_pair_params(p->cells[0], p->cells[1], p->cells[2], Law::kValues, alpha_dispersion, p->r_cut, p->box);
     const ExclList ex = {row_start, col, weight_coulomb, weight_lj, (int)p->num_points, (int)num_entries};
-    const int64_t cells_per_set = (int64_t)p->cells[0] * p->cells[1] * p->cells[2];
-    const int64_t slots = ewald_virial_near_item_slots(p);
-    int2 *items = (int2 *)workspace;
-    double *partial = ewald_virial_near_partials(p, workspace);
-    if (int rc = launch_nearfield_items(p->batch_size * cells_per_set, p->num_points, start, items, stream)) return rc;
-    dispatch_flag(row_start != nullptr, [&](auto masked) {
-        hipLaunchKernelGGL((step_near_kernel<Law, decltype(masked)::value != 0>), dim3((unsigned)slots), dim3(kNearBlock), lds, stream, qc, qd,
-                           lp, ex, (const int2 *)items, pos, xs, start, index, f, partial);
+    return launch_pair_reduction(p, kStepTerms, 1, start, out, workspace, stream, [&](dim3 grid, const int2 *items, double *partial) {
+        dispatch_flag(row_start != nullptr, [&](auto masked) {
+            hipLaunchKernelGGL((step_near_kernel<Law, decltype(masked)::value != 0>), grid, dim3(kNearBlock), lds, stream, qc, qd, lp, ex,
+                               items, pos, xs, start, index, f, partial);
+        });
     });
-    NFFT_HIP_CHECK(hipGetLastError());
-    return launch_virial_sum_terms(partial, kStepTerms, p->batch_size, 1, 0, items, start, (int)cells_per_set, out, stream);
 }
 
 }  // namespace nfft
